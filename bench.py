@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the HRNet hot path (model call + decode, SimpleHRNet.py:281-308) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Metric (BASELINE.json): person-crops/sec, HRNet-W48 384x288, batch 256 per GPU, bf16 MFMA with fp32
 accumulate, synthetic crops already resident in HBM, random-init (seeded) weights.  One "step" = one pass
@@ -73,8 +73,37 @@ def parse():
                     help="DIAGNOSTIC (never the metric): all-zero weights, BN shifts and crops -- every MFMA operand is zero, so the part's "
                          "power budget is out of the picture; against the random run on the same box it tells a power-bound kernel (>= 15 %% faster) "
                          "from a stall-bound one (VERDICT r5 item 1a)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (the gathered joints, float32) as "
+                         "DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments compare output for output")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """``arrays``: name -> numpy array.  Written as float32 (float64 stays float64) to ``out_dir/<name>.npy``; an array that would
+    take the total past DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its leading-axis rows (sorted, so row order is kept)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    used, written = 0, {}
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        arr = arr if arr.dtype in (np.float32, np.float64) else arr.astype(np.float32)
+        room = DUMP_LIMIT_BYTES - used
+        if arr.nbytes > room and arr.ndim > 0:
+            keep = room // (arr.nbytes // arr.shape[0])
+            arr = arr[np.sort(np.random.default_rng(0).choice(arr.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr))
+        used += arr.nbytes
+        written[name] = list(arr.shape)
+    return written
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -801,6 +830,8 @@ def main():
     el = reduce_max(el)
     per_rank = gather_floats(a.batch * a.steps / el_mine)
     assert tuple(pts.shape) == (a.batch * world, 17, 3) and bool(torch.isfinite(pts).all())
+    # --dump-outputs: what the last timed step handed its caller -- the all-gathered (y, x, confidence) joints of every crop
+    dumped = dump_outputs(a.dump_outputs, {"pts": pts.cpu().numpy()}) if a.dump_outputs and rank == 0 else None
     # --check-gather: the gathered joints of ALL ranks against ONE engine run over every rank's crops on this rank's GPU (crops and
     # boxes are seeded per rank, so any rank can regenerate them): what the sharding + all-gather must not change
     gather_ok = None
@@ -842,6 +873,8 @@ def main():
             "whole_net_tflops": round(value / world * flops / 1e12, 2),
             "gflop_per_crop": round(flops / 1e9, 3),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
         if not a.no_roofline and a.model_name == "HRNet":
             # per-kernel HIP-event times of one internal pass, same stream as the launches
             nb = min(a.max_batch, a.batch)

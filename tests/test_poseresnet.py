@@ -1,8 +1,5 @@
-"""PoseResNet (models_/poseresnet.py): synth spec and oracle against the reference (build
-container / fixture), then the HIP engine against the fixture."""
-import os
-import sys
-
+"""PoseResNet (models_/poseresnet.py): synth spec and oracle against the reference's
+stored outputs (tests/golden), then the HIP engine against the fixture."""
 import numpy as np
 import pytest
 import torch
@@ -11,7 +8,6 @@ from conftest import golden, load_pkg
 from oracle import hrnet_torch_oracle as T
 
 NAME = "poseresnet50_128x96_n2"
-REF = "/root/reference"
 
 
 def _sd(pkg, size, seed):
@@ -29,19 +25,15 @@ def test_oracle_matches_reference_fixture():
     np.testing.assert_array_equal(T.decode_heatmaps(hm, g["boxes"])[..., :2], g["pts"][..., :2])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
 @pytest.mark.parametrize("size", [50, 101])
 def test_synth_spec_equals_reference_state_dict(size):
-    sys.path.insert(0, REF)
-    try:
-        from models_.poseresnet import PoseResNet
-    finally:
-        sys.path.remove(REF)
+    """key order and shapes of the reference's own ``PoseResNet(size, 17).state_dict()``, stored by
+    tests/golden/make_state_spec_golden.py"""
+    g = golden("reference_state_specs")
     pkg = load_pkg()
-    ref = PoseResNet(size, 17).state_dict()
     spec = pkg.synth.poseresnet_state_spec(size, 17)
-    assert [k for k, _, _ in spec] == list(ref.keys())
-    assert all(tuple(ref[k].shape) == tuple(shape) for k, shape, _ in spec)
+    assert [k for k, _, _ in spec] == list(g["PoseResNet_%d_keys" % size])
+    assert ["x".join(map(str, shape)) for _, shape, _ in spec] == list(g["PoseResNet_%d_shapes" % size])
 
 
 def test_plan_only_census_and_errors():

@@ -49,6 +49,9 @@ def test_constructor_errors_without_gpu():
 def test_device_strings_of_the_reference_map_to_one_gpu_per_process(monkeypatch):
     from importlib import import_module
     resolve = import_module("simple-hrnet_amd.simple_hrnet").resolve_device
+    # an 8-GPU node, whatever this box has: LOCAL_RANK=1 below must name a visible device (1-GPU boxes refuse it, test_round3.py)
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 8)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
     monkeypatch.delenv("LOCAL_RANK", raising=False)
     assert resolve("cuda:3") == torch.device("cuda", 3) and resolve(torch.device("cuda:2")) == torch.device("cuda", 2)
     assert resolve("cuda") == torch.device("cuda", 0) and resolve(None) == torch.device("cuda", 0)
