@@ -31,7 +31,9 @@ extern "C" {
 
 typedef struct hrn_ctx *hrn_handle;
 
-enum { HRN_F32 = 0, HRN_BF16 = 1 };            /* arithmetic / activation storage type       */
+enum { HRN_F32 = 0, HRN_BF16 = 1, HRN_F16 = 2 }; /* arithmetic / activation storage type: fp32,
+                                                  bf16 or fp16 storage (fp32 accumulation);
+                                                  HRN_F16 runs the bf16 plan and kernels  */
 enum { HRN_BOX_I32 = 0, HRN_BOX_F32 = 1 };     /* boxes dtype: SimpleHRNet.py:230 vs :223      */
 enum { HRN_T_F32 = 0, HRN_T_I64 = 1 };         /* hrn_tensor_desc.dtype                        */
 
@@ -80,7 +82,11 @@ void hrn_destroy(hrn_handle h);
 const char *hrn_last_error(hrn_handle h); /* h may be NULL: error of the last failed hrn_create */
 
 /* Replaces `model.load_state_dict(checkpoint)` (SimpleHRNet.py:117-121).  Folds every
- * (conv, BatchNorm) pair (eps 1e-5), repacks to the MFMA fragment layout and uploads. */
+ * (conv, BatchNorm) pair (eps 1e-5), repacks to the MFMA fragment layout and uploads.
+ * 16-bit handles store the folded weights rounded to nearest even (biases stay fp32); an HRN_F16 handle fails
+ * when a folded weight exceeds 65504 in magnitude (no fp16 representation) instead of storing inf.
+ * The blob of an HRN_F16 handle has the bf16 handle's layout and size, not its bytes: ranks of one job must
+ * share the dtype (dist.ShardedHRNet checks it before the broadcast). */
 int hrn_load_weights(hrn_handle h, const hrn_tensor_desc *descs, int n);
 
 /* Multi-GPU weight distribution (replaces DataParallel's per-forward `replicate`,

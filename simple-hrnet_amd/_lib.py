@@ -18,8 +18,13 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libhrnet_mi355.so")
 if os.environ.get("HRN_LIB_TAG"):   # A/B runs of compile-time variants (tools/mkvariant.sh builds libhrnet_mi355_<tag>.so beforehand)
     LIB_PATH = LIB_PATH.replace(".so", "_%s.so" % os.environ["HRN_LIB_TAG"])
-SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "conv3x3_f32.hip", "bottleneck_chain.hip", "prepath.hip", "nms.hip", "postproc.cpp", "hrnet_mi355.cpp"]
-HEADERS = [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "conv3x3_n96.inc"), os.path.join(INCLUDE, "hrnet_mi355.h")]
+SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "conv3x3_f32.hip", "bottleneck_chain.hip", "prepath.hip", "nms.hip", "postproc.cpp", "hrnet_mi355.cpp",
+           # fp16 instantiations of the three hand-scheduled kernel families (bodies shared through conv3x3_lds.inc / conv_s2.inc /
+           # bottleneck_chain.inc): translation units of their own, so that each bf16 file still compiles to exactly its kernel set
+           "conv3x3_lds_f16.hip", "conv_s2_f16.hip", "bottleneck_chain_f16.hip"]
+HEADERS = [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "dt16.h"), os.path.join(CSRC, "conv3x3_n96.inc"), os.path.join(CSRC, "conv3x3_lds.inc"),
+           os.path.join(CSRC, "conv_s2.inc"), os.path.join(CSRC, "bottleneck_chain.inc"), os.path.join(INCLUDE, "hrnet_mi355.h")]
+MAX_BUILD_WORKERS = 16   # compiler processes at once (a shared build box gives a job 16 CPUs, whatever os.cpu_count() says)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-result", "-Wno-inline-asm"]
 
 
@@ -36,7 +41,8 @@ def _obj_dir() -> str:
 
 
 def _deps(src: str) -> List[str]:
-    """files whose change invalidates the object of `src` (every source includes kernels.h; conv3x3_lds.hip the .inc files)"""
+    """files whose change invalidates the object of `src` (every source includes kernels.h; the kernel sources dt16.h and the
+    .inc files that hold their bodies -- conv3x3_lds(_f16).hip, conv_s2(_f16).hip, bottleneck_chain(_f16).hip)"""
     d = [os.path.join(CSRC, src)] + HEADERS
     return d + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".inc") or f.endswith(".h")]
 
@@ -126,7 +132,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
                 todo = [s for s in SOURCES if force or _stale(s)]
                 stamp = _stamp()
-                with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 4) or 1) as ex:
+                with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 4, MAX_BUILD_WORKERS) or 1) as ex:
                     list(ex.map(compile_one, todo))
                 tmp = "%s.tmp.%d" % (LIB_PATH, os.getpid())
                 cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp] + [_obj(s) for s in SOURCES]

@@ -121,7 +121,7 @@ __device__ __forceinline__ void n96_glds(const GLOBAL_AS char *base, unsigned vo
 // a tile's slab is still one run of flat rows, from the first pixel's window start to the last one's end -- `slab_rows` rows,
 // the longest such run of the geometry --, and a fragment's 16 lanes are 16 consecutive REAL pixels, so every pixel fragment has its
 // own slab address and swizzle bits (measured on the flat enumeration: ~4 % of the loop, profiles/EXPERIMENTS.md) and the outputs their own rows.
-template <int MR, bool CP = false>
+template <int MR, bool CP, int DT>
 __device__ __forceinline__ void c3n_run(const Conv3Problem &p_, const int nt, const int mt0, const int tiles_this_block,
                                         const int nb, char *smem) {
     constexpr bool PF = CP;   // one slab address per pixel fragment
@@ -471,7 +471,10 @@ __device__ __forceinline__ void c3n_run(const Conv3Problem &p_, const int nt, co
                         // and needs up to twice their registers
 #pragma unroll
                         for (int i = 0; i < MR; ++i)
-                            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(wf[j]), "v"(xf[xs][i]));
+                            if constexpr (DT == DT_F16)
+                                asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(wf[j]), "v"(xf[xs][i]));
+                            else
+                                asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(wf[j]), "v"(xf[xs][i]));
                         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(wf[j]) : "v"(wl_rd), "i"((((cc + 1) % 3) * NRB + j) * 1024));
                         if (xpre) {
 #pragma unroll
@@ -561,24 +564,23 @@ __device__ __forceinline__ void c3n_run(const Conv3Problem &p_, const int nt, co
 #pragma unroll
                         for (int j = 0; j < NRB; ++j) {
                             const unsigned r01 = rpre[i][j >> 1][2 * (j & 1)], r23 = rpre[i][j >> 1][2 * (j & 1) + 1];
-                            float v0 = acc[i][j][0] + __uint_as_float(r01 << 16);
-                            float v1 = acc[i][j][1] + __uint_as_float(r01 & 0xffff0000u);
-                            float v2 = acc[i][j][2] + __uint_as_float(r23 << 16);
-                            float v3 = acc[i][j][3] + __uint_as_float(r23 & 0xffff0000u);
-                            typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+                            float v0 = acc[i][j][0] + H16<DT>::lo(r01);
+                            float v1 = acc[i][j][1] + H16<DT>::hi(r01);
+                            float v2 = acc[i][j][2] + H16<DT>::lo(r23);
+                            float v3 = acc[i][j][3] + H16<DT>::hi(r23);
                             if (p.relu) {
                                 // ReLU and the pad mask in ONE op per value: med3(x, 0, lim), lim = +inf on real pixels, 0 on pad pixels
                                 asm("v_med3_f32 %0, %1, 0, %2" : "=v"(v0) : "v"(v0), "v"(lim));
                                 asm("v_med3_f32 %0, %1, 0, %2" : "=v"(v1) : "v"(v1), "v"(lim));
                                 asm("v_med3_f32 %0, %1, 0, %2" : "=v"(v2) : "v"(v2), "v"(lim));
                                 asm("v_med3_f32 %0, %1, 0, %2" : "=v"(v3) : "v"(v3), "v"(lim));
-                                const bf16x2 lo = {(__bf16)v0, (__bf16)v1}, hi = {(__bf16)v2, (__bf16)v3};   // RNE, v_cvt_pk_bf16_f32
-                                pk[2 * j] = __builtin_bit_cast(unsigned, lo);
-                                pk[2 * j + 1] = __builtin_bit_cast(unsigned, hi);
+                                const unsigned lo = H16<DT>::pk(v0, v1), hi = H16<DT>::pk(v2, v3);   // RNE, v_cvt_pk_{bf16,f16}_f32
+                                pk[2 * j] = lo;
+                                pk[2 * j + 1] = hi;
                             } else {
-                                const bf16x2 lo = {(__bf16)v0, (__bf16)v1}, hi = {(__bf16)v2, (__bf16)v3};
-                                pk[2 * j] = ok ? __builtin_bit_cast(unsigned, lo) : 0u;
-                                pk[2 * j + 1] = ok ? __builtin_bit_cast(unsigned, hi) : 0u;
+                                const unsigned lo = H16<DT>::pk(v0, v1), hi = H16<DT>::pk(v2, v3);
+                                pk[2 * j] = ok ? lo : 0u;
+                                pk[2 * j + 1] = ok ? hi : 0u;
                             }
                         }
 #pragma unroll

@@ -190,7 +190,7 @@
         a.ksize = cv.k, a.stride = cv.stride, a.relu = cv.relu, a.kchunks = cv.kchunks;
         a.rev = rev;
         a.pre_mode = pre_mode;
-        a.wlds = direct_wlds && dtype == 1 ? 1 : 0;
+        a.wlds = direct_wlds && is16() ? 1 : 0;
         a.xlds = conv_xl(cv) ? 1 : 0;
         a.up = cv.up ? 1 : 0, a.up_a = cv.up ? (cv.up - 1) >> 1 : 0, a.up_b = cv.up ? (cv.up - 1) & 1 : 0;
         a.up_wp = tensors[cv.out_t].wp, a.up_hpwp = tensors[cv.out_t].hpwp;

@@ -35,14 +35,14 @@
 
     int default_nr(int cout, int stride) const {
         int nr = (cout % 64 == 0) ? 4 : (cout % 48 == 0) ? 3 : 2;
-        if (dtype == HRN_BF16 && stride == 2 && cout % 96 == 0 && direct_nr6) nr = 6;  // halves the A gathers per MFMA
+        if (is16() && stride == 2 && cout % 96 == 0 && direct_nr6) nr = 6;  // halves the A gathers per MFMA
         return nr;
     }
     // widest cout tile every member of a set of sibling convolutions can use
     int common_nr(const std::vector<int> &couts, int stride) const {
         bool all64 = true, all48 = true, all96 = true;
         for (int co : couts) all64 &= co % 64 == 0, all48 &= co % 48 == 0, all96 &= co % 96 == 0;
-        if (dtype == HRN_BF16 && stride == 2 && all96 && direct_nr6) return 6;
+        if (is16() && stride == 2 && all96 && direct_nr6) return 6;
         return all64 ? 4 : all48 ? 3 : 2;
     }
 
@@ -63,7 +63,7 @@
         const int oh = ti.h / stride, ow = ti.w / stride;
         op.up = up;
         op.out_t = up ? up_out_t : new_tensor(cout, oh, ow);
-        const int kc = dtype == HRN_BF16 ? 32 : 16;
+        const int kc = is16() ? 32 : 16;
         const int K = k * k * op.cin;
         op.kchunks = (K + kc - 1) / kc;
         op.kpad = op.kchunks * kc;
@@ -72,7 +72,7 @@
         // pipelined LDS kernel (conv3x3_lds.hip): KS = 48 / 48-cout tiles for the HRNet-W48 branch widths, KS = 32 with
         // 64-, 48- or 32-cout tiles for everything else whose channel counts are multiples of 32
         int lds_ks = 0, lds_nrb = 0;
-        if (dtype == HRN_BF16 && k == 3 && stride == 1 && !disable_lds && !up && !force_generic) {
+        if (is16() && k == 3 && stride == 1 && !disable_lds && !up && !force_generic) {
             // widths that are multiples of 96 (the 96 / 192 / 384-channel branches of W48): 96 couts per block, 32-channel slices.
             // At EVERY batch size (its K order differs from the other forms'); its address arithmetic is 32-bit: tensors < 4 GB.
             const int64_t out_bytes = ((int64_t)max_batch * (oh + 1) * (ow + 1) + 2 * (ow + 2) + 512) * std::max(op.cin, cout) * 2;
@@ -104,7 +104,7 @@
             op.slices = op.cin / 16, op.ntiles = cout / (16 * op.nr), op.nch = 9;
             op.kpad = 9 * 16 * op.slices;
         }
-        if (dtype == HRN_BF16 && k == 3 && stride == 2 && (op.cin == 48 || op.cin == 32 || op.cin == 64) &&   // (cin = 96 does not fit the registers: conv_s2.hip)
+        if (is16() && k == 3 && stride == 2 && (op.cin == 48 || op.cin == 32 || op.cin == 64) &&   // (cin = 96 does not fit the registers: conv_s2.hip)
             cout % (16 * s2_frags_per_part(op.cin)) == 0 && !up && !disable_s2 && op.algo == 0 &&
             // at least two output rows per tile (or the whole image): with one, half of every slab is halo (three input rows
             // for one output row -- the 64 -> 64 stem conv of a 384x288 net) and the kernel moves 1.5x the tensor
@@ -245,7 +245,7 @@
                 const int i2 = (int)convs.size() - 1, i1 = g1[b];
                 // a 48 -> 48 -> 48 block in bf16: both convolutions in one pass over the tile, Y stays in LDS
                 const ConvOp &a1 = convs[i1], &a2 = convs[i2];
-                if (!disable_bbf && dtype == 1 && a1.algo == 1 && a2.algo == 1 && a1.ks == 48 && a1.nr == 3 && a1.slices == 1 &&
+                if (!disable_bbf && is16() && a1.algo == 1 && a2.algo == 1 && a1.ks == 48 && a1.nr == 3 && a1.slices == 1 &&
                     a1.ntiles == 1 && a2.slices == 1 && a2.ntiles == 1 && conv3x3_lds_bbf_ok(tensors[t2].wp)) {
                     convs[i1].fuse_with = i2;
                     convs[i2].fused_away = true;
@@ -329,7 +329,7 @@
             snprintf(buf, sizeof buf, "layer1.%d", b);
             const std::string p = buf;
             int o1 = o1_next, r = x;
-            const bool chain = dtype == HRN_BF16 && !disable_chain && b < nblocks - 1;
+            const bool chain = is16() && !disable_chain && b < nblocks - 1;
             int ds_idx = -1;
             if (b == 0 && chain && !disable_chain_ds) {
                 // the projection shortcut is computed inside the chain kernel: its 256-channel tensor never exists
@@ -348,7 +348,7 @@
             // kernel -- in the generic kernel's arithmetic (generic weight image, NR = 2), so conv2's own tensor is never written
             // (that arithmetic is taken for these convolutions under EVERY switch setting -- with the fusion or the chain kernel off they
             // run on conv_direct_kernel -- so that all plan variants stay bit-identical)
-            const bool c2_generic = dtype == HRN_BF16 && b >= 1;
+            const bool c2_generic = is16() && b >= 1;
             const bool chain3 = c2_generic && !disable_chain && !disable_chain3;
             const int o2 = c2_generic ? add_conv(p + ".conv2", p + ".bn2", o1, 64, 3, 1, 1, -1, !chain3, 2, 0, -1, true)
                                       : add_conv(p + ".conv2", p + ".bn2", o1, 64, 3, 1, 1);
@@ -448,7 +448,7 @@
         stem_conv2_op = (int)ops.size() - 1;
         // bf16: conv1 + conv2 as ONE kernel (stem_fused.hip) that keeps conv1's output in LDS.  Planned BESIDE the two launches
         // above, which stay the path of a call that taps "stem" and of HRN_DISABLE_STEM_FUSE=1; tile = one output row of conv2
-        if (dtype == HRN_BF16 && !disable_stem_fuse && !disable_stem_mfma && stem_fused_fits(tensors[x].wp, W)) {
+        if (is16() && !disable_stem_fuse && !disable_stem_mfma && stem_fused_fits(tensors[x].wp, W)) {
             stem_fuse = true;
             convs.back().w2_image = true;
             stemf = S2Group();

@@ -57,7 +57,7 @@
         a.n = nb, a.H = H, a.W = W;
         a.out_h = t.h, a.out_w = t.w, a.out_wp = t.wp, a.out_hpwp = t.hpwp;
         a.flip = flip;
-        return launch_stem_fused(s2probs_dev + g.prob_first, sl->dev, sl->nblocks, a, s);
+        return launch_stem_fused(dtype, s2probs_dev + g.prob_first, sl->dev, sl->nblocks, a, s);
     }
 
     hipError_t exec_op(const Op &op, bool rev, const float *images, int nb, const void *boxes, int box_dtype, float *pts,
@@ -69,7 +69,7 @@
             StemArgs a;
             a.images = images, a.out = row0(stem_out_t);
             a.w = (const float *)(blob + stem_w_off), a.bias = (const float *)(blob + stem_b_off);
-            a.wp = (dtype == HRN_BF16 && !disable_stem_mfma) ? (const void *)(blob + stem_wp_off) : nullptr;
+            a.wp = (is16() && !disable_stem_mfma) ? (const void *)(blob + stem_wp_off) : nullptr;
             a.n = nb, a.H = H, a.W = W;
             a.out_h = t.h, a.out_w = t.w, a.out_wp = t.wp, a.out_hpwp = t.hpwp;
             a.flip = flip;
@@ -81,7 +81,7 @@
             Stem7Args a;
             a.images = images, a.out = row0(stem_out_t);
             a.w = (const float *)(blob + stem_w_off), a.bias = (const float *)(blob + stem_b_off);
-            a.wp = (dtype == HRN_BF16 && !disable_stem_mfma) ? (const void *)(blob + stem_wp_off) : nullptr;
+            a.wp = (is16() && !disable_stem_mfma) ? (const void *)(blob + stem_wp_off) : nullptr;
             a.n = nb, a.H = H, a.W = W;
             a.out_h = t.h, a.out_w = t.w, a.out_wp = t.wp, a.out_hpwp = t.hpwp;
             a.flip = flip;
@@ -121,8 +121,9 @@
                 sl->nb = nb;
                 ++map_builds;
             }
-            e = launch_conv3x3_lds(probs_dev + g.prob_first, sl->dev, sl->nblocks, nb, convs[g.conv_idx[0]].ks,
-                                   convs[g.conv_idx[0]].nr, s);
+            // (fp16: the same kernels instantiated with fp16 elements, conv3x3_lds_f16.hip)
+            e = (dtype == HRN_F16 ? launch_conv3x3_lds_f16 : launch_conv3x3_lds)(probs_dev + g.prob_first, sl->dev, sl->nblocks, nb,
+                                                                             convs[g.conv_idx[0]].ks, convs[g.conv_idx[0]].nr, s);
             break;
         }
         case OP_CONV_GROUP: {
@@ -149,7 +150,7 @@
                 ++map_builds;
             }
             {
-                int wl = direct_wlds && dtype == 1 ? 1 : 0;   // 2: a member takes the XL form (its LDS layout is the larger one)
+                int wl = direct_wlds && is16() ? 1 : 0;   // 2: a member takes the XL form (its LDS layout is the larger one)
                 if (wl)
                     for (int ci : g.conv_idx)
                         if (conv_xl(convs[ci])) wl = 2;
@@ -182,7 +183,7 @@
                 sl->nb = nb;
                 ++map_builds;
             }
-            e = launch_conv_s2(s2probs_dev + g.prob_first, sl->dev, sl->nblocks, s);
+            e = (dtype == HRN_F16 ? launch_conv_s2_f16 : launch_conv_s2)(s2probs_dev + g.prob_first, sl->dev, sl->nblocks, s);
             break;
         }
         case OP_CHAIN: {
@@ -210,7 +211,7 @@
                 a.res = nullptr;
             }
             a.m = nb * to.hpwp, a.h = to.h, a.w = to.w, a.wp = to.wp, a.hpwp = to.hpwp, a.rev = rev, a.max_blocks = chain_blocks;
-            e = launch_bottleneck_chain(a, s);
+            e = dtype == HRN_F16 ? launch_bottleneck_chain_f16(a, s) : launch_bottleneck_chain(a, s);
             break;
         }
         case OP_FUSE: {
@@ -238,7 +239,7 @@
             HeadArgs a;
             a.in = row0(head_in_t);
             a.wgt = (const float *)(blob + head_w_off), a.bias = (const float *)(blob + head_b_off);
-            a.wimg = (dtype == HRN_BF16 && !disable_head_mfma) ? (const void *)(blob + head_wp_off) : nullptr;
+            a.wimg = (is16() && !disable_head_mfma) ? (const void *)(blob + head_wp_off) : nullptr;
             a.heatmaps = heatmaps, a.part_val = part_val, a.part_idx = part_idx;
             a.n = nb, a.c = t.c, a.joints = joints, a.h = t.h, a.w = t.w, a.wp = t.wp, a.hpwp = t.hpwp;
             a.slabs = head_slabs_for(nb), a.slab_px = head_px_for(nb);

@@ -141,3 +141,21 @@ inline uint16_t f32_to_bf16_host(float f) {
     return (uint16_t)(u >> 16);
 }
 
+// fp32 -> fp16, round to nearest even, subnormals kept: bit-equal to torch's .to(torch.float16); |f| >= 65520 becomes +-inf
+// (load_weights refuses folded weights above 65504 before it gets there)
+inline uint16_t f32_to_f16_host(float f) {
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    const uint16_t sign = (uint16_t)((x >> 16) & 0x8000u);
+    const uint32_t ax = x & 0x7fffffffu;
+    if (ax > 0x7f800000u) return sign | 0x7e00u;                 // NaN
+    if (ax >= 0x477ff000u) return sign | 0x7c00u;                // 65520 and up (ties to even go up): inf
+    if (ax >= 0x38800000u) {                                     // normal: 2^-14 and up
+        uint32_t m = ax - 0x38000000u;                           // exponent re-biased 127 -> 15
+        m += 0xfffu + ((m >> 13) & 1u);
+        return sign | (uint16_t)(m >> 13);
+    }
+    float a;                                                     // subnormal: units of 2^-24, the scaling is exact
+    memcpy(&a, &ax, 4);
+    return sign | (uint16_t)std::nearbyint(a * 16777216.0f);     // (default rounding mode: nearest even)
+}

@@ -46,6 +46,7 @@
             m[descs[i].name] = Src{(const float *)descs[i].data, cnt};
         }
         std::vector<char> host((size_t)blob_bytes, 0);
+        pack_overflow = false;
         std::vector<double> scale, shift;
         if (model == 1) {  // PoseResNet stem: w[k = (ci*7 + kh)*7 + kw][co]
             const float *w;
@@ -65,7 +66,7 @@
                         for (int e = 0; e < 8; ++e) {
                             const int k = kc * 32 + g * 8 + e;
                             dp[((kc * 4 + j) * 64 + lane) * 8 + e] =
-                                f32_to_bf16_host(k < 147 ? (float)((double)w[co * 147 + k] * scale[co]) : 0.f);
+                                to16(k < 147 ? (float)((double)w[co * 147 + k] * scale[co]) : 0.f);
                         }
                     }
         } else {  // stem: w[k = ci*9+kh*3+kw][co]
@@ -85,7 +86,7 @@
                     const int co = (li >> 2) * 16 + j * 4 + (li & 3);
                     for (int e = 0; e < 8; ++e) {
                         const int k = g * 8 + e;
-                        dp[(j * 64 + lane) * 8 + e] = f32_to_bf16_host(k < 27 ? (float)((double)w[co * 27 + k] * scale[co]) : 0.f);
+                        dp[(j * 64 + lane) * 8 + e] = to16(k < 27 ? (float)((double)w[co * 27 + k] * scale[co]) : 0.f);
                     }
                 }
         }
@@ -154,8 +155,12 @@
                         for (int e = 0; e < 8; ++e) {
                             const int j = f * 16 + (lane & 15), k = kc * 32 + (lane >> 4) * 8 + e;
                             img[((size_t)(f * kch + kc) * 64 + lane) * 8 + e] =
-                                (j < joints && k < c) ? f32_to_bf16_host(w[(size_t)j * c + k]) : (uint16_t)0;
+                                (j < joints && k < c) ? to16(w[(size_t)j * c + k]) : (uint16_t)0;
                         }
+        }
+        if (pack_overflow) {
+            err = "a folded weight exceeds 65504 in magnitude: it has no fp16 representation (use dtype bf16 or fp32)";
+            return false;
         }
         if (plan_only) {
             memcpy(blob, host.data(), (size_t)blob_bytes);
@@ -168,13 +173,22 @@
         return true;
     }
 
+    // one folded weight in the handle's 16-bit format (bf16 / fp16, round to nearest even); an fp16 magnitude above 65504 is
+    // noted and fails the load
+    mutable bool pack_overflow = false;
+    uint16_t to16(float v) const {
+        if (dtype != HRN_F16) return f32_to_bf16_host(v);
+        if (std::fabs(v) > 65504.f) pack_overflow = true;
+        return f32_to_f16_host(v);
+    }
+
     // Fragment-major packing (DESIGN.md §4).  One fragment = 16 packed rows x one K-chunk = 64 lanes x 16 B,
     // stored lane-linear so a wave loads it with one coalesced 1 KiB access.  Fragment f = ng*NR + j holds,
     // in packed row i (= lane & 15), output channel  ng*16*NR + (i>>2)*4*NR + j*4 + (i&3); lane group
     // g = lane>>4 holds k = kc*KC + g*VEC + [0,VEC).  With the operand swap D = W * X^T each lane then owns
     // 4*NR contiguous channels of one pixel.
     void pack_conv(const ConvOp &cv, const float *wf, int K, char *dst) const {
-        const int KC = dtype == HRN_BF16 ? 32 : 16, VEC = dtype == HRN_BF16 ? 8 : 4;
+        const int KC = is16() ? 32 : 16, VEC = is16() ? 8 : 4;
         const int nfrag = cv.cout / 16;
         for (int f = 0; f < nfrag; ++f) {
             const int ng = f / cv.nr, j = f % cv.nr;
@@ -186,8 +200,8 @@
                     for (int e = 0; e < VEC; ++e) {
                         const int k = kc * KC + g * VEC + e;
                         const float v = k < K ? wf[(size_t)co * K + k] : 0.f;
-                        if (dtype == HRN_BF16)
-                            ((uint16_t *)d)[e] = f32_to_bf16_host(v);
+                        if (is16())
+                            ((uint16_t *)d)[e] = to16(v);
                         else
                             ((float *)d)[e] = v;
                     }
@@ -232,7 +246,7 @@
                                     const int tap = kl / KS, cil = kl % KS;
                                     v = wf[(size_t)co * K + tap * cv.cin + s * KS + cil];
                                 }
-                                d[e] = f32_to_bf16_host(v);
+                                d[e] = to16(v);
                             }
                         }
             }

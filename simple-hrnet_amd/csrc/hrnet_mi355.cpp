@@ -44,6 +44,8 @@ struct hrn_ctx {
     bool plan_only;
     int esize;
     std::string err;
+    // the 16-bit MFMA path: bf16 and fp16 handles share every plan, layout and kernel; only the element format differs
+    bool is16() const { return dtype == HRN_BF16 || dtype == HRN_F16; }
 
     std::vector<Tensor> tensors;
     std::vector<Buffer> buffers;
@@ -88,7 +90,7 @@ struct hrn_ctx {
     // LDS-DMA into a per-wave LDS ring (kernels.hip: XL); same arithmetic in the same order: bit-identical to HRN_DIRECT_XLDS=0
     bool direct_xlds = !(env_sw("HRN_DIRECT_XLDS") && atoi(env_sw("HRN_DIRECT_XLDS")) == 0);
     bool conv_xl(const ConvOp &cv) const {
-        return direct_xlds && direct_wlds && dtype == 1 && cv.k == 3 && cv.stride == 2 && cv.cin % 32 == 0 && !cv.up && cv.res_t < 0 && cv.nr == 6 &&
+        return direct_xlds && direct_wlds && is16() && cv.k == 3 && cv.stride == 2 && cv.cin % 32 == 0 && !cv.up && cv.res_t < 0 && cv.nr == 6 &&
                cv.kchunks >= 4;
     }
     // fused BasicBlocks on the 48-channel branch (conv3x3_lds.hip: bbf_run): bit-identical, 2.5x less HBM traffic on that
@@ -230,8 +232,8 @@ int hrn_create_model(hrn_handle *out, int model, int c, int nof_joints, int heig
         g_create_error = "nof_joints must be in [1, 32]";
         return 2;
     }
-    if (dtype != HRN_F32 && dtype != HRN_BF16) {
-        g_create_error = "dtype must be HRN_F32 or HRN_BF16";
+    if (dtype != HRN_F32 && dtype != HRN_BF16 && dtype != HRN_F16) {
+        g_create_error = "dtype must be HRN_F32, HRN_BF16 or HRN_F16";
         return 2;
     }
     if (max_batch <= 0) {
@@ -244,7 +246,7 @@ int hrn_create_model(hrn_handle *out, int model, int c, int nof_joints, int heig
     h->model = model;
     h->c = c, h->joints = nof_joints, h->H = height, h->W = width, h->dtype = dtype, h->max_batch = max_batch;
     h->device = device_id, h->plan_only = device_id < 0;
-    h->esize = dtype == HRN_BF16 ? 2 : 4;
+    h->esize = h->is16() ? 2 : 4;
     if (!h->plan_only) {
         int ndev = 0;
         hipError_t e = hipGetDeviceCount(&ndev);

@@ -36,7 +36,7 @@ inline const char *hrn_env(const char *name) {
     return debug ? getenv(name) : nullptr;
 }
 
-enum { DT_F32 = 0, DT_BF16 = 1 };
+enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2 };   // = HRN_F32 / HRN_BF16 / HRN_F16 (include/hrnet_mi355.h)
 
 // Activation tensors use the "flat padded NHWC" layout:
 //   row(n, r, c) = n*Hp*Wp + r*Wp + c,  Wp = W+1, Hp = H+1, C channels per row,
@@ -142,6 +142,7 @@ struct S2Problem {
     S2Part part[kS2MaxParts];
 };
 hipError_t launch_conv_s2(const S2Problem *probs_dev, const void *map_dev, int nblocks, hipStream_t s);
+hipError_t launch_conv_s2_f16(const S2Problem *probs_dev, const void *map_dev, int nblocks, hipStream_t s);   // conv_s2_f16.hip
 
 // The stem as one kernel (stem_fused.hip, round 4, bf16): conv1 computed into the stride-2 slab's LDS layout, conv2 from there;
 // one output row of conv2 per tile.  `probs_dev[.]` = conv2 as a slab-kernel problem with rows = 1 (its `in` is not read),
@@ -171,6 +172,7 @@ struct ChainArgs {
     int max_blocks;        // persistent blocks of the launch (512: two per CU)
 };
 hipError_t launch_bottleneck_chain(const ChainArgs &a, hipStream_t s);
+hipError_t launch_bottleneck_chain_f16(const ChainArgs &a, hipStream_t s);   // bottleneck_chain_f16.hip
 
 struct StemArgs {          // conv1 3->64 3x3 s2 + BN + ReLU, NCHW fp32 in, flat padded out
     const float *images;   // (n,3,H,W)
@@ -183,7 +185,7 @@ struct StemArgs {          // conv1 3->64 3x3 s2 + BN + ReLU, NCHW fp32 in, flat
     int flip;              // read the crops mirrored left-right (flip-TTA: misc/utils.py flip_tensor(image, dim=-1))
 };
 
-hipError_t launch_stem_fused(const S2Problem *probs_dev, const void *map_dev, int nblocks, const StemArgs &stem, hipStream_t s);
+hipError_t launch_stem_fused(int dtype, const S2Problem *probs_dev, const void *map_dev, int nblocks, const StemArgs &stem, hipStream_t s);
 
 // Crop pre-path (prepath.hip): one person's slice of the frame, its zero padding and where its horizontal pass lives
 struct CropParams {
@@ -294,6 +296,8 @@ hipError_t launch_conv_group(int dtype, const ConvArgs *probs_dev, const void *m
                              hipStream_t s);
 hipError_t launch_conv3x3_lds(const Conv3Problem *probs_dev, const void *blockmap_dev, int nblocks, int nb, int ks,
                               int nrb, hipStream_t s);
+hipError_t launch_conv3x3_lds_f16(const Conv3Problem *probs_dev, const void *blockmap_dev, int nblocks, int nb, int ks,
+                                  int nrb, hipStream_t s);   // conv3x3_lds_f16.hip: the same kernels with fp16 elements
 hipError_t launch_stem(int dtype, const StemArgs &a, hipStream_t s);
 hipError_t launch_fuse(int dtype, const FuseArgs &a, hipStream_t s);
 hipError_t launch_head(int dtype, const HeadArgs &a, hipStream_t s);

@@ -2,7 +2,7 @@
 //
 //   conv_direct_kernel  generic implicit-GEMM convolution (1x1 / 3x3, stride 1 / 2) on MFMA with the
 //                       fused epilogue  out = [relu]( acc + bias [+ residual] ), zero at pad pixels.
-//                       bf16: v_mfma_f32_16x16x32_bf16 (fp32 accumulate); fp32: v_mfma_f32_16x16x4_f32
+//                       bf16 / fp16: v_mfma_f32_16x16x32_{bf16,f16} (fp32 accumulate); fp32: v_mfma_f32_16x16x4_f32
 //                       (exact fp32 fma chain).  Operands are swapped (D = W * X^T) so that one lane owns
 //                       4*NR *contiguous* output channels of one pixel -> wide NHWC stores.
 //   stem_kernel         conv1 (3->64, 3x3 s2) + BN + ReLU straight from the caller's NCHW fp32 crops.
@@ -10,6 +10,7 @@
 //   head_kernel         final 1x1 conv + bias, optional heat-map write-out, per-slab arg-max.
 //   decode_kernel       arg-max merge (first maximum wins) + box scaling in fp64, SimpleHRNet.py:297-308.
 #include "kernels.h"
+#include "dt16.h"
 #include <stdlib.h>
 
 namespace hrn {
@@ -26,6 +27,9 @@ __device__ __forceinline__ unsigned short f32_to_bf16(float f) {  // round to ne
     return (unsigned short)(u >> 16);
 }
 
+// the 16-bit MFMA path (bf16 or fp16 elements: same layouts, tiles and kernels) versus the fp32 one
+constexpr bool is16(int dt) { return dt != DT_F32; }
+
 template <int DT>
 struct Tr;
 template <>
@@ -36,6 +40,15 @@ struct Tr<DT_BF16> {
     static constexpr int KC = 32, VEC = 8;
     static __device__ __forceinline__ float ld(elem e) { return bf16_to_f32(e); }
     static __device__ __forceinline__ elem st(float f) { return f32_to_bf16(f); }
+};
+template <>
+struct Tr<DT_F16> {   // the bf16 layouts and tiles with fp16 elements (dt16.h)
+    using elem = unsigned short;
+    using vec = s16x8;
+    using out4 = s16x4;
+    static constexpr int KC = 32, VEC = 8;
+    static __device__ __forceinline__ float ld(elem e) { return H16<DT_F16>::ld(e); }
+    static __device__ __forceinline__ elem st(float f) { return H16<DT_F16>::st(f); }
 };
 template <>
 struct Tr<DT_F32> {
@@ -53,6 +66,10 @@ template <>
 __device__ __forceinline__ f32x4 mma<DT_BF16>(s16x8 w, s16x8 x, f32x4 acc) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0,
                                                    0, 0);
+}
+template <>
+__device__ __forceinline__ f32x4 mma<DT_F16>(s16x8 w, s16x8 x, f32x4 acc) {
+    return H16<DT_F16>::mma(w, x, acc);
 }
 template <>
 __device__ __forceinline__ f32x4 mma<DT_F32>(f32x4 w, f32x4 x, f32x4 acc) {
@@ -103,7 +120,7 @@ __device__ __forceinline__ void conv_direct_epilogue(const ConvArgs &p, const in
             if (!ok) continue;
             o = ((size_t)(q / p.out_hpwp) * p.up_hpwp + (size_t)(2 * ho + p.up_a) * p.up_wp + 2 * wo + p.up_b) * p.cout + ch0;
         }
-        if constexpr (DT == DT_BF16 && (NR % 2 == 0)) {
+        if constexpr (is16(DT) && (NR % 2 == 0)) {
             // 8 contiguous channels per access: 16-byte residual loads and stores
 #pragma unroll
             for (int j = 0; j < NR; j += 2) {
@@ -218,7 +235,7 @@ __device__ __forceinline__ void conv_direct_body(const ConvArgs &p, const int ng
     // round 6, small launches (MR <= 2, bf16): a block's K loop is a chain of L2 round trips -- 27 for a 96 -> 192 stride-2 convolution, 18 us
     // per launch at 8 crops with the chip mostly idle.  The operands of KU chunks are requested together, then multiplied in the
     // same order as before (bit-identical): a quarter / half of the round trips.
-    constexpr int KU = (DT == DT_BF16 && !WL && !PRE) ? (MR == 1 ? 4 : MR == 2 ? 2 : 1) : 1;
+    constexpr int KU = (is16(DT) && !WL && !PRE) ? (MR == 1 ? 4 : MR == 2 ? 2 : 1) : 1;
     if constexpr (KU > 1) {
         for (int kc0 = 0; kc0 < p.kchunks; kc0 += KU) {
             vec b[KU][NR], a[KU][MR];
@@ -322,7 +339,7 @@ __device__ __forceinline__ bool conv_xl_ok(const ConvArgs &p) {
 __device__ __forceinline__ void xl_glds(const GLOBAL_AS char *base, unsigned voff, unsigned lds_dst) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" ::"v"(voff), "s"(lds_dst), "s"(base) : "memory", "m0");
 }
-template <int NR>
+template <int DT, int NR>
 __device__ __forceinline__ void conv_direct_xl_body(const ConvArgs &p, const int ng, const int mtile_in, char *smem) {
     constexpr int MR = 4;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -407,11 +424,11 @@ __device__ __forceinline__ void conv_direct_xl_body(const ConvArgs &p, const int
 #pragma unroll
         for (int i = 0; i < MR; ++i)
 #pragma unroll
-            for (int j = 0; j < NR; ++j) acc[i][j] = mma<DT_BF16>(b[j], a[i], acc[i][j]);
+            for (int j = 0; j < NR; ++j) acc[i][j] = mma<DT>(b[j], a[i], acc[i][j]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the dummy requests past the end: nothing of this block may land in LDS after it)
     s16x8 rpre[1][1];
-    conv_direct_epilogue<DT_BF16, NR, MR, false>(p, ng, m0, li, g, acc, rpre);
+    conv_direct_epilogue<DT, NR, MR, false>(p, ng, m0, li, g, acc, rpre);
 }
 
 // one convolution per launch.  1-D grid, cout tile fastest: the blocks that share an activation tile are dispatched
@@ -423,9 +440,9 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const ConvArgs p) {
     const int ngroups = p.cout / (16 * NR);
     const int ng = (blockIdx.x >> 3) % ngroups;
     const int mtile = (blockIdx.x / (8 * ngroups)) * 8 + (blockIdx.x & 7);
-    if constexpr (WL && DT == DT_BF16 && NR == 6 && MR == 4 && !PRE) {
+    if constexpr (WL && is16(DT) && NR == 6 && MR == 4 && !PRE) {
         if (p.xlds && conv_xl_ok(p)) {
-            conv_direct_xl_body<NR>(p, ng, mtile, smem_direct);
+            conv_direct_xl_body<DT, NR>(p, ng, mtile, smem_direct);
             return;
         }
     }
@@ -443,9 +460,9 @@ __global__ __launch_bounds__(256) void conv_direct_group_kernel(const ConvArgs *
     const int prob = __builtin_amdgcn_readfirstlane(e.x & 255), ng = __builtin_amdgcn_readfirstlane(e.x >> 8);
     const int mtile = __builtin_amdgcn_readfirstlane(e.y);
     const ConvArgs p = probs[prob];
-    if constexpr (WL && DT == DT_BF16 && NR == 6 && MR == 4) {
+    if constexpr (WL && is16(DT) && NR == 6 && MR == 4) {
         if (p.xlds && conv_xl_ok(p)) {
-            conv_direct_xl_body<NR>(p, ng, mtile, smem_direct);
+            conv_direct_xl_body<DT, NR>(p, ng, mtile, smem_direct);
             return;
         }
     }
@@ -456,7 +473,7 @@ __global__ __launch_bounds__(256) void conv_direct_group_kernel(const ConvArgs *
 template <int DT, int NR>
 static constexpr int direct_lds_bytes(int wlds) {
     const int wl = 2 * WL_G * NR * 1024;
-    if (DT == DT_BF16 && NR == 6 && wlds == 2) return wl > xl_lds_bytes(NR) ? wl : xl_lds_bytes(NR);
+    if (is16(DT) && NR == 6 && wlds == 2) return wl > xl_lds_bytes(NR) ? wl : xl_lds_bytes(NR);
     return wl;
 }
 
@@ -466,15 +483,15 @@ static hipError_t launch_conv_group_t(const ConvArgs *probs, const int2 *map, in
         hipLaunchKernelGGL((conv_direct_group_kernel<DT, NR, 1>), dim3(nblocks), dim3(256), 0, s, probs, map);
     else if (mr == 2)
         hipLaunchKernelGGL((conv_direct_group_kernel<DT, NR, 2>), dim3(nblocks), dim3(256), 0, s, probs, map);
-    else if (DT == DT_BF16 && wlds)
+    else if (is16(DT) && wlds)
     {
         const int lds = direct_lds_bytes<DT, NR>(wlds);
         static std::atomic<unsigned long long> lds_set{0};   // (more than 64 KiB of dynamic LDS: per device, kernels.h set_dynamic_lds)
         if (lds > 65536) {
-            const hipError_t e = set_dynamic_lds((const void *)conv_direct_group_kernel<DT, NR, 4, DT == DT_BF16>, direct_lds_bytes<DT, NR>(2), lds_set);
+            const hipError_t e = set_dynamic_lds((const void *)conv_direct_group_kernel<DT, NR, 4, is16(DT)>, direct_lds_bytes<DT, NR>(2), lds_set);
             if (e != hipSuccess) return e;
         }
-        hipLaunchKernelGGL((conv_direct_group_kernel<DT, NR, 4, DT == DT_BF16>), dim3(nblocks), dim3(256), lds, s, probs, map);
+        hipLaunchKernelGGL((conv_direct_group_kernel<DT, NR, 4, is16(DT)>), dim3(nblocks), dim3(256), lds, s, probs, map);
     }
     else
         hipLaunchKernelGGL((conv_direct_group_kernel<DT, NR, 4>), dim3(nblocks), dim3(256), 0, s, probs, map);
@@ -491,6 +508,11 @@ hipError_t launch_conv_group(int dtype, const ConvArgs *probs_dev, const void *m
         if (nr == 4) return launch_conv_group_t<DT_BF16, 4>(probs_dev, map, nblocks, mr, wlds, s);
         if (nr == 3) return launch_conv_group_t<DT_BF16, 3>(probs_dev, map, nblocks, mr, wlds, s);
         if (nr == 2) return launch_conv_group_t<DT_BF16, 2>(probs_dev, map, nblocks, mr, wlds, s);
+    } else if (dtype == DT_F16) {
+        if (nr == 6) return launch_conv_group_t<DT_F16, 6>(probs_dev, map, nblocks, mr, wlds, s);
+        if (nr == 4) return launch_conv_group_t<DT_F16, 4>(probs_dev, map, nblocks, mr, wlds, s);
+        if (nr == 3) return launch_conv_group_t<DT_F16, 3>(probs_dev, map, nblocks, mr, wlds, s);
+        if (nr == 2) return launch_conv_group_t<DT_F16, 2>(probs_dev, map, nblocks, mr, wlds, s);
     } else {
         if (nr == 4) return launch_conv_group_t<DT_F32, 4>(probs_dev, map, nblocks, mr, wlds, s);
         if (nr == 3) return launch_conv_group_t<DT_F32, 3>(probs_dev, map, nblocks, mr, wlds, s);
@@ -509,7 +531,7 @@ static hipError_t launch_conv_tt(const ConvArgs &a, hipStream_t s) {
 
 template <int DT, int NR>
 static hipError_t launch_conv_t(const ConvArgs &a, hipStream_t s) {
-    if constexpr (DT == DT_BF16 && NR % 2 == 0) {
+    if constexpr (is16(DT) && NR % 2 == 0) {
         const int pre_mode = a.pre_mode;
         if (a.res && a.ksize == 1 && pre_mode == 1) return launch_conv_tt<DT, NR, 4, true>(a, s);
         if (a.res && a.ksize == 1 && pre_mode == 2) return launch_conv_tt<DT, NR, 2, true>(a, s);
@@ -520,7 +542,7 @@ static hipError_t launch_conv_t(const ConvArgs &a, hipStream_t s) {
     const long blocks4 = (long)((a.m + 255) / 256) * ngroups;
     if (blocks4 < 256) return launch_conv_tt<DT, NR, 1, false>(a, s);
     if (blocks4 < 512) return launch_conv_tt<DT, NR, 2, false>(a, s);
-    if constexpr (DT == DT_BF16)
+    if constexpr (is16(DT))
         if (a.wlds && a.kchunks >= 2 * WL_G) {
             const int mtiles = (a.m + 255) / 256;
             dim3 grid(((mtiles + 7) / 8) * 8 * (a.cout / (16 * NR)));
@@ -543,6 +565,11 @@ hipError_t launch_conv(int dtype, const ConvArgs &a, int nr, hipStream_t s) {
         if (nr == 4) return launch_conv_t<DT_BF16, 4>(a, s);
         if (nr == 3) return launch_conv_t<DT_BF16, 3>(a, s);
         if (nr == 2) return launch_conv_t<DT_BF16, 2>(a, s);
+    } else if (dtype == DT_F16) {
+        if (nr == 6) return launch_conv_t<DT_F16, 6>(a, s);
+        if (nr == 4) return launch_conv_t<DT_F16, 4>(a, s);
+        if (nr == 3) return launch_conv_t<DT_F16, 3>(a, s);
+        if (nr == 2) return launch_conv_t<DT_F16, 2>(a, s);
     } else {
         if (nr == 4) return launch_conv_t<DT_F32, 4>(a, s);
         if (nr == 3) return launch_conv_t<DT_F32, 3>(a, s);
@@ -651,8 +678,9 @@ __global__ __launch_bounds__(256) void stem7_kernel(const Stem7Args p) {
     }
 }
 
-// bf16 mode: the 7x7 stem on MFMA.  K = 147 (ci, kh, kw) padded to five 32-wide chunks; a lane gathers its 8 k-values
-// of one output pixel per chunk straight from the NCHW fp32 crop (rounded to bf16), accumulators start at the bias.
+// 16-bit modes (bf16 / fp16): the 7x7 stem on MFMA.  K = 147 (ci, kh, kw) padded to five 32-wide chunks; a lane gathers its 8 k-values
+// of one output pixel per chunk straight from the NCHW fp32 crop (rounded to the 16-bit format), accumulators start at the bias.
+template <int DT>
 __global__ __launch_bounds__(256) void stem7_mfma_kernel(const Stem7Args p) {
     constexpr int MR = 4, NR = 4, KCH = 5;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -698,10 +726,10 @@ __global__ __launch_bounds__(256) void stem7_mfma_kernel(const Stem7Args p) {
                 float v = 0.f;
                 if (okp[i] && kc * 32 + g * 8 + e < 147 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
                     v = img[i][((size_t)dci[e] * p.H + iy) * p.W + (p.flip ? p.W - 1 - ix : ix)];
-                xf[e] = (short)f32_to_bf16(v);
+                xf[e] = (short)Tr<DT>::st(v);
             }
 #pragma unroll
-            for (int j = 0; j < NR; ++j) acc[i][j] = mma<DT_BF16>(wf[j], xf, acc[i][j]);
+            for (int j = 0; j < NR; ++j) acc[i][j] = mma<DT>(wf[j], xf, acc[i][j]);
         }
     }
     unsigned short *out = (unsigned short *)p.out;
@@ -716,7 +744,7 @@ __global__ __launch_bounds__(256) void stem7_mfma_kernel(const Stem7Args p) {
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 const float v = okp[i] ? fmaxf(acc[i][j + (r >> 2)][r & 3], 0.f) : 0.f;
-                o8[r] = (short)f32_to_bf16(v);
+                o8[r] = (short)Tr<DT>::st(v);
             }
             *(s16x8 *)(o + j * 4) = o8;
         }
@@ -728,9 +756,13 @@ hipError_t launch_stem7(int dtype, const Stem7Args &a, hipStream_t s) {
     if (m <= 0) return hipSuccess;
     dim3 grid((m + 255) / 256);
     if (dtype == DT_BF16 && a.wp)
-        hipLaunchKernelGGL(stem7_mfma_kernel, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(stem7_mfma_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
+    else if (dtype == DT_F16 && a.wp)
+        hipLaunchKernelGGL(stem7_mfma_kernel<DT_F16>, grid, dim3(256), 0, s, a);
     else if (dtype == DT_BF16)
         hipLaunchKernelGGL(stem7_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(stem7_kernel<DT_F16>, grid, dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(stem7_kernel<DT_F32>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
@@ -772,20 +804,23 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const PoolArgs p) {
 }
 
 hipError_t launch_maxpool(int dtype, const PoolArgs &a, hipStream_t s) {
-    const long total = (long)a.n * a.out_hpwp * (a.c / (dtype == DT_BF16 ? 8 : 4));
+    const long total = (long)a.n * a.out_hpwp * (a.c / (dtype != DT_F32 ? 8 : 4));
     if (total <= 0) return hipSuccess;
     dim3 grid((unsigned)((total + 255) / 256));
     if (dtype == DT_BF16)
         hipLaunchKernelGGL(maxpool_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(maxpool_kernel<DT_F16>, grid, dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(maxpool_kernel<DT_F32>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
-// bf16 mode: the same 3->64 stride-2 convolution on MFMA.  K = 27 (ci, kh, kw) padded to one 32-wide chunk; a
+// 16-bit modes: the same 3->64 stride-2 convolution on MFMA.  K = 27 (ci, kh, kw) padded to one 32-wide chunk; a
 // lane gathers its 8 k-values of one output pixel straight from the NCHW fp32 crop (rounded to bf16 -- every
 // later activation is bf16 as well), the 4 KiB weight image is held in registers, and one wave turns 64 pixels x
 // 64 channels with 16 MFMAs instead of 1728 scalar-weight FMAs per pixel.  Output: 32 contiguous bytes per lane.
+template <int DT>
 __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemArgs p) {
     constexpr int MR = 4, NR = 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -825,10 +860,10 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemArgs p) {
             float v = 0.f;
             if (okp[i] && g * 8 + e < 27 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
                 v = img[((size_t)dci[e] * p.H + iy) * p.W + (p.flip ? p.W - 1 - ix : ix)];
-            xf[e] = (short)f32_to_bf16(v);
+            xf[e] = (short)Tr<DT>::st(v);
         }
 #pragma unroll
-        for (int j = 0; j < NR; ++j) acc[i][j] = mma<DT_BF16>(wf[j], xf, acc[i][j]);
+        for (int j = 0; j < NR; ++j) acc[i][j] = mma<DT>(wf[j], xf, acc[i][j]);
     }
     unsigned short *out = (unsigned short *)p.out;
 #pragma unroll
@@ -842,7 +877,7 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemArgs p) {
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 const float v = okp[i] ? fmaxf(acc[i][j + (r >> 2)][r & 3], 0.f) : 0.f;
-                o8[r] = (short)f32_to_bf16(v);
+                o8[r] = (short)Tr<DT>::st(v);
             }
             *(s16x8 *)(o + j * 4) = o8;
         }
@@ -854,9 +889,13 @@ hipError_t launch_stem(int dtype, const StemArgs &a, hipStream_t s) {
     if (m <= 0) return hipSuccess;
     dim3 grid((m + 255) / 256);
     if (dtype == DT_BF16 && a.wp)
-        hipLaunchKernelGGL(stem_mfma_kernel, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(stem_mfma_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
+    else if (dtype == DT_F16 && a.wp)
+        hipLaunchKernelGGL(stem_mfma_kernel<DT_F16>, grid, dim3(256), 0, s, a);
     else if (dtype == DT_BF16)
         hipLaunchKernelGGL(stem_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(stem_kernel<DT_F16>, grid, dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(stem_kernel<DT_F32>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
@@ -923,11 +962,13 @@ __global__ __launch_bounds__(256) void fuse_group_kernel(const FuseGroupArgs g) 
 }
 
 hipError_t launch_fuse(int dtype, const FuseArgs &a, hipStream_t s) {
-    const long total = (long)a.m * (a.c / (dtype == DT_BF16 ? 8 : 4));
+    const long total = (long)a.m * (a.c / (dtype != DT_F32 ? 8 : 4));
     if (total <= 0) return hipSuccess;
     dim3 grid((unsigned)((total + 255) / 256));
     if (dtype == DT_BF16)
         hipLaunchKernelGGL(fuse_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(fuse_kernel<DT_F16>, grid, dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(fuse_kernel<DT_F32>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
@@ -936,13 +977,15 @@ hipError_t launch_fuse(int dtype, const FuseArgs &a, hipStream_t s) {
 hipError_t launch_fuse_group(int dtype, FuseGroupArgs &g, hipStream_t s) {
     long end = 0;
     for (int i = 0; i < g.nf; ++i) {
-        const long total = (long)g.f[i].m * (g.f[i].c / (dtype == DT_BF16 ? 8 : 4));
+        const long total = (long)g.f[i].m * (g.f[i].c / (dtype != DT_F32 ? 8 : 4));
         end += (total + 255) / 256;
         g.block_end[i] = (int)end;
     }
     if (end <= 0) return hipSuccess;
     if (dtype == DT_BF16)
         hipLaunchKernelGGL(fuse_group_kernel<DT_BF16>, dim3((unsigned)end), dim3(256), 0, s, g);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(fuse_group_kernel<DT_F16>, dim3((unsigned)end), dim3(256), 0, s, g);
     else
         hipLaunchKernelGGL(fuse_group_kernel<DT_F32>, dim3((unsigned)end), dim3(256), 0, s, g);
     return hipGetLastError();
@@ -1050,11 +1093,12 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs p) {
     }
 }
 
-// bf16 mode: the same head on MFMA.  D[joint][pixel] = W[joint][k] * X[k][pixel], joints padded to 32 (two
+// 16-bit modes: the same head on MFMA.  D[joint][pixel] = W[joint][k] * X[k][pixel], joints padded to 32 (two
 // fragments), K = c padded to a multiple of 32 (weights zero there; the x operand is forced to zero too, so stray
 // bytes never meet the matrix unit).  Lane (li, g) ends up with joints 4g..4g+3 and 16+4g..16+4g+3 of pixel li:
 // a running (max, first index) per slot over the wave's 16 pixel fragments, then a 16-lane butterfly over li, then
 // the four waves through LDS.  wimg = [fragment][chunk][lane][8 bf16] (hrnet_mi355.cpp: load_weights).
+template <int DT>
 __global__ __launch_bounds__(256) void head_mfma_kernel(const HeadArgs p) {
     __shared__ float red_v[4 * kMaxJoints];
     __shared__ int red_i[4 * kMaxJoints];
@@ -1093,7 +1137,7 @@ __global__ __launch_bounds__(256) void head_mfma_kernel(const HeadArgs p) {
             s16x8 x = {};
             if (k0 < p.c) x = *(const GLOBAL_AS s16x8 *)(row + k0);
 #pragma unroll
-            for (int f = 0; f < 2; ++f) acc[f] = mma<DT_BF16>(wimg[(f * kch + kc) * 64 + lane], x, acc[f]);
+            for (int f = 0; f < 2; ++f) acc[f] = mma<DT>(wimg[(f * kch + kc) * 64 + lane], x, acc[f]);
         }
 #pragma unroll
         for (int f = 0; f < 2; ++f)
@@ -1139,13 +1183,18 @@ hipError_t launch_head(int dtype, const HeadArgs &a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
     if (a.joints > kMaxJoints) return hipErrorInvalidValue;
     dim3 grid(a.slabs, a.n);
-    if (dtype == DT_BF16 && a.wimg && a.slab_px % 64 == 0) {
-        hipLaunchKernelGGL(head_mfma_kernel, grid, dim3(256), 0, s, a);
+    if (dtype != DT_F32 && a.wimg && a.slab_px % 64 == 0) {
+        if (dtype == DT_F16)
+            hipLaunchKernelGGL(head_mfma_kernel<DT_F16>, grid, dim3(256), 0, s, a);
+        else
+            hipLaunchKernelGGL(head_mfma_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
         return hipGetLastError();
     }
     const size_t shm = sizeof(float) * ((size_t)a.joints * a.c + 4 * kMaxJoints) + sizeof(int) * 4 * kMaxJoints;
     if (dtype == DT_BF16)
         hipLaunchKernelGGL(head_kernel<DT_BF16>, grid, dim3(256), shm, s, a);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(head_kernel<DT_F16>, grid, dim3(256), shm, s, a);
     else
         hipLaunchKernelGGL(head_kernel<DT_F32>, grid, dim3(256), shm, s, a);
     return hipGetLastError();
@@ -1264,6 +1313,8 @@ hipError_t launch_tap(int dtype, const TapArgs &a, hipStream_t s) {
     dim3 grid((unsigned)((total + 255) / 256));
     if (dtype == DT_BF16)
         hipLaunchKernelGGL(tap_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(tap_kernel<DT_F16>, grid, dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(tap_kernel<DT_F32>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
@@ -1294,6 +1345,8 @@ hipError_t launch_pad_check(int dtype, const PadCheckArgs &a, hipStream_t s) {
     const unsigned blocks = (unsigned)((a.rows + 255) / 256 < 4096 ? (a.rows + 255) / 256 : 4096);
     if (dtype == DT_BF16)
         hipLaunchKernelGGL(pad_check_kernel<DT_BF16>, dim3(blocks), dim3(256), 0, s, a);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(pad_check_kernel<DT_F16>, dim3(blocks), dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(pad_check_kernel<DT_F32>, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();

@@ -1,5 +1,5 @@
 // The stem as ONE kernel (round 4): conv1 (3 -> 64, 3x3 stride 2, BN, ReLU; models_/hrnet.py:79-80,158-160) computed into LDS and
-// conv2 (64 -> 64, 3x3 stride 2, BN, ReLU; :81-83,161-163) read from there -- bf16 mode, written for gfx950.
+// conv2 (64 -> 64, 3x3 stride 2, BN, ReLU; :81-83,161-163) read from there -- bf16 / fp16 mode, written for gfx950.
 //
 // Separately the two convolutions write and read back the largest tensor of the pass (64 channels at half resolution: 0.9 GB
 // at 256 crops of 384x288) and took 0.43 + 0.38 ms of a 23.6-ms pass, both HBM-bound; this kernel takes 0.34 ms.
@@ -27,6 +27,7 @@
 // every phase is a dependent chain (gather -> MFMA -> pack -> LDS write; LDS read -> MFMA) that two waves cannot cover.
 // profiles/EXPERIMENTS.md (round 4) has the steps that got it from 643 us to here and what each was worth.
 #include "kernels.h"
+#include "dt16.h"
 
 namespace hrn {
 
@@ -49,6 +50,7 @@ constexpr int SF_PATCH = SF_W1 + 4096;                 // two patch buffers
 constexpr int SF_LDS = SF_PATCH + 2 * kStemFusePatchBytes;
 static_assert(SF_LDS <= 160 * 1024, "LDS budget");
 
+template <int DT>
 __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const StemArgs st, const int ntile, const int tile0, char *smem) {
     constexpr int NF = 2, ROWB = 32, NCH = 18, CPP = 32, NT = 512;
     // everything the loop needs as scalars, once (no kernel-argument / descriptor load may be in flight while counted lgkmcnt
@@ -209,8 +211,8 @@ __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const S
                 const float x0 = flip ? pre[q][3] : pre[q][0], x1 = flip ? pre[q][2] : pre[q][1];
                 const float x2 = flip ? pre[q][1] : pre[q][2], x3 = flip ? pre[q][0] : pre[q][3];
                 unsigned lo2, hi2;
-                asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo2) : "v"(x0), "v"(x1));
-                asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi2) : "v"(x2), "v"(x3));
+                lo2 = H16<DT>::pk_asm(x0, x1);
+                hi2 = H16<DT>::pk_asm(x2, x3);
                 *(u32x2 *)(pb + (fd & 0xfffffu)) = u32x2{in ? lo2 : 0u, in ? hi2 : 0u};
             }
         }
@@ -270,7 +272,7 @@ __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const S
                 f32x4 acc[4];
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj)
-                    acc[jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w1r[jj]), __builtin_bit_cast(bf16x8, xf), b1r[jj], 0, 0, 0);
+                    acc[jj] = H16<DT>::mma(w1r[jj], xf, b1r[jj]);
                 // ReLU (clamp to [0, inf]) or, where conv2's padding is, exact zeros (clamp to [0, 0]); bf16 (nearest even, as
                 // stem_mfma_kernel); the lane owns channels 16 g .. 16 g + 15 of its pixel = its 32-byte sub-slot in region g
                 const float hi = ok ? INFINITY : 0.f;
@@ -281,7 +283,7 @@ __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const S
                     for (int h = 0; h < 2; ++h) {
                         // (the builtin, not asm: the compiler has to see this first read of the MFMA results to space it)
                         const float a0 = __builtin_amdgcn_fmed3f(acc[jj][2 * h], 0.f, hi), a1 = __builtin_amdgcn_fmed3f(acc[jj][2 * h + 1], 0.f, hi);
-                        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk[2 * jj + h]) : "v"(a0), "v"(a1));
+                        pk[2 * jj + h] = H16<DT>::pk_asm(a0, a1);
                     }
                 if (fd & (1u << 19)) {
                     char *d = sl + g * SF_REGION + ((awave + 8 * i) * 16 + li) * ROWB;
@@ -337,7 +339,7 @@ __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const S
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int j = 0; j < NF; ++j)
-                        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[c][j]), __builtin_bit_cast(bf16x8, xf[c & 3]), acc[j], 0, 0, 0);
+                        acc[j] = H16<DT>::mma(wf[c][j], xf[c & 3], acc[j]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #undef SF_READ
@@ -357,7 +359,7 @@ __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const S
                             float a0 = acc[j][2 * h] + bs[j][2 * h], a1 = acc[j][2 * h + 1] + bs[j][2 * h + 1];
                             asm("v_med3_f32 %0, %1, %2, %3" : "=v"(a0) : "v"(a0), "v"(lo_i), "v"(hi));
                             asm("v_med3_f32 %0, %1, %2, %3" : "=v"(a1) : "v"(a1), "v"(lo_i), "v"(hi));
-                            asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk2[2 * j + h]) : "v"(a0), "v"(a1));
+                            pk2[2 * j + h] = H16<DT>::pk_asm(a0, a1);
                         }
                     GLOBAL_AS unsigned short *o = out + (size_t)(q0 + tp) * cout + ch0 + g * 4 * NF;
                     *(GLOBAL_AS u32x4 *)o = u32x4{pk2[0], pk2[1], pk2[2], pk2[3]};
@@ -369,12 +371,13 @@ __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const S
 
 }  // namespace
 
+template <int DT>
 __global__ __launch_bounds__(512) void stem_fused_kernel(const S2Problem *__restrict__ probs, const int2 *__restrict__ map, const StemArgs stem) {
     extern __shared__ __attribute__((aligned(1024))) char smem_sf[];
     const int2 e = map[blockIdx.x];
     const int prob = __builtin_amdgcn_readfirstlane(e.x & 0xff), ntile = __builtin_amdgcn_readfirstlane(e.x >> 8);
     const int tile0 = __builtin_amdgcn_readfirstlane(e.y);
-    stemf_run((const GLOBAL_AS S2Problem *)(probs + prob), stem, ntile, tile0, smem_sf);
+    stemf_run<DT>((const GLOBAL_AS S2Problem *)(probs + prob), stem, ntile, tile0, smem_sf);
 }
 
 // the fused stem handles this geometry (conv2's output width + pad column, the crop width): its slab regions and patch buffers hold it
@@ -382,16 +385,22 @@ int stem_fused_fits(int wop, int w_in) {
     return w_in % 4 == 0 && s2_pair_pitch(wop) + 2 * wop <= kStemFuseRegionBytes / 32 && 21 * (w_in + 8) * 2 <= kStemFusePatchBytes;
 }
 
-hipError_t launch_stem_fused(const S2Problem *probs_dev, const void *map_dev, int nblocks, const StemArgs &stem, hipStream_t s) {
+template <int DT>
+static hipError_t launch_stem_fused_t(const S2Problem *probs_dev, const void *map_dev, int nblocks, const StemArgs &stem, hipStream_t s) {
     if (nblocks <= 0) return hipSuccess;
     static std::atomic<unsigned long long> lds_set{0};   // per device: kernels.h set_dynamic_lds
     {
-        const hipError_t e = set_dynamic_lds((const void *)stem_fused_kernel, SF_LDS, lds_set);
+        const hipError_t e = set_dynamic_lds((const void *)stem_fused_kernel<DT>, SF_LDS, lds_set);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(stem_fused_kernel, dim3(nblocks), dim3(512), SF_LDS, s, probs_dev, (const int2 *)map_dev, stem);
+    hipLaunchKernelGGL(stem_fused_kernel<DT>, dim3(nblocks), dim3(512), SF_LDS, s, probs_dev, (const int2 *)map_dev, stem);
     return hipGetLastError();
 }
 
-}  // namespace hrn
+// bf16 or fp16 elements (dt16.h): the same kernel, two instantiations
+hipError_t launch_stem_fused(int dtype, const S2Problem *probs_dev, const void *map_dev, int nblocks, const StemArgs &stem, hipStream_t s) {
+    return dtype == DT_F16 ? launch_stem_fused_t<DT_F16>(probs_dev, map_dev, nblocks, stem, s)
+                           : launch_stem_fused_t<DT_BF16>(probs_dev, map_dev, nblocks, stem, s);
+}
 
+}  // namespace hrn

@@ -61,6 +61,17 @@ class ShardedHRNet:
             self.net.load_state_dict(state_dict)
         if self.world > 1:
             blob = self.net.weight_blob_tensor()
+            # the blob moves byte for byte: a rank whose engine packs for another dtype (bf16 / fp16 / fp32 images differ in
+            # format, not only in size) must not adopt it -- every rank checks every other's (dtype, bytes) first, so all
+            # of them refuse together instead of leaving the source waiting in the broadcast
+            code = {"fp32": 0, "bf16": 1, "fp16": 2}.get(getattr(self.net, "dtype", None), -1)
+            mine = torch.tensor([code, blob.numel()], dtype=torch.int64, device=blob.device)
+            every = torch.empty((self.world, 2), dtype=torch.int64, device=blob.device)
+            self._all_gather(every, mine.view(1, 2))
+            every = every.cpu()
+            if not bool((every == every[src]).all()):
+                raise ValueError("ranks disagree on the packed-weight format (dtype code, blob bytes) per rank: %s -- every rank "
+                                 "needs the same model, resolution and dtype" % every.tolist())
             self._broadcast(blob, src)
             if self.rank != src:
                 self.net.adopt_weights()

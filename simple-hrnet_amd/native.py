@@ -18,7 +18,9 @@ import torch
 
 from . import _lib
 
-DTYPES = {"fp32": 0, "f32": 0, "float32": 0, torch.float32: 0, "bf16": 1, "bfloat16": 1, torch.bfloat16: 1}
+DTYPES = {"fp32": 0, "f32": 0, "float32": 0, torch.float32: 0, "bf16": 1, "bfloat16": 1, torch.bfloat16: 1,
+          "fp16": 2, "f16": 2, "float16": 2, "half": 2, torch.float16: 2}
+DTYPE_NAMES = {0: "fp32", 1: "bf16", 2: "fp16"}
 
 
 def _device_index(device) -> int:
@@ -35,7 +37,8 @@ class NativeHRNet:
 
     Parameters mirror ``HRNet(c, nof_joints)`` (models_/hrnet.py:75) plus what a static engine
     needs up front: input ``resolution`` (h, w), arithmetic ``dtype`` ('bf16' MFMA with fp32
-    accumulate, or 'fp32' exact-fp32 MFMA), and ``max_batch`` = crops per internal pass.
+    accumulate, 'fp16' -- the same plan and kernels with fp16 storage: 11 significant bits instead of 8 --,
+    or 'fp32' exact-fp32 MFMA), and ``max_batch`` = crops per internal pass.
     ``device=-1`` builds a plan-only handle (graph + weight packing on the host, no GPU): it cannot
     run -- there is no CPU compute path.
     """
@@ -43,7 +46,7 @@ class NativeHRNet:
     def __init__(self, c: int = 48, nof_joints: int = 17, resolution: Tuple[int, int] = (384, 288),
                  dtype: Union[str, torch.dtype] = "bf16", max_batch: int = 32, device=0, model_name: str = "HRNet"):
         if dtype not in DTYPES:
-            raise ValueError("dtype must be 'bf16' or 'fp32'")
+            raise ValueError("dtype must be 'bf16', 'fp16' or 'fp32'")
         if model_name in ("HRNet", "hrnet"):            # SimpleHRNet.py:109-112
             model = 0
         elif model_name in ("PoseResNet", "poseresnet", "ResNet", "resnet"):
@@ -53,7 +56,7 @@ class NativeHRNet:
         self.model_name = "HRNet" if model == 0 else "PoseResNet"
         self.c, self.nof_joints = int(c), int(nof_joints)
         self.resolution = (int(resolution[0]), int(resolution[1]))
-        self.dtype = "bf16" if DTYPES[dtype] == 1 else "fp32"
+        self.dtype = DTYPE_NAMES[DTYPES[dtype]]
         self.max_batch = int(max_batch)
         self.device_index = -1 if (isinstance(device, int) and device < 0) else _device_index(device)
         self._lib = _lib.load()

@@ -12,7 +12,8 @@ different, and why:
   ``cv2.resize(frame, (W, H), interpolation)`` does it (``:213-218``; ``interpolation`` = ``cv2.INTER_NEAREST`` 0 /
   ``INTER_LINEAR`` 1 / ``INTER_CUBIC`` 2, default cubic as in the reference, anything else raises) -- OpenCV's published generic
   8-bit arithmetic, NOT pinned against a cv2 build (cv2 is absent here; ``include/hrnet_mi355.h``: ``hrn_resize_frames``);
-* ``dtype`` picks the arithmetic mode of the engine (``"fp32"`` = parity mode, ``"bf16"`` = MFMA bf16);
+* ``dtype`` picks the arithmetic mode of the engine (``"fp32"`` = parity mode, ``"bf16"`` = MFMA bf16, ``"fp16"`` = the same
+  MFMA path with fp16 storage -- the counterpart of the reference's half-precision TensorRT export, ``--half``);
 * devices: ``'cuda:N'`` is that GPU.  ``'cuda'`` (all GPUs) and ``'cuda:1,2'`` (the listed ones) are, in a plain Python
   process, ONE engine per listed GPU driven from this process (``native.MultiDeviceHRNet``: the crop batch of a
   ``predict()`` call is split by index range, one host thread per GPU) -- what ``DataParallel`` gives the reference with
