@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the HRNet hot path (model call + decode, SimpleHRNet.py:281-308) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): person-crops/sec, HRNet-W48 384x288, batch 256 per GPU, bf16 MFMA with fp32
 accumulate, synthetic crops already resident in HBM, random-init (seeded) weights.  One "step" = one pass
@@ -12,7 +12,9 @@ per-step collective is the all-gather of 204 B/crop of joints.  `python bench.py
 ranks (re-executes itself under torch.distributed.run) when it was not started by a launcher; started BY a
 launcher (RANK / WORLD_SIZE in the environment) it is one of the ranks.
 
-Prints ONE JSON line on rank 0: the driver-contract fields plus
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the
+driver-contract fields; nothing else runs, so the run costs little beyond its steps.  --full adds, each after the timed
+steps and from runs of its own (the --no-* options leave single blocks out):
   roofline      dominant kernel (stage-3/4 BasicBlock 3x3 convs) against the dense bf16 MFMA peak, HIP-event timed
   parity        N=1: the first 32 crops of the TIMED batch against the CPU oracle (fp32 engine: identical coordinates;
                 bf16 engine: arg-max agreement and pixel histogram)
@@ -22,7 +24,7 @@ Prints ONE JSON line on rank 0: the driver-contract fields plus
                 against the cell the construction puts every joint's peak in
   config1_fp32  N=1: BASELINE configs[1] -- HRNet-W32 256x192, batch 64, fp32, against the fp32 MFMA peak
   fp32_w48_384x288  N=1: the headline shape in the parity mode (fp32), timed
-  prepath, pcie_inclusive   side measurements
+  prepath, pcie_inclusive, two_lanes   side measurements
 """
 from __future__ import annotations
 
@@ -58,6 +60,9 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--max-batch", type=int, default=int(os.environ.get("HRN_MAX_BATCH", "256")),
                     help="crops per internal pass (workspace size)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every side measurement and check (roofline, two_lanes, cpu_baseline, parity, clip, "
+                         "config1_fp32, fp32_w48_384x288, prepath, pcie_inclusive); the --no-* options below leave single ones out")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip cpu_baseline AND parity (both need the CPU oracle)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU budget of the cpu_baseline sample")
     ap.add_argument("--no-roofline", action="store_true")
@@ -692,6 +697,136 @@ def parity_measure(pkg, net, a, images, boxes, dev, cpu_out):
     return out
 
 
+def full_measure(pkg, net, a, images, boxes, boxes_np, dev, local, world, value, pts):
+    """--full, rank 0, after the timed steps: every side measurement and check of the benchmark, each from runs of its own.
+    Returns the blocks to add to the result line (none of them is `value`)."""
+    import numpy as np
+    import torch
+
+    out = {}
+    peak = PEAK_BF16_TFLOPS if a.dtype == "bf16" else PEAK_F32_TFLOPS
+    if not a.no_roofline and a.model_name == "HRNet":
+        # per-kernel HIP-event times of one internal pass, same stream as the launches
+        nb = min(a.max_batch, a.batch)
+        for _ in range(2):
+            conv_ms, other = net.profile_pass(images[:nb])
+        infos = net.conv_infos()
+        # dominant kernel = conv3x3_lds_kernel; graded subset = the stage-3/4 BasicBlock convs.  The k-th conv of
+        # every branch of a stage module is ONE grouped launch: count launches by (module, block, conv) key.
+        sub = [(i, ms) for i, ms in zip(infos, conv_ms)
+               if b".branches." in i.name and (i.name.startswith(b"stage3") or i.name.startswith(b"stage4"))]
+
+        def _group(name):
+            f = name.decode().split(".")     # stageX.M.branches.B.K.convN
+            return (f[0], f[1], f[4], f[5])
+
+        launches = len({_group(i.name) for i, _ in sub})
+        sub_flops = sum(i.flops for i, _ in sub) * nb
+        sub_ms = sum(ms for _, ms in sub)
+        ach = sub_flops / (sub_ms * 1e-3) / 1e12
+        # algorithmic HBM bytes of the same launches: input + output (+ residual) activations and the weights
+        esz = 2 if a.dtype == "bf16" else 4
+        sub_bytes = sum(((2 + i.has_residual) * i.cout * i.out_h * i.out_w * nb + 9 * i.cin * i.cout) * esz for i, _ in sub)
+        traffic, traffic_src = pmc_traffic(a, nb)
+        all_ms = sum(conv_ms) + sum(other.values())
+        out["roofline"] = {
+            "bound": "mfma",
+            "kernel": "conv3x3_lds_kernel: stage-3/4 BasicBlock 3x3 convs, %d convs in %d grouped launches"
+                      % (len(sub), launches),
+            "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4),
+            "traffic": traffic, "traffic_unit": "bytes per grouped launch", "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": round(sub_bytes / launches),
+            "flops_per_launch": round(sub_flops / launches / 1e9, 3), "flops_unit": "GFLOP (algorithmic, 2*MAC)",
+            "avg_launch_ms": round(sub_ms / launches, 4),
+            "timing": "HIP events on the launch stream around every kernel of one pass of %d crops" % nb,
+            "subset_share_of_pass_time": round(sub_ms / all_ms, 3),
+            "pass_ms": {"convs": round(sum(conv_ms), 3), **{k: round(v, 3) for k, v in other.items()}},
+            "source_hash": source_hash(),
+        }
+    # Side measurement, never `value`: the same step with TWO engines on this GPU, each on its own stream with half of the
+    # batch (native.MultiDeviceHRNet).  The launches of one engine fill the tails and
+    # drains of the other's: same kernels, same joints, twice the activation workspace.
+    if world == 1 and not a.no_two_lanes and a.model_name == "HRNet" and a.batch >= 4:
+        try:
+            native = importlib.import_module("simple-hrnet_amd.native")
+            two = native.MultiDeviceHRNet([local, local], a.c, 17, (a.height, a.width), a.dtype,
+                                          max_batch=min(a.max_batch, -(-a.batch // 2)), model_name=a.model_name).adopt_from(net)
+            for _ in range(2):
+                p2 = two.predict_crops(images, boxes)
+            torch.cuda.synchronize()
+            n2 = max(3, min(a.steps, 10))
+            t2 = time.perf_counter()
+            for _ in range(n2):
+                p2 = two.predict_crops(images, boxes)
+            torch.cuda.synchronize()
+            v2 = a.batch * n2 / (time.perf_counter() - t2)
+            out["two_lanes"] = {"crops_per_s": round(v2, 1), "vs_value": round(v2 / value, 4), "steps": n2,
+                                "same_joints_as_one_engine": bool(torch.equal(p2, pts)),
+                                "workspace_bytes_total": int(sum(e.workspace_bytes() for e in two.nets)),
+                                "note": "two engines on one GPU, %d crops each per step, on two streams" % (-(-a.batch // 2))}
+            two.close()
+        except Exception as e:   # a side measurement: never lose the main one to it
+            out["two_lanes"] = {"error": "%s: %s" % (type(e).__name__, e)}
+    cpu = None
+    tmpdir = tempfile.mkdtemp(prefix="hrn_bench_")
+    if world == 1 and not a.no_cpu_baseline and a.model_name == "HRNet":
+        k = min(PARITY_CROPS, a.batch)
+        spec = {"c": a.c, "h": a.height, "w": a.width, "budget_s": a.cpu_seconds, "crops": os.path.join(tmpdir, "crops.npy"),
+                "boxes": boxes_np[:k].tolist(), "out": os.path.join(tmpdir, "ref.npz"), "clip": None,
+                "emulate_bf16": a.dtype == "bf16" and a.model_name == "HRNet",
+                "peaked": None if a.no_peaked else {"n": a.batch, "seed": PEAKED_SEED, "idx": [i for i in PEAKED_IDX if i < a.batch]}}
+        np.save(spec["crops"], images[:k].cpu().numpy())
+        if not a.no_clip:
+            clip, dets = make_clip()
+            np.save(os.path.join(tmpdir, "frame0.npy"), clip[0])
+            spec["clip"] = {"frame": os.path.join(tmpdir, "frame0.npy"), "dets": dets[0, :, :4].tolist(), "out": os.path.join(tmpdir, "clip_ref.npz")}
+            del clip
+        cpu = _run_cpu_worker(spec, a.cpu_seconds)
+        if os.path.exists(spec["out"]):
+            try:
+                out["parity"] = parity_measure(pkg, net, a, images, boxes, dev, spec["out"])
+            except Exception as e:   # never lose the GPU number to the checker
+                out["parity"] = {"error": "%s: %s" % (type(e).__name__, e)}
+            if not a.no_peaked:
+                try:
+                    out["parity"]["peaked"] = peaked_measure(pkg, a, dev, spec["out"])
+                except Exception as e:
+                    out["parity"]["peaked"] = {"error": "%s: %s" % (type(e).__name__, e)}
+    if world == 1 and not a.no_clip and a.model_name == "HRNet":
+        try:
+            res, (clip, dets, gpu_pts) = clip_measure(pkg, net, None, 0, 1, (cpu or {}).get("clip"))
+            ref_path = os.path.join(tmpdir, "clip_ref.npz")
+            if os.path.exists(ref_path):   # frame 0 against the reference loop restated on the CPU (bf16 engine: agreement rate)
+                ref = np.load(ref_path)
+                h4 = net.resolution[0] // 4
+                res["frame0_boxes_identical_to_cpu_loop"] = bool(np.array_equal(net.preprocess_frame(clip[0], dets[0])[1], ref["boxes"]))
+                res["frame0_joints_agree_frac"] = round(float((np.abs(gpu_pts[0][..., :2] - ref["pts"][..., :2]).max(-1) <
+                                                               (ref["boxes"][:, 3] - ref["boxes"][:, 1]).reshape(-1, 1) / h4 * 0.5).mean()), 4)
+            out["clip"] = res
+        except Exception as e:
+            out["clip"] = {"error": "%s: %s" % (type(e).__name__, e)}
+    if world == 1 and not a.no_config1 and a.model_name == "HRNet":
+        try:
+            out["config1_fp32"] = config1_measure(pkg, dev)
+        except Exception as e:
+            out["config1_fp32"] = {"error": "%s: %s" % (type(e).__name__, e)}
+    if world == 1 and not a.no_fp32_w48 and a.model_name == "HRNet":
+        try:
+            out["fp32_w48_384x288"] = fp32_w48_measure(pkg, a, dev)
+        except Exception as e:
+            out["fp32_w48_384x288"] = {"error": "%s: %s" % (type(e).__name__, e)}
+    if world == 1 and not a.no_prepath:
+        out["prepath"] = prepath_measure(pkg, net, dev)
+        out["pcie_inclusive"] = pcie_measure(pkg, net, min(a.batch, a.max_batch), dev)
+    if cpu is not None:
+        cpu.pop("clip", None)
+        out["cpu_baseline"] = cpu
+    import shutil
+
+    shutil.rmtree(tmpdir, ignore_errors=True)
+    return out
+
+
 def self_launch(a):
     """`python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU over RCCL) and relay rank 0's line."""
     import socket
@@ -807,7 +942,7 @@ def main():
     boxes = torch.from_numpy(boxes_np).to(dev)
 
     # the timed path: ONE engine per GPU, ONE stream.  (Two engines sharing the GPU with half of the batch each measure +2.3 ... +3.3 %
-    # in same-box pairs -- the `two_lanes` side measurement below -- and are NOT the headline: launches that overlap on the GPU cannot be
+    # in same-box pairs -- the `two_lanes` side measurement of --full -- and are NOT the headline: launches that overlap on the GPU cannot be
     # timed one by one, so `roofline` and the rocprofv3 kernel statistics would no longer describe the timed path.  VERDICT r4 item 5.)
     def step():
         return eng.predict_crops_local_then_gather(images, boxes)
@@ -849,7 +984,6 @@ def main():
         crops_total = a.batch * world * a.steps
         value = crops_total / el
         flops = net.flops_per_crop()
-        peak = PEAK_BF16_TFLOPS if a.dtype == "bf16" else PEAK_F32_TFLOPS
         name = "HRNet-W%d" % a.c if a.model_name == "HRNet" else "PoseResNet-%d" % a.c
         out = {
             "metric": "person-crops/sec %s %dx%d (model forward + heat-map decode)" % (name, a.height, a.width),
@@ -875,125 +1009,8 @@ def main():
         }
         if dumped is not None:
             out["dumped_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
-        if not a.no_roofline and a.model_name == "HRNet":
-            # per-kernel HIP-event times of one internal pass, same stream as the launches
-            nb = min(a.max_batch, a.batch)
-            for _ in range(2):
-                conv_ms, other = net.profile_pass(images[:nb])
-            infos = net.conv_infos()
-            # dominant kernel = conv3x3_lds_kernel; graded subset = the stage-3/4 BasicBlock convs.  The k-th conv of
-            # every branch of a stage module is ONE grouped launch: count launches by (module, block, conv) key.
-            sub = [(i, ms) for i, ms in zip(infos, conv_ms)
-                   if b".branches." in i.name and (i.name.startswith(b"stage3") or i.name.startswith(b"stage4"))]
-
-            def _group(name):
-                f = name.decode().split(".")     # stageX.M.branches.B.K.convN
-                return (f[0], f[1], f[4], f[5])
-
-            launches = len({_group(i.name) for i, _ in sub})
-            sub_flops = sum(i.flops for i, _ in sub) * nb
-            sub_ms = sum(ms for _, ms in sub)
-            ach = sub_flops / (sub_ms * 1e-3) / 1e12
-            # algorithmic HBM bytes of the same launches: input + output (+ residual) activations and the weights
-            esz = 2 if a.dtype == "bf16" else 4
-            sub_bytes = sum(((2 + i.has_residual) * i.cout * i.out_h * i.out_w * nb + 9 * i.cin * i.cout) * esz for i, _ in sub)
-            traffic, traffic_src = pmc_traffic(a, nb)
-            all_ms = sum(conv_ms) + sum(other.values())
-            out["roofline"] = {
-                "bound": "mfma",
-                "kernel": "conv3x3_lds_kernel: stage-3/4 BasicBlock 3x3 convs, %d convs in %d grouped launches"
-                          % (len(sub), launches),
-                "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4),
-                "traffic": traffic, "traffic_unit": "bytes per grouped launch", "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": round(sub_bytes / launches),
-                "flops_per_launch": round(sub_flops / launches / 1e9, 3), "flops_unit": "GFLOP (algorithmic, 2*MAC)",
-                "avg_launch_ms": round(sub_ms / launches, 4),
-                "timing": "HIP events on the launch stream around every kernel of one pass of %d crops" % nb,
-                "subset_share_of_pass_time": round(sub_ms / all_ms, 3),
-                "pass_ms": {"convs": round(sum(conv_ms), 3), **{k: round(v, 3) for k, v in other.items()}},
-                "source_hash": source_hash(),
-            }
-        # Side measurement, never `value`: the same step with TWO engines on this GPU, each on its own stream with half of the
-        # batch (native.MultiDeviceHRNet).  The launches of one engine fill the tails and
-        # drains of the other's: same kernels, same joints, twice the activation workspace.
-        if world == 1 and not a.no_two_lanes and a.model_name == "HRNet" and a.batch >= 4:
-            try:
-                native = importlib.import_module("simple-hrnet_amd.native")
-                two = native.MultiDeviceHRNet([local, local], a.c, 17, (a.height, a.width), a.dtype,
-                                              max_batch=min(a.max_batch, -(-a.batch // 2)), model_name=a.model_name).adopt_from(net)
-                for _ in range(2):
-                    p2 = two.predict_crops(images, boxes)
-                torch.cuda.synchronize()
-                n2 = max(3, min(a.steps, 10))
-                t2 = time.perf_counter()
-                for _ in range(n2):
-                    p2 = two.predict_crops(images, boxes)
-                torch.cuda.synchronize()
-                v2 = a.batch * n2 / (time.perf_counter() - t2)
-                out["two_lanes"] = {"crops_per_s": round(v2, 1), "vs_value": round(v2 / value, 4), "steps": n2,
-                                    "same_joints_as_one_engine": bool(torch.equal(p2, pts)),
-                                    "workspace_bytes_total": int(sum(e.workspace_bytes() for e in two.nets)),
-                                    "note": "two engines on one GPU, %d crops each per step, on two streams" % (-(-a.batch // 2))}
-                two.close()
-            except Exception as e:   # a side measurement: never lose the main one to it
-                out["two_lanes"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        cpu = None
-        tmpdir = tempfile.mkdtemp(prefix="hrn_bench_")
-        if world == 1 and not a.no_cpu_baseline and a.model_name == "HRNet":
-            k = min(PARITY_CROPS, a.batch)
-            spec = {"c": a.c, "h": a.height, "w": a.width, "budget_s": a.cpu_seconds, "crops": os.path.join(tmpdir, "crops.npy"),
-                    "boxes": boxes_np[:k].tolist(), "out": os.path.join(tmpdir, "ref.npz"), "clip": None,
-                    "emulate_bf16": a.dtype == "bf16" and a.model_name == "HRNet",
-                    "peaked": None if a.no_peaked else {"n": a.batch, "seed": PEAKED_SEED, "idx": [i for i in PEAKED_IDX if i < a.batch]}}
-            np.save(spec["crops"], images[:k].cpu().numpy())
-            if not a.no_clip:
-                clip, dets = make_clip()
-                np.save(os.path.join(tmpdir, "frame0.npy"), clip[0])
-                spec["clip"] = {"frame": os.path.join(tmpdir, "frame0.npy"), "dets": dets[0, :, :4].tolist(), "out": os.path.join(tmpdir, "clip_ref.npz")}
-                del clip
-            cpu = _run_cpu_worker(spec, a.cpu_seconds)
-            if os.path.exists(spec["out"]):
-                try:
-                    out["parity"] = parity_measure(pkg, net, a, images, boxes, dev, spec["out"])
-                except Exception as e:   # never lose the GPU number to the checker
-                    out["parity"] = {"error": "%s: %s" % (type(e).__name__, e)}
-                if not a.no_peaked:
-                    try:
-                        out["parity"]["peaked"] = peaked_measure(pkg, a, dev, spec["out"])
-                    except Exception as e:
-                        out["parity"]["peaked"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not a.no_clip and a.model_name == "HRNet":
-            try:
-                res, (clip, dets, gpu_pts) = clip_measure(pkg, net, None, 0, 1, (cpu or {}).get("clip"))
-                ref_path = os.path.join(tmpdir, "clip_ref.npz")
-                if os.path.exists(ref_path):   # frame 0 against the reference loop restated on the CPU (bf16 engine: agreement rate)
-                    ref = np.load(ref_path)
-                    h4 = net.resolution[0] // 4
-                    res["frame0_boxes_identical_to_cpu_loop"] = bool(np.array_equal(net.preprocess_frame(clip[0], dets[0])[1], ref["boxes"]))
-                    res["frame0_joints_agree_frac"] = round(float((np.abs(gpu_pts[0][..., :2] - ref["pts"][..., :2]).max(-1) <
-                                                                   (ref["boxes"][:, 3] - ref["boxes"][:, 1]).reshape(-1, 1) / h4 * 0.5).mean()), 4)
-                out["clip"] = res
-            except Exception as e:
-                out["clip"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not a.no_config1 and a.model_name == "HRNet":
-            try:
-                out["config1_fp32"] = config1_measure(pkg, dev)
-            except Exception as e:
-                out["config1_fp32"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not a.no_fp32_w48 and a.model_name == "HRNet":
-            try:
-                out["fp32_w48_384x288"] = fp32_w48_measure(pkg, a, dev)
-            except Exception as e:
-                out["fp32_w48_384x288"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not a.no_prepath:
-            out["prepath"] = prepath_measure(pkg, net, dev)
-            out["pcie_inclusive"] = pcie_measure(pkg, net, min(a.batch, a.max_batch), dev)
-        if cpu is not None:
-            cpu.pop("clip", None)
-            out["cpu_baseline"] = cpu
-        import shutil
-
-        shutil.rmtree(tmpdir, ignore_errors=True)
+        if a.full:
+            out.update(full_measure(pkg, net, a, images, boxes, boxes_np, dev, local, world, value, pts))
     if dist:
         dist.barrier()
         dist.destroy_process_group()
