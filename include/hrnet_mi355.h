@@ -156,6 +156,34 @@ int hrn_resize_frames(hrn_handle h, const uint8_t *frames_dev, int n, int frame_
 int hrn_forward_flip_tta(hrn_handle h, const void *images_dev, int n, const int32_t *flip_pairs_host, int npairs,
                          int post_processing, float *heatmaps_dev, float *preds_dev, float *maxvals_dev, void *stream);
 
+/* Sub-pixel joint decoding (opt-in; hrn_forward keeps the integer arg-max of SimpleHRNet.py:297-308).  Each mode works on
+ * one raw heat-map H (h x w fp32, as the head writes it) and its integer arg-max (px, py) -- the first maximum of the
+ * unsmoothed map -- and moves it by an offset (ox, oy) in cells:
+ *   HRN_REFINE_NONE     no offset: bit-identical to hrn_forward.
+ *   HRN_REFINE_QUARTER  get_final_preds's rule (misc/utils.py:154-175; hrn_forward_flip_tta's post_processing): when
+ *                       1 < px < w-1 and 1 < py < h-1, ox = sign(H[py][px+1] - H[py][px-1]) * 0.25, oy likewise.
+ *   HRN_REFINE_DARK     distribution-aware decoding (DARK, Zhang et al., CVPR 2020), when 2 <= px <= w-3 and 2 <= py <= h-3:
+ *                       B = H blurred by the separable 11-tap Gaussian g[k] = exp(-k^2/8) / sum, k = -5..5 (sigma 2,
+ *                       cv2.getGaussianKernel(11, 0)), H = 0 outside the map; L = ln(max(B, 1e-10)); central differences
+ *                       dx = (L(1,0) - L(-1,0))/2, dxx = (L(2,0) - 2L(0,0) + L(-2,0))/4, dy / dyy likewise,
+ *                       dxy = (L(1,1) - L(1,-1) - L(-1,1) + L(-1,-1))/4; offset = -Hess^-1 (dx, dy), applied only when the
+ *                       Hessian is negative definite (dxx < 0, det > 0), each component clamped to [-1, 1].  DarkPose's
+ *                       max(H)/max(B) rescaling is left out: a positive factor does not change the derivatives of L.
+ *                       Evaluated in fp64.  (The definiteness test and the clamp are this library's: on near-flat maps an
+ *                       unguarded Newton step can be arbitrarily large.)
+ * Joints: y = (py + oy) / h * (y2 - y1) + y1, x likewise, in fp64 as hrn_forward; the confidence stays the raw maximum. */
+enum { HRN_REFINE_NONE = 0, HRN_REFINE_QUARTER = 1, HRN_REFINE_DARK = 2 };
+/* hrn_forward with a refine mode: the same arguments, pts_dev required unless refine is HRN_REFINE_NONE (which IS
+ * hrn_forward).  The head then writes heat-maps -- to heatmaps_dev when given, otherwise to a scratch buffer of max_batch
+ * crops the handle allocates on its first refined call without heatmaps_dev -- and the decode reads them; same launch count. */
+int hrn_forward_refined(hrn_handle h, const void *images_dev, int n, const void *boxes_dev, int box_dtype, int refine,
+                        float *pts_dev, float *heatmaps_dev, void *stream);
+/* The offset alone, in heat-map space (DARK on hrn_forward_flip_tta's averaged maps; synthetic maps in tests):
+ *   heatmaps_dev  (n,J,h,w) fp32 of this handle's shape
+ *   coords_dev    (n,J,2) (x, y), integer-valued on entry (e.g. hrn_forward_flip_tta with post_processing = 0), refined
+ *                 in place; an entry outside [0, w-1] x [0, h-1] is left as it is.  HRN_REFINE_NONE changes nothing. */
+int hrn_refine_coords(hrn_handle h, const float *heatmaps_dev, int n, int refine, float *coords_dev, void *stream);
+
 /* Greedy IoU non-maximum suppression -- the reference's only native component:
  * `void _nms(int *keep_out, int *num_out, const float *boxes_host, int boxes_num, int boxes_dim, float thresh,
  * int device_id)` (misc/nms/gpu_nms.hpp; kernel misc/nms/nms_kernel.cu:33-77, caller misc/nms/gpu_nms.pyx:19-34).

@@ -19,10 +19,11 @@ LIB_PATH = os.path.join(_HERE, "libhrnet_mi355.so")
 if os.environ.get("HRN_LIB_TAG"):   # A/B runs of compile-time variants (tools/mkvariant.sh builds libhrnet_mi355_<tag>.so beforehand)
     LIB_PATH = LIB_PATH.replace(".so", "_%s.so" % os.environ["HRN_LIB_TAG"])
 SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "conv3x3_f32.hip", "bottleneck_chain.hip", "prepath.hip", "nms.hip", "postproc.cpp", "hrnet_mi355.cpp",
+           "refine.hip",   # sub-pixel joint decoding (HRN_REFINE_QUARTER / _DARK)
            # fp16 instantiations of the three hand-scheduled kernel families (bodies shared through conv3x3_lds.inc / conv_s2.inc /
            # bottleneck_chain.inc): translation units of their own, so that each bf16 file still compiles to exactly its kernel set
            "conv3x3_lds_f16.hip", "conv_s2_f16.hip", "bottleneck_chain_f16.hip"]
-HEADERS = [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "dt16.h"), os.path.join(CSRC, "conv3x3_n96.inc"), os.path.join(CSRC, "conv3x3_lds.inc"),
+HEADERS = [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "dt16.h"), os.path.join(CSRC, "argmax.h"), os.path.join(CSRC, "conv3x3_n96.inc"), os.path.join(CSRC, "conv3x3_lds.inc"),
            os.path.join(CSRC, "conv_s2.inc"), os.path.join(CSRC, "bottleneck_chain.inc"), os.path.join(INCLUDE, "hrnet_mi355.h")]
 MAX_BUILD_WORKERS = 16   # compiler processes at once (a shared build box gives a job 16 CPUs, whatever os.cpu_count() says)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-result", "-Wno-inline-asm"]
@@ -186,6 +187,8 @@ SYMBOLS = {
     "hrn_resize_frames": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
     "hrn_preprocess_frame": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
     "hrn_forward_flip_tta": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
+    "hrn_forward_refined": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    "hrn_refine_coords": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),
     "hrn_nms": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int]),
     "hrn_nms_release": (ctypes.c_int, [ctypes.c_int]),
     "hrn_nms_last_error": (ctypes.c_char_p, []),

@@ -7,7 +7,7 @@
     };
 
     bool run_pass(const float *images, int nb, const void *boxes, int box_dtype, float *pts, float *heatmaps,
-                  hipStream_t s, Timing *tm, int flip = 0, const TapReq *tap = nullptr) {
+                  hipStream_t s, Timing *tm, int flip = 0, const TapReq *tap = nullptr, int refine = RF_NONE) {
         if (tm && !hip_ok(hipEventRecord(tm->ev[0], s), "hipEventRecord")) return false;
         // the fused stem writes conv2's output only: a call that taps "stem" (ops[0]'s tensor) takes the two launches
         const bool fused_stem = stem_fuse && !(tap && tap->op == 0);
@@ -19,7 +19,7 @@
             if (fused_stem && oi == 0)
                 e = exec_stem_fused(images, nb, s, flip);
             else if (!(fused_stem && (int)oi == stem_conv2_op))
-                e = exec_op(ops[oi], rev, images, nb, boxes, box_dtype, pts, heatmaps, s, flip);
+                e = exec_op(ops[oi], rev, images, nb, boxes, box_dtype, pts, heatmaps, s, flip, refine);
             if (!hip_ok(e, "kernel launch")) return false;
             if (tap && tap->op == (int)oi) {  // debug tap: the tensor this launch completed, as (ncrops, C, H, W) fp32
                 const Tensor &t = tensors[tap->tensor];
@@ -61,7 +61,7 @@
     }
 
     hipError_t exec_op(const Op &op, bool rev, const float *images, int nb, const void *boxes, int box_dtype, float *pts,
-                       float *heatmaps, hipStream_t s, int flip) {
+                       float *heatmaps, hipStream_t s, int flip, int refine) {
         hipError_t e = hipSuccess;
         switch (op.kind) {
         case OP_STEM: {
@@ -162,7 +162,7 @@
             S2Group &g = s2groups[op.idx];
             if (!s2_active(g, nb)) {  // too few tiles for the slab kernel: the same convolutions on the generic kernel
                 for (const Op &f : g.fallback) {
-                    e = exec_op(f, rev, images, nb, boxes, box_dtype, pts, heatmaps, s, flip);
+                    e = exec_op(f, rev, images, nb, boxes, box_dtype, pts, heatmaps, s, flip, refine);
                     if (e != hipSuccess) break;
                 }
                 break;
@@ -249,6 +249,14 @@
         case OP_DECODE: {
             if (!pts) break;
             const Tensor &t = tensors[head_in_t];
+            if (refine != RF_NONE) {   // sub-pixel decode: reads the heat-maps the head just wrote (hrn_forward_refined)
+                RefineArgs r;
+                r.part_val = part_val, r.part_idx = part_idx, r.heatmaps = heatmaps, r.boxes = boxes;
+                r.box_is_float = box_dtype == HRN_BOX_F32, r.pts = pts, r.coords = nullptr;
+                r.n = nb, r.joints = joints, r.h = t.h, r.w = t.w, r.slabs = head_slabs_for(nb), r.mode = refine;
+                e = heatmaps ? launch_refine_decode(r, s) : hipErrorInvalidValue;
+                break;
+            }
             DecodeArgs a;
             a.part_val = part_val, a.part_idx = part_idx, a.boxes = boxes;
             a.box_is_float = box_dtype == HRN_BOX_F32, a.pts = pts;

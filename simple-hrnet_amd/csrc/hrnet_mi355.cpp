@@ -373,6 +373,66 @@ int hrn_forward_flip_tta(hrn_handle h, const void *images_dev, int n, const int3
     return scope.leave() ? 0 : 6;
 }
 
+// Sub-pixel joint decoding (refine.hip): hrn_forward's passes with the head writing heat-maps -- the caller's, or the
+// handle's flip-TTA scratch (max_batch maps, allocated on first use) -- and OP_DECODE launching the refined decode.
+int hrn_forward_refined(hrn_handle h, const void *images_dev, int n, const void *boxes_dev, int box_dtype, int refine,
+                        float *pts_dev, float *heatmaps_dev, void *stream) {
+    if (!h) return 1;
+    if (refine != HRN_REFINE_NONE && refine != HRN_REFINE_QUARTER && refine != HRN_REFINE_DARK) {
+        h->err = "refine must be HRN_REFINE_NONE, HRN_REFINE_QUARTER or HRN_REFINE_DARK";
+        return 7;
+    }
+    if (refine == HRN_REFINE_NONE) return hrn_forward(h, images_dev, n, boxes_dev, box_dtype, pts_dev, heatmaps_dev, stream);
+    if (!h->check_forward_args(images_dev, n, boxes_dev, pts_dev, heatmaps_dev)) return 7;
+    if (!pts_dev) {
+        h->err = "hrn_forward_refined: a refine mode needs pts (it refines the joint coordinates)";
+        return 7;
+    }
+    if (n == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    const int hm = (h->H / 4) * (h->W / 4);
+    if (!heatmaps_dev && !h->tta_hm &&
+        !h->hip_ok(hipMalloc((void **)&h->tta_hm, (size_t)h->max_batch * h->joints * hm * sizeof(float)), "hipMalloc(refine heat-maps)"))
+        return 6;
+    PassScope scope(h, (hipStream_t)stream);
+    if (!scope.entered) return 6;
+    for (int off = 0; off < n; off += h->max_batch) {
+        const int nb = n - off < h->max_batch ? n - off : h->max_batch;
+        const float *img = (const float *)images_dev + (size_t)off * 3 * h->H * h->W;
+        const void *bx = (const char *)boxes_dev + (size_t)off * 16;
+        float *p = pts_dev + (size_t)off * h->joints * 3;
+        float *hp = heatmaps_dev ? heatmaps_dev + (size_t)off * h->joints * hm : h->tta_hm;
+        if (!h->run_pass(img, nb, bx, box_dtype, p, hp, (hipStream_t)stream, nullptr, 0, nullptr, refine)) return 8;
+    }
+    return scope.leave() ? 0 : 6;
+}
+
+int hrn_refine_coords(hrn_handle h, const float *heatmaps_dev, int n, int refine, float *coords_dev, void *stream) {
+    if (!h) return 1;
+    if (refine != HRN_REFINE_NONE && refine != HRN_REFINE_QUARTER && refine != HRN_REFINE_DARK) {
+        h->err = "refine must be HRN_REFINE_NONE, HRN_REFINE_QUARTER or HRN_REFINE_DARK";
+        return 7;
+    }
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (n < 0 || (n > 0 && (!heatmaps_dev || !coords_dev))) {
+        h->err = "hrn_refine_coords: bad heatmaps / coords / n";
+        return 7;
+    }
+    if (n == 0 || refine == HRN_REFINE_NONE) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    RefineArgs a;
+    a.part_val = nullptr, a.part_idx = nullptr, a.heatmaps = heatmaps_dev, a.boxes = nullptr, a.box_is_float = 0;
+    a.pts = nullptr, a.coords = coords_dev;
+    a.n = n, a.joints = h->joints, a.h = h->H / 4, a.w = h->W / 4, a.slabs = 0, a.mode = refine;
+    PassScope scope(h, (hipStream_t)stream);
+    if (!scope.entered) return 6;
+    if (!h->hip_ok(launch_refine_coords(a, (hipStream_t)stream), "refine launch")) return 8;
+    return scope.leave() ? 0 : 6;
+}
+
 // SimpleHRNet.py:236-278.  The box arithmetic is Python's, restated in double: round() is round-half-even on a
 // float, `//` on non-negative ints is C's `/`, int(round(x)) = nearbyint under the default rounding mode.
 int hrn_preprocess_frame(hrn_handle h, const uint8_t *frame_dev, int frame_h, int frame_w, const float *dets_host,

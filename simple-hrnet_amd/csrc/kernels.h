@@ -265,6 +265,22 @@ struct DecodeArgs {        // SimpleHRNet.py:297-308
     int n, joints, h, w, slabs;
 };
 
+// Sub-pixel joint decoding (refine.hip): the integer arg-max moved by a quarter cell towards the higher neighbour
+// (get_final_preds) or by DARK's Newton step on the log of the Gaussian-blurred map (include/hrnet_mi355.h: HRN_REFINE_*)
+enum { RF_NONE = 0, RF_QUARTER = 1, RF_DARK = 2 };   // = HRN_REFINE_NONE / _QUARTER / _DARK
+struct RefineArgs {
+    const float *part_val;  // decode form: the head's slab candidates, merged as decode_kernel merges them
+    const int *part_idx;
+    const float *heatmaps;  // (n,joints,h,w) fp32, as the head wrote them
+    const void *boxes;      // decode form: (n,4) int32 or fp32
+    int box_is_float;
+    float *pts;             // decode form: (n,joints,3) (y, x, confidence)
+    float *coords;          // coords form: (n,joints,2) (x, y) in heat-map cells, integer-valued in, refined in place
+    int n, joints, h, w, slabs, mode;
+};
+hipError_t launch_refine_decode(const RefineArgs &a, hipStream_t s);
+hipError_t launch_refine_coords(const RefineArgs &a, hipStream_t s);
+
 struct TtaArgs {           // flip-TTA combine + get_max_preds + quarter-pixel refinement (misc/utils.py:19-29, 125-175)
     float *hm;             // (n,joints,h,w): plain pass in, average out
     const float *hm_flipped;  // the mirrored crops' heat-maps

@@ -10,6 +10,7 @@
 //   head_kernel         final 1x1 conv + bias, optional heat-map write-out, per-slab arg-max.
 //   decode_kernel       arg-max merge (first maximum wins) + box scaling in fp64, SimpleHRNet.py:297-308.
 #include "kernels.h"
+#include "argmax.h"
 #include "dt16.h"
 #include <stdlib.h>
 
@@ -997,17 +998,7 @@ hipError_t launch_fuse_group(int dtype, FuseGroupArgs &g, hipStream_t s) {
 // heat-maps, and leaves one (max, first index) candidate per joint.
 constexpr int kMaxJoints = 32;
 
-// Arg-max order of np.argmax / torch.max (SimpleHRNet.py:300): the first maximum wins and a NaN is a maximum (numpy
-// returns the index of the first NaN).  `kNoIdx` marks "nothing seen yet": any real candidate beats it, so a map of
-// -inf everywhere decodes to index 0 like numpy, not to the sentinel.
-constexpr int kNoIdx = 0x7fffffff;
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) {
-    const bool vn = v != v, bn = bv != bv;
-    if (vn != bn) return vn;
-    return v > bv || ((v == bv || vn) && i < bi);
-}
-// scan step for candidates visited in increasing index order
-__device__ __forceinline__ bool takes(float v, float bv, int bi) { return v > bv || bi == kNoIdx || (v != v && bv == bv); }
+// (arg-max order: kNoIdx / better / takes, argmax.h)
 
 template <int DT>
 __global__ __launch_bounds__(256) void head_kernel(const HeadArgs p) {

@@ -21,6 +21,15 @@ from . import _lib
 DTYPES = {"fp32": 0, "f32": 0, "float32": 0, torch.float32: 0, "bf16": 1, "bfloat16": 1, torch.bfloat16: 1,
           "fp16": 2, "f16": 2, "float16": 2, "half": 2, torch.float16: 2}
 DTYPE_NAMES = {0: "fp32", 1: "bf16", 2: "fp16"}
+# sub-pixel joint decoding (include/hrnet_mi355.h: HRN_REFINE_*): None = the integer arg-max of SimpleHRNet.py:297-308
+REFINE_MODES = {None: 0, "quarter": 1, "dark": 2}
+
+
+def refine_code(refine) -> int:
+    """HRN_REFINE_* of a ``refine`` argument: None, "quarter" or "dark"; anything else raises ValueError"""
+    if not (refine is None or isinstance(refine, str)) or refine not in REFINE_MODES:
+        raise ValueError("refine must be None, 'quarter' or 'dark', got %r" % (refine,))
+    return REFINE_MODES[refine]
 
 
 def _device_index(device) -> int:
@@ -182,10 +191,13 @@ class NativeHRNet:
 
     forward = __call__
 
-    def predict_crops(self, images: torch.Tensor, boxes, return_heatmaps: bool = False):
+    def predict_crops(self, images: torch.Tensor, boxes, return_heatmaps: bool = False, refine: Optional[str] = None):
         """Model call + decode (SimpleHRNet.py:281-308): returns ``pts`` (n,J,3) fp32 CUDA tensor of
         ``(y, x, confidence)``; with ``return_heatmaps`` also the (n,J,H/4,W/4) heat-maps.
-        ``boxes``: (n,4) ``[x1,y1,x2,y2]`` int32 (multi-person path) or float32 (single-person)."""
+        ``boxes``: (n,4) ``[x1,y1,x2,y2]`` int32 (multi-person path) or float32 (single-person).
+        ``refine``: None = the integer arg-max; ``"quarter"`` = a quarter cell towards the higher neighbour
+        (get_final_preds); ``"dark"`` = DARK's sub-pixel decoding (include/hrnet_mi355.h: hrn_forward_refined)."""
+        mode = refine_code(refine)
         x = self._images_ptr(images)
         n = x.shape[0]
         b = boxes if isinstance(boxes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(boxes))
@@ -200,14 +212,19 @@ class NativeHRNet:
         pts = torch.empty((n, self.nof_joints, 3), dtype=torch.float32, device=x.device)
         hm = torch.empty((n, self.nof_joints, h // 4, w // 4), dtype=torch.float32,
                          device=x.device) if return_heatmaps else None
-        if n:
+        if n and mode == 0:
             with torch.cuda.device(self.device_index):
                 self._check(self._lib.hrn_forward(self._h, x.data_ptr(), n, b.data_ptr(), box_dtype, pts.data_ptr(),
                                                   hm.data_ptr() if hm is not None else None, self._stream()),
                             "hrn_forward")
+        elif n:
+            with torch.cuda.device(self.device_index):
+                self._check(self._lib.hrn_forward_refined(self._h, x.data_ptr(), n, b.data_ptr(), box_dtype, mode, pts.data_ptr(),
+                                                          hm.data_ptr() if hm is not None else None, self._stream()),
+                            "hrn_forward_refined")
         return (hm, pts) if return_heatmaps else pts
 
-    def predict_stream(self, batches, return_heatmaps: bool = False):
+    def predict_stream(self, batches, return_heatmaps: bool = False, refine: Optional[str] = None):
         """Model call + decode for a sequence of HOST-resident batches with the uploads hidden behind the compute:
         batch k+1 crosses PCIe on a copy stream (two device staging buffers) while batch k runs on the current stream.
         ``batches``: iterable of ``(images, boxes (n,4))`` with ``n <= max_batch``; ``images`` is a HOST tensor (pinned memory for
@@ -216,7 +233,8 @@ class NativeHRNet:
         leaves before ``cvtColor`` / ``ToTensor`` / ``Normalize``): a quarter of the bytes over PCIe (85 MB instead of 340 MB per
         256 crops of 384x288), the colour flip and the normalisation then run on the GPU (``hrn_resize_frames`` at identity size:
         the reference transform's float32 arithmetic).  Yields, per batch, what ``predict_crops`` returns (results of batch k
-        are ready on the current stream; read them after a synchronize or through ``.cpu()``)."""
+        are ready on the current stream; read them after a synchronize or through ``.cpu()``).  ``refine``: as in ``predict_crops``."""
+        refine_code(refine)
         dev = self.torch_device
         compute = torch.cuda.current_stream(dev)
         copy = torch.cuda.Stream(dev)
@@ -271,18 +289,22 @@ class NativeHRNet:
                 x = self.resize_frames(stage[slot][:n], 0, out=norm[slot])
             else:
                 x = stage[slot][:n]
-            out = self.predict_crops(x, boxes, return_heatmaps=return_heatmaps)
+            out = self.predict_crops(x, boxes, return_heatmaps=return_heatmaps, refine=refine)
             consumed[slot] = torch.cuda.Event()
             consumed[slot].record(compute)
             yield out
             k += 1
 
     # -- introspection --------------------------------------------------------------------------
-    def predict_flip_tta(self, images: torch.Tensor, flip_pairs, post_processing: bool = True):
+    def predict_flip_tta(self, images: torch.Tensor, flip_pairs, post_processing: Union[bool, str] = True):
         """Flip test-time augmentation + evaluation decode (``testing/Test.py:132-140``, ``misc/utils.py:9-29, 125-175``):
         returns ``(heatmaps (n,J,h,w) averaged over the crop and its mirror image, preds (n,J,2) = (x, y) in heat-map
         pixels with the quarter-pixel refinement, maxvals (n,J,1))`` -- what ``get_final_preds`` works on before its
-        inverse affine."""
+        inverse affine.  ``post_processing="dark"``: no quarter-pixel step; DARK's offset on the averaged maps instead
+        (``refine_coords``), as DarkPose decodes its flip-averaged maps."""
+        dark = isinstance(post_processing, str)
+        if dark and post_processing != "dark":
+            raise ValueError("post_processing must be True, False or 'dark', got %r" % (post_processing,))
         x = self._images_ptr(images)
         n = x.shape[0]
         fp = np.ascontiguousarray(np.asarray(flip_pairs, dtype=np.int32).reshape(-1, 2))
@@ -293,9 +315,32 @@ class NativeHRNet:
         if n:
             with torch.cuda.device(self.device_index):
                 self._check(self._lib.hrn_forward_flip_tta(self._h, x.data_ptr(), n, fp.ctypes.data, len(fp),
-                                                           1 if post_processing else 0, hm.data_ptr(), preds.data_ptr(),
-                                                           maxvals.data_ptr(), self._stream()), "hrn_forward_flip_tta")
+                                                           1 if post_processing and not dark else 0, hm.data_ptr(),
+                                                           preds.data_ptr(), maxvals.data_ptr(), self._stream()), "hrn_forward_flip_tta")
+                if dark:
+                    self._check(self._lib.hrn_refine_coords(self._h, hm.data_ptr(), n, REFINE_MODES["dark"], preds.data_ptr(),
+                                                            self._stream()), "hrn_refine_coords")
         return hm, preds, maxvals
+
+    def refine_coords(self, heatmaps, coords, mode: Optional[str]) -> torch.Tensor:
+        """The sub-pixel offset alone, in heat-map space: ``heatmaps`` (n,J,H/4,W/4) and integer-valued ``coords`` (n,J,2) =
+        (x, y) in cells (e.g. ``predict_flip_tta(..., post_processing=False)``'s preds) -> the refined coordinates as a new
+        (n,J,2) float32 tensor on this engine's GPU (include/hrnet_mi355.h: hrn_refine_coords).  ``mode``: "quarter", "dark"
+        or None (a copy)."""
+        code = refine_code(mode)
+        h, w = self.resolution
+        dev = self.torch_device
+        hm = torch.as_tensor(heatmaps).to(dev, torch.float32).contiguous()
+        out = torch.as_tensor(coords).to(dev, torch.float32).clone().contiguous()
+        n = int(hm.shape[0]) if hm.dim() == 4 else -1
+        if tuple(hm.shape) != (n, self.nof_joints, h // 4, w // 4) or tuple(out.shape) != (n, self.nof_joints, 2):
+            raise ValueError("heatmaps must be (n,%d,%d,%d) and coords (n,%d,2), got %s and %s"
+                             % (self.nof_joints, h // 4, w // 4, self.nof_joints, tuple(hm.shape), tuple(out.shape)))
+        if n and code:
+            with torch.cuda.device(self.device_index):
+                self._check(self._lib.hrn_refine_coords(self._h, hm.data_ptr(), n, code, out.data_ptr(), self._stream()),
+                            "hrn_refine_coords")
+        return out
 
     def preprocess_frame(self, frame: torch.Tensor, detections, variant: str = "pad") -> Tuple[torch.Tensor, np.ndarray, torch.Tensor]:
         """The crop pre-path of ``SimpleHRNet.predict`` for one frame (``SimpleHRNet.py:236-278``) on the GPU.
@@ -363,11 +408,12 @@ class NativeHRNet:
             self._check(rc, "hrn_resize_frames")
         return images
 
-    def predict_frame(self, frame, detections, return_heatmaps: bool = False, variant: str = "pad"):
+    def predict_frame(self, frame, detections, return_heatmaps: bool = False, variant: str = "pad", refine: Optional[str] = None):
         """pre-path + model + decode for one frame: what ``SimpleHRNet._predict_single`` does after the detector.
-        Returns ``(boxes (P,4) int32 numpy, pts (P,J,3) on the GPU[, heatmaps])``."""
+        Returns ``(boxes (P,4) int32 numpy, pts (P,J,3) on the GPU[, heatmaps])``.  ``refine``: as in ``predict_crops``."""
+        refine_code(refine)
         images, boxes, boxes_dev = self.preprocess_frame(frame, detections, variant)
-        out = self.predict_crops(images, boxes_dev, return_heatmaps=return_heatmaps)
+        out = self.predict_crops(images, boxes_dev, return_heatmaps=return_heatmaps, refine=refine)
         if return_heatmaps:
             return boxes, out[1], out[0]
         return boxes, out
@@ -572,15 +618,17 @@ class MultiDeviceHRNet:
         """single-person pre-path (``NativeHRNet.resize_frames``) on the first device; ``predict_crops`` shards the result"""
         return self.nets[0].resize_frames(frames, interpolation)
 
-    def predict_crops(self, images: torch.Tensor, boxes, return_heatmaps: bool = False):
+    def predict_crops(self, images: torch.Tensor, boxes, return_heatmaps: bool = False, refine: Optional[str] = None):
+        refine_code(refine)
+        kw = {} if refine is None else {"refine": refine}   # None: every engine is called as without the option
         n = int(images.shape[0])
         b = boxes if isinstance(boxes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(boxes))
         if n == 0:
-            return self.nets[0].predict_crops(images, b, return_heatmaps=return_heatmaps)
+            return self.nets[0].predict_crops(images, b, return_heatmaps=return_heatmaps, **kw)
 
         def work(k, net, lo, hi):
             x = images[lo:hi].to(net.torch_device, non_blocking=True)
-            out = net.predict_crops(x, b[lo:hi], return_heatmaps=return_heatmaps)
+            out = net.predict_crops(x, b[lo:hi], return_heatmaps=return_heatmaps, **kw)
             return out if return_heatmaps else (out,)
 
         outs = self._run(n, work)
@@ -616,17 +664,19 @@ class MultiDeviceHRNet:
         return (torch.cat([o[0] for o in outs], 0), np.concatenate([b for b in boxes_np if b is not None], 0),
                 torch.cat([o[1] for o in outs], 0))
 
-    def predict_frame(self, frame, detections, return_heatmaps: bool = False, variant: str = "pad"):
+    def predict_frame(self, frame, detections, return_heatmaps: bool = False, variant: str = "pad", refine: Optional[str] = None):
+        refine_code(refine)
+        kw = {} if refine is None else {"refine": refine}
         dets = np.ascontiguousarray(np.asarray(detections.cpu() if isinstance(detections, torch.Tensor) else detections,
                                                dtype=np.float32))
         if len(dets) == 0:
-            return self.nets[0].predict_frame(frame, dets, return_heatmaps=return_heatmaps, variant=variant)
+            return self.nets[0].predict_frame(frame, dets, return_heatmaps=return_heatmaps, variant=variant, **kw)
         if not isinstance(frame, torch.Tensor):
             frame = torch.from_numpy(np.ascontiguousarray(frame))
         boxes_np = [None] * len(self.nets)
 
         def work(k, net, lo, hi):
-            out = net.predict_frame(frame, dets[lo:hi], return_heatmaps=return_heatmaps, variant=variant)
+            out = net.predict_frame(frame, dets[lo:hi], return_heatmaps=return_heatmaps, variant=variant, **kw)
             boxes_np[k] = out[0]
             return tuple(out[1:])
 

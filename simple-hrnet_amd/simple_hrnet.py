@@ -14,6 +14,9 @@ different, and why:
   8-bit arithmetic, NOT pinned against a cv2 build (cv2 is absent here; ``include/hrnet_mi355.h``: ``hrn_resize_frames``);
 * ``dtype`` picks the arithmetic mode of the engine (``"fp32"`` = parity mode, ``"bf16"`` = MFMA bf16, ``"fp16"`` = the same
   MFMA path with fp16 storage -- the counterpart of the reference's half-precision TensorRT export, ``--half``);
+* ``refine`` (opt-in, default None = the reference's integer arg-max): ``"quarter"`` moves every joint a quarter heat-map cell
+  towards the higher neighbour (the reference's ``get_final_preds`` step), ``"dark"`` decodes it to sub-cell precision with
+  DARK (``include/hrnet_mi355.h``: ``HRN_REFINE_*``); every ``predict()`` path applies it;
 * devices: ``'cuda:N'`` is that GPU.  ``'cuda'`` (all GPUs) and ``'cuda:1,2'`` (the listed ones) are, in a plain Python
   process, ONE engine per listed GPU driven from this process (``native.MultiDeviceHRNet``: the crop batch of a
   ``predict()`` call is split by index range, one host thread per GPU) -- what ``DataParallel`` gives the reference with
@@ -28,7 +31,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .native import MultiDeviceHRNet, NativeHRNet
+from .native import MultiDeviceHRNet, NativeHRNet, refine_code
 
 _MEAN = (0.485, 0.456, 0.406)   # SimpleHRNet.py:171
 _STD = (0.229, 0.224, 0.225)
@@ -130,7 +133,9 @@ class SimpleHRNet:
     def __init__(self, c, nof_joints, checkpoint_path, model_name="HRNet", resolution=(384, 288), interpolation=None,
                  multiperson=True, return_heatmaps=False, return_bounding_boxes=False, max_batch_size=32,
                  yolo_version="v3", yolo_model_def=None, yolo_class_path=None, yolo_weights_path=None, device=None,
-                 enable_tensorrt=False, *, detector=None, dtype="fp32"):
+                 enable_tensorrt=False, *, detector=None, dtype="fp32", refine=None):
+        refine_code(refine)   # (raises ValueError before any engine is built)
+        self.refine = refine
         self.c, self.nof_joints, self.checkpoint_path = c, nof_joints, checkpoint_path
         self.model_name, self.resolution = model_name, tuple(resolution)
         self.interpolation = 2 if interpolation is None else int(interpolation)   # cv2.INTER_CUBIC (SimpleHRNet.py:27)
@@ -186,6 +191,10 @@ class SimpleHRNet:
         std = torch.tensor(_STD, dtype=torch.float32, device=self.device).view(1, 3, 1, 1)
         return ((x - mean) / std).contiguous()
 
+    def _refine_kw(self):
+        """the engine's ``refine`` argument; None: the engine is called exactly as without the option"""
+        return {} if self.refine is None else {"refine": self.refine}
+
     def _hm_shape(self, n):
         return (n, self.nof_joints, self.resolution[0] // 4, self.resolution[1] // 4)
 
@@ -194,14 +203,14 @@ class SimpleHRNet:
         if not self.multiperson:
             images = self._normalise(image)
             boxes = np.asarray([[0, 0, image.shape[1], image.shape[0]]], dtype=np.float32)
-            hm, pts = self.model.predict_crops(images, boxes, return_heatmaps=True)
+            hm, pts = self.model.predict_crops(images, boxes, return_heatmaps=True, **self._refine_kw())
             return self._result(hm.cpu().numpy(), boxes, pts.cpu().numpy())
         found = self.detector.predict_single(image)
         if found is None or len(found) == 0:
             return self._result(np.zeros(self._hm_shape(0), np.float32), np.empty((0, 4), np.int32),
                                 np.empty((0, 0, 3), dtype=np.float32))             # :331
         dets = np.asarray(found.cpu() if isinstance(found, torch.Tensor) else found, np.float32)[:, :4]
-        out = self.model.predict_frame(image, dets, return_heatmaps=self.return_heatmaps)
+        out = self.model.predict_frame(image, dets, return_heatmaps=self.return_heatmaps, **self._refine_kw())
         boxes, pts = out[0], out[1].cpu().numpy()
         hm = out[2].cpu().numpy() if self.return_heatmaps else None
         return self._result(hm, boxes, pts)
@@ -211,7 +220,7 @@ class SimpleHRNet:
         if not self.multiperson:
             x = self._normalise(images)
             boxes = np.repeat(np.asarray([[0, 0, images.shape[2], images.shape[1]]], dtype=np.float32), len(images), axis=0)
-            hm, pts = self.model.predict_crops(x, boxes, return_heatmaps=True)
+            hm, pts = self.model.predict_crops(x, boxes, return_heatmaps=True, **self._refine_kw())
             return self._result(hm.cpu().numpy(), boxes, np.expand_dims(pts.cpu().numpy(), axis=1))   # :475
         per_frame = self.detector.predict(images)
         crops, boxes = [], []
@@ -227,7 +236,7 @@ class SimpleHRNet:
             pts = [np.zeros((0, self.nof_joints, 3), dtype=np.float32) for _ in per_frame]
             return self._result(np.zeros(self._hm_shape(0), np.float32), np.asarray([], dtype=np.int32), pts)
         boxes = np.concatenate(boxes, 0)
-        out = self.model.predict_crops(torch.cat(crops, 0), boxes, return_heatmaps=self.return_heatmaps)
+        out = self.model.predict_crops(torch.cat(crops, 0), boxes, return_heatmaps=self.return_heatmaps, **self._refine_kw())
         hm, pts = (out[0].cpu().numpy(), out[1].cpu().numpy()) if self.return_heatmaps else (None, out.cpu().numpy())
         pts_b, hm_b, boxes_b, index = [], [], [], 0                                  # :445-472: re-add the batch axis
         for n in counts:
