@@ -1,4 +1,4 @@
-// Arg-max order shared by the head / decode kernels (kernels.hip) and the refined decode (refine.hip).
+// Arg-max order shared by the head kernels (kernels.hip) and the decode kernels (decode.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -526,7 +526,7 @@
             for (auto &b : buffers)
                 if (b.dev) (void)hipFree(b.dev);
             if (blob) (void)hipFree(blob);
-            if (tta_hm) (void)hipFree(tta_hm);
+            if (scratch_hm) (void)hipFree(scratch_hm);
             if (pre_tmp) (void)hipFree(pre_tmp);
             if (rs_taps) (void)hipFree(rs_taps);
             rs_taps = nullptr, rs_taps_cap = 0;

@@ -246,21 +246,13 @@
             e = launch_head(dtype, a, s);
             break;
         }
-        case OP_DECODE: {
+        case OP_DECODE: {   // decode_kernel<refine>: a sub-pixel mode reads the heat-maps the head just wrote (hrn_forward_refined)
             if (!pts) break;
             const Tensor &t = tensors[head_in_t];
-            if (refine != RF_NONE) {   // sub-pixel decode: reads the heat-maps the head just wrote (hrn_forward_refined)
-                RefineArgs r;
-                r.part_val = part_val, r.part_idx = part_idx, r.heatmaps = heatmaps, r.boxes = boxes;
-                r.box_is_float = box_dtype == HRN_BOX_F32, r.pts = pts, r.coords = nullptr;
-                r.n = nb, r.joints = joints, r.h = t.h, r.w = t.w, r.slabs = head_slabs_for(nb), r.mode = refine;
-                e = heatmaps ? launch_refine_decode(r, s) : hipErrorInvalidValue;
-                break;
-            }
-            DecodeArgs a;
-            a.part_val = part_val, a.part_idx = part_idx, a.boxes = boxes;
+            DecodeArgs a{};
+            a.part_val = part_val, a.part_idx = part_idx, a.heatmaps = heatmaps, a.boxes = boxes;
             a.box_is_float = box_dtype == HRN_BOX_F32, a.pts = pts;
-            a.n = nb, a.joints = joints, a.h = t.h, a.w = t.w, a.slabs = head_slabs_for(nb);
+            a.n = nb, a.joints = joints, a.h = t.h, a.w = t.w, a.slabs = head_slabs_for(nb), a.mode = refine;
             e = launch_decode(a, s);
             break;
         }

@@ -1,11 +1,14 @@
-// Sub-pixel joint decoding for gfx950 (include/hrnet_mi355.h: HRN_REFINE_*, hrn_forward_refined, hrn_refine_coords).
+// Heat-map to joint-coordinate kernels for gfx950: every decode of the head's arg-max (include/hrnet_mi355.h: hrn_forward,
+// hrn_forward_refined, hrn_forward_flip_tta, hrn_refine_coords).
 //
-//   refine_decode_kernel  decode_kernel's slab merge (first maximum wins), then the offset of the arg-max read from the
-//                         head's heat-maps, then the box scaling in fp64: y = (py + oy) / h * (y2 - y1) + y1.
+//   decode_kernel<MODE>   arg-max merge of the head's slab candidates (first maximum wins), the MODE offset of the arg-max read from
+//                         the head's heat-maps (none for RF_NONE), then the box scaling in fp64, SimpleHRNet.py:297-308.
 //   refine_coords_kernel  the same offset for integer (x, y) coordinates given by the caller (flip-TTA's averaged maps).
+//   tta_decode_kernel     flip-TTA: average with the mirrored pass, arg-max, and (post_processing) the quarter-cell offset.
 //
-// One thread per (crop, joint): ~4 k joints per 256-crop pass, a 15 x 15 window each -- no LDS, no MFMA.
-// QUARTER is get_final_preds's rule (misc/utils.py:154-175), the arithmetic of tta_decode_kernel's post_processing branch.
+// The per-joint kernels run one thread per (crop, joint): ~4 k joints per 256-crop pass, DARK reads a 15 x 15 window each -- no LDS,
+// no MFMA.
+// QUARTER is get_final_preds's rule (misc/utils.py:154-175).
 // DARK (Zhang et al., CVPR 2020) is evaluated in fp64: the 13 blurred values it needs, their logarithms, a Newton step.
 #include "kernels.h"
 #include "argmax.h"
@@ -80,7 +83,12 @@ __device__ __forceinline__ void subpixel_offset(const float *hm, int h, int w, i
     oy = sy < -1. ? -1. : (sy > 1. ? 1. : sy);
 }
 
-__global__ __launch_bounds__(64) void refine_decode_kernel(const RefineArgs p) {
+// Decode (SimpleHRNet.py:297-308): merge the slab candidates (lowest flat index among equal maxima = np.argmax), move the arg-max
+// by the MODE offset, then  y = (py + oy) * 1. / h * (y2 - y1) + y1,  x = (px + ox) * 1. / w * (x2 - x1) + x1  evaluated in float64
+// exactly as numpy does (box difference first, in the boxes' own dtype), stored as fp32.  The offset keeps its own fp contraction
+// (subpixel_offset is outside this kernel's contract(off)).  Launch bounds: 1024 (the default) for RF_NONE, 64 for the refined modes.
+template <int MODE>
+__global__ __launch_bounds__(MODE == RF_NONE ? 1024 : 64) void decode_kernel(const DecodeArgs p) {
 #pragma clang fp contract(off)
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= p.n * p.joints) return;
@@ -95,15 +103,15 @@ __global__ __launch_bounds__(64) void refine_decode_kernel(const RefineArgs p) {
             i = oi;
         }
     }
-    if (i == kNoIdx) i = 0;
+    if (i == kNoIdx) i = 0;  // (unreachable with h*w >= 1; never form coordinates from the sentinel)
     const int py = i / p.w, px = i - py * p.w;
-    double ox, oy;
-    subpixel_offset(p.heatmaps + (size_t)t * p.h * p.w, p.h, p.w, px, py, p.mode, ox, oy);
+    double ox = 0., oy = 0.;
+    if constexpr (MODE != RF_NONE) subpixel_offset(p.heatmaps + (size_t)t * p.h * p.w, p.h, p.w, px, py, MODE, ox, oy);
     double x1, y1, dx, dy;
     if (p.box_is_float) {
         const float *b = (const float *)p.boxes + 4 * (size_t)n;
         x1 = b[0], y1 = b[1];
-        dx = (double)(b[2] - b[0]);  // fp32 subtraction first, like numpy float32 scalars (decode_kernel)
+        dx = (double)(b[2] - b[0]);  // fp32 subtraction first, like numpy float32 scalars
         dy = (double)(b[3] - b[1]);
     } else {
         const int *b = (const int *)p.boxes + 4 * (size_t)n;
@@ -117,7 +125,7 @@ __global__ __launch_bounds__(64) void refine_decode_kernel(const RefineArgs p) {
     o[2] = v;
 }
 
-__global__ __launch_bounds__(64) void refine_coords_kernel(const RefineArgs p) {
+__global__ __launch_bounds__(64) void refine_coords_kernel(const DecodeArgs p) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= p.n * p.joints) return;
     float *c = p.coords + (size_t)t * 2;
@@ -129,18 +137,73 @@ __global__ __launch_bounds__(64) void refine_coords_kernel(const RefineArgs p) {
     c[1] = (float)((double)y + oy);
 }
 
-// 64-thread blocks: a 256-crop pass of 17 joints spreads over 68 CUs instead of 34
-hipError_t launch_refine_decode(const RefineArgs &a, hipStream_t s) {
+// RF_NONE: 128-thread blocks.  QUARTER / DARK: 64-thread blocks, so that a 256-crop pass of 17 joints spreads over 68 CUs instead of 34.
+hipError_t launch_decode(const DecodeArgs &a, hipStream_t s) {
+    if (a.mode != RF_NONE && !a.heatmaps) return hipErrorInvalidValue;   // the offset reads the maps the head wrote
     const int total = a.n * a.joints;
     if (total <= 0) return hipSuccess;
-    hipLaunchKernelGGL(refine_decode_kernel, dim3((total + 63) / 64), dim3(64), 0, s, a);
+    if (a.mode == RF_NONE)
+        hipLaunchKernelGGL(decode_kernel<RF_NONE>, dim3((total + 127) / 128), dim3(128), 0, s, a);
+    else if (a.mode == RF_QUARTER)
+        hipLaunchKernelGGL(decode_kernel<RF_QUARTER>, dim3((total + 63) / 64), dim3(64), 0, s, a);
+    else
+        hipLaunchKernelGGL(decode_kernel<RF_DARK>, dim3((total + 63) / 64), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_refine_coords(const RefineArgs &a, hipStream_t s) {
+hipError_t launch_refine_coords(const DecodeArgs &a, hipStream_t s) {
     const int total = a.n * a.joints;
     if (total <= 0) return hipSuccess;
     hipLaunchKernelGGL(refine_coords_kernel, dim3((total + 63) / 64), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// Flip-TTA combine + decode (testing/Test.py:134-140, misc/utils.py:19-29, 125-175): per (crop, joint)
+//   avg = (hm[j] + mirror(hm_flipped[pair(j)])) * 0.5     written back over hm
+//   (max, first arg-max) of avg -> x = idx % w, y = idx / w, zeroed when max <= 0   (get_max_preds)
+//   post_processing: +-0.25 px towards the higher neighbour when 1 < x < w-1 and 1 < y < h-1   (get_final_preds)
+__global__ __launch_bounds__(256) void tta_decode_kernel(const TtaArgs p) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    const int j = blockIdx.x, n = blockIdx.y, hw = p.h * p.w;
+    float *hm = p.hm + ((size_t)n * p.joints + j) * hw;
+    const float *hf = p.hm_flipped + ((size_t)n * p.joints + p.pair[j]) * hw;
+    float bv = -INFINITY;
+    int bi = kNoIdx;
+    for (int px = threadIdx.x; px < hw; px += 256) {
+        const int y = px / p.w, x = px - y * p.w;
+        const float v = (hm[px] + hf[y * p.w + (p.w - 1 - x)]) * 0.5f;
+        hm[px] = v;
+        if (takes(v, bv, bi)) bv = v, bi = px;  // px grows: strict > keeps the first maximum
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        if (better(ov, oi, bv, bi)) bv = ov, bi = oi;
+    }
+    if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = bv, si[threadIdx.x >> 6] = bi;
+    __threadfence_block();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (better(sv[w], si[w], bv, bi)) bv = sv[w], bi = si[w];
+        float x = (float)(bi % p.w), y = (float)(bi / p.w);
+        if (!(bv > 0.f)) x = 0.f, y = 0.f;
+        if (p.post_processing) {   // x, y are integer valued: x + ox in fp64 rounds to x + 0.25f, bit for bit
+            double ox, oy;
+            subpixel_offset(hm, p.h, p.w, (int)x, (int)y, RF_QUARTER, ox, oy);
+            x = (float)((double)x + ox), y = (float)((double)y + oy);
+        }
+        p.preds[((size_t)n * p.joints + j) * 2 + 0] = x;
+        p.preds[((size_t)n * p.joints + j) * 2 + 1] = y;
+        p.maxvals[(size_t)n * p.joints + j] = bv;
+    }
+}
+
+hipError_t launch_tta_decode(const TtaArgs &a, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(tta_decode_kernel, dim3(a.joints, a.n), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -171,7 +171,13 @@ struct hrn_ctx {
     unsigned pre_ring_next = 0;
     uint64_t map_clock = 0;     // LRU stamp of the block-map slots
     int64_t map_builds = 0;     // block maps built + uploaded since creation (hrn_map_rebuilds)
-    float *tta_hm = nullptr;  // flip-TTA: heat-maps of the mirrored micro-batch (allocated on first use)
+    float *scratch_hm = nullptr;  // max_batch heat-maps of the handle's own: flip-TTA's mirrored pass, a refined decode the caller gave no maps
+    float *scratch_heatmaps() {   // allocated on first use; nullptr (and err) if that fails
+        if (!scratch_hm && !hip_ok(hipMalloc((void **)&scratch_hm, (size_t)max_batch * joints * (H / 4) * (W / 4) * sizeof(float)),
+                                   "hipMalloc(scratch heat-maps)"))
+            scratch_hm = nullptr;
+        return scratch_hm;
+    }
     int64_t workspace_bytes = 0;
 
 #include "ctx_plan.inc"
@@ -197,6 +203,47 @@ struct PassScope {
         if (entered && !left) (void)h->pass_leave(s);
     }
 };
+
+// The loop of every forward entry: the device, then (n > 0) the scratch heat-maps if asked for, one PassScope and
+// pass(off, nb) for each micro-batch of at most max_batch crops (false: the entry returns 8).
+template <class Pass>
+int each_micro_batch(hrn_ctx *h, int n, bool scratch, hipStream_t s, const Pass &pass) {
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    if (n == 0) return 0;
+    if (scratch && !h->scratch_heatmaps()) return 6;
+    PassScope scope(h, s);
+    if (!scope.entered) return 6;
+    for (int off = 0; off < n; off += h->max_batch)
+        if (!pass(off, std::min(n - off, h->max_batch))) return 8;
+    return scope.leave() ? 0 : 6;
+}
+
+bool valid_refine(hrn_ctx *h, int refine) {
+    if (refine == HRN_REFINE_NONE || refine == HRN_REFINE_QUARTER || refine == HRN_REFINE_DARK) return true;
+    h->err = "refine must be HRN_REFINE_NONE, HRN_REFINE_QUARTER or HRN_REFINE_DARK";
+    return false;
+}
+
+// hrn_forward (HRN_REFINE_NONE) and hrn_forward_refined: one pass per micro-batch, its OP_DECODE launching decode_kernel<refine>
+// (decode.hip).  A sub-pixel mode has the head write heat-maps -- the caller's, or the handle's scratch -- for the decode to read.
+int forward(hrn_ctx *h, const void *images, int n, const void *boxes, int box_dtype, int refine, float *pts, float *heatmaps,
+            hipStream_t s) {
+    if (!h) return 1;
+    if (!valid_refine(h, refine)) return 7;
+    if (!h->check_forward_args(images, n, boxes, pts, heatmaps)) return 7;
+    if (refine != HRN_REFINE_NONE && !pts) {
+        h->err = "hrn_forward_refined: a refine mode needs pts (it refines the joint coordinates)";
+        return 7;
+    }
+    const bool scratch = refine != HRN_REFINE_NONE && !heatmaps;
+    return each_micro_batch(h, n, scratch, s, [&](int off, int nb) {
+        const float *img = (const float *)images + (size_t)off * 3 * h->H * h->W;
+        const void *bx = boxes ? (const char *)boxes + (size_t)off * 16 : nullptr;
+        float *p = pts ? pts + (size_t)off * h->joints * 3 : nullptr;
+        float *hp = heatmaps ? heatmaps + (size_t)off * h->joints * (h->H / 4) * (h->W / 4) : scratch ? h->scratch_hm : nullptr;
+        return h->run_pass(img, nb, bx, box_dtype, p, hp, s, nullptr, 0, nullptr, refine);
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -309,22 +356,7 @@ int hrn_weight_blob_read(hrn_handle h, int64_t offset, void *dst, int64_t nbytes
 
 int hrn_forward(hrn_handle h, const void *images_dev, int n, const void *boxes_dev, int box_dtype, float *pts_dev,
                 float *heatmaps_dev, void *stream) {
-    if (!h) return 1;
-    if (!h->check_forward_args(images_dev, n, boxes_dev, pts_dev, heatmaps_dev)) return 7;
-    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
-    const int hm = (h->H / 4) * (h->W / 4);
-    if (n == 0) return 0;
-    PassScope scope(h, (hipStream_t)stream);
-    if (!scope.entered) return 6;
-    for (int off = 0; off < n; off += h->max_batch) {
-        const int nb = n - off < h->max_batch ? n - off : h->max_batch;
-        const float *img = (const float *)images_dev + (size_t)off * 3 * h->H * h->W;
-        const void *bx = boxes_dev ? (const char *)boxes_dev + (size_t)off * 16 : nullptr;
-        float *p = pts_dev ? pts_dev + (size_t)off * h->joints * 3 : nullptr;
-        float *hp = heatmaps_dev ? heatmaps_dev + (size_t)off * h->joints * hm : nullptr;
-        if (!h->run_pass(img, nb, bx, box_dtype, p, hp, (hipStream_t)stream, nullptr)) return 8;
-    }
-    return scope.leave() ? 0 : 6;
+    return forward(h, images_dev, n, boxes_dev, box_dtype, HRN_REFINE_NONE, pts_dev, heatmaps_dev, (hipStream_t)stream);
 }
 
 // Flip test-time augmentation + the evaluation decode (testing/Test.py:132-140, training/COCO.py:206-230,
@@ -350,69 +382,28 @@ int hrn_forward_flip_tta(hrn_handle h, const void *images_dev, int n, const int3
         // (equal to "p0 <-> p1" only while no joint occurs in two pairs)
         std::swap(a.pair[p0], a.pair[p1]);
     }
-    if (n == 0) return 0;
-    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
-    const int hh = h->H / 4, ww = h->W / 4, hm = hh * ww;
-    if (!h->tta_hm &&
-        !h->hip_ok(hipMalloc((void **)&h->tta_hm, (size_t)h->max_batch * h->joints * hm * sizeof(float)), "hipMalloc(flip-TTA)"))
-        return 6;
+    a.joints = h->joints, a.h = h->H / 4, a.w = h->W / 4, a.post_processing = post_processing;
     hipStream_t s = (hipStream_t)stream;
-    PassScope scope(h, s);
-    if (!scope.entered) return 6;
-    for (int off = 0; off < n; off += h->max_batch) {
-        const int nb = n - off < h->max_batch ? n - off : h->max_batch;
+    return each_micro_batch(h, n, /*scratch=*/true, s, [&](int off, int nb) {   // the scratch takes the mirrored pass
         const float *img = (const float *)images_dev + (size_t)off * 3 * h->H * h->W;
-        float *out = heatmaps_dev + (size_t)off * h->joints * hm;
-        if (!h->run_pass(img, nb, nullptr, 0, nullptr, out, s, nullptr, 0)) return 8;
-        if (!h->run_pass(img, nb, nullptr, 0, nullptr, h->tta_hm, s, nullptr, 1)) return 8;
-        a.hm = out, a.hm_flipped = h->tta_hm;
+        float *out = heatmaps_dev + (size_t)off * h->joints * a.h * a.w;
+        if (!h->run_pass(img, nb, nullptr, 0, nullptr, out, s, nullptr, 0) ||
+            !h->run_pass(img, nb, nullptr, 0, nullptr, h->scratch_hm, s, nullptr, 1))
+            return false;
+        a.hm = out, a.hm_flipped = h->scratch_hm, a.n = nb;
         a.preds = preds_dev + (size_t)off * h->joints * 2, a.maxvals = maxvals_dev + (size_t)off * h->joints;
-        a.n = nb, a.joints = h->joints, a.h = hh, a.w = ww, a.post_processing = post_processing;
-        if (!h->hip_ok(launch_tta_decode(a, s), "flip-TTA decode launch")) return 8;
-    }
-    return scope.leave() ? 0 : 6;
+        return h->hip_ok(launch_tta_decode(a, s), "flip-TTA decode launch");
+    });
 }
 
-// Sub-pixel joint decoding (refine.hip): hrn_forward's passes with the head writing heat-maps -- the caller's, or the
-// handle's flip-TTA scratch (max_batch maps, allocated on first use) -- and OP_DECODE launching the refined decode.
 int hrn_forward_refined(hrn_handle h, const void *images_dev, int n, const void *boxes_dev, int box_dtype, int refine,
                         float *pts_dev, float *heatmaps_dev, void *stream) {
-    if (!h) return 1;
-    if (refine != HRN_REFINE_NONE && refine != HRN_REFINE_QUARTER && refine != HRN_REFINE_DARK) {
-        h->err = "refine must be HRN_REFINE_NONE, HRN_REFINE_QUARTER or HRN_REFINE_DARK";
-        return 7;
-    }
-    if (refine == HRN_REFINE_NONE) return hrn_forward(h, images_dev, n, boxes_dev, box_dtype, pts_dev, heatmaps_dev, stream);
-    if (!h->check_forward_args(images_dev, n, boxes_dev, pts_dev, heatmaps_dev)) return 7;
-    if (!pts_dev) {
-        h->err = "hrn_forward_refined: a refine mode needs pts (it refines the joint coordinates)";
-        return 7;
-    }
-    if (n == 0) return 0;
-    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
-    const int hm = (h->H / 4) * (h->W / 4);
-    if (!heatmaps_dev && !h->tta_hm &&
-        !h->hip_ok(hipMalloc((void **)&h->tta_hm, (size_t)h->max_batch * h->joints * hm * sizeof(float)), "hipMalloc(refine heat-maps)"))
-        return 6;
-    PassScope scope(h, (hipStream_t)stream);
-    if (!scope.entered) return 6;
-    for (int off = 0; off < n; off += h->max_batch) {
-        const int nb = n - off < h->max_batch ? n - off : h->max_batch;
-        const float *img = (const float *)images_dev + (size_t)off * 3 * h->H * h->W;
-        const void *bx = (const char *)boxes_dev + (size_t)off * 16;
-        float *p = pts_dev + (size_t)off * h->joints * 3;
-        float *hp = heatmaps_dev ? heatmaps_dev + (size_t)off * h->joints * hm : h->tta_hm;
-        if (!h->run_pass(img, nb, bx, box_dtype, p, hp, (hipStream_t)stream, nullptr, 0, nullptr, refine)) return 8;
-    }
-    return scope.leave() ? 0 : 6;
+    return forward(h, images_dev, n, boxes_dev, box_dtype, refine, pts_dev, heatmaps_dev, (hipStream_t)stream);
 }
 
 int hrn_refine_coords(hrn_handle h, const float *heatmaps_dev, int n, int refine, float *coords_dev, void *stream) {
     if (!h) return 1;
-    if (refine != HRN_REFINE_NONE && refine != HRN_REFINE_QUARTER && refine != HRN_REFINE_DARK) {
-        h->err = "refine must be HRN_REFINE_NONE, HRN_REFINE_QUARTER or HRN_REFINE_DARK";
-        return 7;
-    }
+    if (!valid_refine(h, refine)) return 7;
     if (h->plan_only) {
         h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
         return 7;
@@ -423,10 +414,9 @@ int hrn_refine_coords(hrn_handle h, const float *heatmaps_dev, int n, int refine
     }
     if (n == 0 || refine == HRN_REFINE_NONE) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
-    RefineArgs a;
-    a.part_val = nullptr, a.part_idx = nullptr, a.heatmaps = heatmaps_dev, a.boxes = nullptr, a.box_is_float = 0;
-    a.pts = nullptr, a.coords = coords_dev;
-    a.n = n, a.joints = h->joints, a.h = h->H / 4, a.w = h->W / 4, a.slabs = 0, a.mode = refine;
+    DecodeArgs a{};
+    a.heatmaps = heatmaps_dev, a.coords = coords_dev;
+    a.n = n, a.joints = h->joints, a.h = h->H / 4, a.w = h->W / 4, a.mode = refine;
     PassScope scope(h, (hipStream_t)stream);
     if (!scope.entered) return 6;
     if (!h->hip_ok(launch_refine_coords(a, (hipStream_t)stream), "refine launch")) return 8;

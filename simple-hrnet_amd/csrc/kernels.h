@@ -256,32 +256,23 @@ struct HeadArgs {          // final 1x1 conv (+bias) and per-(crop, joint) parti
     int n, c, joints, h, w, wp, hpwp, slabs, slab_px;
 };
 
-struct DecodeArgs {        // SimpleHRNet.py:297-308
-    const float *part_val;
-    const int *part_idx;
-    const void *boxes;     // (n,4) int32 or fp32
-    int box_is_float;
-    float *pts;            // (n,joints,3)
-    int n, joints, h, w, slabs;
-};
-
-// Sub-pixel joint decoding (refine.hip): the integer arg-max moved by a quarter cell towards the higher neighbour
-// (get_final_preds) or by DARK's Newton step on the log of the Gaussian-blurred map (include/hrnet_mi355.h: HRN_REFINE_*)
+// Heat-map to joint decoding (decode.hip).  The sub-pixel modes move the integer arg-max by a quarter cell towards the higher
+// neighbour (get_final_preds) or by DARK's Newton step on the log of the Gaussian-blurred map (include/hrnet_mi355.h: HRN_REFINE_*).
 enum { RF_NONE = 0, RF_QUARTER = 1, RF_DARK = 2 };   // = HRN_REFINE_NONE / _QUARTER / _DARK
-struct RefineArgs {
-    const float *part_val;  // decode form: the head's slab candidates, merged as decode_kernel merges them
+struct DecodeArgs {        // SimpleHRNet.py:297-308
+    const float *part_val; // decode_kernel: the head's slab candidates
     const int *part_idx;
-    const float *heatmaps;  // (n,joints,h,w) fp32, as the head wrote them
-    const void *boxes;      // decode form: (n,4) int32 or fp32
+    const void *boxes;     // decode_kernel: (n,4) int32 or fp32
     int box_is_float;
-    float *pts;             // decode form: (n,joints,3) (y, x, confidence)
-    float *coords;          // coords form: (n,joints,2) (x, y) in heat-map cells, integer-valued in, refined in place
+    float *pts;            // decode_kernel: (n,joints,3) (y, x, confidence)
     int n, joints, h, w, slabs, mode;
+    const float *heatmaps; // (n,joints,h,w) fp32, as the head wrote them: read where mode != RF_NONE
+    float *coords;         // refine_coords_kernel: (n,joints,2) (x, y) in heat-map cells, integer-valued in, refined in place
 };
-hipError_t launch_refine_decode(const RefineArgs &a, hipStream_t s);
-hipError_t launch_refine_coords(const RefineArgs &a, hipStream_t s);
+hipError_t launch_decode(const DecodeArgs &a, hipStream_t s);   // decode_kernel<mode>
+hipError_t launch_refine_coords(const DecodeArgs &a, hipStream_t s);
 
-struct TtaArgs {           // flip-TTA combine + get_max_preds + quarter-pixel refinement (misc/utils.py:19-29, 125-175)
+struct TtaArgs {           // flip-TTA combine + get_max_preds + quarter-pixel refinement (misc/utils.py:19-29, 125-175; decode.hip)
     float *hm;             // (n,joints,h,w): plain pass in, average out
     const float *hm_flipped;  // the mirrored crops' heat-maps
     float *preds;          // (n,joints,2): x, y in heat-map pixels
@@ -317,7 +308,6 @@ hipError_t launch_conv3x3_lds_f16(const Conv3Problem *probs_dev, const void *blo
 hipError_t launch_stem(int dtype, const StemArgs &a, hipStream_t s);
 hipError_t launch_fuse(int dtype, const FuseArgs &a, hipStream_t s);
 hipError_t launch_head(int dtype, const HeadArgs &a, hipStream_t s);
-hipError_t launch_decode(const DecodeArgs &a, hipStream_t s);
 
 // rows per block of the conv kernels: buffers keep this many guard rows after the last image
 // -- and the longest slab a compact tile of the 96-cout form may read past the last image (a last tile that holds a single

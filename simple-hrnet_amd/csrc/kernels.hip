@@ -7,8 +7,7 @@
 //                       4*NR *contiguous* output channels of one pixel -> wide NHWC stores.
 //   stem_kernel         conv1 (3->64, 3x3 s2) + BN + ReLU straight from the caller's NCHW fp32 crops.
 //   fuse_kernel         cross-resolution sum (nearest upsample folded into the read index) + ReLU.
-//   head_kernel         final 1x1 conv + bias, optional heat-map write-out, per-slab arg-max.
-//   decode_kernel       arg-max merge (first maximum wins) + box scaling in fp64, SimpleHRNet.py:297-308.
+//   head_kernel         final 1x1 conv + bias, optional heat-map write-out, per-slab arg-max (decoded in decode.hip).
 #include "kernels.h"
 #include "argmax.h"
 #include "dt16.h"
@@ -1191,98 +1190,6 @@ hipError_t launch_head(int dtype, const HeadArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Decode (SimpleHRNet.py:297-308): merge the slab candidates (lowest flat index among equal maxima =
-// np.argmax), then  y = py * 1. / h * (y2 - y1) + y1,  x = px * 1. / w * (x2 - x1) + x1  evaluated in
-// float64 exactly as numpy does (box difference first, in the boxes' own dtype), stored as fp32.
-__global__ void decode_kernel(const DecodeArgs p) {
-#pragma clang fp contract(off)
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= p.n * p.joints) return;
-    const int n = t / p.joints;
-    float v = -INFINITY;
-    int i = kNoIdx;
-    for (int s = 0; s < p.slabs; ++s) {
-        const float ov = p.part_val[(size_t)t * p.slabs + s];
-        const int oi = p.part_idx[(size_t)t * p.slabs + s];
-        if (better(ov, oi, v, i)) {
-            v = ov;
-            i = oi;
-        }
-    }
-    if (i == kNoIdx) i = 0;  // (unreachable with h*w >= 1; never form coordinates from the sentinel)
-    const int py = i / p.w, px = i - py * p.w;
-    double x1, y1, dx, dy;
-    if (p.box_is_float) {
-        const float *b = (const float *)p.boxes + 4 * (size_t)n;
-        x1 = b[0], y1 = b[1];
-        dx = (double)(b[2] - b[0]);  // fp32 subtraction first, like numpy float32 scalars
-        dy = (double)(b[3] - b[1]);
-    } else {
-        const int *b = (const int *)p.boxes + 4 * (size_t)n;
-        x1 = b[0], y1 = b[1];
-        dx = (double)(b[2] - b[0]);
-        dy = (double)(b[3] - b[1]);
-    }
-    float *o = p.pts + (size_t)t * 3;
-    o[0] = (float)((double)py * 1. / (double)p.h * dy + y1);
-    o[1] = (float)((double)px * 1. / (double)p.w * dx + x1);
-    o[2] = v;
-}
-
-// Flip-TTA combine + decode (testing/Test.py:134-140, misc/utils.py:19-29, 125-175): per (crop, joint)
-//   avg = (hm[j] + mirror(hm_flipped[pair(j)])) * 0.5     written back over hm
-//   (max, first arg-max) of avg -> x = idx % w, y = idx / w, zeroed when max <= 0   (get_max_preds)
-//   post_processing: +-0.25 px towards the higher neighbour when 1 < x < w-1 and 1 < y < h-1   (get_final_preds)
-__global__ __launch_bounds__(256) void tta_decode_kernel(const TtaArgs p) {
-    __shared__ float sv[4];
-    __shared__ int si[4];
-    const int j = blockIdx.x, n = blockIdx.y, hw = p.h * p.w;
-    float *hm = p.hm + ((size_t)n * p.joints + j) * hw;
-    const float *hf = p.hm_flipped + ((size_t)n * p.joints + p.pair[j]) * hw;
-    float bv = -INFINITY;
-    int bi = kNoIdx;
-    for (int px = threadIdx.x; px < hw; px += 256) {
-        const int y = px / p.w, x = px - y * p.w;
-        const float v = (hm[px] + hf[y * p.w + (p.w - 1 - x)]) * 0.5f;
-        hm[px] = v;
-        if (takes(v, bv, bi)) bv = v, bi = px;  // px grows: strict > keeps the first maximum
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(bv, off);
-        const int oi = __shfl_xor(bi, off);
-        if (better(ov, oi, bv, bi)) bv = ov, bi = oi;
-    }
-    if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = bv, si[threadIdx.x >> 6] = bi;
-    __threadfence_block();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (better(sv[w], si[w], bv, bi)) bv = sv[w], bi = si[w];
-        float x = (float)(bi % p.w), y = (float)(bi / p.w);
-        if (!(bv > 0.f)) x = 0.f, y = 0.f;
-        if (p.post_processing) {
-            const int ix = (int)x, iy = (int)y;  // integer valued
-            if (1 < ix && ix < p.w - 1 && 1 < iy && iy < p.h - 1) {
-                const float dx = hm[iy * p.w + ix + 1] - hm[iy * p.w + ix - 1];
-                const float dy = hm[(iy + 1) * p.w + ix] - hm[(iy - 1) * p.w + ix];
-                x += (dx > 0.f ? 0.25f : (dx < 0.f ? -0.25f : 0.f));
-                y += (dy > 0.f ? 0.25f : (dy < 0.f ? -0.25f : 0.f));
-            }
-        }
-        p.preds[((size_t)n * p.joints + j) * 2 + 0] = x;
-        p.preds[((size_t)n * p.joints + j) * 2 + 1] = y;
-        p.maxvals[(size_t)n * p.joints + j] = bv;
-    }
-}
-
-hipError_t launch_tta_decode(const TtaArgs &a, hipStream_t s) {
-    if (a.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(tta_decode_kernel, dim3(a.joints, a.n), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
 // Debug tap (hrn_forward_tap): the stored values of a flat padded NHWC tensor, widened exactly, as NCHW fp32.
 template <int DT>
 __global__ __launch_bounds__(256) void tap_kernel(const TapArgs p) {
@@ -1340,13 +1247,6 @@ hipError_t launch_pad_check(int dtype, const PadCheckArgs &a, hipStream_t s) {
         hipLaunchKernelGGL(pad_check_kernel<DT_F16>, dim3(blocks), dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(pad_check_kernel<DT_F32>, dim3(blocks), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_decode(const DecodeArgs &a, hipStream_t s) {
-    const int total = a.n * a.joints;
-    if (total <= 0) return hipSuccess;
-    hipLaunchKernelGGL(decode_kernel, dim3((total + 127) / 128), dim3(128), 0, s, a);
     return hipGetLastError();
 }
 

@@ -212,12 +212,7 @@ class NativeHRNet:
         pts = torch.empty((n, self.nof_joints, 3), dtype=torch.float32, device=x.device)
         hm = torch.empty((n, self.nof_joints, h // 4, w // 4), dtype=torch.float32,
                          device=x.device) if return_heatmaps else None
-        if n and mode == 0:
-            with torch.cuda.device(self.device_index):
-                self._check(self._lib.hrn_forward(self._h, x.data_ptr(), n, b.data_ptr(), box_dtype, pts.data_ptr(),
-                                                  hm.data_ptr() if hm is not None else None, self._stream()),
-                            "hrn_forward")
-        elif n:
+        if n:   # (mode 0 = HRN_REFINE_NONE: hrn_forward_refined is hrn_forward)
             with torch.cuda.device(self.device_index):
                 self._check(self._lib.hrn_forward_refined(self._h, x.data_ptr(), n, b.data_ptr(), box_dtype, mode, pts.data_ptr(),
                                                           hm.data_ptr() if hm is not None else None, self._stream()),

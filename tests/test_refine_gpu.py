@@ -1,4 +1,4 @@
-"""Sub-pixel joint decoding on the MI355X (include/hrnet_mi355.h: HRN_REFINE_*; csrc/refine.hip) against the numpy
+"""Sub-pixel joint decoding on the MI355X (include/hrnet_mi355.h: HRN_REFINE_*; csrc/decode.hip) against the numpy
 restatement of tests/subpixel_ref.py, run on the engine's own heat-maps.  QUARTER must be equal; DARK (fp64 on both sides)
 within 1e-3 heat-map cell, except joints where another evaluation order may legitimately decide otherwise (an ill-conditioned
 Hessian, a definiteness or clamp decision within 1e-5 of its threshold): those are counted, printed and kept under 2 %."""
