@@ -71,7 +71,11 @@ extern "C" int hrn_debug_q_timing(long long *host_out) {
 int conv3x3_n96_ch64() { return N96_CH64; }
 int conv3x3_n96_max_rows() { return N96_MAXROWS; }
 
-int conv3x3_lds_bbf_ok(int wp) { return (512 + 4 * (wp + 1)) * 6 <= BBF_XY / 16; }
+// X of a tile fits XY, and so do the whole 64-lane LDS-DMA pieces of a sliding tile's last 2 halo rows (bbf_run: fetch_x)
+int conv3x3_lds_bbf_ok(int wp) {
+    const int cunits = 2 * (wp + 1) * 6;
+    return (512 + 4 * (wp + 1)) * 6 <= BBF_XY / 16 && 3072 + cunits + (cunits + 63) / 64 * 64 <= BBF_XY / 16;
+}
 
 // pixels per M tile for a (KS, wp) pair: 512, or 384 when two 512-row slabs (+ halo) would not fit in LDS; 0 = unsupported
 int conv3x3_lds_bm(int ks, int nrb, int wp) {

@@ -443,9 +443,12 @@ __device__ __forceinline__ void conv3_run(const Conv3Problem &p, const int nt, c
 //          the lane's residual values (X centre rows) are read into registers, then Y overwrites X in place
 //     C2 : Z = relu(W2 * Y + b2 + X) for rows [p0, p0 + 512)               -> global
 //   and the next tile's X is requested before the epilogue's stores, which it lands under.
+// The tiles after a block's first one slide: tile t + 1's Y rows [0, 2 halo) are tile t's Y rows [512, 512 + 2 halo),
+// so they are carried over (read after C2's last chunk, written to rows [0, 2 halo) beside the next X), only X rows
+// [2 halo, 512 + 4 halo) are loaded and C1 computes only Y rows [2 halo, 512 + 2 halo): 32 fragments, 4 per wave.
 // Bit-identical to the two separate launches (same K order, same bf16 rounding of Y, same epilogue arithmetic).
 // The vector-memory instructions per wave and 2 x 512 convolved pixels drop from ~43 to 18, HBM traffic from five
-// tensor passes to two; the price is 1 + 2 halo / 512 = 1.29 x the MFMAs in C1 (1.145 x overall at wp = 73).
+// tensor passes to two; the price is 1 + 2 halo / 512 = 1.29 x the MFMAs in C1 on a block's first tile, none after it.
 constexpr int BBF_W = 14 * 3 * 1024;            // one packed weight image (cout tile 0, slice 0, both parts)
 constexpr int BBF_XY = 4864 * 16;               // 810 rows of 96 B, rounded up to whole 64-lane pieces
 constexpr int BBF_LDS = 2 * BBF_W + BBF_XY;     // = 160 KiB
@@ -570,6 +573,7 @@ __device__ __forceinline__ void bbf_run(const Conv3Problem &p, const int mt0, co
     const int halo = p.wp + 1;
     const int xrows = BM + 4 * halo, yrows = BM + 2 * halo;
     const int xunits = xrows * 6;
+    const int cunits = 2 * halo * 6;   // the rows a sliding tile carries over / does not load (<= 888 units: two per lane)
     // conv1's pixel fragments: nfr of them, dealt to the waves base or base + 1 each, contiguous
     const int nfr = (yrows + 15) >> 4, base = nfr >> 3, extra = nfr & 7;
     const int cnt = base + (wave < extra ? 1 : 0);
@@ -616,19 +620,22 @@ __device__ __forceinline__ void bbf_run(const Conv3Problem &p, const int mt0, co
             }
         }
     };
-    // The same X, for the tiles after the first, through registers: requested when conv2 starts and written to XY
-    // once conv2 has finished with Y -- conv2's compute time to land, nothing exposed but ten ds_write.
-    // Pieces 0..7 (units < 4096) go through registers; pieces 8 and 9 land beyond Y's last row (660 rows = 3960 units
-    // at most), which nothing reads during conv2: those go straight to their place by LDS-DMA.
-    constexpr int NXP = BBF_XY / 16 / NT + 1, NXR = 8;
+    // The X of a sliding tile (rows [2 halo, xrows); rows [0, 2 halo) receive the carried Y): requested when conv2
+    // starts and written to XY once conv2 has finished with Y -- conv2's compute time to land, nothing exposed but six
+    // ds_write.  Its first 512 rows (pieces 0..5, 3072 units) overlap the Y rows conv2 reads and go through registers;
+    // the last 2 halo rows (pieces 6 and 7, at most 888 units) lie beyond Y's last row, which nothing reads during conv2:
+    // those go straight to their place by LDS-DMA.  (conv3x3_lds_bbf_ok: the 64-lane pieces of the last 2 halo rows end inside XY.)
+    constexpr int NXR = 6, NXP = NXR + 2;
     u32x4 xpre[NXR];
-    // unit u = k * 512 + tid of the X image is slot u % 6 of row u / 6; 512 = 85 * 6 + 2, so piece k follows from piece 0
+    const int xu0 = cunits;   // the first X unit a sliding tile loads
+    // unit u = xu0 + k * 512 + tid of the X image is slot u % 6 of row u / 6; 512 = 85 * 6 + 2, so piece k follows from
+    // piece 0
     const int r0u = (int)(((unsigned)tid * 43691u) >> 18), q0u = tid - r0u * 6;
     auto x_src = [&](int tt, int k) {
         const int row0 = (mt0 + tt) * BM - 2 * halo;   // (all row numbers fit 32 bits: m < 2^27)
         int r = r0u, q8 = q0u;
-        asm volatile("" : "+v"(r), "+v"(q8));          // derive per tile: hoisted, the ten row / slot pairs would spill
-        r += 85 * k + (2 * k) / 6, q8 += (2 * k) % 6;
+        asm volatile("" : "+v"(r), "+v"(q8));          // derive per tile: hoisted, the eight row / slot pairs would spill
+        r += 2 * halo + 85 * k + (2 * k) / 6, q8 += (2 * k) % 6;
         if (q8 >= 6) q8 -= 6, ++r;
         if (r >= xrows) r = xrows - 1, q8 = 5;          // past the end: re-read the last unit
         int gr = row0 + r;
@@ -638,20 +645,28 @@ __device__ __forceinline__ void bbf_run(const Conv3Problem &p, const int mt0, co
     };
     auto fetch_x = [&](int tt) {
 #pragma unroll
-        // (unconditional: a piece past the end re-reads the last unit and is not written.  Plain loads, not inline asm:
-        // should the register allocator ever spill one, the compiler waits for it first -- slower, never wrong)
+        // (the register pieces are always whole.  Plain loads, not inline asm: should the register allocator ever spill
+        // one, the compiler waits for it first -- slower, never wrong)
         for (int k = 0; k < NXR; ++k) xpre[k] = *(const GLOBAL_AS u32x4 *)x_src(tt, k);
 #pragma unroll
         for (int k = NXR; k < NXP; ++k)
-            if (k * NT + wave * 64 < xunits) glds16((const GLOBAL_AS char *)x_src(tt, k), xy + (k * NT + wave * 64) * 16);
+            if (xu0 + k * NT + wave * 64 < xunits) glds16((const GLOBAL_AS char *)x_src(tt, k), xy + (xu0 + k * NT + wave * 64) * 16);
     };
     auto store_x = [&]() {
-        const unsigned a0 = lds0 + 2 * BBF_W + tid * 16;
+        const unsigned a0 = lds0 + 2 * BBF_W + (xu0 + tid) * 16;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // registers and LDS-DMA alike
 #pragma unroll
         for (int k = 0; k < NXR; ++k)
-            if (k * NT + wave * 64 < xunits)
-                asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(a0), "v"(xpre[k]), "i"(k * NT * 16) : "memory");
+            asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(a0), "v"(xpre[k]), "i"(k * NT * 16) : "memory");
+    };
+    // The carry: Y rows [BM, yrows) -> rows [0, 2 halo), a straight copy of cunits 16-byte units, unit tid and 512 + tid
+    // of each lane (the reads are clamped into the source rows, the writes masked to the copy)
+    u32x4 ycar[2];
+    const unsigned ca0 = lds0 + 2 * BBF_W + (tid < cunits ? tid : 0) * 16;
+    const unsigned ca1 = lds0 + 2 * BBF_W + (tid + NT < cunits ? tid + NT : 0) * 16;
+    auto store_carry = [&]() {
+        if (tid < cunits) asm volatile("ds_write_b128 %0, %1" ::"v"(ca0), "v"(ycar[0]) : "memory");
+        if (tid + NT < cunits) asm volatile("ds_write_b128 %0, %1" ::"v"(ca1), "v"(ycar[1]) : "memory");
     };
     {   // both weight images, once per block
         const GLOBAL_AS char *w1 = (const GLOBAL_AS char *)p.w, *w2 = (const GLOBAL_AS char *)p.w2;
@@ -679,15 +694,18 @@ __device__ __forceinline__ void bbf_run(const Conv3Problem &p, const int mt0, co
         long long tC = 0;
         u32x2 rpre[MR][3];
         const unsigned res_a = lds0 + 2 * BBF_W + (wave * 16 * MR + li + 2 * halo) * ROWB + g * 24;
-        if (cnt == 6)
-            bbf_conv1<6, DT>(p, xoff, bvec1, lds0, row_first, row_last, p0 - halo, m, lane, res_a, rpre, tC);
-        else if (cnt == 5)
-            bbf_conv1<5, DT>(p, xoff, bvec1, lds0, row_first, row_last, p0 - halo, m, lane, res_a, rpre, tC);
+        // a sliding tile (tt > 0) holds Y rows [0, 2 halo) already: conv1 computes rows [2 halo, yrows), 4 fragments per wave
+        const int rf = tt > 0 ? 2 * halo + wave * 64 : row_first, rl = tt > 0 ? rf + 48 : row_last;
+        if (tt == 0 && cnt == 6)
+            bbf_conv1<6, DT>(p, xoff, bvec1, lds0, rf, rl, p0 - halo, m, lane, res_a, rpre, tC);
+        else if (tt == 0 && cnt == 5)
+            bbf_conv1<5, DT>(p, xoff, bvec1, lds0, rf, rl, p0 - halo, m, lane, res_a, rpre, tC);
         else
-            bbf_conv1<4, DT>(p, xoff, bvec1, lds0, row_first, row_last, p0 - halo, m, lane, res_a, rpre, tC);
+            bbf_conv1<4, DT>(p, xoff, bvec1, lds0, rf, rl, p0 - halo, m, lane, res_a, rpre, tC);
         C3_T(tD);
         // ---- conv2 over Y: the chunk loop of conv3_run with both weight parts resident
-        if (tt + 1 < ntile) fetch_x(tt + 1);   // the next tile's X lands in registers meanwhile
+        const bool carry = tt + 1 < ntile;
+        if (carry) fetch_x(tt + 1);   // the next tile's X lands in registers meanwhile
         unsigned okbits2 = 0;                  // the epilogue's pad mask, ahead of the loop for the same reason as conv1's
 #pragma unroll
         for (int i = 0; i < MR; ++i) {
@@ -731,6 +749,10 @@ __device__ __forceinline__ void bbf_run(const Conv3Problem &p, const int mt0, co
                     asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(NRB + MR) : "memory");
                 } else {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if (carry) {   // the Y rows the next tile keeps: read under the last chunk's MFMAs
+                        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ycar[0]) : "v"(ca0), "i"(BM * ROWB) : "memory");
+                        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ycar[1]) : "v"(ca1), "i"(BM * ROWB) : "memory");
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -743,8 +765,12 @@ __device__ __forceinline__ void bbf_run(const Conv3Problem &p, const int mt0, co
 #undef BBF_READ2
         }
         C3_T(tE);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the carried rows are in registers
         __builtin_amdgcn_s_barrier();  // every wave is done reading Y: XY may be refilled
-        if (tt + 1 < ntile) store_x();
+        if (carry) {
+            store_carry();
+            store_x();
+        }
         __builtin_amdgcn_sched_barrier(0);
         C3_T(tF);
         // ---- epilogue of conv2 (as in conv3_run): + residual, ReLU, zero on pad pixels, 24 contiguous bytes per lane

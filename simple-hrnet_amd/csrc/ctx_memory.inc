@@ -149,10 +149,10 @@
                             if (tiles > tpb) tiles = tpb;
                             double key = (i + 0.5) / total;  // proportional interleave of the problems
                             if (block_order == 1)            // longest-processing-time first (estimated block cost)
-                                key = -(double)tiles * (fused         ? 28000.0
-                                                        : cv.ks == 16 ? cv.slices * (double)bm * 36.0 + 2000.0   // fp32: 9 x 4 MR NRB MFMAs of 32 cycles per slice
+                                key = -(fused ? 28000.0 + (tiles - 1) * bbf_slide_cost   // a fused block's later tiles slide (bbf_run)
+                                        : (double)tiles * (cv.ks == 16 ? cv.slices * (double)bm * 36.0 + 2000.0   // fp32: 9 x 4 MR NRB MFMAs of 32 cycles per slice
                                                         : cv.n96      ? cv.slices * 3.0 * (bm == 512 ? 3900.0 : 3000.0) + (bm == 512 ? 7000.0 : 5000.0)
-                                                                 : cv.slices * 2.0 * (bm == 512 ? 4300.0 : 3500.0) + (bm == 512 ? 5000.0 : 3000.0)) +
+                                                                 : cv.slices * 2.0 * (bm == 512 ? 4300.0 : 3500.0) + (bm == 512 ? 5000.0 : 3000.0))) +
                                       1e-3 * key;
                             int mt0 = first + mg * tpb;
                             // every other launch walks the tensors backwards: a launch starts on what its producer

@@ -96,7 +96,13 @@ struct hrn_ctx {
     // fused BasicBlocks on the 48-channel branch (conv3x3_lds.hip: bbf_run): bit-identical, 2.5x less HBM traffic on that
     // branch, +2.6 % on the whole pass at 256 crops; HRN_BBF=0 goes back to two launches per block
     bool disable_bbf = env_sw("HRN_BBF") && atoi(env_sw("HRN_BBF")) == 0;
-    int bbf_tpb_div = env_sw("HRN_BBF_TPB_DIV") ? std::max(1, atoi(env_sw("HRN_BBF_TPB_DIV"))) : 3;  // a fused tile ~ 3 plain ones
+    // a fused block walks conv3_tiles_per_block / bbf_tpb_div tiles (short blocks of 1; long ones, 85 % of the tiles, long_factor = 4
+    // times that): 64 % of the fused tiles slide (conv1's halo rows carried over, not recomputed).  Longer blocks (2 / 1: 81 / 87 %
+    // sliding) measured +0.5 % on two boxes and -4.4 % on a third (profiles/carry_block_length_sweep.txt): not adopted
+    int bbf_tpb_div = env_sw("HRN_BBF_TPB_DIV") ? std::max(1, atoi(env_sw("HRN_BBF_TPB_DIV"))) : 3;
+    // estimated cost of a sliding tile for the longest-first order, against 28000 for a block's first tile (as the plain blocks'
+    // estimates count): the phase stamps measured 21.2 k ticks against 24.1 k
+    double bbf_slide_cost = env_sw("HRN_BBF_SLIDE_COST") ? atof(env_sw("HRN_BBF_SLIDE_COST")) : 24600.0;
     // fused only when the call has at least this many 512-pixel tiles (four per CU): measured at 384x288 +2 % at 256
     // crops (3541 tiles), +1 % at 128-192, +6 % at 96 (1328 tiles), -1 % at 64 (885 tiles), -2 % at 20, -5 % at one crop,
     // where the two plain launches with their smaller tiles spread the work over more CUs
