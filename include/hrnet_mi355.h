@@ -144,6 +144,34 @@ enum { HRN_INTER_NEAREST = 0, HRN_INTER_LINEAR = 1, HRN_INTER_CUBIC = 2 };
 int hrn_resize_frames(hrn_handle h, const uint8_t *frames_dev, int n, int frame_h, int frame_w, int interpolation,
                       float *images_dev, void *stream);
 
+/* Evaluation pre-path on the GPU: replaces, for every person of a batch of the dataset path (testing/Test.py through
+ * datasets/COCO.py:290-304; misc/utils.py:99-107 is the same call),
+ *   trans = get_affine_transform(center, scale, pixel_std, rot, image_size)           (misc/utils.py:46-75)
+ *   image = cv2.warpAffine(image, trans, (W, H), flags=cv2.INTER_LINEAR); image = ToTensor + Normalize
+ * and writes the (n,3,H,W) fp32 batch hrn_forward / hrn_forward_flip_tta read: the frames cross PCIe once as uint8.
+ *   frames_dev        (nframes, frame_h, frame_w, 3) uint8 BGR, device (sides up to 32 766: OpenCV saturates coordinates to int16)
+ *   frame_index_host  n entries on the HOST: the frame crop i is cut from; NULL: crop i reads frame i (nframes == n) or
+ *                     frame 0 (nframes == 1)
+ *   matrices_host     (n, 6) float64 on the HOST: the FORWARD 2x3 matrices (frame -> crop), row-major, as
+ *                     get_affine_transform(..., inv=0) returns them (postproc.affine_matrix)
+ *   images_dev        out: (n,3,H,W) float32, device.  Any n: it is not bounded by max_batch.
+ * The arithmetic is warpAffine's classic 8-bit INTER_LINEAR path, integer throughout:
+ *   the matrix is inverted in float64 as cv::warpAffine does (D = M0*M4 - M1*M3; D = 1/D; A11 = M4*D; A22 = M0*D; M0 = A11;
+ *   M1 *= -D; M3 *= -D; M4 = A22; b1 = -M0*M2 - M1*M5; b2 = -M3*M2 - M4*M5; M2 = b1; M5 = b2 -- no fused multiply-add);
+ *   X = (rint((M1*y + M2) * 1024) + 16 + rint(M0*x * 1024)) >> 5, Y likewise with M4, M5 and M3 (1/32 pixel, rint = round half
+ *   to even); sx = X >> 5, fx = X & 31, likewise sy, fy;
+ *   v = (p00*(32-fx)*(32-fy) + p01*fx*(32-fy) + p10*(32-fx)*fy + p11*fx*fy + 512) >> 10 per channel, every tap outside the frame
+ *   reading 0 (BORDER_CONSTANT, value 0: the reference passes no border arguments); then BGR -> RGB, v / 255, (x - mean) / std
+ *   in float32 as hrn_resize_frames.
+ * Fails (code 7, nothing launched) on a plan-only handle, n < 0, a frame side above 32 766, a frame index outside [0, nframes),
+ * and a matrix that is not finite, is singular (the reference would sample one pixel everywhere), or maps a corner of the crop
+ * further than 2^20 pixels from the frame's origin (the fixed point would overflow).
+ * OpenCV is not available where this library is built and tested: tests/warp_affine_ref.py restates the arithmetic above and
+ * the kernel equals that restatement bit for bit; parity with a cv2 build is NOT pinned (newer releases carry float warpAffine
+ * kernels).  tests/golden/make_warp_golden.py produces the fixture wherever opencv-python is installed. */
+int hrn_warp_crops(hrn_handle h, const uint8_t *frames_dev, int nframes, int frame_h, int frame_w,
+                   const int32_t *frame_index_host, const double *matrices_host, int n, float *images_dev, void *stream);
+
 /* Flip test-time augmentation + evaluation decode (testing/Test.py:132-140,
  * training/COCO.py:206-230, misc/utils.py:9-29 flip_tensor / flip_back, :125-151 get_max_preds, :154-175 the
  * post-processing of get_final_preds):

@@ -535,6 +535,10 @@
             if (pass_done) (void)hipEventDestroy(pass_done);
             pass_done = nullptr;
             if (pre_params) (void)hipFree(pre_params);
+            if (warp_params) (void)hipFree(warp_params);
+            warp_params = nullptr, warp_params_cap = 0;
+            if (warp_done) (void)hipEventDestroy(warp_done);
+            warp_done = nullptr;
             if (part_val) (void)hipFree(part_val);
             if (part_idx) (void)hipFree(part_idx);
             if (probs_dev) (void)hipFree(probs_dev);

@@ -175,6 +175,31 @@ struct hrn_ctx {
     size_t pre_pin_bytes[kPreRing] = {0, 0, 0, 0};
     hipEvent_t pre_landed[kPreRing] = {nullptr, nullptr, nullptr, nullptr};
     unsigned pre_ring_next = 0;
+    // the next image of the ring, at least `need` bytes, free to be rewritten (nullptr + err on failure); the caller records
+    // pre_landed[*ring] behind the uploads that read it
+    char *pre_stage(size_t need, unsigned *ring_out) {
+        const unsigned ring = pre_ring_next++ % kPreRing;
+        if (pre_landed[ring]) {
+            if (!hip_ok(hipEventSynchronize(pre_landed[ring]), "hipEventSynchronize")) return nullptr;
+        } else if (!hip_ok(hipEventCreateWithFlags(&pre_landed[ring], hipEventDisableTiming), "hipEventCreate")) {
+            return nullptr;
+        }
+        if (need > pre_pin_bytes[ring]) {
+            if (pre_pin[ring]) (void)hipHostFree(pre_pin[ring]);
+            pre_pin[ring] = nullptr, pre_pin_bytes[ring] = 0;
+            const size_t cap = std::max<size_t>(need * 2, 4096);
+            if (!hip_ok(hipHostMalloc((void **)&pre_pin[ring], cap, hipHostMallocDefault), "hipHostMalloc(crop params)")) return nullptr;
+            pre_pin_bytes[ring] = cap;
+        }
+        *ring_out = ring;
+        return pre_pin[ring];
+    }
+    // evaluation pre-path (hrn_warp_crops): the inverse matrices of the last call on the device; like the resize's tap table,
+    // a call on ANOTHER stream than the previous one rewrites them only after that one's kernel has read them
+    WarpParams *warp_params = nullptr;
+    int warp_params_cap = 0;
+    hipEvent_t warp_done = nullptr;
+    hipStream_t warp_stream = nullptr;
     uint64_t map_clock = 0;     // LRU stamp of the block-map slots
     int64_t map_builds = 0;     // block maps built + uploaded since creation (hrn_map_rebuilds)
     float *scratch_hm = nullptr;  // max_batch heat-maps of the handle's own: flip-TTA's mirrored pass, a refined decode the caller gave no maps
@@ -453,19 +478,8 @@ int hrn_preprocess_frame(hrn_handle h, const uint8_t *frame_dev, int frame_h, in
     // crop parameters + boxes are written straight into a pinned image the async uploads below read after this call
     // has returned; kPreRing images in rotation, each reused only once the upload that read it last has completed
     const size_t cp_bytes = ((size_t)n * sizeof(CropParams) + 63) / 64 * 64, need = cp_bytes + (size_t)n * 16;
-    const unsigned ring = h->pre_ring_next++ % hrn_ctx::kPreRing;
-    if (h->pre_landed[ring]) {
-        if (!h->hip_ok(hipEventSynchronize(h->pre_landed[ring]), "hipEventSynchronize")) return 6;
-    } else if (!h->hip_ok(hipEventCreateWithFlags(&h->pre_landed[ring], hipEventDisableTiming), "hipEventCreate")) {
-        return 6;
-    }
-    if (need > h->pre_pin_bytes[ring]) {
-        if (h->pre_pin[ring]) (void)hipHostFree(h->pre_pin[ring]);
-        h->pre_pin[ring] = nullptr, h->pre_pin_bytes[ring] = 0;
-        const size_t cap = std::max<size_t>(need * 2, 4096);
-        if (!h->hip_ok(hipHostMalloc((void **)&h->pre_pin[ring], cap, hipHostMallocDefault), "hipHostMalloc(crop params)")) return 6;
-        h->pre_pin_bytes[ring] = cap;
-    }
+    unsigned ring = 0;
+    if (!h->pre_stage(need, &ring)) return 6;
     CropParams *cps = (CropParams *)h->pre_pin[ring];
     int32_t *boxes = (int32_t *)(h->pre_pin[ring] + cp_bytes);
     size_t tmp_bytes = 0;
@@ -593,6 +607,101 @@ int hrn_resize_frames(hrn_handle h, const uint8_t *frames_dev, int n, int frame_
     h->rs_stream = s;
     if (!h->hip_ok(hipEventRecord(h->rs_done, s), "hipEventRecord")) return 6;
     return 0;
+}
+
+namespace {
+// The inversion cv::warpAffine performs on a forward matrix (no WARP_INVERSE_MAP), statement for statement, each product and
+// sum rounded on its own.  False when the matrix is not finite, singular, or its inverse is not finite.
+bool invert_affine(const double *fwd, double *M) {
+#pragma clang fp contract(off)
+    for (int k = 0; k < 6; ++k) {
+        if (!std::isfinite(fwd[k])) return false;
+        M[k] = fwd[k];
+    }
+    double D = M[0] * M[4] - M[1] * M[3];
+    if (D == 0) return false;   // (the reference would go on with D = 0 and sample one pixel everywhere)
+    D = 1. / D;
+    const double A11 = M[4] * D, A22 = M[0] * D;
+    M[0] = A11, M[1] *= -D;
+    M[3] *= -D, M[4] = A22;
+    const double b1 = -M[0] * M[2] - M[1] * M[5];
+    const double b2 = -M[3] * M[2] - M[4] * M[5];
+    M[2] = b1, M[5] = b2;
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(M[k])) return false;
+    return true;
+}
+}  // namespace
+
+// datasets/COCO.py:290-304 / misc/utils.py:99-107.  Everything that can be refused is refused before anything is queued.
+int hrn_warp_crops(hrn_handle h, const uint8_t *frames_dev, int nframes, int frame_h, int frame_w, const int32_t *frame_index_host,
+                   const double *matrices_host, int n, float *images_dev, void *stream) {
+    if (!h) return 1;
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (n < 0 || nframes < 0 || frame_h <= 0 || frame_w <= 0 || (n > 0 && (nframes < 1 || !frames_dev || !matrices_host || !images_dev))) {
+        h->err = "bad frames / matrices / n";
+        return 7;
+    }
+    if (frame_h > 32766 || frame_w > 32766) {   // OpenCV saturates source coordinates to int16
+        h->err = "hrn_warp_crops: a frame side above 32766 is not supported";
+        return 7;
+    }
+    if (n == 0) return 0;
+    if (!frame_index_host && nframes != n && nframes != 1) {
+        h->err = "hrn_warp_crops: without frame_index there must be one frame per crop, or one frame";
+        return 7;
+    }
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    const int H = h->H, W = h->W;
+    unsigned ring = 0;
+    WarpParams *wp = (WarpParams *)h->pre_stage((size_t)n * sizeof(WarpParams), &ring);
+    if (!wp) return 6;
+    for (int i = 0; i < n; ++i) {
+        const long f = frame_index_host ? (long)frame_index_host[i] : nframes == 1 ? 0 : i;
+        if (f < 0 || f >= nframes) {
+            h->err = "hrn_warp_crops: frame_index " + std::to_string(f) + " of crop " + std::to_string(i) + " is outside [0, " +
+                     std::to_string(nframes) + ")";
+            return 7;
+        }
+        WarpParams &p = wp[i];
+        p.frame = (int)f, p.pad_ = 0;
+        if (!invert_affine(matrices_host + (size_t)i * 6, p.m)) {
+            h->err = "hrn_warp_crops: matrix " + std::to_string(i) + " is not finite or singular";
+            return 7;
+        }
+        // the fixed point is 10 fractional bits in int32 in OpenCV: keep every source coordinate of the crop (an affine map
+        // takes its extremes at the corners) within 2^20
+        const double lim = 1048576.0;
+        for (int c = 0; c < 4; ++c) {
+            const double x = (c & 1) ? W - 1 : 0, y = (c & 2) ? H - 1 : 0;
+            const double sx = p.m[0] * x + p.m[1] * y + p.m[2], sy = p.m[3] * x + p.m[4] * y + p.m[5];
+            if (!(std::fabs(sx) <= lim) || !(std::fabs(sy) <= lim)) {
+                h->err = "hrn_warp_crops: matrix " + std::to_string(i) + " maps the crop beyond 2^20 pixels from the frame's origin";
+                return 7;
+            }
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (n > h->warp_params_cap) {   // grow: wait for whoever still reads the old array
+        if (h->warp_done && !h->hip_ok(hipEventSynchronize(h->warp_done), "hipEventSynchronize")) return 6;
+        if (h->warp_params) (void)hipFree(h->warp_params);
+        h->warp_params = nullptr, h->warp_params_cap = 0;
+        const int cap = std::max(n, 256);
+        if (!h->hip_ok(hipMalloc((void **)&h->warp_params, (size_t)cap * sizeof(WarpParams)), "hipMalloc(warp params)")) return 6;
+        h->warp_params_cap = cap;
+    }
+    if (h->warp_done && h->warp_stream != s && !h->hip_ok(hipStreamWaitEvent(s, h->warp_done, 0), "hipStreamWaitEvent")) return 6;
+    if (!h->warp_done && !h->hip_ok(hipEventCreateWithFlags(&h->warp_done, hipEventDisableTiming), "hipEventCreate")) return 6;
+    if (!h->hip_ok(hipMemcpyAsync(h->warp_params, wp, (size_t)n * sizeof(WarpParams), hipMemcpyHostToDevice, s), "hipMemcpyAsync(warp params)"))
+        return 6;
+    if (!h->hip_ok(hipEventRecord(h->pre_landed[ring], s), "hipEventRecord")) return 6;
+    const hipError_t e = launch_warp_crops(frames_dev, frame_h, frame_w, h->warp_params, n, images_dev, H, W, s);
+    h->warp_stream = s;
+    if (!h->hip_ok(hipEventRecord(h->warp_done, s), "hipEventRecord")) return 6;
+    return h->hip_ok(e, "warp launch") ? 0 : 8;
 }
 
 // Debug tap: one micro-batch with the named tensor copied out right after the launch that completes it.

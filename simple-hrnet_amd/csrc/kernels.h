@@ -203,6 +203,14 @@ struct ResizeTaps {
 };
 hipError_t launch_resize_frames(const unsigned char *frames_dev, int n, int src_h, int src_w, int interp, ResizeTaps *taps_dev,
                                 float *images_dev, int H, int W, hipStream_t s);
+// evaluation pre-path (warp.hip): cv2.warpAffine(INTER_LINEAR, zero border) of one crop out of one frame of the stack
+struct WarpParams {
+    double m[6];   // the INVERSE 2x3 matrix (crop -> frame), row-major, inverted on the host as cv::warpAffine does
+    int frame;     // index into the frame stack
+    int pad_;
+};
+hipError_t launch_warp_crops(const unsigned char *frames_dev, int frame_h, int frame_w, const WarpParams *params_dev, int n,
+                             float *images_dev, int H, int W, hipStream_t s);
 
 struct Stem7Args {         // PoseResNet conv1: 3->64 7x7 s2 p3 + BN + ReLU, NCHW fp32 in, flat padded out (poseresnet.py:25-27)
     const float *images;

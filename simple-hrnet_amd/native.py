@@ -41,6 +41,62 @@ def _device_index(device) -> int:
     return d.index if d.index is not None else torch.cuda.current_device()
 
 
+def _frame_stack(frames) -> torch.Tensor:
+    """``frames`` of ``warp_crops`` as an (F, Hf, Wf, 3) uint8 tensor (host or device, as given); ValueError otherwise"""
+    if not isinstance(frames, torch.Tensor):
+        frames = torch.from_numpy(np.ascontiguousarray(frames))
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+        raise ValueError("frames must be (Hf, Wf, 3) or (F, Hf, Wf, 3) uint8 BGR")
+    if max(int(frames.shape[1]), int(frames.shape[2])) > 32766 or min(int(frames.shape[1]), int(frames.shape[2])) < 1:
+        raise ValueError("frame sides must be in [1, 32766]")
+    return frames
+
+
+def _warp_arguments(nframes: int, size_wh, centers, scales, rotations, frame_index, pixel_std, matrices):
+    """the host-side arguments of ``hrn_warp_crops``: ``(matrices (n, 6) float64, frame_index (n,) int32)``, checked -- every
+    argument error is a ValueError here, before the library is called"""
+    from . import postproc
+
+    if matrices is not None:
+        if centers is not None or scales is not None or rotations is not None:
+            raise ValueError("give either centers / scales (/ rotations) or matrices, not both")
+        m = np.asarray(matrices, dtype=np.float64)
+        if m.ndim < 2 or m.size != m.shape[0] * 6 or tuple(m.shape[1:]) not in ((2, 3), (6,)):
+            raise ValueError("matrices must be (n, 2, 3) or (n, 6)")
+        m = np.ascontiguousarray(m.reshape(-1, 6))
+    else:
+        if centers is None or scales is None:
+            raise ValueError("centers and scales (or matrices) are needed")
+        c = np.asarray(centers)
+        n = len(c)
+        sc = np.asarray(scales)
+        rot = np.zeros(n) if rotations is None else np.asarray(rotations)
+        if c.shape != (n, 2) or sc.shape not in ((n, 2), (n,)) or rot.shape != (n,):
+            raise ValueError("centers must be (n, 2), scales (n, 2) or (n,), rotations (n,): got %s, %s, %s" % (c.shape, sc.shape, rot.shape))
+        m = np.empty((n, 6), np.float64)
+        for i in range(n):
+            m[i] = postproc.affine_matrix(c[i], sc[i], pixel_std, rot[i], size_wh).reshape(6)
+    n = len(m)
+    if not np.isfinite(m).all():
+        raise ValueError("a matrix is not finite")
+    if n and ((m[:, 0] * m[:, 4] - m[:, 1] * m[:, 3]) == 0).any():
+        raise ValueError("a matrix is singular")
+    if frame_index is None:
+        if nframes not in (1, n):
+            raise ValueError("without frame_index there must be one frame per crop, or one frame: %d frames, %d crops" % (nframes, n))
+        fi = np.zeros(n, np.int32) if nframes == 1 else np.arange(n, dtype=np.int32)
+    else:
+        fi = np.asarray(frame_index)
+        if fi.shape != (n,) or fi.dtype.kind not in "iu":
+            raise ValueError("frame_index must be %d integers" % n)
+        if n and (fi.min() < 0 or fi.max() >= nframes):
+            raise ValueError("frame_index outside [0, %d)" % nframes)
+        fi = np.ascontiguousarray(fi, dtype=np.int32)
+    return m, fi
+
+
 class NativeHRNet:
     """HRNet-W{c} pose network compiled to hand-written gfx950 kernels.
 
@@ -403,6 +459,61 @@ class NativeHRNet:
             self._check(rc, "hrn_resize_frames")
         return images
 
+    def warp_crops(self, frames, centers=None, scales=None, rotations=None, frame_index=None, pixel_std=200, matrices=None) -> torch.Tensor:
+        """The evaluation pre-path (``datasets/COCO.py:290-304``, ``misc/utils.py:99-107``) on the GPU: per person
+        ``cv2.warpAffine(image, get_affine_transform(center, scale, pixel_std, rot, (W, H)), (W, H), flags=cv2.INTER_LINEAR)``
+        + ToTensor + Normalize.
+
+        ``frames``: (Hf, Wf, 3) or (F, Hf, Wf, 3) uint8 BGR (host arrays are uploaded once); ``centers`` (n, 2) / ``scales``
+        (n, 2) or (n,) as the dataset provides them (``postproc.box_to_center_scale``), ``rotations`` (n,) in degrees -- or
+        explicit forward 2x3 ``matrices`` (n, 2, 3), frame -> crop.  ``frame_index`` (n,): the frame of each crop; None = crop i
+        reads frame i (F == n) or the one frame (F == 1).  Returns (n, 3, H, W) float32 on the GPU, for any n.
+        Follows warpAffine's 8-bit integer path (include/hrnet_mi355.h); equality with a particular cv2 build is not pinned."""
+        frames = _frame_stack(frames)
+        h, w = self.resolution
+        m, fi = _warp_arguments(int(frames.shape[0]), (w, h), centers, scales, rotations, frame_index, pixel_std, matrices)
+        frames = frames.to(self.torch_device, non_blocking=True).contiguous()
+        n = len(m)
+        images = torch.empty((n, 3, h, w), dtype=torch.float32, device=self.torch_device)
+        if n:
+            with torch.cuda.device(self.device_index):
+                rc = self._lib.hrn_warp_crops(self._h, frames.data_ptr(), int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2]),
+                                              fi.ctypes.data, m.ctypes.data, n, images.data_ptr(), self._stream())
+            self._check(rc, "hrn_warp_crops")
+        return images
+
+    def decode_eval(self, images: torch.Tensor, flip_pairs, flip: bool = True, post_processing: Union[bool, str] = True):
+        """heat-maps + evaluation decode of a crop batch: ``predict_flip_tta`` (``flip``), or one plain pass followed by the same
+        decode -- get_max_preds (coordinates zeroed where the maximum is not positive), then the quarter-pixel or DARK offset.
+        Returns ``(heatmaps, preds (n,J,2) = (x, y) in heat-map pixels, maxvals (n,J,1))``."""
+        if flip:
+            return self.predict_flip_tta(images, flip_pairs, post_processing=post_processing)
+        if isinstance(post_processing, str) and post_processing != "dark":
+            raise ValueError("post_processing must be True, False or 'dark', got %r" % (post_processing,))
+        h, w = self.resolution
+        n = int(images.shape[0])
+        cells = torch.tensor([[0, 0, w // 4, h // 4]] * n, dtype=torch.float32).reshape(n, 4)   # pts come out in heat-map cells
+        hm, pts = self.predict_crops(images, cells, return_heatmaps=True)
+        maxvals = pts[:, :, 2:3].contiguous()
+        preds = torch.where(maxvals > 0, pts[:, :, [1, 0]], torch.zeros_like(maxvals))
+        if post_processing:
+            preds = self.refine_coords(hm, preds, "dark" if post_processing == "dark" else "quarter")
+        return hm, preds, maxvals
+
+    def predict_eval(self, frames, centers, scales, flip_pairs, frame_index=None, flip: bool = True,
+                     post_processing: Union[bool, str] = True, pixel_std=200):
+        """One batch of ``Test._test`` (``testing/Test.py:124-140``) + ``get_final_preds`` from uint8 images:
+        ``warp_crops`` -> ``predict_flip_tta`` (``flip=False``: one plain pass and the same decode) -> ``postproc.final_preds``.
+        ``frames`` / ``centers`` / ``scales`` / ``frame_index`` as in ``warp_crops`` (no rotation at test time);
+        ``post_processing`` as in ``predict_flip_tta``.  Returns ``(preds (n,J,2) float32 numpy = (x, y) in image pixels,
+        maxvals (n,J,1) on the GPU, heatmaps (n,J,H/4,W/4) on the GPU)``."""
+        from . import postproc
+
+        images = self.warp_crops(frames, centers, scales, frame_index=frame_index, pixel_std=pixel_std)
+        hm, preds, maxvals = self.decode_eval(images, flip_pairs, flip=flip, post_processing=post_processing)
+        h, w = self.resolution
+        return postproc.final_preds(preds, np.asarray(centers), np.asarray(scales), pixel_std, (w // 4, h // 4)), maxvals, hm
+
     def predict_frame(self, frame, detections, return_heatmaps: bool = False, variant: str = "pad", refine: Optional[str] = None):
         """pre-path + model + decode for one frame: what ``SimpleHRNet._predict_single`` does after the detector.
         Returns ``(boxes (P,4) int32 numpy, pts (P,J,3) on the GPU[, heatmaps])``.  ``refine``: as in ``predict_crops``."""
@@ -658,6 +769,36 @@ class MultiDeviceHRNet:
         outs = self._run(len(dets), work)
         return (torch.cat([o[0] for o in outs], 0), np.concatenate([b for b in boxes_np if b is not None], 0),
                 torch.cat([o[1] for o in outs], 0))
+
+    def warp_crops(self, frames, centers=None, scales=None, rotations=None, frame_index=None, pixel_std=200, matrices=None) -> torch.Tensor:
+        """``NativeHRNet.warp_crops`` with the crops split into index ranges: every device gets the frames once, cuts its range, and
+        the batch is gathered on the first one"""
+        frames = _frame_stack(frames)
+        h, w = self.resolution
+        m, fi = _warp_arguments(int(frames.shape[0]), (w, h), centers, scales, rotations, frame_index, pixel_std, matrices)
+        if len(m) == 0:
+            return self.nets[0].warp_crops(frames, matrices=m, frame_index=fi)
+        outs = self._run(len(m), lambda k, net, lo, hi: (net.warp_crops(frames, matrices=m[lo:hi], frame_index=fi[lo:hi]),))
+        return torch.cat([o[0] for o in outs], 0)
+
+    def predict_eval(self, frames, centers, scales, flip_pairs, frame_index=None, flip: bool = True,
+                     post_processing: Union[bool, str] = True, pixel_std=200):
+        """``NativeHRNet.predict_eval`` by the same split: each device warps, runs and decodes its range of people"""
+        from . import postproc
+
+        frames = _frame_stack(frames)
+        h, w = self.resolution
+        m, fi = _warp_arguments(int(frames.shape[0]), (w, h), centers, scales, None, frame_index, pixel_std, None)
+        if len(m) == 0:
+            return self.nets[0].predict_eval(frames, centers, scales, flip_pairs, frame_index, flip, post_processing, pixel_std)
+
+        def work(k, net, lo, hi):
+            images = net.warp_crops(frames, matrices=m[lo:hi], frame_index=fi[lo:hi])
+            return net.decode_eval(images, flip_pairs, flip=flip, post_processing=post_processing)
+
+        outs = self._run(len(m), work)
+        hm, preds, maxvals = (torch.cat([o[j] for o in outs], 0) for j in range(3))
+        return postproc.final_preds(preds, np.asarray(centers), np.asarray(scales), pixel_std, (w // 4, h // 4)), maxvals, hm
 
     def predict_frame(self, frame, detections, return_heatmaps: bool = False, variant: str = "pad", refine: Optional[str] = None):
         refine_code(refine)

@@ -164,6 +164,65 @@ def inverse_affine(center, scale, pixel_std, output_size) -> np.ndarray:
     return np.linalg.solve(a, b).reshape(2, 3)
 
 
+def _solve_affine(frm: np.ndarray, to: np.ndarray) -> np.ndarray:
+    """what ``cv2.getAffineTransform(frm, to)`` solves, three float32 point pairs -> the 2x3 float64 matrix: the same 6x6
+    system, the same LU solve as ``inverse_affine``"""
+    a = np.zeros((6, 6), np.float64)
+    b = np.zeros(6, np.float64)
+    for k in range(3):
+        a[2 * k, 0:3] = (frm[k, 0], frm[k, 1], 1.0)
+        a[2 * k + 1, 3:6] = (frm[k, 0], frm[k, 1], 1.0)
+        b[2 * k], b[2 * k + 1] = to[k, 0], to[k, 1]
+    return np.linalg.solve(a, b).reshape(2, 3)
+
+
+def affine_matrix(center, scale, pixel_std, rot, output_size, inv=0) -> np.ndarray:
+    """``get_affine_transform(center, scale, pixel_std, rot, output_size, inv=inv)`` in full (``misc/utils.py:46-96``): the
+    2x3 float64 matrix that takes image coordinates to crop coordinates (``inv=0``: what ``cv2.warpAffine`` /
+    ``NativeHRNet.warp_crops`` are given) or back (``inv=1``).  ``rot`` in degrees; ``output_size`` = (width, height).
+    The three point pairs are built as the reference builds them -- ``get_dir`` in float64 ``sin`` / ``cos``, then the float32
+    point arrays -- and ``cv2.getAffineTransform`` is replaced by the float64 solve ``inverse_affine`` uses: for ``rot = 0``,
+    ``inv = 1`` the two functions return the same bits."""
+    scale = np.asarray(scale)
+    if scale.ndim == 0:
+        scale = np.array([scale, scale])
+    scale_tmp = scale * 1.0 * pixel_std
+    src_w, dst_w, dst_h = scale_tmp[0], output_size[0], output_size[1]
+    shift = np.array([0, 0], dtype=np.float32)
+    rot_rad = np.pi * rot / 180
+    sn, cs = np.sin(rot_rad), np.cos(rot_rad)                # get_dir([0, src_w * -0.5], rot_rad)
+    src_point = [0, src_w * -0.5]
+    src_dir = [src_point[0] * cs - src_point[1] * sn, src_point[0] * sn + src_point[1] * cs]
+    dst_dir = np.array([0, dst_w * -0.5], np.float32)
+    src, dst = np.zeros((3, 2), dtype=np.float32), np.zeros((3, 2), dtype=np.float32)
+    src[0, :] = center + scale_tmp * shift
+    src[1, :] = center + src_dir + scale_tmp * shift
+    dst[0, :] = [dst_w * 0.5, dst_h * 0.5]
+    dst[1, :] = np.array([dst_w * 0.5, dst_h * 0.5]) + dst_dir
+    for pts in (src, dst):                                   # get_3rd_point: b + (-(a - b).y, (a - b).x)
+        direct = pts[0, :] - pts[1, :]
+        pts[2, :] = pts[1, :] + np.array([-direct[1], direct[0]], dtype=np.float32)
+    return _solve_affine(dst, src) if inv else _solve_affine(src, dst)
+
+
+def box_to_center_scale(box_xywh, aspect_ratio, pixel_std=200):
+    """``_box2cs`` / ``_xywh2cs`` (``datasets/COCO.py:394-413``): an ``(x, y, w, h)`` box -> ``(center (2,), scale (2,))``
+    float32, the box grown to ``aspect_ratio`` = crop width / crop height about its centre, in units of ``pixel_std`` pixels,
+    with the reference's 1.25 margin (applied unless ``center[0] == -1``)."""
+    x, y, w, h = box_xywh[:4]
+    center = np.zeros((2,), dtype=np.float32)
+    center[0] = x + w * 0.5
+    center[1] = y + h * 0.5
+    if w > aspect_ratio * h:
+        h = w * 1.0 / aspect_ratio
+    elif w < aspect_ratio * h:
+        w = h * aspect_ratio
+    scale = np.array([w * 1.0 / pixel_std, h * 1.0 / pixel_std], dtype=np.float32)
+    if center[0] != -1:
+        scale = scale * 1.25
+    return center, scale
+
+
 def transform_preds(coords, center, scale, pixel_std, output_size) -> np.ndarray:
     """``misc/utils.py:116-123``: (J, 2) heat-map coordinates of one crop -> image coordinates, float32.  With the
     ``preds`` of ``NativeHRNet.predict_flip_tta`` this completes ``get_final_preds`` (``misc/utils.py:154-180``)."""
