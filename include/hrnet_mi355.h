@@ -184,6 +184,71 @@ int hrn_warp_crops(hrn_handle h, const uint8_t *frames_dev, int nframes, int fra
 int hrn_forward_flip_tta(hrn_handle h, const void *images_dev, int n, const int32_t *flip_pairs_host, int npairs,
                          int post_processing, float *heatmaps_dev, float *preds_dev, float *maxvals_dev, void *stream);
 
+/* ---- scoring an evaluation batch: Gaussian targets, loss and PCK (testing/Test.py:141-157, training/COCO.py `_val`) ----
+ * The two numbers Test.py prints per batch, `loss_fn(output, target, target_weight)` and `ds.evaluate_accuracy(output, target)`,
+ * from heat-maps that stay on the device.
+ *
+ * Targets (datasets/COCO.py:460-515, `_generate_target`; heatmap_type 'gaussian'), per person and joint, from joints in CROP
+ * pixels (float64, after affine_transform: COCO.py:298-300 = postproc.joints_to_crop) and their visibility, with
+ * h = height / 4, w = width / 4, t = 3 * sigma:
+ *   mu = int(joint / 4 + 0.5) in float64, truncated towards zero (feat_stride = image_size / heatmap_size = 4);
+ *   weight = visibility, set to 0 when mu_x - t >= w or mu_y - t >= h or mu_x + t + 1 < 0 or mu_y + t + 1 < 0;
+ *   when weight > 0.5 the cells (x, y) of the map with |x - mu_x| <= t and |y - mu_y| <= t receive
+ *   g[(x - mu_x)^2 + (y - mu_y)^2], everything else is 0; target_weight = weight * joints_weight[j] (float32) when given.
+ *   A QUIRK KEPT: the test is `br < 0`, not `<= 0` -- a joint with mu = -(t + 1) on an axis keeps its weight although its
+ *   window misses the map: an all-zero target that enters the loss with full weight.
+ *   The table is this library's: g[d2] = float32(exp(-double(d2) / (2 sigma^2))), d2 = 0 .. 2 t^2, evaluated in float64 on the
+ *   host and rounded once (kept in the handle per sigma).  The reference evaluates numpy's float32 SIMD exp, which is not
+ *   correctly rounded and differs between numpy builds (1 ulp at sigma 2, up to 3 ulp at sigma 3 where this was written), so
+ *   the pin against it is "same support, values within a measured number of ulps", not bit equality.
+ * hrn_target_centers (no handle, host only): mu_out (n,J,2) int32 (x, y); draw_out (n,J) the weight before joints_weight;
+ *   target_weight_out (n,J); each may be NULL.  height / width: the crop resolution.  Errors: hrn_last_error(NULL).
+ * hrn_generate_targets: the (n,J,h,w) fp32 target maps on the device (for inspection, and for tests of the analytic mode cell
+ *   by cell) and target_weight_host (n,J) (may be NULL). */
+int hrn_target_centers(const double *joints, const float *vis, const float *joints_weight /* J or NULL */, int n, int J,
+                       int height, int width, double sigma, int32_t *mu_out, float *draw_out, float *target_weight_out);
+int hrn_generate_targets(hrn_handle h, const double *joints_host, const float *vis_host, const float *joints_weight_host,
+                         int n, double sigma, float *targets_dev, float *target_weight_host, void *stream);
+/* hrn_score_heatmaps: one pass over heatmaps_dev (n,J,h,w) fp32 (what hrn_forward / hrn_forward_flip_tta write), then one
+ * small kernel.  Every field of hrn_score_out is a DEVICE pointer the caller provides:
+ *   map_loss (n,J) fp64   L[i][j] = 0.5 / (h*w) * sum_p (double(o) * w - double(t) * w)^2, w = target_weight[i][j], every term
+ *                         and the sum in fp64, in an order fixed by (h, w): the same bits for a map in any batch, at any
+ *                         position, in both target modes
+ *   loss_mse fp64         mean(L) = JointsMSELoss(use_target_weight=True) (losses/loss.py:20-54)
+ *   loss_ohkm fp64        mean over persons of the mean of the ohkm_topk largest L[i][:] = JointsOHKMMSELoss
+ *                         (losses/loss.py:6-16, 73-92, with the module-level ohkm its forward means); NaN when ohkm_topk <= 0
+ *   preds, target_preds (n,J,2) fp32   get_max_preds (misc/utils.py:125-151): (x, y) of the first maximum (a NaN is a maximum,
+ *                         as torch.max has it), (0, 0) where the maximum is not > 0
+ *   maxvals (n,J) fp32    the maxima of the output maps
+ *   dists (J,n), acc (J), avg_acc fp32, cnt int32   calc_dists / dist_acc / evaluate_pck_accuracy (misc/utils.py:185-244) in
+ *                         float32 with the reference's operations: norm = (h / 10, w / 10) -- x is divided by h / 10 and y by
+ *                         w / 10, as written there --, dist = sqrt(dx*dx + dy*dy) of the normalised differences (no fused
+ *                         multiply-add) when target_x > 1 and target_y > 1, else -1; acc[j] = count(d < pck_thr) /
+ *                         count(d != -1) or -1; avg_acc = mean of the acc[j] >= 0 (0 when there is none), cnt their number
+ * Target source, exactly one of:
+ *   analytic  joints_host (n,J,2) float64 + vis_host (n,J) [+ joints_weight_host (J)] + sigma: t is the Gaussian above, looked
+ *             up in the table; nothing of target size is read or written.  target_preds = mu clamped to the map where the
+ *             window is drawn and meets the map, else (0, 0) -- the arg-max of that target map.
+ *   maps      targets_dev (n,J,h,w) fp32 + target_weight_host (n,J) as the dataset returns them (sigma is not read): any
+ *             tensor of that shape, e.g. another engine's heat-maps; its arg-max is taken in the same pass.
+ * Stream-ordered like hrn_forward (no synchronise inside), any n >= 0 (not bounded by max_batch; n = 0 gives NaN losses and
+ * cnt 0); the staging and the table live in the handle: nothing is allocated after the first call of a size class.
+ * Fails (code 7, nothing launched) on: a plan-only handle, n < 0, both or neither target source, maps that are not 16-byte
+ * aligned, sigma <= 0 or 3 * sigma not an integer (this library's restriction; the reference's configurations use 1, 2, 3), a
+ * joint that is not finite or whose joint / 4 + 0.5 does not fit an int32 (the reference's int() raises there), ohkm_topk > J,
+ * pck_thr not finite, a NULL field of hrn_score_out (the per-person arrays may be NULL when n is 0). */
+typedef struct {
+    double *loss_mse, *loss_ohkm;
+    float *avg_acc;
+    int32_t *cnt;
+    float *acc, *dists;
+    double *map_loss;
+    float *preds, *target_preds, *maxvals;
+} hrn_score_out;
+int hrn_score_heatmaps(hrn_handle h, const float *heatmaps_dev, int n, const float *targets_dev, const double *joints_host,
+                       const float *vis_host, const float *joints_weight_host, double sigma, const float *target_weight_host,
+                       float pck_thr, int ohkm_topk, const hrn_score_out *out_dev, void *stream);
+
 /* Sub-pixel joint decoding (opt-in; hrn_forward keeps the integer arg-max of SimpleHRNet.py:297-308).  Each mode works on
  * one raw heat-map H (h x w fp32, as the head writes it) and its integer arg-max (px, py) -- the first maximum of the
  * unsmoothed map -- and moves it by an offset (ox, oy) in cells:

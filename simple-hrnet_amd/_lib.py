@@ -20,6 +20,7 @@ if os.environ.get("HRN_LIB_TAG"):   # A/B runs of compile-time variants (tools/m
     LIB_PATH = LIB_PATH.replace(".so", "_%s.so" % os.environ["HRN_LIB_TAG"])
 SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "conv3x3_f32.hip", "bottleneck_chain.hip", "prepath.hip", "warp.hip", "nms.hip", "postproc.cpp", "hrnet_mi355.cpp",
            "decode.hip",   # heat-maps to joint coordinates: the plain and sub-pixel decodes, flip-TTA's decode
+           "score.hip",    # heat-maps against the ground truth: Gaussian targets, loss and PCK of an evaluation batch
            # fp16 instantiations of the three hand-scheduled kernel families (bodies shared through conv3x3_lds.inc / conv_s2.inc /
            # bottleneck_chain.inc): translation units of their own, so that each bf16 file still compiles to exactly its kernel set
            "conv3x3_lds_f16.hip", "conv_s2_f16.hip", "bottleneck_chain_f16.hip"]
@@ -169,6 +170,12 @@ class TapInfo(ctypes.Structure):
                 ("conv_index", ctypes.c_int32)]
 
 
+class ScoreOut(ctypes.Structure):
+    """hrn_score_out: device pointers, in the header's order"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("loss_mse", "loss_ohkm", "avg_acc", "cnt", "acc", "dists", "map_loss", "preds",
+                                                     "target_preds", "maxvals")]
+
+
 # every symbol include/hrnet_mi355.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 SYMBOLS = {
@@ -186,6 +193,10 @@ SYMBOLS = {
     "hrn_forward": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P]),
     "hrn_resize_frames": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
     "hrn_warp_crops": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P]),
+    "hrn_target_centers": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, _P, _P, _P]),
+    "hrn_generate_targets": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.c_double, _P, _P, _P]),
+    "hrn_score_heatmaps": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_double, _P, ctypes.c_float, ctypes.c_int,
+                                          ctypes.POINTER(ScoreOut), _P]),
     "hrn_preprocess_frame": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
     "hrn_forward_flip_tta": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
     "hrn_forward_refined": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]),

@@ -539,6 +539,12 @@
             warp_params = nullptr, warp_params_cap = 0;
             if (warp_done) (void)hipEventDestroy(warp_done);
             warp_done = nullptr;
+            if (score_joints) (void)hipFree(score_joints);
+            score_joints = nullptr, score_joints_cap = 0;
+            if (score_done) (void)hipEventDestroy(score_done);
+            score_done = nullptr;
+            for (auto &kv : score_tables) (void)hipFree(kv.second);
+            score_tables.clear();
             if (part_val) (void)hipFree(part_val);
             if (part_idx) (void)hipFree(part_idx);
             if (probs_dev) (void)hipFree(probs_dev);

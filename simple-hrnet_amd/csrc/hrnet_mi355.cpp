@@ -200,7 +200,49 @@ struct hrn_ctx {
     int warp_params_cap = 0;
     hipEvent_t warp_done = nullptr;
     hipStream_t warp_stream = nullptr;
-    uint64_t map_clock = 0;     // LRU stamp of the block-map slots
+    // scoring (hrn_score_heatmaps, hrn_generate_targets): the per-(crop, joint) records of the last call on the device, guarded
+    // like warp_params, and the Gaussian tables g[d2] = float32(exp(-d2 / (2 sigma^2))), d2 = 0 .. 2 t^2, by t = 3 sigma
+    ScoreJoint *score_joints = nullptr;
+    int64_t score_joints_cap = 0;
+    hipEvent_t score_done = nullptr;
+    hipStream_t score_stream = nullptr;
+    std::map<int, float *> score_tables;
+    const float *score_table(int t, double sigma) {   // built in fp64 and rounded once, on the first call with this sigma
+        auto it = score_tables.find(t);
+        if (it != score_tables.end()) return it->second;
+        std::vector<float> g((size_t)2 * t * t + 1);
+        for (size_t d2 = 0; d2 < g.size(); ++d2) g[d2] = (float)std::exp(-(double)d2 / (2.0 * sigma * sigma));
+        float *dev = nullptr;
+        if (!hip_ok(hipMalloc((void **)&dev, g.size() * sizeof(float)), "hipMalloc(Gaussian table)")) return nullptr;
+        if (!hip_ok(hipMemcpy(dev, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(Gaussian table)")) {
+            (void)hipFree(dev);
+            return nullptr;
+        }
+        return score_tables[t] = dev;
+    }
+    // `count` records from image `ring` of the pinned staging ring to the device array (grown on demand; a call on ANOTHER
+    // stream than the previous one rewrites it only after that one's kernels have read it); score_ran() goes behind the launches
+    bool score_upload(const ScoreJoint *pinned, unsigned ring, int64_t count, hipStream_t s) {
+        if (count > score_joints_cap) {
+            if (score_done && !hip_ok(hipEventSynchronize(score_done), "hipEventSynchronize")) return false;
+            if (score_joints) (void)hipFree(score_joints);
+            score_joints = nullptr, score_joints_cap = 0;
+            const int64_t cap = std::max<int64_t>(count, 256 * 17);
+            if (!hip_ok(hipMalloc((void **)&score_joints, (size_t)cap * sizeof(ScoreJoint)), "hipMalloc(score records)")) return false;
+            score_joints_cap = cap;
+        }
+        if (score_done && score_stream != s && !hip_ok(hipStreamWaitEvent(s, score_done, 0), "hipStreamWaitEvent")) return false;
+        if (!score_done && !hip_ok(hipEventCreateWithFlags(&score_done, hipEventDisableTiming), "hipEventCreate")) return false;
+        if (!hip_ok(hipMemcpyAsync(score_joints, pinned, (size_t)count * sizeof(ScoreJoint), hipMemcpyHostToDevice, s),
+                    "hipMemcpyAsync(score records)"))
+            return false;
+        return hip_ok(hipEventRecord(pre_landed[ring], s), "hipEventRecord");
+    }
+    bool score_ran(hipStream_t s) {
+        score_stream = s;
+        return hip_ok(hipEventRecord(score_done, s), "hipEventRecord");
+    }
+    uint64_t map_clock = 0;    // LRU stamp of the block-map slots
     int64_t map_builds = 0;     // block maps built + uploaded since creation (hrn_map_rebuilds)
     float *scratch_hm = nullptr;  // max_batch heat-maps of the handle's own: flip-TTA's mirrored pass, a refined decode the caller gave no maps
     float *scratch_heatmaps() {   // allocated on first use; nullptr (and err) if that fails
@@ -702,6 +744,158 @@ int hrn_warp_crops(hrn_handle h, const uint8_t *frames_dev, int nframes, int fra
     h->warp_stream = s;
     if (!h->hip_ok(hipEventRecord(h->warp_done, s), "hipEventRecord")) return 6;
     return h->hip_ok(e, "warp launch") ? 0 : 8;
+}
+
+extern "C++" {
+namespace {
+// datasets/COCO.py:466-488, 512-513 for n persons: mu = int(joint / feat_stride + 0.5) (float64, truncated towards zero; the
+// stride is image_size / heatmap_size = 4), ul = mu - t, br = mu + t + 1, weight = visibility, 0 when ul >= size or br < 0 on
+// either axis (`br < 0`, not `<= 0`: a window that ends exactly at the map's edge keeps its weight and draws nothing).
+// Any of the outputs may be NULL.  Returns "" or what is wrong with the arguments; nothing is written then.
+std::string target_centers(const double *joints, const float *vis, const float *joints_weight, int n, int J, int height, int width,
+                           double sigma, int32_t *mu_out, float *draw_out, float *target_weight_out, ScoreJoint *recs) {
+    if (n < 0 || J <= 0 || (n > 0 && (!joints || !vis))) return "bad joints / visibility / n";
+    if (height <= 0 || width <= 0 || height % 32 || width % 32) return "resolution must be a positive multiple of 32 in both dimensions";
+    const double t_real = 3.0 * sigma;
+    if (!(sigma > 0) || !std::isfinite(sigma) || t_real != std::floor(t_real) || t_real > 1024)
+        return "sigma must be positive with 3 * sigma an integer (at most 1024)";
+    const long long t = (long long)t_real, h = height / 4, w = width / 4;
+    const double stride_x = (double)width / (double)w, stride_y = (double)height / (double)h;
+    for (size_t k = 0; k < (size_t)n * J; ++k) {   // everything is checked before anything is written
+        const double fx = joints[2 * k] / stride_x + 0.5, fy = joints[2 * k + 1] / stride_y + 0.5;
+        if (!std::isfinite(joints[2 * k]) || !std::isfinite(joints[2 * k + 1]) || !(std::fabs(fx) < 2147483648.0) ||
+            !(std::fabs(fy) < 2147483648.0))
+            return "joint " + std::to_string(k % J) + " of person " + std::to_string(k / J) + " is not finite or does not fit an int32 in heat-map cells";
+    }
+    for (size_t k = 0; k < (size_t)n * J; ++k) {
+        const long long mx = (long long)(joints[2 * k] / stride_x + 0.5), my = (long long)(joints[2 * k + 1] / stride_y + 0.5);
+        const bool off = mx - t >= w || my - t >= h || mx + t + 1 < 0 || my + t + 1 < 0;
+        const float v = off ? 0.f : vis[k];
+        const bool draw = v > 0.5f && mx + t + 1 > 0 && my + t + 1 > 0;   // (the window meets the map)
+        const float tw = joints_weight ? v * joints_weight[k % J] : v;
+        if (mu_out) mu_out[2 * k] = (int32_t)mx, mu_out[2 * k + 1] = (int32_t)my;
+        if (draw_out) draw_out[k] = v;
+        if (target_weight_out) target_weight_out[k] = tw;
+        if (recs) recs[k] = ScoreJoint{draw ? (int)mx : 0, draw ? (int)my : 0, tw, draw ? 1 : 0};
+    }
+    return "";
+}
+}  // namespace
+}  // extern "C++"
+
+int hrn_target_centers(const double *joints, const float *vis, const float *joints_weight, int n, int J, int height, int width,
+                       double sigma, int32_t *mu_out, float *draw_out, float *target_weight_out) {
+    g_create_error = target_centers(joints, vis, joints_weight, n, J, height, width, sigma, mu_out, draw_out, target_weight_out, nullptr);
+    if (!g_create_error.empty()) g_create_error = "hrn_target_centers: " + g_create_error;
+    return g_create_error.empty() ? 0 : 7;
+}
+
+// datasets/COCO.py:460-515 for a batch.  Everything that can be refused is refused before anything is queued.
+int hrn_generate_targets(hrn_handle h, const double *joints_host, const float *vis_host, const float *joints_weight_host, int n,
+                         double sigma, float *targets_dev, float *target_weight_host, void *stream) {
+    if (!h) return 1;
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (n < 0 || (n > 0 && !targets_dev) || ((uintptr_t)targets_dev & 15)) {
+        h->err = "hrn_generate_targets: bad targets / n (targets must be 16-byte aligned)";
+        return 7;
+    }
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    const int64_t count = (int64_t)n * h->joints;
+    unsigned ring = 0;
+    ScoreJoint *recs = (ScoreJoint *)h->pre_stage((size_t)std::max<int64_t>(count, 1) * sizeof(ScoreJoint), &ring);
+    if (!recs) return 6;
+    const std::string bad = target_centers(joints_host, vis_host, joints_weight_host, n, h->joints, h->H, h->W, sigma, nullptr, nullptr,
+                                           target_weight_host, recs);
+    if (!bad.empty()) {
+        h->err = "hrn_generate_targets: " + bad;
+        return 7;
+    }
+    if (n == 0) return 0;
+    ScoreArgs a{};
+    a.t = (int)(3.0 * sigma);
+    a.table = h->score_table(a.t, sigma);
+    if (!a.table) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    if (!h->score_upload(recs, ring, count, s)) return 6;
+    a.joints = h->score_joints, a.n = n, a.J = h->joints, a.h = h->H / 4, a.w = h->W / 4;
+    const hipError_t e = launch_targets(a, targets_dev, s);
+    if (!h->score_ran(s)) return 6;
+    return h->hip_ok(e, "targets launch") ? 0 : 8;
+}
+
+// testing/Test.py:141-157: loss_fn(output, target, target_weight) and evaluate_pck_accuracy(output, target) of one batch.
+int hrn_score_heatmaps(hrn_handle h, const float *heatmaps_dev, int n, const float *targets_dev, const double *joints_host,
+                       const float *vis_host, const float *joints_weight_host, double sigma, const float *target_weight_host,
+                       float pck_thr, int ohkm_topk, const hrn_score_out *out_dev, void *stream) {
+    if (!h) return 1;
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (n < 0 || (n > 0 && !heatmaps_dev)) {
+        h->err = "hrn_score_heatmaps: bad heatmaps / n";
+        return 7;
+    }
+    if (((uintptr_t)heatmaps_dev | (uintptr_t)targets_dev) & 15) {
+        h->err = "hrn_score_heatmaps: heatmaps / targets must be 16-byte aligned (the maps are read with 16-byte loads)";
+        return 7;
+    }
+    const bool maps = targets_dev != nullptr, analytic = joints_host != nullptr;
+    if (maps == analytic) {
+        h->err = "hrn_score_heatmaps: give either targets (with target_weight) or joints (with visibility), not both and not neither";
+        return 7;
+    }
+    if (maps ? (!target_weight_host || vis_host || joints_weight_host) : (!vis_host || target_weight_host != nullptr)) {
+        h->err = maps ? "hrn_score_heatmaps: target maps come with target_weight and without visibility / joints_weight"
+                      : "hrn_score_heatmaps: joints come with visibility and without target_weight";
+        return 7;
+    }
+    if (!std::isfinite(pck_thr)) {
+        h->err = "hrn_score_heatmaps: pck_thr is not finite";
+        return 7;
+    }
+    if (ohkm_topk > h->joints) {
+        h->err = "hrn_score_heatmaps: ohkm_topk " + std::to_string(ohkm_topk) + " exceeds the " + std::to_string(h->joints) + " joints";
+        return 7;
+    }
+    if (!out_dev || !out_dev->loss_mse || !out_dev->loss_ohkm || !out_dev->avg_acc || !out_dev->cnt || !out_dev->acc ||
+        (n > 0 && (!out_dev->dists || !out_dev->map_loss || !out_dev->preds || !out_dev->target_preds || !out_dev->maxvals))) {
+        h->err = "hrn_score_heatmaps: every field of hrn_score_out must point to device memory (the per-person ones unless n is 0)";
+        return 7;
+    }
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    const int64_t count = (int64_t)n * h->joints;
+    unsigned ring = 0;
+    ScoreJoint *recs = (ScoreJoint *)h->pre_stage((size_t)std::max<int64_t>(count, 1) * sizeof(ScoreJoint), &ring);
+    if (!recs) return 6;
+    ScoreArgs a{};
+    if (analytic) {
+        const std::string bad = target_centers(joints_host, vis_host, joints_weight_host, n, h->joints, h->H, h->W, sigma, nullptr, nullptr,
+                                               nullptr, recs);
+        if (!bad.empty()) {
+            h->err = "hrn_score_heatmaps: " + bad;
+            return 7;
+        }
+        a.t = (int)(3.0 * sigma);
+        a.table = h->score_table(a.t, sigma);
+        if (!a.table) return 6;
+    } else {
+        for (int64_t k = 0; k < count; ++k) recs[k] = ScoreJoint{0, 0, target_weight_host[k], 0};
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (count > 0 && !h->score_upload(recs, ring, count, s)) return 6;
+    if (!h->score_done && !h->hip_ok(hipEventCreateWithFlags(&h->score_done, hipEventDisableTiming), "hipEventCreate")) return 6;
+    a.heatmaps = heatmaps_dev, a.targets = targets_dev, a.joints = h->score_joints;
+    a.n = n, a.J = h->joints, a.h = h->H / 4, a.w = h->W / 4;
+    a.map_loss = out_dev->map_loss, a.preds = out_dev->preds, a.target_preds = out_dev->target_preds, a.maxvals = out_dev->maxvals;
+    a.loss_mse = out_dev->loss_mse, a.loss_ohkm = out_dev->loss_ohkm, a.avg_acc = out_dev->avg_acc, a.acc = out_dev->acc;
+    a.dists = out_dev->dists, a.cnt = out_dev->cnt, a.pck_thr = pck_thr, a.ohkm_topk = ohkm_topk;
+    const hipError_t e = launch_score(a, s);
+    if (!h->score_ran(s)) return 6;
+    return h->hip_ok(e, "score launch") ? 0 : 8;
 }
 
 // Debug tap: one micro-batch with the named tensor copied out right after the launch that completes it.

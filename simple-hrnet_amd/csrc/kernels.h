@@ -290,6 +290,32 @@ struct TtaArgs {           // flip-TTA combine + get_max_preds + quarter-pixel r
 };
 hipError_t launch_tta_decode(const TtaArgs &a, hipStream_t s);
 
+// Scoring of an evaluation batch (score.hip; include/hrnet_mi355.h: hrn_score_heatmaps, hrn_generate_targets)
+struct ScoreJoint {        // one (crop, joint), prepared on the host (datasets/COCO.py:477-488)
+    int mu_x, mu_y;        // centre of the Gaussian in heat-map cells; meaningful where draw != 0
+    float weight;          // target_weight[i][j] as the dataset returns it (visibility, 0 off the map, times joints_weight)
+    int draw;              // 1: the window [mu - t, mu + t] is drawn and meets the map; 0: the target map is all zero
+};
+struct ScoreArgs {
+    const float *heatmaps;     // (n,J,h,w) fp32: the output maps
+    const float *targets;      // maps mode: (n,J,h,w) fp32; analytic mode: nullptr
+    const ScoreJoint *joints;  // n*J entries (maps mode reads `weight` only)
+    const float *table;        // analytic mode: g[d2] = float32(exp(-d2 / (2 sigma^2))), d2 = 0 .. 2 t^2
+    int t;                     // 3 * sigma
+    int n, J, h, w;
+    double *map_loss;          // (n,J)
+    float *preds, *target_preds;   // (n,J,2) (x, y), zeroed where the maximum is not positive (get_max_preds)
+    float *maxvals;            // (n,J)
+    // the finish: scalars and the PCK
+    double *loss_mse, *loss_ohkm;
+    float *avg_acc, *acc, *dists;  // (), (J), (J,n)
+    int *cnt;
+    float pck_thr;
+    int ohkm_topk;
+};
+hipError_t launch_score(const ScoreArgs &a, hipStream_t s);            // score_kernel<analytic | maps>, then score_finish_kernel
+hipError_t launch_targets(const ScoreArgs &a, float *targets_out, hipStream_t s);   // targets_kernel: (n,J,h,w) from joints / table
+
 struct TapArgs {           // debug tap: crops crop0, crop0 + crop_step, ... of a flat padded tensor -> (ncrops, c, h, w) fp32
     const void *in;
     float *dst;

@@ -514,6 +514,113 @@ class NativeHRNet:
         h, w = self.resolution
         return postproc.final_preds(preds, np.asarray(centers), np.asarray(scales), pixel_std, (w // 4, h // 4)), maxvals, hm
 
+    # -- scoring an evaluation batch (testing/Test.py:141-157) ---------------------------------------
+    def _joint_arguments(self, joints, visibility, joints_weight):
+        """host arguments of the analytic target source: ``(joints (n,J,2) float64, visibility (n,J) float32, joints_weight (J,)
+        float32 or None)``; ``visibility`` may be (n,J) or the dataset's (n,J,k), whose column 0 is read (``COCO.py:467``)"""
+        J = self.nof_joints
+        jt = np.asarray(joints.cpu() if isinstance(joints, torch.Tensor) else joints, dtype=np.float64)
+        if jt.ndim != 3 or jt.shape[1] != J or jt.shape[2] < 2:
+            raise ValueError("joints must be (n, %d, 2), got %s" % (J, jt.shape))
+        jt = np.ascontiguousarray(jt[:, :, :2])
+        vis = np.asarray(visibility.cpu() if isinstance(visibility, torch.Tensor) else visibility, dtype=np.float32)
+        if vis.ndim == 3:
+            vis = vis[:, :, 0]
+        if vis.shape != jt.shape[:2]:
+            raise ValueError("visibility must be (n, %d) or (n, %d, k), got %s" % (J, J, vis.shape))
+        vis = np.ascontiguousarray(vis)
+        jw = None
+        if joints_weight is not None:
+            jw = np.ascontiguousarray(np.asarray(joints_weight, dtype=np.float32).reshape(-1))
+            if jw.shape != (J,):
+                raise ValueError("joints_weight must hold %d values" % J)
+        return jt, vis, jw
+
+    def generate_targets(self, joints, visibility, sigma=2, joints_weight=None):
+        """``_generate_target`` (``datasets/COCO.py:460-515``) for a batch, on the GPU: ``joints`` (n,J,2) in crop pixels (float64,
+        ``postproc.joints_to_crop``), ``visibility`` (n,J) or (n,J,k).  Returns ``(targets (n,J,H/4,W/4) float32 on the GPU,
+        target_weight (n,J,1) float32 numpy)``.  The Gaussian table is the library's (include/hrnet_mi355.h)."""
+        jt, vis, jw = self._joint_arguments(joints, visibility, joints_weight)
+        n, (h, w) = len(jt), self.resolution
+        targets = torch.empty((n, self.nof_joints, h // 4, w // 4), dtype=torch.float32, device=self.torch_device)
+        tw = np.empty((n, self.nof_joints, 1), np.float32)
+        with torch.cuda.device(self.device_index):
+            rc = self._lib.hrn_generate_targets(self._h, jt.ctypes.data, vis.ctypes.data, None if jw is None else jw.ctypes.data, n,
+                                                float(sigma), targets.data_ptr(), tw.ctypes.data, self._stream())
+        self._check(rc, "hrn_generate_targets")
+        return targets, tw
+
+    def score_heatmaps(self, heatmaps, joints=None, visibility=None, targets=None, target_weight=None, sigma=2, joints_weight=None,
+                       thr: float = 0.5, topk: int = 0) -> Dict:
+        """Loss and PCK of a batch of heat-maps against its ground truth (``testing/Test.py:141-157``), on the GPU.
+
+        Target source: ``joints`` (n,J,2) in crop pixels + ``visibility`` [+ ``joints_weight``] + ``sigma`` -- the Gaussian targets
+        are evaluated inside the kernel, nothing of target size exists -- or ``targets`` (n,J,h,w) + ``target_weight`` (n,J[,1])
+        as the dataset returns them (any tensor of that shape: another engine's heat-maps with weights of one).
+        Returns a dict of tensors on the GPU (stream-ordered, nothing is synchronised):
+        ``loss`` = ``JointsMSELoss``, ``loss_ohkm`` = ``JointsOHKMMSELoss(topk)`` (NaN for ``topk=0``), both float64 scalars;
+        ``accs`` (J,), ``avg_acc`` (), ``cnt`` () int32, ``joints_preds`` / ``joints_target`` (n,J,2) = the five values of
+        ``evaluate_pck_accuracy(output, target, thr=thr)``; ``dists`` (J,n), ``maxvals`` (n,J,1), ``map_loss`` (n,J) float64."""
+        h, w = self.resolution
+        J, dev = self.nof_joints, self.torch_device
+        hm = torch.as_tensor(heatmaps).to(dev, torch.float32).contiguous()
+        n = int(hm.shape[0]) if hm.dim() == 4 else -1
+        if tuple(hm.shape) != (n, J, h // 4, w // 4):
+            raise ValueError("heatmaps must be (n,%d,%d,%d), got %s" % (J, h // 4, w // 4, tuple(hm.shape)))
+        if (joints is None) == (targets is None):
+            raise ValueError("give either joints and visibility, or targets and target_weight")
+        jt = vis = jw = tg = tw = None
+        if joints is not None:
+            if visibility is None or target_weight is not None:
+                raise ValueError("joints come with visibility and without target_weight")
+            jt, vis, jw = self._joint_arguments(joints, visibility, joints_weight)
+            if len(jt) != n:
+                raise ValueError("%d heat-maps but %d persons" % (n, len(jt)))
+        else:
+            if target_weight is None or visibility is not None or joints_weight is not None:
+                raise ValueError("targets come with target_weight and without visibility / joints_weight")
+            tg = torch.as_tensor(targets).to(dev, torch.float32).contiguous()
+            tw = np.ascontiguousarray(np.asarray(target_weight.cpu() if isinstance(target_weight, torch.Tensor) else target_weight,
+                                                 dtype=np.float32).reshape(-1))
+            if tuple(tg.shape) != tuple(hm.shape) or tw.size != n * J:
+                raise ValueError("targets must have the heat-maps' shape and target_weight n*J entries")
+        f32, f64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.float64, device=dev)
+        t = {"loss_mse": torch.empty((), **f64), "loss_ohkm": torch.empty((), **f64), "avg_acc": torch.empty((), **f32),
+             "cnt": torch.empty((), dtype=torch.int32, device=dev), "acc": torch.empty((J,), **f32), "dists": torch.empty((J, n), **f32),
+             "map_loss": torch.empty((n, J), **f64), "preds": torch.empty((n, J, 2), **f32), "target_preds": torch.empty((n, J, 2), **f32),
+             "maxvals": torch.empty((n, J, 1), **f32)}
+        out = _lib.ScoreOut(**{k: v.data_ptr() for k, v in t.items()})
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data
+
+        with torch.cuda.device(self.device_index):
+            rc = self._lib.hrn_score_heatmaps(self._h, hm.data_ptr(), n, None if tg is None else tg.data_ptr(), ptr(jt), ptr(vis), ptr(jw),
+                                              float(sigma), ptr(tw), float(thr), int(topk), ctypes.byref(out), self._stream())
+        self._check(rc, "hrn_score_heatmaps")
+        return {"loss": t["loss_mse"], "loss_ohkm": t["loss_ohkm"], "accs": t["acc"], "avg_acc": t["avg_acc"], "cnt": t["cnt"],
+                "joints_preds": t["preds"], "joints_target": t["target_preds"], "dists": t["dists"], "maxvals": t["maxvals"],
+                "map_loss": t["map_loss"]}
+
+    def score_eval(self, frames, centers, scales, flip_pairs, gt_joints, gt_visibility, frame_index=None, flip: bool = True,
+                   post_processing: Union[bool, str] = True, pixel_std=200, sigma=2, joints_weight=None, thr: float = 0.5, topk: int = 0):
+        """``predict_eval`` plus the score of its heat-maps against the ground truth: one batch of ``Test._test``
+        (``testing/Test.py:124-157``) from uint8 images and the annotations.  ``gt_joints`` (n,J,2) in IMAGE pixels and
+        ``gt_visibility`` (n,J) or (n,J,k) as the dataset holds them; the joints are taken to crop pixels by the matrices the crops
+        are cut with (``postproc.joints_to_crop``).  Returns ``(predict_eval's tuple, score_heatmaps' dict)``."""
+        from . import postproc
+
+        h, w = self.resolution
+        c, s = np.asarray(centers), np.asarray(scales)
+        m = np.stack([postproc.affine_matrix(c[i], s[i], pixel_std, 0, (w, h)) for i in range(len(c))]) if len(c) else np.zeros((0, 2, 3))
+        crop_joints = postproc.joints_to_crop(gt_joints, gt_visibility, m)
+        self._joint_arguments(crop_joints, gt_visibility, joints_weight)   # argument errors before the network runs
+        out = self.predict_eval(frames, centers, scales, flip_pairs, frame_index=frame_index, flip=flip, post_processing=post_processing,
+                                pixel_std=pixel_std)
+        score = self.score_heatmaps(out[2], joints=crop_joints, visibility=gt_visibility, sigma=sigma, joints_weight=joints_weight,
+                                    thr=thr, topk=topk)
+        return out, score
+
     def predict_frame(self, frame, detections, return_heatmaps: bool = False, variant: str = "pad", refine: Optional[str] = None):
         """pre-path + model + decode for one frame: what ``SimpleHRNet._predict_single`` does after the detector.
         Returns ``(boxes (P,4) int32 numpy, pts (P,J,3) on the GPU[, heatmaps])``.  ``refine``: as in ``predict_crops``."""

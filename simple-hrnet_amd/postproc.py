@@ -242,3 +242,49 @@ def final_preds(preds, center, scale, pixel_std, heatmap_size) -> np.ndarray:
     for i in range(preds.shape[0]):
         out[i] = transform_preds(preds[i], center[i], scale[i], pixel_std, heatmap_size)
     return out
+
+
+def joints_to_crop(joints_image, visibility, matrices) -> np.ndarray:
+    """``affine_transform`` (``misc/utils.py:78-81``) of every visible ground-truth joint by its person's forward matrix
+    (``affine_matrix(..., inv=0)``, image -> crop), as ``datasets/COCO.py:298-300`` does before ``_generate_target``:
+    ``joints_image`` (n, J, 2) in image pixels, ``visibility`` (n, J) or (n, J, k) (column 0 is read), ``matrices`` (n, 2, 3).
+    Returns (n, J, 2) float64; a joint whose visibility is not > 0 is left as it is."""
+    jt = np.array(joints_image, dtype=np.float64)
+    vis = np.asarray(visibility)
+    if vis.ndim == 3:
+        vis = vis[:, :, 0]
+    m = np.asarray(matrices, dtype=np.float64)
+    if jt.ndim != 3 or jt.shape[2] < 2 or vis.shape != jt.shape[:2] or m.shape != (jt.shape[0], 2, 3):
+        raise ValueError("joints_image must be (n, J, 2), visibility (n, J) or (n, J, k), matrices (n, 2, 3): got %s, %s, %s"
+                         % (jt.shape, vis.shape, m.shape))
+    jt = np.ascontiguousarray(jt[:, :, :2])
+    for i in range(jt.shape[0]):
+        for j in range(jt.shape[1]):
+            if vis[i, j] > 0.:
+                jt[i, j] = np.dot(m[i], np.array([jt[i, j, 0], jt[i, j, 1], 1.]).T)[:2]
+    return jt
+
+
+def target_centers(joints, visibility, resolution, sigma=2, joints_weight=None):
+    """The host half of ``_generate_target`` (``datasets/COCO.py:466-488, 512-513``; ``hrn_target_centers``, no GPU): ``joints``
+    (n, J, 2) in crop pixels, ``visibility`` (n, J), ``resolution`` = (height, width) of the crop.  Returns ``(mu (n, J, 2) int32
+    = (x, y) in heat-map cells, weight (n, J) float32 before joints_weight, target_weight (n, J) float32)``."""
+    import ctypes
+
+    from . import _lib
+
+    jt = np.ascontiguousarray(np.asarray(joints, dtype=np.float64))
+    vis = np.ascontiguousarray(np.asarray(visibility, dtype=np.float32))
+    if jt.ndim != 3 or jt.shape[2] != 2 or vis.shape != jt.shape[:2]:
+        raise ValueError("joints must be (n, J, 2) and visibility (n, J), got %s and %s" % (jt.shape, vis.shape))
+    n, J = vis.shape
+    jw = None if joints_weight is None else np.ascontiguousarray(np.asarray(joints_weight, dtype=np.float32).reshape(-1))
+    if jw is not None and jw.shape != (J,):
+        raise ValueError("joints_weight must hold %d values" % J)
+    mu, draw, tw = np.empty((n, J, 2), np.int32), np.empty((n, J), np.float32), np.empty((n, J), np.float32)
+    lib = _lib.load()
+    rc = lib.hrn_target_centers(jt.ctypes.data, vis.ctypes.data, None if jw is None else jw.ctypes.data, n, J, int(resolution[0]),
+                                int(resolution[1]), ctypes.c_double(float(sigma)), mu.ctypes.data, draw.ctypes.data, tw.ctypes.data)
+    if rc != 0:
+        raise ValueError(lib.hrn_last_error(None).decode())
+    return mu, draw, tw
