@@ -62,8 +62,24 @@ typedef struct {
     double flops;         /* 2*MAC per crop                                                    */
 } hrn_conv_info;
 
+/* Largest nof_joints a handle takes (COCO 17, face 68 / 98 / 106, COCO-WholeBody 133, Halpe 136 ...).  The head works the
+ * joints in groups of 32 (two 16-row MFMA fragments); the bound is the size of flip-TTA's pair table, a kernel argument.
+ * Two invariants hold for every nof_joints in [1, HRN_MAX_JOINTS], in all three dtypes:
+ *   1. A joint's numbers do not depend on how many other joints the model has: its heat-map value is the same dot
+ *      product in the same K order plus its bias, and its arg-max follows the same order (first maximum; a NaN is a
+ *      maximum), whether it is one of 17 or of 133 -- a model holding only rows [32g, 32g + 32) of final_layer returns the
+ *      bits of those joints of the full model.
+ *   2. For nof_joints <= 32 the head is one group: the same kernels, grid, weight blob, launches per pass and bits as a
+ *      build without groups.
+ * The tail of the weight blob is final_layer: [nof_joints][c] fp32 weights, nof_joints fp32 biases, then (each padded to
+ * 256 bytes) the MFMA image, ceil(nof_joints / 32) groups of [2 fragments][ceil(c / 32) chunks][64 lanes][8 x 16 bit],
+ * group g = joints 32g .. 32g + 31 exactly as a head of those joints alone packs them, rows past the last joint zero.
+ * Cost at large J: a refined decode without caller heat-maps, and flip-TTA, keep max_batch * nof_joints * (H/4) * (W/4)
+ * fp32 of scratch in the handle, allocated on first use (256 x 133 x 96 x 72: 940 MB); size max_batch accordingly. */
+#define HRN_MAX_JOINTS 256
+
 /* Replaces `HRNet(c, nof_joints)` + `.to(device).eval()` (SimpleHRNet.py:110,141-142; graph of
- * models_/hrnet.py:75-155).  height/width = network input resolution (multiples of 32),
+ * models_/hrnet.py:75-155).  nof_joints in [1, HRN_MAX_JOINTS].  height/width = network input resolution (multiples of 32),
  * max_batch = largest micro-batch one internal pass will process (workspace is sized for it;
  * hrn_forward accepts any n and chunks internally like SimpleHRNet.py:285-294).
  * device_id >= 0: HIP device.  device_id < 0: plan-only handle (no GPU touched; graph,
@@ -179,7 +195,9 @@ int hrn_warp_crops(hrn_handle h, const uint8_t *frames_dev, int nframes, int fra
  *   preds    = arg-max of each map as (x, y) in heat-map pixels, zero where the maximum is <= 0, moved a quarter
  *              pixel towards the higher neighbour when post_processing != 0            -> preds_dev (n,J,2)
  *   maxvals  = the maxima                                                              -> maxvals_dev (n,J)
- * flip_pairs_host: npairs x 2 joint indices that swap under mirroring (COCO: datasets/COCO.py:113).  The inverse
+ * flip_pairs_host: npairs x 2 joint indices that swap under mirroring (COCO: datasets/COCO.py:113), each in
+ * [0, nof_joints) -- anything else fails with code 7 and nothing launched; any number of pairs up to the table of
+ * HRN_MAX_JOINTS joints.  Pairs that share a joint compose in order, as flip_back's in-place swaps do.  The inverse
  * affine of get_final_preds (transform_preds, cv2) stays with the caller. */
 int hrn_forward_flip_tta(hrn_handle h, const void *images_dev, int n, const int32_t *flip_pairs_host, int npairs,
                          int post_processing, float *heatmaps_dev, float *preds_dev, float *maxvals_dev, void *stream);

@@ -552,7 +552,8 @@
         }
         head_w_off = off, off = align_up(off + (int64_t)joints * head_c * 4, 256);
         head_b_off = off, off = align_up(off + joints * 4, 256);
-        head_wp_off = off, off = align_up(off + 2 * ((head_c + 31) / 32) * 1024, 256);  // bf16 MFMA image (head_mfma_kernel)
+        // bf16 MFMA image (head_mfma_kernel): one two-fragment image per group of 32 joints, group g behind group g - 1
+        head_wp_off = off, off = align_up(off + (int64_t)((joints + 31) / 32) * 2 * ((head_c + 31) / 32) * 1024, 256);
         blob_bytes = off;
 
         const int hw = (H / 4) * (W / 4);

@@ -146,17 +146,20 @@
                 return false;
             memcpy(host.data() + head_w_off, w, sizeof(float) * joints * c);
             memcpy(host.data() + head_b_off, b, sizeof(float) * joints);
-            // MFMA image: fragment f, chunk kc, lane (li, g): joint f*16 + li, k = kc*32 + g*8 + e
+            // MFMA image of joint group gr (joints 32 gr ..): fragment f, chunk kc, lane (li, g): joint 32*gr + f*16 + li,
+            // k = kc*32 + g*8 + e; rows past the last joint are zero.  Group gr lies behind group gr - 1, each the image a head of
+            // those 32 joints alone would have.
             const int kch = (c + 31) / 32;
             uint16_t *img = (uint16_t *)(host.data() + head_wp_off);
-            for (int f = 0; f < 2; ++f)
-                for (int kc = 0; kc < kch; ++kc)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int j = f * 16 + (lane & 15), k = kc * 32 + (lane >> 4) * 8 + e;
-                            img[((size_t)(f * kch + kc) * 64 + lane) * 8 + e] =
-                                (j < joints && k < c) ? to16(w[(size_t)j * c + k]) : (uint16_t)0;
-                        }
+            for (int gr = 0; gr < (joints + 31) / 32; ++gr)
+                for (int f = 0; f < 2; ++f)
+                    for (int kc = 0; kc < kch; ++kc)
+                        for (int lane = 0; lane < 64; ++lane)
+                            for (int e = 0; e < 8; ++e) {
+                                const int j = gr * 32 + f * 16 + (lane & 15), k = kc * 32 + (lane >> 4) * 8 + e;
+                                img[((size_t)((gr * 2 + f) * kch + kc) * 64 + lane) * 8 + e] =
+                                    (j < joints && k < c) ? to16(w[(size_t)j * c + k]) : (uint16_t)0;
+                            }
         }
         if (pack_overflow) {
             err = "a folded weight exceeds 65504 in magnitude: it has no fp16 representation (use dtype bf16 or fp32)";

@@ -348,8 +348,9 @@ int hrn_create_model(hrn_handle *out, int model, int c, int nof_joints, int heig
         g_create_error = "resolution must be a positive multiple of 32 in both dimensions";
         return 2;
     }
-    if (nof_joints <= 0 || nof_joints > 32) {
-        g_create_error = "nof_joints must be in [1, 32]";
+    static_assert(HRN_MAX_JOINTS == kMaxJoints, "the header's bound is the kernels' bound");
+    if (nof_joints <= 0 || nof_joints > HRN_MAX_JOINTS) {
+        g_create_error = "nof_joints must be in [1, HRN_MAX_JOINTS = " + std::to_string(HRN_MAX_JOINTS) + "]";
         return 2;
     }
     if (dtype != HRN_F32 && dtype != HRN_BF16 && dtype != HRN_F16) {
@@ -444,7 +445,7 @@ int hrn_forward_flip_tta(hrn_handle h, const void *images_dev, int n, const int3
         return 7;
     }
     TtaArgs a;
-    for (int j = 0; j < 32; ++j) a.pair[j] = j;
+    for (int j = 0; j < kMaxJoints; ++j) a.pair[j] = j;
     for (int k = 0; k < npairs; ++k) {
         const int p0 = flip_pairs_host[2 * k], p1 = flip_pairs_host[2 * k + 1];
         if (p0 < 0 || p1 < 0 || p0 >= h->joints || p1 >= h->joints) {

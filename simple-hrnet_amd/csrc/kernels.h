@@ -253,10 +253,11 @@ struct FuseGroupArgs {     // up to four independent fuse outputs in one launch;
 };
 hipError_t launch_fuse_group(int dtype, FuseGroupArgs &g, hipStream_t s);
 
+constexpr int kMaxJoints = 256;   // = HRN_MAX_JOINTS (include/hrnet_mi355.h): joints of a head, worked in groups of 32 (kernels.hip)
 struct HeadArgs {          // final 1x1 conv (+bias) and per-(crop, joint) partial arg-max
     const void *in;        // fused branch 0, flat padded, c channels
     const float *wgt;      // [joints][c] fp32
-    const void *wimg;      // bf16 mode: MFMA image of the weights, [2 frags][ceil(c/32) chunks][64 lanes][8 bf16]
+    const void *wimg;      // bf16 mode: MFMA image of the weights, [ceil(joints/32) groups][2 frags][ceil(c/32) chunks][64 lanes][8 bf16]
     const float *bias;     // [joints]
     float *heatmaps;       // (n,joints,h,w) fp32 NCHW or nullptr
     float *part_val;       // [n][joints][slabs]
@@ -285,7 +286,7 @@ struct TtaArgs {           // flip-TTA combine + get_max_preds + quarter-pixel r
     const float *hm_flipped;  // the mirrored crops' heat-maps
     float *preds;          // (n,joints,2): x, y in heat-map pixels
     float *maxvals;        // (n,joints)
-    int pair[32];          // joint j of the mirrored output is joint pair[j] (flip_back)
+    int pair[kMaxJoints];  // joint j of the mirrored output is joint pair[j] (flip_back); 1 KiB of the 4-KiB kernel-argument segment
     int n, joints, h, w, post_processing;
 };
 hipError_t launch_tta_decode(const TtaArgs &a, hipStream_t s);

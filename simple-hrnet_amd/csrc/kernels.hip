@@ -995,51 +995,57 @@ hipError_t launch_fuse_group(int dtype, FuseGroupArgs &g, hipStream_t s) {
 // Head: final_layer 1x1 conv c->joints WITH bias (hrnet.py:155,187), fp32 weights/accumulate.
 // grid = (slabs, n); each block scans slab_px pixels of one crop, optionally writes the NCHW fp32
 // heat-maps, and leaves one (max, first index) candidate per joint.
-constexpr int kMaxJoints = 32;
+//
+// Joints are worked in GROUPS of kJointGroup = 32 (two 16-row MFMA fragments); a block walks the groups one after the other
+// over its own slab, whose pixels it re-reads per group (a slab is at most 1024 pixels x c channels: it comes back from the
+// cache, not from HBM).  Group g of a J-joint head runs the arithmetic a head of joints [32g, 32g + 32) alone would, in the same
+// order: a joint's values and candidates do not depend on how many other joints the model has.  A head of up to 32 joints is
+// one group and runs head_kernel / head_mfma_kernel, which have no group loop -- the kernels they always were; more joints run
+// head_groups_kernel / head_mfma_groups_kernel.
+constexpr int kJointGroup = 32;
 
 // (arg-max order: kNoIdx / better / takes, argmax.h)
 
+// one joint group [j0, j0 + jn) of head_kernel; `again`: a previous group's wsh / red_v / red_i may still be read
 template <int DT>
-__global__ __launch_bounds__(256) void head_kernel(const HeadArgs p) {
+__device__ __forceinline__ void head_group(const HeadArgs &p, const int j0, const int jn, const bool again, float *wsh, float *red_v,
+                                           int *red_i) {
     using T = Tr<DT>;
     using vec = typename T::vec;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *wsh = smem;                       // [joints][c]
-    float *red_v = smem + p.joints * p.c;    // [4][joints]
-    int *red_i = (int *)(red_v + 4 * kMaxJoints);
-    for (int i = threadIdx.x; i < p.joints * p.c; i += 256) wsh[i] = p.wgt[i];
+    if (again) __syncthreads();
+    for (int i = threadIdx.x; i < jn * p.c; i += 256) wsh[i] = p.wgt[(size_t)j0 * p.c + i];
     __syncthreads();
     const int slab = blockIdx.x, n = blockIdx.y;
     const int hw = p.h * p.w;
     const int px_end = min(hw, (slab + 1) * p.slab_px);
-    float bv[kMaxJoints];
-    int bi[kMaxJoints];
+    float bv[kJointGroup];
+    int bi[kJointGroup];
 #pragma unroll
-    for (int j = 0; j < kMaxJoints; ++j) {
+    for (int j = 0; j < kJointGroup; ++j) {
         bv[j] = -INFINITY;
         bi[j] = kNoIdx;
     }
     for (int px = slab * p.slab_px + threadIdx.x; px < px_end; px += 256) {
         const int r = px / p.w, c = px - r * p.w;
         const typename T::elem *row = (const typename T::elem *)p.in + ((size_t)n * p.hpwp + r * p.wp + c) * p.c;
-        float acc[kMaxJoints];
+        float acc[kJointGroup];
 #pragma unroll
-        for (int j = 0; j < kMaxJoints; ++j) acc[j] = 0.f;
+        for (int j = 0; j < kJointGroup; ++j) acc[j] = 0.f;
         for (int c0 = 0; c0 < p.c; c0 += T::VEC) {
             const vec v = *(const vec *)(row + c0);
 #pragma unroll
             for (int e = 0; e < T::VEC; ++e) {
                 const float x = T::ld((typename T::elem)v[e]);
 #pragma unroll
-                for (int j = 0; j < kMaxJoints; ++j)
-                    if (j < p.joints) acc[j] = fmaf(x, wsh[j * p.c + c0 + e], acc[j]);
+                for (int j = 0; j < kJointGroup; ++j)
+                    if (j < jn) acc[j] = fmaf(x, wsh[j * p.c + c0 + e], acc[j]);
             }
         }
 #pragma unroll
-        for (int j = 0; j < kMaxJoints; ++j) {
-            if (j < p.joints) {
-                const float v = acc[j] + p.bias[j];
-                if (p.heatmaps) p.heatmaps[((size_t)n * p.joints + j) * hw + px] = v;
+        for (int j = 0; j < kJointGroup; ++j) {
+            if (j < jn) {
+                const float v = acc[j] + p.bias[j0 + j];
+                if (p.heatmaps) p.heatmaps[((size_t)n * p.joints + j0 + j) * hw + px] = v;
                 if (takes(v, bv[j], bi[j])) {  // px increases monotonically per thread: strict > keeps the first maximum
                     bv[j] = v;
                     bi[j] = px;
@@ -1049,8 +1055,8 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs p) {
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int j = 0; j < kMaxJoints; ++j) {
-        if (j < p.joints) {
+    for (int j = 0; j < kJointGroup; ++j) {
+        if (j < jn) {
             float v = bv[j];
             int i = bi[j];
 #pragma unroll
@@ -1063,49 +1069,67 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs p) {
                 }
             }
             if (lane == 0) {
-                red_v[wave * kMaxJoints + j] = v;
-                red_i[wave * kMaxJoints + j] = i;
+                red_v[wave * kJointGroup + j] = v;
+                red_i[wave * kJointGroup + j] = i;
             }
         }
     }
     __syncthreads();
-    if (threadIdx.x < p.joints) {
+    if (threadIdx.x < jn) {
         const int j = threadIdx.x;
         float v = red_v[j];
         int i = red_i[j];
         for (int w = 1; w < 4; ++w)
-            if (better(red_v[w * kMaxJoints + j], red_i[w * kMaxJoints + j], v, i)) {
-                v = red_v[w * kMaxJoints + j];
-                i = red_i[w * kMaxJoints + j];
+            if (better(red_v[w * kJointGroup + j], red_i[w * kJointGroup + j], v, i)) {
+                v = red_v[w * kJointGroup + j];
+                i = red_i[w * kJointGroup + j];
             }
-        p.part_val[((size_t)n * p.joints + j) * p.slabs + slab] = v;
-        p.part_idx[((size_t)n * p.joints + j) * p.slabs + slab] = i;
+        p.part_val[((size_t)n * p.joints + j0 + j) * p.slabs + slab] = v;
+        p.part_idx[((size_t)n * p.joints + j0 + j) * p.slabs + slab] = i;
     }
 }
 
-// 16-bit modes: the same head on MFMA.  D[joint][pixel] = W[joint][k] * X[k][pixel], joints padded to 32 (two
+// head_kernel: joints <= 32, one group and no loop around it -- the kernel of every head up to 32 joints, as it always was.
+// head_groups_kernel: more joints, the groups one after the other.
+template <int DT>
+__global__ __launch_bounds__(256) void head_kernel(const HeadArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *red_v = smem + p.joints * p.c;   // smem = [joints][c] weights, then [4][kJointGroup] values and indices
+    head_group<DT>(p, 0, p.joints, false, smem, red_v, (int *)(red_v + 4 * kJointGroup));
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void head_groups_kernel(const HeadArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *red_v = smem + kJointGroup * p.c;   // smem = [kJointGroup][c] weights of one group, then the wave merge
+    int *red_i = (int *)(red_v + 4 * kJointGroup);
+#pragma unroll 1
+    for (int j0 = 0; j0 < p.joints; j0 += kJointGroup)
+        head_group<DT>(p, j0, min(kJointGroup, p.joints - j0), j0 != 0, smem, red_v, red_i);
+}
+
+// 16-bit modes: the same head on MFMA.  D[joint][pixel] = W[joint][k] * X[k][pixel], the joints of a group padded to 32 (two
 // fragments), K = c padded to a multiple of 32 (weights zero there; the x operand is forced to zero too, so stray
 // bytes never meet the matrix unit).  Lane (li, g) ends up with joints 4g..4g+3 and 16+4g..16+4g+3 of pixel li:
 // a running (max, first index) per slot over the wave's 16 pixel fragments, then a 16-lane butterfly over li, then
-// the four waves through LDS.  wimg = [fragment][chunk][lane][8 bf16] (hrnet_mi355.cpp: load_weights).
+// the four waves through LDS.  wimg = [group][fragment][chunk][lane][8 bf16] (hrnet_mi355.cpp: load_weights).
+// one joint group [j0, j0 + jn) of head_mfma_kernel; `again`: a previous group's red_v / red_i may still be read
 template <int DT>
-__global__ __launch_bounds__(256) void head_mfma_kernel(const HeadArgs p) {
-    __shared__ float red_v[4 * kMaxJoints];
-    __shared__ int red_i[4 * kMaxJoints];
+__device__ __forceinline__ void head_mfma_group(const HeadArgs &p, const int j0, const int jn, const bool again, float *red_v, int *red_i) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, g = lane >> 4;
     const int slab = blockIdx.x, n = blockIdx.y;
     const int hw = p.h * p.w;
     const int kch = (p.c + 31) >> 5;
     const GLOBAL_AS unsigned short *__restrict__ in = (const GLOBAL_AS unsigned short *)p.in;
-    const GLOBAL_AS s16x8 *__restrict__ wimg = (const GLOBAL_AS s16x8 *)p.wimg;
+    const GLOBAL_AS s16x8 *__restrict__ wimg = (const GLOBAL_AS s16x8 *)p.wimg + (size_t)(j0 >> 4) * kch * 64;
     float bias[8];
 #pragma unroll
     for (int f = 0; f < 2; ++f)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = f * 16 + 4 * g + r;
-            bias[f * 4 + r] = j < p.joints ? p.bias[j] : 0.f;
+            bias[f * 4 + r] = j < jn ? p.bias[j0 + j] : 0.f;
         }
     float bv[8];
     int bi[8];
@@ -1135,12 +1159,13 @@ __global__ __launch_bounds__(256) void head_mfma_kernel(const HeadArgs p) {
             for (int q = 0; q < 4; ++q) {
                 const int t = f * 4 + q, j = f * 16 + 4 * g + q;
                 const float v = acc[f][q] + bias[t];
-                if (live && j < p.joints) {
-                    if (p.heatmaps) p.heatmaps[((size_t)n * p.joints + j) * hw + px] = v;
+                if (live && j < jn) {
+                    if (p.heatmaps) p.heatmaps[((size_t)n * p.joints + j0 + j) * hw + px] = v;
                     if (takes(v, bv[t], bi[t])) bv[t] = v, bi[t] = px;  // px grows with `it`: strict > keeps the first maximum
                 }
             }
     }
+    if (again) __syncthreads();
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
         float v = bv[t];
@@ -1152,41 +1177,60 @@ __global__ __launch_bounds__(256) void head_mfma_kernel(const HeadArgs p) {
             if (better(ov, oi, v, i)) v = ov, i = oi;
         }
         const int j = (t >> 2) * 16 + 4 * g + (t & 3);
-        if (li == 0 && j < kMaxJoints) red_v[wave * kMaxJoints + j] = v, red_i[wave * kMaxJoints + j] = i;
+        if (li == 0 && j < kJointGroup) red_v[wave * kJointGroup + j] = v, red_i[wave * kJointGroup + j] = i;
     }
     __syncthreads();
-    if (threadIdx.x < p.joints) {
+    if (threadIdx.x < jn) {
         const int j = threadIdx.x;
         float v = red_v[j];
         int i = red_i[j];
         for (int w = 1; w < 4; ++w)
-            if (better(red_v[w * kMaxJoints + j], red_i[w * kMaxJoints + j], v, i)) {
-                v = red_v[w * kMaxJoints + j];
-                i = red_i[w * kMaxJoints + j];
+            if (better(red_v[w * kJointGroup + j], red_i[w * kJointGroup + j], v, i)) {
+                v = red_v[w * kJointGroup + j];
+                i = red_i[w * kJointGroup + j];
             }
-        p.part_val[((size_t)n * p.joints + j) * p.slabs + slab] = v;
-        p.part_idx[((size_t)n * p.joints + j) * p.slabs + slab] = i;
+        p.part_val[((size_t)n * p.joints + j0 + j) * p.slabs + slab] = v;
+        p.part_idx[((size_t)n * p.joints + j0 + j) * p.slabs + slab] = i;
     }
+}
+
+template <int DT>   // joints <= 32
+__global__ __launch_bounds__(256) void head_mfma_kernel(const HeadArgs p) {
+    __shared__ float red_v[4 * kJointGroup];
+    __shared__ int red_i[4 * kJointGroup];
+    head_mfma_group<DT>(p, 0, p.joints, false, red_v, red_i);
+}
+
+template <int DT>   // more joints: the groups one after the other
+__global__ __launch_bounds__(256) void head_mfma_groups_kernel(const HeadArgs p) {
+    __shared__ float red_v[4 * kJointGroup];
+    __shared__ int red_i[4 * kJointGroup];
+#pragma unroll 1
+    for (int j0 = 0; j0 < p.joints; j0 += kJointGroup)
+        head_mfma_group<DT>(p, j0, min(kJointGroup, p.joints - j0), j0 != 0, red_v, red_i);
 }
 
 hipError_t launch_head(int dtype, const HeadArgs &a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
-    if (a.joints > kMaxJoints) return hipErrorInvalidValue;
+    if (a.joints <= 0 || a.joints > kMaxJoints) return hipErrorInvalidValue;
+    const bool groups = a.joints > kJointGroup;
     dim3 grid(a.slabs, a.n);
     if (dtype != DT_F32 && a.wimg && a.slab_px % 64 == 0) {
         if (dtype == DT_F16)
-            hipLaunchKernelGGL(head_mfma_kernel<DT_F16>, grid, dim3(256), 0, s, a);
+            hipLaunchKernelGGL(groups ? head_mfma_groups_kernel<DT_F16> : head_mfma_kernel<DT_F16>, grid, dim3(256), 0, s, a);
         else
-            hipLaunchKernelGGL(head_mfma_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
+            hipLaunchKernelGGL(groups ? head_mfma_groups_kernel<DT_BF16> : head_mfma_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
         return hipGetLastError();
     }
-    const size_t shm = sizeof(float) * ((size_t)a.joints * a.c + 4 * kMaxJoints) + sizeof(int) * 4 * kMaxJoints;
+    // the weight stage holds ONE group's rows: at most 32 x c floats (32 KiB at PoseResNet's c = 256), whatever the joint count
+    const int staged = groups ? kJointGroup : a.joints;
+    const size_t shm = sizeof(float) * ((size_t)staged * a.c + 4 * kJointGroup) + sizeof(int) * 4 * kJointGroup;
     if (dtype == DT_BF16)
-        hipLaunchKernelGGL(head_kernel<DT_BF16>, grid, dim3(256), shm, s, a);
+        hipLaunchKernelGGL(groups ? head_groups_kernel<DT_BF16> : head_kernel<DT_BF16>, grid, dim3(256), shm, s, a);
     else if (dtype == DT_F16)
-        hipLaunchKernelGGL(head_kernel<DT_F16>, grid, dim3(256), shm, s, a);
+        hipLaunchKernelGGL(groups ? head_groups_kernel<DT_F16> : head_kernel<DT_F16>, grid, dim3(256), shm, s, a);
     else
-        hipLaunchKernelGGL(head_kernel<DT_F32>, grid, dim3(256), shm, s, a);
+        hipLaunchKernelGGL(groups ? head_groups_kernel<DT_F32> : head_kernel<DT_F32>, grid, dim3(256), shm, s, a);
     return hipGetLastError();
 }
 

@@ -157,17 +157,21 @@ __global__ __launch_bounds__(SCORE_THREADS) void score_finish_kernel(const Score
         double row = 0.;
         for (int j = 0; j < J; ++j) row = row + L[j];
         mse = mse + row;
-        if (p.ohkm_topk > 0) {   // the topk largest of the row, largest first (J <= 32: one bit per joint already taken)
-            unsigned taken = 0;
-            double top = 0.;
+        if (p.ohkm_topk > 0) {   // the topk largest of the row, largest first
+            // No "already taken" set: the row is totally ordered by (value in topk's order, then joint index), and pick k is the
+            // first element of that order behind pick k - 1.  Among equal values the lower joint goes first, as a scan that
+            // skipped taken joints had it; any J, any topk <= J, O(topk * J) reads of a row that sits in the cache.
+            double top = 0., pv = 0.;
+            int pj = -1;
             for (int k = 0; k < p.ohkm_topk; ++k) {
                 int best = -1;
                 double bv = 0.;
                 for (int j = 0; j < J; ++j) {
                     const double v = L[j];
-                    if (!((taken >> j) & 1u) && (best < 0 || larger(v, bv))) best = j, bv = v;
+                    const bool behind = pj < 0 || larger(pv, v) || (!larger(v, pv) && j > pj);   // v comes after the last pick
+                    if (behind && (best < 0 || larger(v, bv))) best = j, bv = v;
                 }
-                taken |= 1u << best;
+                pv = bv, pj = best;
                 top = top + bv;
             }
             ohkm = ohkm + top / (double)p.ohkm_topk;
@@ -230,7 +234,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void targets_kernel(const ScoreArgs 
 namespace {
 // every map is h*w floats read as float4 groups that do not straddle a row
 bool score_shape_ok(const ScoreArgs &a) {
-    return a.n >= 0 && a.J > 0 && a.J <= 32 && a.h > 0 && a.w > 0 && a.w % 4 == 0 && (long long)a.n * a.J <= 0x7fffffffLL;
+    return a.n >= 0 && a.J > 0 && a.J <= kMaxJoints && a.h > 0 && a.w > 0 && a.w % 4 == 0 && (long long)a.n * a.J <= 0x7fffffffLL;
 }
 }  // namespace
 

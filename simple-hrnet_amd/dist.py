@@ -7,7 +7,7 @@ full heat-maps (470 KB/crop) to GPU 0.  Here:
   * weights: ONE broadcast of the packed blob (folded, MFMA-fragment layout) at start-up;
   * crops:   contiguous index ranges, rank r owns [r*ceil(N/G), min(N,(r+1)*ceil(N/G)))  -- every crop is
              independent (eval-mode BatchNorm), so there is no data-path collective inside the network;
-  * results: one all-gather of the decoded joints, 17*3*4 = 204 B per crop; heat-maps never leave their GPU.
+  * results: one all-gather of the decoded joints, 12 * J bytes per crop (204 B at 17 joints, 1596 B at 133); heat-maps never leave their GPU.
 """
 from __future__ import annotations
 
