@@ -143,6 +143,45 @@ int hrn_preprocess_frame(hrn_handle h, const uint8_t *frame_dev, int frame_h, in
                          int det_stride, int n, int variant, float *images_dev, int32_t *boxes_host, int32_t *boxes_dev,
                          void *stream);
 
+/* Crop pre-path for the people of MANY frames in one call: the multi-frame form of hrn_preprocess_frame.  Replaces the
+ * per-image loop of the stack path, SimpleHRNet.py:383-412 (HRN_CROP_CLAMP: one call instead of one hrn_preprocess_frame per
+ * image of the stack plus the `torch.cat` of :409-412 -- the crops are written once, where the model reads them), and the
+ * same loop around :236-278 (HRN_CROP_PAD) that scripts/extract-keypoints.py:88-123 runs frame after frame over a video file.
+ * One pair of launches cuts, pads, resizes and normalises every person; the frames may differ in size.
+ *   frames_host       nframes entries on the HOST: device pointer of a contiguous (height, width, 3) uint8 BGR frame and its size;
+ *                     a frame nobody refers to may be null
+ *   dets_host         (n, det_stride) float32 on the HOST, as hrn_preprocess_frame
+ *   frame_index_host  n entries on the HOST: person i is cut from frames_host[frame_index_host[i]]; people come in any order
+ *                     and the outputs keep the given order.  NULL: nframes == 1, everybody is cut from that frame
+ *   images_dev / boxes_host / boxes_dev / variant   as hrn_preprocess_frame; any n (not bounded by max_batch)
+ * Person for person the arithmetic, and so every bit of the result, is hrn_preprocess_frame's on that person's frame: both
+ * entries run the same two kernels, hrn_preprocess_frame with a one-frame table.
+ * Fails with code 7 and nothing launched on: a variant other than HRN_CROP_PAD / HRN_CROP_CLAMP; n < 0, det_stride < 4 or a
+ * null table / detections / output; a frame index outside [0, nframes); a frame a person refers to that is null or has a
+ * non-positive side; a plan-only handle; a detection that is degenerate, starts outside its frame, or is degenerate after
+ * clamping (the three failures of hrn_preprocess_frame, with its texts).  The arguments are judged before the handle's device
+ * is touched, so a plan-only handle reports a bad index or table as such. */
+typedef struct { const uint8_t *data; int32_t height, width; } hrn_frame;   /* device pointer, (height, width, 3) uint8 BGR, contiguous */
+int hrn_preprocess_frames(hrn_handle h, const hrn_frame *frames_host, int nframes, const float *dets_host, int det_stride,
+                          const int32_t *frame_index_host /* n entries; NULL: nframes == 1 */, int n, int variant,
+                          float *images_dev, int32_t *boxes_host, int32_t *boxes_dev, void *stream);
+
+/* The box arithmetic of the two entries above on the HOST, without a handle or a GPU: per detection -- round (half to even),
+ * correct the aspect ratio to height / width (SimpleHRNet.py:243-272 by padding, HRN_CROP_PAD; :396-407 by enlarging and
+ * clamping to the frame, HRN_CROP_CLAMP), slice as numpy does (:274, :408).
+ *   frame_hw       (n, 2) int32 (height, width) of each person's frame when per_person_hw != 0, else (1, 2) for all
+ *   height, width  the network's input size
+ *   boxes_out      (n, 4) int32 [x1,y1,x2,y2]: the boxes the decode scales by (may be NULL)
+ *   slice_out      (n, 8) int32: x1, y1, w_crop, h_crop = the part of the frame that is read; pad_top, pad_left = zero rows /
+ *                  columns in front of it; h_pad, w_pad = the size of the padded crop, the resize's input (may be NULL)
+ * Returns 0, or 7 with hrn_crop_geometry_last_error() (per thread) = "detection i is degenerate", "detection i starts outside
+ * the frame", "detection i is degenerate after clamping", "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP" or
+ * "bad frame / detections / n"; outputs of the detections before the failing one are written. */
+int hrn_crop_geometry(const float *dets, int det_stride, int n, const int32_t *frame_hw /* (n,2) or (1,2) */, int per_person_hw,
+                      int height, int width, int variant, int32_t *boxes_out /* (n,4) */,
+                      int32_t *slice_out /* (n,8): x1,y1,w_crop,h_crop,pad_top,pad_left,h_pad,w_pad */);
+const char *hrn_crop_geometry_last_error(void);
+
 /* Single-person pre-path on the GPU: replaces, for every frame of a call with multiperson=False,
  *   cv2.resize(image, (W, H), interpolation=self.interpolation); cv2.cvtColor(image, cv2.COLOR_BGR2RGB); self.transform(image)
  * (SimpleHRNet.py:213-222 for one frame, :355-366 for a stack; default interpolation cv2.INTER_CUBIC, :27) and writes the

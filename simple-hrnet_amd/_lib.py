@@ -176,6 +176,11 @@ class ScoreOut(ctypes.Structure):
                                                      "target_preds", "maxvals")]
 
 
+class Frame(ctypes.Structure):
+    """hrn_frame: one entry of hrn_preprocess_frames' frame table"""
+    _fields_ = [("data", ctypes.c_void_p), ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
+
+
 # every symbol include/hrnet_mi355.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 SYMBOLS = {
@@ -198,6 +203,9 @@ SYMBOLS = {
     "hrn_score_heatmaps": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_double, _P, ctypes.c_float, ctypes.c_int,
                                           ctypes.POINTER(ScoreOut), _P]),
     "hrn_preprocess_frame": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
+    "hrn_preprocess_frames": (ctypes.c_int, [_P, ctypes.POINTER(Frame), ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
+    "hrn_crop_geometry": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "hrn_crop_geometry_last_error": (ctypes.c_char_p, []),
     "hrn_forward_flip_tta": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
     "hrn_forward_refined": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
     "hrn_refine_coords": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),

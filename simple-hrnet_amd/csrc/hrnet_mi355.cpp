@@ -497,29 +497,75 @@ int hrn_refine_coords(hrn_handle h, const float *heatmaps_dev, int n, int refine
     return scope.leave() ? 0 : 6;
 }
 
-// SimpleHRNet.py:236-278.  The box arithmetic is Python's, restated in double: round() is round-half-even on a
-// float, `//` on non-negative ints is C's `/`, int(round(x)) = nearbyint under the default rounding mode.
-int hrn_preprocess_frame(hrn_handle h, const uint8_t *frame_dev, int frame_h, int frame_w, const float *dets_host,
-                         int det_stride, int n, int variant, float *images_dev, int32_t *boxes_host, int32_t *boxes_dev,
-                         void *stream) {
-    if (!h) return 1;
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
+namespace {
+// SimpleHRNet.py:236-278 (PAD) / :383-412 (CLAMP) for ONE detection in a frame of frame_h x frame_w, network input H x W.
+// The box arithmetic is Python's, restated in double: round() is round-half-even on a float, `//` on non-negative ints is
+// C's `/`, int(round(x)) = nearbyint under the default rounding mode.  Fills the slice / pad numbers of `cp` (tmp_off and the
+// frame are the caller's) and the reported box; false + err when the reference would wrap around or divide by zero.
+bool crop_geometry_one(const float *d, int i, int frame_h, int frame_w, int H, int W, int variant, CropParams &cp, int32_t *box,
+                       std::string &err) {
+    const long x1 = (long)std::nearbyint((double)d[0]), y1 = (long)std::nearbyint((double)d[1]);
+    const long x2 = (long)std::nearbyint((double)d[2]), y2 = (long)std::nearbyint((double)d[3]);
+    if (x2 <= x1 || y2 <= y1) {
+        err = "detection " + std::to_string(i) + " is degenerate";
+        return false;
     }
-    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
-        h->err = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
-        return 7;
+    const double cf = (double)H / (double)W * (double)(x2 - x1) / (double)(y2 - y1);
+    // The reference slices numpy arrays with these numbers: a negative start would wrap around.  The PAD variant
+    // slices with the rounded box itself; the CLAMP variant re-derives (and clamps to the frame) the side it
+    // enlarges, so only the OTHER side has to be inside the frame as given (SimpleHRNet.py:396-407).
+    const bool x_as_given = variant == HRN_CROP_PAD || !(cf < 1), y_as_given = variant == HRN_CROP_PAD || !(cf > 1);
+    if ((x_as_given && (x1 < 0 || x1 >= frame_w)) || (y_as_given && (y1 < 0 || y1 >= frame_h))) {
+        err = "detection " + std::to_string(i) + " starts outside the frame";
+        return false;
     }
-    if (n < 0 || det_stride < 4 || frame_h <= 0 || frame_w <= 0 || (n > 0 && (!frame_dev || !dets_host || !images_dev))) {
-        h->err = "bad frame / detections / n";
-        return 7;
+    long x1n = x1, x2n = x2, y1n = y1, y2n = y2, pt = 0, pb = 0, pl = 0, pr = 0;
+    long sx1 = x1, sy1 = y1, sx2 = x2, sy2 = y2;  // what is sliced out of the frame
+    if (variant == HRN_CROP_CLAMP) {  // SimpleHRNet.py:396-407: enlarge, clamp to the frame, slice the enlarged box
+        if (cf > 1) {
+            const long center = y1 + (y2 - y1) / 2;
+            const long length = (long)std::nearbyint((double)(y2 - y1) * cf);
+            y1n = std::max<long>(0, center - length / 2), y2n = std::min<long>(frame_h, center + length / 2);
+        } else if (cf < 1) {
+            const long center = x1 + (x2 - x1) / 2;
+            const long length = (long)std::nearbyint((double)(x2 - x1) * 1 / cf);
+            x1n = std::max<long>(0, center - length / 2), x2n = std::min<long>(frame_w, center + length / 2);
+        }
+        sx1 = x1n, sy1 = y1n, sx2 = x2n, sy2 = y2n;
+        if (sx2 <= sx1 || sy2 <= sy1 || sx1 >= frame_w || sy1 >= frame_h) {
+            err = "detection " + std::to_string(i) + " is degenerate after clamping";
+            return false;
+        }
+    } else if (cf > 1) {  // increase y side
+        const long center = y1 + (y2 - y1) / 2;
+        const long length = (long)std::nearbyint((double)(y2 - y1) * cf);
+        y1n = center - length / 2, y2n = center + length / 2;
+        pt = std::labs(y1n - y1), pb = std::labs(y2n - y2);
+    } else if (cf < 1) {
+        const long center = x1 + (x2 - x1) / 2;
+        const long length = (long)std::nearbyint((double)(x2 - x1) * 1 / cf);
+        x1n = center - length / 2, x2n = center + length / 2;
+        pl = std::labs(x1n - x1), pr = std::labs(x2n - x2);
     }
-    if (n == 0) return 0;
+    cp.x1 = (int)sx1, cp.y1 = (int)sy1;
+    cp.w_crop = (int)(std::min<long>(sx2, frame_w) - sx1), cp.h_crop = (int)(std::min<long>(sy2, frame_h) - sy1);  // numpy slicing
+    cp.pad_top = (int)pt, cp.pad_left = (int)pl;
+    cp.h_pad = cp.h_crop + (int)(pt + pb), cp.w_pad = cp.w_crop + (int)(pl + pr);
+    box[0] = (int32_t)x1n, box[1] = (int32_t)y1n, box[2] = (int32_t)x2n, box[3] = (int32_t)y2n;
+    return true;
+}
+
+thread_local std::string g_geometry_error;
+
+// the one body of hrn_preprocess_frame and hrn_preprocess_frames, behind their argument checks: person i is cut from
+// frames[fidx ? fidx[i] : 0]; everything that can be refused is refused before anything is queued
+int preprocess_people(hrn_handle h, const hrn_frame *frames, const int32_t *fidx, const float *dets_host, int det_stride, int n,
+                      int variant, float *images_dev, int32_t *boxes_host, int32_t *boxes_dev, hipStream_t s) {
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     const int H = h->H, W = h->W;
-    // crop parameters + boxes are written straight into a pinned image the async uploads below read after this call
-    // has returned; kPreRing images in rotation, each reused only once the upload that read it last has completed
+    // crop parameters (each with its frame's pointer and size: the frame table travels inside them) + boxes are written
+    // straight into a pinned image the async uploads below read after this call has returned; kPreRing images in rotation,
+    // each reused only once the upload that read it last has completed
     const size_t cp_bytes = ((size_t)n * sizeof(CropParams) + 63) / 64 * 64, need = cp_bytes + (size_t)n * 16;
     unsigned ring = 0;
     if (!h->pre_stage(need, &ring)) return 6;
@@ -528,62 +574,15 @@ int hrn_preprocess_frame(hrn_handle h, const uint8_t *frame_dev, int frame_h, in
     size_t tmp_bytes = 0;
     int max_h_pad = 0;
     for (int i = 0; i < n; ++i) {
-        const float *d = dets_host + (size_t)i * det_stride;
-        const long x1 = (long)std::nearbyint((double)d[0]), y1 = (long)std::nearbyint((double)d[1]);
-        const long x2 = (long)std::nearbyint((double)d[2]), y2 = (long)std::nearbyint((double)d[3]);
-        if (x2 <= x1 || y2 <= y1) {
-            h->err = "detection " + std::to_string(i) + " is degenerate";
-            return 7;
-        }
-        const double cf = (double)H / (double)W * (double)(x2 - x1) / (double)(y2 - y1);
-        // The reference slices numpy arrays with these numbers: a negative start would wrap around.  The PAD variant
-        // slices with the rounded box itself; the CLAMP variant re-derives (and clamps to the frame) the side it
-        // enlarges, so only the OTHER side has to be inside the frame as given (SimpleHRNet.py:396-407).
-        const bool x_as_given = variant == HRN_CROP_PAD || !(cf < 1), y_as_given = variant == HRN_CROP_PAD || !(cf > 1);
-        if ((x_as_given && (x1 < 0 || x1 >= frame_w)) || (y_as_given && (y1 < 0 || y1 >= frame_h))) {
-            h->err = "detection " + std::to_string(i) + " starts outside the frame";
-            return 7;
-        }
-        long x1n = x1, x2n = x2, y1n = y1, y2n = y2, pt = 0, pb = 0, pl = 0, pr = 0;
-        long sx1 = x1, sy1 = y1, sx2 = x2, sy2 = y2;  // what is sliced out of the frame
-        if (variant == HRN_CROP_CLAMP) {  // SimpleHRNet.py:396-407: enlarge, clamp to the frame, slice the enlarged box
-            if (cf > 1) {
-                const long center = y1 + (y2 - y1) / 2;
-                const long length = (long)std::nearbyint((double)(y2 - y1) * cf);
-                y1n = std::max<long>(0, center - length / 2), y2n = std::min<long>(frame_h, center + length / 2);
-            } else if (cf < 1) {
-                const long center = x1 + (x2 - x1) / 2;
-                const long length = (long)std::nearbyint((double)(x2 - x1) * 1 / cf);
-                x1n = std::max<long>(0, center - length / 2), x2n = std::min<long>(frame_w, center + length / 2);
-            }
-            sx1 = x1n, sy1 = y1n, sx2 = x2n, sy2 = y2n;
-            if (sx2 <= sx1 || sy2 <= sy1 || sx1 >= frame_w || sy1 >= frame_h) {
-                h->err = "detection " + std::to_string(i) + " is degenerate after clamping";
-                return 7;
-            }
-        } else if (cf > 1) {  // increase y side
-            const long center = y1 + (y2 - y1) / 2;
-            const long length = (long)std::nearbyint((double)(y2 - y1) * cf);
-            y1n = center - length / 2, y2n = center + length / 2;
-            pt = std::labs(y1n - y1), pb = std::labs(y2n - y2);
-        } else if (cf < 1) {
-            const long center = x1 + (x2 - x1) / 2;
-            const long length = (long)std::nearbyint((double)(x2 - x1) * 1 / cf);
-            x1n = center - length / 2, x2n = center + length / 2;
-            pl = std::labs(x1n - x1), pr = std::labs(x2n - x2);
-        }
+        const hrn_frame &f = frames[fidx ? fidx[i] : 0];
         CropParams &cp = cps[i];
-        cp.x1 = (int)sx1, cp.y1 = (int)sy1;
-        cp.w_crop = (int)(std::min<long>(sx2, frame_w) - sx1), cp.h_crop = (int)(std::min<long>(sy2, frame_h) - sy1);  // numpy slicing
-        cp.pad_top = (int)pt, cp.pad_left = (int)pl;
-        cp.h_pad = cp.h_crop + (int)(pt + pb), cp.w_pad = cp.w_crop + (int)(pl + pr);
+        if (!crop_geometry_one(dets_host + (size_t)i * det_stride, i, f.height, f.width, H, W, variant, cp, boxes + (size_t)i * 4, h->err))
+            return 7;
+        cp.frame = f.data, cp.frame_w = f.width, cp.frame_h = f.height;
         cp.tmp_off = (long long)tmp_bytes;
         tmp_bytes += ((size_t)cp.h_pad * W * 3 + 255) / 256 * 256;
         if (cp.h_pad > max_h_pad) max_h_pad = cp.h_pad;
-        boxes[(size_t)i * 4 + 0] = (int32_t)x1n, boxes[(size_t)i * 4 + 1] = (int32_t)y1n;
-        boxes[(size_t)i * 4 + 2] = (int32_t)x2n, boxes[(size_t)i * 4 + 3] = (int32_t)y2n;
     }
-    hipStream_t s = (hipStream_t)stream;
     if (tmp_bytes > h->pre_tmp_bytes || n > h->pre_params_cap) {  // grow the scratch: wait for whoever still reads the old one
         if (!h->hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return 6;
         if (tmp_bytes > h->pre_tmp_bytes) {
@@ -607,10 +606,101 @@ int hrn_preprocess_frame(hrn_handle h, const uint8_t *frame_dev, int frame_h, in
         return 6;
     if (!h->hip_ok(hipEventRecord(h->pre_landed[ring], s), "hipEventRecord")) return 6;
     if (boxes_host) memcpy(boxes_host, boxes, (size_t)n * 16);
-    if (!h->hip_ok(launch_prepath(frame_dev, frame_w, h->pre_params, n, max_h_pad, h->pre_tmp, images_dev, H, W, s),
-                   "pre-path launch"))
-        return 8;
+    if (!h->hip_ok(launch_prepath(h->pre_params, n, max_h_pad, h->pre_tmp, images_dev, H, W, s), "pre-path launch")) return 8;
     return 0;
+}
+}  // namespace
+
+int hrn_crop_geometry(const float *dets, int det_stride, int n, const int32_t *frame_hw, int per_person_hw, int height, int width,
+                      int variant, int32_t *boxes_out, int32_t *slice_out) {
+    g_geometry_error.clear();
+    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
+        g_geometry_error = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
+        return 7;
+    }
+    if (n < 0 || det_stride < 4 || height <= 0 || width <= 0 || (n > 0 && (!dets || !frame_hw))) {
+        g_geometry_error = "bad frame / detections / n";
+        return 7;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int32_t *hw = frame_hw + (per_person_hw ? (size_t)i * 2 : 0);
+        if (hw[0] <= 0 || hw[1] <= 0) {
+            g_geometry_error = "bad frame / detections / n";
+            return 7;
+        }
+        CropParams cp{};
+        int32_t box[4];
+        if (!crop_geometry_one(dets + (size_t)i * det_stride, i, hw[0], hw[1], height, width, variant, cp, box, g_geometry_error)) return 7;
+        if (boxes_out) memcpy(boxes_out + (size_t)i * 4, box, sizeof(box));
+        if (slice_out) {
+            const int32_t sl[8] = {cp.x1, cp.y1, cp.w_crop, cp.h_crop, cp.pad_top, cp.pad_left, cp.h_pad, cp.w_pad};
+            memcpy(slice_out + (size_t)i * 8, sl, sizeof(sl));
+        }
+    }
+    return 0;
+}
+
+const char *hrn_crop_geometry_last_error(void) { return g_geometry_error.c_str(); }
+
+int hrn_preprocess_frame(hrn_handle h, const uint8_t *frame_dev, int frame_h, int frame_w, const float *dets_host,
+                         int det_stride, int n, int variant, float *images_dev, int32_t *boxes_host, int32_t *boxes_dev,
+                         void *stream) {
+    if (!h) return 1;
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
+        h->err = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
+        return 7;
+    }
+    if (n < 0 || det_stride < 4 || frame_h <= 0 || frame_w <= 0 || (n > 0 && (!frame_dev || !dets_host || !images_dev))) {
+        h->err = "bad frame / detections / n";
+        return 7;
+    }
+    if (n == 0) return 0;
+    const hrn_frame one = {frame_dev, frame_h, frame_w};   // a one-frame table: the same kernels, the same bits
+    return preprocess_people(h, &one, nullptr, dets_host, det_stride, n, variant, images_dev, boxes_host, boxes_dev, (hipStream_t)stream);
+}
+
+// SimpleHRNet.py:383-412 over a whole stack, or :236-278 over many frames.  The arguments are judged first (they need no
+// device, so a plan-only handle judges them too), then the handle, then the boxes; nothing is queued before all have passed.
+int hrn_preprocess_frames(hrn_handle h, const hrn_frame *frames_host, int nframes, const float *dets_host, int det_stride,
+                          const int32_t *frame_index_host, int n, int variant, float *images_dev, int32_t *boxes_host,
+                          int32_t *boxes_dev, void *stream) {
+    if (!h) return 1;
+    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
+        h->err = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
+        return 7;
+    }
+    if (n < 0 || nframes < 0 || det_stride < 4 || (n > 0 && (nframes < 1 || !frames_host || !dets_host || !images_dev))) {
+        h->err = "bad frames / detections / n";
+        return 7;
+    }
+    if (n > 0 && !frame_index_host && nframes != 1) {
+        h->err = "hrn_preprocess_frames: without frame_index there must be one frame";
+        return 7;
+    }
+    for (int i = 0; i < n; ++i) {
+        const long f = frame_index_host ? (long)frame_index_host[i] : 0;
+        if (f < 0 || f >= nframes) {
+            h->err = "hrn_preprocess_frames: frame_index " + std::to_string(f) + " of person " + std::to_string(i) + " is outside [0, " +
+                     std::to_string(nframes) + ")";
+            return 7;
+        }
+        if (!frames_host[f].data || frames_host[f].height <= 0 || frames_host[f].width <= 0) {
+            h->err = "hrn_preprocess_frames: frame " + std::to_string(f) + ", which person " + std::to_string(i) +
+                     " is cut from, is null or has no size";
+            return 7;
+        }
+    }
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (n == 0) return 0;
+    return preprocess_people(h, frames_host, frame_index_host, dets_host, det_stride, n, variant, images_dev, boxes_host, boxes_dev,
+                             (hipStream_t)stream);
 }
 
 int hrn_resize_frames(hrn_handle h, const uint8_t *frames_dev, int n, int frame_h, int frame_w, int interpolation,

@@ -187,15 +187,18 @@ struct StemArgs {          // conv1 3->64 3x3 s2 + BN + ReLU, NCHW fp32 in, flat
 
 hipError_t launch_stem_fused(int dtype, const S2Problem *probs_dev, const void *map_dev, int nblocks, const StemArgs &stem, hipStream_t s);
 
-// Crop pre-path (prepath.hip): one person's slice of the frame, its zero padding and where its horizontal pass lives
+// Crop pre-path (prepath.hip): one person's slice of its frame, its zero padding and where its horizontal pass lives
 struct CropParams {
     int x1, y1, w_crop, h_crop;   // slice of the frame that is actually read (numpy clamps the stop index)
     int pad_top, pad_left;        // zero rows / columns in front of it (np.pad)
     int h_pad, w_pad;             // size of the padded crop = input of the resize
     long long tmp_off;            // byte offset of this crop's [h_pad][W][3] uint8 intermediate
+    const unsigned char *frame;   // the frame this person is cut from: (frame_h, frame_w, 3) uint8 BGR, device
+    int frame_w, frame_h;
 };
-hipError_t launch_prepath(const unsigned char *frame_dev, int frame_w, const CropParams *crops_dev, int n, int max_h_pad,
-                          unsigned char *tmp_dev, float *images_dev, int H, int W, hipStream_t s);
+// crops [0, n) of crops_dev, each from its own frame, into images_dev[0, n); any n (sliced by the grid's y limit)
+hipError_t launch_prepath(const CropParams *crops_dev, int n, int max_h_pad, unsigned char *tmp_dev, float *images_dev, int H, int W,
+                          hipStream_t s);
 // single-person pre-path (prepath.hip): cv2.resize of whole frames; one entry per output column, then per output row
 struct ResizeTaps {
     int ofs;       // first source index of the window (may lie outside: replicate border)

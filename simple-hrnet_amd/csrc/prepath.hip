@@ -1,6 +1,7 @@
-// Crop pre-path of SimpleHRNet.predict(), single image / multi-person (SimpleHRNet.py:236-278), on the GPU:
-// the frame crosses PCIe once as uint8 and every person's crop is cut, zero-padded, resized and normalised here,
-// straight into the (n,3,H,W) fp32 batch the stem reads.
+// Crop pre-path of SimpleHRNet.predict(), single image / multi-person (SimpleHRNet.py:236-278) and the stack path
+// (SimpleHRNet.py:383-412), on the GPU: every frame crosses PCIe once as uint8 and every person's crop is cut, zero-padded,
+// resized and normalised here, straight into the (n,3,H,W) fp32 batch the stem reads.  A person's record names its frame
+// (base pointer, width, height), so the people of many frames -- of differing sizes -- go through one pair of launches.
 //
 // The resize is Pillow's (torchvision Resize on a PIL image = Image.resize(BILINEAR); libImaging/Resample.c):
 //   two separable 8-bit passes, horizontal then vertical, rounded and clipped to uint8 in between;
@@ -66,25 +67,25 @@ __device__ __forceinline__ int clip8(int v) {
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-// padded-crop pixel (y, x) of channel c (RGB order) -- zero in the padding, the BGR frame flipped elsewhere
-__device__ __forceinline__ int crop_px(const unsigned char *frame, int frame_w, const CropParams &cp, int y, int x, int c) {
+// padded-crop pixel (y, x) of channel c (RGB order) -- zero in the padding, the person's BGR frame flipped elsewhere
+__device__ __forceinline__ int crop_px(const CropParams &cp, int y, int x, int c) {
     const int yy = y - cp.pad_top, xx = x - cp.pad_left;
     if (yy < 0 || yy >= cp.h_crop || xx < 0 || xx >= cp.w_crop) return 0;
-    return frame[((size_t)(cp.y1 + yy) * frame_w + cp.x1 + xx) * 3 + (2 - c)];
+    return cp.frame[((size_t)(cp.y1 + yy) * cp.frame_w + cp.x1 + xx) * 3 + (2 - c)];
 }
 
 }  // namespace
 
-// pass 1: rows of the padded crop -> W output columns (uint8 RGB, row-major [h_pad][W][3] per crop)
-__global__ __launch_bounds__(256) void prepath_horizontal_kernel(const unsigned char *frame, int frame_w,
-                                                                 const CropParams *crops, unsigned char *tmp, int W) {
+// pass 1: rows of the padded crop -> W output columns (uint8 RGB, row-major [h_pad][W][3] per crop); every crop reads the
+// frame its record names, so one launch serves the people of any number of frames, of any sizes
+__global__ __launch_bounds__(256) void prepath_horizontal_kernel(const CropParams *crops, unsigned char *tmp, int W) {
     const CropParams cp = crops[blockIdx.y];
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)cp.h_pad * W) return;
     const int y = (int)(idx / W), xx = (int)(idx - (long)y * W);
     unsigned char *o = tmp + cp.tmp_off + ((size_t)y * W + xx) * 3;
     if (cp.w_pad == W) {  // no horizontal pass in Pillow either
-        for (int c = 0; c < 3; ++c) o[c] = (unsigned char)crop_px(frame, frame_w, cp, y, xx, c);
+        for (int c = 0; c < 3; ++c) o[c] = (unsigned char)crop_px(cp, y, xx, c);
         return;
     }
     const Taps t = taps_of(xx, cp.w_pad, W);
@@ -93,9 +94,9 @@ __global__ __launch_bounds__(256) void prepath_horizontal_kernel(const unsigned 
     int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
     for (int x = 0; x < t.n; ++x) {
         const int k = coeff(t, xx, x, ww);
-        s0 += crop_px(frame, frame_w, cp, y, t.xmin + x, 0) * k;
-        s1 += crop_px(frame, frame_w, cp, y, t.xmin + x, 1) * k;
-        s2 += crop_px(frame, frame_w, cp, y, t.xmin + x, 2) * k;
+        s0 += crop_px(cp, y, t.xmin + x, 0) * k;
+        s1 += crop_px(cp, y, t.xmin + x, 1) * k;
+        s2 += crop_px(cp, y, t.xmin + x, 2) * k;
     }
     o[0] = (unsigned char)clip8(s0), o[1] = (unsigned char)clip8(s1), o[2] = (unsigned char)clip8(s2);
 }
@@ -132,13 +133,17 @@ __global__ __launch_bounds__(256) void prepath_vertical_kernel(const CropParams 
     }
 }
 
-hipError_t launch_prepath(const unsigned char *frame_dev, int frame_w, const CropParams *crops_dev, int n, int max_h_pad,
-                          unsigned char *tmp_dev, float *images_dev, int H, int W, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    dim3 g1((unsigned)(((long)max_h_pad * W + 255) / 256), n);
-    hipLaunchKernelGGL(prepath_horizontal_kernel, g1, dim3(256), 0, s, frame_dev, frame_w, crops_dev, tmp_dev, W);
-    dim3 g2((unsigned)(((long)H * W + 255) / 256), n);
-    hipLaunchKernelGGL(prepath_vertical_kernel, g2, dim3(256), 0, s, crops_dev, tmp_dev, images_dev, H, W);
+hipError_t launch_prepath(const CropParams *crops_dev, int n, int max_h_pad, unsigned char *tmp_dev, float *images_dev, int H, int W,
+                          hipStream_t s) {
+    constexpr int kMaxGridY = 65535;   // blockIdx.y is the crop: more people than that go out in slices
+    for (int lo = 0; lo < n; lo += kMaxGridY) {
+        const int nb = n - lo < kMaxGridY ? n - lo : kMaxGridY;
+        dim3 g1((unsigned)(((long)max_h_pad * W + 255) / 256), nb);
+        hipLaunchKernelGGL(prepath_horizontal_kernel, g1, dim3(256), 0, s, crops_dev + lo, tmp_dev, W);
+        dim3 g2((unsigned)(((long)H * W + 255) / 256), nb);
+        hipLaunchKernelGGL(prepath_vertical_kernel, g2, dim3(256), 0, s, crops_dev + lo, (const unsigned char *)tmp_dev,
+                           images_dev + (size_t)lo * 3 * H * W, H, W);
+    }
     return hipGetLastError();
 }
 

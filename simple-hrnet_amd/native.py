@@ -54,6 +54,60 @@ def _frame_stack(frames) -> torch.Tensor:
     return frames
 
 
+def group_frames(counts, limit: int, people_per_pass: Optional[int] = None):
+    """The frame-grouping rule of ``predict_frames`` and ``predict_clip``: which people share a pass.
+
+    ``counts``: people per frame, in order (any iterable; it is read lazily, one frame ahead of the group being formed);
+    ``limit``: the engine's ``max_batch``; ``people_per_pass``: at most that many people per group (default ``limit``; more than
+    ``limit`` is refused with ValueError, as is anything below 1).  Yields groups, each a list of ``(frame, lo, hi)``: people
+    ``lo:hi`` of frame ``frame`` -- in frame order, every person exactly once, every frame in at least one group:
+
+    * consecutive frames are packed greedily while their people fit; a frame is never split to fill a group up;
+    * a frame without people joins the group being formed as ``(frame, 0, 0)`` (its empty result keeps its place in the order);
+    * a frame with more people than fit one pass closes the group being formed and goes out alone, in as many groups of its
+      own as it needs (``(f, 0, P), (f, P, 2P), ...``); the frame after it starts a fresh group."""
+    per_pass = limit if people_per_pass is None else people_per_pass
+    if isinstance(per_pass, bool) or int(per_pass) != per_pass or per_pass < 1:
+        raise ValueError("people_per_pass must be a positive integer, got %r" % (people_per_pass,))
+    if per_pass > limit:
+        raise ValueError("people_per_pass=%d exceeds max_batch=%d" % (per_pass, limit))
+    per_pass = int(per_pass)
+    group, held = [], 0
+    for f, c in enumerate(counts):
+        c = int(c)
+        if c < 0:
+            raise ValueError("frame %d has a negative number of people" % f)
+        if c > per_pass:
+            if group:
+                yield group
+            for lo in range(0, c, per_pass):
+                yield [(f, lo, min(c, lo + per_pass))]
+            group, held = [], 0
+            continue
+        if held + c > per_pass:
+            yield group
+            group, held = [], 0
+        group.append((f, 0, c))
+        held += c
+    if group:
+        yield group
+
+
+def _detections(detections) -> np.ndarray:
+    """one frame's detections as a contiguous (P, 4) float32 array (None: nobody); ValueError otherwise"""
+    if detections is None:
+        return np.zeros((0, 4), np.float32)
+    d = np.asarray(detections.cpu() if isinstance(detections, torch.Tensor) else detections, dtype=np.float32)
+    if d.ndim != 2 or (len(d) and d.shape[1] < 4):
+        raise ValueError("detections must be (P, >=4)")
+    return np.ascontiguousarray(d[:, :4]) if len(d) else np.zeros((0, 4), np.float32)
+
+
+def _check_frame(frame, k: int):
+    if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3 or min(frame.shape[:2]) < 1:
+        raise ValueError("frame %d must be (H, W, 3) uint8 BGR" % k)
+
+
 def _warp_arguments(nframes: int, size_wh, centers, scales, rotations, frame_index, pixel_std, matrices):
     """the host-side arguments of ``hrn_warp_crops``: ``(matrices (n, 6) float64, frame_index (n,) int32)``, checked -- every
     argument error is a ValueError here, before the library is called"""
@@ -630,6 +684,227 @@ class NativeHRNet:
         if return_heatmaps:
             return boxes, out[1], out[0]
         return boxes, out
+
+    # -- clip mode: the people of many frames in one pre-path launch and one pass (throughput, not latency) ------------------
+    def _device_frames(self, frames) -> List[Optional[torch.Tensor]]:
+        """``frames`` of ``preprocess_frames`` as a list of contiguous (Hf, Wf, 3) uint8 tensors on the engine's GPU; a 4-D stack
+        crosses PCIe in one copy and is then indexed, a sequence frame by frame (once each)"""
+        dev = self.torch_device
+        if isinstance(frames, np.ndarray) and frames.ndim == 4:
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        if isinstance(frames, torch.Tensor):
+            if frames.dim() != 4:
+                raise ValueError("frames must be (F, Hf, Wf, 3) uint8 BGR or a sequence of (Hf, Wf, 3) frames")
+            stack = frames.to(dev, non_blocking=True).contiguous()
+            out = [stack[k] for k in range(int(stack.shape[0]))]
+        else:
+            out = [None if f is None else (f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)))
+                   for f in frames]
+            out = [None if f is None else f.to(dev, non_blocking=True).contiguous() for f in out]
+        for k, f in enumerate(out):
+            if f is not None:
+                _check_frame(f, k)
+        return out
+
+    def _preprocess_table(self, table, nframes: int, dets: np.ndarray, frame_index: np.ndarray, variant: str):
+        """``hrn_preprocess_frames`` over a ready frame table (``_lib.Frame`` array whose device memory the caller keeps alive):
+        ``dets`` (n, 4) float32, ``frame_index`` (n,) int32.  Returns ``(images, boxes numpy, boxes on the device)``."""
+        n = len(dets)
+        h, w = self.resolution
+        images = torch.empty((n, 3, h, w), dtype=torch.float32, device=self.torch_device)
+        boxes = np.empty((n, 4), dtype=np.int32)
+        boxes_dev = torch.empty((n, 4), dtype=torch.int32, device=self.torch_device)
+        if n:
+            with torch.cuda.device(self.device_index):
+                rc = self._lib.hrn_preprocess_frames(self._h, table, nframes, dets.ctypes.data, 4, frame_index.ctypes.data, n,
+                                                     0 if variant == "pad" else 1, images.data_ptr(), boxes.ctypes.data,
+                                                     boxes_dev.data_ptr(), self._stream())
+            self._check(rc, "hrn_preprocess_frames")
+        return images, boxes, boxes_dev
+
+    @staticmethod
+    def _frame_table(frames):
+        """the ``hrn_frame`` table of a list of device frames (None: a null entry, for a frame nobody is cut from)"""
+        table = (_lib.Frame * max(len(frames), 1))()
+        for k, f in enumerate(frames):
+            if f is not None:
+                table[k].data, table[k].height, table[k].width = f.data_ptr(), int(f.shape[0]), int(f.shape[1])
+        return table
+
+    def _frame_arguments(self, frames, detections, variant):
+        if variant not in ("pad", "clamp"):
+            raise ValueError("variant must be 'pad' or 'clamp'")
+        frames = self._device_frames(frames)
+        dets = [_detections(d) for d in detections]
+        if len(dets) != len(frames):
+            raise ValueError("%d frames but %d detection arrays" % (len(frames), len(dets)))
+        for k, (f, d) in enumerate(zip(frames, dets)):
+            if f is None and len(d):
+                raise ValueError("frame %d is None but has %d detections" % (k, len(d)))
+        return frames, dets
+
+    def preprocess_frames(self, frames, detections, variant: str = "pad"):
+        """The crop pre-path for the people of MANY frames in one call (``hrn_preprocess_frames``): one pair of launches, and the
+        crops are written once, into the one batch the model reads -- no ``preprocess_frame`` per frame, no ``torch.cat``.
+
+        ``frames``: (F, Hf, Wf, 3) uint8 BGR tensor or array, or a sequence of (Hf_k, Wf_k, 3) frames of differing sizes (host
+        frames are uploaded once; a frame without people may be None); ``detections``: F arrays (P_k, >=4), empty arrays and
+        None allowed; ``variant`` as in ``preprocess_frame``.
+        Returns ``(images (sum P, 3, H, W) float32 on the GPU, boxes (sum P, 4) int32 numpy, boxes on the GPU, counts [P_k])``, the
+        people in frame order -- bit-identical to the concatenated ``preprocess_frame`` outputs of the frames."""
+        frames, dets = self._frame_arguments(frames, detections, variant)
+        counts = [len(d) for d in dets]
+        all_dets = np.ascontiguousarray(np.concatenate(dets, 0)) if dets else np.zeros((0, 4), np.float32)
+        frame_index = np.repeat(np.arange(len(counts), dtype=np.int32), counts).astype(np.int32)
+        images, boxes, boxes_dev = self._preprocess_table(self._frame_table(frames), len(frames), all_dets, frame_index, variant)
+        return images, boxes, boxes_dev, counts
+
+    def _run_group(self, table, nframes, dets, group, variant, return_heatmaps, refine):
+        """pre-path + pass + decode of one group of ``group_frames``: ``[(frame, lo, hi, boxes, pts, heatmaps or None)]``"""
+        parts = [dets[f][lo:hi] for f, lo, hi in group]
+        sizes = [hi - lo for _, lo, hi in group]
+        all_dets = np.ascontiguousarray(np.concatenate(parts, 0))
+        frame_index = np.repeat(np.asarray([f for f, _, _ in group], np.int32), sizes).astype(np.int32)
+        images, boxes, boxes_dev = self._preprocess_table(table, nframes, all_dets, frame_index, variant)
+        out = self.predict_crops(images, boxes_dev, return_heatmaps=return_heatmaps, refine=refine)
+        hm, pts = out if return_heatmaps else (None, out)
+        res, at = [], 0
+        for (f, lo, hi), n in zip(group, sizes):
+            res.append((f, lo, hi, boxes[at:at + n], pts[at:at + n], None if hm is None else hm[at:at + n]))
+            at += n
+        return res
+
+    @staticmethod
+    def _frame_result(pieces, return_heatmaps):
+        """one frame's ``(boxes, pts[, heatmaps])`` from the pieces of its passes (one piece: views, nothing is copied)"""
+        if len(pieces) == 1:
+            boxes, pts, hm = pieces[0]
+        else:
+            boxes = np.concatenate([p[0] for p in pieces], 0)
+            pts = torch.cat([p[1] for p in pieces], 0)
+            hm = torch.cat([p[2] for p in pieces], 0) if return_heatmaps else None
+        return (boxes, pts, hm) if return_heatmaps else (boxes, pts)
+
+    def predict_frames(self, frames, detections, return_heatmaps: bool = False, variant: str = "pad", refine: Optional[str] = None):
+        """``preprocess_frames`` + ``predict_crops`` for a set of resident (or small) frames: the THROUGHPUT form of ``predict_frame``
+        -- the people of consecutive frames share a pass (``group_frames``: greedily while they fit ``max_batch``; a frame with more
+        people than ``max_batch`` runs in several passes).  Nothing about one frame's latency improves: ``predict_frame`` stays the
+        call of a live loop.  ``frames`` / ``detections`` / ``variant`` as in ``preprocess_frames``, ``refine`` as in ``predict_crops``.
+        Returns one ``(boxes (P_k,4) int32 numpy, pts (P_k,J,3) on the GPU[, heatmaps])`` per frame, ``pts`` / ``heatmaps`` views of
+        their pass's outputs; a frame without people gives (0,4), (0,J,3) and (0,J,H/4,W/4)."""
+        refine_code(refine)
+        frames, dets = self._frame_arguments(frames, detections, variant)
+        table = self._frame_table(frames)
+        pieces = [[] for _ in frames]
+        for group in group_frames([len(d) for d in dets], self.max_batch):
+            if any(hi > lo for _, lo, hi in group):
+                for f, lo, hi, bx, pts, hm in self._run_group(table, len(frames), dets, group, variant, return_heatmaps, refine):
+                    if hi > lo:
+                        pieces[f].append((bx, pts, hm))
+        return [self._frame_result(p, return_heatmaps) if p else self._empty_result(return_heatmaps) for p in pieces]
+
+    def _empty_result(self, return_heatmaps):
+        h, w = self.resolution
+        dev = self.torch_device
+        out = (np.zeros((0, 4), np.int32), torch.zeros((0, self.nof_joints, 3), dtype=torch.float32, device=dev))
+        return out + (torch.zeros((0, self.nof_joints, h // 4, w // 4), dtype=torch.float32, device=dev),) if return_heatmaps else out
+
+    def predict_clip(self, items, people_per_pass: Optional[int] = None, return_heatmaps: bool = False, variant: str = "pad",
+                     refine: Optional[str] = None):
+        """The throughput loop over a video file or a wall of cameras, modelled on ``predict_stream``: HOST frames in, joints out,
+        with the uploads hidden behind the compute.  Not a latency path -- a frame's result comes when its group has run.
+
+        ``items``: iterable of ``(frame, detections)``; ``frame`` a HOST (Hf, Wf, 3) uint8 BGR tensor or array (pinned memory for a
+        truly asynchronous copy), of any size from item to item; a frame without people may be None; ``detections`` (P, >=4), empty
+        or None.  Device-resident frames are refused (TypeError): they go to ``predict_frames``.
+        Frames are read ahead into groups of at most ``people_per_pass`` people (default and upper bound ``max_batch``;
+        ``group_frames``).  A group's frames are uploaded on a copy stream into one of two device arenas (grown on demand, frames at
+        256-byte offsets; the frame table points into the arena) while the group before it runs pre-path, pass and decode on the
+        current stream.  A frame with more people than one pass crosses once per pass.
+        Yields per frame, in order, what ``predict_frames`` returns per frame; results are ready on the current stream (read them
+        after a synchronize or through ``.cpu()``)."""
+        refine_code(refine)
+        if variant not in ("pad", "clamp"):
+            raise ValueError("variant must be 'pad' or 'clamp'")
+        per_pass = self.max_batch if people_per_pass is None else people_per_pass
+        dev = self.torch_device
+        compute = torch.cuda.current_stream(dev)
+        copy = torch.cuda.Stream(dev)
+        arena = [None, None]
+        landed = [torch.cuda.Event(), torch.cuda.Event()]
+        consumed = [None, None]
+        held = {}            # frame number -> (host frame or None, detections) of the frames read ahead and not yet run
+
+        def counts():        # feeds group_frames, which reads one frame ahead of the group it forms
+            for k, item in enumerate(items):
+                frame, d = item
+                if isinstance(frame, torch.Tensor) and frame.device.type != "cpu":
+                    raise TypeError("predict_clip takes host frames; device-resident frames go to predict_frames")
+                d = _detections(d)
+                if frame is not None:
+                    frame = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame))
+                    _check_frame(frame, k)
+                    frame = frame.contiguous()
+                elif len(d):
+                    raise ValueError("frame %d is None but has %d detections" % (k, len(d)))
+                held[k] = (frame, d)
+                yield len(d)
+
+        def upload(slot, group):
+            """the frames of `group` that somebody is cut from -> arena[slot] on the copy stream; returns the group's table"""
+            first = group[0][0]
+            nfr = group[-1][0] - first + 1
+            table = (_lib.Frame * nfr)()
+            offs, need = {}, 0
+            for f, lo, hi in group:
+                if hi > lo and f not in offs:
+                    offs[f] = need
+                    need += (held[f][0].numel() + 255) // 256 * 256
+            if need and (arena[slot] is None or arena[slot].numel() < need):
+                # a new arena comes from the caching allocator on the COMPUTE stream and may be recycled memory that kernels already
+                # queued there still read: the upload into it must not overtake them
+                arena[slot] = torch.empty((need + need // 4,), dtype=torch.uint8, device=dev)
+                arena[slot].record_stream(copy)
+                copy.wait_stream(compute)
+            with torch.cuda.stream(copy):
+                if consumed[slot] is not None:
+                    copy.wait_event(consumed[slot])              # the pre-path that read this arena has finished
+                for f, off in offs.items():
+                    frame = held[f][0]
+                    arena[slot][off:off + frame.numel()].copy_(frame.view(-1), non_blocking=True)
+                    table[f - first].data = arena[slot].data_ptr() + off
+                    table[f - first].height, table[f - first].width = int(frame.shape[0]), int(frame.shape[1])
+                landed[slot].record(copy)
+            return table, first, nfr, bool(offs)
+
+        # the arenas come from the caching allocator on the COMPUTE stream (see upload): the first upload must not overtake it
+        copy.wait_stream(compute)
+        groups = group_frames(counts(), self.max_batch, per_pass)
+        nxt = next(groups, None)
+        pending = upload(0, nxt) if nxt is not None else None
+        k, pieces = 0, {}
+        while nxt is not None:
+            slot, group, (table, first, nfr, busy) = k & 1, nxt, pending
+            nxt = next(groups, None)
+            pending = upload(slot ^ 1, nxt) if nxt is not None else None   # goes out while this group computes
+            if busy:
+                compute.wait_event(landed[slot])
+                local = [(f - first, lo, hi) for f, lo, hi in group]
+                dets = {f - first: held[f][1] for f, _, _ in group}
+                for f, lo, hi, bx, pts, hm in self._run_group(table, nfr, dets, local, variant, return_heatmaps, refine):
+                    if hi > lo:
+                        pieces.setdefault(f + first, []).append((bx, pts, hm))
+                consumed[slot] = torch.cuda.Event()
+                consumed[slot].record(compute)
+            last = group[-1][0]
+            for f in sorted({g[0] for g in group}):
+                # a frame above one pass spans several groups: it is complete with the group that holds its last people
+                if f == last and nxt is not None and nxt[0][0] == f:
+                    continue
+                p = pieces.pop(f, None)
+                del held[f]
+                yield self._frame_result(p, return_heatmaps) if p else self._empty_result(return_heatmaps)
+            k += 1
 
     def tap_infos(self) -> List[_lib.TapInfo]:
         """the tensors ``forward_tap`` can read: name, (c, h, w), index of the convolution that writes it (or -1)"""

@@ -223,20 +223,20 @@ class SimpleHRNet:
             hm, pts = self.model.predict_crops(x, boxes, return_heatmaps=True, **self._refine_kw())
             return self._result(hm.cpu().numpy(), boxes, np.expand_dims(pts.cpu().numpy(), axis=1))   # :475
         per_frame = self.detector.predict(images)
-        crops, boxes = [], []
-        counts = []
-        for index, found in enumerate(per_frame):
-            n = 0 if found is None else len(found)
-            counts.append(None if found is None else n)
-            if n:
-                dets = np.asarray(found.cpu() if isinstance(found, torch.Tensor) else found, np.float32)[:, :4]
-                im, bx, _ = self.model.preprocess_frame(images[index], dets, "clamp")   # :383-412
-                crops.append(im), boxes.append(bx)
-        if not crops:                                                                # :477-484
+        counts = [None if found is None else len(found) for found in per_frame]
+        dets = [None if not n else np.asarray(found.cpu() if isinstance(found, torch.Tensor) else found, np.float32)[:, :4]
+                for found, n in zip(per_frame, counts)]
+        if not any(counts):                                                          # :477-484
             pts = [np.zeros((0, self.nof_joints, 3), dtype=np.float32) for _ in per_frame]
             return self._result(np.zeros(self._hm_shape(0), np.float32), np.asarray([], dtype=np.int32), pts)
-        boxes = np.concatenate(boxes, 0)
-        out = self.model.predict_crops(torch.cat(crops, 0), boxes, return_heatmaps=self.return_heatmaps, **self._refine_kw())
+        if hasattr(self.model, "preprocess_frames"):
+            # :383-412 for the whole stack in one call: the stack crosses PCIe once, one pair of launches cuts everybody, and the
+            # crops are written once, where the model reads them (no call per image, no torch.cat of :409-412)
+            crops, boxes, _, _ = self.model.preprocess_frames(images, dets, "clamp")
+        else:   # an engine without the multi-frame entry (native.MultiDeviceHRNet shards one frame's people): image by image
+            parts = [self.model.preprocess_frame(images[index], d, "clamp") for index, d in enumerate(dets) if d is not None]
+            crops, boxes = torch.cat([p[0] for p in parts], 0), np.concatenate([p[1] for p in parts], 0)
+        out = self.model.predict_crops(crops, boxes, return_heatmaps=self.return_heatmaps, **self._refine_kw())
         hm, pts = (out[0].cpu().numpy(), out[1].cpu().numpy()) if self.return_heatmaps else (None, out.cpu().numpy())
         pts_b, hm_b, boxes_b, index = [], [], [], 0                                  # :445-472: re-add the batch axis
         for n in counts:
