@@ -166,6 +166,45 @@ int hrn_preprocess_frames(hrn_handle h, const hrn_frame *frames_host, int nframe
                           const int32_t *frame_index_host /* n entries; NULL: nframes == 1 */, int n, int variant,
                           float *images_dev, int32_t *boxes_host, int32_t *boxes_dev, void *stream);
 
+/* The crop pre-path from VIDEO frames as decoders deliver them: 4:2:0 YCbCr, 8 bits, NV12 (a Y plane and one plane of
+ * interleaved U, V pairs) or I420 (Y, U and V planes), each plane with a row pitch in bytes.  The frame crosses PCIe at 1.5 bytes
+ * per pixel, or not at all when a decoder left it on the device, and is never converted as a whole: the horizontal pass reads
+ * every tap through the conversion.
+ *
+ * The conversion is cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420)'s form: the chroma sample of a 2x2 block is shared by its four
+ * pixels (nearest, no interpolation), 20-bit fixed point in int32 with an arithmetic shift:
+ *   yy = max(0, Y - y0) * CY;  u = U - 128;  v = V - 128;  h = 1 << 19
+ *   B = clip8((yy + h + CUB*u) >> 20);  G = clip8((yy + h + CVG*v + CUG*u) >> 20);  R = clip8((yy + h + CVR*v) >> 20)
+ * hrn_yuv_coefficients writes (y0, CY, CUB, CUG, CVG, CVR) of a matrix and a range; it needs no handle and no GPU.  BT.601
+ * limited -- the default of every video source that says nothing else -- is OpenCV's published table verbatim
+ * (16, 1220542, 2116026, -409993, -852492, 1673527); the other three are floor(x * 2^20 + 0.5) of the exact coefficients
+ * (Kr / Kb = 0.299 / 0.114 or 0.2126 / 0.0722; luma x 255/219 and chroma x 255/224 for limited range, y0 = 16; both 1 and
+ * y0 = 0 for full range).  No sum leaves int32 for any byte triple.
+ * PINNED: the kernels equal the numpy restatement of these lines (tests/yuv_ref.py) bit for bit, and crops cut from a YUV
+ * frame equal the BGR path's crops of that restatement's BGR frame bit for bit, images and boxes.  The restatement is within
+ * one grey level of the rounded float64 formula for all 2^24 byte triples.  UNPINNED: equality with a cv2 build, which is not
+ * available where this library is tested (tests/golden/make_yuv_golden.py makes the pin wherever opencv-python is installed).
+ *
+ * hrn_yuv_to_bgr converts a whole frame to contiguous (height, width, 3) uint8 BGR on the device, for the consumer that needs
+ * BGR (the detector), so that the frame still crosses PCIe once.
+ * hrn_preprocess_frames_yuv is hrn_preprocess_frames over a table of such frames: the same contract, word for word -- box
+ * arithmetic (hrn_crop_geometry's), staging, any n, outputs, failure codes and texts; padding is zero AFTER the conversion
+ * (RGB 0, not the conversion of YUV 0).  The people of one call come all from YUV frames or all from BGR frames.
+ * Both fail with code 7 and nothing launched, beyond hrn_preprocess_frames' failures, on a frame (that a person refers to)
+ * with: an unknown format, matrix or range; an odd or non-positive width or height; pitch_y < width; pitch_c < width (NV12)
+ * or < width / 2 (I420); a null plane (y, u; v for I420).  Everything is judged before the device is touched, so a plan-only
+ * handle reports argument errors as such and a good call as "plan-only". */
+enum { HRN_PIX_NV12 = 1, HRN_PIX_I420 = 2 };
+enum { HRN_YUV_BT601 = 0, HRN_YUV_BT709 = 1 };
+enum { HRN_YUV_LIMITED = 0, HRN_YUV_FULL = 1 };
+typedef struct { const uint8_t *y, *u, *v;     /* device; NV12: u = the UV plane, v ignored */
+                 int32_t height, width, pitch_y, pitch_c, format, matrix, range; } hrn_yuv_frame;
+int hrn_yuv_coefficients(int matrix, int range, int32_t out[6]);
+int hrn_yuv_to_bgr(hrn_handle h, const hrn_yuv_frame *frame_host, uint8_t *bgr_dev, void *stream);
+int hrn_preprocess_frames_yuv(hrn_handle h, const hrn_yuv_frame *frames_host, int nframes, const float *dets_host,
+                              int det_stride, const int32_t *frame_index_host, int n, int variant,
+                              float *images_dev, int32_t *boxes_host, int32_t *boxes_dev, void *stream);
+
 /* The box arithmetic of the two entries above on the HOST, without a handle or a GPU: per detection -- round (half to even),
  * correct the aspect ratio to height / width (SimpleHRNet.py:243-272 by padding, HRN_CROP_PAD; :396-407 by enlarging and
  * clamping to the frame, HRN_CROP_CLAMP), slice as numpy does (:274, :408).

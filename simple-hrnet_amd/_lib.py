@@ -181,6 +181,13 @@ class Frame(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
 
 
+class YuvFrameC(ctypes.Structure):
+    """hrn_yuv_frame: one NV12 / I420 frame of hrn_preprocess_frames_yuv's table, or hrn_yuv_to_bgr's frame"""
+    _fields_ = [("y", ctypes.c_void_p), ("u", ctypes.c_void_p), ("v", ctypes.c_void_p), ("height", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("pitch_y", ctypes.c_int32), ("pitch_c", ctypes.c_int32), ("format", ctypes.c_int32),
+                ("matrix", ctypes.c_int32), ("range", ctypes.c_int32)]
+
+
 # every symbol include/hrnet_mi355.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 SYMBOLS = {
@@ -204,6 +211,10 @@ SYMBOLS = {
                                           ctypes.POINTER(ScoreOut), _P]),
     "hrn_preprocess_frame": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
     "hrn_preprocess_frames": (ctypes.c_int, [_P, ctypes.POINTER(Frame), ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
+    "hrn_yuv_coefficients": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P]),
+    "hrn_yuv_to_bgr": (ctypes.c_int, [_P, ctypes.POINTER(YuvFrameC), _P, _P]),
+    "hrn_preprocess_frames_yuv": (ctypes.c_int, [_P, ctypes.POINTER(YuvFrameC), ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int,
+                                                 _P, _P, _P, _P]),
     "hrn_crop_geometry": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
     "hrn_crop_geometry_last_error": (ctypes.c_char_p, []),
     "hrn_forward_flip_tta": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),

@@ -535,6 +535,8 @@
             if (pass_done) (void)hipEventDestroy(pass_done);
             pass_done = nullptr;
             if (pre_params) (void)hipFree(pre_params);
+            if (pre_yuv) (void)hipFree(pre_yuv);
+            pre_yuv = nullptr, pre_yuv_cap = 0;
             if (warp_params) (void)hipFree(warp_params);
             warp_params = nullptr, warp_params_cap = 0;
             if (warp_done) (void)hipEventDestroy(warp_done);

@@ -168,6 +168,8 @@ struct hrn_ctx {
     hipStream_t rs_stream = nullptr;
     CropParams *pre_params = nullptr;
     int pre_params_cap = 0;
+    YuvSource *pre_yuv = nullptr;    // hrn_preprocess_frames_yuv: person i's planes, pitches and coefficients beside pre_params[i]
+    int pre_yuv_cap = 0;
     // pinned host image of one call's crop parameters + boxes (the async uploads read it after the call returned);
     // kPreRing images in rotation, each rewritten only after the upload that last read it has completed
     static constexpr int kPreRing = 4;
@@ -557,33 +559,78 @@ bool crop_geometry_one(const float *d, int i, int frame_h, int frame_w, int H, i
 
 thread_local std::string g_geometry_error;
 
+// (y0, CY, CUB, CUG, CVG, CVR) in 20-bit fixed point; false on an unknown matrix or range
+bool yuv_coefficients(int matrix, int range, int32_t out[6]) {
+    if ((matrix != HRN_YUV_BT601 && matrix != HRN_YUV_BT709) || (range != HRN_YUV_LIMITED && range != HRN_YUV_FULL)) return false;
+    if (matrix == HRN_YUV_BT601 && range == HRN_YUV_LIMITED) {   // OpenCV's published constants (color_yuv: ITUR_BT_601_*), verbatim
+        const int32_t cv[6] = {16, 1220542, 2116026, -409993, -852492, 1673527};
+        memcpy(out, cv, sizeof(cv));
+        return true;
+    }
+    const double kr = matrix == HRN_YUV_BT601 ? 0.299 : 0.2126, kb = matrix == HRN_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
+    const double sy = range == HRN_YUV_LIMITED ? 255.0 / 219.0 : 1.0, sc = range == HRN_YUV_LIMITED ? 255.0 / 224.0 : 1.0;
+    const double x[5] = {sy, 2.0 * (1.0 - kb) * sc, -2.0 * (1.0 - kb) * kb / kg * sc, -2.0 * (1.0 - kr) * kr / kg * sc, 2.0 * (1.0 - kr) * sc};
+    out[0] = range == HRN_YUV_LIMITED ? 16 : 0;
+    for (int k = 0; k < 5; ++k) out[1 + k] = (int32_t)std::floor(x[k] * 1048576.0 + 0.5);
+    return true;
+}
+
+// what is wrong with a YUV frame somebody reads, or nullptr
+const char *yuv_frame_fault(const hrn_yuv_frame &f) {
+    if (f.format != HRN_PIX_NV12 && f.format != HRN_PIX_I420) return "has an unknown format (HRN_PIX_NV12 or HRN_PIX_I420)";
+    if (f.matrix != HRN_YUV_BT601 && f.matrix != HRN_YUV_BT709) return "has an unknown matrix (HRN_YUV_BT601 or HRN_YUV_BT709)";
+    if (f.range != HRN_YUV_LIMITED && f.range != HRN_YUV_FULL) return "has an unknown range (HRN_YUV_LIMITED or HRN_YUV_FULL)";
+    if (f.height <= 0 || f.width <= 0 || (f.height & 1) || (f.width & 1)) return "has an odd or non-positive width or height";
+    if (f.pitch_y < f.width) return "has pitch_y below its width";
+    if (f.pitch_c < (f.format == HRN_PIX_NV12 ? f.width : f.width / 2))
+        return f.format == HRN_PIX_NV12 ? "has pitch_c below its width" : "has pitch_c below half its width";
+    if (!f.y || !f.u || (f.format == HRN_PIX_I420 && !f.v)) return "has a null plane";
+    return nullptr;
+}
+
+YuvSource yuv_source(const hrn_yuv_frame &f) {   // of a frame yuv_frame_fault has passed
+    YuvSource ys{};
+    ys.y = f.y, ys.u = f.u, ys.v = f.format == HRN_PIX_I420 ? f.v : nullptr;
+    ys.pitch_y = f.pitch_y, ys.pitch_c = f.pitch_c, ys.format = f.format;
+    int32_t c[6];
+    (void)yuv_coefficients(f.matrix, f.range, c);
+    for (int k = 0; k < 6; ++k) ys.coef[k] = c[k];
+    return ys;
+}
+
 // the one body of hrn_preprocess_frame and hrn_preprocess_frames, behind their argument checks: person i is cut from
 // frames[fidx ? fidx[i] : 0]; everything that can be refused is refused before anything is queued
-int preprocess_people(hrn_handle h, const hrn_frame *frames, const int32_t *fidx, const float *dets_host, int det_stride, int n,
-                      int variant, float *images_dev, int32_t *boxes_host, int32_t *boxes_dev, hipStream_t s) {
+// (yframes: the people are cut from YUV frames instead -- the same records, staging and vertical pass, a YuvSource beside each)
+int preprocess_people(hrn_handle h, const hrn_frame *frames, const hrn_yuv_frame *yframes, const int32_t *fidx, const float *dets_host,
+                      int det_stride, int n, int variant, float *images_dev, int32_t *boxes_host, int32_t *boxes_dev, hipStream_t s) {
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     const int H = h->H, W = h->W;
     // crop parameters (each with its frame's pointer and size: the frame table travels inside them) + boxes are written
     // straight into a pinned image the async uploads below read after this call has returned; kPreRing images in rotation,
     // each reused only once the upload that read it last has completed
-    const size_t cp_bytes = ((size_t)n * sizeof(CropParams) + 63) / 64 * 64, need = cp_bytes + (size_t)n * 16;
+    const size_t cp_bytes = ((size_t)n * sizeof(CropParams) + 63) / 64 * 64, box_bytes = (size_t)n * 16;
+    const size_t need = cp_bytes + box_bytes + (yframes ? (size_t)n * sizeof(YuvSource) : 0);
     unsigned ring = 0;
     if (!h->pre_stage(need, &ring)) return 6;
     CropParams *cps = (CropParams *)h->pre_pin[ring];
     int32_t *boxes = (int32_t *)(h->pre_pin[ring] + cp_bytes);
+    YuvSource *srcs = (YuvSource *)(h->pre_pin[ring] + cp_bytes + box_bytes);
     size_t tmp_bytes = 0;
     int max_h_pad = 0;
     for (int i = 0; i < n; ++i) {
-        const hrn_frame &f = frames[fidx ? fidx[i] : 0];
+        const int fi = fidx ? fidx[i] : 0;
+        const int frame_h = yframes ? yframes[fi].height : frames[fi].height, frame_w = yframes ? yframes[fi].width : frames[fi].width;
         CropParams &cp = cps[i];
-        if (!crop_geometry_one(dets_host + (size_t)i * det_stride, i, f.height, f.width, H, W, variant, cp, boxes + (size_t)i * 4, h->err))
+        if (!crop_geometry_one(dets_host + (size_t)i * det_stride, i, frame_h, frame_w, H, W, variant, cp, boxes + (size_t)i * 4, h->err))
             return 7;
-        cp.frame = f.data, cp.frame_w = f.width, cp.frame_h = f.height;
+        cp.frame = yframes ? nullptr : frames[fi].data, cp.frame_w = frame_w, cp.frame_h = frame_h;
+        if (yframes) srcs[i] = yuv_source(yframes[fi]);
         cp.tmp_off = (long long)tmp_bytes;
         tmp_bytes += ((size_t)cp.h_pad * W * 3 + 255) / 256 * 256;
         if (cp.h_pad > max_h_pad) max_h_pad = cp.h_pad;
     }
-    if (tmp_bytes > h->pre_tmp_bytes || n > h->pre_params_cap) {  // grow the scratch: wait for whoever still reads the old one
+    // grow the scratch: wait for whoever still reads the old one
+    if (tmp_bytes > h->pre_tmp_bytes || n > h->pre_params_cap || (yframes && n > h->pre_yuv_cap)) {
         if (!h->hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return 6;
         if (tmp_bytes > h->pre_tmp_bytes) {
             if (h->pre_tmp) (void)hipFree(h->pre_tmp);
@@ -597,7 +644,16 @@ int preprocess_people(hrn_handle h, const hrn_frame *frames, const int32_t *fidx
             if (!h->hip_ok(hipMalloc((void **)&h->pre_params, (size_t)n * sizeof(CropParams)), "hipMalloc(crop params)")) return 6;
             h->pre_params_cap = n;
         }
+        if (yframes && n > h->pre_yuv_cap) {
+            if (h->pre_yuv) (void)hipFree(h->pre_yuv);
+            h->pre_yuv = nullptr, h->pre_yuv_cap = 0;
+            if (!h->hip_ok(hipMalloc((void **)&h->pre_yuv, (size_t)n * sizeof(YuvSource)), "hipMalloc(YUV sources)")) return 6;
+            h->pre_yuv_cap = n;
+        }
     }
+    if (yframes && !h->hip_ok(hipMemcpyAsync(h->pre_yuv, srcs, (size_t)n * sizeof(YuvSource), hipMemcpyHostToDevice, s),
+                              "hipMemcpyAsync(YUV sources)"))
+        return 6;
     if (!h->hip_ok(hipMemcpyAsync(h->pre_params, cps, (size_t)n * sizeof(CropParams), hipMemcpyHostToDevice, s),
                    "hipMemcpyAsync(crop params)"))
         return 6;
@@ -606,7 +662,9 @@ int preprocess_people(hrn_handle h, const hrn_frame *frames, const int32_t *fidx
         return 6;
     if (!h->hip_ok(hipEventRecord(h->pre_landed[ring], s), "hipEventRecord")) return 6;
     if (boxes_host) memcpy(boxes_host, boxes, (size_t)n * 16);
-    if (!h->hip_ok(launch_prepath(h->pre_params, n, max_h_pad, h->pre_tmp, images_dev, H, W, s), "pre-path launch")) return 8;
+    const hipError_t e = yframes ? launch_prepath_yuv(h->pre_params, h->pre_yuv, n, max_h_pad, h->pre_tmp, images_dev, H, W, s)
+                                 : launch_prepath(h->pre_params, n, max_h_pad, h->pre_tmp, images_dev, H, W, s);
+    if (!h->hip_ok(e, "pre-path launch")) return 8;
     return 0;
 }
 }  // namespace
@@ -660,7 +718,8 @@ int hrn_preprocess_frame(hrn_handle h, const uint8_t *frame_dev, int frame_h, in
     }
     if (n == 0) return 0;
     const hrn_frame one = {frame_dev, frame_h, frame_w};   // a one-frame table: the same kernels, the same bits
-    return preprocess_people(h, &one, nullptr, dets_host, det_stride, n, variant, images_dev, boxes_host, boxes_dev, (hipStream_t)stream);
+    return preprocess_people(h, &one, nullptr, nullptr, dets_host, det_stride, n, variant, images_dev, boxes_host, boxes_dev,
+                             (hipStream_t)stream);
 }
 
 // SimpleHRNet.py:383-412 over a whole stack, or :236-278 over many frames.  The arguments are judged first (they need no
@@ -699,8 +758,73 @@ int hrn_preprocess_frames(hrn_handle h, const hrn_frame *frames_host, int nframe
         return 7;
     }
     if (n == 0) return 0;
-    return preprocess_people(h, frames_host, frame_index_host, dets_host, det_stride, n, variant, images_dev, boxes_host, boxes_dev,
-                             (hipStream_t)stream);
+    return preprocess_people(h, frames_host, nullptr, frame_index_host, dets_host, det_stride, n, variant, images_dev, boxes_host,
+                             boxes_dev, (hipStream_t)stream);
+}
+
+int hrn_yuv_coefficients(int matrix, int range, int32_t out[6]) {
+    if (!out) return 7;
+    return yuv_coefficients(matrix, range, out) ? 0 : 7;
+}
+
+int hrn_yuv_to_bgr(hrn_handle h, const hrn_yuv_frame *frame_host, uint8_t *bgr_dev, void *stream) {
+    if (!h) return 1;
+    if (!frame_host || !bgr_dev) {
+        h->err = "hrn_yuv_to_bgr: null frame or output";
+        return 7;
+    }
+    if (const char *fault = yuv_frame_fault(*frame_host)) {
+        h->err = std::string("hrn_yuv_to_bgr: the frame ") + fault;
+        return 7;
+    }
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    if (!h->hip_ok(launch_yuv_to_bgr(yuv_source(*frame_host), frame_host->height, frame_host->width, bgr_dev, (hipStream_t)stream),
+                   "yuv_to_bgr launch"))
+        return 8;
+    return 0;
+}
+
+// hrn_preprocess_frames over YUV frames: its checks and texts, then the frames' own, then the handle, then the boxes
+int hrn_preprocess_frames_yuv(hrn_handle h, const hrn_yuv_frame *frames_host, int nframes, const float *dets_host, int det_stride,
+                              const int32_t *frame_index_host, int n, int variant, float *images_dev, int32_t *boxes_host,
+                              int32_t *boxes_dev, void *stream) {
+    if (!h) return 1;
+    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
+        h->err = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
+        return 7;
+    }
+    if (n < 0 || nframes < 0 || det_stride < 4 || (n > 0 && (nframes < 1 || !frames_host || !dets_host || !images_dev))) {
+        h->err = "bad frames / detections / n";
+        return 7;
+    }
+    if (n > 0 && !frame_index_host && nframes != 1) {
+        h->err = "hrn_preprocess_frames_yuv: without frame_index there must be one frame";
+        return 7;
+    }
+    for (int i = 0; i < n; ++i) {
+        const long f = frame_index_host ? (long)frame_index_host[i] : 0;
+        if (f < 0 || f >= nframes) {
+            h->err = "hrn_preprocess_frames_yuv: frame_index " + std::to_string(f) + " of person " + std::to_string(i) +
+                     " is outside [0, " + std::to_string(nframes) + ")";
+            return 7;
+        }
+        if (const char *fault = yuv_frame_fault(frames_host[f])) {
+            h->err = "hrn_preprocess_frames_yuv: frame " + std::to_string(f) + ", which person " + std::to_string(i) + " is cut from, " +
+                     fault;
+            return 7;
+        }
+    }
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (n == 0) return 0;
+    return preprocess_people(h, nullptr, frames_host, frame_index_host, dets_host, det_stride, n, variant, images_dev, boxes_host,
+                             boxes_dev, (hipStream_t)stream);
 }
 
 int hrn_resize_frames(hrn_handle h, const uint8_t *frames_dev, int n, int frame_h, int frame_w, int interpolation,

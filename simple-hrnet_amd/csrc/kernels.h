@@ -199,6 +199,20 @@ struct CropParams {
 // crops [0, n) of crops_dev, each from its own frame, into images_dev[0, n); any n (sliced by the grid's y limit)
 hipError_t launch_prepath(const CropParams *crops_dev, int n, int max_h_pad, unsigned char *tmp_dev, float *images_dev, int H, int W,
                           hipStream_t s);
+// The same pre-path cut from 4:2:0 YCbCr frames (NV12 / I420): person i's CropParams (frame = nullptr, frame_w / frame_h the
+// frame's size) plus this record of its own -- CropParams, the BGR kernels and their launch stay exactly as they are.
+struct YuvSource {
+    const unsigned char *y, *u, *v;   // planes of the person's frame, device; NV12: u = the interleaved UV plane, v unused
+    int pitch_y, pitch_c;             // bytes between rows of the Y plane / of a chroma plane
+    int format;                       // HRN_PIX_NV12 (1) or HRN_PIX_I420 (2)
+    int coef[6];                      // y0, CY, CUB, CUG, CVG, CVR of hrn_yuv_coefficients: 20-bit fixed point
+    int pad_;
+};
+// as launch_prepath, the horizontal pass reading every tap through the YUV -> RGB conversion; the vertical pass is the same kernel
+hipError_t launch_prepath_yuv(const CropParams *crops_dev, const YuvSource *src_dev, int n, int max_h_pad, unsigned char *tmp_dev,
+                              float *images_dev, int H, int W, hipStream_t s);
+// a whole frame to contiguous (height, width, 3) uint8 BGR (prepath.hip): height and width even
+hipError_t launch_yuv_to_bgr(const YuvSource &src, int height, int width, unsigned char *bgr_dev, hipStream_t s);
 // single-person pre-path (prepath.hip): cv2.resize of whole frames; one entry per output column, then per output row
 struct ResizeTaps {
     int ofs;       // first source index of the window (may lie outside: replicate border)

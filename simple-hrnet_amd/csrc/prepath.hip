@@ -148,6 +148,183 @@ hipError_t launch_prepath(const CropParams *crops_dev, int n, int max_h_pad, uns
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The same pre-path from 4:2:0 YCbCr frames (NV12 / I420), as decoders deliver them: the frame crosses PCIe at 1.5 bytes per
+// pixel and is never converted as a whole.  A tap is read through the conversion of cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420):
+// the chroma sample of a 2x2 block is shared (nearest), 20-bit fixed point in int32 (coef = y0, CY, CUB, CUG, CVG, CVR):
+//   yy = max(0, Y - y0) * CY;  u = U - 128;  v = V - 128;  h = 1 << 19
+//   B = clip8((yy + h + CUB*u) >> 20);  G = clip8((yy + h + CVG*v + CUG*u) >> 20);  R = clip8((yy + h + CVR*v) >> 20)
+// Everything behind the tap is the BGR path's arithmetic, so a crop equals, bit for bit, the BGR path's crop of the converted
+// frame (tests/yuv_ref.py restates the conversion; tests/test_yuv_gpu.py holds both equalities).
+namespace {
+
+constexpr int kPixNV12 = 1;   // HRN_PIX_NV12, HRN_PIX_I420 of include/hrnet_mi355.h
+constexpr int kPixI420 = 2;
+
+struct Rgb {
+    int r, g, b;
+};
+
+__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+__device__ __forceinline__ Rgb yuv_rgb(const int *coef, int Y, int U, int V) {
+    int yy = Y - coef[0];
+    yy = (yy < 0 ? 0 : yy) * coef[1] + (1 << 19);
+    const int u = U - 128, v = V - 128;
+    Rgb o;
+    o.b = sat8((yy + coef[2] * u) >> 20);
+    o.g = sat8((yy + coef[4] * v + coef[3] * u) >> 20);
+    o.r = sat8((yy + coef[5] * v) >> 20);
+    return o;
+}
+
+// pixel (fy, fx) of the frame: one Y byte, one chroma pair, one conversion
+template <int FMT>
+__device__ __forceinline__ Rgb yuv_frame_px(const YuvSource &ys, int fy, int fx) {
+    const int Y = ys.y[(size_t)fy * ys.pitch_y + fx];
+    int U, V;
+    if (FMT == kPixNV12) {
+        const unsigned char *c = ys.u + (size_t)(fy >> 1) * ys.pitch_c + (fx & ~1);
+        U = c[0], V = c[1];
+    } else {
+        const size_t off = (size_t)(fy >> 1) * ys.pitch_c + (fx >> 1);
+        U = ys.u[off], V = ys.v[off];
+    }
+    return yuv_rgb(ys.coef, Y, U, V);
+}
+
+// padded-crop pixel (y, x), all three channels: RGB 0 in the padding (zero AFTER the conversion, as np.pad of the RGB crop)
+template <int FMT>
+__device__ __forceinline__ Rgb crop_px_yuv(const CropParams &cp, const YuvSource &ys, int y, int x) {
+    const int yy = y - cp.pad_top, xx = x - cp.pad_left;
+    if (yy < 0 || yy >= cp.h_crop || xx < 0 || xx >= cp.w_crop) return Rgb{0, 0, 0};
+    return yuv_frame_px<FMT>(ys, cp.y1 + yy, cp.x1 + xx);
+}
+
+// prepath_horizontal_kernel's body for one output sample, its taps read from a frame of layout FMT
+template <int FMT>
+__device__ __forceinline__ void horizontal_yuv(const CropParams &cp, const YuvSource &ys, unsigned char *o, int y, int xx, int W) {
+    if (cp.w_pad == W) {  // no horizontal pass in Pillow either
+        const Rgb p = crop_px_yuv<FMT>(cp, ys, y, xx);
+        o[0] = (unsigned char)p.r, o[1] = (unsigned char)p.g, o[2] = (unsigned char)p.b;
+        return;
+    }
+    const Taps t = taps_of(xx, cp.w_pad, W);
+    double ww;
+    weights_of(t, xx, &ww);
+    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    for (int x = 0; x < t.n; ++x) {
+        const int k = coeff(t, xx, x, ww);
+        const Rgb p = crop_px_yuv<FMT>(cp, ys, y, t.xmin + x);
+        s0 += p.r * k, s1 += p.g * k, s2 += p.b * k;
+    }
+    o[0] = (unsigned char)clip8(s0), o[1] = (unsigned char)clip8(s1), o[2] = (unsigned char)clip8(s2);
+}
+
+// four bytes at p (p + 3 readable): one dword where the address allows it
+__device__ __forceinline__ unsigned load4(const unsigned char *p) {
+    if (((size_t)p & 3) == 0) return *(const unsigned *)p;
+    return (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) | ((unsigned)p[3] << 24);
+}
+
+}  // namespace
+
+// pass 1 from YUV frames: the layout is the crop's (one crop per blockIdx.y, so the branch is uniform over the block)
+__global__ __launch_bounds__(256) void prepath_horizontal_yuv_kernel(const CropParams *crops, const YuvSource *srcs, unsigned char *tmp,
+                                                                    int W) {
+    const CropParams cp = crops[blockIdx.y];
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)cp.h_pad * W) return;
+    const YuvSource ys = srcs[blockIdx.y];
+    const int y = (int)(idx / W), xx = (int)(idx - (long)y * W);
+    unsigned char *o = tmp + cp.tmp_off + ((size_t)y * W + xx) * 3;
+    if (ys.format == kPixNV12)
+        horizontal_yuv<kPixNV12>(cp, ys, o, y, xx, W);
+    else
+        horizontal_yuv<kPixI420>(cp, ys, o, y, xx, W);
+}
+
+hipError_t launch_prepath_yuv(const CropParams *crops_dev, const YuvSource *src_dev, int n, int max_h_pad, unsigned char *tmp_dev,
+                              float *images_dev, int H, int W, hipStream_t s) {
+    constexpr int kMaxGridY = 65535;   // as launch_prepath
+    for (int lo = 0; lo < n; lo += kMaxGridY) {
+        const int nb = n - lo < kMaxGridY ? n - lo : kMaxGridY;
+        dim3 g1((unsigned)(((long)max_h_pad * W + 255) / 256), nb);
+        hipLaunchKernelGGL(prepath_horizontal_yuv_kernel, g1, dim3(256), 0, s, crops_dev + lo, src_dev + lo, tmp_dev, W);
+        dim3 g2((unsigned)(((long)H * W + 255) / 256), nb);
+        hipLaunchKernelGGL(prepath_vertical_kernel, g2, dim3(256), 0, s, crops_dev + lo, (const unsigned char *)tmp_dev,
+                           images_dev + (size_t)lo * 3 * H * W, H, W);
+    }
+    return hipGetLastError();
+}
+
+// A whole frame to contiguous (height, width, 3) BGR, for the consumer that needs BGR (the detector).  One thread converts a
+// run of 4 pixels of a row PAIR: 2 x 4 Y bytes and the 2 chroma pairs they share, out as 2 x 12 bytes = three dword stores per
+// row where the row's address allows it (always when width % 4 == 0), bytes otherwise and in a last run of 2 pixels.
+constexpr int kYuvRun = 4;
+
+template <int FMT>
+__global__ __launch_bounds__(256) void yuv_to_bgr_kernel(YuvSource ys, int height, int width, unsigned char *bgr) {
+    const int runs = (width + kYuvRun - 1) / kYuvRun;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)(height / 2) * runs) return;
+    const int yp = (int)(idx / runs), x0 = (int)(idx - (long)yp * runs) * kYuvRun;
+    const int npx = width - x0 < kYuvRun ? width - x0 : kYuvRun;   // 4, or 2 at the end of a row (width is even)
+    int U[2], V[2];
+    if (FMT == kPixNV12) {
+        const unsigned char *c = ys.u + (size_t)yp * ys.pitch_c + x0;
+        if (npx == kYuvRun) {
+            const unsigned q = load4(c);
+            U[0] = q & 255, V[0] = (q >> 8) & 255, U[1] = (q >> 16) & 255, V[1] = q >> 24;
+        } else {
+            U[0] = U[1] = c[0], V[0] = V[1] = c[1];
+        }
+    } else {
+        const size_t off = (size_t)yp * ys.pitch_c + (x0 >> 1);
+        const int last = npx == kYuvRun ? 1 : 0;
+        U[0] = ys.u[off], V[0] = ys.v[off], U[1] = ys.u[off + last], V[1] = ys.v[off + last];
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int fy = 2 * yp + r;
+        const unsigned char *yrow = ys.y + (size_t)fy * ys.pitch_y + x0;
+        unsigned char *o = bgr + ((size_t)fy * width + x0) * 3;
+        if (npx == kYuvRun) {
+            const unsigned q = load4(yrow);
+            unsigned char px[12];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const Rgb p = yuv_rgb(ys.coef, (q >> (8 * k)) & 255, U[k >> 1], V[k >> 1]);
+                px[3 * k] = (unsigned char)p.b, px[3 * k + 1] = (unsigned char)p.g, px[3 * k + 2] = (unsigned char)p.r;
+            }
+            if (((size_t)o & 3) == 0) {
+                unsigned *o4 = (unsigned *)o;
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    o4[k] = (unsigned)px[4 * k] | ((unsigned)px[4 * k + 1] << 8) | ((unsigned)px[4 * k + 2] << 16) | ((unsigned)px[4 * k + 3] << 24);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 12; ++k) o[k] = px[k];
+            }
+        } else {
+            for (int k = 0; k < npx; ++k) {
+                const Rgb p = yuv_rgb(ys.coef, yrow[k], U[0], V[0]);
+                o[3 * k] = (unsigned char)p.b, o[3 * k + 1] = (unsigned char)p.g, o[3 * k + 2] = (unsigned char)p.r;
+            }
+        }
+    }
+}
+
+hipError_t launch_yuv_to_bgr(const YuvSource &src, int height, int width, unsigned char *bgr_dev, hipStream_t s) {
+    const long threads = (long)(height / 2) * ((width + kYuvRun - 1) / kYuvRun);
+    dim3 g((unsigned)((threads + 255) / 256));
+    if (src.format == kPixNV12)
+        hipLaunchKernelGGL(yuv_to_bgr_kernel<kPixNV12>, g, dim3(256), 0, s, src, height, width, bgr_dev);
+    else
+        hipLaunchKernelGGL(yuv_to_bgr_kernel<kPixI420>, g, dim3(256), 0, s, src, height, width, bgr_dev);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Single-person pre-path: cv2.resize(frame, (W, H), interpolation) + BGR -> RGB + ToTensor + Normalize
 // (SimpleHRNet.py:213-222, 355-366) for 8-bit 3-channel frames.  OpenCV is a third-party dependency of the reference that is
 // not in this image: the arithmetic below follows the published generic path of modules/imgproc/src/resize.cpp (fixed-point

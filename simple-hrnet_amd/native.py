@@ -103,9 +103,90 @@ def _detections(detections) -> np.ndarray:
     return np.ascontiguousarray(d[:, :4]) if len(d) else np.zeros((0, 4), np.float32)
 
 
+def _host_bytes(frame) -> torch.Tensor:
+    """the bytes of a host frame of ``predict_clip`` as a flat uint8 tensor: what is uploaded (a ``YuvFrame``: 1.5 bytes per pixel)"""
+    return frame.data if isinstance(frame, YuvFrame) else frame.view(-1)
+
+
 def _check_frame(frame, k: int):
     if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3 or min(frame.shape[:2]) < 1:
         raise ValueError("frame %d must be (H, W, 3) uint8 BGR" % k)
+
+
+PIX_FORMATS = {"nv12": 1, "i420": 2}          # include/hrnet_mi355.h: HRN_PIX_*
+YUV_MATRICES = {"bt601": 0, "bt709": 1}        # HRN_YUV_BT601 / _BT709
+YUV_RANGES = {"limited": 0, "full": 1}         # HRN_YUV_LIMITED / _FULL
+
+
+class YuvFrame:
+    """One 8-bit 4:2:0 video frame as a decoder or ``ffmpeg -pix_fmt nv12|yuv420p`` delivers it, accepted wherever a BGR frame is
+    (``preprocess_frame(s)``, ``predict_frame(s)``, ``predict_clip``) and by ``NativeHRNet.yuv_to_bgr``.
+
+    ``data``: uint8 tensor or array of any shape, host or device, in the rawvideo layout: ``height`` rows of ``pitch`` bytes of Y,
+    then the chroma -- ``"nv12"``: ``height / 2`` rows of ``pitch`` bytes of interleaved U, V; ``"i420"``: ``height / 2`` rows of
+    ``pitch / 2`` bytes of U, then the same of V.  ``pitch`` defaults to ``width``; bytes of a row beyond the width are never
+    read into a result.  ``matrix``: ``"bt601"`` or ``"bt709"``; ``range``: ``"limited"`` (16..235) or ``"full"``.
+    ValueError on an odd or non-positive size, a pitch below the width (odd, for i420), a buffer shorter than ``nbytes``, or
+    an unknown format, matrix or range."""
+
+    def __init__(self, data, height: int, width: int, format: str = "nv12", matrix: str = "bt601", range: str = "limited",  # noqa: A002
+                 pitch: Optional[int] = None):
+        if format not in PIX_FORMATS:
+            raise ValueError("format must be 'nv12' or 'i420', got %r" % (format,))
+        if matrix not in YUV_MATRICES:
+            raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
+        if range not in YUV_RANGES:
+            raise ValueError("range must be 'limited' or 'full', got %r" % (range,))
+        height, width = int(height), int(width)
+        if height <= 0 or width <= 0 or height % 2 or width % 2:
+            raise ValueError("a 4:2:0 frame has an even, positive height and width, got %d x %d" % (height, width))
+        pitch = width if pitch is None else int(pitch)
+        if pitch < width:
+            raise ValueError("pitch %d is below the width %d" % (pitch, width))
+        if format == "i420" and pitch % 2:
+            raise ValueError("an i420 frame has an even pitch (its chroma rows are pitch / 2 bytes), got %d" % pitch)
+        if not isinstance(data, torch.Tensor):
+            data = torch.from_numpy(np.ascontiguousarray(data))
+        if data.dtype != torch.uint8:
+            raise ValueError("data must be uint8")
+        self.height, self.width, self.pitch = height, width, pitch
+        self.format, self.matrix, self.range = format, matrix, range
+        data = data.contiguous().view(-1)
+        if data.numel() < self.nbytes:
+            raise ValueError("a %d x %d %s frame of pitch %d has %d bytes, the buffer has %d"
+                             % (height, width, format, pitch, self.nbytes, data.numel()))
+        self.data = data[:self.nbytes]
+
+    @property
+    def nbytes(self) -> int:
+        return self.pitch * self.height * 3 // 2
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def to(self, device, non_blocking: bool = False) -> "YuvFrame":
+        """the same frame with its bytes on ``device`` (itself when they already are)"""
+        data = self.data.to(device, non_blocking=non_blocking)
+        return self if data is self.data else YuvFrame(data, self.height, self.width, self.format, self.matrix, self.range, self.pitch)
+
+    def _fill(self, entry: "_lib.YuvFrameC", base: Optional[int] = None):
+        """``entry`` = the ``hrn_yuv_frame`` of this frame, its bytes at device address ``base`` (default: where ``data`` is)"""
+        base = self.data.data_ptr() if base is None else base
+        luma = self.pitch * self.height
+        entry.y, entry.u = base, base + luma
+        entry.v = base + luma + (self.pitch // 2) * (self.height // 2) if self.format == "i420" else None
+        entry.height, entry.width, entry.pitch_y = self.height, self.width, self.pitch
+        entry.pitch_c = self.pitch if self.format == "nv12" else self.pitch // 2
+        entry.format, entry.matrix, entry.range = PIX_FORMATS[self.format], YUV_MATRICES[self.matrix], YUV_RANGES[self.range]
+
+
+def _frame_kind(frames) -> bool:
+    """True when the (non-None) frames are ``YuvFrame``s, False when none is; a mixture raises ValueError"""
+    kinds = {isinstance(f, YuvFrame) for f in frames if f is not None}
+    if len(kinds) > 1:
+        raise ValueError("the frames of one call are all YuvFrames or all BGR frames, not a mixture")
+    return kinds == {True}
 
 
 def _warp_arguments(nframes: int, size_wh, centers, scales, rotations, frame_index, pixel_std, matrices):
@@ -450,7 +531,8 @@ class NativeHRNet:
     def preprocess_frame(self, frame: torch.Tensor, detections, variant: str = "pad") -> Tuple[torch.Tensor, np.ndarray, torch.Tensor]:
         """The crop pre-path of ``SimpleHRNet.predict`` for one frame (``SimpleHRNet.py:236-278``) on the GPU.
 
-        ``frame``: (Hf, Wf, 3) uint8 BGR (the cv2 frame; host tensors / arrays are uploaded once);
+        ``frame``: (Hf, Wf, 3) uint8 BGR (the cv2 frame; host tensors / arrays are uploaded once), or a ``YuvFrame`` (NV12 / I420:
+        the crops equal, bit for bit, those of the frame ``yuv_to_bgr`` makes of it);
         ``detections``: (P, >=4) float array-like, columns 0..3 = x1, y1, x2, y2 as the detector returns them.
         ``variant``: ``"pad"`` = the single-image path (aspect ratio corrected by zero padding), ``"clamp"`` = the batch
         path's enlarge-and-clamp (``SimpleHRNet.py:383-412``; call once per image of the stack).
@@ -458,6 +540,10 @@ class NativeHRNet:
         to the reference's ``ToPILImage -> Resize -> ToTensor -> Normalize`` of the RGB crops."""
         if variant not in ("pad", "clamp"):
             raise ValueError("variant must be 'pad' or 'clamp'")
+        if isinstance(frame, YuvFrame):   # the same call over a one-frame table of hrn_preprocess_frames_yuv
+            frame = frame.to(self.torch_device, non_blocking=True)
+            dets = _detections(detections)
+            return self._preprocess_table(self._frame_table([frame]), 1, dets, np.zeros(len(dets), np.int32), variant)
         if not isinstance(frame, torch.Tensor):
             frame = torch.from_numpy(np.ascontiguousarray(frame))
         if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3:
@@ -480,6 +566,20 @@ class NativeHRNet:
                                                     boxes.ctypes.data, boxes_dev.data_ptr(), self._stream())
             self._check(rc, "hrn_preprocess_frame")
         return images, boxes, boxes_dev
+
+    def yuv_to_bgr(self, frame: YuvFrame) -> torch.Tensor:
+        """A whole ``YuvFrame`` as an (H, W, 3) uint8 BGR tensor on the engine's GPU (``hrn_yuv_to_bgr``): the bridge to a consumer
+        that needs BGR, such as the detector -- a host frame still crosses PCIe once, at 1.5 bytes per pixel.  The arithmetic is
+        the crop pre-path's (include/hrnet_mi355.h), cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420)'s form."""
+        if not isinstance(frame, YuvFrame):
+            raise TypeError("yuv_to_bgr takes a YuvFrame")
+        frame = frame.to(self.torch_device, non_blocking=True)
+        out = torch.empty((frame.height, frame.width, 3), dtype=torch.uint8, device=self.torch_device)
+        entry = _lib.YuvFrameC()
+        frame._fill(entry)
+        with torch.cuda.device(self.device_index):
+            self._check(self._lib.hrn_yuv_to_bgr(self._h, ctypes.byref(entry), out.data_ptr(), self._stream()), "hrn_yuv_to_bgr")
+        return out
 
     def resize_frames(self, frames, interpolation: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The single-person pre-path (``multiperson=False``, ``SimpleHRNet.py:213-222`` / ``:355-366``) on the GPU:
@@ -688,7 +788,8 @@ class NativeHRNet:
     # -- clip mode: the people of many frames in one pre-path launch and one pass (throughput, not latency) ------------------
     def _device_frames(self, frames) -> List[Optional[torch.Tensor]]:
         """``frames`` of ``preprocess_frames`` as a list of contiguous (Hf, Wf, 3) uint8 tensors on the engine's GPU; a 4-D stack
-        crosses PCIe in one copy and is then indexed, a sequence frame by frame (once each)"""
+        crosses PCIe in one copy and is then indexed, a sequence frame by frame (once each).  A sequence of ``YuvFrame``s comes
+        back as ``YuvFrame``s on the GPU; one that mixes the two kinds raises ValueError"""
         dev = self.torch_device
         if isinstance(frames, np.ndarray) and frames.ndim == 4:
             frames = torch.from_numpy(np.ascontiguousarray(frames))
@@ -698,6 +799,9 @@ class NativeHRNet:
             stack = frames.to(dev, non_blocking=True).contiguous()
             out = [stack[k] for k in range(int(stack.shape[0]))]
         else:
+            frames = list(frames)
+            if _frame_kind(frames):
+                return [None if f is None else f.to(dev, non_blocking=True) for f in frames]
             out = [None if f is None else (f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)))
                    for f in frames]
             out = [None if f is None else f.to(dev, non_blocking=True).contiguous() for f in out]
@@ -707,8 +811,12 @@ class NativeHRNet:
         return out
 
     def _preprocess_table(self, table, nframes: int, dets: np.ndarray, frame_index: np.ndarray, variant: str):
-        """``hrn_preprocess_frames`` over a ready frame table (``_lib.Frame`` array whose device memory the caller keeps alive):
-        ``dets`` (n, 4) float32, ``frame_index`` (n,) int32.  Returns ``(images, boxes numpy, boxes on the device)``."""
+        """``hrn_preprocess_frames`` over a ready frame table (``_lib.Frame`` array whose device memory the caller keeps alive), or
+        ``hrn_preprocess_frames_yuv`` over a ``_lib.YuvFrameC`` array: ``dets`` (n, 4) float32, ``frame_index`` (n,) int32.
+        Returns ``(images, boxes numpy, boxes on the device)``."""
+        yuv = isinstance(table, ctypes.Array) and table._type_ is _lib.YuvFrameC
+        entry, name = (self._lib.hrn_preprocess_frames_yuv, "hrn_preprocess_frames_yuv") if yuv else \
+            (self._lib.hrn_preprocess_frames, "hrn_preprocess_frames")
         n = len(dets)
         h, w = self.resolution
         images = torch.empty((n, 3, h, w), dtype=torch.float32, device=self.torch_device)
@@ -716,15 +824,21 @@ class NativeHRNet:
         boxes_dev = torch.empty((n, 4), dtype=torch.int32, device=self.torch_device)
         if n:
             with torch.cuda.device(self.device_index):
-                rc = self._lib.hrn_preprocess_frames(self._h, table, nframes, dets.ctypes.data, 4, frame_index.ctypes.data, n,
-                                                     0 if variant == "pad" else 1, images.data_ptr(), boxes.ctypes.data,
-                                                     boxes_dev.data_ptr(), self._stream())
-            self._check(rc, "hrn_preprocess_frames")
+                rc = entry(self._h, table, nframes, dets.ctypes.data, 4, frame_index.ctypes.data, n, 0 if variant == "pad" else 1,
+                           images.data_ptr(), boxes.ctypes.data, boxes_dev.data_ptr(), self._stream())
+            self._check(rc, name)
         return images, boxes, boxes_dev
 
     @staticmethod
     def _frame_table(frames):
-        """the ``hrn_frame`` table of a list of device frames (None: a null entry, for a frame nobody is cut from)"""
+        """the ``hrn_frame`` table of a list of device frames (None: a null entry, for a frame nobody is cut from); the
+        ``hrn_yuv_frame`` table when they are ``YuvFrame``s"""
+        if _frame_kind(frames):
+            table = (_lib.YuvFrameC * len(frames))()
+            for k, f in enumerate(frames):
+                if f is not None:
+                    f._fill(table[k])
+            return table
         table = (_lib.Frame * max(len(frames), 1))()
         for k, f in enumerate(frames):
             if f is not None:
@@ -748,8 +862,9 @@ class NativeHRNet:
         crops are written once, into the one batch the model reads -- no ``preprocess_frame`` per frame, no ``torch.cat``.
 
         ``frames``: (F, Hf, Wf, 3) uint8 BGR tensor or array, or a sequence of (Hf_k, Wf_k, 3) frames of differing sizes (host
-        frames are uploaded once; a frame without people may be None); ``detections``: F arrays (P_k, >=4), empty arrays and
-        None allowed; ``variant`` as in ``preprocess_frame``.
+        frames are uploaded once; a frame without people may be None), or a sequence of ``YuvFrame``s of any sizes, formats,
+        matrices and ranges (all frames of a call are of one kind: a mixture raises ValueError); ``detections``: F arrays
+        (P_k, >=4), empty arrays and None allowed; ``variant`` as in ``preprocess_frame``.
         Returns ``(images (sum P, 3, H, W) float32 on the GPU, boxes (sum P, 4) int32 numpy, boxes on the GPU, counts [P_k])``, the
         people in frame order -- bit-identical to the concatenated ``preprocess_frame`` outputs of the frames."""
         frames, dets = self._frame_arguments(frames, detections, variant)
@@ -815,7 +930,8 @@ class NativeHRNet:
         with the uploads hidden behind the compute.  Not a latency path -- a frame's result comes when its group has run.
 
         ``items``: iterable of ``(frame, detections)``; ``frame`` a HOST (Hf, Wf, 3) uint8 BGR tensor or array (pinned memory for a
-        truly asynchronous copy), of any size from item to item; a frame without people may be None; ``detections`` (P, >=4), empty
+        truly asynchronous copy), of any size from item to item, or a host ``YuvFrame`` (half the upload bytes; all frames of a
+        clip are of one kind, a mixture raises ValueError); a frame without people may be None; ``detections`` (P, >=4), empty
         or None.  Device-resident frames are refused (TypeError): they go to ``predict_frames``.
         Frames are read ahead into groups of at most ``people_per_pass`` people (default and upper bound ``max_batch``;
         ``group_frames``).  A group's frames are uploaded on a copy stream into one of two device arenas (grown on demand, frames at
@@ -834,17 +950,22 @@ class NativeHRNet:
         landed = [torch.cuda.Event(), torch.cuda.Event()]
         consumed = [None, None]
         held = {}            # frame number -> (host frame or None, detections) of the frames read ahead and not yet run
+        kinds = set()        # {True}: a clip of YuvFrames, {False}: of BGR frames
 
         def counts():        # feeds group_frames, which reads one frame ahead of the group it forms
             for k, item in enumerate(items):
                 frame, d = item
-                if isinstance(frame, torch.Tensor) and frame.device.type != "cpu":
+                if isinstance(frame, (torch.Tensor, YuvFrame)) and frame.device.type != "cpu":
                     raise TypeError("predict_clip takes host frames; device-resident frames go to predict_frames")
                 d = _detections(d)
                 if frame is not None:
-                    frame = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame))
-                    _check_frame(frame, k)
-                    frame = frame.contiguous()
+                    kinds.add(isinstance(frame, YuvFrame))
+                    if len(kinds) > 1:
+                        raise ValueError("the frames of one clip are all YuvFrames or all BGR frames, not a mixture")
+                    if not isinstance(frame, YuvFrame):
+                        frame = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame))
+                        _check_frame(frame, k)
+                        frame = frame.contiguous()
                 elif len(d):
                     raise ValueError("frame %d is None but has %d detections" % (k, len(d)))
                 held[k] = (frame, d)
@@ -854,12 +975,12 @@ class NativeHRNet:
             """the frames of `group` that somebody is cut from -> arena[slot] on the copy stream; returns the group's table"""
             first = group[0][0]
             nfr = group[-1][0] - first + 1
-            table = (_lib.Frame * nfr)()
+            table = ((_lib.YuvFrameC if kinds == {True} else _lib.Frame) * nfr)()
             offs, need = {}, 0
             for f, lo, hi in group:
                 if hi > lo and f not in offs:
                     offs[f] = need
-                    need += (held[f][0].numel() + 255) // 256 * 256
+                    need += (_host_bytes(held[f][0]).numel() + 255) // 256 * 256
             if need and (arena[slot] is None or arena[slot].numel() < need):
                 # a new arena comes from the caching allocator on the COMPUTE stream and may be recycled memory that kernels already
                 # queued there still read: the upload into it must not overtake them
@@ -871,7 +992,11 @@ class NativeHRNet:
                     copy.wait_event(consumed[slot])              # the pre-path that read this arena has finished
                 for f, off in offs.items():
                     frame = held[f][0]
-                    arena[slot][off:off + frame.numel()].copy_(frame.view(-1), non_blocking=True)
+                    flat = _host_bytes(frame)
+                    arena[slot][off:off + flat.numel()].copy_(flat, non_blocking=True)
+                    if isinstance(frame, YuvFrame):
+                        frame._fill(table[f - first], arena[slot].data_ptr() + off)
+                        continue
                     table[f - first].data = arena[slot].data_ptr() + off
                     table[f - first].height, table[f - first].width = int(frame.shape[0]), int(frame.shape[1])
                 landed[slot].record(copy)

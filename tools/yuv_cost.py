@@ -1,0 +1,206 @@
+"""NV12 input against BGR input, measured: writes DIR/yuv_input.txt (and prints it).  No number here is a gate: whether YUV
+input is faster or slower than BGR input per call is a result to record.
+
+  (a) preprocess_frame, 16 people of one 1080p frame at 384x288 (the boxes of bench.py's `prepath` block), the frame resident
+      in HBM: from NV12 and from BGR.  HIP events, interleaved (round r runs the candidates in a rotated order), medians.
+  (b) yuv_to_bgr of a 1080p NV12 frame against the floor of moving its 3.1 MB in and 6.2 MB out at 6.15 TB/s (the middle of the
+      6.0-6.3 TB/s measured on MI355X, as in tools/warp_cost.py).
+  (c) a 30-frame 1080p clip, 8 people per frame (bench.make_clip), through predict_clip from pinned host memory to joints on the
+      host: host NV12 frames and host BGR frames, with the bytes each uploads.  Engine: bench.py's flagship (HRNet-W48, 384x288,
+      bf16, max_batch 256, synthetic weights); wall clock, interleaved, medians.
+  (d) the host alternative: the numpy restatement (tests/yuv_ref.py) of one 1080p NV12 -> BGR conversion, single thread of
+      numpy -- NOT cv2, which is not installed where this runs.
+  (e) --ab-root DIR: BGR preprocess_frame of (a) in THIS tree against the same call in the checkout at DIR (the parent commit,
+      built), each in fresh child processes run alternately on the same box; a difference inside the spread of the children's
+      medians is "unchanged".  Without --ab-root the pair is reported as NOT MEASURED.
+
+usage: python tools/yuv_cost.py --out DIR [--rounds R] [--reps K] [--ab-root DIR] [--skip-clip]
+       python tools/yuv_cost.py --bgr-only [--root DIR]     (the child of (e): one JSON line)"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+ap = argparse.ArgumentParser()
+ap.add_argument("--out", help="directory yuv_input.txt is written to")
+ap.add_argument("--rounds", type=int, default=9)
+ap.add_argument("--reps", type=int, default=20, help="calls per timed sample")
+ap.add_argument("--ab-root", help="checkout of the parent commit, built: BGR preprocess_frame there against here")
+ap.add_argument("--ab-pairs", type=int, default=3, help="child processes per side of the A/B")
+ap.add_argument("--skip-clip", action="store_true", help="leave (c) out (reported as NOT MEASURED)")
+ap.add_argument("--bgr-only", action="store_true", help="time BGR preprocess_frame of (a) alone and print one JSON line")
+ap.add_argument("--root", default=ROOT, help="with --bgr-only: the checkout whose package is timed")
+args = ap.parse_args()
+if not args.bgr_only and not args.out:
+    ap.error("--out is needed")
+sys.path.insert(0, os.path.abspath(args.root) if args.bgr_only else ROOT)
+import numpy as np   # noqa: E402
+import torch         # noqa: E402
+
+h, w, hf, wf, people = 384, 288, 1080, 1920, 16
+FLOOR_RATE = 6.15e12
+
+
+def prepath_boxes():
+    rng = np.random.default_rng(5)                      # bench.py: prepath_measure
+    rng.integers(0, 256, (hf, wf, 3), dtype=np.uint8)   # (its frame: drawn first there, so the boxes are the same)
+    dets = np.zeros((people, 4), np.float32)
+    for i in range(people):
+        bh = rng.integers(300, 900)
+        bw = int(bh * rng.uniform(0.3, 0.6))
+        x1, y1 = rng.uniform(0, wf - bw), rng.uniform(0, hf - bh)
+        dets[i] = (x1, y1, x1 + bw, y1 + bh)
+    return dets
+
+
+def timed(cands, rounds, reps):
+    """HIP-event ms per call of every candidate: `rounds` samples of `reps` calls each, interleaved in a rotated order"""
+    for fn in cands.values():            # warm-up: staging ring, scratch, the allocator's blocks, clocks
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    names = list(cands)
+    samples = {k: [] for k in names}
+    for r in range(rounds):
+        for k in names[r % len(names):] + names[:r % len(names)]:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                cands[k]()
+            b.record()
+            b.synchronize()
+            samples[k].append(a.elapsed_time(b) / reps)
+    return samples
+
+
+pkg = importlib.import_module("simple-hrnet_amd")
+dets16 = prepath_boxes()
+
+if args.bgr_only:
+    net = pkg.NativeHRNet(32, 17, (h, w), "bf16", max_batch=32, device=0)   # the pre-path needs no weights
+    fdev = torch.from_numpy(np.random.default_rng(6).integers(0, 256, (hf, wf, 3), dtype=np.uint8)).cuda()
+    s = timed({"bgr": lambda: net.preprocess_frame(fdev, dets16)}, args.rounds, args.reps)["bgr"]
+    net.close()
+    print(json.dumps({"median_ms": statistics.median(s), "min_ms": min(s), "max_ms": max(s)}))
+    sys.exit(0)
+
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import yuv_ref       # noqa: E402
+
+import bench         # noqa: E402  (make_clip)
+
+os.makedirs(args.out, exist_ok=True)
+lines = []
+
+
+def say(text=""):
+    print(text, flush=True)
+    lines.append(text)
+
+
+def fmt(s):
+    return "%8.4f ms  (min %.4f .. max %.4f)" % (statistics.median(s), min(s), max(s))
+
+
+say("YUV (NV12 / I420) input -- tools/yuv_cost.py; %d samples of %d calls per candidate, interleaved, HIP events, medians" % (args.rounds, args.reps))
+say("device: %s" % torch.cuda.get_device_name(0))
+rng = np.random.default_rng(6)
+nv12_host = rng.integers(0, 256, hf * wf * 3 // 2, dtype=np.uint8)
+yuv_dev = pkg.YuvFrame(nv12_host, hf, wf, "nv12").to("cuda:0")
+net = pkg.NativeHRNet(32, 17, (h, w), "bf16", max_batch=32, device=0)
+bgr_dev = net.yuv_to_bgr(yuv_dev)                      # the same picture on both sides
+same = torch.equal(net.preprocess_frame(yuv_dev, dets16)[0], net.preprocess_frame(bgr_dev, dets16)[0])
+s = timed({"nv12": lambda: net.preprocess_frame(yuv_dev, dets16), "bgr": lambda: net.preprocess_frame(bgr_dev, dets16),
+           "to_bgr": lambda: net.yuv_to_bgr(yuv_dev)}, args.rounds, args.reps)
+net.close()
+say()
+say("(a) preprocess_frame, %d people of a %dx%d frame resident in HBM, %dx%d crops (crops equal bit for bit: %s)"
+    % (people, wf, hf, h, w, "yes" if same else "NO"))
+say("    from NV12  %s" % fmt(s["nv12"]))
+say("    from BGR   %s" % fmt(s["bgr"]))
+say("    NV12 / BGR = %.3f" % (statistics.median(s["nv12"]) / statistics.median(s["bgr"])))
+floor_ms = (hf * wf * 3 // 2 + hf * wf * 3) / FLOOR_RATE * 1e3
+say()
+say("(b) yuv_to_bgr of a %dx%d NV12 frame: %.1f MB in, %.1f MB out" % (wf, hf, hf * wf * 1.5 / 1e6, hf * wf * 3 / 1e6))
+say("    measured   %s   (includes the call's host side and the allocation of the output tensor)" % fmt(s["to_bgr"]))
+say("    floor      %8.4f ms  at %.2f TB/s; measured / floor = %.1f" % (floor_ms, FLOOR_RATE / 1e12, statistics.median(s["to_bgr"]) / floor_ms))
+
+say()
+if args.skip_clip:
+    say("(c) 30-frame clip through predict_clip, host NV12 against host BGR: NOT MEASURED (--skip-clip)")
+else:
+    nf = 30
+    _, dets = bench.make_clip(frames=nf)
+    eng = pkg.NativeHRNet(48, 17, (384, 288), "bf16", max_batch=256, device=0).load_state_dict(pkg.synth_state_dict(48, 17, 0))
+    conv = pkg.NativeHRNet(32, 17, (64, 64), "bf16", max_batch=1, device=0)
+    crng = np.random.default_rng(7)
+    yuv_items, bgr_items = [], []
+    for f in range(nf):                              # the same pictures on both sides: random NV12 and its BGR conversion
+        raw = torch.from_numpy(crng.integers(0, 256, hf * wf * 3 // 2, dtype=np.uint8)).pin_memory()
+        yf = pkg.YuvFrame(raw, hf, wf, "nv12")
+        yuv_items.append((yf, dets[f]))
+        bgr_items.append((conv.yuv_to_bgr(yf).cpu().pin_memory(), dets[f]))
+    conv.close()
+
+    def run(items):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = list(eng.predict_clip(iter(items), people_per_pass=64, variant="clamp"))
+        host = torch.cat([r[1] for r in res]).cpu().numpy()
+        torch.cuda.synchronize()
+        return host, time.perf_counter() - t0
+
+    arms = {"nv12": lambda: run(yuv_items), "bgr": lambda: run(bgr_items)}
+    ref = {k: arms[k]()[0] for k in arms}            # warm-up, and the joints of both sides
+    secs = {k: [] for k in arms}
+    names = list(arms)
+    for r in range(max(args.rounds, 9)):
+        for k in names[r % 2:] + names[:r % 2]:
+            secs[k].append(arms[k]()[1])
+    eng.close()
+    say("(c) %d frames %dx%d x %d people through predict_clip (people_per_pass 64), pinned host frames -> joints on the host;"
+        % (nf, wf, hf, dets.shape[1]))
+    say("    HRNet-W48 384x288 bf16, max_batch 256, synthetic weights; wall clock, %d repetitions, interleaved (joints equal: %s)"
+        % (len(secs["bgr"]), "yes" if np.array_equal(ref["nv12"], ref["bgr"]) else "NO"))
+    for k, label, nbytes in (("nv12", "host NV12", hf * wf * 3 // 2), ("bgr", "host BGR ", hf * wf * 3)):
+        ms = sorted(1e3 * v for v in secs[k])
+        say("    %s  %8.2f ms  (min %.2f .. max %.2f)  %6.1f FPS   uploads %.1f MB per clip"
+            % (label, statistics.median(ms), ms[0], ms[-1], nf / (statistics.median(ms) / 1e3), nf * nbytes / 1e6))
+    say("    NV12 / BGR = %.3f" % (statistics.median(secs["nv12"]) / statistics.median(secs["bgr"])))
+
+say()
+t = []
+for _ in range(5):
+    t0 = time.perf_counter()
+    yuv_ref.yuv_to_bgr(nv12_host, hf, wf, "nv12")
+    t.append(1e3 * (time.perf_counter() - t0))
+say("(d) the host alternative, NUMPY (tests/yuv_ref.py, not cv2): one %dx%d NV12 -> BGR conversion" % (wf, hf))
+say("    %8.2f ms  (min %.2f .. max %.2f of 5)" % (statistics.median(t), min(t), max(t)))
+
+say()
+if not args.ab_root:
+    say("(e) BGR preprocess_frame of (a), this tree against the parent commit: NOT MEASURED (no --ab-root)")
+else:
+    sides = {"parent": os.path.abspath(args.ab_root), "this tree": ROOT}
+    meds = {k: [] for k in sides}
+    for _ in range(args.ab_pairs):
+        for k, root in sides.items():    # fresh children, alternately
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--bgr-only", "--root", root, "--rounds", str(args.rounds),
+                                  "--reps", str(args.reps)],
+                                 capture_output=True, text=True, timeout=300, check=True).stdout
+            meds[k].append(json.loads(out.strip().splitlines()[-1])["median_ms"])
+    say("(e) BGR preprocess_frame of (a): this tree against the parent commit, %d fresh processes per side, alternately, same box" % args.ab_pairs)
+    for k in sides:
+        say("    %-10s medians %s ms -> %.4f ms" % (k, ", ".join("%.4f" % v for v in meds[k]), statistics.median(meds[k])))
+    spread = max(max(v) - min(v) for v in meds.values())
+    diff = statistics.median(meds["this tree"]) - statistics.median(meds["parent"])
+    say("    difference %+.4f ms; spread of the processes' medians (the wider side) %.4f ms -> %s"
+        % (diff, spread, "unchanged" if abs(diff) <= spread else ("SLOWER" if diff > 0 else "faster") + " beyond the spread"))
+with open(os.path.join(args.out, "yuv_input.txt"), "w") as f:
+    f.write("\n".join(lines) + "\n")
