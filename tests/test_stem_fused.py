@@ -2,9 +2,10 @@
 models_/hrnet.py:158-163).
 
 CPU: which handles plan it, that its problem and block map cover every output row of conv2 once, that the two-launch path
-stays in the plan.  GPU: with the kernel on / off the net is BIT-IDENTICAL -- conv2's own output (tap "conv2") and the heat
-maps -- on every geometry (crop widths from 32 to 288, W32 / W48), for mirrored
-crops (flip-TTA), at batch 1 and at batch 256; a call that taps "stem" still gets conv1's output."""
+stays in the plan.  GPU: with the kernel on / off the PLAIN pass is BIT-IDENTICAL -- conv2's own output (tap "conv2") and the heat
+maps -- on every geometry of GEOMS (crop widths from 32 to 288, W32 / W48) and at batch 256; a call that taps "stem" still gets
+conv1's output.  Mirrored crops (flip-TTA) are compared on / off here at W48 384x288 only: the kernel's mirrored load on the other
+widths, in bf16 and fp16, is pinned by tests/test_flip_exact_gpu.py (exactly, against the plain pass on host-flipped crops)."""
 import numpy as np
 import pytest
 import torch
