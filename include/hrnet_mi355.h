@@ -221,6 +221,68 @@ int hrn_crop_geometry(const float *dets, int det_stride, int n, const int32_t *f
                       int32_t *slice_out /* (n,8): x1,y1,w_crop,h_crop,pad_top,pad_left,h_pad,w_pad */);
 const char *hrn_crop_geometry_last_error(void);
 
+/* ---- pose overlays on the GPU: the joints and bones of every person, drawn into frames that stay on the device ----
+ * Replaces, for every frame of the two demo programs (scripts/live-demo.py:135-138, scripts/extract-keypoints.py's sibling loop),
+ *   for i, pt in enumerate(pts): frame = draw_points_and_skeleton(frame, pt, skeleton, person_index=i, ...)
+ * (misc/visualization.py:71-192: cv2.line per bone, thickness 2, then cv2.circle per joint, filled) -- the one step that still
+ * forced a decoded frame through the host.  OpenCV is not available where this library is built and tested, and cv2.line's
+ * fixed-point polygon fill cannot be restated blind, so THE CONTRACT IS THIS INTEGER DEFINITION, which looks like the reference's
+ * overlay; pixel equality with a cv2 build is NOT claimed (tests/golden/make_draw_golden.py counts the differing pixels wherever
+ * opencv-python is installed).  tests/draw_ref.py restates the definition in numpy; the kernels equal it byte for byte.
+ *
+ * Inputs.  pts (n, J, 3) float32 (y, x, confidence), as hrn_forward writes them.  A joint is LIVE iff confidence > threshold
+ * (float32; equality and NaN are not live), y and x are finite, and X = trunc(x), Y = trunc(y) (towards zero, Python's int():
+ * -0.7 -> 0) lie in [-8192, 16383].  Frame sides are at most 8192.  With these bounds every expression below fits signed 64 bits:
+ * |w| < 2^14 and |d| < 2^14.6 per component, 4 cross^2 < 2^62.
+ * Joint disc.  Radius r >= 1 (radius = 0: the reference's max(1, min(height, width) / 160), per canvas).  The disc of a live joint
+ * covers pixel (px, py) iff (px - X)^2 + (py - Y)^2 <= r*r + r: the 3x3 square for r = 1, the 5x5 without corners for r = 2, row
+ * half-widths 3, 3, 2, 1 for r = 3.
+ * Bone.  Bone k = (a, b) of the skeleton is drawn iff both joints are live; thickness T.  With P0 = (Xa, Ya), P1 = (Xb, Yb),
+ * d = P1 - P0, L2 = d.d, w = p - P0, t = w.d it covers p iff
+ *     t <= 0  and 4 |w|^2 <= T^2,   or   t >= L2 and 4 |p - P1|^2 <= T^2,   or otherwise   4 (wx dy - wy dx)^2 <= T^2 L2
+ * -- a capsule of radius T / 2 around the segment (T = 2: a horizontal bone is 3 rows thick with one-pixel tips; P0 == P1: a plus).
+ * Order.  Primitives are numbered person-major in call order, inside a person the bones k = 0 .. K-1, then the joints
+ * j = 0 .. J-1; a pixel takes the colour of the HIGHEST-numbered primitive that covers it (the reference's loop: later draws
+ * overwrite).  Joint j takes point_colors[j % Cp]; every bone of person i takes bone_colors[person_index[i] mod Cb] (Python's
+ * modulo: never negative; person_index NULL: i).
+ * Untouched pixels are NOT WRITTEN: the call is in place, every other byte of a buffer (pitch padding included) keeps its value.
+ * YUV canvases (NV12 / I420, even sides, any pitch): colours are (Y, U, V) bytes (hrn_yuv_from_bgr); a covered pixel's Y byte takes
+ * the winner's Y; the chroma sample of a 2x2 block is written iff at least one of its four pixels is covered, and takes U and V of
+ * the highest-numbered primitive that covers any of the four.
+ *
+ *   canvases_host     nframes entries on the HOST; hrn_canvas has hrn_yuv_frame's fields with writable planes.  HRN_PIX_BGR: y = the
+ *                     (height, width, 3) uint8 pixels, pitch_y = bytes between rows >= 3 * width (a view into a larger buffer
+ *                     works), the other fields unused.  NV12 / I420: as hrn_yuv_frame; matrix and range are documentation only.
+ *                     All canvases people refer to are BGR, or all are YUV; one nobody refers to may be null.
+ *                     The canvases people refer to must NOT OVERLAP in memory (each byte has one writer, in no order between
+ *                     canvases): two entries with the same first plane are refused, overlapping views are the caller's to avoid.
+ *   pts_dev           (n, J, 3) float32 on the device, J in [1, HRN_MAX_JOINTS]
+ *   frame_index_host  n entries: person i is drawn on canvases_host[frame_index_host[i]]; NULL: nframes == 1
+ *   skeleton_host     K pairs of int32 joint indices in [0, J), K in [0, 65535]
+ *   point_colors_host / bone_colors_host   Cp / Cb colours of three bytes, in the canvas's channel order (B, G, R or Y, U, V)
+ *   radius in [0, 64], thickness in [1, 16]
+ * Two launches whatever n and nframes (build: one record per person from the joints where they lie, no host synchronisation;
+ * rasterise: one block per 32 x 32 tile of the canvases referred to), stream-ordered.  n == 0 succeeds and launches nothing.
+ * Fails with code 7 and nothing launched, each failure naming its cause, on: null tables; n < 0; J, K, Cp, Cb, radius or thickness
+ * out of range; a skeleton index outside [0, J); a frame index outside [0, nframes); a referenced canvas that is null, has an
+ * unknown format, a non-positive, odd-for-YUV or over-8192 side, or too small a pitch; mixed formats; two referenced canvases
+ * that name the same buffer; a plan-only handle.
+ * Everything is judged before the device is touched, as in hrn_preprocess_frames_yuv.
+ *
+ * hrn_yuv_from_bgr (no handle, no GPU): n (B, G, R) colours to (Y, U, V) by the float64 forward formula of the matrix and range
+ * that hrn_yuv_coefficients quantises: Y' = Kr R + Kg G + Kb B; Y = y0 + sy Y'; U = 128 + sc (B - Y') / (2 (1 - Kb));
+ * V = 128 + sc (R - Y') / (2 (1 - Kr)); sy = 219/255 and sc = 224/255 for limited range (y0 = 16), 1 for full; each clip8(rint(.)).
+ * Through the conversion above the round trip errs by at most 2 grey levels (limited) / 1 (full) over all 2^24 colours. */
+enum { HRN_PIX_BGR = 0 };
+typedef struct { uint8_t *y, *u, *v;           /* device; BGR: y = the pixels; NV12: u = the UV plane */
+                 int32_t height, width, pitch_y, pitch_c, format, matrix, range; } hrn_canvas;
+int hrn_draw_poses(hrn_handle h, const hrn_canvas *canvases_host, int nframes, const float *pts_dev, int n, int J,
+                   const int32_t *frame_index_host /* n entries; NULL: nframes == 1 */, const int32_t *skeleton_host, int K,
+                   const uint8_t *point_colors_host, int Cp, const uint8_t *bone_colors_host, int Cb,
+                   const int32_t *person_index_host /* n entries or NULL */, int radius /* 0: the reference's rule */,
+                   int thickness, float threshold, void *stream);
+int hrn_yuv_from_bgr(int matrix, int range, const uint8_t *bgr /* (n,3) */, int n, uint8_t *yuv_out /* (n,3) */);
+
 /* Single-person pre-path on the GPU: replaces, for every frame of a call with multiperson=False,
  *   cv2.resize(image, (W, H), interpolation=self.interpolation); cv2.cvtColor(image, cv2.COLOR_BGR2RGB); self.transform(image)
  * (SimpleHRNet.py:213-222 for one frame, :355-366 for a stack; default interpolation cv2.INTER_CUBIC, :27) and writes the

@@ -21,6 +21,7 @@ if os.environ.get("HRN_LIB_TAG"):   # A/B runs of compile-time variants (tools/m
 SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "conv3x3_f32.hip", "bottleneck_chain.hip", "prepath.hip", "warp.hip", "nms.hip", "postproc.cpp", "hrnet_mi355.cpp",
            "decode.hip",   # heat-maps to joint coordinates: the plain and sub-pixel decodes, flip-TTA's decode
            "score.hip",    # heat-maps against the ground truth: Gaussian targets, loss and PCK of an evaluation batch
+           "draw.hip",     # pose overlays: joints and bones of every person drawn into BGR / NV12 / I420 frames on the device
            # fp16 instantiations of the three hand-scheduled kernel families (bodies shared through conv3x3_lds.inc / conv_s2.inc /
            # bottleneck_chain.inc): translation units of their own, so that each bf16 file still compiles to exactly its kernel set
            "conv3x3_lds_f16.hip", "conv_s2_f16.hip", "bottleneck_chain_f16.hip"]
@@ -188,6 +189,12 @@ class YuvFrameC(ctypes.Structure):
                 ("matrix", ctypes.c_int32), ("range", ctypes.c_int32)]
 
 
+class CanvasC(ctypes.Structure):
+    """hrn_canvas: one frame hrn_draw_poses draws into -- hrn_yuv_frame's fields with writable planes (BGR: y = the pixels,
+    pitch_y = bytes between rows, format 0)"""
+    _fields_ = list(YuvFrameC._fields_)
+
+
 # every symbol include/hrnet_mi355.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 SYMBOLS = {
@@ -215,6 +222,9 @@ SYMBOLS = {
     "hrn_yuv_to_bgr": (ctypes.c_int, [_P, ctypes.POINTER(YuvFrameC), _P, _P]),
     "hrn_preprocess_frames_yuv": (ctypes.c_int, [_P, ctypes.POINTER(YuvFrameC), ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int,
                                                  _P, _P, _P, _P]),
+    "hrn_draw_poses": (ctypes.c_int, [_P, ctypes.POINTER(CanvasC), ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_int,
+                                      _P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P]),
+    "hrn_yuv_from_bgr": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
     "hrn_crop_geometry": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
     "hrn_crop_geometry_last_error": (ctypes.c_char_p, []),
     "hrn_forward_flip_tta": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),

@@ -537,6 +537,11 @@
             if (pre_params) (void)hipFree(pre_params);
             if (pre_yuv) (void)hipFree(pre_yuv);
             pre_yuv = nullptr, pre_yuv_cap = 0;
+            if (draw_table) (void)hipFree(draw_table);
+            if (draw_records) (void)hipFree(draw_records);
+            draw_table = draw_records = nullptr, draw_table_bytes = draw_records_bytes = 0;
+            if (draw_done) (void)hipEventDestroy(draw_done);
+            draw_done = nullptr;
             if (warp_params) (void)hipFree(warp_params);
             warp_params = nullptr, warp_params_cap = 0;
             if (warp_done) (void)hipEventDestroy(warp_done);

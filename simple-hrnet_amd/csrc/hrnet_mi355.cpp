@@ -244,6 +244,12 @@ struct hrn_ctx {
         score_stream = s;
         return hip_ok(hipEventRecord(score_done, s), "hipEventRecord");
     }
+    // pose overlays (hrn_draw_poses): the call's table (canvases, people by canvas, colours, skeleton) and the per-person records the
+    // build launch writes, both on the device and grown on demand; guarded like warp_params against a call on another stream
+    char *draw_table = nullptr, *draw_records = nullptr;
+    size_t draw_table_bytes = 0, draw_records_bytes = 0;
+    hipEvent_t draw_done = nullptr;
+    hipStream_t draw_stream = nullptr;
     uint64_t map_clock = 0;    // LRU stamp of the block-map slots
     int64_t map_builds = 0;     // block maps built + uploaded since creation (hrn_map_rebuilds)
     float *scratch_hm = nullptr;  // max_batch heat-maps of the handle's own: flip-TTA's mirrored pass, a refined decode the caller gave no maps
@@ -825,6 +831,176 @@ int hrn_preprocess_frames_yuv(hrn_handle h, const hrn_yuv_frame *frames_host, in
     if (n == 0) return 0;
     return preprocess_people(h, nullptr, frames_host, frame_index_host, dets_host, det_stride, n, variant, images_dev, boxes_host,
                              boxes_dev, (hipStream_t)stream);
+}
+
+int hrn_yuv_from_bgr(int matrix, int range, const uint8_t *bgr, int n, uint8_t *yuv_out) {
+    if ((matrix != HRN_YUV_BT601 && matrix != HRN_YUV_BT709) || (range != HRN_YUV_LIMITED && range != HRN_YUV_FULL)) return 7;
+    if (n < 0 || (n > 0 && (!bgr || !yuv_out))) return 7;
+    const double kr = matrix == HRN_YUV_BT601 ? 0.299 : 0.2126, kb = matrix == HRN_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
+    const double y0 = range == HRN_YUV_LIMITED ? 16.0 : 0.0, sy = range == HRN_YUV_LIMITED ? 219.0 / 255.0 : 1.0,
+                 sc = range == HRN_YUV_LIMITED ? 224.0 / 255.0 : 1.0;
+    const auto clip8 = [](double v) { return (uint8_t)std::min(255.0, std::max(0.0, std::nearbyint(v))); };
+    for (int i = 0; i < n; ++i) {
+        const double b = bgr[3 * i], g = bgr[3 * i + 1], r = bgr[3 * i + 2];
+        const double luma = kr * r + kg * g + kb * b;
+        yuv_out[3 * i] = clip8(y0 + sy * luma);
+        yuv_out[3 * i + 1] = clip8(128.0 + sc * (b - luma) / (2.0 * (1.0 - kb)));
+        yuv_out[3 * i + 2] = clip8(128.0 + sc * (r - luma) / (2.0 * (1.0 - kr)));
+    }
+    return 0;
+}
+
+namespace {
+// what is wrong with a canvas somebody is drawn on, or nullptr
+const char *canvas_fault(const hrn_canvas &c) {
+    if (!c.y && !c.u && !c.v) return "is null";
+    if (c.format != HRN_PIX_BGR && c.format != HRN_PIX_NV12 && c.format != HRN_PIX_I420)
+        return "has an unknown format (HRN_PIX_BGR, HRN_PIX_NV12 or HRN_PIX_I420)";
+    if (c.height <= 0 || c.width <= 0) return "has a non-positive width or height";
+    if (c.height > 8192 || c.width > 8192) return "has a side above 8192";
+    if (c.format == HRN_PIX_BGR) {
+        if ((long)c.pitch_y < 3L * c.width) return "has a pitch below three times its width";
+        return c.y ? nullptr : "is null";
+    }
+    if ((c.height & 1) || (c.width & 1)) return "has an odd width or height";
+    if (c.pitch_y < c.width) return "has pitch_y below its width";
+    if (c.pitch_c < (c.format == HRN_PIX_NV12 ? c.width : c.width / 2))
+        return c.format == HRN_PIX_NV12 ? "has pitch_c below its width" : "has pitch_c below half its width";
+    if (!c.y || !c.u || (c.format == HRN_PIX_I420 && !c.v)) return "has a null plane";
+    return nullptr;
+}
+inline unsigned pack_colour(const uint8_t *c) { return (unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16); }
+inline size_t align16(size_t v) { return (v + 15) / 16 * 16; }
+}  // namespace
+
+// misc/visualization.py:71-192 for every person of every frame: the arguments are judged first (they need no device), then the
+// handle; one table upload and two launches follow
+int hrn_draw_poses(hrn_handle h, const hrn_canvas *canvases_host, int nframes, const float *pts_dev, int n, int J,
+                   const int32_t *frame_index_host, const int32_t *skeleton_host, int K, const uint8_t *point_colors_host, int Cp,
+                   const uint8_t *bone_colors_host, int Cb, const int32_t *person_index_host, int radius, int thickness,
+                   float threshold, void *stream) {
+    if (!h) return 1;
+    const auto fail = [&](const std::string &what) {
+        h->err = "hrn_draw_poses: " + what;
+        return 7;
+    };
+    if (n < 0) return fail("n is negative");
+    if (J < 1 || J > HRN_MAX_JOINTS) return fail("J must be in [1, " + std::to_string(HRN_MAX_JOINTS) + "]");
+    if (K < 0 || K > kDrawMaxBones) return fail("K must be in [0, " + std::to_string(kDrawMaxBones) + "]");
+    if (Cp < 1 || Cb < 1) return fail("Cp and Cb must be at least 1");
+    if (thickness < 1 || thickness > 16) return fail("thickness must be in [1, 16]");
+    if (radius < 0 || radius > 64) return fail("radius must be in [0, 64]");
+    if (!canvases_host || nframes < 1 || !point_colors_host || !bone_colors_host || (K > 0 && !skeleton_host) || (n > 0 && !pts_dev))
+        return fail("null canvases / joints / skeleton / colours");
+    if (!frame_index_host && nframes != 1) return fail("without frame_index there must be one frame");
+    for (int k = 0; k < 2 * K; ++k)
+        if (skeleton_host[k] < 0 || skeleton_host[k] >= J)
+            return fail("skeleton index " + std::to_string(skeleton_host[k]) + " of bone " + std::to_string(k / 2) + " is outside [0, " +
+                        std::to_string(J) + ")");
+    int kind = -1;   // 0: BGR canvases, 1: YUV
+    for (int i = 0; i < n; ++i) {
+        const long f = frame_index_host ? (long)frame_index_host[i] : 0;
+        if (f < 0 || f >= nframes)
+            return fail("frame_index " + std::to_string(f) + " of person " + std::to_string(i) + " is outside [0, " + std::to_string(nframes) + ")");
+        if (const char *fault = canvas_fault(canvases_host[f]))
+            return fail("canvas " + std::to_string(f) + ", which person " + std::to_string(i) + " is drawn on, " + fault);
+        const int k = canvases_host[f].format == HRN_PIX_BGR ? 0 : 1;
+        if (kind >= 0 && k != kind)
+            return fail("canvas " + std::to_string(f) + ", which person " + std::to_string(i) +
+                        " is drawn on, mixes formats: the canvases of a call are all BGR or all YUV");
+        kind = k;
+    }
+    // one writer per byte needs canvases that do not overlap: two table entries people are drawn on that start at the same address
+    // are refused (overlapping views of one buffer cannot be told from here: the header forbids them)
+    std::map<const uint8_t *, int> first_at;
+    for (int i = 0; i < n; ++i) {
+        const int f = frame_index_host ? frame_index_host[i] : 0;
+        const auto seen = first_at.emplace(canvases_host[f].y, f);
+        if (!seen.second && seen.first->second != f)
+            return fail("canvases " + std::to_string(seen.first->second) + " and " + std::to_string(f) +
+                        " name the same buffer: the canvases of a call must not overlap");
+    }
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (n == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+
+    // the canvases somebody refers to, in table order, and their people in call order
+    std::vector<int> slot(nframes, -1), count(nframes, 0);
+    for (int i = 0; i < n; ++i) ++count[frame_index_host ? frame_index_host[i] : 0];
+    int used = 0;
+    for (int f = 0; f < nframes; ++f)
+        if (count[f]) slot[f] = used++;
+    const size_t off_order = align16((size_t)used * sizeof(DrawFrame)), off_pframe = off_order + align16((size_t)n * 4),
+                 off_bone = off_pframe + align16((size_t)n * 4), off_point = off_bone + align16((size_t)n * 4),
+                 off_skel = off_point + align16((size_t)Cp * 4), table_bytes = off_skel + align16((size_t)std::max(K, 1) * 4);
+    unsigned ring = 0;
+    char *pin = h->pre_stage(table_bytes, &ring);
+    if (!pin) return 6;
+    DrawFrame *frames = (DrawFrame *)pin;
+    int *order = (int *)(pin + off_order), *pframe = (int *)(pin + off_pframe);
+    unsigned *bone = (unsigned *)(pin + off_bone), *point = (unsigned *)(pin + off_point), *skel = (unsigned *)(pin + off_skel);
+    int tiles = 0, people = 0;
+    for (int f = 0; f < nframes; ++f) {
+        if (slot[f] < 0) continue;
+        const hrn_canvas &c = canvases_host[f];
+        DrawFrame &d = frames[slot[f]];
+        d.p0 = c.y, d.p1 = c.format == HRN_PIX_BGR ? nullptr : c.u, d.p2 = c.format == HRN_PIX_I420 ? c.v : nullptr;
+        d.height = c.height, d.width = c.width, d.pitch0 = c.pitch_y, d.pitch1 = c.format == HRN_PIX_BGR ? 0 : c.pitch_c;
+        d.format = c.format;
+        d.radius = radius > 0 ? radius : std::max(1, std::min(c.height, c.width) / 160);   // (at most 8192 / 160 = 51)
+        d.tile_start = tiles, d.tiles_x = (c.width + kDrawTile - 1) / kDrawTile;
+        tiles += d.tiles_x * ((c.height + kDrawTile - 1) / kDrawTile);                      // (at most 256 x 256 per canvas)
+        d.person_start = people, d.person_count = 0;
+        people += count[f];
+    }
+    for (int i = 0; i < n; ++i) {
+        DrawFrame &d = frames[slot[frame_index_host ? frame_index_host[i] : 0]];
+        order[d.person_start + d.person_count++] = i;
+        pframe[i] = (int)(&d - frames);
+        const long id = person_index_host ? (long)person_index_host[i] : (long)i;
+        bone[i] = pack_colour(bone_colors_host + 3 * (size_t)(((id % Cb) + Cb) % Cb));      // Python's modulo
+    }
+    for (int k = 0; k < Cp; ++k) point[k] = pack_colour(point_colors_host + 3 * (size_t)k);
+    for (int k = 0; k < K; ++k) skel[k] = (unsigned)skeleton_host[2 * k] | ((unsigned)skeleton_host[2 * k + 1] << 16);
+
+    const size_t off_live = align16((size_t)n * J * sizeof(short2)), off_box = off_live + align16((size_t)n * (kMaxJoints / 32) * 4),
+                 rec_bytes = off_box + (size_t)n * sizeof(int4);
+    if (table_bytes > h->draw_table_bytes || rec_bytes > h->draw_records_bytes) {   // grow: wait for whoever still reads the old ones
+        if (h->draw_done && !h->hip_ok(hipEventSynchronize(h->draw_done), "hipEventSynchronize")) return 6;
+        if (table_bytes > h->draw_table_bytes) {
+            if (h->draw_table) (void)hipFree(h->draw_table);
+            h->draw_table = nullptr, h->draw_table_bytes = 0;
+            const size_t cap = std::max<size_t>(table_bytes * 2, 4096);
+            if (!h->hip_ok(hipMalloc((void **)&h->draw_table, cap), "hipMalloc(draw table)")) return 6;
+            h->draw_table_bytes = cap;
+        }
+        if (rec_bytes > h->draw_records_bytes) {
+            if (h->draw_records) (void)hipFree(h->draw_records);
+            h->draw_records = nullptr, h->draw_records_bytes = 0;
+            const size_t cap = std::max<size_t>(rec_bytes * 2, 4096);
+            if (!h->hip_ok(hipMalloc((void **)&h->draw_records, cap), "hipMalloc(draw records)")) return 6;
+            h->draw_records_bytes = cap;
+        }
+    }
+    if (h->draw_done && h->draw_stream != s && !h->hip_ok(hipStreamWaitEvent(s, h->draw_done, 0), "hipStreamWaitEvent")) return 6;
+    if (!h->draw_done && !h->hip_ok(hipEventCreateWithFlags(&h->draw_done, hipEventDisableTiming), "hipEventCreate")) return 6;
+    if (!h->hip_ok(hipMemcpyAsync(h->draw_table, pin, table_bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync(draw table)")) return 6;
+    if (!h->hip_ok(hipEventRecord(h->pre_landed[ring], s), "hipEventRecord")) return 6;
+    DrawArgs a{};
+    a.pts = pts_dev, a.n = n, a.J = J, a.K = K, a.Cp = Cp, a.nframes = used, a.total_tiles = tiles, a.thickness = thickness;
+    a.threshold = threshold;
+    a.frames = (const DrawFrame *)h->draw_table, a.order = (const int *)(h->draw_table + off_order);
+    a.person_frame = (const int *)(h->draw_table + off_pframe), a.bone_colour = (const unsigned *)(h->draw_table + off_bone);
+    a.point_colour = (const unsigned *)(h->draw_table + off_point), a.skeleton = (const unsigned *)(h->draw_table + off_skel);
+    a.xy = (short2 *)h->draw_records, a.live = (unsigned *)(h->draw_records + off_live), a.box = (int4 *)(h->draw_records + off_box);
+    const hipError_t e = launch_draw(a, s);
+    h->draw_stream = s;
+    if (!h->hip_ok(hipEventRecord(h->draw_done, s), "hipEventRecord")) return 6;
+    return h->hip_ok(e, "draw launch") ? 0 : 8;
 }
 
 int hrn_resize_frames(hrn_handle h, const uint8_t *frames_dev, int n, int frame_h, int frame_w, int interpolation,

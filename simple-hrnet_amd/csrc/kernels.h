@@ -334,6 +334,35 @@ struct ScoreArgs {
 hipError_t launch_score(const ScoreArgs &a, hipStream_t s);            // score_kernel<analytic | maps>, then score_finish_kernel
 hipError_t launch_targets(const ScoreArgs &a, float *targets_out, hipStream_t s);   // targets_kernel: (n,J,h,w) from joints / table
 
+// Pose overlays (draw.hip; include/hrnet_mi355.h: hrn_draw_poses).  The host uploads one table per call -- the canvases somebody
+// is drawn on, the people grouped by canvas in call order, colours and skeleton -- and two launches do the rest.
+constexpr int kDrawTile = 32;      // a block rasterises one 32 x 32 tile, a thread one 2 x 2 block of it (= one 4:2:0 chroma sample)
+constexpr int kDrawMaxBones = 65535;
+struct DrawFrame {                 // one canvas that at least one person refers to
+    unsigned char *p0, *p1, *p2;   // BGR: the pixels; NV12: Y, interleaved UV; I420: Y, U, V
+    int height, width, pitch0, pitch1;
+    int format;                    // HRN_PIX_BGR (0), HRN_PIX_NV12 (1) or HRN_PIX_I420 (2)
+    int radius;                    // of a joint's disc on this canvas
+    int tile_start, tiles_x;       // first tile of the launch that belongs to this canvas, tiles per tile row
+    int person_start, person_count;   // its people: order[person_start .. + person_count), in call order
+};
+struct DrawArgs {
+    const float *pts;              // (n, J, 3) (y, x, confidence), device: where the decode left them
+    int n, J, K, Cp, nframes, total_tiles, thickness;
+    float threshold;
+    const DrawFrame *frames;       // nframes entries
+    const int *order;              // n person indices grouped by canvas, call order kept inside a canvas
+    const int *person_frame;       // n: index into frames
+    const unsigned *bone_colour;   // n: the three colour bytes of the person's bones, byte 0 first
+    const unsigned *point_colour;  // Cp
+    const unsigned *skeleton;      // K: a | b << 16
+    // written by the build launch, read by the rasteriser
+    short2 *xy;                    // (n, J): truncated (x, y)
+    unsigned *live;                // (n, kMaxJoints / 32): bit j = joint j is live
+    int4 *box;                     // n: bounding box of the live joints grown by max(radius, ceil(T / 2)); (1, 1, 0, 0) when nobody is
+};
+hipError_t launch_draw(const DrawArgs &a, hipStream_t s);   // draw_build_kernel, then draw_raster_kernel
+
 struct TapArgs {           // debug tap: crops crop0, crop0 + crop_step, ... of a flat padded tensor -> (ncrops, c, h, w) fp32
     const void *in;
     float *dst;

@@ -189,6 +189,90 @@ def _frame_kind(frames) -> bool:
     return kinds == {True}
 
 
+DRAW_TILE = 32   # csrc/kernels.h: kDrawTile -- the rasteriser of draw_poses works on 32 x 32 tiles (tests place shapes across the borders)
+
+# The palettes of the reference's demo programs (scripts/live-demo.py, misc/visualization.py defaults) as (B, G, R) rows, kept
+# here so that drawing works where matplotlib is not installed; tests/golden/palettes.json holds the reference's colours they
+# (and palette()) are pinned to.  Listed palettes (tab20, Set2) ignore the sample count; sampled ones are keyed by it.
+EMBEDDED_PALETTES = {
+    ("tab20", None): [[180, 119, 31], [232, 199, 174], [14, 127, 255], [120, 187, 255], [44, 160, 44], [138, 223, 152], [40, 39, 214],
+                      [150, 152, 255], [189, 103, 148], [213, 176, 197], [75, 86, 140], [148, 156, 196], [194, 119, 227], [210, 182, 247],
+                      [127, 127, 127], [199, 199, 199], [34, 189, 188], [141, 219, 219], [207, 190, 23], [229, 218, 158]],
+    ("Set2", None): [[165, 194, 102], [98, 141, 252], [203, 160, 141], [195, 138, 231], [84, 216, 166], [47, 217, 255], [148, 196, 229],
+                     [179, 179, 179]],
+    ("gist_rainbow", 10): [[41, 0, 255], [0, 110, 255], [0, 255, 249], [0, 255, 92], [59, 255, 0], [215, 255, 0], [255, 143, 0],
+                           [255, 0, 14], [255, 0, 167], [191, 0, 255]],
+    ("jet", 8): [[128, 0, 0], [255, 16, 0], [255, 164, 0], [183, 255, 64], [64, 255, 183], [0, 185, 255], [0, 48, 255], [0, 0, 128]],
+}
+_PALETTE_CACHE: Dict[Tuple[str, int], np.ndarray] = {}
+
+
+def embedded_palette(name: str, samples: int) -> Optional[np.ndarray]:
+    """the stored (C, 3) uint8 BGR table of a demo palette, or None"""
+    rows = EMBEDDED_PALETTES.get((name, None)) or EMBEDDED_PALETTES.get((name, int(samples)))
+    return None if rows is None else np.asarray(rows, np.uint8)
+
+
+def palette(name: str, samples: int = 16) -> np.ndarray:
+    """The colours ``draw_points`` / ``draw_skeleton`` derive from a matplotlib palette name (``misc/visualization.py:91-98``) as a
+    (C, 3) uint8 array of (B, G, R) rows: a listed palette's own colours, else ``samples`` colours sampled over [0, 1].  Evaluated
+    with matplotlib where it can be imported; without it the four palettes of the demo programs (``tab20``, ``Set2``,
+    ``gist_rainbow`` at 10 samples, ``jet`` at 8) come from stored tables and any other name raises ValueError."""
+    key = (str(name), int(samples))
+    if key in _PALETTE_CACHE:
+        return _PALETTE_CACHE[key].copy()
+    try:
+        import matplotlib
+    except ImportError:
+        matplotlib = None
+    if matplotlib is None:
+        out = embedded_palette(*key)
+        if out is None:
+            raise ValueError("palette %r with %d samples is not stored and matplotlib is not installed" % key)
+    else:
+        registry = getattr(matplotlib, "colormaps", None)       # matplotlib >= 3.5; before that the lookup lived in matplotlib.cm
+        if registry is None:
+            from matplotlib import cm
+            cmap = cm.get_cmap(key[0])
+        elif key[0] in registry:
+            cmap = registry[key[0]]
+        else:
+            raise ValueError("matplotlib has no palette %r" % key[0])
+        listed = getattr(cmap, "colors", None)                   # a listed palette's own colours; a continuous one is sampled
+        rgb = np.asarray(listed, np.float64) if listed is not None else np.asarray(cmap(np.linspace(0.0, 1.0, key[1])), np.float64)
+        out = np.rint(rgb[:, :3] * 255.0).astype(np.uint8)[:, ::-1]   # 8 bits per channel, rounded half to even; R, G, B -> B, G, R
+    _PALETTE_CACHE[key] = np.ascontiguousarray(out)
+    return _PALETTE_CACHE[key].copy()
+
+
+def bgr_to_yuv_colors(colors, matrix: str = "bt601", range: str = "limited") -> np.ndarray:  # noqa: A002
+    """(C, 3) uint8 (B, G, R) colours as (Y, U, V) of a matrix and range (``hrn_yuv_from_bgr``: the float64 forward formula of the
+    conversion ``YuvFrame``s are read with, rounded once): what ``draw_poses`` draws with on a ``YuvFrame``."""
+    if matrix not in YUV_MATRICES or range not in YUV_RANGES:
+        raise ValueError("matrix must be 'bt601' or 'bt709' and range 'limited' or 'full', got %r, %r" % (matrix, range))
+    c = np.ascontiguousarray(np.asarray(colors, dtype=np.uint8).reshape(-1, 3))
+    out = np.empty_like(c)
+    rc = _lib.load().hrn_yuv_from_bgr(YUV_MATRICES[matrix], YUV_RANGES[range], c.ctypes.data, len(c), out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("hrn_yuv_from_bgr failed (%d)" % rc)
+    return out
+
+
+def _colors(spec, samples) -> np.ndarray:
+    """a palette name, or ready (C, 3) uint8 BGR colours"""
+    if isinstance(spec, str):
+        return palette(spec, samples)
+    c = np.asarray(spec)
+    if c.ndim != 2 or c.shape[1] != 3 or len(c) < 1 or c.dtype != np.uint8:
+        raise ValueError("colours must be a palette name or a (C, 3) uint8 array of (B, G, R) rows")
+    return np.ascontiguousarray(c)
+
+
+def _bgr_rows(t: torch.Tensor) -> bool:
+    """an (H, W, 3) tensor the overlay can be drawn into where it lies: packed pixels, rows any pitch >= 3 W apart"""
+    return t.stride(2) == 1 and t.stride(1) == 3 and (t.shape[0] == 1 or t.stride(0) >= 3 * t.shape[1])
+
+
 def _warp_arguments(nframes: int, size_wh, centers, scales, rotations, frame_index, pixel_std, matrices):
     """the host-side arguments of ``hrn_warp_crops``: ``(matrices (n, 6) float64, frame_index (n,) int32)``, checked -- every
     argument error is a ValueError here, before the library is called"""
@@ -580,6 +664,90 @@ class NativeHRNet:
         with torch.cuda.device(self.device_index):
             self._check(self._lib.hrn_yuv_to_bgr(self._h, ctypes.byref(entry), out.data_ptr(), self._stream()), "hrn_yuv_to_bgr")
         return out
+
+    def draw_poses(self, frames, pts, skeleton, frame_index=None, person_ids=None, points_palette="tab20", points_samples: int = 16,
+                   skeleton_palette="Set2", skeleton_samples: int = 8, confidence_threshold: float = 0.5, radius: Optional[int] = None,
+                   thickness: int = 2):
+        """The overlay of the reference's demo programs on the GPU (``hrn_draw_poses``): for every person the bones of ``skeleton``
+        and then the joints, later people over earlier ones -- the loop around ``draw_points_and_skeleton``
+        (``scripts/live-demo.py:135-138``, ``misc/visualization.py:71-192``) in two launches, whatever the number of frames and
+        people, and without the frame leaving the device.  The shapes are the integer definition of include/hrnet_mi355.h (discs,
+        capsules), which looks like cv2's circles and lines; pixel equality with cv2 is not claimed.
+
+        ``frames``: one (H, W, 3) uint8 BGR tensor or array (rows may be strided: a view into a larger frame), a ``YuvFrame``, or a
+        list of either kind (entries nobody is drawn on may be None).  Frames on the engine's GPU are drawn IN PLACE and returned;
+        host frames are uploaded and the device copy is returned.  Only covered pixels are written.
+        ``pts``: (J, 3) or (n, J, 3) (y, x, confidence) as ``predict*`` returns them, on the device or the host;
+        ``skeleton``: (K, 2) joint index pairs (``joints_dict()[set]["skeleton"]`` of the reference);
+        ``frame_index``: n frame numbers when there are several frames; ``person_ids``: the ``person_index`` of each person
+        (bone colour ``person_ids[i] % len(palette)``; default i);
+        palettes: a matplotlib name (``palette``) or ready (C, 3) uint8 BGR colours -- converted with ``bgr_to_yuv_colors`` for
+        ``YuvFrame``s, which then share one matrix and range;
+        ``radius``: of a joint's disc (default: the reference's ``max(1, min(H, W) // 160)`` per frame); ``thickness``: of a bone."""
+        single = not isinstance(frames, (list, tuple))
+        items = [frames] if single else list(frames)
+        if not items:
+            raise ValueError("draw_poses needs at least one frame")
+        yuv = _frame_kind(items)
+        dev = self.torch_device
+        canvases: List = []
+        table = (_lib.CanvasC * len(items))()
+        for k, f in enumerate(items):
+            if f is None:
+                canvases.append(None)
+                continue
+            if yuv:
+                f = f.to(dev, non_blocking=True)
+                f._fill(table[k])
+            else:
+                if not isinstance(f, torch.Tensor):
+                    f = torch.from_numpy(f if isinstance(f, np.ndarray) and all(s > 0 for s in f.strides) else np.ascontiguousarray(f))
+                _check_frame(f, k)
+                if f.device != dev:
+                    f = f.to(dev, non_blocking=True)
+                    if not _bgr_rows(f):
+                        f = f.contiguous()
+                elif not _bgr_rows(f):
+                    raise ValueError("frame %d cannot be drawn in place: its pixels must be packed (B, G, R) bytes in rows" % k)
+                e = table[k]
+                e.y, e.height, e.width = f.data_ptr(), int(f.shape[0]), int(f.shape[1])
+                e.pitch_y, e.format = max(int(f.stride(0)), 3 * int(f.shape[1])), 0
+            canvases.append(f)
+        if not isinstance(pts, torch.Tensor):
+            pts = torch.from_numpy(np.ascontiguousarray(np.asarray(pts, dtype=np.float32)))
+        if pts.dim() == 2:
+            pts = pts.unsqueeze(0)
+        if pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[1] < 1:
+            raise ValueError("pts must be (J, 3) or (n, J, 3) (y, x, confidence)")
+        pts = pts.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+        n, joints = int(pts.shape[0]), int(pts.shape[1])
+        skel = np.ascontiguousarray(np.asarray(skeleton, dtype=np.int32).reshape(-1, 2))
+        fi = None
+        if frame_index is not None:
+            fi = np.ascontiguousarray(np.asarray(frame_index, dtype=np.int32).reshape(-1))
+            if len(fi) != n:
+                raise ValueError("frame_index must have one entry per person: %d for %d people" % (len(fi), n))
+        elif len(items) != 1:
+            raise ValueError("several frames need frame_index: which frame each person is drawn on")
+        ids = None
+        if person_ids is not None:
+            ids = np.ascontiguousarray(np.asarray(person_ids, dtype=np.int32).reshape(-1))
+            if len(ids) != n:
+                raise ValueError("person_ids must have one entry per person: %d for %d people" % (len(ids), n))
+        pc, bc = _colors(points_palette, points_samples), _colors(skeleton_palette, skeleton_samples)
+        if yuv:
+            spaces = {(f.matrix, f.range) for f in canvases if f is not None}
+            if len(spaces) != 1:
+                raise ValueError("the YuvFrames of one draw_poses call share one matrix and range (the colours are converted once)")
+            (matrix, range_), = spaces
+            pc, bc = bgr_to_yuv_colors(pc, matrix, range_), bgr_to_yuv_colors(bc, matrix, range_)
+        with torch.cuda.device(self.device_index):
+            rc = self._lib.hrn_draw_poses(self._h, table, len(items), pts.data_ptr(), n, joints, None if fi is None else fi.ctypes.data,
+                                          skel.ctypes.data if len(skel) else None, len(skel), pc.ctypes.data, len(pc), bc.ctypes.data,
+                                          len(bc), None if ids is None else ids.ctypes.data, 0 if radius is None else int(radius),
+                                          int(thickness), float(confidence_threshold), self._stream())
+        self._check(rc, "hrn_draw_poses")
+        return canvases[0] if single else canvases
 
     def resize_frames(self, frames, interpolation: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The single-person pre-path (``multiperson=False``, ``SimpleHRNet.py:213-222`` / ``:355-366``) on the GPU:
