@@ -221,6 +221,70 @@ int hrn_crop_geometry(const float *dets, int det_stride, int n, const int32_t *f
                       int32_t *slice_out /* (n,8): x1,y1,w_crop,h_crop,pad_top,pad_left,h_pad,w_pad */);
 const char *hrn_crop_geometry_last_error(void);
 
+/* ---- the tracking link: people followed between two detector runs, on the device ----
+ * A top-down video pipeline runs its detector on every K-th frame only and, in between, cuts the next frame's crops from the
+ * previous frame's joints.  The two parts below make that chain -- pts(k) -> boxes -> crop records -> crops(k+1) -> pass ->
+ * pts(k+1) -- run on the device, stream-ordered, with no host read in between.  What is PINNED is that the chain equals, bit for
+ * bit, the host composition it replaces (download pts, hrn_pose_boxes, hrn_preprocess_frames with host detections); how well
+ * such boxes track on a trained network is not claimed.
+ *
+ * 1. Boxes from joints.  pts (n, J, 3) float32 (y, x, confidence) as hrn_forward writes them; each person's frame (height, width).
+ * Joint j is LIVE iff confidence > threshold (a float32 compare: equality and NaN are not live) and y and x are finite; a live
+ * coordinate enters as (double)v + 0.0 (no negative zero).  nlive < min_joints: the row is five zeros.  Otherwise, in double and in
+ * this order (no contraction):
+ *     xmin, xmax, ymin, ymax over the live joints;  cx = (xmin + xmax) * 0.5;  w = max((xmax - xmin) * scale, min_side);
+ *     x1 = max(0, cx - w * 0.5);  x2 = min(frame_w, cx + w * 0.5);  y likewise with frame_h;
+ *     score = (sum of the live confidences, as doubles, in joint order) / nlive
+ * (max(a, b) = a > b ? a : b, min(a, b) = a < b ? a : b: a zero result is +0), each of the five rounded once to float32.  The
+ * row (x1, y1, x2, y2, score) is a detection row as the detector wrappers return them: det_stride 5.  scale = 1.25 is the factor
+ * of the datasets' _box2cs.  A box lies inside its frame unless every live joint lies on one side of it (then x2 < x1 or
+ * y2 < y1: a degenerate detection, status 1 below).  tests/pose_boxes_ref.py restates the definition in numpy float64.
+ *   frame_hw   (n, 2) int32 (height, width) per person when per_person_hw != 0, else (1, 2) for everybody; HOST in both entries
+ *   threshold  float32; min_joints >= 1; scale finite and > 0; min_side finite and >= 0
+ * hrn_pose_boxes is the host form: no handle, no GPU (pts and dets_out on the host); 0, or 7 with hrn_pose_boxes_last_error()
+ * (per thread) naming the argument.  hrn_boxes_from_poses is ONE launch, one wave per person, over pts_dev where the decode left
+ * them, into dets_dev (n, 5) float32 on the device; both compile one function text (csrc/track_geometry.h).  n == 0 succeeds and
+ * launches nothing.  Fails with code 7 and nothing launched, naming the cause, on: n < 0; J outside [1, HRN_MAX_JOINTS];
+ * min_joints < 1; a non-finite or non-positive scale; a negative or non-finite min_side; null tables (n > 0); a non-positive
+ * frame side; and, after these, a plan-only handle. */
+int hrn_pose_boxes(const float *pts /* (n,J,3) */, int n, int J, const int32_t *frame_hw /* (n,2) or (1,2) */, int per_person_hw,
+                   float threshold, int min_joints, double scale, double min_side, float *dets_out /* (n,5) */);
+const char *hrn_pose_boxes_last_error(void);
+int hrn_boxes_from_poses(hrn_handle h, const float *pts_dev, int n, int J, const int32_t *frame_hw_host /* (n,2) or (1,2) */,
+                         int per_person_hw, float threshold, int min_joints, double scale, double min_side,
+                         float *dets_dev /* (n,5) */, void *stream);
+
+/* 2. The crop pre-path from detections ON THE DEVICE.  hrn_preprocess_frames_dev / _yuv_dev follow the contract of
+ * hrn_preprocess_frames / _yuv with these differences: dets_dev (n, det_stride) float32 lies on the device (det_stride >= 4);
+ * there is no boxes_host; boxes_dev (n, 4) int32 and status_dev (n) int32 are required.  The frame table and frame_index_host stay
+ * on the host: which frame a person belongs to is known without reading the device.
+ * A record kernel, one thread per person, runs hrn_crop_geometry's arithmetic (the same function text, csrc/track_geometry.h)
+ * and writes the crop record the host path would have uploaded; the horizontal and vertical kernels of the host-detection path
+ * then run unchanged on those records, so images and boxes equal hrn_preprocess_frames' bit for bit.
+ * SCRATCH.  The host sizes grid and scratch without knowing the boxes: with hcap(frame) = max(frame_h, ceil(H * frame_w / W)) + 2
+ * rows -- what a box inside the frame can need -- and hcap = the maximum over the frames people refer to (at least H), person i's
+ * intermediate lies at i * roundup(hcap * W * 3, 256): n * hcap * W * 3 bytes, about 2.2 MB per person at 1080p / 384x288 (the
+ * host-detection path allocates what the boxes need, usually much less).  It is kept by the handle and grown on demand.
+ * STATUS.  A person cannot make a stream-ordered call fail, so the call reports it in status_dev:
+ *     0  ok
+ *     1  degenerate                                  }
+ *     2  starts outside the frame                    }  the three refusals of hrn_preprocess_frames, with its predicates
+ *     3  degenerate after clamping (HRN_CROP_CLAMP)  }
+ *     4  padded crop taller than hcap of its frame (HRN_CROP_PAD; cannot happen for a box inside its frame, which every box of
+ *        hrn_boxes_from_poses is)
+ *     5  a coordinate that is not finite or exceeds 2^30 in magnitude (judged first)
+ * A five-zero row of part 1 gives status 1.  A person with status != 0 gets box (0, 0, 0, 0) and the all-padding crop -- an empty
+ * slice, h_pad = H, w_pad = W: Normalize(0) per channel; its neighbours are untouched, and its joints after the pass are
+ * meaningless, which the status says.  The padded WIDTH is not bounded, as in the host path: the cost of a crop grows with it.
+ * Argument errors are code 7, judged before the device is touched, word for word those of the host-detection entries minus the
+ * per-detection ones ("bad frames / detections / n" covers the null outputs); then a plan-only handle.  n == 0 launches nothing. */
+int hrn_preprocess_frames_dev(hrn_handle h, const hrn_frame *frames_host, int nframes, const float *dets_dev, int det_stride,
+                              const int32_t *frame_index_host /* n entries; NULL: nframes == 1 */, int n, int variant,
+                              float *images_dev, int32_t *boxes_dev, int32_t *status_dev, void *stream);
+int hrn_preprocess_frames_yuv_dev(hrn_handle h, const hrn_yuv_frame *frames_host, int nframes, const float *dets_dev,
+                                  int det_stride, const int32_t *frame_index_host, int n, int variant, float *images_dev,
+                                  int32_t *boxes_dev, int32_t *status_dev, void *stream);
+
 /* ---- pose overlays on the GPU: the joints and bones of every person, drawn into frames that stay on the device ----
  * Replaces, for every frame of the two demo programs (scripts/live-demo.py:135-138, scripts/extract-keypoints.py's sibling loop),
  *   for i, pt in enumerate(pts): frame = draw_points_and_skeleton(frame, pt, skeleton, person_index=i, ...)

@@ -22,6 +22,7 @@ SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "c
            "decode.hip",   # heat-maps to joint coordinates: the plain and sub-pixel decodes, flip-TTA's decode
            "score.hip",    # heat-maps against the ground truth: Gaussian targets, loss and PCK of an evaluation batch
            "draw.hip",     # pose overlays: joints and bones of every person drawn into BGR / NV12 / I420 frames on the device
+           "track.hip",    # the tracking link: boxes from joints, crop records from detections on the device (track_geometry.h)
            # fp16 instantiations of the three hand-scheduled kernel families (bodies shared through conv3x3_lds.inc / conv_s2.inc /
            # bottleneck_chain.inc): translation units of their own, so that each bf16 file still compiles to exactly its kernel set
            "conv3x3_lds_f16.hip", "conv_s2_f16.hip", "bottleneck_chain_f16.hip"]
@@ -227,6 +228,15 @@ SYMBOLS = {
     "hrn_yuv_from_bgr": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
     "hrn_crop_geometry": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
     "hrn_crop_geometry_last_error": (ctypes.c_char_p, []),
+    "hrn_pose_boxes": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_double,
+                                      ctypes.c_double, _P]),
+    "hrn_pose_boxes_last_error": (ctypes.c_char_p, []),
+    "hrn_boxes_from_poses": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                            ctypes.c_double, ctypes.c_double, _P, _P]),
+    "hrn_preprocess_frames_dev": (ctypes.c_int, [_P, ctypes.POINTER(Frame), ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int,
+                                                 _P, _P, _P, _P]),
+    "hrn_preprocess_frames_yuv_dev": (ctypes.c_int, [_P, ctypes.POINTER(YuvFrameC), ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int,
+                                                     ctypes.c_int, _P, _P, _P, _P]),
     "hrn_forward_flip_tta": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
     "hrn_forward_refined": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
     "hrn_refine_coords": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),

@@ -542,6 +542,10 @@
             draw_table = draw_records = nullptr, draw_table_bytes = draw_records_bytes = 0;
             if (draw_done) (void)hipEventDestroy(draw_done);
             draw_done = nullptr;
+            if (trk_table) (void)hipFree(trk_table);
+            trk_table = nullptr, trk_table_bytes = 0;
+            if (trk_done) (void)hipEventDestroy(trk_done);
+            trk_done = nullptr;
             if (warp_params) (void)hipFree(warp_params);
             warp_params = nullptr, warp_params_cap = 0;
             if (warp_done) (void)hipEventDestroy(warp_done);

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "track_geometry.h"
 
 namespace {
 #include "ctx_types.h"
@@ -250,6 +251,56 @@ struct hrn_ctx {
     size_t draw_table_bytes = 0, draw_records_bytes = 0;
     hipEvent_t draw_done = nullptr;
     hipStream_t draw_stream = nullptr;
+    // the tracking link (hrn_boxes_from_poses, hrn_preprocess_frames_dev): the call's host table on the device (frame sizes per
+    // person; frame table and frame index), grown on demand and guarded like warp_params against a call on another stream
+    char *trk_table = nullptr;
+    size_t trk_table_bytes = 0;
+    hipEvent_t trk_done = nullptr;
+    hipStream_t trk_stream = nullptr;
+    // `bytes` from image `ring` of the pinned staging ring to trk_table; trk_ran() goes behind the launch that reads it
+    bool trk_upload(const char *pinned, unsigned ring, size_t bytes, hipStream_t s) {
+        if (bytes > trk_table_bytes) {
+            if (trk_done && !hip_ok(hipEventSynchronize(trk_done), "hipEventSynchronize")) return false;
+            if (trk_table) (void)hipFree(trk_table);
+            trk_table = nullptr, trk_table_bytes = 0;
+            const size_t cap = std::max<size_t>(bytes * 2, 4096);
+            if (!hip_ok(hipMalloc((void **)&trk_table, cap), "hipMalloc(tracking table)")) return false;
+            trk_table_bytes = cap;
+        }
+        if (trk_done && trk_stream != s && !hip_ok(hipStreamWaitEvent(s, trk_done, 0), "hipStreamWaitEvent")) return false;
+        if (!hip_ok(hipMemcpyAsync(trk_table, pinned, bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync(tracking table)")) return false;
+        return hip_ok(hipEventRecord(pre_landed[ring], s), "hipEventRecord");
+    }
+    bool trk_ran(hipStream_t s) {
+        if (!trk_done && !hip_ok(hipEventCreateWithFlags(&trk_done, hipEventDisableTiming), "hipEventCreate")) return false;
+        trk_stream = s;
+        return hip_ok(hipEventRecord(trk_done, s), "hipEventRecord");
+    }
+    // the pre-path's device scratch for n people: `tmp_bytes` of intermediates, n records (and n YUV sources); growing waits for
+    // whoever still reads the old ones
+    bool pre_reserve(size_t tmp_bytes, int n, bool yuv, hipStream_t s) {
+        if (!(tmp_bytes > pre_tmp_bytes || n > pre_params_cap || (yuv && n > pre_yuv_cap))) return true;
+        if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return false;
+        if (tmp_bytes > pre_tmp_bytes) {
+            if (pre_tmp) (void)hipFree(pre_tmp);
+            pre_tmp = nullptr, pre_tmp_bytes = 0;
+            if (!hip_ok(hipMalloc((void **)&pre_tmp, tmp_bytes), "hipMalloc(pre-path scratch)")) return false;
+            pre_tmp_bytes = tmp_bytes;
+        }
+        if (n > pre_params_cap) {
+            if (pre_params) (void)hipFree(pre_params);
+            pre_params = nullptr, pre_params_cap = 0;
+            if (!hip_ok(hipMalloc((void **)&pre_params, (size_t)n * sizeof(CropParams)), "hipMalloc(crop params)")) return false;
+            pre_params_cap = n;
+        }
+        if (yuv && n > pre_yuv_cap) {
+            if (pre_yuv) (void)hipFree(pre_yuv);
+            pre_yuv = nullptr, pre_yuv_cap = 0;
+            if (!hip_ok(hipMalloc((void **)&pre_yuv, (size_t)n * sizeof(YuvSource)), "hipMalloc(YUV sources)")) return false;
+            pre_yuv_cap = n;
+        }
+        return true;
+    }
     uint64_t map_clock = 0;    // LRU stamp of the block-map slots
     int64_t map_builds = 0;     // block maps built + uploaded since creation (hrn_map_rebuilds)
     float *scratch_hm = nullptr;  // max_batch heat-maps of the handle's own: flip-TTA's mirrored pass, a refined decode the caller gave no maps
@@ -506,61 +557,16 @@ int hrn_refine_coords(hrn_handle h, const float *heatmaps_dev, int n, int refine
 }
 
 namespace {
-// SimpleHRNet.py:236-278 (PAD) / :383-412 (CLAMP) for ONE detection in a frame of frame_h x frame_w, network input H x W.
-// The box arithmetic is Python's, restated in double: round() is round-half-even on a float, `//` on non-negative ints is
-// C's `/`, int(round(x)) = nearbyint under the default rounding mode.  Fills the slice / pad numbers of `cp` (tmp_off and the
-// frame are the caller's) and the reported box; false + err when the reference would wrap around or divide by zero.
+// track_geometry.h's crop_geometry_one (the box arithmetic, one text for the host and the record kernel of track.hip) with the
+// host entries' refusals: false + err when the reference would wrap around or divide by zero
 bool crop_geometry_one(const float *d, int i, int frame_h, int frame_w, int H, int W, int variant, CropParams &cp, int32_t *box,
                        std::string &err) {
-    const long x1 = (long)std::nearbyint((double)d[0]), y1 = (long)std::nearbyint((double)d[1]);
-    const long x2 = (long)std::nearbyint((double)d[2]), y2 = (long)std::nearbyint((double)d[3]);
-    if (x2 <= x1 || y2 <= y1) {
-        err = "detection " + std::to_string(i) + " is degenerate";
-        return false;
-    }
-    const double cf = (double)H / (double)W * (double)(x2 - x1) / (double)(y2 - y1);
-    // The reference slices numpy arrays with these numbers: a negative start would wrap around.  The PAD variant
-    // slices with the rounded box itself; the CLAMP variant re-derives (and clamps to the frame) the side it
-    // enlarges, so only the OTHER side has to be inside the frame as given (SimpleHRNet.py:396-407).
-    const bool x_as_given = variant == HRN_CROP_PAD || !(cf < 1), y_as_given = variant == HRN_CROP_PAD || !(cf > 1);
-    if ((x_as_given && (x1 < 0 || x1 >= frame_w)) || (y_as_given && (y1 < 0 || y1 >= frame_h))) {
-        err = "detection " + std::to_string(i) + " starts outside the frame";
-        return false;
-    }
-    long x1n = x1, x2n = x2, y1n = y1, y2n = y2, pt = 0, pb = 0, pl = 0, pr = 0;
-    long sx1 = x1, sy1 = y1, sx2 = x2, sy2 = y2;  // what is sliced out of the frame
-    if (variant == HRN_CROP_CLAMP) {  // SimpleHRNet.py:396-407: enlarge, clamp to the frame, slice the enlarged box
-        if (cf > 1) {
-            const long center = y1 + (y2 - y1) / 2;
-            const long length = (long)std::nearbyint((double)(y2 - y1) * cf);
-            y1n = std::max<long>(0, center - length / 2), y2n = std::min<long>(frame_h, center + length / 2);
-        } else if (cf < 1) {
-            const long center = x1 + (x2 - x1) / 2;
-            const long length = (long)std::nearbyint((double)(x2 - x1) * 1 / cf);
-            x1n = std::max<long>(0, center - length / 2), x2n = std::min<long>(frame_w, center + length / 2);
-        }
-        sx1 = x1n, sy1 = y1n, sx2 = x2n, sy2 = y2n;
-        if (sx2 <= sx1 || sy2 <= sy1 || sx1 >= frame_w || sy1 >= frame_h) {
-            err = "detection " + std::to_string(i) + " is degenerate after clamping";
-            return false;
-        }
-    } else if (cf > 1) {  // increase y side
-        const long center = y1 + (y2 - y1) / 2;
-        const long length = (long)std::nearbyint((double)(y2 - y1) * cf);
-        y1n = center - length / 2, y2n = center + length / 2;
-        pt = std::labs(y1n - y1), pb = std::labs(y2n - y2);
-    } else if (cf < 1) {
-        const long center = x1 + (x2 - x1) / 2;
-        const long length = (long)std::nearbyint((double)(x2 - x1) * 1 / cf);
-        x1n = center - length / 2, x2n = center + length / 2;
-        pl = std::labs(x1n - x1), pr = std::labs(x2n - x2);
-    }
-    cp.x1 = (int)sx1, cp.y1 = (int)sy1;
-    cp.w_crop = (int)(std::min<long>(sx2, frame_w) - sx1), cp.h_crop = (int)(std::min<long>(sy2, frame_h) - sy1);  // numpy slicing
-    cp.pad_top = (int)pt, cp.pad_left = (int)pl;
-    cp.h_pad = cp.h_crop + (int)(pt + pb), cp.w_pad = cp.w_crop + (int)(pl + pr);
-    box[0] = (int32_t)x1n, box[1] = (int32_t)y1n, box[2] = (int32_t)x2n, box[3] = (int32_t)y2n;
-    return true;
+    long pad_hw[2];
+    const int status = hrn::crop_geometry_one(d, frame_h, frame_w, H, W, variant, cp, box, pad_hw);
+    if (status == CROP_OK) return true;
+    err = "detection " + std::to_string(i) +
+          (status == CROP_DEGENERATE ? " is degenerate" : status == CROP_OUTSIDE ? " starts outside the frame" : " is degenerate after clamping");
+    return false;
 }
 
 thread_local std::string g_geometry_error;
@@ -635,28 +641,7 @@ int preprocess_people(hrn_handle h, const hrn_frame *frames, const hrn_yuv_frame
         tmp_bytes += ((size_t)cp.h_pad * W * 3 + 255) / 256 * 256;
         if (cp.h_pad > max_h_pad) max_h_pad = cp.h_pad;
     }
-    // grow the scratch: wait for whoever still reads the old one
-    if (tmp_bytes > h->pre_tmp_bytes || n > h->pre_params_cap || (yframes && n > h->pre_yuv_cap)) {
-        if (!h->hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return 6;
-        if (tmp_bytes > h->pre_tmp_bytes) {
-            if (h->pre_tmp) (void)hipFree(h->pre_tmp);
-            h->pre_tmp = nullptr, h->pre_tmp_bytes = 0;
-            if (!h->hip_ok(hipMalloc((void **)&h->pre_tmp, tmp_bytes), "hipMalloc(pre-path scratch)")) return 6;
-            h->pre_tmp_bytes = tmp_bytes;
-        }
-        if (n > h->pre_params_cap) {
-            if (h->pre_params) (void)hipFree(h->pre_params);
-            h->pre_params = nullptr, h->pre_params_cap = 0;
-            if (!h->hip_ok(hipMalloc((void **)&h->pre_params, (size_t)n * sizeof(CropParams)), "hipMalloc(crop params)")) return 6;
-            h->pre_params_cap = n;
-        }
-        if (yframes && n > h->pre_yuv_cap) {
-            if (h->pre_yuv) (void)hipFree(h->pre_yuv);
-            h->pre_yuv = nullptr, h->pre_yuv_cap = 0;
-            if (!h->hip_ok(hipMalloc((void **)&h->pre_yuv, (size_t)n * sizeof(YuvSource)), "hipMalloc(YUV sources)")) return 6;
-            h->pre_yuv_cap = n;
-        }
-    }
+    if (!h->pre_reserve(tmp_bytes, n, yframes != nullptr, s)) return 6;
     if (yframes && !h->hip_ok(hipMemcpyAsync(h->pre_yuv, srcs, (size_t)n * sizeof(YuvSource), hipMemcpyHostToDevice, s),
                               "hipMemcpyAsync(YUV sources)"))
         return 6;
@@ -831,6 +816,204 @@ int hrn_preprocess_frames_yuv(hrn_handle h, const hrn_yuv_frame *frames_host, in
     if (n == 0) return 0;
     return preprocess_people(h, nullptr, frames_host, frame_index_host, dets_host, det_stride, n, variant, images_dev, boxes_host,
                              boxes_dev, (hipStream_t)stream);
+}
+
+// ---- the tracking link: boxes from joints, and the crop pre-path from detections on the device --------------------------------
+namespace {
+thread_local std::string g_pose_boxes_error;
+
+// what is wrong with the arguments of hrn_pose_boxes / hrn_boxes_from_poses, into `why` (false: nothing); needs no device
+bool pose_box_fault(const void *pts, int n, int J, const int32_t *frame_hw, int per_person_hw, int min_joints, double scale,
+                    double min_side, const void *dets, std::string &why) {
+    why.clear();
+    if (n < 0) why = "n is negative";
+    else if (J < 1 || J > HRN_MAX_JOINTS) why = "J must be in [1, " + std::to_string(HRN_MAX_JOINTS) + "]";
+    else if (min_joints < 1) why = "min_joints must be at least 1";
+    else if (!std::isfinite(scale) || !(scale > 0)) why = "scale must be finite and positive";
+    else if (!std::isfinite(min_side) || min_side < 0) why = "min_side must be finite and not negative";
+    else if (n > 0 && (!pts || !frame_hw || !dets)) why = "null joints / frame sizes / output";
+    for (int i = 0; why.empty() && i < (per_person_hw ? n : std::min(n, 1)); ++i)
+        if (frame_hw[2 * (size_t)i] <= 0 || frame_hw[2 * (size_t)i + 1] <= 0)
+            why = "the frame of person " + std::to_string(i) + " has a non-positive side";
+    return !why.empty();
+}
+
+// the one body of hrn_preprocess_frames_dev and hrn_preprocess_frames_yuv_dev, behind their argument checks
+int preprocess_people_dev(hrn_handle h, const hrn_frame *frames, const hrn_yuv_frame *yframes, int nframes, const int32_t *fidx,
+                          const float *dets_dev, int det_stride, int n, int variant, float *images_dev, int32_t *boxes_dev,
+                          int32_t *status_dev, hipStream_t s) {
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    const int H = h->H, W = h->W;
+    const auto entry = [&](int f) {
+        TrackFrame t{};
+        if (yframes) {
+            if (!yuv_frame_fault(yframes[f])) t.height = yframes[f].height, t.width = yframes[f].width, t.yuv = yuv_source(yframes[f]);
+        } else {
+            t.bgr = frames[f].data, t.height = frames[f].height, t.width = frames[f].width;
+        }
+        return t;
+    };
+    // the host sizes grid and scratch without knowing the boxes: every person gets the rows a box inside the largest frame
+    // referred to can need -- and at least H, the rows of the all-padding crop of a refused person
+    long rows = H;
+    for (int i = 0; i < n; ++i) {
+        const int f = fidx ? fidx[i] : 0;
+        const int frame_h = yframes ? yframes[f].height : frames[f].height, frame_w = yframes ? yframes[f].width : frames[f].width;
+        rows = std::max(rows, crop_hcap(frame_h, frame_w, H, W));
+    }
+    const size_t slot = ((size_t)rows * W * 3 + 255) / 256 * 256;
+    if (!h->pre_reserve((size_t)n * slot, n, yframes != nullptr, s)) return 6;
+    CropRecordArgs a{};
+    a.dets = dets_dev, a.det_stride = det_stride, a.n = n, a.H = H, a.W = W, a.variant = variant, a.yuv = yframes ? 1 : 0;
+    a.slot_bytes = (long long)slot;
+    a.crops = h->pre_params, a.srcs = h->pre_yuv, a.boxes = boxes_dev, a.status = status_dev;
+    if (fidx) {   // the table and everybody's entry of it, through the pinned ring
+        const size_t table_bytes = (size_t)nframes * sizeof(TrackFrame), need = table_bytes + (size_t)n * sizeof(int32_t);
+        unsigned ring = 0;
+        char *pin = h->pre_stage(need, &ring);
+        if (!pin) return 6;
+        std::vector<char> used((size_t)nframes, 0);
+        for (int i = 0; i < n; ++i) used[fidx[i]] = 1;
+        for (int f = 0; f < nframes; ++f) ((TrackFrame *)pin)[f] = used[f] ? entry(f) : TrackFrame{};
+        memcpy(pin + table_bytes, fidx, (size_t)n * sizeof(int32_t));
+        if (!h->trk_upload(pin, ring, need, s)) return 6;
+        a.frames = (const TrackFrame *)h->trk_table, a.frame_index = (const int *)(h->trk_table + table_bytes);
+    } else {
+        a.frame0 = entry(0);
+    }
+    if (!h->hip_ok(launch_crop_records(a, s), "crop records launch")) return 8;
+    if (fidx && !h->trk_ran(s)) return 6;
+    const hipError_t e = yframes ? launch_prepath_yuv(h->pre_params, h->pre_yuv, n, (int)rows, h->pre_tmp, images_dev, H, W, s)
+                                 : launch_prepath(h->pre_params, n, (int)rows, h->pre_tmp, images_dev, H, W, s);
+    if (!h->hip_ok(e, "pre-path launch")) return 8;
+    return 0;
+}
+}  // namespace
+
+int hrn_pose_boxes(const float *pts, int n, int J, const int32_t *frame_hw, int per_person_hw, float threshold, int min_joints,
+                   double scale, double min_side, float *dets_out) {
+    if (pose_box_fault(pts, n, J, frame_hw, per_person_hw, min_joints, scale, min_side, dets_out, g_pose_boxes_error)) return 7;
+    for (int i = 0; i < n; ++i) {
+        const int32_t *hw = frame_hw + (per_person_hw ? (size_t)i * 2 : 0);
+        pose_box_one(pts + (size_t)i * J * 3, J, hw[0], hw[1], threshold, min_joints, scale, min_side, dets_out + (size_t)i * 5);
+    }
+    return 0;
+}
+
+const char *hrn_pose_boxes_last_error(void) { return g_pose_boxes_error.c_str(); }
+
+int hrn_boxes_from_poses(hrn_handle h, const float *pts_dev, int n, int J, const int32_t *frame_hw_host, int per_person_hw,
+                         float threshold, int min_joints, double scale, double min_side, float *dets_dev, void *stream) {
+    if (!h) return 1;
+    std::string fault;
+    if (pose_box_fault(pts_dev, n, J, frame_hw_host, per_person_hw, min_joints, scale, min_side, dets_dev, fault)) {
+        h->err = "hrn_boxes_from_poses: " + fault;
+        return 7;
+    }
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (n == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    PoseBoxArgs a{};
+    a.pts = pts_dev, a.n = n, a.J = J, a.threshold = threshold, a.min_joints = min_joints, a.scale = scale, a.min_side = min_side;
+    a.dets = dets_dev;
+    if (per_person_hw) {   // a frame size per person: through the pinned ring
+        const size_t need = (size_t)n * 2 * sizeof(int32_t);
+        unsigned ring = 0;
+        char *pin = h->pre_stage(need, &ring);
+        if (!pin) return 6;
+        memcpy(pin, frame_hw_host, need);
+        if (!h->trk_upload(pin, ring, need, s)) return 6;
+        a.frame_hw = (const int *)h->trk_table;
+    } else {
+        a.frame_h = frame_hw_host[0], a.frame_w = frame_hw_host[1];
+    }
+    if (!h->hip_ok(launch_pose_boxes(a, s), "pose boxes launch")) return 8;
+    if (per_person_hw && !h->trk_ran(s)) return 6;
+    return 0;
+}
+
+// hrn_preprocess_frames with the detections on the device: its argument checks and texts (minus the per-detection ones, which
+// become status_dev), then the handle
+int hrn_preprocess_frames_dev(hrn_handle h, const hrn_frame *frames_host, int nframes, const float *dets_dev, int det_stride,
+                              const int32_t *frame_index_host, int n, int variant, float *images_dev, int32_t *boxes_dev,
+                              int32_t *status_dev, void *stream) {
+    if (!h) return 1;
+    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
+        h->err = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
+        return 7;
+    }
+    if (n < 0 || nframes < 0 || det_stride < 4 ||
+        (n > 0 && (nframes < 1 || !frames_host || !dets_dev || !images_dev || !boxes_dev || !status_dev))) {
+        h->err = "bad frames / detections / n";
+        return 7;
+    }
+    if (n > 0 && !frame_index_host && nframes != 1) {
+        h->err = "hrn_preprocess_frames_dev: without frame_index there must be one frame";
+        return 7;
+    }
+    for (int i = 0; i < n; ++i) {
+        const long f = frame_index_host ? (long)frame_index_host[i] : 0;
+        if (f < 0 || f >= nframes) {
+            h->err = "hrn_preprocess_frames_dev: frame_index " + std::to_string(f) + " of person " + std::to_string(i) + " is outside [0, " +
+                     std::to_string(nframes) + ")";
+            return 7;
+        }
+        if (!frames_host[f].data || frames_host[f].height <= 0 || frames_host[f].width <= 0) {
+            h->err = "hrn_preprocess_frames_dev: frame " + std::to_string(f) + ", which person " + std::to_string(i) +
+                     " is cut from, is null or has no size";
+            return 7;
+        }
+    }
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (n == 0) return 0;
+    return preprocess_people_dev(h, frames_host, nullptr, nframes, frame_index_host, dets_dev, det_stride, n, variant, images_dev,
+                                 boxes_dev, status_dev, (hipStream_t)stream);
+}
+
+int hrn_preprocess_frames_yuv_dev(hrn_handle h, const hrn_yuv_frame *frames_host, int nframes, const float *dets_dev, int det_stride,
+                                  const int32_t *frame_index_host, int n, int variant, float *images_dev, int32_t *boxes_dev,
+                                  int32_t *status_dev, void *stream) {
+    if (!h) return 1;
+    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
+        h->err = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
+        return 7;
+    }
+    if (n < 0 || nframes < 0 || det_stride < 4 ||
+        (n > 0 && (nframes < 1 || !frames_host || !dets_dev || !images_dev || !boxes_dev || !status_dev))) {
+        h->err = "bad frames / detections / n";
+        return 7;
+    }
+    if (n > 0 && !frame_index_host && nframes != 1) {
+        h->err = "hrn_preprocess_frames_yuv_dev: without frame_index there must be one frame";
+        return 7;
+    }
+    for (int i = 0; i < n; ++i) {
+        const long f = frame_index_host ? (long)frame_index_host[i] : 0;
+        if (f < 0 || f >= nframes) {
+            h->err = "hrn_preprocess_frames_yuv_dev: frame_index " + std::to_string(f) + " of person " + std::to_string(i) +
+                     " is outside [0, " + std::to_string(nframes) + ")";
+            return 7;
+        }
+        if (const char *fault = yuv_frame_fault(frames_host[f])) {
+            h->err = "hrn_preprocess_frames_yuv_dev: frame " + std::to_string(f) + ", which person " + std::to_string(i) +
+                     " is cut from, " + fault;
+            return 7;
+        }
+    }
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (n == 0) return 0;
+    return preprocess_people_dev(h, nullptr, frames_host, nframes, frame_index_host, dets_dev, det_stride, n, variant, images_dev,
+                                 boxes_dev, status_dev, (hipStream_t)stream);
 }
 
 int hrn_yuv_from_bgr(int matrix, int range, const uint8_t *bgr, int n, uint8_t *yuv_out) {

@@ -363,6 +363,38 @@ struct DrawArgs {
 };
 hipError_t launch_draw(const DrawArgs &a, hipStream_t s);   // draw_build_kernel, then draw_raster_kernel
 
+// The tracking link (track.hip; include/hrnet_mi355.h: hrn_boxes_from_poses, hrn_preprocess_frames_dev): boxes from the joints
+// where the decode left them, and the crop records of the pre-path from detections on the device -- one launch each.
+struct PoseBoxArgs {
+    const float *pts;              // (n, J, 3) (y, x, confidence), device
+    int n, J;
+    const int *frame_hw;           // per person: (n, 2) (height, width), device; nullptr: frame_h / frame_w for everybody
+    int frame_h, frame_w;
+    float threshold;
+    int min_joints;
+    double scale, min_side;
+    float *dets;                   // out: (n, 5) (x1, y1, x2, y2, score)
+};
+hipError_t launch_pose_boxes(const PoseBoxArgs &a, hipStream_t s);   // pose_boxes_kernel: one wave per person
+struct TrackFrame {                // one frame of the call's table
+    const unsigned char *bgr;      // BGR frames: the pixels; YUV frames: nullptr
+    int height, width;
+    YuvSource yuv;                 // YUV frames: planes, pitches and coefficients
+};
+struct CropRecordArgs {
+    const float *dets;             // (n, det_stride) float32, device
+    int det_stride, n, H, W, variant, yuv;
+    TrackFrame frame0;             // frame_index == nullptr: everybody's frame, in the kernel arguments (nothing is uploaded)
+    const TrackFrame *frames;      // else the table and each person's entry of it, device
+    const int *frame_index;
+    long long slot_bytes;          // person i's intermediate lies at i * slot_bytes
+    CropParams *crops;             // out: the records launch_prepath(_yuv) reads
+    YuvSource *srcs;               // out (yuv != 0)
+    int *boxes;                    // out: (n, 4)
+    int *status;                   // out: n
+};
+hipError_t launch_crop_records(const CropRecordArgs &a, hipStream_t s);   // crop_records_kernel: one thread per person
+
 struct TapArgs {           // debug tap: crops crop0, crop0 + crop_step, ... of a flat padded tensor -> (ncrops, c, h, w) fp32
     const void *in;
     float *dst;

@@ -953,6 +953,114 @@ class NativeHRNet:
             return boxes, out[1], out[0]
         return boxes, out
 
+    # -- the tracking link: between two detector runs the next frame's crops are cut from the previous frame's joints ------------
+    def boxes_from_poses(self, pts, frame_hw, threshold: float = 0.5, min_joints: int = 3, scale: float = 1.25,
+                         min_side: float = 0.0) -> torch.Tensor:
+        """``postproc.pose_boxes`` on the GPU (``hrn_boxes_from_poses``: one launch, one wave per person, no synchronisation):
+        ``pts`` (n, J, 3) float32 ``(y, x, confidence)`` where the decode left them (any J up to 256; a host array is uploaded),
+        ``frame_hw`` = (height, width) for everybody or (n, 2), on the host.  Returns (n, 5) float32 detection rows
+        ``(x1, y1, x2, y2, score)`` on the GPU, bit for bit ``pose_boxes``'s; five zeros where fewer than ``min_joints`` joints
+        have ``confidence > threshold``."""
+        from .postproc import _frame_sizes
+
+        if not isinstance(pts, torch.Tensor):
+            pts = torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float32))
+        if pts.dim() != 3 or pts.shape[2] != 3:
+            raise ValueError("pts must be (n, J, 3), got %s" % (tuple(pts.shape),))
+        pts = pts.to(self.torch_device, dtype=torch.float32, non_blocking=True).contiguous()
+        n, J = int(pts.shape[0]), int(pts.shape[1])
+        hw, per_person = _frame_sizes(frame_hw, n)
+        dets = torch.empty((n, 5), dtype=torch.float32, device=self.torch_device)
+        with torch.cuda.device(self.device_index):
+            rc = self._lib.hrn_boxes_from_poses(self._h, pts.data_ptr(), n, J, hw.ctypes.data, per_person, ctypes.c_float(threshold),
+                                                int(min_joints), ctypes.c_double(scale), ctypes.c_double(min_side), dets.data_ptr(),
+                                                self._stream())
+        self._check(rc, "hrn_boxes_from_poses")
+        return dets
+
+    def _tracked_frames(self, frames, frame_index, n: int):
+        """``frames`` / ``frame_index`` of ``preprocess_frames_dev`` / ``track_frame`` as (device frames, int32 index or None)"""
+        single = isinstance(frames, YuvFrame) or (isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3)
+        frames = self._device_frames([frames] if single else frames)
+        if frame_index is None:
+            if len(frames) != 1:
+                raise ValueError("%d frames need a frame_index (one entry per person)" % len(frames))
+            return frames, None
+        index = np.ascontiguousarray(np.asarray(frame_index.cpu() if isinstance(frame_index, torch.Tensor) else frame_index,
+                                                dtype=np.int32).reshape(-1))
+        if len(index) != n:
+            raise ValueError("frame_index has %d entries for %d people" % (len(index), n))
+        if len(index) and (index.min() < 0 or index.max() >= len(frames)):
+            raise ValueError("frame_index must lie in [0, %d)" % len(frames))
+        if any(frames[f] is None for f in set(index.tolist())):
+            raise ValueError("a frame somebody is cut from is None")
+        return frames, index
+
+    def _preprocess_dev(self, frames, dets_dev: torch.Tensor, index, variant: str):
+        """``hrn_preprocess_frames_dev`` / ``_yuv_dev`` over device frames (a list ``_tracked_frames`` made)"""
+        if variant not in ("pad", "clamp"):
+            raise ValueError("variant must be 'pad' or 'clamp'")
+        if dets_dev.dim() != 2 or dets_dev.shape[1] < 4:
+            raise ValueError("detections must be (P, >=4)")
+        dets_dev = dets_dev.to(self.torch_device, dtype=torch.float32, non_blocking=True).contiguous()
+        n = int(dets_dev.shape[0])
+        table = self._frame_table(frames)
+        yuv = table._type_ is _lib.YuvFrameC
+        entry, name = (self._lib.hrn_preprocess_frames_yuv_dev, "hrn_preprocess_frames_yuv_dev") if yuv else \
+            (self._lib.hrn_preprocess_frames_dev, "hrn_preprocess_frames_dev")
+        h, w = self.resolution
+        dev = self.torch_device
+        images = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+        boxes_dev = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        status_dev = torch.empty((n,), dtype=torch.int32, device=dev)
+        if n:
+            with torch.cuda.device(self.device_index):
+                rc = entry(self._h, table, len(frames), dets_dev.data_ptr(), int(dets_dev.shape[1]),
+                           None if index is None else index.ctypes.data, n, 0 if variant == "pad" else 1, images.data_ptr(),
+                           boxes_dev.data_ptr(), status_dev.data_ptr(), self._stream())
+            self._check(rc, name)
+        return images, boxes_dev, status_dev
+
+    def preprocess_frames_dev(self, frames, dets_dev, frame_index=None, variant: str = "pad"):
+        """The crop pre-path with the detections ON THE GPU (``hrn_preprocess_frames_dev``): ``preprocess_frames`` without a host
+        read of the boxes, for detections a kernel made -- ``boxes_from_poses``, or a detector that leaves its rows on the device.
+
+        ``frames``: one frame ((Hf, Wf, 3) uint8 BGR or a ``YuvFrame``), or a stack / sequence of frames as in
+        ``preprocess_frames`` together with ``frame_index`` (one frame number per person, on the host: who belongs to which
+        frame is known without reading the device); ``dets_dev``: (P, >=4) float32, columns 0..3 = x1, y1, x2, y2 (a host array is
+        uploaded).  Returns ``(images (P, 3, H, W) float32, boxes (P, 4) int32, status (P,) int32)``, all on the GPU, nothing
+        synchronised.  ``status`` 0: images and boxes are ``preprocess_frames``'s, bit for bit.  Otherwise the person's box is
+        zero and its crop all padding (1 degenerate, 2 starts outside the frame, 3 degenerate after clamping, 4 padded crop too
+        tall for the scratch, 5 a coordinate not finite or beyond 2^30: include/hrnet_mi355.h).  The scratch is sized for the
+        tallest crop a box inside the frame can need: about 2.2 MB per person at 1080p / 384x288, kept by the engine."""
+        if not isinstance(dets_dev, torch.Tensor):
+            dets_dev = torch.from_numpy(np.ascontiguousarray(dets_dev, dtype=np.float32))
+        frames, index = self._tracked_frames(frames, frame_index, int(dets_dev.shape[0]))
+        return self._preprocess_dev(frames, dets_dev, index, variant)
+
+    def track_frame(self, frame, prev_pts, frame_index=None, variant: str = "pad", refine: Optional[str] = None,
+                    return_heatmaps: bool = False, **box_args):
+        """One frame of a video loop WITHOUT the detector: the people are cut from ``frame`` where their joints were in the
+        previous frame -- ``boxes_from_poses(prev_pts)`` -> ``preprocess_frames_dev`` -> ``predict_crops``, device tensors in and
+        out, stream-ordered, no synchronisation.  ``prev_pts``: (P, J, 3) as ``predict_frame`` / ``track_frame`` returned them;
+        ``box_args``: ``threshold``, ``min_joints``, ``scale``, ``min_side`` of ``boxes_from_poses``.  Given a list of frames plus
+        ``frame_index`` it is the clip form: the people of many streams in one call.
+        Returns ``(boxes (P, 4) int32, pts (P, J, 3), status (P,) int32[, heatmaps])`` on the GPU.  A person whose ``status`` is
+        not 0 (too few live joints, or all of them on one side of the frame) went through the pass as an all-padding crop: its
+        ``pts`` mean nothing -- drop it, or run the detector again.  Equal, bit for bit, to downloading ``prev_pts``,
+        ``postproc.pose_boxes`` and ``predict_frame`` with those host detections."""
+        refine_code(refine)
+        n = int(prev_pts.shape[0])
+        frames, index = self._tracked_frames(frame, frame_index, n)
+        sizes = np.asarray([(0, 0) if f is None else ((f.height, f.width) if isinstance(f, YuvFrame) else tuple(f.shape[:2]))
+                            for f in frames], np.int32)
+        dets = self.boxes_from_poses(prev_pts, sizes[0] if index is None else sizes[index].reshape(n, 2), **box_args)
+        images, boxes_dev, status_dev = self._preprocess_dev(frames, dets, index, variant)
+        out = self.predict_crops(images, boxes_dev, return_heatmaps=return_heatmaps, refine=refine)
+        if return_heatmaps:
+            return boxes_dev, out[1], status_dev, out[0]
+        return boxes_dev, out, status_dev
+
     # -- clip mode: the people of many frames in one pre-path launch and one pass (throughput, not latency) ------------------
     def _device_frames(self, frames) -> List[Optional[torch.Tensor]]:
         """``frames`` of ``preprocess_frames`` as a list of contiguous (Hf, Wf, 3) uint8 tensors on the engine's GPU; a 4-D stack

@@ -288,3 +288,39 @@ def target_centers(joints, visibility, resolution, sigma=2, joints_weight=None):
     if rc != 0:
         raise ValueError(lib.hrn_last_error(None).decode())
     return mu, draw, tw
+
+
+def _frame_sizes(frame_hw, n: int):
+    """``frame_hw`` of ``pose_boxes`` / ``NativeHRNet.boxes_from_poses`` as a contiguous int32 array and its per-person flag: one
+    (height, width) for everybody, or (n, 2)"""
+    hw = np.ascontiguousarray(np.asarray(frame_hw, dtype=np.int32))
+    if hw.shape == (2,):
+        hw = hw.reshape(1, 2)
+    if hw.ndim != 2 or hw.shape[1] != 2 or len(hw) not in (1, n):
+        raise ValueError("frame_hw must be (height, width) or (n, 2), got %s for %d people" % (hw.shape, n))
+    return hw, int(len(hw) == n and n > 1)
+
+
+def pose_boxes(pts, frame_hw, threshold: float = 0.5, min_joints: int = 3, scale: float = 1.25, min_side: float = 0.0) -> np.ndarray:
+    """A detection-shaped box around each person's joints, on the host (``hrn_pose_boxes``, no GPU): what a tracker cuts the next
+    frame's crop from between two detector runs.  ``pts`` (n, J, 3) float32 ``(y, x, confidence)``; ``frame_hw`` = (height, width)
+    for everybody or (n, 2).  Returns (n, 5) float32 rows ``(x1, y1, x2, y2, score)``: the extent of the joints with
+    ``confidence > threshold`` grown by ``scale`` about its centre, at least ``min_side`` long, cut to the frame; ``score`` is their
+    mean confidence; five zeros where fewer than ``min_joints`` are live (include/hrnet_mi355.h has the definition, to the bit;
+    ``NativeHRNet.boxes_from_poses`` is the same on the GPU)."""
+    import ctypes
+
+    from . import _lib
+
+    p = np.ascontiguousarray(np.asarray(pts, dtype=np.float32))
+    if p.ndim != 3 or p.shape[2] != 3:
+        raise ValueError("pts must be (n, J, 3), got %s" % (p.shape,))
+    n, J = p.shape[:2]
+    hw, per_person = _frame_sizes(frame_hw, n)
+    out = np.empty((n, 5), np.float32)
+    lib = _lib.load()
+    rc = lib.hrn_pose_boxes(p.ctypes.data, n, J, hw.ctypes.data, per_person, ctypes.c_float(threshold), int(min_joints),
+                            ctypes.c_double(scale), ctypes.c_double(min_side), out.ctypes.data)
+    if rc != 0:
+        raise ValueError("hrn_pose_boxes: " + lib.hrn_pose_boxes_last_error().decode())
+    return out

@@ -17,6 +17,11 @@ different, and why:
 * ``refine`` (opt-in, default None = the reference's integer arg-max): ``"quarter"`` moves every joint a quarter heat-map cell
   towards the higher neighbour (the reference's ``get_final_preds`` step), ``"dark"`` decodes it to sub-cell precision with
   DARK (``include/hrnet_mi355.h``: ``HRN_REFINE_*``); every ``predict()`` path applies it;
+* ``redetect_every`` (opt-in, default 1 = the detector runs on every call, as in the reference): with K > 1 the single-image
+  multi-person path runs the detector on every K-th ``predict()`` call only -- and on a call that follows one that returned
+  nobody -- and otherwise cuts the people from the new frame where their joints were in the previous one
+  (``NativeHRNet.track_frame``, on the GPU; ``track_args`` = its ``threshold`` / ``min_joints`` / ``scale`` / ``min_side``).  People
+  who cannot be followed (too few confident joints, or all of them beyond the frame) are dropped from the returned arrays;
 * devices: ``'cuda:N'`` is that GPU.  ``'cuda'`` (all GPUs) and ``'cuda:1,2'`` (the listed ones) are, in a plain Python
   process, ONE engine per listed GPU driven from this process (``native.MultiDeviceHRNet``: the crop batch of a
   ``predict()`` call is split by index range, one host thread per GPU) -- what ``DataParallel`` gives the reference with
@@ -133,9 +138,13 @@ class SimpleHRNet:
     def __init__(self, c, nof_joints, checkpoint_path, model_name="HRNet", resolution=(384, 288), interpolation=None,
                  multiperson=True, return_heatmaps=False, return_bounding_boxes=False, max_batch_size=32,
                  yolo_version="v3", yolo_model_def=None, yolo_class_path=None, yolo_weights_path=None, device=None,
-                 enable_tensorrt=False, *, detector=None, dtype="fp32", refine=None):
+                 enable_tensorrt=False, *, detector=None, dtype="fp32", refine=None, redetect_every=1, track_args=None):
         refine_code(refine)   # (raises ValueError before any engine is built)
         self.refine = refine
+        if int(redetect_every) != redetect_every or redetect_every < 1:
+            raise ValueError("redetect_every must be a positive integer, got %r" % (redetect_every,))
+        self.redetect_every, self.track_args = int(redetect_every), dict(track_args or {})
+        self._calls, self._last_pts = 0, None   # single-image multi-person calls so far; the joints the next call tracks from
         self.c, self.nof_joints, self.checkpoint_path = c, nof_joints, checkpoint_path
         self.model_name, self.resolution = model_name, tuple(resolution)
         self.interpolation = 2 if interpolation is None else int(interpolation)   # cv2.INTER_CUBIC (SimpleHRNet.py:27)
@@ -148,6 +157,8 @@ class SimpleHRNet:
         if enable_tensorrt:
             raise ValueError("TensorRT is an NVIDIA engine; this class IS the native engine on MI355X")
         self.devices = resolve_devices(device)
+        if self.redetect_every > 1 and len(self.devices) > 1:
+            raise ValueError("redetect_every > 1 runs on one GPU (tracking is not sharded over devices)")
         self.device = torch.device("cuda", self.devices[0])      # where results are gathered / single-GPU work runs
         if multiperson and detector is None:
             raise ValueError("multiperson=True needs detector= (the reference's YOLO wrappers are un-vendored third-party code)")
@@ -205,15 +216,42 @@ class SimpleHRNet:
             boxes = np.asarray([[0, 0, image.shape[1], image.shape[0]]], dtype=np.float32)
             hm, pts = self.model.predict_crops(images, boxes, return_heatmaps=True, **self._refine_kw())
             return self._result(hm.cpu().numpy(), boxes, pts.cpu().numpy())
+        if self.redetect_every > 1:
+            return self._one_frame_tracked(image)
         found = self.detector.predict_single(image)
         if found is None or len(found) == 0:
-            return self._result(np.zeros(self._hm_shape(0), np.float32), np.empty((0, 4), np.int32),
-                                np.empty((0, 0, 3), dtype=np.float32))             # :331
+            return self._nobody()
         dets = np.asarray(found.cpu() if isinstance(found, torch.Tensor) else found, np.float32)[:, :4]
         out = self.model.predict_frame(image, dets, return_heatmaps=self.return_heatmaps, **self._refine_kw())
         boxes, pts = out[0], out[1].cpu().numpy()
         hm = out[2].cpu().numpy() if self.return_heatmaps else None
         return self._result(hm, boxes, pts)
+
+    def _nobody(self):                                                              # :331
+        return self._result(np.zeros(self._hm_shape(0), np.float32), np.empty((0, 4), np.int32), np.empty((0, 0, 3), dtype=np.float32))
+
+    def _one_frame_tracked(self, image):
+        """``redetect_every`` = K > 1: the detector on calls 0, K, 2K, ... and after a call that returned nobody; every other call
+        follows the previous call's people on the GPU.  The joints stay on the device between calls; what is downloaded is what
+        the contract returns."""
+        call, self._calls = self._calls, self._calls + 1
+        if call % self.redetect_every == 0 or self._last_pts is None:
+            self._last_pts = None
+            found = self.detector.predict_single(image)
+            if found is None or len(found) == 0:
+                return self._nobody()
+            dets = np.asarray(found.cpu() if isinstance(found, torch.Tensor) else found, np.float32)[:, :4]
+            out = self.model.predict_frame(image, dets, return_heatmaps=self.return_heatmaps, **self._refine_kw())
+            self._last_pts = out[1]
+            return self._result(out[2].cpu().numpy() if self.return_heatmaps else None, out[0], out[1].cpu().numpy())
+        out = self.model.track_frame(image, self._last_pts, return_heatmaps=self.return_heatmaps, **self._refine_kw(), **self.track_args)
+        alive = out[2] == 0                                  # people who could not be followed are dropped
+        self._last_pts = out[1][alive]
+        boxes, pts = out[0][alive].cpu().numpy(), self._last_pts.cpu().numpy()
+        if len(pts) == 0:
+            self._last_pts = None
+            return self._nobody()
+        return self._result(out[3][alive].cpu().numpy() if self.return_heatmaps else None, boxes, pts)
 
     # ------------------------------------------------------------------------------------------ SimpleHRNet.py:345-496
     def _frame_stack(self, images):
