@@ -285,6 +285,51 @@ int hrn_preprocess_frames_yuv_dev(hrn_handle h, const hrn_yuv_frame *frames_host
                                   int det_stride, const int32_t *frame_index_host, int n, int variant, float *images_dev,
                                   int32_t *boxes_dev, int32_t *status_dev, void *stream);
 
+/* ---- person ids between two frames: association, smoothing and numbering, on the host and on the device ----
+ * What the demo loop does after every frame (scripts/live-demo.py:114-130): find_person_id_associations (misc/utils.py:387-429)
+ * decides who of the previous frame is who of this one, carries the ids over, smooths matched boxes and joints and numbers the new
+ * people; then next_id = max(next_id, max(ids) + 1).  Both entries solve P independent problems (one video: P = 1; the streams of
+ * a camera wall: one problem each): problem p has the current people [cur_start[p], cur_start[p + 1]) and the previous people
+ * [prev_start[p], prev_start[p + 1]) of the arrays below.  The arithmetic is csrc/assoc_math.h's, one text for both entries
+ * (its header states every expression and its rounding): box IoU and OKS as hrn_pose_similarity computes them, except that exp is
+ * the header's own (at most 1 ulp from libm's on [-29, 0], measured; host and device agree to the bit); the float32 blend
+ * sim_pose * f32(pose_alpha) + sim_box * f32(1 - pose_alpha); cost (double)(1.0f - sim); hrn_assignment's matching (ties go to the
+ * lowest column); a matched pair is ACCEPTED iff sim > f32(similarity_threshold); an accepted person takes the previous id and,
+ * when smoothing_alpha != 0, joints f32(1 - a) * now + f32(a) * before (float32, all three components) and box
+ * (1 - a) * now + a * before in fp64 truncated towards zero; everybody whose id is then -1 is numbered in index order from
+ * next_id[p].  A NON-FINITE blended similarity (two zero boxes: IoU 0 / 0) counts as 0 in the cost and is never accepted.
+ *   cur_start, prev_start  P + 1 int32 each, non-decreasing, on the HOST in both entries (counts are shapes: known without a read)
+ *   boxes      (n, 4) int32 (x1, y1, x2, y2), in / out        pts       (n, J, 3) float32 (y, x, confidence), in / out
+ *   prev_boxes, prev_pts, prev_ids (int32)                    the previous frame; must not overlap the current arrays
+ *   next_id    P int32, in / out (a problem with nobody in the current frame leaves it)
+ *   pose_alpha, similarity_threshold  finite;  smoothing_alpha in [0, 1]
+ *   ids        n int32 out;   match  n int32 out: the accepted previous person, counted from prev_start[p], or -1
+ *   status     P int32 out: 0 clean; bit 0: a non-finite similarity was replaced; bit 1: the assignment found no path (nobody
+ *              matched; cannot happen while every cost is finite)
+ * At most HRN_MAX_TRACKED people on either side of one problem and J in [1, HRN_MAX_JOINTS]: more is code 7, like every other
+ * argument error (null tables, a decreasing segment table, parameters out of range), judged before anything is written;
+ * hrn_associate_people_last_error() (per thread) / hrn_last_error(h) names it.
+ * hrn_associate_people is the host form: no handle, no GPU.  hrn_associate_people_dev has every array except the two segment
+ * tables in device memory: ONE launch, one 256-thread block per problem (similarities by all threads, the assignment by one wave,
+ * ids and smoothing by the block), stream-ordered, no host read; its results equal the host form's bit for bit.  It keeps
+ * 12 * n * m bytes of scratch per problem in the handle (at most 768 KiB), grown on demand.  For P > 1 the problem table goes
+ * through one upload; P == 1 uploads nothing.  P == 0 launches nothing.
+ * hrn_assoc_exp (no GPU): the header's exp of n doubles, for measuring it.  hrn_associate_similarity (no GPU): the (n, m) costs
+ * (double) and blended similarities (float32, NaN where the blend was not finite) of one problem exactly as both entries compute
+ * them, for measuring them against the reference's matrices; 0, or 7 on null tables or sizes out of range. */
+#define HRN_MAX_TRACKED 256
+int hrn_associate_people(int P, const int32_t *cur_start, const int32_t *prev_start, int J, int32_t *boxes, float *pts,
+                         const int32_t *prev_boxes, const float *prev_pts, const int32_t *prev_ids, int32_t *next_id, double pose_alpha,
+                         double similarity_threshold, double smoothing_alpha, int32_t *ids, int32_t *match, int32_t *status);
+const char *hrn_associate_people_last_error(void);
+int hrn_associate_people_dev(hrn_handle h, int P, const int32_t *cur_start_host, const int32_t *prev_start_host, int J,
+                             int32_t *boxes_dev, float *pts_dev, const int32_t *prev_boxes_dev, const float *prev_pts_dev,
+                             const int32_t *prev_ids_dev, int32_t *next_id_dev, double pose_alpha, double similarity_threshold,
+                             double smoothing_alpha, int32_t *ids_dev, int32_t *match_dev, int32_t *status_dev, void *stream);
+int hrn_assoc_exp(const double *x, int n, double *out);
+int hrn_associate_similarity(const int32_t *boxes, const float *pts, int n, const int32_t *prev_boxes, const float *prev_pts, int m, int J,
+                             double pose_alpha, double *cost_out /* (n,m) */, float *sim_out /* (n,m) */);
+
 /* ---- pose overlays on the GPU: the joints and bones of every person, drawn into frames that stay on the device ----
  * Replaces, for every frame of the two demo programs (scripts/live-demo.py:135-138, scripts/extract-keypoints.py's sibling loop),
  *   for i, pt in enumerate(pts): frame = draw_points_and_skeleton(frame, pt, skeleton, person_index=i, ...)
@@ -345,6 +390,14 @@ int hrn_draw_poses(hrn_handle h, const hrn_canvas *canvases_host, int nframes, c
                    const uint8_t *point_colors_host, int Cp, const uint8_t *bone_colors_host, int Cb,
                    const int32_t *person_index_host /* n entries or NULL */, int radius /* 0: the reference's rule */,
                    int thickness, float threshold, void *stream);
+/* hrn_draw_poses with the person indices ON THE DEVICE (the ids hrn_associate_people_dev wrote): person_index_dev holds n int32
+ * and is required; everything else, the checks and the drawn bytes are hrn_draw_poses'.  The bone palette is uploaded with the
+ * call's table and one small launch behind the copy fills each person's bone colour, bone_colors[person_index mod Cb] (Python's
+ * modulo), before the two launches of hrn_draw_poses: three launches, no host read. */
+int hrn_draw_poses_ids_dev(hrn_handle h, const hrn_canvas *canvases_host, int nframes, const float *pts_dev, int n, int J,
+                           const int32_t *frame_index_host, const int32_t *skeleton_host, int K, const uint8_t *point_colors_host,
+                           int Cp, const uint8_t *bone_colors_host, int Cb, const int32_t *person_index_dev, int radius,
+                           int thickness, float threshold, void *stream);
 int hrn_yuv_from_bgr(int matrix, int range, const uint8_t *bgr /* (n,3) */, int n, uint8_t *yuv_out /* (n,3) */);
 
 /* Single-person pre-path on the GPU: replaces, for every frame of a call with multiperson=False,

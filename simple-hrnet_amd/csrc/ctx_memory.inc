@@ -542,6 +542,10 @@
             draw_table = draw_records = nullptr, draw_table_bytes = draw_records_bytes = 0;
             if (draw_done) (void)hipEventDestroy(draw_done);
             draw_done = nullptr;
+            if (assoc_buf) (void)hipFree(assoc_buf);
+            assoc_buf = nullptr, assoc_buf_bytes = 0;
+            if (assoc_done) (void)hipEventDestroy(assoc_done);
+            assoc_done = nullptr;
             if (trk_table) (void)hipFree(trk_table);
             trk_table = nullptr, trk_table_bytes = 0;
             if (trk_done) (void)hipEventDestroy(trk_done);

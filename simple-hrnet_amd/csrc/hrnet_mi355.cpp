@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "assoc_math.h"
 #include "kernels.h"
 #include "track_geometry.h"
 
@@ -72,6 +73,7 @@ struct hrn_ctx {
     bool weights_loaded = false;
 
     bool disable_lds = env_sw("HRN_DISABLE_LDS") != nullptr;
+    bool assoc_no_assign = env_sw("HRN_ASSOC_NO_ASSIGN") != nullptr;   // timing only: hrn_associate_people_dev skips its assignment phase
     bool disable_group = env_sw("HRN_DISABLE_GROUP") != nullptr;
     bool disable_dgroup = env_sw("HRN_DISABLE_DGROUP") != nullptr;
     bool disable_chain = env_sw("HRN_DISABLE_CHAIN") != nullptr;
@@ -251,6 +253,12 @@ struct hrn_ctx {
     size_t draw_table_bytes = 0, draw_records_bytes = 0;
     hipEvent_t draw_done = nullptr;
     hipStream_t draw_stream = nullptr;
+    // person ids (hrn_associate_people_dev): the problem table of a call with several problems, then the costs and similarities the
+    // kernel keeps between its phases; on the device, grown on demand, guarded like warp_params against a call on another stream
+    char *assoc_buf = nullptr;
+    size_t assoc_buf_bytes = 0;
+    hipEvent_t assoc_done = nullptr;
+    hipStream_t assoc_stream = nullptr;
     // the tracking link (hrn_boxes_from_poses, hrn_preprocess_frames_dev): the call's host table on the device (frame sizes per
     // person; frame table and frame index), grown on demand and guarded like warp_params against a call on another stream
     char *trk_table = nullptr;
@@ -1056,17 +1064,20 @@ inline unsigned pack_colour(const uint8_t *c) { return (unsigned)c[0] | ((unsign
 inline size_t align16(size_t v) { return (v + 15) / 16 * 16; }
 }  // namespace
 
-// misc/visualization.py:71-192 for every person of every frame: the arguments are judged first (they need no device), then the
-// handle; one table upload and two launches follow
-int hrn_draw_poses(hrn_handle h, const hrn_canvas *canvases_host, int nframes, const float *pts_dev, int n, int J,
-                   const int32_t *frame_index_host, const int32_t *skeleton_host, int K, const uint8_t *point_colors_host, int Cp,
-                   const uint8_t *bone_colors_host, int Cb, const int32_t *person_index_host, int radius, int thickness,
-                   float threshold, void *stream) {
+namespace {
+// misc/visualization.py:71-192 for every person of every frame, the one body of hrn_draw_poses (person_index_dev == nullptr) and
+// hrn_draw_poses_ids_dev (ids_on_device): the arguments are judged first (they need no device), then the handle; one table
+// upload and two launches follow (three with the ids on the device)
+int draw_poses(const char *entry, hrn_handle h, const hrn_canvas *canvases_host, int nframes, const float *pts_dev, int n, int J,
+               const int32_t *frame_index_host, const int32_t *skeleton_host, int K, const uint8_t *point_colors_host, int Cp,
+               const uint8_t *bone_colors_host, int Cb, const int32_t *person_index_host, const int32_t *person_index_dev,
+               bool ids_on_device, int radius, int thickness, float threshold, void *stream) {
     if (!h) return 1;
     const auto fail = [&](const std::string &what) {
-        h->err = "hrn_draw_poses: " + what;
+        h->err = std::string(entry) + ": " + what;
         return 7;
     };
+    if (ids_on_device && n > 0 && !person_index_dev) return fail("null person_index_dev");
     if (n < 0) return fail("n is negative");
     if (J < 1 || J > HRN_MAX_JOINTS) return fail("J must be in [1, " + std::to_string(HRN_MAX_JOINTS) + "]");
     if (K < 0 || K > kDrawMaxBones) return fail("K must be in [0, " + std::to_string(kDrawMaxBones) + "]");
@@ -1119,7 +1130,8 @@ int hrn_draw_poses(hrn_handle h, const hrn_canvas *canvases_host, int nframes, c
         if (count[f]) slot[f] = used++;
     const size_t off_order = align16((size_t)used * sizeof(DrawFrame)), off_pframe = off_order + align16((size_t)n * 4),
                  off_bone = off_pframe + align16((size_t)n * 4), off_point = off_bone + align16((size_t)n * 4),
-                 off_skel = off_point + align16((size_t)Cp * 4), table_bytes = off_skel + align16((size_t)std::max(K, 1) * 4);
+                 off_skel = off_point + align16((size_t)Cp * 4), off_palette = off_skel + align16((size_t)std::max(K, 1) * 4),
+                 table_bytes = off_palette + (ids_on_device ? align16((size_t)Cb * 4) : 0);   // (host ids: the table ends at off_palette)
     unsigned ring = 0;
     char *pin = h->pre_stage(table_bytes, &ring);
     if (!pin) return 6;
@@ -1145,8 +1157,10 @@ int hrn_draw_poses(hrn_handle h, const hrn_canvas *canvases_host, int nframes, c
         order[d.person_start + d.person_count++] = i;
         pframe[i] = (int)(&d - frames);
         const long id = person_index_host ? (long)person_index_host[i] : (long)i;
-        bone[i] = pack_colour(bone_colors_host + 3 * (size_t)(((id % Cb) + Cb) % Cb));      // Python's modulo
+        bone[i] = ids_on_device ? 0u : pack_colour(bone_colors_host + 3 * (size_t)(((id % Cb) + Cb) % Cb));   // Python's modulo
     }
+    if (ids_on_device)   // the palette travels with the table; a launch behind the copy fills bone[] from the ids on the device
+        for (int k = 0; k < Cb; ++k) ((unsigned *)(pin + off_palette))[k] = pack_colour(bone_colors_host + 3 * (size_t)k);
     for (int k = 0; k < Cp; ++k) point[k] = pack_colour(point_colors_host + 3 * (size_t)k);
     for (int k = 0; k < K; ++k) skel[k] = (unsigned)skeleton_host[2 * k] | ((unsigned)skeleton_host[2 * k + 1] << 16);
 
@@ -1173,6 +1187,12 @@ int hrn_draw_poses(hrn_handle h, const hrn_canvas *canvases_host, int nframes, c
     if (!h->draw_done && !h->hip_ok(hipEventCreateWithFlags(&h->draw_done, hipEventDisableTiming), "hipEventCreate")) return 6;
     if (!h->hip_ok(hipMemcpyAsync(h->draw_table, pin, table_bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync(draw table)")) return 6;
     if (!h->hip_ok(hipEventRecord(h->pre_landed[ring], s), "hipEventRecord")) return 6;
+    if (ids_on_device && !h->hip_ok(launch_bone_ids(person_index_dev, n, (const unsigned *)(h->draw_table + off_palette), Cb,
+                                                    (unsigned *)(h->draw_table + off_bone), s), "bone colour launch")) {
+        h->draw_stream = s;   // (the table copy is in flight on s: a later call on another stream waits for it)
+        (void)hipEventRecord(h->draw_done, s);
+        return 8;
+    }
     DrawArgs a{};
     a.pts = pts_dev, a.n = n, a.J = J, a.K = K, a.Cp = Cp, a.nframes = used, a.total_tiles = tiles, a.thickness = thickness;
     a.threshold = threshold;
@@ -1184,6 +1204,88 @@ int hrn_draw_poses(hrn_handle h, const hrn_canvas *canvases_host, int nframes, c
     h->draw_stream = s;
     if (!h->hip_ok(hipEventRecord(h->draw_done, s), "hipEventRecord")) return 6;
     return h->hip_ok(e, "draw launch") ? 0 : 8;
+}
+}  // namespace
+
+int hrn_draw_poses(hrn_handle h, const hrn_canvas *canvases_host, int nframes, const float *pts_dev, int n, int J,
+                   const int32_t *frame_index_host, const int32_t *skeleton_host, int K, const uint8_t *point_colors_host, int Cp,
+                   const uint8_t *bone_colors_host, int Cb, const int32_t *person_index_host, int radius, int thickness,
+                   float threshold, void *stream) {
+    return draw_poses("hrn_draw_poses", h, canvases_host, nframes, pts_dev, n, J, frame_index_host, skeleton_host, K, point_colors_host,
+                      Cp, bone_colors_host, Cb, person_index_host, nullptr, false, radius, thickness, threshold, stream);
+}
+
+int hrn_draw_poses_ids_dev(hrn_handle h, const hrn_canvas *canvases_host, int nframes, const float *pts_dev, int n, int J,
+                           const int32_t *frame_index_host, const int32_t *skeleton_host, int K, const uint8_t *point_colors_host,
+                           int Cp, const uint8_t *bone_colors_host, int Cb, const int32_t *person_index_dev, int radius,
+                           int thickness, float threshold, void *stream) {
+    return draw_poses("hrn_draw_poses_ids_dev", h, canvases_host, nframes, pts_dev, n, J, frame_index_host, skeleton_host, K,
+                      point_colors_host, Cp, bone_colors_host, Cb, nullptr, person_index_dev, true, radius, thickness, threshold, stream);
+}
+
+// find_person_id_associations and the demo's next_id update for P problems in one launch (assoc.hip); the arguments are judged
+// first (assoc_math.h's assoc_fault, as in the host form: they need no device), then the handle
+int hrn_associate_people_dev(hrn_handle h, int P, const int32_t *cur_start_host, const int32_t *prev_start_host, int J,
+                             int32_t *boxes_dev, float *pts_dev, const int32_t *prev_boxes_dev, const float *prev_pts_dev,
+                             const int32_t *prev_ids_dev, int32_t *next_id_dev, double pose_alpha, double similarity_threshold,
+                             double smoothing_alpha, int32_t *ids_dev, int32_t *match_dev, int32_t *status_dev, void *stream) {
+    if (!h) return 1;
+    if (const char *fault = assoc_fault(P, cur_start_host, prev_start_host, J, boxes_dev, pts_dev, prev_boxes_dev, prev_pts_dev,
+                                        prev_ids_dev, next_id_dev, pose_alpha, similarity_threshold, smoothing_alpha, ids_dev,
+                                        match_dev, status_dev)) {
+        h->err = std::string("hrn_associate_people_dev: ") + fault;
+        return 7;
+    }
+    if (h->plan_only) {
+        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return 7;
+    }
+    if (P == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    // the problems, each with its piece of the scratch behind the table
+    const size_t table_bytes = P > 1 ? ((size_t)P * sizeof(AssocProblem) + 255) / 256 * 256 : 0;
+    std::vector<AssocProblem> probs((size_t)P);
+    size_t need = table_bytes;
+    for (int p = 0; p < P; ++p) {
+        AssocProblem &q = probs[p];
+        q.cur0 = cur_start_host[p], q.n = cur_start_host[p + 1] - q.cur0;
+        q.prev0 = prev_start_host[p], q.m = prev_start_host[p + 1] - q.prev0;
+        q.scratch = (long long)need;
+        need += ((size_t)q.n * q.m * 12 + 15) / 16 * 16;
+    }
+    if (need > h->assoc_buf_bytes) {   // grow: wait for whoever still uses the old one
+        if (h->assoc_done && !h->hip_ok(hipEventSynchronize(h->assoc_done), "hipEventSynchronize")) return 6;
+        if (h->assoc_buf) (void)hipFree(h->assoc_buf);
+        h->assoc_buf = nullptr, h->assoc_buf_bytes = 0;
+        const size_t cap = std::max<size_t>(need * 2, 65536);
+        if (!h->hip_ok(hipMalloc((void **)&h->assoc_buf, cap), "hipMalloc(association scratch)")) return 6;
+        h->assoc_buf_bytes = cap;
+    }
+    if (h->assoc_done && h->assoc_stream != s && !h->hip_ok(hipStreamWaitEvent(s, h->assoc_done, 0), "hipStreamWaitEvent")) return 6;
+    if (!h->assoc_done && !h->hip_ok(hipEventCreateWithFlags(&h->assoc_done, hipEventDisableTiming), "hipEventCreate")) return 6;
+    AssocArgs a{};
+    a.P = P, a.J = J, a.no_assign = h->assoc_no_assign ? 1 : 0;
+    if (P > 1) {   // the table through the pinned ring
+        unsigned ring = 0;
+        char *pin = h->pre_stage(table_bytes, &ring);
+        if (!pin) return 6;
+        memcpy(pin, probs.data(), (size_t)P * sizeof(AssocProblem));
+        if (!h->hip_ok(hipMemcpyAsync(h->assoc_buf, pin, (size_t)P * sizeof(AssocProblem), hipMemcpyHostToDevice, s),
+                       "hipMemcpyAsync(association table)"))
+            return 6;
+        if (!h->hip_ok(hipEventRecord(h->pre_landed[ring], s), "hipEventRecord")) return 6;
+        a.table = (const AssocProblem *)h->assoc_buf;
+    } else {
+        a.one = probs[0];
+    }
+    a.boxes = boxes_dev, a.pts = pts_dev, a.prev_boxes = prev_boxes_dev, a.prev_pts = prev_pts_dev, a.prev_ids = prev_ids_dev;
+    a.next_id = next_id_dev, a.pose_alpha = pose_alpha, a.similarity_threshold = similarity_threshold, a.smoothing_alpha = smoothing_alpha;
+    a.ids = ids_dev, a.match = match_dev, a.status = status_dev, a.scratch = h->assoc_buf;
+    const hipError_t e = launch_assoc(a, s);
+    h->assoc_stream = s;
+    if (!h->hip_ok(hipEventRecord(h->assoc_done, s), "hipEventRecord")) return 6;
+    return h->hip_ok(e, "association launch") ? 0 : 8;
 }
 
 int hrn_resize_frames(hrn_handle h, const uint8_t *frames_dev, int n, int frame_h, int frame_w, int interpolation,

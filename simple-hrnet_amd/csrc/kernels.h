@@ -395,6 +395,31 @@ struct CropRecordArgs {
 };
 hipError_t launch_crop_records(const CropRecordArgs &a, hipStream_t s);   // crop_records_kernel: one thread per person
 
+// Person re-identification between two frames (assoc.hip; include/hrnet_mi355.h: hrn_associate_people_dev): similarity, optimal
+// assignment, ids and smoothing of P independent problems in one launch, one block per problem (the arithmetic: assoc_math.h).
+struct AssocProblem {              // one problem: n current people from cur0, m previous people from prev0
+    int cur0, n, prev0, m;
+    long long scratch;             // byte offset of its n * m costs (double), then n * m similarities (float), in AssocArgs::scratch
+};
+struct AssocArgs {
+    int P, J;
+    int no_assign;                 // debug (HRN_ASSOC_NO_ASSIGN): phase 2 is skipped and nobody is matched -- what the other phases cost
+    AssocProblem one;              // P == 1: the problem, in the kernel arguments (nothing is uploaded)
+    const AssocProblem *table;     // else P entries, device
+    int *boxes;                    // (n, 4) int32, in / out
+    float *pts;                    // (n, J, 3) float32, in / out
+    const int *prev_boxes;
+    const float *prev_pts;
+    const int *prev_ids;
+    int *next_id;                  // P, in / out
+    double pose_alpha, similarity_threshold, smoothing_alpha;
+    int *ids, *match, *status;     // out: n, n, P
+    char *scratch;
+};
+hipError_t launch_assoc(const AssocArgs &a, hipStream_t s);   // assoc_kernel: P blocks of 256 threads
+// bone[i] = palette[ids[i] mod Cb] (Python's modulo) for hrn_draw_poses_ids_dev: the ids never leave the device
+hipError_t launch_bone_ids(const int *ids, int n, const unsigned *palette, int Cb, unsigned *bone, hipStream_t s);
+
 struct TapArgs {           // debug tap: crops crop0, crop0 + crop_step, ... of a flat padded tensor -> (ncrops, c, h, w) fp32
     const void *in;
     float *dst;

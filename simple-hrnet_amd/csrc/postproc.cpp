@@ -14,7 +14,10 @@
 #include <cstring>
 #include <limits>
 #include <numeric>
+#include <string>
 #include <vector>
+
+#include "assoc_math.h"
 
 #pragma clang fp contract(off)
 
@@ -225,6 +228,95 @@ int hrn_assignment(const double *cost, int rows, int cols, int32_t *row_to_col) 
             else
                 row_to_col[small] = big;
         }
+    return 0;
+}
+
+// Person re-identification between two frames on the host: P independent problems, each postproc.find_person_id_associations
+// followed by the demo's next_id update (scripts/live-demo.py:120-124), in assoc_math.h's arithmetic -- the text the kernel of
+// assoc.hip compiles, so hrn_associate_people_dev equals this bit for bit.
+namespace {
+thread_local std::string g_associate_error;
+}
+
+int hrn_associate_people(int P, const int32_t *cur_start, const int32_t *prev_start, int J, int32_t *boxes, float *pts,
+                         const int32_t *prev_boxes, const float *prev_pts, const int32_t *prev_ids, int32_t *next_id, double pose_alpha,
+                         double similarity_threshold, double smoothing_alpha, int32_t *ids, int32_t *match, int32_t *status) {
+    using namespace hrn;
+    if (const char *fault = assoc_fault(P, cur_start, prev_start, J, boxes, pts, prev_boxes, prev_pts, prev_ids, next_id, pose_alpha,
+                                        similarity_threshold, smoothing_alpha, ids, match, status)) {
+        g_associate_error = fault;
+        return 7;
+    }
+    const AssocParams prm = assoc_params(pose_alpha, similarity_threshold, smoothing_alpha);
+    double vars[17];
+    for (int j = 0; j < 17; ++j) vars[j] = assoc_coco_var(j);
+    std::vector<double> cost;
+    std::vector<float> sim;
+    std::vector<int32_t> col;
+    const size_t per = (size_t)J * 3;
+    for (int p = 0; p < P; ++p) {
+        const int cur0 = cur_start[p], n = cur_start[p + 1] - cur0, prev0 = prev_start[p], m = prev_start[p + 1] - prev0;
+        status[p] = 0;
+        if (n == 0) continue;   // nobody here: next_id stays
+        cost.assign((size_t)n * m, 0.0), sim.assign((size_t)n * m, 0.0f), col.assign(n, -1);
+        for (int i = 0; i < n; ++i)
+            for (int k = 0; k < m; ++k)
+                status[p] |= assoc_pair(pts + (cur0 + i) * per, prev_pts + (prev0 + k) * per, J, boxes + (size_t)(cur0 + i) * 4,
+                                        prev_boxes + (size_t)(prev0 + k) * 4, vars, prm, &cost[(size_t)i * m + k], &sim[(size_t)i * m + k]);
+        if (m > 0 && hrn_assignment(cost.data(), n, m, col.data()) != 0) {   // (cannot happen: every cost is finite)
+            col.assign(n, -1);
+            status[p] |= 2;
+        }
+        int rank = 0;
+        int32_t max_id = std::numeric_limits<int32_t>::min();
+        for (int i = 0; i < n; ++i) {
+            const int c = col[i];
+            const bool accepted = c >= 0 && assoc_accepted(sim[(size_t)i * m + c], prm);
+            int32_t id = accepted ? prev_ids[prev0 + c] : -1;
+            if (id == -1) id = assoc_fresh_id(next_id[p], rank++);
+            ids[cur0 + i] = id, match[cur0 + i] = accepted ? c : -1;
+            max_id = std::max(max_id, id);
+            if (accepted && prm.smoothing != 0.0) {
+                for (int k = 0; k < 4; ++k) {
+                    int32_t *b = boxes + (size_t)(cur0 + i) * 4 + k;
+                    *b = assoc_smooth_box(*b, prev_boxes[(size_t)(prev0 + c) * 4 + k], prm);
+                }
+                for (size_t e = 0; e < per; ++e) {
+                    float *q = pts + (cur0 + i) * per + e;
+                    *q = assoc_smooth_joint(*q, prev_pts[(prev0 + c) * per + e], prm);
+                }
+            }
+        }
+        next_id[p] = assoc_next_id(next_id[p], max_id);
+    }
+    return 0;
+}
+
+const char *hrn_associate_people_last_error(void) { return g_associate_error.c_str(); }
+
+// the (n, m) costs and blended similarities of ONE problem as both entries compute them (assoc_math.h's assoc_pair: the
+// similarity is NaN where the blend was not finite), for measuring them against the reference's matrices; returns 0 or 7
+int hrn_associate_similarity(const int32_t *boxes, const float *pts, int n, const int32_t *prev_boxes, const float *prev_pts, int m, int J,
+                             double pose_alpha, double *cost_out, float *sim_out) {
+    using namespace hrn;
+    if (n < 0 || m < 0 || J < 1 || J > kAssocMaxJoints || !(pose_alpha - pose_alpha == 0.0) || (n && (!boxes || !pts)) ||
+        (m && (!prev_boxes || !prev_pts)) || (n && m && (!cost_out || !sim_out)))
+        return 7;
+    const AssocParams prm = assoc_params(pose_alpha, 0.0, 0.0);
+    double vars[17];
+    for (int j = 0; j < 17; ++j) vars[j] = assoc_coco_var(j);
+    const size_t per = (size_t)J * 3;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < m; ++k)
+            (void)assoc_pair(pts + i * per, prev_pts + k * per, J, boxes + (size_t)i * 4, prev_boxes + (size_t)k * 4, vars, prm,
+                             &cost_out[(size_t)i * m + k], &sim_out[(size_t)i * m + k]);
+    return 0;
+}
+
+// assoc_math.h's exp, n values (its error is measured through this entry)
+int hrn_assoc_exp(const double *x, int n, double *out) {
+    if (n < 0 || (n && (!x || !out))) return 7;
+    for (int i = 0; i < n; ++i) out[i] = hrn::assoc_exp(x[i]);
     return 0;
 }
 

@@ -680,7 +680,9 @@ class NativeHRNet:
         ``pts``: (J, 3) or (n, J, 3) (y, x, confidence) as ``predict*`` returns them, on the device or the host;
         ``skeleton``: (K, 2) joint index pairs (``joints_dict()[set]["skeleton"]`` of the reference);
         ``frame_index``: n frame numbers when there are several frames; ``person_ids``: the ``person_index`` of each person
-        (bone colour ``person_ids[i] % len(palette)``; default i);
+        (bone colour ``person_ids[i] % len(palette)``; default i) -- a tensor on the engine's GPU (the ids of
+        ``associate_people`` / ``PersonTracker.update``) stays there: ``hrn_draw_poses_ids_dev`` looks the colours up on the
+        device, with no host read; anything else is read on the host as before;
         palettes: a matplotlib name (``palette``) or ready (C, 3) uint8 BGR colours -- converted with ``bgr_to_yuv_colors`` for
         ``YuvFrame``s, which then share one matrix and range;
         ``radius``: of a joint's disc (default: the reference's ``max(1, min(H, W) // 160)`` per frame); ``thickness``: of a bone."""
@@ -729,8 +731,15 @@ class NativeHRNet:
                 raise ValueError("frame_index must have one entry per person: %d for %d people" % (len(fi), n))
         elif len(items) != 1:
             raise ValueError("several frames need frame_index: which frame each person is drawn on")
-        ids = None
-        if person_ids is not None:
+        ids = ids_dev = None
+        if isinstance(person_ids, torch.Tensor) and person_ids.is_cuda:
+            if person_ids.device != dev or person_ids.dtype != torch.int32:
+                raise ValueError("person_ids on a GPU must be an int32 tensor on the engine's device %s (the ids of associate_people / "
+                                 "PersonTracker.update), got %s on %s" % (dev, person_ids.dtype, person_ids.device))
+            ids_dev = person_ids.reshape(-1).contiguous()
+            if len(ids_dev) != n:
+                raise ValueError("person_ids must have one entry per person: %d for %d people" % (len(ids_dev), n))
+        elif person_ids is not None:
             ids = np.ascontiguousarray(np.asarray(person_ids, dtype=np.int32).reshape(-1))
             if len(ids) != n:
                 raise ValueError("person_ids must have one entry per person: %d for %d people" % (len(ids), n))
@@ -741,12 +750,14 @@ class NativeHRNet:
                 raise ValueError("the YuvFrames of one draw_poses call share one matrix and range (the colours are converted once)")
             (matrix, range_), = spaces
             pc, bc = bgr_to_yuv_colors(pc, matrix, range_), bgr_to_yuv_colors(bc, matrix, range_)
+        entry, name = (self._lib.hrn_draw_poses, "hrn_draw_poses") if ids_dev is None else \
+            (self._lib.hrn_draw_poses_ids_dev, "hrn_draw_poses_ids_dev")
+        index = (None if ids is None else ids.ctypes.data) if ids_dev is None else ids_dev.data_ptr()
         with torch.cuda.device(self.device_index):
-            rc = self._lib.hrn_draw_poses(self._h, table, len(items), pts.data_ptr(), n, joints, None if fi is None else fi.ctypes.data,
-                                          skel.ctypes.data if len(skel) else None, len(skel), pc.ctypes.data, len(pc), bc.ctypes.data,
-                                          len(bc), None if ids is None else ids.ctypes.data, 0 if radius is None else int(radius),
-                                          int(thickness), float(confidence_threshold), self._stream())
-        self._check(rc, "hrn_draw_poses")
+            rc = entry(self._h, table, len(items), pts.data_ptr(), n, joints, None if fi is None else fi.ctypes.data,
+                       skel.ctypes.data if len(skel) else None, len(skel), pc.ctypes.data, len(pc), bc.ctypes.data, len(bc), index,
+                       0 if radius is None else int(radius), int(thickness), float(confidence_threshold), self._stream())
+        self._check(rc, name)
         return canvases[0] if single else canvases
 
     def resize_frames(self, frames, interpolation: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1060,6 +1071,66 @@ class NativeHRNet:
         if return_heatmaps:
             return boxes_dev, out[1], status_dev, out[0]
         return boxes_dev, out, status_dev
+
+    # -- person ids between two frames: who of the previous frame is who of this one ------------------------------------------------
+    def associate_people(self, boxes, pts, prev_boxes, prev_pts, prev_ids, next_id, pose_alpha: float = 0.5,
+                         similarity_threshold: float = 0.5, smoothing_alpha: float = 0.0, counts=None, prev_counts=None):
+        """``postproc.associate_people`` on the GPU (``hrn_associate_people_dev``: one launch, one block per problem, no host
+        read): ``find_person_id_associations`` of the reference's demo loop and its ``next_id`` update, for one video or the
+        streams of a camera wall (``counts`` / ``prev_counts``: people per stream, on the host).
+
+        ``boxes`` (n, 4) int32 and ``pts`` (n, J, 3) float32 as ``predict_frame`` / ``track_frame`` return them, ``prev_boxes``,
+        ``prev_pts``, ``prev_ids`` (m,) int32 of the previous frame, ``next_id`` one int or (P,) int32.  Tensors of the right type
+        on the engine's GPU are used where they lie -- ``boxes`` and ``pts`` are then smoothed IN PLACE and ``next_id`` is
+        updated in place; host arrays are uploaded.  Returns ``(boxes, pts, ids, match, next_id, status)`` on the GPU, bit for
+        bit the host form's: ``match`` the accepted previous person (counted inside its problem) or -1, ``status`` per problem
+        (bit 0: a non-finite similarity, e.g. of two zero boxes, was counted as 0 and not accepted).  At most 256 people per
+        problem and side."""
+        from .postproc import _next_ids, _segments
+
+        dev = self.torch_device
+
+        def on_device(v, dtype, shape):
+            if not isinstance(v, torch.Tensor):
+                v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.int32 if dtype == torch.int32 else np.float32))
+            return v.to(dev, dtype=dtype, non_blocking=True).reshape(shape).contiguous()
+
+        boxes, prev_boxes = on_device(boxes, torch.int32, (-1, 4)), on_device(prev_boxes, torch.int32, (-1, 4))
+        n, m = int(boxes.shape[0]), int(prev_boxes.shape[0])
+        pts, prev_pts = (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
+                         for v in (pts, prev_pts))
+        widths = {int(v.shape[1]) for v in (pts, prev_pts) if v.dim() == 3 and v.shape[0]}
+        if len(widths) > 1:
+            raise ValueError("the two sets of skeletons have different joint counts")
+        joints = widths.pop() if widths else 1
+        pts, prev_pts = on_device(pts, torch.float32, (-1, joints, 3)), on_device(prev_pts, torch.float32, (-1, joints, 3))
+        prev_ids = on_device(prev_ids, torch.int32, (-1,))
+        if int(pts.shape[0]) != n or int(prev_pts.shape[0]) != m or int(prev_ids.shape[0]) != m:
+            raise ValueError("pts must be (n, J, 3) beside (n, 4) boxes with one J on both sides, and prev_ids one per previous "
+                             "person: got %s, %s, %s, %s, %s" % tuple(tuple(v.shape) for v in (boxes, pts, prev_boxes, prev_pts, prev_ids)))
+        cur, prev = _segments(counts, n, "counts"), _segments(prev_counts, m, "prev_counts")
+        if len(cur) != len(prev):
+            raise ValueError("counts and prev_counts name %d and %d problems" % (len(cur) - 1, len(prev) - 1))
+        problems = len(cur) - 1
+        if isinstance(next_id, torch.Tensor) and next_id.is_cuda:   # used where it lies: never read on the host
+            if next_id.device != dev or next_id.dtype != torch.int32 or next_id.numel() != problems or not next_id.is_contiguous():
+                raise ValueError("next_id on a GPU must be a contiguous int32 tensor of %d value(s) on %s, got %s %s on %s"
+                                 % (problems, dev, next_id.dtype, tuple(next_id.shape), next_id.device))
+            nxt = next_id.reshape(-1)
+        else:
+            nxt = torch.from_numpy(_next_ids(next_id.numpy() if isinstance(next_id, torch.Tensor) else next_id, problems))
+            nxt = nxt.to(dev, non_blocking=True)
+        ids = torch.empty((n,), dtype=torch.int32, device=dev)
+        match = torch.empty((n,), dtype=torch.int32, device=dev)
+        status = torch.zeros((problems,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(self.device_index):
+            rc = self._lib.hrn_associate_people_dev(self._h, problems, cur.ctypes.data, prev.ctypes.data, joints, boxes.data_ptr(),
+                                                    pts.data_ptr(), prev_boxes.data_ptr(), prev_pts.data_ptr(), prev_ids.data_ptr(),
+                                                    nxt.data_ptr(), float(pose_alpha), float(similarity_threshold),
+                                                    float(smoothing_alpha), ids.data_ptr(), match.data_ptr(), status.data_ptr(),
+                                                    self._stream())
+        self._check(rc, "hrn_associate_people_dev")
+        return boxes, pts, ids, match, nxt, status
 
     # -- clip mode: the people of many frames in one pre-path launch and one pass (throughput, not latency) ------------------
     def _device_frames(self, frames) -> List[Optional[torch.Tensor]]:

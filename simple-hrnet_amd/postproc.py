@@ -136,6 +136,68 @@ def find_person_id_associations(boxes, pts, prev_boxes, prev_pts, prev_person_id
     return boxes, pts, person_ids
 
 
+def _segments(counts, total: int, what: str) -> np.ndarray:
+    """``counts`` of ``associate_people`` as the int32 segment table (P + 1 starts); None: one problem with everybody"""
+    c = np.asarray([total] if counts is None else counts, dtype=np.int64).reshape(-1)
+    if (c < 0).any() or int(c.sum()) != total:
+        raise ValueError("%s must be non-negative and sum to %d people, got %s" % (what, total, c.tolist()))
+    return np.ascontiguousarray(np.concatenate([[0], np.cumsum(c)]), dtype=np.int32)
+
+
+def _next_ids(next_id, problems: int) -> np.ndarray:
+    """``next_id`` of ``associate_people`` as P int32 values of its own (one int serves every problem)"""
+    v = np.array(next_id, dtype=np.int32).reshape(-1)
+    if len(v) == 1 and problems != 1:
+        v = np.repeat(v, problems)
+    if len(v) != problems:
+        raise ValueError("next_id must hold one value per problem: %d for %d" % (len(v), problems))
+    return np.ascontiguousarray(v)
+
+
+def associate_people(boxes, pts, prev_boxes, prev_pts, prev_ids, next_id, pose_alpha=0.5, similarity_threshold=0.5,
+                     smoothing_alpha=0., counts=None, prev_counts=None):
+    """``find_person_id_associations`` plus the demo's ``next_id = max(next_id, max(ids) + 1)`` for P independent problems in one
+    native call (``hrn_associate_people``, no GPU): the host form of ``NativeHRNet.associate_people``, equal to it bit for bit.
+
+    ``boxes`` (n, 4) int32, ``pts`` (n, J, 3) float32 ``(y, x, confidence)``, ``prev_*`` likewise with ``prev_ids`` (m,) int32;
+    ``counts`` / ``prev_counts``: people per problem on either side (the streams of a camera wall; None: one problem);
+    ``next_id``: one int, or one per problem.  C-contiguous int32 ``boxes`` / float32 ``pts`` are smoothed IN PLACE, as
+    ``find_person_id_associations`` does; anything else is converted first and the converted arrays are returned.
+    Returns ``(boxes, pts, ids (n,) int32, match (n,) int32, next_id (P,) int32, status (P,) int32)``: ``match`` is the accepted
+    previous person counted inside its problem, or -1; ``status`` bit 0: a non-finite similarity (two zero boxes) was counted as 0
+    and not accepted -- where ``find_person_id_associations`` raises.  At most 256 people per problem and side."""
+    boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
+    prev_boxes = np.ascontiguousarray(prev_boxes, dtype=np.int32).reshape(-1, 4)
+    pts, prev_pts = np.ascontiguousarray(pts, dtype=np.float32), np.ascontiguousarray(prev_pts, dtype=np.float32)
+    prev_ids = np.ascontiguousarray(prev_ids, dtype=np.int32).reshape(-1)
+    if pts.size == 0 and pts.ndim != 3:           # (an empty list of skeletons)
+        pts = pts.reshape(0, prev_pts.shape[1] if prev_pts.ndim == 3 else 1, 3)
+    if prev_pts.size == 0 and prev_pts.ndim != 3:
+        prev_pts = prev_pts.reshape(0, pts.shape[1], 3)
+    n, m = len(boxes), len(prev_boxes)
+    if pts.ndim != 3 or prev_pts.ndim != 3 or pts.shape[2] != 3 or prev_pts.shape[2] != 3 or len(pts) != n or len(prev_pts) != m \
+            or len(prev_ids) != m:
+        raise ValueError("pts must be (n, J, 3) beside (n, 4) boxes, and prev_ids one per previous person: got %s, %s, %s, %s, %s"
+                         % (boxes.shape, pts.shape, prev_boxes.shape, prev_pts.shape, prev_ids.shape))
+    if n and m and pts.shape[1] != prev_pts.shape[1]:
+        raise ValueError("the two sets of skeletons have different joint counts")
+    joints = int(pts.shape[1] if n else prev_pts.shape[1]) or 1
+    cur, prev = _segments(counts, n, "counts"), _segments(prev_counts, m, "prev_counts")
+    if len(cur) != len(prev):
+        raise ValueError("counts and prev_counts name %d and %d problems" % (len(cur) - 1, len(prev) - 1))
+    problems = len(cur) - 1
+    nxt = _next_ids(next_id, problems)
+    ids, match, status = np.empty(n, np.int32), np.empty(n, np.int32), np.zeros(problems, np.int32)
+    lib = _lib.load()
+    rc = lib.hrn_associate_people(problems, cur.ctypes.data, prev.ctypes.data, joints, boxes.ctypes.data, pts.ctypes.data,
+                                  prev_boxes.ctypes.data, prev_pts.ctypes.data, prev_ids.ctypes.data, nxt.ctypes.data,
+                                  float(pose_alpha), float(similarity_threshold), float(smoothing_alpha), ids.ctypes.data,
+                                  match.ctypes.data, status.ctypes.data)
+    if rc:
+        raise ValueError("hrn_associate_people: " + lib.hrn_associate_people_last_error().decode())
+    return boxes, pts, ids, match, nxt, status
+
+
 def inverse_affine(center, scale, pixel_std, output_size) -> np.ndarray:
     """The 2x3 matrix ``get_affine_transform(center, scale, pixel_std, 0, output_size, inv=1)`` returns
     (``misc/utils.py:44-76``): heat-map coordinates back to image coordinates for an unrotated crop.  The reference builds

@@ -1,0 +1,83 @@
+"""Person ids over a video: the state of the reference's demo loop (``scripts/live-demo.py:114-130``) kept where the joints are.
+
+``PersonTracker`` holds the previous frame's boxes, joints and ids and ``next_id``; every ``update`` is one
+``associate_people`` -- ``NativeHRNet.associate_people`` on the engine's GPU (one launch, no host read: the ids feed
+``draw_poses`` from the device), or ``postproc.associate_people`` on the host when there is no engine."""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from . import postproc
+
+
+class PersonTracker:
+    """``net``: a ``NativeHRNet`` -- state and results are tensors on its GPU -- or None: numpy arrays on the host, the same numbers.
+    ``pose_alpha``, ``similarity_threshold``, ``smoothing_alpha``: as ``find_person_id_associations``; the defaults are the demo's.
+
+    ``update(boxes, pts, counts=None) -> (boxes, pts, ids)``: ``boxes`` (n, 4) int32 and ``pts`` (n, J, 3) float32 of this frame
+    (``predict_frame`` / ``track_frame``); ``counts``: people per stream when several streams are tracked at once (the same
+    number of streams in every update).  The arguments are left as they are; the returned ``boxes`` and ``pts`` (smoothed where
+    matched) are the tracker's state until the next update -- read them, do not write to them.  The FIRST update follows the
+    demo: ids ``arange(n)`` and ``next_id = n + 1`` per stream that has somebody (no kernel; a first frame without people leaves
+    ``next_id`` at 0, as the demo does).  An update with nobody keeps ``next_id`` and stores empty arrays.  ``status`` holds the
+    last association's status per stream (None before), ``next_id`` the counters; ``reset()`` forgets everything."""
+
+    def __init__(self, net=None, pose_alpha: float = 0.2, similarity_threshold: float = 0.4, smoothing_alpha: float = 0.1):
+        self.net = net
+        self.pose_alpha, self.similarity_threshold, self.smoothing_alpha = float(pose_alpha), float(similarity_threshold), float(smoothing_alpha)
+        self.reset()
+
+    def reset(self):
+        self.prev_boxes = self.prev_pts = self.prev_ids = self.prev_counts = self.next_id = self.status = None
+
+    def _own(self, boxes, pts):
+        """copies of this frame's boxes and joints where the tracker works: (n, 4) int32 and (n, J, 3) float32"""
+        if self.net is None:
+            b = np.array(boxes.cpu() if hasattr(boxes, "cpu") else boxes, dtype=np.int32).reshape(-1, 4)
+            p = np.array(pts.cpu() if hasattr(pts, "cpu") else pts, dtype=np.float32)
+            return b, p.reshape(len(b), -1 if p.size else 1, 3) if p.ndim != 3 else p
+        import torch
+
+        dev = self.net.torch_device
+
+        def own(v, dtype, np_dtype):
+            if not isinstance(v, torch.Tensor):
+                return torch.from_numpy(np.ascontiguousarray(v, dtype=np_dtype)).to(dev, non_blocking=True)
+            moved = v.to(dev, dtype=dtype, non_blocking=True)
+            return moved.clone() if moved is v else moved
+
+        b = own(boxes, torch.int32, np.int32).reshape(-1, 4).contiguous()
+        p = own(pts, torch.float32, np.float32)
+        return b, (p.reshape(int(b.shape[0]), -1 if p.numel() else 1, 3) if p.dim() != 3 else p).contiguous()
+
+    def _upload(self, v: np.ndarray):
+        if self.net is None:
+            return v
+        import torch
+
+        return torch.from_numpy(v).to(self.net.torch_device, non_blocking=True)
+
+    def update(self, boxes, pts, counts: Optional[object] = None):
+        boxes, pts = self._own(boxes, pts)
+        n = int(boxes.shape[0])
+        if int(pts.shape[0]) != n:
+            raise ValueError("%d boxes for %d skeletons" % (n, int(pts.shape[0])))
+        counts = np.asarray([n] if counts is None else counts, dtype=np.int64).reshape(-1)
+        if (counts < 0).any() or int(counts.sum()) != n:
+            raise ValueError("counts must be non-negative and sum to %d people, got %s" % (n, counts.tolist()))
+        if self.prev_counts is not None and len(counts) != len(self.prev_counts):
+            raise ValueError("%d streams after %d: reset() the tracker first" % (len(counts), len(self.prev_counts)))
+        if self.prev_counts is None:      # live-demo.py:116-118, per stream
+            ids = np.concatenate([np.arange(c, dtype=np.int32) for c in counts]) if n else np.zeros(0, np.int32)
+            ids, self.next_id = self._upload(ids), self._upload(np.where(counts > 0, counts + 1, 0).astype(np.int32))
+        elif n == 0:                      # live-demo.py:125-126: nobody, next_id stays
+            ids = self._upload(np.zeros(0, np.int32))
+        else:
+            entry = postproc.associate_people if self.net is None else self.net.associate_people
+            boxes, pts, ids, _, self.next_id, self.status = entry(boxes, pts, self.prev_boxes, self.prev_pts, self.prev_ids, self.next_id,
+                                                                  self.pose_alpha, self.similarity_threshold, self.smoothing_alpha,
+                                                                  counts=counts, prev_counts=self.prev_counts)
+        self.prev_boxes, self.prev_pts, self.prev_ids, self.prev_counts = boxes, pts, ids, counts
+        return boxes, pts, ids
