@@ -7,6 +7,11 @@
         err = std::string(what) + ": " + hipGetErrorString(e);
         return false;
     }
+    // true (and the text) on a handle made with device_id < 0: the entries that would touch the device refuse it
+    bool refuse_plan_only() {
+        if (plan_only) err = "plan-only handle (device_id < 0): there is no CPU compute path";
+        return plan_only;
+    }
 
     bool allocate() {
         workspace_bytes = 0;
@@ -527,39 +532,7 @@
                 if (b.dev) (void)hipFree(b.dev);
             if (blob) (void)hipFree(blob);
             if (scratch_hm) (void)hipFree(scratch_hm);
-            if (pre_tmp) (void)hipFree(pre_tmp);
-            if (rs_taps) (void)hipFree(rs_taps);
-            rs_taps = nullptr, rs_taps_cap = 0;
-            if (rs_done) (void)hipEventDestroy(rs_done);
-            rs_done = nullptr;
-            if (pass_done) (void)hipEventDestroy(pass_done);
-            pass_done = nullptr;
-            if (pre_params) (void)hipFree(pre_params);
-            if (pre_yuv) (void)hipFree(pre_yuv);
-            pre_yuv = nullptr, pre_yuv_cap = 0;
-            if (draw_table) (void)hipFree(draw_table);
-            if (draw_records) (void)hipFree(draw_records);
-            draw_table = draw_records = nullptr, draw_table_bytes = draw_records_bytes = 0;
-            if (draw_done) (void)hipEventDestroy(draw_done);
-            draw_done = nullptr;
-            if (assoc_buf) (void)hipFree(assoc_buf);
-            assoc_buf = nullptr, assoc_buf_bytes = 0;
-            if (assoc_done) (void)hipEventDestroy(assoc_done);
-            assoc_done = nullptr;
-            if (trk_table) (void)hipFree(trk_table);
-            trk_table = nullptr, trk_table_bytes = 0;
-            if (trk_done) (void)hipEventDestroy(trk_done);
-            trk_done = nullptr;
-            if (warp_params) (void)hipFree(warp_params);
-            warp_params = nullptr, warp_params_cap = 0;
-            if (warp_done) (void)hipEventDestroy(warp_done);
-            warp_done = nullptr;
-            if (score_joints) (void)hipFree(score_joints);
-            score_joints = nullptr, score_joints_cap = 0;
-            if (score_done) (void)hipEventDestroy(score_done);
-            score_done = nullptr;
-            for (auto &kv : score_tables) (void)hipFree(kv.second);
-            score_tables.clear();
+            free_scratch();
             if (part_val) (void)hipFree(part_val);
             if (part_idx) (void)hipFree(part_idx);
             if (probs_dev) (void)hipFree(probs_dev);
@@ -571,11 +544,6 @@
                 for (MapSlot &sl : g.slot) free_slot(sl);
             for (auto &g : dgroups)
                 for (MapSlot &sl : g.slot) free_slot(sl);
-            for (int k = 0; k < kPreRing; ++k) {
-                if (pre_pin[k]) (void)hipHostFree(pre_pin[k]);
-                if (pre_landed[k]) (void)hipEventDestroy(pre_landed[k]);
-                pre_pin[k] = nullptr, pre_landed[k] = nullptr, pre_pin_bytes[k] = 0;
-            }
         }
         blob = nullptr;
     }

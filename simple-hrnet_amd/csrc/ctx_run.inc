@@ -261,10 +261,7 @@
     }
 
     bool check_forward_args(const void *images, int n, const void *boxes, float *pts, float *heatmaps, bool outputs_optional = false) {
-        if (plan_only) {
-            err = "plan-only handle (device_id < 0): there is no CPU compute path";
-            return false;
-        }
+        if (refuse_plan_only()) return false;
         if (!weights_loaded) {
             err = "weights not loaded (call hrn_load_weights or hrn_adopt_weights)";
             return false;

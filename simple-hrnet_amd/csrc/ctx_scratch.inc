@@ -1,0 +1,158 @@
+// hrn_ctx, part 5: what a call keeps on the handle outside the planned workspace -- the guard that serialises calls on different
+// streams, the device arrays a call rewrites, the pinned staging ring their uploads go through, the Gaussian tables of the scoring.
+// Included inside struct hrn_ctx (hrnet_mi355.cpp).
+
+    // One handle, one copy of everything a call writes: calls on DIFFERENT streams must not overlap on it.  Whoever uses the guarded
+    // thing records `done` behind its last kernel (leave); a call on another stream than the previous one waits for that event first
+    // (enter).  Same stream: ordered anyway, nothing is waited for.
+    struct CallGuard {
+        hipEvent_t done = nullptr;
+        hipStream_t stream = nullptr;   // of the last user
+        bool enter(hrn_ctx *h, hipStream_t s) {
+            if (!done) return h->hip_ok(hipEventCreateWithFlags(&done, hipEventDisableTiming), "hipEventCreate");
+            return stream == s || h->hip_ok(hipStreamWaitEvent(s, done, 0), "hipStreamWaitEvent");
+        }
+        bool leave(hrn_ctx *h, hipStream_t s) {
+            stream = s;
+            return h->hip_ok(hipEventRecord(done, s), "hipEventRecord");
+        }
+        void release() {
+            if (done) (void)hipEventDestroy(done);
+            done = nullptr, stream = nullptr;
+        }
+    };
+
+    // A device array of the handle that each call rewrites, with its guard.  reserve() before enter(): growing waits on the host
+    // until the last user's kernels have read the old array.  A family with several arrays enters the guard of its first one and
+    // names it as `readers` when it reserves the others.
+    struct CallScratch : CallGuard {
+        char *ptr = nullptr;
+        size_t bytes = 0;
+        template <class T>
+        T *as() const { return (T *)ptr; }
+        // at least `need` bytes; a grow allocates `cap` (>= need: the caller's growth rule)
+        bool reserve(hrn_ctx *h, size_t need, size_t cap, const char *what, CallGuard *readers = nullptr) {
+            if (need <= bytes) return true;
+            if (!readers) readers = this;
+            if (readers->done && !h->hip_ok(hipEventSynchronize(readers->done), "hipEventSynchronize")) return false;
+            if (ptr) (void)hipFree(ptr);
+            ptr = nullptr, bytes = 0;
+            if (!h->hip_ok(hipMalloc((void **)&ptr, cap), what)) return false;
+            bytes = cap;
+            return true;
+        }
+        void release() {
+            if (ptr) (void)hipFree(ptr);
+            ptr = nullptr, bytes = 0;
+            CallGuard::release();
+        }
+    };
+
+    // enter() .. leave() on EVERY exit (ADVICE r3): kernels and copies already queued by a call that failed half-way must be covered
+    // by `done` too, or the next call on another stream could rewrite what they still read.  A null guard guards nothing.
+    struct CallScope {
+        hrn_ctx *h;
+        CallGuard *g;
+        hipStream_t s;
+        bool entered, left = false;
+        CallScope(hrn_ctx *h_, CallGuard *g_, hipStream_t s_) : h(h_), g(g_), s(s_), entered(!g_ || g_->enter(h_, s_)) {}
+        CallScope(const CallScope &) = delete;
+        bool leave() {
+            left = true;
+            return entered && (!g || g->leave(h, s));
+        }
+        ~CallScope() {   // a failure exit: the call's own error text stays
+            if (g && entered && !left) g->stream = s, (void)hipEventRecord(g->done, s);
+        }
+    };
+
+    CallGuard pass;            // the workspace: every entry point that runs a pass
+    CallScratch rs_taps;       // hrn_resize_frames: tap tables of the last (frame size, interpolation)
+    CallScratch pre_tmp, pre_params, pre_yuv;   // crop pre-path: intermediates, CropParams and (YUV frames) a YuvSource per person; pre_tmp's guard
+    CallScratch warp_params;   // hrn_warp_crops: the inverse matrices
+    CallScratch score_joints;  // hrn_score_heatmaps, hrn_generate_targets: the per-(crop, joint) records
+    CallScratch draw_table, draw_records;   // hrn_draw_poses: the call's table (canvases, people by canvas, colours, skeleton) and the
+                                            // per-person records the build launch writes; draw_table's guard
+    CallScratch assoc_buf;     // hrn_associate_people_dev: the problem table of a call with several problems, then the costs and
+                               // similarities the kernel keeps between its phases
+    CallScratch trk_table;     // the tracking link: the call's host table (frame sizes per person; frame table and frame index)
+
+    // the pre-path's device scratch for n people: `tmp_bytes` of intermediates (exact: they can be large), n records (and n YUV sources)
+    bool pre_reserve(size_t tmp_bytes, int n, bool yuv) {
+        return pre_tmp.reserve(this, tmp_bytes, tmp_bytes, "hipMalloc(pre-path scratch)") &&
+               pre_params.reserve(this, (size_t)n * sizeof(CropParams), (size_t)n * sizeof(CropParams), "hipMalloc(crop params)", &pre_tmp) &&
+               (!yuv || pre_yuv.reserve(this, (size_t)n * sizeof(YuvSource), (size_t)n * sizeof(YuvSource), "hipMalloc(YUV sources)", &pre_tmp));
+    }
+    // a table of `need` bytes: twice the need, at least `floor`
+    bool table_reserve(CallScratch &t, size_t need, size_t floor, const char *what, CallGuard *readers = nullptr) {
+        return t.reserve(this, need, std::max(need * 2, floor), what, readers);
+    }
+
+    // pinned host image of one call's tables (the async uploads read it after the call returned); kPreRing images in rotation,
+    // each rewritten only after the upload that last read it has completed
+    static constexpr int kPreRing = 4;
+    char *pre_pin[kPreRing] = {nullptr, nullptr, nullptr, nullptr};
+    size_t pre_pin_bytes[kPreRing] = {0, 0, 0, 0};
+    hipEvent_t pre_landed[kPreRing] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned pre_ring_next = 0;
+    // the next image of the ring, at least `need` bytes, free to be rewritten (nullptr + err on failure); pre_upload(*ring, ...)
+    // sends it
+    char *pre_stage(size_t need, unsigned *ring_out) {
+        const unsigned ring = pre_ring_next++ % kPreRing;
+        if (pre_landed[ring]) {
+            if (!hip_ok(hipEventSynchronize(pre_landed[ring]), "hipEventSynchronize")) return nullptr;
+        } else if (!hip_ok(hipEventCreateWithFlags(&pre_landed[ring], hipEventDisableTiming), "hipEventCreate")) {
+            return nullptr;
+        }
+        if (need > pre_pin_bytes[ring]) {
+            if (pre_pin[ring]) (void)hipHostFree(pre_pin[ring]);
+            pre_pin[ring] = nullptr, pre_pin_bytes[ring] = 0;
+            const size_t cap = std::max<size_t>(need * 2, 4096);
+            if (!hip_ok(hipHostMalloc((void **)&pre_pin[ring], cap, hipHostMallocDefault), "hipHostMalloc(crop params)")) return nullptr;
+            pre_pin_bytes[ring] = cap;
+        }
+        *ring_out = ring;
+        return pre_pin[ring];
+    }
+    // pieces of image `ring` to the device on s, then the event that lets the image be rewritten (a null destination: skipped)
+    struct PreCopy {
+        void *dst;
+        const void *src;
+        size_t bytes;
+        const char *what;
+    };
+    bool pre_upload(unsigned ring, hipStream_t s, std::initializer_list<PreCopy> copies) {
+        for (const PreCopy &c : copies)
+            if (c.dst && !hip_ok(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyHostToDevice, s), c.what)) return false;
+        return hip_ok(hipEventRecord(pre_landed[ring], s), "hipEventRecord");
+    }
+
+    // scoring: the Gaussian tables g[d2] = float32(exp(-d2 / (2 sigma^2))), d2 = 0 .. 2 t^2, by t = 3 sigma
+    std::map<int, float *> score_tables;
+    const float *score_table(int t, double sigma) {   // built in fp64 and rounded once, on the first call with this sigma
+        auto it = score_tables.find(t);
+        if (it != score_tables.end()) return it->second;
+        std::vector<float> g((size_t)2 * t * t + 1);
+        for (size_t d2 = 0; d2 < g.size(); ++d2) g[d2] = (float)std::exp(-(double)d2 / (2.0 * sigma * sigma));
+        float *dev = nullptr;
+        if (!hip_ok(hipMalloc((void **)&dev, g.size() * sizeof(float)), "hipMalloc(Gaussian table)")) return nullptr;
+        if (!hip_ok(hipMemcpy(dev, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(Gaussian table)")) {
+            (void)hipFree(dev);
+            return nullptr;
+        }
+        return score_tables[t] = dev;
+    }
+
+    void free_scratch() {
+        for (CallScratch *c : {&rs_taps, &pre_tmp, &pre_params, &pre_yuv, &warp_params, &score_joints, &draw_table, &draw_records, &assoc_buf,
+                               &trk_table})
+            c->release();
+        pass.release();
+        for (auto &kv : score_tables) (void)hipFree(kv.second);
+        score_tables.clear();
+        for (int k = 0; k < kPreRing; ++k) {
+            if (pre_pin[k]) (void)hipHostFree(pre_pin[k]);
+            if (pre_landed[k]) (void)hipEventDestroy(pre_landed[k]);
+            pre_pin[k] = nullptr, pre_landed[k] = nullptr, pre_pin_bytes[k] = 0;
+        }
+    }

@@ -148,167 +148,6 @@ struct hrn_ctx {
     int head_slabs_for(int nb) const { return (long)nb * head_slabs >= 192 ? head_slabs : head_slabs_small; }
     float *part_val = nullptr;
     int *part_idx = nullptr;
-    // crop pre-path scratch (grown on demand, never inside hrn_forward)
-    unsigned char *pre_tmp = nullptr;
-    size_t pre_tmp_bytes = 0;
-    ResizeTaps *rs_taps = nullptr;   // single-person pre-path: tap tables of the last (frame size, interpolation), device
-    int rs_taps_cap = 0;
-    // One workspace per handle: passes on DIFFERENT streams must not overlap on the device.  Every entry point that runs a pass
-    // records `pass_done` behind it; a call on another stream than the previous one waits for that event first (same stream:
-    // ordered anyway, nothing is waited for).
-    hipEvent_t pass_done = nullptr;
-    hipStream_t pass_stream = nullptr;
-    bool pass_enter(hipStream_t s) {
-        if (pass_done && pass_stream != s) return hip_ok(hipStreamWaitEvent(s, pass_done, 0), "hipStreamWaitEvent");
-        return true;
-    }
-    bool pass_leave(hipStream_t s) {
-        if (!pass_done && !hip_ok(hipEventCreateWithFlags(&pass_done, hipEventDisableTiming), "hipEventCreate")) return false;
-        pass_stream = s;
-        return hip_ok(hipEventRecord(pass_done, s), "hipEventRecord");
-    }
-    hipEvent_t rs_done = nullptr;    // recorded behind the last resize launch: a call on ANOTHER stream rewrites the table after it
-    hipStream_t rs_stream = nullptr;
-    CropParams *pre_params = nullptr;
-    int pre_params_cap = 0;
-    YuvSource *pre_yuv = nullptr;    // hrn_preprocess_frames_yuv: person i's planes, pitches and coefficients beside pre_params[i]
-    int pre_yuv_cap = 0;
-    // pinned host image of one call's crop parameters + boxes (the async uploads read it after the call returned);
-    // kPreRing images in rotation, each rewritten only after the upload that last read it has completed
-    static constexpr int kPreRing = 4;
-    char *pre_pin[kPreRing] = {nullptr, nullptr, nullptr, nullptr};
-    size_t pre_pin_bytes[kPreRing] = {0, 0, 0, 0};
-    hipEvent_t pre_landed[kPreRing] = {nullptr, nullptr, nullptr, nullptr};
-    unsigned pre_ring_next = 0;
-    // the next image of the ring, at least `need` bytes, free to be rewritten (nullptr + err on failure); the caller records
-    // pre_landed[*ring] behind the uploads that read it
-    char *pre_stage(size_t need, unsigned *ring_out) {
-        const unsigned ring = pre_ring_next++ % kPreRing;
-        if (pre_landed[ring]) {
-            if (!hip_ok(hipEventSynchronize(pre_landed[ring]), "hipEventSynchronize")) return nullptr;
-        } else if (!hip_ok(hipEventCreateWithFlags(&pre_landed[ring], hipEventDisableTiming), "hipEventCreate")) {
-            return nullptr;
-        }
-        if (need > pre_pin_bytes[ring]) {
-            if (pre_pin[ring]) (void)hipHostFree(pre_pin[ring]);
-            pre_pin[ring] = nullptr, pre_pin_bytes[ring] = 0;
-            const size_t cap = std::max<size_t>(need * 2, 4096);
-            if (!hip_ok(hipHostMalloc((void **)&pre_pin[ring], cap, hipHostMallocDefault), "hipHostMalloc(crop params)")) return nullptr;
-            pre_pin_bytes[ring] = cap;
-        }
-        *ring_out = ring;
-        return pre_pin[ring];
-    }
-    // evaluation pre-path (hrn_warp_crops): the inverse matrices of the last call on the device; like the resize's tap table,
-    // a call on ANOTHER stream than the previous one rewrites them only after that one's kernel has read them
-    WarpParams *warp_params = nullptr;
-    int warp_params_cap = 0;
-    hipEvent_t warp_done = nullptr;
-    hipStream_t warp_stream = nullptr;
-    // scoring (hrn_score_heatmaps, hrn_generate_targets): the per-(crop, joint) records of the last call on the device, guarded
-    // like warp_params, and the Gaussian tables g[d2] = float32(exp(-d2 / (2 sigma^2))), d2 = 0 .. 2 t^2, by t = 3 sigma
-    ScoreJoint *score_joints = nullptr;
-    int64_t score_joints_cap = 0;
-    hipEvent_t score_done = nullptr;
-    hipStream_t score_stream = nullptr;
-    std::map<int, float *> score_tables;
-    const float *score_table(int t, double sigma) {   // built in fp64 and rounded once, on the first call with this sigma
-        auto it = score_tables.find(t);
-        if (it != score_tables.end()) return it->second;
-        std::vector<float> g((size_t)2 * t * t + 1);
-        for (size_t d2 = 0; d2 < g.size(); ++d2) g[d2] = (float)std::exp(-(double)d2 / (2.0 * sigma * sigma));
-        float *dev = nullptr;
-        if (!hip_ok(hipMalloc((void **)&dev, g.size() * sizeof(float)), "hipMalloc(Gaussian table)")) return nullptr;
-        if (!hip_ok(hipMemcpy(dev, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(Gaussian table)")) {
-            (void)hipFree(dev);
-            return nullptr;
-        }
-        return score_tables[t] = dev;
-    }
-    // `count` records from image `ring` of the pinned staging ring to the device array (grown on demand; a call on ANOTHER
-    // stream than the previous one rewrites it only after that one's kernels have read it); score_ran() goes behind the launches
-    bool score_upload(const ScoreJoint *pinned, unsigned ring, int64_t count, hipStream_t s) {
-        if (count > score_joints_cap) {
-            if (score_done && !hip_ok(hipEventSynchronize(score_done), "hipEventSynchronize")) return false;
-            if (score_joints) (void)hipFree(score_joints);
-            score_joints = nullptr, score_joints_cap = 0;
-            const int64_t cap = std::max<int64_t>(count, 256 * 17);
-            if (!hip_ok(hipMalloc((void **)&score_joints, (size_t)cap * sizeof(ScoreJoint)), "hipMalloc(score records)")) return false;
-            score_joints_cap = cap;
-        }
-        if (score_done && score_stream != s && !hip_ok(hipStreamWaitEvent(s, score_done, 0), "hipStreamWaitEvent")) return false;
-        if (!score_done && !hip_ok(hipEventCreateWithFlags(&score_done, hipEventDisableTiming), "hipEventCreate")) return false;
-        if (!hip_ok(hipMemcpyAsync(score_joints, pinned, (size_t)count * sizeof(ScoreJoint), hipMemcpyHostToDevice, s),
-                    "hipMemcpyAsync(score records)"))
-            return false;
-        return hip_ok(hipEventRecord(pre_landed[ring], s), "hipEventRecord");
-    }
-    bool score_ran(hipStream_t s) {
-        score_stream = s;
-        return hip_ok(hipEventRecord(score_done, s), "hipEventRecord");
-    }
-    // pose overlays (hrn_draw_poses): the call's table (canvases, people by canvas, colours, skeleton) and the per-person records the
-    // build launch writes, both on the device and grown on demand; guarded like warp_params against a call on another stream
-    char *draw_table = nullptr, *draw_records = nullptr;
-    size_t draw_table_bytes = 0, draw_records_bytes = 0;
-    hipEvent_t draw_done = nullptr;
-    hipStream_t draw_stream = nullptr;
-    // person ids (hrn_associate_people_dev): the problem table of a call with several problems, then the costs and similarities the
-    // kernel keeps between its phases; on the device, grown on demand, guarded like warp_params against a call on another stream
-    char *assoc_buf = nullptr;
-    size_t assoc_buf_bytes = 0;
-    hipEvent_t assoc_done = nullptr;
-    hipStream_t assoc_stream = nullptr;
-    // the tracking link (hrn_boxes_from_poses, hrn_preprocess_frames_dev): the call's host table on the device (frame sizes per
-    // person; frame table and frame index), grown on demand and guarded like warp_params against a call on another stream
-    char *trk_table = nullptr;
-    size_t trk_table_bytes = 0;
-    hipEvent_t trk_done = nullptr;
-    hipStream_t trk_stream = nullptr;
-    // `bytes` from image `ring` of the pinned staging ring to trk_table; trk_ran() goes behind the launch that reads it
-    bool trk_upload(const char *pinned, unsigned ring, size_t bytes, hipStream_t s) {
-        if (bytes > trk_table_bytes) {
-            if (trk_done && !hip_ok(hipEventSynchronize(trk_done), "hipEventSynchronize")) return false;
-            if (trk_table) (void)hipFree(trk_table);
-            trk_table = nullptr, trk_table_bytes = 0;
-            const size_t cap = std::max<size_t>(bytes * 2, 4096);
-            if (!hip_ok(hipMalloc((void **)&trk_table, cap), "hipMalloc(tracking table)")) return false;
-            trk_table_bytes = cap;
-        }
-        if (trk_done && trk_stream != s && !hip_ok(hipStreamWaitEvent(s, trk_done, 0), "hipStreamWaitEvent")) return false;
-        if (!hip_ok(hipMemcpyAsync(trk_table, pinned, bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync(tracking table)")) return false;
-        return hip_ok(hipEventRecord(pre_landed[ring], s), "hipEventRecord");
-    }
-    bool trk_ran(hipStream_t s) {
-        if (!trk_done && !hip_ok(hipEventCreateWithFlags(&trk_done, hipEventDisableTiming), "hipEventCreate")) return false;
-        trk_stream = s;
-        return hip_ok(hipEventRecord(trk_done, s), "hipEventRecord");
-    }
-    // the pre-path's device scratch for n people: `tmp_bytes` of intermediates, n records (and n YUV sources); growing waits for
-    // whoever still reads the old ones
-    bool pre_reserve(size_t tmp_bytes, int n, bool yuv, hipStream_t s) {
-        if (!(tmp_bytes > pre_tmp_bytes || n > pre_params_cap || (yuv && n > pre_yuv_cap))) return true;
-        if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return false;
-        if (tmp_bytes > pre_tmp_bytes) {
-            if (pre_tmp) (void)hipFree(pre_tmp);
-            pre_tmp = nullptr, pre_tmp_bytes = 0;
-            if (!hip_ok(hipMalloc((void **)&pre_tmp, tmp_bytes), "hipMalloc(pre-path scratch)")) return false;
-            pre_tmp_bytes = tmp_bytes;
-        }
-        if (n > pre_params_cap) {
-            if (pre_params) (void)hipFree(pre_params);
-            pre_params = nullptr, pre_params_cap = 0;
-            if (!hip_ok(hipMalloc((void **)&pre_params, (size_t)n * sizeof(CropParams)), "hipMalloc(crop params)")) return false;
-            pre_params_cap = n;
-        }
-        if (yuv && n > pre_yuv_cap) {
-            if (pre_yuv) (void)hipFree(pre_yuv);
-            pre_yuv = nullptr, pre_yuv_cap = 0;
-            if (!hip_ok(hipMalloc((void **)&pre_yuv, (size_t)n * sizeof(YuvSource)), "hipMalloc(YUV sources)")) return false;
-            pre_yuv_cap = n;
-        }
-        return true;
-    }
     uint64_t map_clock = 0;    // LRU stamp of the block-map slots
     int64_t map_builds = 0;     // block maps built + uploaded since creation (hrn_map_rebuilds)
     float *scratch_hm = nullptr;  // max_batch heat-maps of the handle's own: flip-TTA's mirrored pass, a refined decode the caller gave no maps
@@ -324,34 +163,21 @@ struct hrn_ctx {
 #include "ctx_memory.inc"
 #include "ctx_weights.inc"
 #include "ctx_run.inc"
+#include "ctx_scratch.inc"
 };
 
 // ====================================================================================================
 namespace {
-// pass_enter() .. pass_leave() on EVERY exit: kernels already queued by a pass that failed half-way must be covered by
-// the handle's "pass done" event too, or the next call on another stream could overlap them on the shared workspace
-struct PassScope {
-    hrn_ctx *h;
-    hipStream_t s;
-    bool entered = false, left = false;
-    PassScope(hrn_ctx *h_, hipStream_t s_) : h(h_), s(s_) { entered = h->pass_enter(s); }
-    bool leave() {
-        left = true;
-        return entered && h->pass_leave(s);
-    }
-    ~PassScope() {
-        if (entered && !left) (void)h->pass_leave(s);
-    }
-};
+using CallScope = hrn_ctx::CallScope;
 
-// The loop of every forward entry: the device, then (n > 0) the scratch heat-maps if asked for, one PassScope and
+// The loop of every forward entry: the device, then (n > 0) the scratch heat-maps if asked for, one CallScope on the pass guard and
 // pass(off, nb) for each micro-batch of at most max_batch crops (false: the entry returns 8).
 template <class Pass>
 int each_micro_batch(hrn_ctx *h, int n, bool scratch, hipStream_t s, const Pass &pass) {
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     if (n == 0) return 0;
     if (scratch && !h->scratch_heatmaps()) return 6;
-    PassScope scope(h, s);
+    CallScope scope(h, &h->pass, s);
     if (!scope.entered) return 6;
     for (int off = 0; off < n; off += h->max_batch)
         if (!pass(off, std::min(n - off, h->max_batch))) return 8;
@@ -362,6 +188,31 @@ bool valid_refine(hrn_ctx *h, int refine) {
     if (refine == HRN_REFINE_NONE || refine == HRN_REFINE_QUARTER || refine == HRN_REFINE_DARK) return true;
     h->err = "refine must be HRN_REFINE_NONE, HRN_REFINE_QUARTER or HRN_REFINE_DARK";
     return false;
+}
+
+// what is wrong with a BGR frame somebody is cut from, or nullptr
+const char *bgr_frame_fault(const hrn_frame &f) { return !f.data || f.height <= 0 || f.width <= 0 ? "is null or has no size" : nullptr; }
+
+// The refusals of the four multi-frame pre-path entries, in their order: the arguments first (they need no device, so a
+// plan-only handle judges them too), then the handle; true + err.  `pointers`: everything the entry requires when n > 0 is there.
+template <class Frame>
+bool frame_table_fault(hrn_handle h, const char *entry, int variant, int n, int nframes, int det_stride, bool pointers, const int32_t *fidx,
+                       const Frame *frames, const char *(*frame_fault)(const Frame &)) {
+    const std::string name = entry;
+    std::string why;
+    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) why = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
+    else if (n < 0 || nframes < 0 || det_stride < 4 || (n > 0 && (nframes < 1 || !pointers))) why = "bad frames / detections / n";
+    else if (n > 0 && !fidx && nframes != 1) why = name + ": without frame_index there must be one frame";
+    for (int i = 0; why.empty() && i < n; ++i) {
+        const long f = fidx ? (long)fidx[i] : 0;
+        if (f < 0 || f >= nframes)
+            why = name + ": frame_index " + std::to_string(f) + " of person " + std::to_string(i) + " is outside [0, " + std::to_string(nframes) + ")";
+        else if (const char *fault = frame_fault(frames[f]))
+            why = name + ": frame " + std::to_string(f) + ", which person " + std::to_string(i) + " is cut from, " + fault;
+    }
+    if (why.empty()) return h->refuse_plan_only();
+    h->err = why;
+    return true;
 }
 
 // hrn_forward (HRN_REFINE_NONE) and hrn_forward_refined: one pass per micro-batch, its OP_DECODE launching decode_kernel<refine>
@@ -545,10 +396,7 @@ int hrn_forward_refined(hrn_handle h, const void *images_dev, int n, const void 
 int hrn_refine_coords(hrn_handle h, const float *heatmaps_dev, int n, int refine, float *coords_dev, void *stream) {
     if (!h) return 1;
     if (!valid_refine(h, refine)) return 7;
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
+    if (h->refuse_plan_only()) return 7;
     if (n < 0 || (n > 0 && (!heatmaps_dev || !coords_dev))) {
         h->err = "hrn_refine_coords: bad heatmaps / coords / n";
         return 7;
@@ -558,7 +406,7 @@ int hrn_refine_coords(hrn_handle h, const float *heatmaps_dev, int n, int refine
     DecodeArgs a{};
     a.heatmaps = heatmaps_dev, a.coords = coords_dev;
     a.n = n, a.joints = h->joints, a.h = h->H / 4, a.w = h->W / 4, a.mode = refine;
-    PassScope scope(h, (hipStream_t)stream);
+    CallScope scope(h, &h->pass, (hipStream_t)stream);
     if (!scope.entered) return 6;
     if (!h->hip_ok(launch_refine_coords(a, (hipStream_t)stream), "refine launch")) return 8;
     return scope.leave() ? 0 : 6;
@@ -649,22 +497,20 @@ int preprocess_people(hrn_handle h, const hrn_frame *frames, const hrn_yuv_frame
         tmp_bytes += ((size_t)cp.h_pad * W * 3 + 255) / 256 * 256;
         if (cp.h_pad > max_h_pad) max_h_pad = cp.h_pad;
     }
-    if (!h->pre_reserve(tmp_bytes, n, yframes != nullptr, s)) return 6;
-    if (yframes && !h->hip_ok(hipMemcpyAsync(h->pre_yuv, srcs, (size_t)n * sizeof(YuvSource), hipMemcpyHostToDevice, s),
-                              "hipMemcpyAsync(YUV sources)"))
+    if (!h->pre_reserve(tmp_bytes, n, yframes != nullptr)) return 6;
+    CallScope scope(h, &h->pre_tmp, s);
+    if (!scope.entered) return 6;
+    CropParams *params = h->pre_params.as<CropParams>();
+    YuvSource *yuv = yframes ? h->pre_yuv.as<YuvSource>() : nullptr;
+    if (!h->pre_upload(ring, s, {{yuv, srcs, (size_t)n * sizeof(YuvSource), "hipMemcpyAsync(YUV sources)"},
+                                 {params, cps, (size_t)n * sizeof(CropParams), "hipMemcpyAsync(crop params)"},
+                                 {boxes_dev, boxes, (size_t)n * 16, "hipMemcpyAsync(boxes)"}}))
         return 6;
-    if (!h->hip_ok(hipMemcpyAsync(h->pre_params, cps, (size_t)n * sizeof(CropParams), hipMemcpyHostToDevice, s),
-                   "hipMemcpyAsync(crop params)"))
-        return 6;
-    if (boxes_dev && !h->hip_ok(hipMemcpyAsync(boxes_dev, boxes, (size_t)n * 16, hipMemcpyHostToDevice, s),
-                                "hipMemcpyAsync(boxes)"))
-        return 6;
-    if (!h->hip_ok(hipEventRecord(h->pre_landed[ring], s), "hipEventRecord")) return 6;
     if (boxes_host) memcpy(boxes_host, boxes, (size_t)n * 16);
-    const hipError_t e = yframes ? launch_prepath_yuv(h->pre_params, h->pre_yuv, n, max_h_pad, h->pre_tmp, images_dev, H, W, s)
-                                 : launch_prepath(h->pre_params, n, max_h_pad, h->pre_tmp, images_dev, H, W, s);
+    const hipError_t e = yframes ? launch_prepath_yuv(params, yuv, n, max_h_pad, h->pre_tmp.as<unsigned char>(), images_dev, H, W, s)
+                                 : launch_prepath(params, n, max_h_pad, h->pre_tmp.as<unsigned char>(), images_dev, H, W, s);
     if (!h->hip_ok(e, "pre-path launch")) return 8;
-    return 0;
+    return scope.leave() ? 0 : 6;
 }
 }  // namespace
 
@@ -703,10 +549,7 @@ int hrn_preprocess_frame(hrn_handle h, const uint8_t *frame_dev, int frame_h, in
                          int det_stride, int n, int variant, float *images_dev, int32_t *boxes_host, int32_t *boxes_dev,
                          void *stream) {
     if (!h) return 1;
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
+    if (h->refuse_plan_only()) return 7;
     if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
         h->err = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
         return 7;
@@ -727,35 +570,9 @@ int hrn_preprocess_frames(hrn_handle h, const hrn_frame *frames_host, int nframe
                           const int32_t *frame_index_host, int n, int variant, float *images_dev, int32_t *boxes_host,
                           int32_t *boxes_dev, void *stream) {
     if (!h) return 1;
-    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
-        h->err = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
+    if (frame_table_fault(h, "hrn_preprocess_frames", variant, n, nframes, det_stride,
+                          frames_host && dets_host && images_dev, frame_index_host, frames_host, bgr_frame_fault))
         return 7;
-    }
-    if (n < 0 || nframes < 0 || det_stride < 4 || (n > 0 && (nframes < 1 || !frames_host || !dets_host || !images_dev))) {
-        h->err = "bad frames / detections / n";
-        return 7;
-    }
-    if (n > 0 && !frame_index_host && nframes != 1) {
-        h->err = "hrn_preprocess_frames: without frame_index there must be one frame";
-        return 7;
-    }
-    for (int i = 0; i < n; ++i) {
-        const long f = frame_index_host ? (long)frame_index_host[i] : 0;
-        if (f < 0 || f >= nframes) {
-            h->err = "hrn_preprocess_frames: frame_index " + std::to_string(f) + " of person " + std::to_string(i) + " is outside [0, " +
-                     std::to_string(nframes) + ")";
-            return 7;
-        }
-        if (!frames_host[f].data || frames_host[f].height <= 0 || frames_host[f].width <= 0) {
-            h->err = "hrn_preprocess_frames: frame " + std::to_string(f) + ", which person " + std::to_string(i) +
-                     " is cut from, is null or has no size";
-            return 7;
-        }
-    }
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
     if (n == 0) return 0;
     return preprocess_people(h, frames_host, nullptr, frame_index_host, dets_host, det_stride, n, variant, images_dev, boxes_host,
                              boxes_dev, (hipStream_t)stream);
@@ -776,10 +593,7 @@ int hrn_yuv_to_bgr(hrn_handle h, const hrn_yuv_frame *frame_host, uint8_t *bgr_d
         h->err = std::string("hrn_yuv_to_bgr: the frame ") + fault;
         return 7;
     }
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
+    if (h->refuse_plan_only()) return 7;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     if (!h->hip_ok(launch_yuv_to_bgr(yuv_source(*frame_host), frame_host->height, frame_host->width, bgr_dev, (hipStream_t)stream),
                    "yuv_to_bgr launch"))
@@ -792,35 +606,9 @@ int hrn_preprocess_frames_yuv(hrn_handle h, const hrn_yuv_frame *frames_host, in
                               const int32_t *frame_index_host, int n, int variant, float *images_dev, int32_t *boxes_host,
                               int32_t *boxes_dev, void *stream) {
     if (!h) return 1;
-    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
-        h->err = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
+    if (frame_table_fault(h, "hrn_preprocess_frames_yuv", variant, n, nframes, det_stride,
+                          frames_host && dets_host && images_dev, frame_index_host, frames_host, yuv_frame_fault))
         return 7;
-    }
-    if (n < 0 || nframes < 0 || det_stride < 4 || (n > 0 && (nframes < 1 || !frames_host || !dets_host || !images_dev))) {
-        h->err = "bad frames / detections / n";
-        return 7;
-    }
-    if (n > 0 && !frame_index_host && nframes != 1) {
-        h->err = "hrn_preprocess_frames_yuv: without frame_index there must be one frame";
-        return 7;
-    }
-    for (int i = 0; i < n; ++i) {
-        const long f = frame_index_host ? (long)frame_index_host[i] : 0;
-        if (f < 0 || f >= nframes) {
-            h->err = "hrn_preprocess_frames_yuv: frame_index " + std::to_string(f) + " of person " + std::to_string(i) +
-                     " is outside [0, " + std::to_string(nframes) + ")";
-            return 7;
-        }
-        if (const char *fault = yuv_frame_fault(frames_host[f])) {
-            h->err = "hrn_preprocess_frames_yuv: frame " + std::to_string(f) + ", which person " + std::to_string(i) + " is cut from, " +
-                     fault;
-            return 7;
-        }
-    }
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
     if (n == 0) return 0;
     return preprocess_people(h, nullptr, frames_host, frame_index_host, dets_host, det_stride, n, variant, images_dev, boxes_host,
                              boxes_dev, (hipStream_t)stream);
@@ -870,13 +658,19 @@ int preprocess_people_dev(hrn_handle h, const hrn_frame *frames, const hrn_yuv_f
         rows = std::max(rows, crop_hcap(frame_h, frame_w, H, W));
     }
     const size_t slot = ((size_t)rows * W * 3 + 255) / 256 * 256;
-    if (!h->pre_reserve((size_t)n * slot, n, yframes != nullptr, s)) return 6;
+    // (fidx) the frame table and everybody's entry of it
+    const size_t table_bytes = fidx ? (size_t)nframes * sizeof(TrackFrame) : 0, need = fidx ? table_bytes + (size_t)n * sizeof(int32_t) : 0;
+    if (!h->pre_reserve((size_t)n * slot, n, yframes != nullptr) || !h->table_reserve(h->trk_table, need, 4096, "hipMalloc(tracking table)"))
+        return 6;
+    CallScope scope(h, &h->pre_tmp, s), table(h, fidx ? &h->trk_table : nullptr, s);   // (the table's is left behind the launch that reads it)
+    if (!scope.entered || !table.entered) return 6;
+    CropParams *params = h->pre_params.as<CropParams>();
+    YuvSource *yuv = h->pre_yuv.as<YuvSource>();
     CropRecordArgs a{};
     a.dets = dets_dev, a.det_stride = det_stride, a.n = n, a.H = H, a.W = W, a.variant = variant, a.yuv = yframes ? 1 : 0;
     a.slot_bytes = (long long)slot;
-    a.crops = h->pre_params, a.srcs = h->pre_yuv, a.boxes = boxes_dev, a.status = status_dev;
-    if (fidx) {   // the table and everybody's entry of it, through the pinned ring
-        const size_t table_bytes = (size_t)nframes * sizeof(TrackFrame), need = table_bytes + (size_t)n * sizeof(int32_t);
+    a.crops = params, a.srcs = yuv, a.boxes = boxes_dev, a.status = status_dev;
+    if (fidx) {   // through the pinned ring
         unsigned ring = 0;
         char *pin = h->pre_stage(need, &ring);
         if (!pin) return 6;
@@ -884,17 +678,17 @@ int preprocess_people_dev(hrn_handle h, const hrn_frame *frames, const hrn_yuv_f
         for (int i = 0; i < n; ++i) used[fidx[i]] = 1;
         for (int f = 0; f < nframes; ++f) ((TrackFrame *)pin)[f] = used[f] ? entry(f) : TrackFrame{};
         memcpy(pin + table_bytes, fidx, (size_t)n * sizeof(int32_t));
-        if (!h->trk_upload(pin, ring, need, s)) return 6;
-        a.frames = (const TrackFrame *)h->trk_table, a.frame_index = (const int *)(h->trk_table + table_bytes);
+        if (!h->pre_upload(ring, s, {{h->trk_table.ptr, pin, need, "hipMemcpyAsync(tracking table)"}})) return 6;
+        a.frames = h->trk_table.as<const TrackFrame>(), a.frame_index = (const int *)(h->trk_table.ptr + table_bytes);
     } else {
         a.frame0 = entry(0);
     }
     if (!h->hip_ok(launch_crop_records(a, s), "crop records launch")) return 8;
-    if (fidx && !h->trk_ran(s)) return 6;
-    const hipError_t e = yframes ? launch_prepath_yuv(h->pre_params, h->pre_yuv, n, (int)rows, h->pre_tmp, images_dev, H, W, s)
-                                 : launch_prepath(h->pre_params, n, (int)rows, h->pre_tmp, images_dev, H, W, s);
+    if (!table.leave()) return 6;
+    const hipError_t e = yframes ? launch_prepath_yuv(params, yuv, n, (int)rows, h->pre_tmp.as<unsigned char>(), images_dev, H, W, s)
+                                 : launch_prepath(params, n, (int)rows, h->pre_tmp.as<unsigned char>(), images_dev, H, W, s);
     if (!h->hip_ok(e, "pre-path launch")) return 8;
-    return 0;
+    return scope.leave() ? 0 : 6;
 }
 }  // namespace
 
@@ -918,30 +712,29 @@ int hrn_boxes_from_poses(hrn_handle h, const float *pts_dev, int n, int J, const
         h->err = "hrn_boxes_from_poses: " + fault;
         return 7;
     }
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
+    if (h->refuse_plan_only()) return 7;
     if (n == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
     PoseBoxArgs a{};
     a.pts = pts_dev, a.n = n, a.J = J, a.threshold = threshold, a.min_joints = min_joints, a.scale = scale, a.min_side = min_side;
     a.dets = dets_dev;
-    if (per_person_hw) {   // a frame size per person: through the pinned ring
-        const size_t need = (size_t)n * 2 * sizeof(int32_t);
+    const size_t need = per_person_hw ? (size_t)n * 2 * sizeof(int32_t) : 0;   // a frame size per person: a table through the pinned ring
+    if (!h->table_reserve(h->trk_table, need, 4096, "hipMalloc(tracking table)")) return 6;
+    CallScope scope(h, per_person_hw ? &h->trk_table : nullptr, s);
+    if (!scope.entered) return 6;
+    if (per_person_hw) {
         unsigned ring = 0;
         char *pin = h->pre_stage(need, &ring);
         if (!pin) return 6;
         memcpy(pin, frame_hw_host, need);
-        if (!h->trk_upload(pin, ring, need, s)) return 6;
-        a.frame_hw = (const int *)h->trk_table;
+        if (!h->pre_upload(ring, s, {{h->trk_table.ptr, pin, need, "hipMemcpyAsync(tracking table)"}})) return 6;
+        a.frame_hw = h->trk_table.as<const int>();
     } else {
         a.frame_h = frame_hw_host[0], a.frame_w = frame_hw_host[1];
     }
     if (!h->hip_ok(launch_pose_boxes(a, s), "pose boxes launch")) return 8;
-    if (per_person_hw && !h->trk_ran(s)) return 6;
-    return 0;
+    return scope.leave() ? 0 : 6;
 }
 
 // hrn_preprocess_frames with the detections on the device: its argument checks and texts (minus the per-detection ones, which
@@ -950,36 +743,9 @@ int hrn_preprocess_frames_dev(hrn_handle h, const hrn_frame *frames_host, int nf
                               const int32_t *frame_index_host, int n, int variant, float *images_dev, int32_t *boxes_dev,
                               int32_t *status_dev, void *stream) {
     if (!h) return 1;
-    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
-        h->err = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
+    if (frame_table_fault(h, "hrn_preprocess_frames_dev", variant, n, nframes, det_stride,
+                          frames_host && dets_dev && images_dev && boxes_dev && status_dev, frame_index_host, frames_host, bgr_frame_fault))
         return 7;
-    }
-    if (n < 0 || nframes < 0 || det_stride < 4 ||
-        (n > 0 && (nframes < 1 || !frames_host || !dets_dev || !images_dev || !boxes_dev || !status_dev))) {
-        h->err = "bad frames / detections / n";
-        return 7;
-    }
-    if (n > 0 && !frame_index_host && nframes != 1) {
-        h->err = "hrn_preprocess_frames_dev: without frame_index there must be one frame";
-        return 7;
-    }
-    for (int i = 0; i < n; ++i) {
-        const long f = frame_index_host ? (long)frame_index_host[i] : 0;
-        if (f < 0 || f >= nframes) {
-            h->err = "hrn_preprocess_frames_dev: frame_index " + std::to_string(f) + " of person " + std::to_string(i) + " is outside [0, " +
-                     std::to_string(nframes) + ")";
-            return 7;
-        }
-        if (!frames_host[f].data || frames_host[f].height <= 0 || frames_host[f].width <= 0) {
-            h->err = "hrn_preprocess_frames_dev: frame " + std::to_string(f) + ", which person " + std::to_string(i) +
-                     " is cut from, is null or has no size";
-            return 7;
-        }
-    }
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
     if (n == 0) return 0;
     return preprocess_people_dev(h, frames_host, nullptr, nframes, frame_index_host, dets_dev, det_stride, n, variant, images_dev,
                                  boxes_dev, status_dev, (hipStream_t)stream);
@@ -989,36 +755,9 @@ int hrn_preprocess_frames_yuv_dev(hrn_handle h, const hrn_yuv_frame *frames_host
                                   const int32_t *frame_index_host, int n, int variant, float *images_dev, int32_t *boxes_dev,
                                   int32_t *status_dev, void *stream) {
     if (!h) return 1;
-    if (variant != HRN_CROP_PAD && variant != HRN_CROP_CLAMP) {
-        h->err = "variant must be HRN_CROP_PAD or HRN_CROP_CLAMP";
+    if (frame_table_fault(h, "hrn_preprocess_frames_yuv_dev", variant, n, nframes, det_stride,
+                          frames_host && dets_dev && images_dev && boxes_dev && status_dev, frame_index_host, frames_host, yuv_frame_fault))
         return 7;
-    }
-    if (n < 0 || nframes < 0 || det_stride < 4 ||
-        (n > 0 && (nframes < 1 || !frames_host || !dets_dev || !images_dev || !boxes_dev || !status_dev))) {
-        h->err = "bad frames / detections / n";
-        return 7;
-    }
-    if (n > 0 && !frame_index_host && nframes != 1) {
-        h->err = "hrn_preprocess_frames_yuv_dev: without frame_index there must be one frame";
-        return 7;
-    }
-    for (int i = 0; i < n; ++i) {
-        const long f = frame_index_host ? (long)frame_index_host[i] : 0;
-        if (f < 0 || f >= nframes) {
-            h->err = "hrn_preprocess_frames_yuv_dev: frame_index " + std::to_string(f) + " of person " + std::to_string(i) +
-                     " is outside [0, " + std::to_string(nframes) + ")";
-            return 7;
-        }
-        if (const char *fault = yuv_frame_fault(frames_host[f])) {
-            h->err = "hrn_preprocess_frames_yuv_dev: frame " + std::to_string(f) + ", which person " + std::to_string(i) +
-                     " is cut from, " + fault;
-            return 7;
-        }
-    }
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
     if (n == 0) return 0;
     return preprocess_people_dev(h, nullptr, frames_host, nframes, frame_index_host, dets_dev, det_stride, n, variant, images_dev,
                                  boxes_dev, status_dev, (hipStream_t)stream);
@@ -1114,10 +853,7 @@ int draw_poses(const char *entry, hrn_handle h, const hrn_canvas *canvases_host,
             return fail("canvases " + std::to_string(seen.first->second) + " and " + std::to_string(f) +
                         " name the same buffer: the canvases of a call must not overlap");
     }
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
+    if (h->refuse_plan_only()) return 7;
     if (n == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
@@ -1166,44 +902,25 @@ int draw_poses(const char *entry, hrn_handle h, const hrn_canvas *canvases_host,
 
     const size_t off_live = align16((size_t)n * J * sizeof(short2)), off_box = off_live + align16((size_t)n * (kMaxJoints / 32) * 4),
                  rec_bytes = off_box + (size_t)n * sizeof(int4);
-    if (table_bytes > h->draw_table_bytes || rec_bytes > h->draw_records_bytes) {   // grow: wait for whoever still reads the old ones
-        if (h->draw_done && !h->hip_ok(hipEventSynchronize(h->draw_done), "hipEventSynchronize")) return 6;
-        if (table_bytes > h->draw_table_bytes) {
-            if (h->draw_table) (void)hipFree(h->draw_table);
-            h->draw_table = nullptr, h->draw_table_bytes = 0;
-            const size_t cap = std::max<size_t>(table_bytes * 2, 4096);
-            if (!h->hip_ok(hipMalloc((void **)&h->draw_table, cap), "hipMalloc(draw table)")) return 6;
-            h->draw_table_bytes = cap;
-        }
-        if (rec_bytes > h->draw_records_bytes) {
-            if (h->draw_records) (void)hipFree(h->draw_records);
-            h->draw_records = nullptr, h->draw_records_bytes = 0;
-            const size_t cap = std::max<size_t>(rec_bytes * 2, 4096);
-            if (!h->hip_ok(hipMalloc((void **)&h->draw_records, cap), "hipMalloc(draw records)")) return 6;
-            h->draw_records_bytes = cap;
-        }
-    }
-    if (h->draw_done && h->draw_stream != s && !h->hip_ok(hipStreamWaitEvent(s, h->draw_done, 0), "hipStreamWaitEvent")) return 6;
-    if (!h->draw_done && !h->hip_ok(hipEventCreateWithFlags(&h->draw_done, hipEventDisableTiming), "hipEventCreate")) return 6;
-    if (!h->hip_ok(hipMemcpyAsync(h->draw_table, pin, table_bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync(draw table)")) return 6;
-    if (!h->hip_ok(hipEventRecord(h->pre_landed[ring], s), "hipEventRecord")) return 6;
-    if (ids_on_device && !h->hip_ok(launch_bone_ids(person_index_dev, n, (const unsigned *)(h->draw_table + off_palette), Cb,
-                                                    (unsigned *)(h->draw_table + off_bone), s), "bone colour launch")) {
-        h->draw_stream = s;   // (the table copy is in flight on s: a later call on another stream waits for it)
-        (void)hipEventRecord(h->draw_done, s);
+    if (!h->table_reserve(h->draw_table, table_bytes, 4096, "hipMalloc(draw table)") ||
+        !h->table_reserve(h->draw_records, rec_bytes, 4096, "hipMalloc(draw records)", &h->draw_table))
+        return 6;
+    CallScope scope(h, &h->draw_table, s);
+    if (!scope.entered) return 6;
+    char *table = h->draw_table.ptr, *records = h->draw_records.ptr;
+    if (!h->pre_upload(ring, s, {{table, pin, table_bytes, "hipMemcpyAsync(draw table)"}})) return 6;
+    if (ids_on_device && !h->hip_ok(launch_bone_ids(person_index_dev, n, (const unsigned *)(table + off_palette), Cb,
+                                                    (unsigned *)(table + off_bone), s), "bone colour launch"))
         return 8;
-    }
     DrawArgs a{};
     a.pts = pts_dev, a.n = n, a.J = J, a.K = K, a.Cp = Cp, a.nframes = used, a.total_tiles = tiles, a.thickness = thickness;
     a.threshold = threshold;
-    a.frames = (const DrawFrame *)h->draw_table, a.order = (const int *)(h->draw_table + off_order);
-    a.person_frame = (const int *)(h->draw_table + off_pframe), a.bone_colour = (const unsigned *)(h->draw_table + off_bone);
-    a.point_colour = (const unsigned *)(h->draw_table + off_point), a.skeleton = (const unsigned *)(h->draw_table + off_skel);
-    a.xy = (short2 *)h->draw_records, a.live = (unsigned *)(h->draw_records + off_live), a.box = (int4 *)(h->draw_records + off_box);
-    const hipError_t e = launch_draw(a, s);
-    h->draw_stream = s;
-    if (!h->hip_ok(hipEventRecord(h->draw_done, s), "hipEventRecord")) return 6;
-    return h->hip_ok(e, "draw launch") ? 0 : 8;
+    a.frames = (const DrawFrame *)table, a.order = (const int *)(table + off_order);
+    a.person_frame = (const int *)(table + off_pframe), a.bone_colour = (const unsigned *)(table + off_bone);
+    a.point_colour = (const unsigned *)(table + off_point), a.skeleton = (const unsigned *)(table + off_skel);
+    a.xy = (short2 *)records, a.live = (unsigned *)(records + off_live), a.box = (int4 *)(records + off_box);
+    if (!h->hip_ok(launch_draw(a, s), "draw launch")) return 8;
+    return scope.leave() ? 0 : 6;
 }
 }  // namespace
 
@@ -1236,10 +953,7 @@ int hrn_associate_people_dev(hrn_handle h, int P, const int32_t *cur_start_host,
         h->err = std::string("hrn_associate_people_dev: ") + fault;
         return 7;
     }
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
+    if (h->refuse_plan_only()) return 7;
     if (P == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
@@ -1254,16 +968,9 @@ int hrn_associate_people_dev(hrn_handle h, int P, const int32_t *cur_start_host,
         q.scratch = (long long)need;
         need += ((size_t)q.n * q.m * 12 + 15) / 16 * 16;
     }
-    if (need > h->assoc_buf_bytes) {   // grow: wait for whoever still uses the old one
-        if (h->assoc_done && !h->hip_ok(hipEventSynchronize(h->assoc_done), "hipEventSynchronize")) return 6;
-        if (h->assoc_buf) (void)hipFree(h->assoc_buf);
-        h->assoc_buf = nullptr, h->assoc_buf_bytes = 0;
-        const size_t cap = std::max<size_t>(need * 2, 65536);
-        if (!h->hip_ok(hipMalloc((void **)&h->assoc_buf, cap), "hipMalloc(association scratch)")) return 6;
-        h->assoc_buf_bytes = cap;
-    }
-    if (h->assoc_done && h->assoc_stream != s && !h->hip_ok(hipStreamWaitEvent(s, h->assoc_done, 0), "hipStreamWaitEvent")) return 6;
-    if (!h->assoc_done && !h->hip_ok(hipEventCreateWithFlags(&h->assoc_done, hipEventDisableTiming), "hipEventCreate")) return 6;
+    if (!h->table_reserve(h->assoc_buf, need, 65536, "hipMalloc(association scratch)")) return 6;
+    CallScope scope(h, &h->assoc_buf, s);
+    if (!scope.entered) return 6;
     AssocArgs a{};
     a.P = P, a.J = J, a.no_assign = h->assoc_no_assign ? 1 : 0;
     if (P > 1) {   // the table through the pinned ring
@@ -1271,30 +978,22 @@ int hrn_associate_people_dev(hrn_handle h, int P, const int32_t *cur_start_host,
         char *pin = h->pre_stage(table_bytes, &ring);
         if (!pin) return 6;
         memcpy(pin, probs.data(), (size_t)P * sizeof(AssocProblem));
-        if (!h->hip_ok(hipMemcpyAsync(h->assoc_buf, pin, (size_t)P * sizeof(AssocProblem), hipMemcpyHostToDevice, s),
-                       "hipMemcpyAsync(association table)"))
-            return 6;
-        if (!h->hip_ok(hipEventRecord(h->pre_landed[ring], s), "hipEventRecord")) return 6;
-        a.table = (const AssocProblem *)h->assoc_buf;
+        if (!h->pre_upload(ring, s, {{h->assoc_buf.ptr, pin, (size_t)P * sizeof(AssocProblem), "hipMemcpyAsync(association table)"}})) return 6;
+        a.table = h->assoc_buf.as<const AssocProblem>();
     } else {
         a.one = probs[0];
     }
     a.boxes = boxes_dev, a.pts = pts_dev, a.prev_boxes = prev_boxes_dev, a.prev_pts = prev_pts_dev, a.prev_ids = prev_ids_dev;
     a.next_id = next_id_dev, a.pose_alpha = pose_alpha, a.similarity_threshold = similarity_threshold, a.smoothing_alpha = smoothing_alpha;
-    a.ids = ids_dev, a.match = match_dev, a.status = status_dev, a.scratch = h->assoc_buf;
-    const hipError_t e = launch_assoc(a, s);
-    h->assoc_stream = s;
-    if (!h->hip_ok(hipEventRecord(h->assoc_done, s), "hipEventRecord")) return 6;
-    return h->hip_ok(e, "association launch") ? 0 : 8;
+    a.ids = ids_dev, a.match = match_dev, a.status = status_dev, a.scratch = h->assoc_buf.ptr;
+    if (!h->hip_ok(launch_assoc(a, s), "association launch")) return 8;
+    return scope.leave() ? 0 : 6;
 }
 
 int hrn_resize_frames(hrn_handle h, const uint8_t *frames_dev, int n, int frame_h, int frame_w, int interpolation,
                       float *images_dev, void *stream) {
     if (!h) return 1;
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
+    if (h->refuse_plan_only()) return 7;
     if (interpolation != HRN_INTER_NEAREST && interpolation != HRN_INTER_LINEAR && interpolation != HRN_INTER_CUBIC) {
         h->err = "interpolation must be HRN_INTER_NEAREST (0), HRN_INTER_LINEAR (1) or HRN_INTER_CUBIC (2)";
         return 7;
@@ -1307,24 +1006,14 @@ int hrn_resize_frames(hrn_handle h, const uint8_t *frames_dev, int n, int frame_
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
     const int H = h->H, W = h->W;
-    if (W + H > h->rs_taps_cap) {
-        if (h->rs_taps) {
-            if (!h->hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return 6;
-            (void)hipFree(h->rs_taps);
-            h->rs_taps = nullptr, h->rs_taps_cap = 0;
-        }
-        if (!h->hip_ok(hipMalloc((void **)&h->rs_taps, (size_t)(W + H) * sizeof(ResizeTaps)), "hipMalloc(resize taps)")) return 6;
-        h->rs_taps_cap = W + H;
-    }
-    // the one tap table of the handle is rewritten by every call: a call on another stream than the previous one waits until
-    // that one's kernels have read it (same stream: ordered anyway)
-    if (h->rs_done && h->rs_stream != s && !h->hip_ok(hipStreamWaitEvent(s, h->rs_done, 0), "hipStreamWaitEvent")) return 6;
-    if (!h->rs_done && !h->hip_ok(hipEventCreateWithFlags(&h->rs_done, hipEventDisableTiming), "hipEventCreate")) return 6;
-    if (!h->hip_ok(launch_resize_frames(frames_dev, n, frame_h, frame_w, interpolation, h->rs_taps, images_dev, H, W, s), "resize launch"))
+    const size_t taps_bytes = (size_t)(W + H) * sizeof(ResizeTaps);   // the one tap table of the handle, rewritten by every call
+    if (!h->rs_taps.reserve(h, taps_bytes, taps_bytes, "hipMalloc(resize taps)")) return 6;
+    CallScope scope(h, &h->rs_taps, s);
+    if (!scope.entered) return 6;
+    if (!h->hip_ok(launch_resize_frames(frames_dev, n, frame_h, frame_w, interpolation, h->rs_taps.as<ResizeTaps>(), images_dev, H, W, s),
+                   "resize launch"))
         return 8;
-    h->rs_stream = s;
-    if (!h->hip_ok(hipEventRecord(h->rs_done, s), "hipEventRecord")) return 6;
-    return 0;
+    return scope.leave() ? 0 : 6;
 }
 
 namespace {
@@ -1355,10 +1044,7 @@ bool invert_affine(const double *fwd, double *M) {
 int hrn_warp_crops(hrn_handle h, const uint8_t *frames_dev, int nframes, int frame_h, int frame_w, const int32_t *frame_index_host,
                    const double *matrices_host, int n, float *images_dev, void *stream) {
     if (!h) return 1;
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
+    if (h->refuse_plan_only()) return 7;
     if (n < 0 || nframes < 0 || frame_h <= 0 || frame_w <= 0 || (n > 0 && (nframes < 1 || !frames_dev || !matrices_host || !images_dev))) {
         h->err = "bad frames / matrices / n";
         return 7;
@@ -1403,23 +1089,14 @@ int hrn_warp_crops(hrn_handle h, const uint8_t *frames_dev, int nframes, int fra
         }
     }
     hipStream_t s = (hipStream_t)stream;
-    if (n > h->warp_params_cap) {   // grow: wait for whoever still reads the old array
-        if (h->warp_done && !h->hip_ok(hipEventSynchronize(h->warp_done), "hipEventSynchronize")) return 6;
-        if (h->warp_params) (void)hipFree(h->warp_params);
-        h->warp_params = nullptr, h->warp_params_cap = 0;
-        const int cap = std::max(n, 256);
-        if (!h->hip_ok(hipMalloc((void **)&h->warp_params, (size_t)cap * sizeof(WarpParams)), "hipMalloc(warp params)")) return 6;
-        h->warp_params_cap = cap;
-    }
-    if (h->warp_done && h->warp_stream != s && !h->hip_ok(hipStreamWaitEvent(s, h->warp_done, 0), "hipStreamWaitEvent")) return 6;
-    if (!h->warp_done && !h->hip_ok(hipEventCreateWithFlags(&h->warp_done, hipEventDisableTiming), "hipEventCreate")) return 6;
-    if (!h->hip_ok(hipMemcpyAsync(h->warp_params, wp, (size_t)n * sizeof(WarpParams), hipMemcpyHostToDevice, s), "hipMemcpyAsync(warp params)"))
-        return 6;
-    if (!h->hip_ok(hipEventRecord(h->pre_landed[ring], s), "hipEventRecord")) return 6;
-    const hipError_t e = launch_warp_crops(frames_dev, frame_h, frame_w, h->warp_params, n, images_dev, H, W, s);
-    h->warp_stream = s;
-    if (!h->hip_ok(hipEventRecord(h->warp_done, s), "hipEventRecord")) return 6;
-    return h->hip_ok(e, "warp launch") ? 0 : 8;
+    const size_t bytes = (size_t)n * sizeof(WarpParams);
+    if (!h->warp_params.reserve(h, bytes, std::max(n, 256) * sizeof(WarpParams), "hipMalloc(warp params)")) return 6;
+    CallScope scope(h, &h->warp_params, s);
+    if (!scope.entered) return 6;
+    if (!h->pre_upload(ring, s, {{h->warp_params.ptr, wp, bytes, "hipMemcpyAsync(warp params)"}})) return 6;
+    if (!h->hip_ok(launch_warp_crops(frames_dev, frame_h, frame_w, h->warp_params.as<WarpParams>(), n, images_dev, H, W, s), "warp launch"))
+        return 8;
+    return scope.leave() ? 0 : 6;
 }
 
 extern "C++" {
@@ -1470,10 +1147,7 @@ int hrn_target_centers(const double *joints, const float *vis, const float *join
 int hrn_generate_targets(hrn_handle h, const double *joints_host, const float *vis_host, const float *joints_weight_host, int n,
                          double sigma, float *targets_dev, float *target_weight_host, void *stream) {
     if (!h) return 1;
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
+    if (h->refuse_plan_only()) return 7;
     if (n < 0 || (n > 0 && !targets_dev) || ((uintptr_t)targets_dev & 15)) {
         h->err = "hrn_generate_targets: bad targets / n (targets must be 16-byte aligned)";
         return 7;
@@ -1495,11 +1169,13 @@ int hrn_generate_targets(hrn_handle h, const double *joints_host, const float *v
     a.table = h->score_table(a.t, sigma);
     if (!a.table) return 6;
     hipStream_t s = (hipStream_t)stream;
-    if (!h->score_upload(recs, ring, count, s)) return 6;
-    a.joints = h->score_joints, a.n = n, a.J = h->joints, a.h = h->H / 4, a.w = h->W / 4;
-    const hipError_t e = launch_targets(a, targets_dev, s);
-    if (!h->score_ran(s)) return 6;
-    return h->hip_ok(e, "targets launch") ? 0 : 8;
+    const size_t bytes = (size_t)count * sizeof(ScoreJoint);
+    if (!h->score_joints.reserve(h, bytes, (size_t)std::max<int64_t>(count, 256 * 17) * sizeof(ScoreJoint), "hipMalloc(score records)")) return 6;
+    CallScope scope(h, &h->score_joints, s);
+    if (!scope.entered || !h->pre_upload(ring, s, {{h->score_joints.ptr, recs, bytes, "hipMemcpyAsync(score records)"}})) return 6;
+    a.joints = h->score_joints.as<ScoreJoint>(), a.n = n, a.J = h->joints, a.h = h->H / 4, a.w = h->W / 4;
+    if (!h->hip_ok(launch_targets(a, targets_dev, s), "targets launch")) return 8;
+    return scope.leave() ? 0 : 6;
 }
 
 // testing/Test.py:141-157: loss_fn(output, target, target_weight) and evaluate_pck_accuracy(output, target) of one batch.
@@ -1507,10 +1183,7 @@ int hrn_score_heatmaps(hrn_handle h, const float *heatmaps_dev, int n, const flo
                        const float *vis_host, const float *joints_weight_host, double sigma, const float *target_weight_host,
                        float pck_thr, int ohkm_topk, const hrn_score_out *out_dev, void *stream) {
     if (!h) return 1;
-    if (h->plan_only) {
-        h->err = "plan-only handle (device_id < 0): there is no CPU compute path";
-        return 7;
-    }
+    if (h->refuse_plan_only()) return 7;
     if (n < 0 || (n > 0 && !heatmaps_dev)) {
         h->err = "hrn_score_heatmaps: bad heatmaps / n";
         return 7;
@@ -1562,16 +1235,17 @@ int hrn_score_heatmaps(hrn_handle h, const float *heatmaps_dev, int n, const flo
         for (int64_t k = 0; k < count; ++k) recs[k] = ScoreJoint{0, 0, target_weight_host[k], 0};
     }
     hipStream_t s = (hipStream_t)stream;
-    if (count > 0 && !h->score_upload(recs, ring, count, s)) return 6;
-    if (!h->score_done && !h->hip_ok(hipEventCreateWithFlags(&h->score_done, hipEventDisableTiming), "hipEventCreate")) return 6;
-    a.heatmaps = heatmaps_dev, a.targets = targets_dev, a.joints = h->score_joints;
+    const size_t bytes = (size_t)count * sizeof(ScoreJoint);
+    if (!h->score_joints.reserve(h, bytes, (size_t)std::max<int64_t>(count, 256 * 17) * sizeof(ScoreJoint), "hipMalloc(score records)")) return 6;
+    CallScope scope(h, &h->score_joints, s);
+    if (!scope.entered || (count > 0 && !h->pre_upload(ring, s, {{h->score_joints.ptr, recs, bytes, "hipMemcpyAsync(score records)"}}))) return 6;
+    a.heatmaps = heatmaps_dev, a.targets = targets_dev, a.joints = h->score_joints.as<ScoreJoint>();
     a.n = n, a.J = h->joints, a.h = h->H / 4, a.w = h->W / 4;
     a.map_loss = out_dev->map_loss, a.preds = out_dev->preds, a.target_preds = out_dev->target_preds, a.maxvals = out_dev->maxvals;
     a.loss_mse = out_dev->loss_mse, a.loss_ohkm = out_dev->loss_ohkm, a.avg_acc = out_dev->avg_acc, a.acc = out_dev->acc;
     a.dists = out_dev->dists, a.cnt = out_dev->cnt, a.pck_thr = pck_thr, a.ohkm_topk = ohkm_topk;
-    const hipError_t e = launch_score(a, s);
-    if (!h->score_ran(s)) return 6;
-    return h->hip_ok(e, "score launch") ? 0 : 8;
+    if (!h->hip_ok(launch_score(a, s), "score launch")) return 8;
+    return scope.leave() ? 0 : 6;
 }
 
 // Debug tap: one micro-batch with the named tensor copied out right after the launch that completes it.
@@ -1609,7 +1283,7 @@ int hrn_forward_tap(hrn_handle h, const void *images_dev, int n, const char *tap
     }
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     const TapReq req{tp->op, tp->tensor, crop0, ncrops, crop_step, dst_dev};
-    PassScope scope(h, (hipStream_t)stream);
+    CallScope scope(h, &h->pass, (hipStream_t)stream);
     if (!scope.entered) return 6;
     if (!h->run_pass((const float *)images_dev, n, nullptr, 0, nullptr, heatmaps_dev, (hipStream_t)stream, nullptr, 0, &req)) return 8;
     return scope.leave() ? 0 : 6;
@@ -1739,7 +1413,7 @@ int hrn_profile_pass(hrn_handle h, const void *images_dev, int n, float *conv_ms
     tm.ev.resize(h->ops.size() + 1);
     for (auto &e : tm.ev)
         if (!h->hip_ok(hipEventCreate(&e), "hipEventCreate")) return 6;
-    PassScope scope(h, (hipStream_t)stream);
+    CallScope scope(h, &h->pass, (hipStream_t)stream);
     bool ok = scope.entered && h->run_pass((const float *)images_dev, n, nullptr, 0, nullptr, nullptr, (hipStream_t)stream, &tm) && scope.leave();
     ok = ok && h->hip_ok(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
     if (ok) {
