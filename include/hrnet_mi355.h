@@ -330,6 +330,60 @@ int hrn_assoc_exp(const double *x, int n, double *out);
 int hrn_associate_similarity(const int32_t *boxes, const float *pts, int n, const int32_t *prev_boxes, const float *prev_pts, int m, int J,
                              double pose_alpha, double *cost_out /* (n,m) */, float *sim_out /* (n,m) */);
 
+/* ---- pose NMS: rescoring and OKS non-maximum suppression per image or stream, on the host and on the device ----
+ * What the evaluation does after the last batch (datasets/COCO.py:353-382: every person's score becomes box score times the mean
+ * confidence of its joints above in_vis_thre, then oks_nms or soft_oks_nms per image, misc/nms/nms.py:75-177), and what a video
+ * loop needs between two detector runs, when two tracks have drifted onto one body.  Both entries solve P independent problems:
+ * problem p has the people [start[p], start[p + 1]) of the arrays below.  The arithmetic is csrc/pose_nms_math.h's, one text for
+ * both entries (its header states every expression and its rounding); in short:
+ *   layout     flags & HRN_POSE_NMS_ENGINE: kpts = pts (n, J, 3) float32 (y, x, confidence), areas = boxes (n, 4) int32 with area
+ *              (x2 - x1) * (y2 - y1) in fp64, scores = det_scores (n) float32 or NULL = 1.0 -- what hrn_forward and the tracking
+ *              link write.  Otherwise the COCO layout, hrn_oks_nms's: kpts (n, J, 3) float64 (x, y, score), areas (n) float64,
+ *              scores (n) float64.  Every value is widened exactly to fp64 before any arithmetic.
+ *   rescoring  rescore_thre NaN: off.  Else score = mean of the confidences > rescore_thre (sequential fp64 sum in joint order;
+ *              0 when there is none) * score.
+ *   order      descending score, STABLE: equal scores keep index order; NaN scores come last, in index order, and set status bit 0
+ *              (a definition of this library: numpy's argsort()[::-1] is not stable)
+ *   OKS        of a candidate d against a kept person g: e_j = (dx^2 + dy^2) / (2 sigma_j)^2 / ((a_g + a_d) / 2 + spacing(1)) / 2;
+ *              mean of exp(-e_j) over the joints with c_d > in_vis_thre (the CANDIDATE's mask only, the reference's quirk; NaN: all
+ *              joints) in numpy's pairwise summation order; 0.0 without any; exp is assoc_math.h's (at most 1 ulp from libm's).
+ *              sigmas: J fp64 values, or NULL for COCO's 17 (then J must be 17).  A non-finite OKS counts as 0 (status bit 1).
+ *   hard       walk the order; a person still alive is kept and removes every later alive person with OKS > thresh
+ *   soft       flags & HRN_POSE_NMS_SOFT: at most 20 are kept; after each pick every remaining score becomes
+ *              s * exp(-(o * o) / thresh) and the rest is re-ordered (descending, equal scores keeping their positions)
+ *   suppress   flags & HRN_POSE_NMS_SUPPRESS (engine layout only): every person who is not kept gets all J confidences and all
+ *              four box values set to 0 -- what the tracking link gives a lost person, so hrn_draw_poses skips it and the next
+ *              hrn_boxes_from_poses reports it lost.  Nothing else of kpts / areas is written.
+ * Outputs, indices counted from the problem's first person:
+ *   keep        n int32: each problem's segment holds its kept people in selection order, then -1
+ *   num         P int32: how many were kept          scores_out  n fp64: the scores after rescoring
+ *   suppressor  n int32: -1 kept; hard: the kept person that removed it; soft: -2 for the people left over at the cap of 20
+ *   status      P int32: bit 0 a NaN score was ordered last; bit 1 a non-finite OKS was counted as 0
+ * At most HRN_MAX_TRACKED people per problem, J in [1, HRN_MAX_JOINTS]; start holds P + 1 non-decreasing int32 on the HOST in both
+ * entries.  Argument errors are code 7, judged before anything is written: null tables, a decreasing segment table, more people
+ * or joints than that, non-finite thresh, thresh <= 0 with soft NMS, J != 17 without sigmas, suppress in the COCO layout, unknown
+ * flag bits; hrn_pose_nms_last_error() (per thread) / hrn_last_error(h) names the cause.
+ * hrn_pose_nms is the host form: no handle, no GPU.  hrn_pose_nms_dev has every array except the segment table in device memory
+ * (sigmas included): ONE launch, one 256-thread block per problem, stream-ordered, no host read, no atomics; its results equal the
+ * host form's bit for bit.  The block computes one OKS row per KEPT person, one thread per candidate, serial over the joints: a
+ * latency link, not a throughput kernel -- 256 people with 133 joints cost up to 256 serial rows of 133 exps per thread on one
+ * CU.  For P > 1 the problem table goes through one upload; P == 1 uploads nothing; P == 0 launches nothing.
+ * hrn_pose_nms_oks_row (no GPU): the OKS of all n people of one problem against its person g exactly as both entries compute it,
+ * for measuring it against the reference's oks_iou; 0, or 7 on null tables or sizes out of range. */
+#define HRN_POSE_NMS_SOFT 1
+#define HRN_POSE_NMS_SUPPRESS 2
+#define HRN_POSE_NMS_ENGINE 4
+int hrn_pose_nms(int P, const int32_t *start, int J, int flags, void *kpts, void *areas, const void *scores, double thresh,
+                 double in_vis_thre, double rescore_thre, const double *sigmas, int32_t *keep, int32_t *num, double *scores_out,
+                 int32_t *suppressor, int32_t *status);
+const char *hrn_pose_nms_last_error(void);
+int hrn_pose_nms_dev(hrn_handle h, int P, const int32_t *start_host, int J, int flags, void *kpts_dev, void *areas_dev,
+                     const void *scores_dev, double thresh, double in_vis_thre, double rescore_thre, const double *sigmas_dev,
+                     int32_t *keep_dev, int32_t *num_dev, double *scores_out_dev, int32_t *suppressor_dev, int32_t *status_dev,
+                     void *stream);
+int hrn_pose_nms_oks_row(int n, int J, int flags, const void *kpts, const void *areas, int g, double in_vis_thre, const double *sigmas,
+                         double *oks_out /* n */);
+
 /* ---- pose overlays on the GPU: the joints and bones of every person, drawn into frames that stay on the device ----
  * Replaces, for every frame of the two demo programs (scripts/live-demo.py:135-138, scripts/extract-keypoints.py's sibling loop),
  *   for i, pt in enumerate(pts): frame = draw_points_and_skeleton(frame, pt, skeleton, person_index=i, ...)

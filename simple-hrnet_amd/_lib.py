@@ -23,6 +23,7 @@ SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "c
            "score.hip",    # heat-maps against the ground truth: Gaussian targets, loss and PCK of an evaluation batch
            "draw.hip",     # pose overlays: joints and bones of every person drawn into BGR / NV12 / I420 frames on the device
            "track.hip",    # the tracking link: boxes from joints, crop records from detections on the device (track_geometry.h)
+           "pose_nms.hip",  # pose NMS: rescoring and hard / soft OKS NMS per image or stream in one launch (pose_nms_math.h)
            "assoc.hip",    # person ids between two frames: similarity, assignment, ids and smoothing in one launch (assoc_math.h)
            # fp16 instantiations of the three hand-scheduled kernel families (bodies shared through conv3x3_lds.inc / conv_s2.inc /
            # bottleneck_chain.inc): translation units of their own, so that each bf16 file still compiles to exactly its kernel set
@@ -235,6 +236,12 @@ SYMBOLS = {
                                                 ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
     "hrn_assoc_exp": (ctypes.c_int, [_P, ctypes.c_int, _P]),
     "hrn_associate_similarity": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_double, _P, _P]),
+    "hrn_pose_nms": (ctypes.c_int, [ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_double, _P, _P, _P, _P, _P, _P]),
+    "hrn_pose_nms_last_error": (ctypes.c_char_p, []),
+    "hrn_pose_nms_dev": (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, _P, _P, _P, _P, _P, _P, _P]),
+    "hrn_pose_nms_oks_row": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_double, _P, _P]),
     "hrn_yuv_from_bgr": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
     "hrn_crop_geometry": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
     "hrn_crop_geometry_last_error": (ctypes.c_char_p, []),

@@ -75,6 +75,7 @@
                                             // per-person records the build launch writes; draw_table's guard
     CallScratch assoc_buf;     // hrn_associate_people_dev: the problem table of a call with several problems, then the costs and
                                // similarities the kernel keeps between its phases
+    CallScratch nms_table;     // hrn_pose_nms_dev: the problem table of a call with several problems
     CallScratch trk_table;     // the tracking link: the call's host table (frame sizes per person; frame table and frame index)
 
     // the pre-path's device scratch for n people: `tmp_bytes` of intermediates (exact: they can be large), n records (and n YUV sources)
@@ -145,7 +146,7 @@
 
     void free_scratch() {
         for (CallScratch *c : {&rs_taps, &pre_tmp, &pre_params, &pre_yuv, &warp_params, &score_joints, &draw_table, &draw_records, &assoc_buf,
-                               &trk_table})
+                               &nms_table, &trk_table})
             c->release();
         pass.release();
         for (auto &kv : score_tables) (void)hipFree(kv.second);

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "assoc_math.h"
+#include "pose_nms_math.h"
 #include "kernels.h"
 #include "track_geometry.h"
 
@@ -987,6 +988,46 @@ int hrn_associate_people_dev(hrn_handle h, int P, const int32_t *cur_start_host,
     a.next_id = next_id_dev, a.pose_alpha = pose_alpha, a.similarity_threshold = similarity_threshold, a.smoothing_alpha = smoothing_alpha;
     a.ids = ids_dev, a.match = match_dev, a.status = status_dev, a.scratch = h->assoc_buf.ptr;
     if (!h->hip_ok(launch_assoc(a, s), "association launch")) return 8;
+    return scope.leave() ? 0 : 6;
+}
+
+// rescoring and OKS NMS for P problems in one launch (pose_nms.hip); the arguments are judged first (pose_nms_math.h's
+// pose_nms_fault, as in the host form: they need no device), then the handle.  Only a call with several problems touches the handle
+// (its table), so only that call enters a guard.
+int hrn_pose_nms_dev(hrn_handle h, int P, const int32_t *start_host, int J, int flags, void *kpts_dev, void *areas_dev,
+                     const void *scores_dev, double thresh, double in_vis_thre, double rescore_thre, const double *sigmas_dev,
+                     int32_t *keep_dev, int32_t *num_dev, double *scores_out_dev, int32_t *suppressor_dev, int32_t *status_dev,
+                     void *stream) {
+    if (!h) return 1;
+    if (const char *fault = pose_nms_fault(P, start_host, J, flags, kpts_dev, areas_dev, scores_dev, thresh, sigmas_dev, keep_dev, num_dev,
+                                           scores_out_dev, suppressor_dev, status_dev)) {
+        h->err = std::string("hrn_pose_nms_dev: ") + fault;
+        return 7;
+    }
+    if (h->refuse_plan_only()) return 7;
+    if (P == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t table_bytes = (size_t)P * sizeof(PoseNmsProblem);
+    if (P > 1 && !h->table_reserve(h->nms_table, table_bytes, 4096, "hipMalloc(pose NMS table)")) return 6;
+    CallScope scope(h, P > 1 ? &h->nms_table : nullptr, s);
+    if (!scope.entered) return 6;
+    PoseNmsArgs a{};
+    a.P = P, a.J = J, a.flags = flags;
+    if (P > 1) {   // the table through the pinned ring
+        unsigned ring = 0;
+        PoseNmsProblem *pin = (PoseNmsProblem *)h->pre_stage(table_bytes, &ring);
+        if (!pin) return 6;
+        for (int p = 0; p < P; ++p) pin[p].first = start_host[p], pin[p].n = start_host[p + 1] - start_host[p];
+        if (!h->pre_upload(ring, s, {{h->nms_table.ptr, pin, table_bytes, "hipMemcpyAsync(pose NMS table)"}})) return 6;
+        a.table = h->nms_table.as<const PoseNmsProblem>();
+    } else {
+        a.one.first = start_host[0], a.one.n = start_host[1] - start_host[0];
+    }
+    a.kpts = kpts_dev, a.areas = areas_dev, a.scores = scores_dev, a.sigmas = sigmas_dev;
+    a.thresh = thresh, a.in_vis_thre = in_vis_thre, a.rescore_thre = rescore_thre;
+    a.keep = keep_dev, a.num = num_dev, a.scores_out = scores_out_dev, a.suppressor = suppressor_dev, a.status = status_dev;
+    if (!h->hip_ok(launch_pose_nms(a, s), "pose NMS launch")) return 8;
     return scope.leave() ? 0 : 6;
 }
 

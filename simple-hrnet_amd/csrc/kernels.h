@@ -420,6 +420,26 @@ hipError_t launch_assoc(const AssocArgs &a, hipStream_t s);   // assoc_kernel: P
 // bone[i] = palette[ids[i] mod Cb] (Python's modulo) for hrn_draw_poses_ids_dev: the ids never leave the device
 hipError_t launch_bone_ids(const int *ids, int n, const unsigned *palette, int Cb, unsigned *bone, hipStream_t s);
 
+// Pose NMS (pose_nms.hip; include/hrnet_mi355.h: hrn_pose_nms_dev): rescoring, ordering and hard or soft OKS NMS of P independent
+// problems in one launch, one block per problem (the arithmetic: pose_nms_math.h).
+struct PoseNmsProblem {            // one problem: n people from `first`
+    int first, n;
+};
+struct PoseNmsArgs {
+    int P, J, flags;               // flags: HRN_POSE_NMS_SOFT | _SUPPRESS | _ENGINE
+    PoseNmsProblem one;            // P == 1: the problem, in the kernel arguments (nothing is uploaded)
+    const PoseNmsProblem *table;   // else P entries, device
+    void *kpts;                    // COCO layout: (n, J, 3) double (x, y, score); engine layout: float (y, x, confidence), in / out
+    void *areas;                   // COCO layout: n double; engine layout: (n, 4) int32 boxes, in / out
+    const void *scores;            // COCO layout: n double; engine layout: n float or nullptr (1.0)
+    const double *sigmas;          // J, or nullptr: COCO's 17
+    double thresh, in_vis_thre, rescore_thre;
+    int *keep, *num;               // out: n (kept people in selection order, then -1), P
+    double *scores_out;            // out: n
+    int *suppressor, *status;      // out: n, P
+};
+hipError_t launch_pose_nms(const PoseNmsArgs &a, hipStream_t s);   // pose_nms_kernel: P blocks of 256 threads
+
 struct TapArgs {           // debug tap: crops crop0, crop0 + crop_step, ... of a flat padded tensor -> (ncrops, c, h, w) fp32
     const void *in;
     float *dst;

@@ -2,6 +2,8 @@
 //   * OKS non-maximum suppression, hard and soft      misc/nms/nms.py:75-180   (evaluation: datasets/COCO.py:371-374)
 //   * tracker: box-IoU / OKS similarity matrices and the optimal assignment   misc/utils.py:251-429
 //     (live demo: scripts/live-demo.py:120-123)
+//   * person ids and pose NMS in the arithmetic their kernels compile (assoc_math.h, pose_nms_math.h): the host forms of
+//     hrn_associate_people_dev and hrn_pose_nms_dev, equal to them bit for bit
 // These are O(people^2 * joints) on a handful of skeletons: they are host code in the reference (numpy + the munkres
 // package) and stay host code here -- a kernel launch costs more than the whole computation.  What matters is that the
 // numbers are the reference's: float64 arithmetic in numpy's operation order (its pairwise summation included), float32
@@ -18,6 +20,7 @@
 #include <vector>
 
 #include "assoc_math.h"
+#include "pose_nms_math.h"
 
 #pragma clang fp contract(off)
 
@@ -317,6 +320,120 @@ int hrn_associate_similarity(const int32_t *boxes, const float *pts, int n, cons
 int hrn_assoc_exp(const double *x, int n, double *out) {
     if (n < 0 || (n && (!x || !out))) return 7;
     for (int i = 0; i < n; ++i) out[i] = hrn::assoc_exp(x[i]);
+    return 0;
+}
+
+// Pose NMS on the host: P independent problems (the images of an evaluation set, the streams of a camera wall), each rescoring,
+// ordering and hard or soft OKS NMS in pose_nms_math.h's arithmetic -- the text the kernel of pose_nms.hip compiles, so
+// hrn_pose_nms_dev equals this bit for bit.  (hrn_oks_nms / hrn_soft_oks_nms above keep their libm exp and the caller's order.)
+namespace {
+thread_local std::string g_pose_nms_error;
+
+hrn::PoseNmsPeople pose_nms_people(int J, int flags, const void *kpts, const void *areas, const void *scores, double in_vis_thre,
+                                   double rescore_thre) {
+    hrn::PoseNmsPeople p{};
+    p.engine = (flags & hrn::kPoseNmsEngine) != 0, p.J = J, p.vis = in_vis_thre, p.rescore = rescore_thre;
+    if (p.engine)
+        p.pts = (const float *)kpts, p.boxes = (const int32_t *)areas, p.det_scores = (const float *)scores;
+    else
+        p.kpts = (const double *)kpts, p.areas = (const double *)areas, p.scores = (const double *)scores;
+    return p;
+}
+}  // namespace
+
+int hrn_pose_nms(int P, const int32_t *start, int J, int flags, void *kpts, void *areas, const void *scores, double thresh,
+                 double in_vis_thre, double rescore_thre, const double *sigmas, int32_t *keep, int32_t *num, double *scores_out,
+                 int32_t *suppressor, int32_t *status) {
+    using namespace hrn;
+    if (const char *fault = pose_nms_fault(P, start, J, flags, kpts, areas, scores, thresh, sigmas, keep, num, scores_out, suppressor,
+                                           status)) {
+        g_pose_nms_error = fault;
+        return 7;
+    }
+    const PoseNmsPeople ppl = pose_nms_people(J, flags, kpts, areas, scores, in_vis_thre, rescore_thre);
+    std::vector<double> vars(J), gx(J), gy(J), sc, rs, sc2;
+    std::vector<int> ord, ord2;
+    std::vector<char> alive;
+    for (int j = 0; j < J; ++j) vars[j] = pose_nms_var(sigmas, j);
+    auto stage = [&](size_t g) {
+        for (int j = 0; j < J; ++j) gx[j] = pose_nms_x(ppl, g, j), gy[j] = pose_nms_y(ppl, g, j);
+    };
+    for (int p = 0; p < P; ++p) {
+        const size_t first = (size_t)start[p];
+        const int n = start[p + 1] - start[p];
+        int st = 0, bad = 0, kept = 0;
+        sc.resize(n), ord.resize(n), sc2.resize(n), ord2.resize(n), rs.resize(n), alive.assign(n, 1);
+        for (int i = 0; i < n; ++i) {
+            sc[i] = scores_out[first + i] = pose_nms_score(ppl, first + i);
+            if (sc[i] != sc[i]) st |= 1;
+            suppressor[first + i] = -1;
+        }
+        for (int i = 0; i < n; ++i) ord[pose_nms_rank(sc.data(), n, i)] = i;
+        if (!(flags & kPoseNmsSoft)) {
+            for (int pos = 0; pos < n; ++pos) {
+                const int i = ord[pos];
+                if (!alive[i]) continue;
+                keep[first + kept++] = i;
+                stage(first + i);
+                const double a_g = pose_nms_area(ppl, first + i);
+                for (int q = pos + 1; q < n; ++q) {
+                    const int c = ord[q];
+                    if (!alive[c]) continue;
+                    const double o = pose_nms_oks(ppl, gx.data(), gy.data(), a_g, first + c, pose_nms_area(ppl, first + c), vars.data(), &bad);
+                    if (o > thresh) alive[c] = 0, suppressor[first + c] = i;
+                }
+            }
+        } else {
+            int m = n;
+            for (int q = 0; q < n; ++q) sc2[q] = sc[ord[q]];   // the scores by position
+            while (m > 0 && kept < kPoseNmsMaxKeep) {
+                const int i = ord[0];
+                keep[first + kept++] = i;
+                stage(first + i);
+                const double a_g = pose_nms_area(ppl, first + i);
+                for (int q = 1; q < m; ++q) {
+                    const int c = ord[q];
+                    const double o = pose_nms_oks(ppl, gx.data(), gy.data(), a_g, first + c, pose_nms_area(ppl, first + c), vars.data(), &bad);
+                    rs[q - 1] = pose_nms_soften(sc2[q], o, thresh);
+                }
+                for (int q = 1; q < m; ++q) {
+                    const int r = pose_nms_rank(rs.data(), m - 1, q - 1);
+                    ord2[r] = ord[q], sc[r] = rs[q - 1];
+                }
+                --m;
+                std::copy(ord2.begin(), ord2.begin() + m, ord.begin());
+                std::copy(sc.begin(), sc.begin() + m, sc2.begin());
+            }
+            for (int q = 0; q < m; ++q) suppressor[first + ord[q]] = -2;
+        }
+        for (int q = kept; q < n; ++q) keep[first + q] = -1;
+        num[p] = kept, status[p] = st | (bad ? 2 : 0);
+        if (flags & kPoseNmsSuppress)   // a person who is not kept: what track_frame gives a lost person
+            for (int i = 0; i < n; ++i) {
+                if (suppressor[first + i] == -1) continue;
+                for (int j = 0; j < J; ++j) ((float *)kpts)[((first + i) * J + j) * 3 + 2] = 0.0f;
+                for (int k = 0; k < 4; ++k) ((int32_t *)areas)[(first + i) * 4 + k] = 0;
+            }
+    }
+    return 0;
+}
+
+const char *hrn_pose_nms_last_error(void) { return g_pose_nms_error.c_str(); }
+
+// the OKS of all n people of ONE problem against its person g, exactly as both entries compute it (a non-finite value as 0.0),
+// for measuring it against the reference's oks_iou; returns 0 or 7
+int hrn_pose_nms_oks_row(int n, int J, int flags, const void *kpts, const void *areas, int g, double in_vis_thre, const double *sigmas,
+                         double *oks_out) {
+    using namespace hrn;
+    if (n < 1 || n > kMaxTracked || J < 1 || J > kAssocMaxJoints || (flags & ~kPoseNmsEngine) || g < 0 || g >= n || !kpts || !areas ||
+        !oks_out || (!sigmas && J != 17))
+        return 7;
+    const PoseNmsPeople ppl = pose_nms_people(J, flags, kpts, areas, nullptr, in_vis_thre, __builtin_nan(""));
+    std::vector<double> vars(J), gx(J), gy(J);
+    for (int j = 0; j < J; ++j) vars[j] = pose_nms_var(sigmas, j), gx[j] = pose_nms_x(ppl, g, j), gy[j] = pose_nms_y(ppl, g, j);
+    int bad = 0;
+    for (int d = 0; d < n; ++d)
+        oks_out[d] = pose_nms_oks(ppl, gx.data(), gy.data(), pose_nms_area(ppl, g), d, pose_nms_area(ppl, d), vars.data(), &bad);
     return 0;
 }
 

@@ -1132,6 +1132,125 @@ class NativeHRNet:
         self._check(rc, "hrn_associate_people_dev")
         return boxes, pts, ids, match, nxt, status
 
+    # -- pose NMS: duplicate skeletons removed per image or stream, without leaving the device --------------------------------------
+    def _pose_nms_launch(self, engine: bool, kpts, areas, scores, seg: np.ndarray, thresh, in_vis_thre, rescore_thre, soft, sigmas,
+                         suppress):
+        """``hrn_pose_nms_dev`` on device tensors of the right type (``scores`` may be None in the engine layout; ``sigmas`` a host
+        array or None); returns the dict of output tensors"""
+        from .postproc import _nan_if_none, pose_nms_flags
+
+        dev = self.torch_device
+        n, problems, joints = int(areas.shape[0]), len(seg) - 1, int(kpts.shape[1])
+        sg = None
+        if sigmas is not None:
+            sg = torch.as_tensor(np.ascontiguousarray(sigmas, dtype=np.float64).reshape(-1))
+            if sg.numel() != joints:
+                raise ValueError("sigmas must have one value per joint")
+            sg = sg.to(dev, non_blocking=True)
+        keep = torch.empty((n,), dtype=torch.int32, device=dev)
+        num = torch.empty((problems,), dtype=torch.int32, device=dev)
+        scores_out = torch.empty((n,), dtype=torch.float64, device=dev)
+        suppressor = torch.empty((n,), dtype=torch.int32, device=dev)
+        status = torch.empty((problems,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(self.device_index):
+            rc = self._lib.hrn_pose_nms_dev(self._h, problems, seg.ctypes.data, joints, pose_nms_flags(engine, soft, suppress),
+                                            kpts.data_ptr(), areas.data_ptr(), None if scores is None else scores.data_ptr(),
+                                            float(thresh), _nan_if_none(in_vis_thre), _nan_if_none(rescore_thre),
+                                            None if sg is None else sg.data_ptr(), keep.data_ptr(), num.data_ptr(),
+                                            scores_out.data_ptr(), suppressor.data_ptr(), status.data_ptr(), self._stream())
+        self._check(rc, "hrn_pose_nms_dev")
+        return dict(keep=keep, num=num, scores=scores_out, suppressor=suppressor, status=status)
+
+    def pose_nms(self, pts, boxes, det_scores=None, counts=None, thresh: float = 0.9, in_vis_thre=None, rescore_thre=None,
+                 soft: bool = False, sigmas=None, suppress: bool = False):
+        """``postproc.pose_nms`` (engine layout) on the GPU (``hrn_pose_nms_dev``: one launch, one block per problem, no host
+        read): which of the skeletons of a frame are duplicates of a better one -- OKS NMS as the reference's evaluation runs it
+        (``misc/nms/nms.py:97-177``), hard or ``soft``, for one video or the streams of a camera wall (``counts``: people per
+        stream, on the host).
+
+        ``pts`` (n, J, 3) float32 ``(y, x, confidence)`` and ``boxes`` (n, 4) int32 as ``predict_frame`` / ``track_frame`` return
+        them, ``det_scores`` (n,) float32 or None (everybody 1.0).  Tensors of the right type on the engine's GPU are used where
+        they lie; host arrays are uploaded.  ``rescore_thre``: order by the mean confidence of the joints above it times the
+        score (None: by the score as given); ``in_vis_thre``: only the candidate's joints above it enter an OKS.  The order is
+        descending and stable.  ``suppress=True`` zeroes the confidences and the box of everybody who is not kept, IN PLACE:
+        ``draw_poses`` then skips them and the next ``track_frame`` reports them lost (all-padding crop) -- nothing is compacted
+        and no ids are touched.
+        Returns a dict of device tensors, bit for bit the host form's: ``keep`` (n,) int32 -- per problem the kept people in
+        selection order, counted from the problem's first person, then -1; ``num`` (P,); ``scores`` (n,) float64 after rescoring;
+        ``suppressor`` (n,) -- -1 kept, else who removed it (soft: -2 at the cap of 20); ``status`` (P,) -- bit 0 a NaN score was
+        ordered last, bit 1 a non-finite OKS counted as 0; and the ``pts`` / ``boxes`` tensors the call worked on.  At most 256
+        people per problem.  A latency link: one block per problem, one OKS row per kept person."""
+        from .postproc import _segments
+
+        dev = self.torch_device
+
+        def on_device(v, dtype, np_dtype, shape):
+            if not isinstance(v, torch.Tensor):
+                v = torch.from_numpy(np.ascontiguousarray(v, dtype=np_dtype))
+            return v.to(dev, dtype=dtype, non_blocking=True).reshape(shape).contiguous()
+
+        boxes = on_device(boxes, torch.int32, np.int32, (-1, 4))
+        n = int(boxes.shape[0])
+        joints = int(pts.shape[1]) if len(pts.shape) == 3 else (17 if sigmas is None else len(sigmas))
+        pts = on_device(pts, torch.float32, np.float32, (-1, joints, 3))
+        det = None if det_scores is None else on_device(det_scores, torch.float32, np.float32, (-1,))
+        if int(pts.shape[0]) != n or (det is not None and int(det.shape[0]) != n):
+            raise ValueError("pts must be (n, J, 3) beside (n, 4) boxes and n det_scores, got %s, %s, %s"
+                             % (tuple(pts.shape), tuple(boxes.shape), None if det is None else tuple(det.shape)))
+        out = self._pose_nms_launch(True, pts, boxes, det, _segments(counts, n, "counts"), thresh, in_vis_thre, rescore_thre, soft,
+                                    sigmas, suppress)
+        out["pts"], out["boxes"] = pts, boxes
+        return out
+
+    def _pose_nms_coco(self, kpts: np.ndarray, areas: np.ndarray, scores: np.ndarray, counts, thresh, in_vis_thre, rescore_thre, soft,
+                       sigmas):
+        """host arrays in the COCO layout through the device: one upload each, one launch, one download each; numpy results"""
+        from .postproc import _segments
+
+        dev = self.torch_device
+        up = [torch.from_numpy(v).to(dev, non_blocking=True) for v in (kpts, areas, scores)]
+        out = self._pose_nms_launch(False, up[0], up[1], up[2], _segments(counts, len(areas), "counts"), thresh, in_vis_thre,
+                                    rescore_thre, soft, sigmas, False)
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def nms_eval(self, preds, maxvals, areas, box_scores, image_index, oks_thre: float = 0.9, in_vis_thre: float = 0.2,
+                 soft: bool = False, sigmas=None):
+        """The rescoring and OKS NMS of ``evaluate_overall_accuracy`` (``datasets/COCO.py:353-382``) for a whole evaluation set in
+        ONE launch, one block per image: ``preds`` (N, J, 2) image coordinates ``(x, y)`` and ``maxvals`` (N, J) or (N, J, 1) as
+        ``predict_eval`` / ``get_final_preds`` give them, ``areas`` and ``box_scores`` (N,) of the detections, ``image_index`` (N,)
+        integers naming each person's image (any order).  People are grouped by image on the host (a stable sort: inside an image
+        they keep the caller's order); every score becomes the mean confidence of the joints above ``in_vis_thre`` times the box
+        score, then ``oks_nms`` or (``soft``) ``soft_oks_nms`` runs per image with ``oks_thre`` and no visibility mask, as the
+        reference calls them.
+        Returns ``(scores, kept)``: ``scores`` (N,) float64, the rescored scores in the caller's order; ``kept`` a dict, image ->
+        the indices into the caller's arrays that survive, best first, images in order of first appearance -- the structure the
+        reference builds as ``oks_nmsed_kpts``.  Where nothing is kept everybody is returned (``COCO.py:379-380``).  At most 256
+        people per image."""
+        preds = np.asarray(preds.detach().cpu().numpy() if hasattr(preds, "detach") else preds, dtype=np.float64)
+        maxvals = np.asarray(maxvals.detach().cpu().numpy() if hasattr(maxvals, "detach") else maxvals, dtype=np.float64)
+        total = len(preds)
+        if preds.ndim != 3 or preds.shape[2] != 2 or maxvals.size != total * preds.shape[1]:
+            raise ValueError("preds must be (N, J, 2) and maxvals (N, J) or (N, J, 1), got %s, %s" % (preds.shape, maxvals.shape))
+        image_index = np.asarray(image_index).reshape(-1)
+        areas = np.asarray(areas, dtype=np.float64).reshape(-1)
+        box_scores = np.asarray(box_scores, dtype=np.float64).reshape(-1)
+        if not (len(image_index) == len(areas) == len(box_scores) == total):
+            raise ValueError("areas, box_scores and image_index must hold one value per person")
+        order = np.argsort(image_index, kind="stable")
+        images, counts = np.unique(image_index, return_counts=True)
+        kpts = np.ascontiguousarray(np.concatenate([preds, maxvals.reshape(total, -1, 1)], axis=2)[order])
+        res = self._pose_nms_coco(kpts, np.ascontiguousarray(areas[order]), np.ascontiguousarray(box_scores[order]), counts, oks_thre,
+                                  None, in_vis_thre, soft, sigmas)
+        scores = np.empty(total, np.float64)
+        scores[order] = res["scores"]
+        by_image, first = {}, 0
+        for image, count, num in zip(images.tolist(), counts.tolist(), res["num"].tolist()):
+            members = order[first:first + count]
+            by_image[image] = members[res["keep"][first:first + num]] if num else members
+            first += count
+        seen = dict.fromkeys(image_index.tolist())
+        return scores, {image: by_image[image] for image in seen}
+
     # -- clip mode: the people of many frames in one pre-path launch and one pass (throughput, not latency) ------------------
     def _device_frames(self, frames) -> List[Optional[torch.Tensor]]:
         """``frames`` of ``preprocess_frames`` as a list of contiguous (Hf, Wf, 3) uint8 tensors on the engine's GPU; a 4-D stack

@@ -198,6 +198,93 @@ def associate_people(boxes, pts, prev_boxes, prev_pts, prev_ids, next_id, pose_a
     return boxes, pts, ids, match, nxt, status
 
 
+POSE_NMS_SOFT, POSE_NMS_SUPPRESS, POSE_NMS_ENGINE = 1, 2, 4      # HRN_POSE_NMS_* of include/hrnet_mi355.h
+
+
+def pose_nms_flags(engine: bool, soft: bool, suppress: bool) -> int:
+    return (POSE_NMS_ENGINE if engine else 0) | (POSE_NMS_SOFT if soft else 0) | (POSE_NMS_SUPPRESS if suppress else 0)
+
+
+def pose_nms(pts=None, boxes=None, det_scores=None, counts=None, thresh=0.9, in_vis_thre=None, rescore_thre=None, soft=False,
+             sigmas=None, suppress=False, kpts=None, areas=None, scores=None):
+    """Rescoring and OKS NMS, hard or soft, of P independent problems in one native call (``hrn_pose_nms``, no GPU): the host form
+    of ``NativeHRNet.pose_nms``, equal to it bit for bit.  The people come in one of two layouts:
+
+    * engine layout: ``pts`` (n, J, 3) float32 ``(y, x, confidence)`` and ``boxes`` (n, 4) int32 as ``predict_frame`` /
+      ``track_frame`` return them, ``det_scores`` (n,) float32 or None (1.0);
+    * COCO layout (``misc/nms/nms.py``'s): ``kpts`` (n, J, 3) float64 ``(x, y, score)``, ``areas`` (n,), ``scores`` (n,) float64.
+
+    ``counts``: people per problem (the images of an evaluation, the streams of a camera wall; None: one problem).
+    ``in_vis_thre``: only the candidate's joints above it enter an OKS (None: all).  ``rescore_thre``: every score first becomes
+    the mean confidence of the person's joints above it times the score (``datasets/COCO.py:360-372``; None: off).  ``sigmas``: J
+    values, or None for COCO's 17.  ``soft``: gaussian rescoring instead of removal, at most 20 kept.  The order is descending
+    score and stable (equal scores keep index order; NaN last).  ``suppress`` (engine layout): everybody who is not kept gets zero
+    confidences and a zero box IN PLACE when ``pts`` / ``boxes`` are C-contiguous float32 / int32 arrays, else in the converted
+    arrays that are returned.
+
+    Returns a dict: ``keep`` (n,) int32 -- per problem the kept people in selection order, counted from the problem's first
+    person, then -1; ``num`` (P,); ``scores`` (n,) float64 after rescoring; ``suppressor`` (n,) -- -1 kept, else who removed it
+    (soft: -2 for the people left over at the cap); ``status`` (P,) -- bit 0: a NaN score was ordered last, bit 1: a non-finite OKS
+    counted as 0; in the engine layout also ``pts`` and ``boxes``."""
+    engine = kpts is None
+    if engine:
+        if pts is None or boxes is None or areas is not None or scores is not None:
+            raise ValueError("give pts and boxes (engine layout) or kpts, areas and scores (COCO layout)")
+        k = np.ascontiguousarray(pts, dtype=np.float32)
+        a = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
+        sc = None if det_scores is None else np.ascontiguousarray(det_scores, dtype=np.float32).reshape(-1)
+    else:
+        if pts is not None or boxes is not None or det_scores is not None or areas is None or scores is None:
+            raise ValueError("give pts and boxes (engine layout) or kpts, areas and scores (COCO layout)")
+        k = np.ascontiguousarray(kpts, dtype=np.float64)
+        a = np.ascontiguousarray(areas, dtype=np.float64).reshape(-1)
+        sc = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+    n = len(a)
+    if k.size == 0 and k.ndim != 3:
+        k = k.reshape(0, 17 if sigmas is None else len(sigmas), 3)
+    if k.ndim != 3 or k.shape[2] != 3 or len(k) != n or (sc is not None and len(sc) != n):
+        raise ValueError("keypoints must be (n, J, 3) beside n areas / boxes and n scores, got %s, %s, %s"
+                         % (k.shape, a.shape, None if sc is None else sc.shape))
+    joints = int(k.shape[1])
+    sg = None if sigmas is None else np.ascontiguousarray(sigmas, dtype=np.float64).reshape(-1)
+    if sg is not None and len(sg) != joints:
+        raise ValueError("sigmas must have one value per joint")
+    seg = _segments(counts, n, "counts")
+    problems = len(seg) - 1
+    keep, num = np.full(n, -1, np.int32), np.zeros(problems, np.int32)
+    scores_out, suppressor, status = np.zeros(n, np.float64), np.full(n, -1, np.int32), np.zeros(problems, np.int32)
+    lib = _lib.load()
+    rc = lib.hrn_pose_nms(problems, seg.ctypes.data, joints, pose_nms_flags(engine, soft, suppress), k.ctypes.data, a.ctypes.data,
+                          None if sc is None else sc.ctypes.data, float(thresh), _nan_if_none(in_vis_thre), _nan_if_none(rescore_thre),
+                          None if sg is None else sg.ctypes.data, keep.ctypes.data, num.ctypes.data, scores_out.ctypes.data,
+                          suppressor.ctypes.data, status.ctypes.data)
+    if rc:
+        raise ValueError("hrn_pose_nms: " + lib.hrn_pose_nms_last_error().decode())
+    out = dict(keep=keep, num=num, scores=scores_out, suppressor=suppressor, status=status)
+    if engine:
+        out["pts"], out["boxes"] = k, a
+    return out
+
+
+def pose_nms_oks_row(kpts, areas, g: int, in_vis_thre=None, sigmas=None) -> np.ndarray:
+    """The OKS of every person of one problem (COCO layout) against its person ``g`` as ``pose_nms`` computes it -- what
+    ``oks_iou(kpts[g], kpts, areas[g], areas, sigmas, in_vis_thre)`` of ``misc/nms/nms.py`` returns, in pose_nms_math.h's
+    arithmetic (``hrn_pose_nms_oks_row``, no GPU)."""
+    k = np.ascontiguousarray(kpts, dtype=np.float64)
+    a = np.ascontiguousarray(areas, dtype=np.float64).reshape(-1)
+    if k.ndim != 3 or k.shape[2] != 3 or len(k) != len(a):
+        raise ValueError("kpts must be (n, J, 3) beside n areas, got %s, %s" % (k.shape, a.shape))
+    sg = None if sigmas is None else np.ascontiguousarray(sigmas, dtype=np.float64).reshape(-1)
+    if sg is not None and len(sg) != k.shape[1]:
+        raise ValueError("sigmas must have one value per joint")
+    out = np.zeros(len(a), np.float64)
+    rc = _lib.load().hrn_pose_nms_oks_row(len(a), int(k.shape[1]), 0, k.ctypes.data, a.ctypes.data, int(g), _nan_if_none(in_vis_thre),
+                                          None if sg is None else sg.ctypes.data, out.ctypes.data)
+    if rc:
+        raise ValueError("hrn_pose_nms_oks_row: bad arguments")
+    return out
+
+
 def inverse_affine(center, scale, pixel_std, output_size) -> np.ndarray:
     """The 2x3 matrix ``get_affine_transform(center, scale, pixel_std, 0, output_size, inv=1)`` returns
     (``misc/utils.py:44-76``): heat-map coordinates back to image coordinates for an unrotated crop.  The reference builds
