@@ -454,6 +454,88 @@ int hrn_draw_poses_ids_dev(hrn_handle h, const hrn_canvas *canvases_host, int nf
                            int thickness, float threshold, void *stream);
 int hrn_yuv_from_bgr(int matrix, int range, const uint8_t *bgr /* (n,3) */, int n, uint8_t *yuv_out /* (n,3) */);
 
+/* ---- the detector link on the GPU: the letterboxed detector tensor, and the detector's boxes back in frame coordinates ----
+ * Replaces the host code AROUND an injected person detector (the network and its NMS stay the caller's):
+ * models_/detectors/YOLOv3.py:23-76 (letterbox + prepare_data before the network, filter_classes + scale_coords after it) and
+ * models_/detectors/YOLOv5.py:9-39, 88-98 (letterbox before; confidence / class filter and (x - dw) / ratio after).
+ *
+ * GEOMETRY (csrc/letterbox_math.h, one text for both rules; round = nearest, ties to even, on a double -- Python's round):
+ *   HRN_LETTERBOX_MAX_SIDE   YOLOv3's letterbox(mode='square'): out_h == out_w == S; ratio = (double)S / max(h, w)
+ *   HRN_LETTERBOX_MIN_RATIO  YOLOv5's letterbox(auto=False, scaleFill=False, scaleup=True): ratio = min((double)out_h / h,
+ *                            (double)out_w / w); the output may be rectangular
+ *   new_w = round(w * ratio), new_h = round(h * ratio); dw = (out_w - new_w) / 2.0, dh = (out_h - new_h) / 2.0;
+ *   top = round(dh - 0.1), bottom = round(dh + 0.1), left = round(dw - 0.1), right = round(dw + 0.1).
+ *   top + new_h + bottom == out_h and left + new_w + right == out_w (asserted).  new_w == 0 or new_h == 0 (a 1 x 200 frame at
+ *   S = 64) fails with code 7: cv2.resize would raise there.
+ * hrn_letterbox keeps the doubles `ratio` and dw / dh BEFORE rounding beside the integers: YOLOv5's inverse uses those.
+ * hrn_letterbox_geometry needs no handle and no GPU; its failure text: hrn_letterbox_last_error().
+ *
+ * hrn_letterbox_frames / hrn_letterbox_frames_yuv: n frames (a host table of hrn_frame / hrn_yuv_frame, sizes may differ, as
+ * in hrn_preprocess_frames; n <= 65535) to ONE detector tensor in ONE launch, no frame-sized scratch, one writer per byte.
+ *   interior pixel   cv2.resize(frame, (new_w, new_h), INTER_LINEAR): bit for bit the arithmetic of hrn_resize_frames with
+ *                    HRN_INTER_LINEAR (csrc/resize_taps.h is compiled into both kernels), plus the two cases that entry never meets:
+ *                    new size == frame size: a copy (YOLOv5's wrapper skips the resize; cv2.resize copies);
+ *                    frame_w == 2 * new_w and frame_h == 2 * new_h (every 1280 x 720 frame at 640): cv2.resize switches
+ *                    INTER_LINEAR to its INTER_AREA fast path, (a + b + c + d + 2) >> 2 over the 2 x 2 block.
+ *                    OpenCV is not available where this library is built and tested: all three are restated from the published
+ *                    resize.cpp, the 2:1 rule without even a restating oracle of older standing; equality with a cv2 build is
+ *                    NOT pinned (tests/golden/make_letterbox_golden.py makes the pin wherever opencv-python is installed).
+ *   padding pixel    pad[c], c in OUTPUT channel order; no frame byte is read.  (The wrappers' 127.5 is 128 under cv2's
+ *                    round-half-even saturation; YOLOv5 uses 114.)
+ *   order            HRN_LB_RGB (what both wrappers feed the network) or HRN_LB_BGR
+ *   form             HRN_LB_F32 / _F16 / _BF16: (n, 3, out_h, out_w) planar, value = (float)v / 255.0f (true float32 division:
+ *                    torchvision's ToTensor), the 16-bit forms that float rounded to nearest even;
+ *                    HRN_LB_U8_HWC: (n, out_h, out_w, 3) uint8, the byte itself
+ *   YUV frames       every tap is read through the conversion of hrn_preprocess_frames_yuv: the result equals, bit for bit, the
+ *                    BGR entry on the converted frame; padding is pad[], not a conversion of anything
+ *   geometry_host    optional out: n hrn_letterbox
+ * Code 7 and nothing launched, each failure naming its cause: an unknown rule / order / form, out_h or out_w outside
+ * [1, 16384], MAX_SIDE with out_h != out_w, n < 0 or n > 65535, null tables, a frame that is null or malformed (the texts of
+ * hrn_preprocess_frames / _yuv), a frame whose geometry fails, a plan-only handle.  n == 0 succeeds and launches nothing.
+ *
+ * BOXES BACK: hrn_detections_to_frame (host, no handle; failure text: hrn_letterbox_last_error()) and
+ * hrn_detections_to_frame_dev (one launch, one 256-thread block per frame, stream-ordered, no host read).
+ *   dets          (n, det_stride >= 5) float32 rows (x1, y1, x2, y2, ...) in LETTERBOX coordinates, after the detector's NMS
+ *   start_host    P + 1 ascending row offsets on the HOST (start[0] = 0): frame p owns rows [start[p], start[p + 1])
+ *   geometry_host / frame_hw_host   the P hrn_letterbox the forward call returned and the P (height, width) of the frames
+ *   conf_col in [4, det_stride), conf_thres: a row is kept iff row[conf_col] >= conf_thres in float32 (-inf: everybody)
+ *   class_col     column of the class id; negative counts from the end (detections[:, -1]); == det_stride: no class filter.
+ *                 classes_host: nclasses <= 16 accepted ids; a row passes iff row[class_col] == (float)id for one of them
+ *   status (n)    per INPUT row: 0 kept; 5 a coordinate or the confidence is not finite; else 1 below the threshold; else 2 other class
+ *   inverse       MAX_SIDE (scale_coords): gain = (double)max(out_h, out_w) / max(h, w); pad_x = (out_w - w * gain) / 2,
+ *                 pad_y = (out_h - h * gain) / 2 in double; each cast to float32; v' = max((v - pad) / gain, 0) in float32, for all
+ *                 four coordinates (x2 / y2 are not cut to the frame, as in the reference; a negative result, and -0, become +0).
+ *                 MIN_RATIO: v' = (v - (float)dw) / (float)ratio, no clamp.
+ *                 The division is a TRUE float32 division, torch's CPU behaviour and the definition here; torch's GPU kernel
+ *                 multiplies by a reciprocal, so the reference disagrees with itself by an ulp between devices.
+ *   dets_out      a separate (n, det_stride) buffer (overlapping the input is refused).  A kept row: the four mapped coordinates,
+ *                 every other column unchanged.  A row that is not kept: all zeros -- the "lost person" row
+ *                 hrn_preprocess_frames_dev reports as status 1.  With HRN_DET_COMPACT the kept rows of a frame move to the front
+ *                 of that frame's segment in their order and the zero rows follow; counts (P) = kept rows per frame either way. */
+enum { HRN_LETTERBOX_MAX_SIDE = 0, HRN_LETTERBOX_MIN_RATIO = 1 };
+enum { HRN_LB_F32 = 0, HRN_LB_F16 = 1, HRN_LB_BF16 = 2, HRN_LB_U8_HWC = 3 };
+enum { HRN_LB_RGB = 0, HRN_LB_BGR = 1 };
+enum { HRN_DET_COMPACT = 1 };
+enum { HRN_DET_MAX_CLASSES = 16 };
+typedef struct { int32_t new_w, new_h, left, top; double ratio_w, ratio_h, dw, dh; } hrn_letterbox;
+int hrn_letterbox_geometry(int rule, const int32_t *frame_hw /* (n, 2) height, width */, int n, int out_h, int out_w,
+                           hrn_letterbox *out /* n */);
+const char *hrn_letterbox_last_error(void);
+int hrn_letterbox_frames(hrn_handle h, const hrn_frame *frames_host, int n, int rule, int out_h, int out_w,
+                         const uint8_t *pad /* 3 */, int order, int form, void *out_dev, hrn_letterbox *geometry_host /* n or NULL */,
+                         void *stream);
+int hrn_letterbox_frames_yuv(hrn_handle h, const hrn_yuv_frame *frames_host, int n, int rule, int out_h, int out_w,
+                             const uint8_t *pad /* 3 */, int order, int form, void *out_dev,
+                             hrn_letterbox *geometry_host /* n or NULL */, void *stream);
+int hrn_detections_to_frame(int rule, const float *dets, int det_stride, const int32_t *start /* P + 1 */, int P,
+                            const hrn_letterbox *geometry, const int32_t *frame_hw /* (P, 2) */, int out_h, int out_w,
+                            int conf_col, float conf_thres, int class_col, const int32_t *classes, int nclasses, int flags,
+                            float *dets_out, int32_t *counts_out /* P */, int32_t *status_out /* n */);
+int hrn_detections_to_frame_dev(hrn_handle h, int rule, const float *dets_dev, int det_stride, const int32_t *start_host, int P,
+                                const hrn_letterbox *geometry_host, const int32_t *frame_hw_host, int out_h, int out_w,
+                                int conf_col, float conf_thres, int class_col, const int32_t *classes_host, int nclasses, int flags,
+                                float *dets_out_dev, int32_t *counts_dev, int32_t *status_dev, void *stream);
+
 /* Single-person pre-path on the GPU: replaces, for every frame of a call with multiperson=False,
  *   cv2.resize(image, (W, H), interpolation=self.interpolation); cv2.cvtColor(image, cv2.COLOR_BGR2RGB); self.transform(image)
  * (SimpleHRNet.py:213-222 for one frame, :355-366 for a stack; default interpolation cv2.INTER_CUBIC, :27) and writes the

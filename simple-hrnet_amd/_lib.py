@@ -24,6 +24,7 @@ SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "c
            "draw.hip",     # pose overlays: joints and bones of every person drawn into BGR / NV12 / I420 frames on the device
            "track.hip",    # the tracking link: boxes from joints, crop records from detections on the device (track_geometry.h)
            "pose_nms.hip",  # pose NMS: rescoring and hard / soft OKS NMS per image or stream in one launch (pose_nms_math.h)
+           "letterbox.hip",  # the detector link: the letterboxed detector tensor, the detector's boxes back in frame coordinates (letterbox_math.h)
            "assoc.hip",    # person ids between two frames: similarity, assignment, ids and smoothing in one launch (assoc_math.h)
            # fp16 instantiations of the three hand-scheduled kernel families (bodies shared through conv3x3_lds.inc / conv_s2.inc /
            # bottleneck_chain.inc): translation units of their own, so that each bf16 file still compiles to exactly its kernel set
@@ -192,6 +193,12 @@ class YuvFrameC(ctypes.Structure):
                 ("matrix", ctypes.c_int32), ("range", ctypes.c_int32)]
 
 
+class Letterbox(ctypes.Structure):
+    """hrn_letterbox: the letterbox geometry of one frame"""
+    _fields_ = [("new_w", ctypes.c_int32), ("new_h", ctypes.c_int32), ("left", ctypes.c_int32), ("top", ctypes.c_int32),
+                ("ratio_w", ctypes.c_double), ("ratio_h", ctypes.c_double), ("dw", ctypes.c_double), ("dh", ctypes.c_double)]
+
+
 class CanvasC(ctypes.Structure):
     """hrn_canvas: one frame hrn_draw_poses draws into -- hrn_yuv_frame's fields with writable planes (BGR: y = the pixels,
     pitch_y = bytes between rows, format 0)"""
@@ -242,6 +249,16 @@ SYMBOLS = {
     "hrn_pose_nms_dev": (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, ctypes.c_double, ctypes.c_double,
                                         ctypes.c_double, _P, _P, _P, _P, _P, _P, _P]),
     "hrn_pose_nms_oks_row": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_double, _P, _P]),
+    "hrn_letterbox_geometry": (ctypes.c_int, [ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    "hrn_letterbox_last_error": (ctypes.c_char_p, []),
+    "hrn_letterbox_frames": (ctypes.c_int, [_P, ctypes.POINTER(Frame), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int,
+                                            ctypes.c_int, _P, _P, _P]),
+    "hrn_letterbox_frames_yuv": (ctypes.c_int, [_P, ctypes.POINTER(YuvFrameC), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P,
+                                                ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    "hrn_detections_to_frame": (ctypes.c_int, [ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_float, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    "hrn_detections_to_frame_dev": (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_float, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
     "hrn_yuv_from_bgr": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
     "hrn_crop_geometry": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
     "hrn_crop_geometry_last_error": (ctypes.c_char_p, []),

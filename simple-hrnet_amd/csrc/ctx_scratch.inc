@@ -77,6 +77,8 @@
                                // similarities the kernel keeps between its phases
     CallScratch nms_table;     // hrn_pose_nms_dev: the problem table of a call with several problems
     CallScratch trk_table;     // the tracking link: the call's host table (frame sizes per person; frame table and frame index)
+    CallScratch lb_table;      // hrn_letterbox_frames(_yuv): the frame records of a call with several frames
+    CallScratch det_table;     // hrn_detections_to_frame_dev: the frame records of a call with several frames
 
     // the pre-path's device scratch for n people: `tmp_bytes` of intermediates (exact: they can be large), n records (and n YUV sources)
     bool pre_reserve(size_t tmp_bytes, int n, bool yuv) {
@@ -146,7 +148,7 @@
 
     void free_scratch() {
         for (CallScratch *c : {&rs_taps, &pre_tmp, &pre_params, &pre_yuv, &warp_params, &score_joints, &draw_table, &draw_records, &assoc_buf,
-                               &nms_table, &trk_table})
+                               &nms_table, &trk_table, &lb_table, &det_table})
             c->release();
         pass.release();
         for (auto &kv : score_tables) (void)hipFree(kv.second);

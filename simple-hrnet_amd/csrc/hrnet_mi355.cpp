@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "assoc_math.h"
+#include "letterbox_math.h"
 #include "pose_nms_math.h"
 #include "kernels.h"
 #include "track_geometry.h"
@@ -1028,6 +1029,139 @@ int hrn_pose_nms_dev(hrn_handle h, int P, const int32_t *start_host, int J, int 
     a.thresh = thresh, a.in_vis_thre = in_vis_thre, a.rescore_thre = rescore_thre;
     a.keep = keep_dev, a.num = num_dev, a.scores_out = scores_out_dev, a.suppressor = suppressor_dev, a.status = status_dev;
     if (!h->hip_ok(launch_pose_nms(a, s), "pose NMS launch")) return 8;
+    return scope.leave() ? 0 : 6;
+}
+
+// ---- the detector link: the letterboxed detector tensor, and the detector's boxes back in frame coordinates --------------------
+namespace {
+// the one body of hrn_letterbox_frames and hrn_letterbox_frames_yuv: everything is judged -- the arguments, every frame, every
+// geometry, then the handle -- before the device is touched
+int letterbox_frames(const char *entry, hrn_handle h, const hrn_frame *frames, const hrn_yuv_frame *yframes, int n, int rule, int out_h,
+                     int out_w, const uint8_t *pad, int order, int form, void *out_dev, hrn_letterbox *geometry_host, hipStream_t s) {
+    const std::string name = entry;
+    std::string why;
+    if (rule != HRN_LETTERBOX_MAX_SIDE && rule != HRN_LETTERBOX_MIN_RATIO) why = letterbox_fault_text(LB_BAD_RULE);
+    else if (order != HRN_LB_RGB && order != HRN_LB_BGR) why = "order must be HRN_LB_RGB or HRN_LB_BGR";
+    else if (form != HRN_LB_F32 && form != HRN_LB_F16 && form != HRN_LB_BF16 && form != HRN_LB_U8_HWC)
+        why = "form must be HRN_LB_F32, HRN_LB_F16, HRN_LB_BF16 or HRN_LB_U8_HWC";
+    else if (out_h < 1 || out_w < 1 || out_h > 16384 || out_w > 16384) why = "out_h and out_w must be in [1, 16384]";
+    else if (rule == HRN_LETTERBOX_MAX_SIDE && out_h != out_w) why = letterbox_fault_text(LB_NOT_SQUARE);
+    else if (n < 0 || n > 65535) why = "n must be in [0, 65535]";
+    else if (!pad || (n > 0 && (!(frames || yframes) || !out_dev))) why = "null frames / pad / output";
+    std::vector<LetterboxFrame> recs((size_t)(why.empty() ? n : 0));
+    for (int i = 0; why.empty() && i < n; ++i) {
+        const char *fault = yframes ? yuv_frame_fault(yframes[i]) : bgr_frame_fault(frames[i]);
+        if (fault) {
+            why = name + ": frame " + std::to_string(i) + " " + fault;
+            break;
+        }
+        LetterboxFrame &r = recs[i];
+        r = LetterboxFrame{};
+        r.src_h = yframes ? yframes[i].height : frames[i].height, r.src_w = yframes ? yframes[i].width : frames[i].width;
+        hrn_letterbox g;
+        const int code = letterbox_geometry_one(rule, r.src_h, r.src_w, out_h, out_w, &g, nullptr);
+        if (code != LB_OK) {
+            why = name + ": frame " + std::to_string(i) + " (" + std::to_string(r.src_h) + " x " + std::to_string(r.src_w) + ") " +
+                  letterbox_fault_text(code);
+            break;
+        }
+        if (yframes) r.yuv = yuv_source(yframes[i]);
+        else r.bgr = frames[i].data;
+        r.new_h = g.new_h, r.new_w = g.new_w, r.top = g.top, r.left = g.left;
+        r.mode = g.new_h == r.src_h && g.new_w == r.src_w           ? LB_MODE_COPY
+                 : r.src_h == 2 * g.new_h && r.src_w == 2 * g.new_w ? LB_MODE_AREA
+                                                                    : LB_MODE_LINEAR;
+        r.scale_x = resize_scale(g.new_w, r.src_w), r.scale_y = resize_scale(g.new_h, r.src_h);
+        if (geometry_host) geometry_host[i] = g;
+    }
+    if (!why.empty()) {
+        h->err = why.compare(0, name.size(), name) == 0 ? why : name + ": " + why;
+        return 7;
+    }
+    if (h->refuse_plan_only()) return 7;
+    if (n == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    const size_t table_bytes = (size_t)n * sizeof(LetterboxFrame);
+    if (n > 1 && !h->table_reserve(h->lb_table, table_bytes, 4096, "hipMalloc(letterbox table)")) return 6;
+    CallScope scope(h, n > 1 ? &h->lb_table : nullptr, s);
+    if (!scope.entered) return 6;
+    LetterboxArgs a{};
+    a.n = n, a.out_h = out_h, a.out_w = out_w, a.form = form, a.order = order, a.yuv = yframes ? 1 : 0;
+    a.pad[0] = pad[0], a.pad[1] = pad[1], a.pad[2] = pad[2];
+    a.out = out_dev;
+    if (n > 1) {   // the table through the pinned ring
+        unsigned ring = 0;
+        char *pin = h->pre_stage(table_bytes, &ring);
+        if (!pin) return 6;
+        memcpy(pin, recs.data(), table_bytes);
+        if (!h->pre_upload(ring, s, {{h->lb_table.ptr, pin, table_bytes, "hipMemcpyAsync(letterbox table)"}})) return 6;
+        a.table = h->lb_table.as<const LetterboxFrame>();
+    } else {
+        a.one = recs[0];
+    }
+    if (!h->hip_ok(launch_letterbox(a, s), "letterbox launch")) return 8;
+    return scope.leave() ? 0 : 6;
+}
+}  // namespace
+
+int hrn_letterbox_frames(hrn_handle h, const hrn_frame *frames_host, int n, int rule, int out_h, int out_w, const uint8_t *pad, int order,
+                         int form, void *out_dev, hrn_letterbox *geometry_host, void *stream) {
+    if (!h) return 1;
+    return letterbox_frames("hrn_letterbox_frames", h, frames_host, nullptr, n, rule, out_h, out_w, pad, order, form, out_dev, geometry_host,
+                            (hipStream_t)stream);
+}
+
+int hrn_letterbox_frames_yuv(hrn_handle h, const hrn_yuv_frame *frames_host, int n, int rule, int out_h, int out_w, const uint8_t *pad,
+                             int order, int form, void *out_dev, hrn_letterbox *geometry_host, void *stream) {
+    if (!h) return 1;
+    return letterbox_frames("hrn_letterbox_frames_yuv", h, nullptr, frames_host, n, rule, out_h, out_w, pad, order, form, out_dev,
+                            geometry_host, (hipStream_t)stream);
+}
+
+// hrn_detections_to_frame on the device (letterbox.hip): the arguments are judged first (letterbox_math.h's det_fault, as in the
+// host form: they need no device), then the handle.  Only a call with several frames touches the handle (its table).
+int hrn_detections_to_frame_dev(hrn_handle h, int rule, const float *dets_dev, int det_stride, const int32_t *start_host, int P,
+                                const hrn_letterbox *geometry_host, const int32_t *frame_hw_host, int out_h, int out_w, int conf_col,
+                                float conf_thres, int class_col, const int32_t *classes_host, int nclasses, int flags,
+                                float *dets_out_dev, int32_t *counts_dev, int32_t *status_dev, void *stream) {
+    if (!h) return 1;
+    DetFilter q{};
+    if (const char *fault = det_fault(rule, dets_dev, det_stride, start_host, P, geometry_host, frame_hw_host, out_h, out_w, conf_col,
+                                      conf_thres, class_col, classes_host, nclasses, flags, dets_out_dev, counts_dev, status_dev, q)) {
+        h->err = std::string("hrn_detections_to_frame_dev: ") + fault;
+        return 7;
+    }
+    if (P > 65535) {
+        h->err = "hrn_detections_to_frame_dev: at most 65535 frames";
+        return 7;
+    }
+    if (h->refuse_plan_only()) return 7;
+    if (P == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t table_bytes = (size_t)P * sizeof(DetFrame);
+    if (P > 1 && !h->table_reserve(h->det_table, table_bytes, 4096, "hipMalloc(detection table)")) return 6;
+    CallScope scope(h, P > 1 ? &h->det_table : nullptr, s);
+    if (!scope.entered) return 6;
+    const auto frame = [&](int p) {
+        return det_frame(rule, geometry_host[p], frame_hw_host[2 * (size_t)p], frame_hw_host[2 * (size_t)p + 1], out_h, out_w, start_host[p],
+                         start_host[p + 1] - start_host[p]);
+    };
+    DetArgs a{};
+    a.P = P, a.compact = (flags & kDetCompact) ? 1 : 0;
+    a.dets = dets_dev, a.out = dets_out_dev, a.counts = counts_dev, a.status = status_dev;
+    DetFrame one{};
+    if (P > 1) {   // the table through the pinned ring
+        unsigned ring = 0;
+        DetFrame *pin = (DetFrame *)h->pre_stage(table_bytes, &ring);
+        if (!pin) return 6;
+        for (int p = 0; p < P; ++p) pin[p] = frame(p);
+        if (!h->pre_upload(ring, s, {{h->det_table.ptr, pin, table_bytes, "hipMemcpyAsync(detection table)"}})) return 6;
+        a.table = h->det_table.as<const DetFrame>();
+    } else {
+        one = frame(0);
+    }
+    if (!h->hip_ok(launch_detections_to_frame(a, one, q, s), "detections launch")) return 8;
     return scope.leave() ? 0 : 6;
 }
 

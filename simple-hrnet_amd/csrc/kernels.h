@@ -218,6 +218,8 @@ struct ResizeTaps {
     int ofs;       // first source index of the window (may lie outside: replicate border)
     short c[4];    // fixed-point coefficients, 11 bits
 };
+// the scale of an axis, as cv2's resize() forms it: 1 / ((double)dst / src) (the host passes it to the kernels: resize_taps.h)
+inline double resize_scale(int dst, int src) { return 1.0 / ((double)dst / (double)src); }
 hipError_t launch_resize_frames(const unsigned char *frames_dev, int n, int src_h, int src_w, int interp, ResizeTaps *taps_dev,
                                 float *images_dev, int H, int W, hipStream_t s);
 // evaluation pre-path (warp.hip): cv2.warpAffine(INTER_LINEAR, zero border) of one crop out of one frame of the stack
@@ -439,6 +441,33 @@ struct PoseNmsArgs {
     int *suppressor, *status;      // out: n, P
 };
 hipError_t launch_pose_nms(const PoseNmsArgs &a, hipStream_t s);   // pose_nms_kernel: P blocks of 256 threads
+
+// The detector link (letterbox.hip; include/hrnet_mi355.h: hrn_letterbox_frames, hrn_detections_to_frame_dev).
+enum { LB_MODE_LINEAR = 0, LB_MODE_COPY = 1, LB_MODE_AREA = 2 };   // how an interior pixel is formed (cv2.resize's three paths)
+struct LetterboxFrame {            // one frame of the call, prepared on the host (letterbox_math.h's geometry)
+    const unsigned char *bgr;      // BGR frames: the pixels; YUV frames: nullptr
+    YuvSource yuv;                 // YUV frames: planes, pitches and coefficients
+    int src_h, src_w, new_h, new_w, top, left, mode, pad_;
+    double scale_x, scale_y;       // resize_scale(new, src): LB_MODE_LINEAR reads them
+};
+struct LetterboxArgs {
+    int n, out_h, out_w, form, order, yuv;   // form = HRN_LB_*, order = HRN_LB_RGB / _BGR
+    unsigned char pad[4];          // pad[c] in output channel order
+    LetterboxFrame one;            // n == 1: the frame, in the kernel arguments (nothing is uploaded)
+    const LetterboxFrame *table;   // else n entries, device
+    void *out;
+};
+hipError_t launch_letterbox(const LetterboxArgs &a, hipStream_t s);   // letterbox_kernel<form, source>: one launch, blockIdx.y = frame
+struct DetFrame;
+struct DetFilter;
+struct DetArgs {
+    int P, compact;
+    const DetFrame *table;         // P entries, device (P == 1: `one` of the launcher's arguments instead)
+    const float *dets;
+    float *out;
+    int *counts, *status;
+};
+hipError_t launch_detections_to_frame(const DetArgs &a, const DetFrame &one, const DetFilter &q, hipStream_t s);   // P blocks of 256
 
 struct TapArgs {           // debug tap: crops crop0, crop0 + crop_step, ... of a flat padded tensor -> (ncrops, c, h, w) fp32
     const void *in;

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "assoc_math.h"
+#include "letterbox_math.h"
 #include "pose_nms_math.h"
 
 #pragma clang fp contract(off)
@@ -419,6 +420,49 @@ int hrn_pose_nms(int P, const int32_t *start, int J, int flags, void *kpts, void
 }
 
 const char *hrn_pose_nms_last_error(void) { return g_pose_nms_error.c_str(); }
+
+// ---- the detector link on the host: letterbox geometry and the detector's boxes back in frame coordinates (letterbox_math.h) ----
+static thread_local std::string g_letterbox_error;
+
+int hrn_letterbox_geometry(int rule, const int32_t *frame_hw, int n, int out_h, int out_w, hrn_letterbox *out) {
+    using namespace hrn;
+    g_letterbox_error.clear();
+    if (n < 0 || (n > 0 && (!frame_hw || !out))) {
+        g_letterbox_error = "bad frame sizes / output / n";
+        return 7;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int code = letterbox_geometry_one(rule, frame_hw[2 * (size_t)i], frame_hw[2 * (size_t)i + 1], out_h, out_w, &out[i], nullptr);
+        if (code == LB_OK) continue;
+        g_letterbox_error = code == LB_BAD_RULE || code == LB_NOT_SQUARE
+                                ? std::string(letterbox_fault_text(code))
+                                : "frame " + std::to_string(i) + " (" + std::to_string(frame_hw[2 * (size_t)i]) + " x " +
+                                      std::to_string(frame_hw[2 * (size_t)i + 1]) + ") " + letterbox_fault_text(code);
+        return 7;
+    }
+    return 0;
+}
+
+const char *hrn_letterbox_last_error(void) { return g_letterbox_error.c_str(); }
+
+int hrn_detections_to_frame(int rule, const float *dets, int det_stride, const int32_t *start, int P, const hrn_letterbox *geometry,
+                            const int32_t *frame_hw, int out_h, int out_w, int conf_col, float conf_thres, int class_col,
+                            const int32_t *classes, int nclasses, int flags, float *dets_out, int32_t *counts_out, int32_t *status_out) {
+    using namespace hrn;
+    g_letterbox_error.clear();
+    DetFilter q{};
+    if (const char *fault = det_fault(rule, dets, det_stride, start, P, geometry, frame_hw, out_h, out_w, conf_col, conf_thres, class_col,
+                                      classes, nclasses, flags, dets_out, counts_out, status_out, q)) {
+        g_letterbox_error = fault;
+        return 7;
+    }
+    for (int p = 0; p < P; ++p) {
+        const DetFrame f = det_frame(rule, geometry[p], frame_hw[2 * (size_t)p], frame_hw[2 * (size_t)p + 1], out_h, out_w, start[p],
+                                     start[p + 1] - start[p]);
+        counts_out[p] = det_frame_host(dets, f, q, (flags & kDetCompact) != 0, dets_out, status_out);
+    }
+    return 0;
+}
 
 // the OKS of all n people of ONE problem against its person g, exactly as both entries compute it (a non-finite value as 0.0),
 // for measuring it against the reference's oks_iou; returns 0 or 7

@@ -12,6 +12,8 @@
 // result is bit-identical to Pillow's; ToTensor / Normalize are the float32 operations torchvision performs
 // (v / 255, then (x - mean) / std).  A pass whose size does not change is the identity, as in Pillow.
 #include "kernels.h"
+#include "resize_taps.h"
+#include "yuv_px.h"
 
 namespace hrn {
 
@@ -157,41 +159,7 @@ hipError_t launch_prepath(const CropParams *crops_dev, int n, int max_h_pad, uns
 // frame (tests/yuv_ref.py restates the conversion; tests/test_yuv_gpu.py holds both equalities).
 namespace {
 
-constexpr int kPixNV12 = 1;   // HRN_PIX_NV12, HRN_PIX_I420 of include/hrnet_mi355.h
-constexpr int kPixI420 = 2;
-
-struct Rgb {
-    int r, g, b;
-};
-
-__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-__device__ __forceinline__ Rgb yuv_rgb(const int *coef, int Y, int U, int V) {
-    int yy = Y - coef[0];
-    yy = (yy < 0 ? 0 : yy) * coef[1] + (1 << 19);
-    const int u = U - 128, v = V - 128;
-    Rgb o;
-    o.b = sat8((yy + coef[2] * u) >> 20);
-    o.g = sat8((yy + coef[4] * v + coef[3] * u) >> 20);
-    o.r = sat8((yy + coef[5] * v) >> 20);
-    return o;
-}
-
-// pixel (fy, fx) of the frame: one Y byte, one chroma pair, one conversion
-template <int FMT>
-__device__ __forceinline__ Rgb yuv_frame_px(const YuvSource &ys, int fy, int fx) {
-    const int Y = ys.y[(size_t)fy * ys.pitch_y + fx];
-    int U, V;
-    if (FMT == kPixNV12) {
-        const unsigned char *c = ys.u + (size_t)(fy >> 1) * ys.pitch_c + (fx & ~1);
-        U = c[0], V = c[1];
-    } else {
-        const size_t off = (size_t)(fy >> 1) * ys.pitch_c + (fx >> 1);
-        U = ys.u[off], V = ys.v[off];
-    }
-    return yuv_rgb(ys.coef, Y, U, V);
-}
-
+// (the conversion of one pixel: yuv_px.h, shared with letterbox.hip)
 // padded-crop pixel (y, x), all three channels: RGB 0 in the padding (zero AFTER the conversion, as np.pad of the RGB crop)
 template <int FMT>
 __device__ __forceinline__ Rgb crop_px_yuv(const CropParams &cp, const YuvSource &ys, int y, int x) {
@@ -335,46 +303,11 @@ hipError_t launch_yuv_to_bgr(const YuvSource &src, int height, int width, unsign
 // Tap tables are formed on the device (no host staging): one thread per output column / row.
 __global__ __launch_bounds__(256) void resize_taps_kernel(int src_w, int src_h, int W, int H, double scale_x, double scale_y,
                                                           int interp, ResizeTaps *taps) {
-#pragma clang fp contract(off)
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= W + H) return;
     const bool is_x = t < W;
-    const int d = is_x ? t : t - W, src = is_x ? src_w : src_h;
-    const double scale = is_x ? scale_x : scale_y;
-    ResizeTaps o;
-    o.ofs = 0, o.c[0] = o.c[1] = o.c[2] = o.c[3] = 0;
-    if (interp == 0) {   // resizeNN
-        int s = (int)floor(__dmul_rn((double)d, scale));
-        o.ofs = s < src - 1 ? s : src - 1, o.c[0] = 2048;
-    } else {
-        // (no contraction into fused multiply-adds anywhere: the reference rounds after every operation)
-        float f = (float)__dsub_rn(__dmul_rn(__dadd_rn((double)d, 0.5), scale), 0.5);
-        int s = (int)floorf(f);
-        f = __fsub_rn(f, (float)s);
-        if (interp == 2) {   // interpolateCubic, A = -0.75
-            const float A = -0.75f;
-            const float x1 = __fadd_rn(f, 1.f), xm = __fsub_rn(1.f, f);
-            const float c0 = __fsub_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fsub_rn(__fmul_rn(A, x1), __fmul_rn(5.f, A)), x1), __fmul_rn(8.f, A)), x1),
-                                       __fmul_rn(4.f, A));
-            const float c1 = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(A, 2.f), f), __fadd_rn(A, 3.f)), f), f), 1.f);
-            const float c2 = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(A, 2.f), xm), __fadd_rn(A, 3.f)), xm), xm), 1.f);
-            const float c3 = __fsub_rn(__fsub_rn(__fsub_rn(1.f, c0), c1), c2);
-            const float c[4] = {c0, c1, c2, c3};
-            o.ofs = s - 1;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                int v = __float2int_rn(__fmul_rn(c[k], 2048.f));   // saturate_cast<short>: nearest, ties to even
-                o.c[k] = (short)(v < -32768 ? -32768 : v > 32767 ? 32767 : v);
-            }
-        } else {             // INTER_LINEAR
-            if (is_x && s < 0) s = 0, f = 0.f;
-            if (is_x && s >= src - 1) s = src - 1, f = 0.f;
-            o.ofs = s;
-            o.c[0] = (short)__float2int_rn(__fmul_rn(__fsub_rn(1.f, f), 2048.f));
-            o.c[1] = (short)__float2int_rn(__fmul_rn(f, 2048.f));
-        }
-    }
-    taps[t] = o;
+    // (the arithmetic: resize_taps.h, shared with letterbox.hip)
+    taps[t] = resize_tap_of(is_x ? t : t - W, is_x ? src_w : src_h, is_x ? scale_x : scale_y, interp, is_x);
 }
 
 __global__ __launch_bounds__(256) void resize_frames_kernel(const unsigned char *frames, int src_h, int src_w, const ResizeTaps *taps,
@@ -406,7 +339,7 @@ __global__ __launch_bounds__(256) void resize_frames_kernel(const unsigned char 
         if (interp == 2) {        // VResizeCubic + FixedPtCast<int, uchar, 22>
             o = (hor[0][c] * ty.c[0] + hor[1][c] * ty.c[1] + hor[2][c] * ty.c[2] + hor[3][c] * ty.c[3] + (1 << 21)) >> 22;
         } else if (interp == 1) { // VResizeLinear<uchar, int, short>
-            o = (((ty.c[0] * (hor[0][c] >> 4)) >> 16) + ((ty.c[1] * (hor[1][c] >> 4)) >> 16) + 2) >> 2;
+            o = vresize_linear(ty.c[0], hor[0][c], ty.c[1], hor[1][c]);
         } else {
             o = hor[0][c] >> 11;
         }
@@ -424,7 +357,7 @@ __global__ __launch_bounds__(256) void resize_frames_kernel(const unsigned char 
 hipError_t launch_resize_frames(const unsigned char *frames_dev, int n, int src_h, int src_w, int interp, ResizeTaps *taps_dev,
                                 float *images_dev, int H, int W, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    const double scale_x = 1.0 / ((double)W / (double)src_w), scale_y = 1.0 / ((double)H / (double)src_h);
+    const double scale_x = resize_scale(W, src_w), scale_y = resize_scale(H, src_h);
     hipLaunchKernelGGL(resize_taps_kernel, dim3((W + H + 255) / 256), dim3(256), 0, s, src_w, src_h, W, H, scale_x, scale_y, interp, taps_dev);
     dim3 g((unsigned)(((long)H * W + 255) / 256), n);
     hipLaunchKernelGGL(resize_frames_kernel, g, dim3(256), 0, s, frames_dev, src_h, src_w, taps_dev, interp, images_dev, H, W);

@@ -1072,6 +1072,80 @@ class NativeHRNet:
             return boxes_dev, out[1], status_dev, out[0]
         return boxes_dev, out, status_dev
 
+    # -- the detector link: the letterboxed detector tensor, and the detector's boxes back in frame coordinates --------------------
+    LETTERBOX_FORMS = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.uint8: 3}   # include/hrnet_mi355.h: HRN_LB_*
+
+    def detector_input(self, frames, size, style: str = "yolov3", dtype=torch.float32, order: str = "rgb", pad=None):
+        """What the reference's detector wrappers do to a frame BEFORE their network, on the GPU (``hrn_letterbox_frames``: one
+        launch for all frames, no scratch): ``letterbox`` (cv2.resize(INTER_LINEAR) + cv2.copyMakeBorder), BGR -> RGB, ``ToTensor``.
+
+        ``frames``: one frame ((Hf, Wf, 3) uint8 BGR or a ``YuvFrame``), or a stack / sequence of frames of any sizes as in
+        ``preprocess_frames`` (host frames are uploaded); ``size``: the detector's input side, or (height, width) for
+        ``style="yolov5"``; ``style``: ``"yolov3"`` = ``letterbox(mode='square')`` with border 128 (the wrapper's 127.5 as cv2
+        saturates it), ``"yolov5"`` = ``letterbox(auto=False, scaleFill=False)`` with border 114; ``pad``: one value or three, in
+        output channel order; ``order``: ``"rgb"`` (what both wrappers feed their network) or ``"bgr"``; ``dtype``: float32 / float16 /
+        bfloat16 give (n, 3, out_h, out_w) with values ``v / 255``, uint8 gives (n, out_h, out_w, 3).
+        Returns ``(tensor on the GPU, geometry)``; ``geometry`` (``postproc.LetterboxGeometry``) is what ``detections_to_frame``
+        takes.  Nothing is synchronised.  The resize is OpenCV's published 8-bit arithmetic, not pinned against a cv2 build
+        (include/hrnet_mi355.h); a YUV frame gives, bit for bit, the tensor of its ``yuv_to_bgr`` conversion."""
+        from .postproc import LETTERBOX_PAD, LETTERBOX_RULES, LetterboxGeometry, _letterbox_size
+
+        out_h, out_w = _letterbox_size(size, style)
+        if dtype not in self.LETTERBOX_FORMS:
+            raise ValueError("dtype must be torch.float32, float16, bfloat16 or uint8, got %r" % (dtype,))
+        if order not in ("rgb", "bgr"):
+            raise ValueError("order must be 'rgb' or 'bgr', got %r" % (order,))
+        fill = np.asarray(LETTERBOX_PAD[style] if pad is None else pad)
+        if fill.size not in (1, 3) or (fill < 0).any() or (fill > 255).any() or (fill != np.round(fill)).any():
+            raise ValueError("pad must be one or three integers in [0, 255], got %r" % (pad,))
+        fill = np.ascontiguousarray(np.broadcast_to(fill.reshape(-1), (3,)).astype(np.uint8))
+        single = isinstance(frames, YuvFrame) or (isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3)
+        frames = self._device_frames([frames] if single else frames)
+        if not frames or any(f is None for f in frames):
+            raise ValueError("detector_input needs at least one frame, and none of them None")
+        n = len(frames)
+        table = self._frame_table(frames)
+        yuv = table._type_ is _lib.YuvFrameC
+        entry, name = (self._lib.hrn_letterbox_frames_yuv, "hrn_letterbox_frames_yuv") if yuv else \
+            (self._lib.hrn_letterbox_frames, "hrn_letterbox_frames")
+        shape = (n, out_h, out_w, 3) if dtype == torch.uint8 else (n, 3, out_h, out_w)
+        out = torch.empty(shape, dtype=dtype, device=self.torch_device)
+        geometry = (_lib.Letterbox * n)()
+        with torch.cuda.device(self.device_index):
+            rc = entry(self._h, table, n, LETTERBOX_RULES[style], out_h, out_w, fill.ctypes.data, 0 if order == "rgb" else 1,
+                       self.LETTERBOX_FORMS[dtype], out.data_ptr(), ctypes.addressof(geometry), self._stream())
+        self._check(rc, name)
+        hw = np.asarray([(f.height, f.width) if isinstance(f, YuvFrame) else tuple(f.shape[:2]) for f in frames], np.int32)
+        return out, LetterboxGeometry(style, (out_h, out_w), np.ascontiguousarray(hw), geometry)
+
+    def detections_to_frame(self, dets, geometry, counts=None, conf_thres=None, classes=None, compact: bool = True, conf_col: int = 4,
+                            class_col: int = -1):
+        """``postproc.detections_to_frame`` on the GPU (``hrn_detections_to_frame_dev``: one launch, one block per frame, no host
+        read): what the reference's detector wrappers do AFTER their network and its NMS -- confidence and class filter, then the
+        boxes back from letterbox to frame coordinates.  ``dets`` (n, >=5) float32 on the GPU (a host array is uploaded), the rows
+        of frame p are ``counts[p]`` consecutive ones (host-known: the shapes of the detector's per-image tensors); the other
+        arguments as in ``postproc.detections_to_frame``.  Returns ``(rows (n, stride), counts (P,) int32, status (n,) int32)`` on
+        the GPU, bit for bit the host form's.  A row that is not kept is all zeros, which ``preprocess_frames_dev`` reports as
+        status 1; ``rows[:, :4]`` can go there as it is."""
+        from .postproc import detection_arguments
+
+        if not isinstance(dets, torch.Tensor):
+            dets = torch.from_numpy(np.ascontiguousarray(dets, dtype=np.float32))
+        start, thres, col, ids, flags = detection_arguments(tuple(dets.shape), geometry, counts, conf_thres, classes, class_col, compact)
+        dev = self.torch_device
+        dets = dets.to(dev, dtype=torch.float32, non_blocking=True).contiguous()
+        n, P = int(dets.shape[0]), len(geometry)
+        out = torch.empty_like(dets)
+        kept = torch.empty((P,), dtype=torch.int32, device=dev)
+        status = torch.empty((n,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(self.device_index):
+            rc = self._lib.hrn_detections_to_frame_dev(self._h, geometry.rule, dets.data_ptr(), int(dets.shape[1]), start.ctypes.data, P,
+                                                       ctypes.addressof(geometry.table), geometry.frame_hw.ctypes.data, geometry.size[0],
+                                                       geometry.size[1], int(conf_col), ctypes.c_float(thres), col, ids.ctypes.data,
+                                                       len(ids), flags, out.data_ptr(), kept.data_ptr(), status.data_ptr(), self._stream())
+        self._check(rc, "hrn_detections_to_frame_dev")
+        return out, kept, status
+
     # -- person ids between two frames: who of the previous frame is who of this one ------------------------------------------------
     def associate_people(self, boxes, pts, prev_boxes, prev_pts, prev_ids, next_id, pose_alpha: float = 0.5,
                          similarity_threshold: float = 0.5, smoothing_alpha: float = 0.0, counts=None, prev_counts=None):

@@ -473,3 +473,99 @@ def pose_boxes(pts, frame_hw, threshold: float = 0.5, min_joints: int = 3, scale
     if rc != 0:
         raise ValueError("hrn_pose_boxes: " + lib.hrn_pose_boxes_last_error().decode())
     return out
+
+
+# -- the detector link on the host: letterbox geometry and the detector's boxes back in frame coordinates -------------------------
+LETTERBOX_RULES = {"yolov3": 0, "yolov5": 1}     # include/hrnet_mi355.h: HRN_LETTERBOX_MAX_SIDE / _MIN_RATIO
+LETTERBOX_PAD = {"yolov3": 128, "yolov5": 114}   # the wrappers' border: 127.5 is 128 under cv2's round-half-even saturation
+DET_STATUS = {0: "kept", 1: "below the threshold", 2: "other class", 5: "not finite"}
+
+
+class LetterboxGeometry:
+    """What ``letterbox_geometry`` / ``NativeHRNet.detector_input`` return and ``detections_to_frame`` takes: the geometry of
+    ``n`` frames letterboxed to one output size.  ``style``, ``size`` = (out_h, out_w), ``frame_hw`` (n, 2) int32, and per frame the
+    arrays ``new_w``, ``new_h``, ``left``, ``top`` (int32), ``right``, ``bottom`` (derived) and ``ratio``, ``dw``, ``dh`` (float64, the
+    wrappers' values BEFORE rounding: YOLOv5's inverse uses those)."""
+
+    def __init__(self, style: str, size, frame_hw: np.ndarray, table):
+        self.style, self.rule, self.size = style, LETTERBOX_RULES[style], (int(size[0]), int(size[1]))
+        self.frame_hw, self.table = frame_hw, table
+        rows = [table[k] for k in range(len(frame_hw))]
+        self.new_w, self.new_h = (np.asarray([getattr(r, f) for r in rows], np.int32) for f in ("new_w", "new_h"))
+        self.left, self.top = (np.asarray([getattr(r, f) for r in rows], np.int32) for f in ("left", "top"))
+        self.ratio, self.dw, self.dh = (np.asarray([getattr(r, f) for r in rows], np.float64) for f in ("ratio_w", "dw", "dh"))
+        self.right, self.bottom = self.size[1] - self.left - self.new_w, self.size[0] - self.top - self.new_h
+
+    def __len__(self):
+        return len(self.frame_hw)
+
+
+def _letterbox_size(size, style: str):
+    if style not in LETTERBOX_RULES:
+        raise ValueError("style must be 'yolov3' or 'yolov5', got %r" % (style,))
+    out = (int(size), int(size)) if np.ndim(size) == 0 else (int(size[0]), int(size[1]))
+    if style == "yolov3" and out[0] != out[1]:
+        raise ValueError("the yolov3 letterbox is square, got %r" % (size,))
+    return out
+
+
+def letterbox_geometry(frame_hw, size, style: str = "yolov3") -> LetterboxGeometry:
+    """The letterbox of frames of ``frame_hw`` = (height, width) or (n, 2) to ``size`` (an int, or (out_h, out_w) for ``"yolov5"``),
+    on the host (``hrn_letterbox_geometry``, no GPU): ``style="yolov3"`` is ``letterbox(mode='square')`` of the reference's YOLOv3
+    wrapper, ``"yolov5"`` its YOLOv5 wrapper's ``letterbox(auto=False, scaleFill=False)``.  ValueError where the resized frame would
+    be empty (cv2.resize raises there)."""
+    out = _letterbox_size(size, style)
+    hw = np.ascontiguousarray(np.asarray(frame_hw, dtype=np.int32).reshape(-1, 2))
+    table = (_lib.Letterbox * max(len(hw), 1))()
+    lib = _lib.load()
+    rc = lib.hrn_letterbox_geometry(LETTERBOX_RULES[style], hw.ctypes.data, len(hw), out[0], out[1], ctypes.addressof(table))
+    if rc != 0:
+        raise ValueError("hrn_letterbox_geometry: " + lib.hrn_letterbox_last_error().decode())
+    return LetterboxGeometry(style, out, hw, table)
+
+
+def detection_arguments(dets_shape, geometry: LetterboxGeometry, counts, conf_thres, classes, class_col, compact):
+    """the host arguments ``detections_to_frame`` and ``NativeHRNet.detections_to_frame`` share: (start int32 (P + 1), threshold,
+    class column, class ids int32, flags)"""
+    if len(dets_shape) != 2 or dets_shape[1] < 5:
+        raise ValueError("dets must be (n, >=5), got %s" % (tuple(dets_shape),))
+    n, P = int(dets_shape[0]), len(geometry)
+    if counts is None:
+        if P != 1:
+            raise ValueError("%d frames need counts (rows per frame)" % P)
+        counts = [n]
+    start = _segments(counts, n, "rows")
+    if len(start) != P + 1:
+        raise ValueError("counts has %d entries for %d frames" % (len(start) - 1, P))
+    ids = np.ascontiguousarray(np.asarray([] if classes is None else classes, dtype=np.int32).reshape(-1))
+    if len(ids) > 16:
+        raise ValueError("at most 16 classes")
+    col = int(dets_shape[1]) if classes is None else int(class_col)
+    thres = float("-inf") if conf_thres is None else float(conf_thres)
+    return start, thres, col, ids, 1 if compact else 0
+
+
+def detections_to_frame(dets, geometry: LetterboxGeometry, counts=None, conf_thres=None, classes=None, compact=True, conf_col: int = 4,
+                        class_col: int = -1):
+    """A detector's rows from letterbox coordinates back to the frame, on the host (``hrn_detections_to_frame``, no GPU):
+    ``filter_classes`` + ``scale_coords`` of the reference's YOLOv3 wrapper, or the confidence / class filter and
+    ``(x - dw) / ratio`` of its YOLOv5 wrapper, selected by ``geometry.style``.
+
+    ``dets`` (n, >=5) float32 rows ``x1, y1, x2, y2, confidence, ...`` after the detector's NMS; ``geometry`` from
+    ``letterbox_geometry`` / ``detector_input``; ``counts``: rows per frame (one frame: may be None); ``conf_thres``: keep rows with
+    ``row[conf_col] >= conf_thres`` in float32 (None: everybody); ``classes``: up to 16 accepted ids of column ``class_col``
+    (negative: from the end; None: no class filter).  Returns ``(rows (n, stride) float32, counts (P,) int32, status (n,) int32)``:
+    kept rows mapped (columns beyond the fourth unchanged), every other row zeros; ``compact`` moves the kept rows of each frame to
+    the front of its segment in their order; ``status`` per input row: 0 kept, 1 below the threshold, 2 other class, 5 not finite."""
+    d = np.ascontiguousarray(np.asarray(dets, dtype=np.float32))
+    start, thres, col, ids, flags = detection_arguments(d.shape, geometry, counts, conf_thres, classes, class_col, compact)
+    out, status = np.empty_like(d), np.empty((len(d),), np.int32)
+    kept = np.empty((len(geometry),), np.int32)
+    lib = _lib.load()
+    rc = lib.hrn_detections_to_frame(geometry.rule, d.ctypes.data, int(d.shape[1]), start.ctypes.data, len(geometry),
+                                     ctypes.addressof(geometry.table), geometry.frame_hw.ctypes.data, geometry.size[0], geometry.size[1],
+                                     int(conf_col), ctypes.c_float(thres), col, ids.ctypes.data, len(ids), flags, out.ctypes.data,
+                                     kept.ctypes.data, status.ctypes.data)
+    if rc != 0:
+        raise ValueError("hrn_detections_to_frame: " + lib.hrn_letterbox_last_error().decode())
+    return out, kept, status

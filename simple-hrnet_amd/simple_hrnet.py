@@ -22,6 +22,13 @@ different, and why:
   nobody -- and otherwise cuts the people from the new frame where their joints were in the previous one
   (``NativeHRNet.track_frame``, on the GPU; ``track_args`` = its ``threshold`` / ``min_joints`` / ``scale`` / ``min_side``).  People
   who cannot be followed (too few confident joints, or all of them beyond the frame) are dropped from the returned arrays;
+* ``device_detector`` (opt-in, instead of ``detector``): a detector that takes and returns DEVICE tensors -- an object with
+  ``predict_tensor(x)`` (``x``: the letterboxed (n, 3, size, size) float32 RGB batch ``NativeHRNet.detector_input`` made; returns,
+  per image, a device tensor of its NMS-ed rows ``x1, y1, x2, y2, confidence, ...`` in LETTERBOX coordinates, or None) and the
+  attributes ``size``, ``style`` (``"yolov3"`` / ``"yolov5"``), ``conf_thres`` and ``classes`` (either may be None).  The letterbox,
+  the filters and the way back to frame coordinates run on the GPU (``detector_input`` -> ``predict_tensor`` ->
+  ``detections_to_frame`` -> ``preprocess_frames_dev``); only the number of people per image is read back.  A box the host path
+  would refuse with an error (degenerate, outside the frame) goes through as an all-padding crop instead;
 * devices: ``'cuda:N'`` is that GPU.  ``'cuda'`` (all GPUs) and ``'cuda:1,2'`` (the listed ones) are, in a plain Python
   process, ONE engine per listed GPU driven from this process (``native.MultiDeviceHRNet``: the crop batch of a
   ``predict()`` call is split by index range, one host thread per GPU) -- what ``DataParallel`` gives the reference with
@@ -138,7 +145,8 @@ class SimpleHRNet:
     def __init__(self, c, nof_joints, checkpoint_path, model_name="HRNet", resolution=(384, 288), interpolation=None,
                  multiperson=True, return_heatmaps=False, return_bounding_boxes=False, max_batch_size=32,
                  yolo_version="v3", yolo_model_def=None, yolo_class_path=None, yolo_weights_path=None, device=None,
-                 enable_tensorrt=False, *, detector=None, dtype="fp32", refine=None, redetect_every=1, track_args=None):
+                 enable_tensorrt=False, *, detector=None, dtype="fp32", refine=None, redetect_every=1, track_args=None,
+                 device_detector=None):
         refine_code(refine)   # (raises ValueError before any engine is built)
         self.refine = refine
         if int(redetect_every) != redetect_every or redetect_every < 1:
@@ -160,9 +168,13 @@ class SimpleHRNet:
         if self.redetect_every > 1 and len(self.devices) > 1:
             raise ValueError("redetect_every > 1 runs on one GPU (tracking is not sharded over devices)")
         self.device = torch.device("cuda", self.devices[0])      # where results are gathered / single-GPU work runs
-        if multiperson and detector is None:
+        if detector is not None and device_detector is not None:
+            raise ValueError("pass detector= or device_detector=, not both")
+        if device_detector is not None and len(self.devices) > 1:
+            raise ValueError("device_detector= runs on one GPU (the detector link is not sharded over devices)")
+        if multiperson and detector is None and device_detector is None:
             raise ValueError("multiperson=True needs detector= (the reference's YOLO wrappers are un-vendored third-party code)")
-        self.detector = detector
+        self.detector, self.device_detector = detector, device_detector
         if len(self.devices) == 1:
             self.model = NativeHRNet(c, nof_joints, self.resolution, dtype, max_batch=max_batch_size, device=self.device,
                                      model_name=model_name)
@@ -218,6 +230,9 @@ class SimpleHRNet:
             return self._result(hm.cpu().numpy(), boxes, pts.cpu().numpy())
         if self.redetect_every > 1:
             return self._one_frame_tracked(image)
+        if self.device_detector is not None:
+            out = self._one_frame_detected_dev(image)
+            return self._nobody() if out is None else self._result(None if out[2] is None else out[2].cpu().numpy(), out[0], out[1].cpu().numpy())
         found = self.detector.predict_single(image)
         if found is None or len(found) == 0:
             return self._nobody()
@@ -226,6 +241,44 @@ class SimpleHRNet:
         boxes, pts = out[0], out[1].cpu().numpy()
         hm = out[2].cpu().numpy() if self.return_heatmaps else None
         return self._result(hm, boxes, pts)
+
+    def _device_detections(self, frames):
+        """the detector link on the GPU for device frames (one (Hf, Wf, 3) tensor or a stack): ``detector_input`` ->
+        ``predict_tensor`` -> ``detections_to_frame``.  Returns ``(rows, found, kept)``: the compacted rows in frame coordinates
+        on the device (None when the detector found nothing anywhere), per image whether the detector returned rows at all, and
+        the number of rows kept per image -- the one thing read back."""
+        dd = self.device_detector
+        x, geometry = self.model.detector_input(frames, dd.size, dd.style)
+        per_image = list(dd.predict_tensor(x))
+        if len(per_image) != len(geometry):
+            raise ValueError("predict_tensor returned %d results for %d images" % (len(per_image), len(geometry)))
+        found = [t is not None for t in per_image]
+        counts = [int(t.shape[0]) if t is not None else 0 for t in per_image]
+        if not any(counts):
+            return None, found, [0] * len(counts)
+        dets = torch.cat([t.to(self.device, torch.float32) for t in per_image if t is not None and len(t)], 0)
+        rows, kept, _ = self.model.detections_to_frame(dets, geometry, counts=counts, conf_thres=getattr(dd, "conf_thres", None),
+                                                       classes=getattr(dd, "classes", None), compact=True)
+        kept = kept.cpu().numpy().tolist()
+        if len(counts) > 1:   # the kept rows lead each image's segment: gather them (the index is host arithmetic on the counts)
+            starts = np.concatenate([[0], np.cumsum(counts)])
+            index = np.concatenate([np.arange(s, s + k) for s, k in zip(starts, kept)]).astype(np.int64)
+            rows = rows[torch.from_numpy(index).to(self.device)]
+        else:
+            rows = rows[:kept[0]]
+        return rows, found, kept
+
+    def _one_frame_detected_dev(self, image):
+        """the single-image multi-person path behind ``device_detector``: ``(boxes int32 numpy, pts on the GPU, heat-maps on the
+        GPU or None)``, or None when nobody is kept"""
+        frame = torch.from_numpy(np.ascontiguousarray(image)).to(self.device)
+        rows, _, kept = self._device_detections(frame)
+        if rows is None or kept[0] == 0:
+            return None
+        images, boxes_dev, _ = self.model.preprocess_frames_dev(frame, rows[:, :4], variant="pad")
+        out = self.model.predict_crops(images, boxes_dev, return_heatmaps=self.return_heatmaps, **self._refine_kw())
+        hm, pts = out if self.return_heatmaps else (None, out)
+        return boxes_dev.cpu().numpy(), pts, hm
 
     def _nobody(self):                                                              # :331
         return self._result(np.zeros(self._hm_shape(0), np.float32), np.empty((0, 4), np.int32), np.empty((0, 0, 3), dtype=np.float32))
@@ -237,6 +290,12 @@ class SimpleHRNet:
         call, self._calls = self._calls, self._calls + 1
         if call % self.redetect_every == 0 or self._last_pts is None:
             self._last_pts = None
+            if self.device_detector is not None:
+                out = self._one_frame_detected_dev(image)
+                if out is None:
+                    return self._nobody()
+                self._last_pts = out[1]
+                return self._result(None if out[2] is None else out[2].cpu().numpy(), out[0], out[1].cpu().numpy())
             found = self.detector.predict_single(image)
             if found is None or len(found) == 0:
                 return self._nobody()
@@ -260,6 +319,8 @@ class SimpleHRNet:
             boxes = np.repeat(np.asarray([[0, 0, images.shape[2], images.shape[1]]], dtype=np.float32), len(images), axis=0)
             hm, pts = self.model.predict_crops(x, boxes, return_heatmaps=True, **self._refine_kw())
             return self._result(hm.cpu().numpy(), boxes, np.expand_dims(pts.cpu().numpy(), axis=1))   # :475
+        if self.device_detector is not None:
+            return self._frame_stack_detected_dev(images)
         per_frame = self.detector.predict(images)
         counts = [None if found is None else len(found) for found in per_frame]
         dets = [None if not n else np.asarray(found.cpu() if isinstance(found, torch.Tensor) else found, np.float32)[:, :4]
@@ -276,6 +337,23 @@ class SimpleHRNet:
             crops, boxes = torch.cat([p[0] for p in parts], 0), np.concatenate([p[1] for p in parts], 0)
         out = self.model.predict_crops(crops, boxes, return_heatmaps=self.return_heatmaps, **self._refine_kw())
         hm, pts = (out[0].cpu().numpy(), out[1].cpu().numpy()) if self.return_heatmaps else (None, out.cpu().numpy())
+        return self._per_frame(counts, hm, boxes, pts)
+
+    def _frame_stack_detected_dev(self, images):
+        """the stack path behind ``device_detector``: the stack crosses PCIe once; everybody is cut by one pre-path call"""
+        stack = torch.from_numpy(np.ascontiguousarray(images)).to(self.device)
+        rows, found, kept = self._device_detections(stack)
+        if rows is None or not any(kept):                                            # :477-484
+            pts = [np.zeros((0, self.nof_joints, 3), dtype=np.float32) for _ in found]
+            return self._result(np.zeros(self._hm_shape(0), np.float32), np.asarray([], dtype=np.int32), pts)
+        frame_index = np.repeat(np.arange(len(kept), dtype=np.int32), kept)
+        crops, boxes_dev, _ = self.model.preprocess_frames_dev(stack, rows[:, :4], frame_index=frame_index, variant="clamp")
+        out = self.model.predict_crops(crops, boxes_dev, return_heatmaps=self.return_heatmaps, **self._refine_kw())
+        hm, pts = (out[0].cpu().numpy(), out[1].cpu().numpy()) if self.return_heatmaps else (None, out.cpu().numpy())
+        counts = [k if f else None for f, k in zip(found, kept)]
+        return self._per_frame(counts, hm, boxes_dev.cpu().numpy(), pts)
+
+    def _per_frame(self, counts, hm, boxes, pts):
         pts_b, hm_b, boxes_b, index = [], [], [], 0                                  # :445-472: re-add the batch axis
         for n in counts:
             if n is not None:
