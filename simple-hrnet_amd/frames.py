@@ -1,0 +1,223 @@
+"""What a caller's "frames" are, and how they become device memory plus a frame table of the C ABI (include/hrnet_mi355.h).
+
+A frame is an (Hf, Wf, 3) uint8 BGR tensor or array, or a ``YuvFrame`` (NV12 / I420); the frames of a call are one frame, an
+(F, Hf, Wf, 3) stack, or a sequence of frames of any sizes with None for a frame nobody is cut from -- all of one kind.
+``Frames`` is that list together with its kind, its sizes and its ``hrn_frame`` / ``hrn_yuv_frame`` / ``hrn_canvas`` table.
+The coercions every caller's tensor-or-array-like goes through (``as_tensor``, ``host_array``, ``device_tensor``) live here too.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+
+PIX_FORMATS = {"nv12": 1, "i420": 2}          # include/hrnet_mi355.h: HRN_PIX_*
+YUV_MATRICES = {"bt601": 0, "bt709": 1}        # HRN_YUV_BT601 / _BT709
+YUV_RANGES = {"limited": 0, "full": 1}         # HRN_YUV_LIMITED / _FULL
+
+
+NUMPY_DTYPES = {torch.int32: np.int32, torch.float32: np.float32}   # what device_tensor converts an array-like to on the host
+
+
+def as_tensor(x, dtype=None) -> torch.Tensor:
+    """a tensor as it is (host or device); anything else as a host tensor over its contiguous array (of ``dtype``, when given)"""
+    return x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=dtype))
+
+
+def host_array(x, dtype) -> np.ndarray:
+    """a tensor (host or device: it is read back) or array-like as a host array of ``dtype``"""
+    return np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=dtype)
+
+
+def device_tensor(x, device, dtype, shape=None) -> torch.Tensor:
+    """a tensor or array-like as a contiguous ``dtype`` tensor on ``device``, of ``shape`` when given.  A tensor that already
+    is all that is used where it lies -- what is written into the result is written into ``x``; anything else is converted
+    (an array-like on the host when ``dtype`` is in ``NUMPY_DTYPES``, else on the device) or uploaded (once, asynchronously)."""
+    x = as_tensor(x, NUMPY_DTYPES.get(dtype)).to(device, dtype=dtype, non_blocking=True)
+    return (x if shape is None else x.reshape(shape)).contiguous()
+
+
+class YuvFrame:
+    """One 8-bit 4:2:0 video frame as a decoder or ``ffmpeg -pix_fmt nv12|yuv420p`` delivers it, accepted wherever a BGR frame is
+    (``preprocess_frame(s)``, ``predict_frame(s)``, ``predict_clip``) and by ``NativeHRNet.yuv_to_bgr``.
+
+    ``data``: uint8 tensor or array of any shape, host or device, in the rawvideo layout: ``height`` rows of ``pitch`` bytes of Y,
+    then the chroma -- ``"nv12"``: ``height / 2`` rows of ``pitch`` bytes of interleaved U, V; ``"i420"``: ``height / 2`` rows of
+    ``pitch / 2`` bytes of U, then the same of V.  ``pitch`` defaults to ``width``; bytes of a row beyond the width are never
+    read into a result.  ``matrix``: ``"bt601"`` or ``"bt709"``; ``range``: ``"limited"`` (16..235) or ``"full"``.
+    ValueError on an odd or non-positive size, a pitch below the width (odd, for i420), a buffer shorter than ``nbytes``, or
+    an unknown format, matrix or range."""
+
+    def __init__(self, data, height: int, width: int, format: str = "nv12", matrix: str = "bt601", range: str = "limited",  # noqa: A002
+                 pitch: Optional[int] = None):
+        if format not in PIX_FORMATS:
+            raise ValueError("format must be 'nv12' or 'i420', got %r" % (format,))
+        if matrix not in YUV_MATRICES:
+            raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
+        if range not in YUV_RANGES:
+            raise ValueError("range must be 'limited' or 'full', got %r" % (range,))
+        height, width = int(height), int(width)
+        if height <= 0 or width <= 0 or height % 2 or width % 2:
+            raise ValueError("a 4:2:0 frame has an even, positive height and width, got %d x %d" % (height, width))
+        pitch = width if pitch is None else int(pitch)
+        if pitch < width:
+            raise ValueError("pitch %d is below the width %d" % (pitch, width))
+        if format == "i420" and pitch % 2:
+            raise ValueError("an i420 frame has an even pitch (its chroma rows are pitch / 2 bytes), got %d" % pitch)
+        data = as_tensor(data)
+        if data.dtype != torch.uint8:
+            raise ValueError("data must be uint8")
+        self.height, self.width, self.pitch = height, width, pitch
+        self.format, self.matrix, self.range = format, matrix, range
+        data = data.contiguous().view(-1)
+        if data.numel() < self.nbytes:
+            raise ValueError("a %d x %d %s frame of pitch %d has %d bytes, the buffer has %d"
+                             % (height, width, format, pitch, self.nbytes, data.numel()))
+        self.data = data[:self.nbytes]
+
+    @property
+    def nbytes(self) -> int:
+        return self.pitch * self.height * 3 // 2
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def to(self, device, non_blocking: bool = False) -> "YuvFrame":
+        """the same frame with its bytes on ``device`` (itself when they already are)"""
+        data = self.data.to(device, non_blocking=non_blocking)
+        return self if data is self.data else YuvFrame(data, self.height, self.width, self.format, self.matrix, self.range, self.pitch)
+
+    def _fill(self, entry: "_lib.YuvFrameC", base: Optional[int] = None):
+        """``entry`` = the ``hrn_yuv_frame`` of this frame, its bytes at device address ``base`` (default: where ``data`` is)"""
+        base = self.data.data_ptr() if base is None else base
+        luma = self.pitch * self.height
+        entry.y, entry.u = base, base + luma
+        entry.v = base + luma + (self.pitch // 2) * (self.height // 2) if self.format == "i420" else None
+        entry.height, entry.width, entry.pitch_y = self.height, self.width, self.pitch
+        entry.pitch_c = self.pitch if self.format == "nv12" else self.pitch // 2
+        entry.format, entry.matrix, entry.range = PIX_FORMATS[self.format], YUV_MATRICES[self.matrix], YUV_RANGES[self.range]
+
+
+def _frame_kind(frames) -> bool:
+    """True when the (non-None) frames are ``YuvFrame``s, False when none is; a mixture raises ValueError"""
+    kinds = {isinstance(f, YuvFrame) for f in frames if f is not None}
+    if len(kinds) > 1:
+        raise ValueError("the frames of one call are all YuvFrames or all BGR frames, not a mixture")
+    return kinds == {True}
+
+
+def _check_frame(frame, k: int):
+    if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3 or min(frame.shape[:2]) < 1:
+        raise ValueError("frame %d must be (H, W, 3) uint8 BGR" % k)
+
+
+def _bgr_rows(t: torch.Tensor) -> bool:
+    """an (H, W, 3) tensor the overlay can be drawn into where it lies: packed pixels, rows any pitch >= 3 W apart"""
+    return t.stride(2) == 1 and t.stride(1) == 3 and (t.shape[0] == 1 or t.stride(0) >= 3 * t.shape[1])
+
+
+def frame_stack(frames, crops: bool = True) -> torch.Tensor:
+    """``frames`` of ``warp_crops`` (``crops``) or ``resize_frames`` as an (F, Hf, Wf, 3) uint8 tensor (host or device, as
+    given); ValueError otherwise.  Only ``warp_crops`` refuses an empty stack and sides outside [1, 32766]."""
+    frames = as_tensor(frames)
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or (crops and frames.shape[0] < 1):
+        raise ValueError("frames must be (Hf, Wf, 3) or (F, Hf, Wf, 3) uint8 BGR")
+    if crops and (max(int(frames.shape[1]), int(frames.shape[2])) > 32766 or min(int(frames.shape[1]), int(frames.shape[2])) < 1):
+        raise ValueError("frame sides must be in [1, 32766]")
+    return frames
+
+
+def host_bytes(frame) -> torch.Tensor:
+    """the bytes of a host frame of ``predict_clip`` as a flat uint8 tensor: what is uploaded (a ``YuvFrame``: 1.5 bytes per pixel)"""
+    return frame.data if isinstance(frame, YuvFrame) else frame.view(-1)
+
+
+class Frames(list):
+    """The frames of one call: a list of (Hf, Wf, 3) uint8 tensors or of ``YuvFrame``s (``yuv``), None where a frame nobody is
+    cut from is left out."""
+
+    def __init__(self, frames=(), yuv: Optional[bool] = None):
+        super().__init__(frames)
+        self.yuv = _frame_kind(self) if yuv is None else yuv
+
+    @classmethod
+    def resident(cls, frames, device, one: bool = False) -> "Frames":
+        """``frames`` of ``preprocess_frames`` as contiguous frames on ``device``; a 4-D stack crosses PCIe in one copy and is
+        then indexed, a sequence frame by frame (once each).  A sequence of ``YuvFrame``s stays ``YuvFrame``s, now on the
+        device; one that mixes the two kinds raises ValueError.  ``one``: a single frame is taken as a sequence of one."""
+        if one and (isinstance(frames, YuvFrame) or (isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3)):
+            frames = [frames]
+        if isinstance(frames, np.ndarray) and frames.ndim == 4:
+            frames = as_tensor(frames)
+        if isinstance(frames, torch.Tensor):
+            if frames.dim() != 4:
+                raise ValueError("frames must be (F, Hf, Wf, 3) uint8 BGR or a sequence of (Hf, Wf, 3) frames")
+            stack = frames.to(device, non_blocking=True).contiguous()
+            out = [stack[k] for k in range(int(stack.shape[0]))]
+        else:
+            frames = list(frames)
+            if _frame_kind(frames):
+                return cls([None if f is None else f.to(device, non_blocking=True) for f in frames], True)
+            out = [None if f is None else as_tensor(f).to(device, non_blocking=True).contiguous() for f in frames]
+        for k, f in enumerate(out):
+            if f is not None:
+                _check_frame(f, k)
+        return cls(out, False)
+
+    @classmethod
+    def canvases(cls, frames, device) -> "Frames":
+        """the frames of ``draw_poses``: a frame on ``device`` stays where it is (it is drawn in place: ValueError when its
+        pixels are not packed), a host frame is uploaded; the rows of a BGR frame may be strided"""
+        yuv = _frame_kind(frames)
+        out = []
+        for k, f in enumerate(frames):
+            if f is None or yuv:
+                out.append(None if f is None else f.to(device, non_blocking=True))
+                continue
+            if not isinstance(f, torch.Tensor):
+                f = torch.from_numpy(f) if isinstance(f, np.ndarray) and all(s > 0 for s in f.strides) else as_tensor(f)
+            _check_frame(f, k)
+            if f.device != device:
+                f = f.to(device, non_blocking=True)
+                if not _bgr_rows(f):
+                    f = f.contiguous()
+            elif not _bgr_rows(f):
+                raise ValueError("frame %d cannot be drawn in place: its pixels must be packed (B, G, R) bytes in rows" % k)
+            out.append(f)
+        return cls(out, yuv)
+
+    def sizes(self) -> np.ndarray:
+        """(F, 2) int32 ``(height, width)`` per frame; zeros for None"""
+        return np.asarray([(0, 0) if f is None else ((f.height, f.width) if self.yuv else tuple(f.shape[:2])) for f in self],
+                          np.int32).reshape(-1, 2)
+
+    def table(self, bases=None, kind=None):
+        """the ``hrn_frame`` table of the frames (None: a null entry), the ``hrn_yuv_frame`` table when they are ``YuvFrame``s, or
+        a table of another ``kind`` (``_lib.CanvasC``: only there may a BGR frame have strided rows).  ``bases``: frame number ->
+        the device address its bytes were copied to (host frames in an arena); default: where each frame lies."""
+        kind = kind or (_lib.YuvFrameC if self.yuv else _lib.Frame)
+        table = (kind * max(len(self), 1))()
+        for k, f in enumerate(self):
+            if f is None:
+                continue
+            entry = table[k]
+            base = None if bases is None else bases[k]
+            if self.yuv:
+                f._fill(entry, base)
+                continue
+            if base is None:
+                base = f.data_ptr()
+            entry.height, entry.width = int(f.shape[0]), int(f.shape[1])
+            if kind is _lib.Frame:
+                entry.data = base
+            else:   # a canvas: the pixels of a BGR frame in `y`, its rows `pitch_y` bytes apart
+                entry.y = base
+                entry.pitch_y = max(int(f.stride(0)), 3 * int(f.shape[1]))
+                entry.format = 0
+        return table

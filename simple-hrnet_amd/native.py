@@ -10,13 +10,18 @@ PyTorch is used only as the container for device memory and for the current HIP 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import math
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
 from . import _lib
+from .frames import (PIX_FORMATS, YUV_MATRICES, YUV_RANGES, Frames, YuvFrame, _check_frame, _frame_kind, as_tensor,  # noqa: F401
+                     device_tensor, frame_stack, host_array, host_bytes)
+from .palettes import bgr_to_yuv_colors, embedded_palette, find_palette  # noqa: F401
 
 DTYPES = {"fp32": 0, "f32": 0, "float32": 0, torch.float32: 0, "bf16": 1, "bfloat16": 1, torch.bfloat16: 1,
           "fp16": 2, "f16": 2, "float16": 2, "half": 2, torch.float16: 2}
@@ -32,6 +37,40 @@ def refine_code(refine) -> int:
     return REFINE_MODES[refine]
 
 
+def crop_code(variant) -> int:
+    """HRN_CROP_* of a ``variant`` argument: "pad" or "clamp"; anything else raises ValueError"""
+    if variant not in ("pad", "clamp"):
+        raise ValueError("variant must be 'pad' or 'clamp'")
+    return 0 if variant == "pad" else 1
+
+
+DRAW_TILE = 32   # csrc/kernels.h: kDrawTile -- the rasteriser of draw_poses works on 32 x 32 tiles (tests place shapes across the borders)
+
+
+_PALETTE_CACHE: Dict[Tuple[str, int], np.ndarray] = {}   # (tests empty it here, so the cache stays in this module)
+
+
+def palette(name: str, samples: int = 16) -> np.ndarray:
+    """The colours ``draw_points`` / ``draw_skeleton`` derive from a matplotlib palette name (``misc/visualization.py:91-98``) as a
+    (C, 3) uint8 array of (B, G, R) rows: a listed palette's own colours, else ``samples`` colours sampled over [0, 1].  Evaluated
+    with matplotlib where it can be imported; without it the four palettes of the demo programs (``tab20``, ``Set2``,
+    ``gist_rainbow`` at 10 samples, ``jet`` at 8) come from stored tables and any other name raises ValueError."""
+    key = (str(name), int(samples))
+    if key not in _PALETTE_CACHE:
+        _PALETTE_CACHE[key] = find_palette(*key)
+    return _PALETTE_CACHE[key].copy()
+
+
+def _colors(spec, samples) -> np.ndarray:
+    """a palette name, or ready (C, 3) uint8 BGR colours"""
+    if isinstance(spec, str):
+        return palette(spec, samples)
+    c = np.asarray(spec)
+    if c.ndim != 2 or c.shape[1] != 3 or len(c) < 1 or c.dtype != np.uint8:
+        raise ValueError("colours must be a palette name or a (C, 3) uint8 array of (B, G, R) rows")
+    return np.ascontiguousarray(c)
+
+
 def _device_index(device) -> int:
     if isinstance(device, int):
         return device
@@ -39,19 +78,6 @@ def _device_index(device) -> int:
     if d.type != "cuda":
         raise ValueError("Wrong device name.")  # same message as SimpleHRNet.py:139
     return d.index if d.index is not None else torch.cuda.current_device()
-
-
-def _frame_stack(frames) -> torch.Tensor:
-    """``frames`` of ``warp_crops`` as an (F, Hf, Wf, 3) uint8 tensor (host or device, as given); ValueError otherwise"""
-    if not isinstance(frames, torch.Tensor):
-        frames = torch.from_numpy(np.ascontiguousarray(frames))
-    if frames.dim() == 3:
-        frames = frames.unsqueeze(0)
-    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
-        raise ValueError("frames must be (Hf, Wf, 3) or (F, Hf, Wf, 3) uint8 BGR")
-    if max(int(frames.shape[1]), int(frames.shape[2])) > 32766 or min(int(frames.shape[1]), int(frames.shape[2])) < 1:
-        raise ValueError("frame sides must be in [1, 32766]")
-    return frames
 
 
 def group_frames(counts, limit: int, people_per_pass: Optional[int] = None):
@@ -93,184 +119,14 @@ def group_frames(counts, limit: int, people_per_pass: Optional[int] = None):
         yield group
 
 
-def _detections(detections) -> np.ndarray:
-    """one frame's detections as a contiguous (P, 4) float32 array (None: nobody); ValueError otherwise"""
+def _detections(detections, trim: bool = True) -> np.ndarray:
+    """one frame's detections as a contiguous (P, 4) float32 array (None: nobody; ``trim=False``: (P, >=4)); ValueError otherwise"""
     if detections is None:
         return np.zeros((0, 4), np.float32)
-    d = np.asarray(detections.cpu() if isinstance(detections, torch.Tensor) else detections, dtype=np.float32)
+    d = host_array(detections, np.float32)
     if d.ndim != 2 or (len(d) and d.shape[1] < 4):
         raise ValueError("detections must be (P, >=4)")
-    return np.ascontiguousarray(d[:, :4]) if len(d) else np.zeros((0, 4), np.float32)
-
-
-def _host_bytes(frame) -> torch.Tensor:
-    """the bytes of a host frame of ``predict_clip`` as a flat uint8 tensor: what is uploaded (a ``YuvFrame``: 1.5 bytes per pixel)"""
-    return frame.data if isinstance(frame, YuvFrame) else frame.view(-1)
-
-
-def _check_frame(frame, k: int):
-    if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3 or min(frame.shape[:2]) < 1:
-        raise ValueError("frame %d must be (H, W, 3) uint8 BGR" % k)
-
-
-PIX_FORMATS = {"nv12": 1, "i420": 2}          # include/hrnet_mi355.h: HRN_PIX_*
-YUV_MATRICES = {"bt601": 0, "bt709": 1}        # HRN_YUV_BT601 / _BT709
-YUV_RANGES = {"limited": 0, "full": 1}         # HRN_YUV_LIMITED / _FULL
-
-
-class YuvFrame:
-    """One 8-bit 4:2:0 video frame as a decoder or ``ffmpeg -pix_fmt nv12|yuv420p`` delivers it, accepted wherever a BGR frame is
-    (``preprocess_frame(s)``, ``predict_frame(s)``, ``predict_clip``) and by ``NativeHRNet.yuv_to_bgr``.
-
-    ``data``: uint8 tensor or array of any shape, host or device, in the rawvideo layout: ``height`` rows of ``pitch`` bytes of Y,
-    then the chroma -- ``"nv12"``: ``height / 2`` rows of ``pitch`` bytes of interleaved U, V; ``"i420"``: ``height / 2`` rows of
-    ``pitch / 2`` bytes of U, then the same of V.  ``pitch`` defaults to ``width``; bytes of a row beyond the width are never
-    read into a result.  ``matrix``: ``"bt601"`` or ``"bt709"``; ``range``: ``"limited"`` (16..235) or ``"full"``.
-    ValueError on an odd or non-positive size, a pitch below the width (odd, for i420), a buffer shorter than ``nbytes``, or
-    an unknown format, matrix or range."""
-
-    def __init__(self, data, height: int, width: int, format: str = "nv12", matrix: str = "bt601", range: str = "limited",  # noqa: A002
-                 pitch: Optional[int] = None):
-        if format not in PIX_FORMATS:
-            raise ValueError("format must be 'nv12' or 'i420', got %r" % (format,))
-        if matrix not in YUV_MATRICES:
-            raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
-        if range not in YUV_RANGES:
-            raise ValueError("range must be 'limited' or 'full', got %r" % (range,))
-        height, width = int(height), int(width)
-        if height <= 0 or width <= 0 or height % 2 or width % 2:
-            raise ValueError("a 4:2:0 frame has an even, positive height and width, got %d x %d" % (height, width))
-        pitch = width if pitch is None else int(pitch)
-        if pitch < width:
-            raise ValueError("pitch %d is below the width %d" % (pitch, width))
-        if format == "i420" and pitch % 2:
-            raise ValueError("an i420 frame has an even pitch (its chroma rows are pitch / 2 bytes), got %d" % pitch)
-        if not isinstance(data, torch.Tensor):
-            data = torch.from_numpy(np.ascontiguousarray(data))
-        if data.dtype != torch.uint8:
-            raise ValueError("data must be uint8")
-        self.height, self.width, self.pitch = height, width, pitch
-        self.format, self.matrix, self.range = format, matrix, range
-        data = data.contiguous().view(-1)
-        if data.numel() < self.nbytes:
-            raise ValueError("a %d x %d %s frame of pitch %d has %d bytes, the buffer has %d"
-                             % (height, width, format, pitch, self.nbytes, data.numel()))
-        self.data = data[:self.nbytes]
-
-    @property
-    def nbytes(self) -> int:
-        return self.pitch * self.height * 3 // 2
-
-    @property
-    def device(self):
-        return self.data.device
-
-    def to(self, device, non_blocking: bool = False) -> "YuvFrame":
-        """the same frame with its bytes on ``device`` (itself when they already are)"""
-        data = self.data.to(device, non_blocking=non_blocking)
-        return self if data is self.data else YuvFrame(data, self.height, self.width, self.format, self.matrix, self.range, self.pitch)
-
-    def _fill(self, entry: "_lib.YuvFrameC", base: Optional[int] = None):
-        """``entry`` = the ``hrn_yuv_frame`` of this frame, its bytes at device address ``base`` (default: where ``data`` is)"""
-        base = self.data.data_ptr() if base is None else base
-        luma = self.pitch * self.height
-        entry.y, entry.u = base, base + luma
-        entry.v = base + luma + (self.pitch // 2) * (self.height // 2) if self.format == "i420" else None
-        entry.height, entry.width, entry.pitch_y = self.height, self.width, self.pitch
-        entry.pitch_c = self.pitch if self.format == "nv12" else self.pitch // 2
-        entry.format, entry.matrix, entry.range = PIX_FORMATS[self.format], YUV_MATRICES[self.matrix], YUV_RANGES[self.range]
-
-
-def _frame_kind(frames) -> bool:
-    """True when the (non-None) frames are ``YuvFrame``s, False when none is; a mixture raises ValueError"""
-    kinds = {isinstance(f, YuvFrame) for f in frames if f is not None}
-    if len(kinds) > 1:
-        raise ValueError("the frames of one call are all YuvFrames or all BGR frames, not a mixture")
-    return kinds == {True}
-
-
-DRAW_TILE = 32   # csrc/kernels.h: kDrawTile -- the rasteriser of draw_poses works on 32 x 32 tiles (tests place shapes across the borders)
-
-# The palettes of the reference's demo programs (scripts/live-demo.py, misc/visualization.py defaults) as (B, G, R) rows, kept
-# here so that drawing works where matplotlib is not installed; tests/golden/palettes.json holds the reference's colours they
-# (and palette()) are pinned to.  Listed palettes (tab20, Set2) ignore the sample count; sampled ones are keyed by it.
-EMBEDDED_PALETTES = {
-    ("tab20", None): [[180, 119, 31], [232, 199, 174], [14, 127, 255], [120, 187, 255], [44, 160, 44], [138, 223, 152], [40, 39, 214],
-                      [150, 152, 255], [189, 103, 148], [213, 176, 197], [75, 86, 140], [148, 156, 196], [194, 119, 227], [210, 182, 247],
-                      [127, 127, 127], [199, 199, 199], [34, 189, 188], [141, 219, 219], [207, 190, 23], [229, 218, 158]],
-    ("Set2", None): [[165, 194, 102], [98, 141, 252], [203, 160, 141], [195, 138, 231], [84, 216, 166], [47, 217, 255], [148, 196, 229],
-                     [179, 179, 179]],
-    ("gist_rainbow", 10): [[41, 0, 255], [0, 110, 255], [0, 255, 249], [0, 255, 92], [59, 255, 0], [215, 255, 0], [255, 143, 0],
-                           [255, 0, 14], [255, 0, 167], [191, 0, 255]],
-    ("jet", 8): [[128, 0, 0], [255, 16, 0], [255, 164, 0], [183, 255, 64], [64, 255, 183], [0, 185, 255], [0, 48, 255], [0, 0, 128]],
-}
-_PALETTE_CACHE: Dict[Tuple[str, int], np.ndarray] = {}
-
-
-def embedded_palette(name: str, samples: int) -> Optional[np.ndarray]:
-    """the stored (C, 3) uint8 BGR table of a demo palette, or None"""
-    rows = EMBEDDED_PALETTES.get((name, None)) or EMBEDDED_PALETTES.get((name, int(samples)))
-    return None if rows is None else np.asarray(rows, np.uint8)
-
-
-def palette(name: str, samples: int = 16) -> np.ndarray:
-    """The colours ``draw_points`` / ``draw_skeleton`` derive from a matplotlib palette name (``misc/visualization.py:91-98``) as a
-    (C, 3) uint8 array of (B, G, R) rows: a listed palette's own colours, else ``samples`` colours sampled over [0, 1].  Evaluated
-    with matplotlib where it can be imported; without it the four palettes of the demo programs (``tab20``, ``Set2``,
-    ``gist_rainbow`` at 10 samples, ``jet`` at 8) come from stored tables and any other name raises ValueError."""
-    key = (str(name), int(samples))
-    if key in _PALETTE_CACHE:
-        return _PALETTE_CACHE[key].copy()
-    try:
-        import matplotlib
-    except ImportError:
-        matplotlib = None
-    if matplotlib is None:
-        out = embedded_palette(*key)
-        if out is None:
-            raise ValueError("palette %r with %d samples is not stored and matplotlib is not installed" % key)
-    else:
-        registry = getattr(matplotlib, "colormaps", None)       # matplotlib >= 3.5; before that the lookup lived in matplotlib.cm
-        if registry is None:
-            from matplotlib import cm
-            cmap = cm.get_cmap(key[0])
-        elif key[0] in registry:
-            cmap = registry[key[0]]
-        else:
-            raise ValueError("matplotlib has no palette %r" % key[0])
-        listed = getattr(cmap, "colors", None)                   # a listed palette's own colours; a continuous one is sampled
-        rgb = np.asarray(listed, np.float64) if listed is not None else np.asarray(cmap(np.linspace(0.0, 1.0, key[1])), np.float64)
-        out = np.rint(rgb[:, :3] * 255.0).astype(np.uint8)[:, ::-1]   # 8 bits per channel, rounded half to even; R, G, B -> B, G, R
-    _PALETTE_CACHE[key] = np.ascontiguousarray(out)
-    return _PALETTE_CACHE[key].copy()
-
-
-def bgr_to_yuv_colors(colors, matrix: str = "bt601", range: str = "limited") -> np.ndarray:  # noqa: A002
-    """(C, 3) uint8 (B, G, R) colours as (Y, U, V) of a matrix and range (``hrn_yuv_from_bgr``: the float64 forward formula of the
-    conversion ``YuvFrame``s are read with, rounded once): what ``draw_poses`` draws with on a ``YuvFrame``."""
-    if matrix not in YUV_MATRICES or range not in YUV_RANGES:
-        raise ValueError("matrix must be 'bt601' or 'bt709' and range 'limited' or 'full', got %r, %r" % (matrix, range))
-    c = np.ascontiguousarray(np.asarray(colors, dtype=np.uint8).reshape(-1, 3))
-    out = np.empty_like(c)
-    rc = _lib.load().hrn_yuv_from_bgr(YUV_MATRICES[matrix], YUV_RANGES[range], c.ctypes.data, len(c), out.ctypes.data)
-    if rc != 0:
-        raise RuntimeError("hrn_yuv_from_bgr failed (%d)" % rc)
-    return out
-
-
-def _colors(spec, samples) -> np.ndarray:
-    """a palette name, or ready (C, 3) uint8 BGR colours"""
-    if isinstance(spec, str):
-        return palette(spec, samples)
-    c = np.asarray(spec)
-    if c.ndim != 2 or c.shape[1] != 3 or len(c) < 1 or c.dtype != np.uint8:
-        raise ValueError("colours must be a palette name or a (C, 3) uint8 array of (B, G, R) rows")
-    return np.ascontiguousarray(c)
-
-
-def _bgr_rows(t: torch.Tensor) -> bool:
-    """an (H, W, 3) tensor the overlay can be drawn into where it lies: packed pixels, rows any pitch >= 3 W apart"""
-    return t.stride(2) == 1 and t.stride(1) == 3 and (t.shape[0] == 1 or t.stride(0) >= 3 * t.shape[1])
+    return np.ascontiguousarray(d[:, :4] if trim else d) if len(d) else np.zeros((0, 4), np.float32)
 
 
 def _warp_arguments(nframes: int, size_wh, centers, scales, rotations, frame_index, pixel_std, matrices):
@@ -314,6 +170,53 @@ def _warp_arguments(nframes: int, size_wh, centers, scales, rotations, frame_ind
             raise ValueError("frame_index outside [0, %d)" % nframes)
         fi = np.ascontiguousarray(fi, dtype=np.int32)
     return m, fi
+
+
+class UploadPipeline:
+    """Two device buffers ("slots") filled in turn on a copy stream while the stream that was current at construction (the
+    compute stream) works on the other one: the plumbing of ``predict_stream`` and ``predict_clip``.  Per item the caller
+    takes ``buffer(slot, ...)``, copies inside ``with filling(slot)``, and on the compute stream calls ``ready(slot)`` before
+    the work that reads the slot and ``release(slot)`` after it."""
+
+    def __init__(self, device):
+        self.device = device
+        self.compute = torch.cuda.current_stream(device)
+        self.copy = torch.cuda.Stream(device)
+        self.slots = [None, None]
+        self.landed = [torch.cuda.Event(), torch.cuda.Event()]
+        self.consumed = [None, None]
+        self.copy.wait_stream(self.compute)   # the first upload must not overtake the compute stream either (see buffer)
+
+    def buffer(self, slot: int, dtype, shape, at_least: Optional[int] = None) -> torch.Tensor:
+        """the slot's device buffer as long as it has ``dtype`` and ``at_least`` elements (default: those of ``shape``), else a
+        new one of ``shape`` in its place"""
+        have = self.slots[slot]
+        if have is None or have.dtype != dtype or have.numel() < (math.prod(shape) if at_least is None else at_least):
+            # a new block comes from the caching allocator on the COMPUTE stream and may be recycled memory that kernels already
+            # queued there still read: the upload into it must not overtake them
+            self.slots[slot] = torch.empty(shape, dtype=dtype, device=self.device)
+            self.slots[slot].record_stream(self.copy)
+            self.copy.wait_stream(self.compute)
+        return self.slots[slot]
+
+    @contextlib.contextmanager
+    def filling(self, slot: int):
+        """the scope of the copies into the slot: on the copy stream, after the work that read the slot last; what is copied has
+        landed when the scope ends"""
+        with torch.cuda.stream(self.copy):
+            if self.consumed[slot] is not None:
+                self.copy.wait_event(self.consumed[slot])
+            yield
+            self.landed[slot].record(self.copy)
+
+    def ready(self, slot: int):
+        """the compute stream goes on when the copies into the slot have landed"""
+        self.compute.wait_event(self.landed[slot])
+
+    def release(self, slot: int):
+        """the work queued on the compute stream so far is the last that reads the slot"""
+        self.consumed[slot] = torch.cuda.Event()
+        self.consumed[slot].record(self.compute)
 
 
 class NativeHRNet:
@@ -368,6 +271,16 @@ class NativeHRNet:
     def _check(self, rc: int, what: str):
         if rc != 0:
             raise RuntimeError("%s failed (%d): %s" % (what, rc, self._lib.hrn_last_error(self._h).decode()))
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device_index).cuda_stream
+
+    def _launch(self, name: str, *args):
+        """the one way into a GPU entry of the library: ``name(handle, *args, current stream)`` on the engine's device;
+        RuntimeError with the library's message when it refuses"""
+        with torch.cuda.device(self.device_index):
+            rc = getattr(self._lib, name)(self._h, *args, self._stream())
+        self._check(rc, name)
 
     # -- nn.Module look-alikes the reference calls on self.model (SimpleHRNet.py:141-142) --------
     def eval(self):
@@ -428,12 +341,13 @@ class NativeHRNet:
             return torch.as_tensor(raw, device=self.torch_device)
 
     def adopt_weights(self):
-        self._check(self._lib.hrn_adopt_weights(self._h), "hrn_adopt_weights")
+        rc = self._lib.hrn_adopt_weights(self._h)
+        self._check(rc, "hrn_adopt_weights")
 
     def read_blob(self, offset: int, nbytes: int) -> np.ndarray:
         out = np.empty(nbytes, dtype=np.uint8)
-        self._check(self._lib.hrn_weight_blob_read(self._h, offset, out.ctypes.data_as(ctypes.c_void_p), nbytes),
-                    "hrn_weight_blob_read")
+        rc = self._lib.hrn_weight_blob_read(self._h, offset, out.ctypes.data_as(ctypes.c_void_p), nbytes)
+        self._check(rc, "hrn_weight_blob_read")
         return out
 
     # -- the hot path ---------------------------------------------------------------------------
@@ -449,9 +363,6 @@ class NativeHRNet:
             raise ValueError("images live on %s, engine on cuda:%d" % (images.device, self.device_index))
         return images.to(torch.float32).contiguous()
 
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device_index).cuda_stream
-
     def __call__(self, images: torch.Tensor) -> torch.Tensor:
         """``self.model(images)``: (n,3,H,W) fp32 -> heat-maps (n,J,H/4,W/4) fp32 on the same GPU."""
         x = self._images_ptr(images)
@@ -459,9 +370,7 @@ class NativeHRNet:
         h, w = self.resolution
         out = torch.empty((n, self.nof_joints, h // 4, w // 4), dtype=torch.float32, device=x.device)
         if n:
-            with torch.cuda.device(self.device_index):
-                self._check(self._lib.hrn_forward(self._h, x.data_ptr(), n, None, 0, None, out.data_ptr(),
-                                                  self._stream()), "hrn_forward")
+            self._launch("hrn_forward", x.data_ptr(), n, None, 0, None, out.data_ptr())
         return out
 
     forward = __call__
@@ -475,7 +384,7 @@ class NativeHRNet:
         mode = refine_code(refine)
         x = self._images_ptr(images)
         n = x.shape[0]
-        b = boxes if isinstance(boxes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(boxes))
+        b = as_tensor(boxes)
         if tuple(b.shape) != (n, 4):
             raise ValueError("boxes must have shape (%d,4), got %s" % (n, tuple(b.shape)))
         if b.dtype in (torch.int32, torch.int64, torch.int16, torch.uint8):
@@ -488,10 +397,8 @@ class NativeHRNet:
         hm = torch.empty((n, self.nof_joints, h // 4, w // 4), dtype=torch.float32,
                          device=x.device) if return_heatmaps else None
         if n:   # (mode 0 = HRN_REFINE_NONE: hrn_forward_refined is hrn_forward)
-            with torch.cuda.device(self.device_index):
-                self._check(self._lib.hrn_forward_refined(self._h, x.data_ptr(), n, b.data_ptr(), box_dtype, mode, pts.data_ptr(),
-                                                          hm.data_ptr() if hm is not None else None, self._stream()),
-                            "hrn_forward_refined")
+            self._launch("hrn_forward_refined", x.data_ptr(), n, b.data_ptr(), box_dtype, mode, pts.data_ptr(),
+                         hm.data_ptr() if hm is not None else None)
         return (hm, pts) if return_heatmaps else pts
 
     def predict_stream(self, batches, return_heatmaps: bool = False, refine: Optional[str] = None):
@@ -506,15 +413,8 @@ class NativeHRNet:
         are ready on the current stream; read them after a synchronize or through ``.cpu()``).  ``refine``: as in ``predict_crops``."""
         refine_code(refine)
         dev = self.torch_device
-        compute = torch.cuda.current_stream(dev)
-        copy = torch.cuda.Stream(dev)
         h, w = self.resolution
-        stage = [None, None]   # allocated for the first batch: fp32 NCHW or uint8 NHWC staging, by what the caller sends
-        # the staging blocks come from the caching allocator on the COMPUTE stream and may be recycled memory that
-        # kernels already queued there still read: the first upload must not overtake them
-        copy.wait_stream(compute)
-        landed = [torch.cuda.Event(), torch.cuda.Event()]
-        consumed = [None, None]
+        pipe = UploadPipeline(dev)   # its slots: fp32 NCHW or uint8 NHWC staging, by what the caller sends
         norm = [None, None]   # uint8 form: the normalised fp32 crops of each slot
 
         def upload(slot, item):
@@ -529,18 +429,10 @@ class NativeHRNet:
                 raise ValueError("uint8 crops must be (n, %d, %d, 3) BGR at the network's resolution" % (h, w))
             if not u8 and tuple(images.shape[1:]) != (3, h, w):   # (copy_ would broadcast or fail obscurely)
                 raise ValueError("float crops must be (n, 3, %d, %d) at the network's resolution" % (h, w))
-            want = (torch.uint8, (self.max_batch, h, w, 3)) if u8 else (torch.float32, (self.max_batch, 3, h, w))
-            if stage[slot] is None or stage[slot].dtype != want[0]:
-                # a staging block comes from the caching allocator on the COMPUTE stream and may be recycled memory that kernels already
-                # queued there still read: the upload into it must not overtake them
-                stage[slot] = torch.empty(want[1], dtype=want[0], device=dev)
-                stage[slot].record_stream(copy)
-                copy.wait_stream(compute)
-            with torch.cuda.stream(copy):
-                if consumed[slot] is not None:
-                    copy.wait_event(consumed[slot])              # the pass that read this buffer has finished
-                stage[slot][:n].copy_(images if u8 else images.to(torch.float32), non_blocking=True)
-                landed[slot].record(copy)
+            stage = pipe.buffer(slot, torch.uint8, (self.max_batch, h, w, 3)) if u8 else \
+                pipe.buffer(slot, torch.float32, (self.max_batch, 3, h, w))
+            with pipe.filling(slot):                             # the pass that read this buffer has finished
+                stage[:n].copy_(images if u8 else images.to(torch.float32), non_blocking=True)
             return n, boxes, u8
 
         it = iter(batches)
@@ -552,16 +444,15 @@ class NativeHRNet:
             n, boxes, u8 = pending
             nxt = next(it, None)
             pending = upload(slot ^ 1, nxt) if nxt is not None else None   # goes out while this batch computes
-            compute.wait_event(landed[slot])
+            pipe.ready(slot)
             if u8:   # identity size: colour flip + ToTensor + Normalize on the GPU, into ONE fp32 buffer per slot (340 MB at 256 crops)
                 if norm[slot] is None:
                     norm[slot] = torch.empty((self.max_batch, 3, h, w), dtype=torch.float32, device=dev)
-                x = self.resize_frames(stage[slot][:n], 0, out=norm[slot])
+                x = self.resize_frames(pipe.slots[slot][:n], 0, out=norm[slot])
             else:
-                x = stage[slot][:n]
+                x = pipe.slots[slot][:n]
             out = self.predict_crops(x, boxes, return_heatmaps=return_heatmaps, refine=refine)
-            consumed[slot] = torch.cuda.Event()
-            consumed[slot].record(compute)
+            pipe.release(slot)
             yield out
             k += 1
 
@@ -583,13 +474,10 @@ class NativeHRNet:
         preds = torch.empty((n, self.nof_joints, 2), dtype=torch.float32, device=x.device)
         maxvals = torch.empty((n, self.nof_joints, 1), dtype=torch.float32, device=x.device)
         if n:
-            with torch.cuda.device(self.device_index):
-                self._check(self._lib.hrn_forward_flip_tta(self._h, x.data_ptr(), n, fp.ctypes.data, len(fp),
-                                                           1 if post_processing and not dark else 0, hm.data_ptr(),
-                                                           preds.data_ptr(), maxvals.data_ptr(), self._stream()), "hrn_forward_flip_tta")
-                if dark:
-                    self._check(self._lib.hrn_refine_coords(self._h, hm.data_ptr(), n, REFINE_MODES["dark"], preds.data_ptr(),
-                                                            self._stream()), "hrn_refine_coords")
+            self._launch("hrn_forward_flip_tta", x.data_ptr(), n, fp.ctypes.data, len(fp), 1 if post_processing and not dark else 0,
+                         hm.data_ptr(), preds.data_ptr(), maxvals.data_ptr())
+            if dark:
+                self._launch("hrn_refine_coords", hm.data_ptr(), n, REFINE_MODES["dark"], preds.data_ptr())
         return hm, preds, maxvals
 
     def refine_coords(self, heatmaps, coords, mode: Optional[str]) -> torch.Tensor:
@@ -607,9 +495,7 @@ class NativeHRNet:
             raise ValueError("heatmaps must be (n,%d,%d,%d) and coords (n,%d,2), got %s and %s"
                              % (self.nof_joints, h // 4, w // 4, self.nof_joints, tuple(hm.shape), tuple(out.shape)))
         if n and code:
-            with torch.cuda.device(self.device_index):
-                self._check(self._lib.hrn_refine_coords(self._h, hm.data_ptr(), n, code, out.data_ptr(), self._stream()),
-                            "hrn_refine_coords")
+            self._launch("hrn_refine_coords", hm.data_ptr(), n, code, out.data_ptr())
         return out
 
     def preprocess_frame(self, frame: torch.Tensor, detections, variant: str = "pad") -> Tuple[torch.Tensor, np.ndarray, torch.Tensor]:
@@ -622,33 +508,24 @@ class NativeHRNet:
         path's enlarge-and-clamp (``SimpleHRNet.py:383-412``; call once per image of the stack).
         Returns ``(images (P,3,H,W) float32 on the GPU, boxes (P,4) int32 numpy, boxes on the GPU)`` -- bit-identical
         to the reference's ``ToPILImage -> Resize -> ToTensor -> Normalize`` of the RGB crops."""
-        if variant not in ("pad", "clamp"):
-            raise ValueError("variant must be 'pad' or 'clamp'")
+        crop = crop_code(variant)
         if isinstance(frame, YuvFrame):   # the same call over a one-frame table of hrn_preprocess_frames_yuv
-            frame = frame.to(self.torch_device, non_blocking=True)
+            frames = Frames([frame.to(self.torch_device, non_blocking=True)], True)
             dets = _detections(detections)
-            return self._preprocess_table(self._frame_table([frame]), 1, dets, np.zeros(len(dets), np.int32), variant)
-        if not isinstance(frame, torch.Tensor):
-            frame = torch.from_numpy(np.ascontiguousarray(frame))
+            return self._preprocess_table(frames.table(), 1, dets, np.zeros(len(dets), np.int32), variant)
+        frame = as_tensor(frame)
         if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3:
             raise ValueError("frame must be (H, W, 3) uint8 BGR")
         frame = frame.to(self.torch_device, non_blocking=True).contiguous()
-        dets = np.ascontiguousarray(np.asarray(detections.cpu() if isinstance(detections, torch.Tensor) else detections,
-                                               dtype=np.float32))
-        if dets.ndim != 2 or (len(dets) and dets.shape[1] < 4):
-            raise ValueError("detections must be (P, >=4)")
+        dets = _detections(detections, trim=False)   # the rows go to the library as they are, with their stride
         p = len(dets)
         h, w = self.resolution
         images = torch.empty((p, 3, h, w), dtype=torch.float32, device=self.torch_device)
         boxes = np.empty((p, 4), dtype=np.int32)
         boxes_dev = torch.empty((p, 4), dtype=torch.int32, device=self.torch_device)
         if p:
-            with torch.cuda.device(self.device_index):
-                rc = self._lib.hrn_preprocess_frame(self._h, frame.data_ptr(), int(frame.shape[0]), int(frame.shape[1]),
-                                                    dets.ctypes.data, int(dets.shape[1]), p, 0 if variant == "pad" else 1,
-                                                    images.data_ptr(),
-                                                    boxes.ctypes.data, boxes_dev.data_ptr(), self._stream())
-            self._check(rc, "hrn_preprocess_frame")
+            self._launch("hrn_preprocess_frame", frame.data_ptr(), int(frame.shape[0]), int(frame.shape[1]), dets.ctypes.data,
+                         int(dets.shape[1]), p, crop, images.data_ptr(), boxes.ctypes.data, boxes_dev.data_ptr())
         return images, boxes, boxes_dev
 
     def yuv_to_bgr(self, frame: YuvFrame) -> torch.Tensor:
@@ -661,8 +538,7 @@ class NativeHRNet:
         out = torch.empty((frame.height, frame.width, 3), dtype=torch.uint8, device=self.torch_device)
         entry = _lib.YuvFrameC()
         frame._fill(entry)
-        with torch.cuda.device(self.device_index):
-            self._check(self._lib.hrn_yuv_to_bgr(self._h, ctypes.byref(entry), out.data_ptr(), self._stream()), "hrn_yuv_to_bgr")
+        self._launch("hrn_yuv_to_bgr", ctypes.byref(entry), out.data_ptr())
         return out
 
     def draw_poses(self, frames, pts, skeleton, frame_index=None, person_ids=None, points_palette="tab20", points_samples: int = 16,
@@ -690,38 +566,15 @@ class NativeHRNet:
         items = [frames] if single else list(frames)
         if not items:
             raise ValueError("draw_poses needs at least one frame")
-        yuv = _frame_kind(items)
         dev = self.torch_device
-        canvases: List = []
-        table = (_lib.CanvasC * len(items))()
-        for k, f in enumerate(items):
-            if f is None:
-                canvases.append(None)
-                continue
-            if yuv:
-                f = f.to(dev, non_blocking=True)
-                f._fill(table[k])
-            else:
-                if not isinstance(f, torch.Tensor):
-                    f = torch.from_numpy(f if isinstance(f, np.ndarray) and all(s > 0 for s in f.strides) else np.ascontiguousarray(f))
-                _check_frame(f, k)
-                if f.device != dev:
-                    f = f.to(dev, non_blocking=True)
-                    if not _bgr_rows(f):
-                        f = f.contiguous()
-                elif not _bgr_rows(f):
-                    raise ValueError("frame %d cannot be drawn in place: its pixels must be packed (B, G, R) bytes in rows" % k)
-                e = table[k]
-                e.y, e.height, e.width = f.data_ptr(), int(f.shape[0]), int(f.shape[1])
-                e.pitch_y, e.format = max(int(f.stride(0)), 3 * int(f.shape[1])), 0
-            canvases.append(f)
-        if not isinstance(pts, torch.Tensor):
-            pts = torch.from_numpy(np.ascontiguousarray(np.asarray(pts, dtype=np.float32)))
+        canvases = Frames.canvases(items, dev)
+        table = canvases.table(kind=_lib.CanvasC)
+        pts = as_tensor(pts, np.float32)
         if pts.dim() == 2:
             pts = pts.unsqueeze(0)
         if pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[1] < 1:
             raise ValueError("pts must be (J, 3) or (n, J, 3) (y, x, confidence)")
-        pts = pts.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+        pts = device_tensor(pts, dev, torch.float32)
         n, joints = int(pts.shape[0]), int(pts.shape[1])
         skel = np.ascontiguousarray(np.asarray(skeleton, dtype=np.int32).reshape(-1, 2))
         fi = None
@@ -744,21 +597,17 @@ class NativeHRNet:
             if len(ids) != n:
                 raise ValueError("person_ids must have one entry per person: %d for %d people" % (len(ids), n))
         pc, bc = _colors(points_palette, points_samples), _colors(skeleton_palette, skeleton_samples)
-        if yuv:
+        if canvases.yuv:
             spaces = {(f.matrix, f.range) for f in canvases if f is not None}
             if len(spaces) != 1:
                 raise ValueError("the YuvFrames of one draw_poses call share one matrix and range (the colours are converted once)")
             (matrix, range_), = spaces
             pc, bc = bgr_to_yuv_colors(pc, matrix, range_), bgr_to_yuv_colors(bc, matrix, range_)
-        entry, name = (self._lib.hrn_draw_poses, "hrn_draw_poses") if ids_dev is None else \
-            (self._lib.hrn_draw_poses_ids_dev, "hrn_draw_poses_ids_dev")
         index = (None if ids is None else ids.ctypes.data) if ids_dev is None else ids_dev.data_ptr()
-        with torch.cuda.device(self.device_index):
-            rc = entry(self._h, table, len(items), pts.data_ptr(), n, joints, None if fi is None else fi.ctypes.data,
-                       skel.ctypes.data if len(skel) else None, len(skel), pc.ctypes.data, len(pc), bc.ctypes.data, len(bc), index,
-                       0 if radius is None else int(radius), int(thickness), float(confidence_threshold), self._stream())
-        self._check(rc, name)
-        return canvases[0] if single else canvases
+        self._launch("hrn_draw_poses" if ids_dev is None else "hrn_draw_poses_ids_dev", table, len(items), pts.data_ptr(), n, joints,
+                     None if fi is None else fi.ctypes.data, skel.ctypes.data if len(skel) else None, len(skel), pc.ctypes.data, len(pc),
+                     bc.ctypes.data, len(bc), index, 0 if radius is None else int(radius), int(thickness), float(confidence_threshold))
+        return canvases[0] if single else list(canvases)
 
     def resize_frames(self, frames, interpolation: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The single-person pre-path (``multiperson=False``, ``SimpleHRNet.py:213-222`` / ``:355-366``) on the GPU:
@@ -770,13 +619,7 @@ class NativeHRNet:
         Follows OpenCV's published generic 8-bit path; equality with a particular cv2 build is not pinned (include/hrnet_mi355.h)."""
         if interpolation not in (0, 1, 2):
             raise ValueError("interpolation must be cv2.INTER_NEAREST (0), cv2.INTER_LINEAR (1) or cv2.INTER_CUBIC (2)")
-        if not isinstance(frames, torch.Tensor):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        if frames.dim() == 3:
-            frames = frames.unsqueeze(0)
-        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-            raise ValueError("frames must be (n, H, W, 3) uint8 BGR")
-        frames = frames.to(self.torch_device, non_blocking=True).contiguous()
+        frames = frame_stack(frames, crops=False).to(self.torch_device, non_blocking=True).contiguous()
         n, h, w = int(frames.shape[0]), *self.resolution
         if out is not None:
             if out.dtype != torch.float32 or out.device != self.torch_device or not out.is_contiguous() or \
@@ -786,10 +629,8 @@ class NativeHRNet:
         else:
             images = torch.empty((n, 3, h, w), dtype=torch.float32, device=self.torch_device)
         if n:
-            with torch.cuda.device(self.device_index):
-                rc = self._lib.hrn_resize_frames(self._h, frames.data_ptr(), n, int(frames.shape[1]), int(frames.shape[2]),
-                                                 int(interpolation), images.data_ptr(), self._stream())
-            self._check(rc, "hrn_resize_frames")
+            self._launch("hrn_resize_frames", frames.data_ptr(), n, int(frames.shape[1]), int(frames.shape[2]), int(interpolation),
+                         images.data_ptr())
         return images
 
     def warp_crops(self, frames, centers=None, scales=None, rotations=None, frame_index=None, pixel_std=200, matrices=None) -> torch.Tensor:
@@ -802,17 +643,15 @@ class NativeHRNet:
         explicit forward 2x3 ``matrices`` (n, 2, 3), frame -> crop.  ``frame_index`` (n,): the frame of each crop; None = crop i
         reads frame i (F == n) or the one frame (F == 1).  Returns (n, 3, H, W) float32 on the GPU, for any n.
         Follows warpAffine's 8-bit integer path (include/hrnet_mi355.h); equality with a particular cv2 build is not pinned."""
-        frames = _frame_stack(frames)
+        frames = frame_stack(frames)
         h, w = self.resolution
         m, fi = _warp_arguments(int(frames.shape[0]), (w, h), centers, scales, rotations, frame_index, pixel_std, matrices)
         frames = frames.to(self.torch_device, non_blocking=True).contiguous()
         n = len(m)
         images = torch.empty((n, 3, h, w), dtype=torch.float32, device=self.torch_device)
         if n:
-            with torch.cuda.device(self.device_index):
-                rc = self._lib.hrn_warp_crops(self._h, frames.data_ptr(), int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2]),
-                                              fi.ctypes.data, m.ctypes.data, n, images.data_ptr(), self._stream())
-            self._check(rc, "hrn_warp_crops")
+            self._launch("hrn_warp_crops", frames.data_ptr(), int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2]),
+                         fi.ctypes.data, m.ctypes.data, n, images.data_ptr())
         return images
 
     def decode_eval(self, images: torch.Tensor, flip_pairs, flip: bool = True, post_processing: Union[bool, str] = True):
@@ -852,11 +691,11 @@ class NativeHRNet:
         """host arguments of the analytic target source: ``(joints (n,J,2) float64, visibility (n,J) float32, joints_weight (J,)
         float32 or None)``; ``visibility`` may be (n,J) or the dataset's (n,J,k), whose column 0 is read (``COCO.py:467``)"""
         J = self.nof_joints
-        jt = np.asarray(joints.cpu() if isinstance(joints, torch.Tensor) else joints, dtype=np.float64)
+        jt = host_array(joints, np.float64)
         if jt.ndim != 3 or jt.shape[1] != J or jt.shape[2] < 2:
             raise ValueError("joints must be (n, %d, 2), got %s" % (J, jt.shape))
         jt = np.ascontiguousarray(jt[:, :, :2])
-        vis = np.asarray(visibility.cpu() if isinstance(visibility, torch.Tensor) else visibility, dtype=np.float32)
+        vis = host_array(visibility, np.float32)
         if vis.ndim == 3:
             vis = vis[:, :, 0]
         if vis.shape != jt.shape[:2]:
@@ -877,10 +716,8 @@ class NativeHRNet:
         n, (h, w) = len(jt), self.resolution
         targets = torch.empty((n, self.nof_joints, h // 4, w // 4), dtype=torch.float32, device=self.torch_device)
         tw = np.empty((n, self.nof_joints, 1), np.float32)
-        with torch.cuda.device(self.device_index):
-            rc = self._lib.hrn_generate_targets(self._h, jt.ctypes.data, vis.ctypes.data, None if jw is None else jw.ctypes.data, n,
-                                                float(sigma), targets.data_ptr(), tw.ctypes.data, self._stream())
-        self._check(rc, "hrn_generate_targets")
+        self._launch("hrn_generate_targets", jt.ctypes.data, vis.ctypes.data, None if jw is None else jw.ctypes.data, n, float(sigma),
+                     targets.data_ptr(), tw.ctypes.data)
         return targets, tw
 
     def score_heatmaps(self, heatmaps, joints=None, visibility=None, targets=None, target_weight=None, sigma=2, joints_weight=None,
@@ -913,8 +750,7 @@ class NativeHRNet:
             if target_weight is None or visibility is not None or joints_weight is not None:
                 raise ValueError("targets come with target_weight and without visibility / joints_weight")
             tg = torch.as_tensor(targets).to(dev, torch.float32).contiguous()
-            tw = np.ascontiguousarray(np.asarray(target_weight.cpu() if isinstance(target_weight, torch.Tensor) else target_weight,
-                                                 dtype=np.float32).reshape(-1))
+            tw = np.ascontiguousarray(host_array(target_weight, np.float32).reshape(-1))
             if tuple(tg.shape) != tuple(hm.shape) or tw.size != n * J:
                 raise ValueError("targets must have the heat-maps' shape and target_weight n*J entries")
         f32, f64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.float64, device=dev)
@@ -927,10 +763,8 @@ class NativeHRNet:
         def ptr(a):
             return None if a is None else a.ctypes.data
 
-        with torch.cuda.device(self.device_index):
-            rc = self._lib.hrn_score_heatmaps(self._h, hm.data_ptr(), n, None if tg is None else tg.data_ptr(), ptr(jt), ptr(vis), ptr(jw),
-                                              float(sigma), ptr(tw), float(thr), int(topk), ctypes.byref(out), self._stream())
-        self._check(rc, "hrn_score_heatmaps")
+        self._launch("hrn_score_heatmaps", hm.data_ptr(), n, None if tg is None else tg.data_ptr(), ptr(jt), ptr(vis), ptr(jw),
+                     float(sigma), ptr(tw), float(thr), int(topk), ctypes.byref(out))
         return {"loss": t["loss_mse"], "loss_ohkm": t["loss_ohkm"], "accs": t["acc"], "avg_acc": t["avg_acc"], "cnt": t["cnt"],
                 "joints_preds": t["preds"], "joints_target": t["target_preds"], "dists": t["dists"], "maxvals": t["maxvals"],
                 "map_loss": t["map_loss"]}
@@ -974,31 +808,25 @@ class NativeHRNet:
         have ``confidence > threshold``."""
         from .postproc import _frame_sizes
 
-        if not isinstance(pts, torch.Tensor):
-            pts = torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float32))
+        pts = as_tensor(pts, np.float32)
         if pts.dim() != 3 or pts.shape[2] != 3:
             raise ValueError("pts must be (n, J, 3), got %s" % (tuple(pts.shape),))
-        pts = pts.to(self.torch_device, dtype=torch.float32, non_blocking=True).contiguous()
+        pts = device_tensor(pts, self.torch_device, torch.float32)
         n, J = int(pts.shape[0]), int(pts.shape[1])
         hw, per_person = _frame_sizes(frame_hw, n)
         dets = torch.empty((n, 5), dtype=torch.float32, device=self.torch_device)
-        with torch.cuda.device(self.device_index):
-            rc = self._lib.hrn_boxes_from_poses(self._h, pts.data_ptr(), n, J, hw.ctypes.data, per_person, ctypes.c_float(threshold),
-                                                int(min_joints), ctypes.c_double(scale), ctypes.c_double(min_side), dets.data_ptr(),
-                                                self._stream())
-        self._check(rc, "hrn_boxes_from_poses")
+        self._launch("hrn_boxes_from_poses", pts.data_ptr(), n, J, hw.ctypes.data, per_person, ctypes.c_float(threshold),
+                     int(min_joints), ctypes.c_double(scale), ctypes.c_double(min_side), dets.data_ptr())
         return dets
 
     def _tracked_frames(self, frames, frame_index, n: int):
-        """``frames`` / ``frame_index`` of ``preprocess_frames_dev`` / ``track_frame`` as (device frames, int32 index or None)"""
-        single = isinstance(frames, YuvFrame) or (isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3)
-        frames = self._device_frames([frames] if single else frames)
+        """``frames`` / ``frame_index`` of ``preprocess_frames_dev`` / ``track_frame`` as (``Frames`` on the device, int32 index or None)"""
+        frames = self._device_frames(frames, one=True)
         if frame_index is None:
             if len(frames) != 1:
                 raise ValueError("%d frames need a frame_index (one entry per person)" % len(frames))
             return frames, None
-        index = np.ascontiguousarray(np.asarray(frame_index.cpu() if isinstance(frame_index, torch.Tensor) else frame_index,
-                                                dtype=np.int32).reshape(-1))
+        index = np.ascontiguousarray(host_array(frame_index, np.int32).reshape(-1))
         if len(index) != n:
             raise ValueError("frame_index has %d entries for %d people" % (len(index), n))
         if len(index) and (index.min() < 0 or index.max() >= len(frames)):
@@ -1007,29 +835,22 @@ class NativeHRNet:
             raise ValueError("a frame somebody is cut from is None")
         return frames, index
 
-    def _preprocess_dev(self, frames, dets_dev: torch.Tensor, index, variant: str):
-        """``hrn_preprocess_frames_dev`` / ``_yuv_dev`` over device frames (a list ``_tracked_frames`` made)"""
-        if variant not in ("pad", "clamp"):
-            raise ValueError("variant must be 'pad' or 'clamp'")
+    def _preprocess_dev(self, frames: Frames, dets_dev: torch.Tensor, index, variant: str):
+        """``hrn_preprocess_frames_dev`` / ``_yuv_dev`` over device frames (the ``Frames`` ``_tracked_frames`` made)"""
+        crop = crop_code(variant)
         if dets_dev.dim() != 2 or dets_dev.shape[1] < 4:
             raise ValueError("detections must be (P, >=4)")
-        dets_dev = dets_dev.to(self.torch_device, dtype=torch.float32, non_blocking=True).contiguous()
+        dets_dev = device_tensor(dets_dev, self.torch_device, torch.float32)
         n = int(dets_dev.shape[0])
-        table = self._frame_table(frames)
-        yuv = table._type_ is _lib.YuvFrameC
-        entry, name = (self._lib.hrn_preprocess_frames_yuv_dev, "hrn_preprocess_frames_yuv_dev") if yuv else \
-            (self._lib.hrn_preprocess_frames_dev, "hrn_preprocess_frames_dev")
         h, w = self.resolution
         dev = self.torch_device
         images = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
         boxes_dev = torch.empty((n, 4), dtype=torch.int32, device=dev)
         status_dev = torch.empty((n,), dtype=torch.int32, device=dev)
         if n:
-            with torch.cuda.device(self.device_index):
-                rc = entry(self._h, table, len(frames), dets_dev.data_ptr(), int(dets_dev.shape[1]),
-                           None if index is None else index.ctypes.data, n, 0 if variant == "pad" else 1, images.data_ptr(),
-                           boxes_dev.data_ptr(), status_dev.data_ptr(), self._stream())
-            self._check(rc, name)
+            self._launch("hrn_preprocess_frames%s_dev" % ("_yuv" if frames.yuv else ""), frames.table(), len(frames), dets_dev.data_ptr(),
+                         int(dets_dev.shape[1]), None if index is None else index.ctypes.data, n, crop, images.data_ptr(),
+                         boxes_dev.data_ptr(), status_dev.data_ptr())
         return images, boxes_dev, status_dev
 
     def preprocess_frames_dev(self, frames, dets_dev, frame_index=None, variant: str = "pad"):
@@ -1044,8 +865,7 @@ class NativeHRNet:
         zero and its crop all padding (1 degenerate, 2 starts outside the frame, 3 degenerate after clamping, 4 padded crop too
         tall for the scratch, 5 a coordinate not finite or beyond 2^30: include/hrnet_mi355.h).  The scratch is sized for the
         tallest crop a box inside the frame can need: about 2.2 MB per person at 1080p / 384x288, kept by the engine."""
-        if not isinstance(dets_dev, torch.Tensor):
-            dets_dev = torch.from_numpy(np.ascontiguousarray(dets_dev, dtype=np.float32))
+        dets_dev = as_tensor(dets_dev, np.float32)
         frames, index = self._tracked_frames(frames, frame_index, int(dets_dev.shape[0]))
         return self._preprocess_dev(frames, dets_dev, index, variant)
 
@@ -1063,8 +883,7 @@ class NativeHRNet:
         refine_code(refine)
         n = int(prev_pts.shape[0])
         frames, index = self._tracked_frames(frame, frame_index, n)
-        sizes = np.asarray([(0, 0) if f is None else ((f.height, f.width) if isinstance(f, YuvFrame) else tuple(f.shape[:2]))
-                            for f in frames], np.int32)
+        sizes = frames.sizes()
         dets = self.boxes_from_poses(prev_pts, sizes[0] if index is None else sizes[index].reshape(n, 2), **box_args)
         images, boxes_dev, status_dev = self._preprocess_dev(frames, dets, index, variant)
         out = self.predict_crops(images, boxes_dev, return_heatmaps=return_heatmaps, refine=refine)
@@ -1099,24 +918,16 @@ class NativeHRNet:
         if fill.size not in (1, 3) or (fill < 0).any() or (fill > 255).any() or (fill != np.round(fill)).any():
             raise ValueError("pad must be one or three integers in [0, 255], got %r" % (pad,))
         fill = np.ascontiguousarray(np.broadcast_to(fill.reshape(-1), (3,)).astype(np.uint8))
-        single = isinstance(frames, YuvFrame) or (isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3)
-        frames = self._device_frames([frames] if single else frames)
+        frames = self._device_frames(frames, one=True)
         if not frames or any(f is None for f in frames):
             raise ValueError("detector_input needs at least one frame, and none of them None")
         n = len(frames)
-        table = self._frame_table(frames)
-        yuv = table._type_ is _lib.YuvFrameC
-        entry, name = (self._lib.hrn_letterbox_frames_yuv, "hrn_letterbox_frames_yuv") if yuv else \
-            (self._lib.hrn_letterbox_frames, "hrn_letterbox_frames")
         shape = (n, out_h, out_w, 3) if dtype == torch.uint8 else (n, 3, out_h, out_w)
         out = torch.empty(shape, dtype=dtype, device=self.torch_device)
         geometry = (_lib.Letterbox * n)()
-        with torch.cuda.device(self.device_index):
-            rc = entry(self._h, table, n, LETTERBOX_RULES[style], out_h, out_w, fill.ctypes.data, 0 if order == "rgb" else 1,
-                       self.LETTERBOX_FORMS[dtype], out.data_ptr(), ctypes.addressof(geometry), self._stream())
-        self._check(rc, name)
-        hw = np.asarray([(f.height, f.width) if isinstance(f, YuvFrame) else tuple(f.shape[:2]) for f in frames], np.int32)
-        return out, LetterboxGeometry(style, (out_h, out_w), np.ascontiguousarray(hw), geometry)
+        self._launch("hrn_letterbox_frames" + ("_yuv" if frames.yuv else ""), frames.table(), n, LETTERBOX_RULES[style], out_h, out_w,
+                     fill.ctypes.data, 0 if order == "rgb" else 1, self.LETTERBOX_FORMS[dtype], out.data_ptr(), ctypes.addressof(geometry))
+        return out, LetterboxGeometry(style, (out_h, out_w), frames.sizes(), geometry)
 
     def detections_to_frame(self, dets, geometry, counts=None, conf_thres=None, classes=None, compact: bool = True, conf_col: int = 4,
                             class_col: int = -1):
@@ -1129,21 +940,17 @@ class NativeHRNet:
         status 1; ``rows[:, :4]`` can go there as it is."""
         from .postproc import detection_arguments
 
-        if not isinstance(dets, torch.Tensor):
-            dets = torch.from_numpy(np.ascontiguousarray(dets, dtype=np.float32))
+        dets = as_tensor(dets, np.float32)
         start, thres, col, ids, flags = detection_arguments(tuple(dets.shape), geometry, counts, conf_thres, classes, class_col, compact)
         dev = self.torch_device
-        dets = dets.to(dev, dtype=torch.float32, non_blocking=True).contiguous()
+        dets = device_tensor(dets, dev, torch.float32)
         n, P = int(dets.shape[0]), len(geometry)
         out = torch.empty_like(dets)
         kept = torch.empty((P,), dtype=torch.int32, device=dev)
         status = torch.empty((n,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(self.device_index):
-            rc = self._lib.hrn_detections_to_frame_dev(self._h, geometry.rule, dets.data_ptr(), int(dets.shape[1]), start.ctypes.data, P,
-                                                       ctypes.addressof(geometry.table), geometry.frame_hw.ctypes.data, geometry.size[0],
-                                                       geometry.size[1], int(conf_col), ctypes.c_float(thres), col, ids.ctypes.data,
-                                                       len(ids), flags, out.data_ptr(), kept.data_ptr(), status.data_ptr(), self._stream())
-        self._check(rc, "hrn_detections_to_frame_dev")
+        self._launch("hrn_detections_to_frame_dev", geometry.rule, dets.data_ptr(), int(dets.shape[1]), start.ctypes.data, P,
+                     ctypes.addressof(geometry.table), geometry.frame_hw.ctypes.data, geometry.size[0], geometry.size[1], int(conf_col),
+                     ctypes.c_float(thres), col, ids.ctypes.data, len(ids), flags, out.data_ptr(), kept.data_ptr(), status.data_ptr())
         return out, kept, status
 
     # -- person ids between two frames: who of the previous frame is who of this one ------------------------------------------------
@@ -1163,22 +970,15 @@ class NativeHRNet:
         from .postproc import _next_ids, _segments
 
         dev = self.torch_device
-
-        def on_device(v, dtype, shape):
-            if not isinstance(v, torch.Tensor):
-                v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.int32 if dtype == torch.int32 else np.float32))
-            return v.to(dev, dtype=dtype, non_blocking=True).reshape(shape).contiguous()
-
-        boxes, prev_boxes = on_device(boxes, torch.int32, (-1, 4)), on_device(prev_boxes, torch.int32, (-1, 4))
+        boxes, prev_boxes = device_tensor(boxes, dev, torch.int32, (-1, 4)), device_tensor(prev_boxes, dev, torch.int32, (-1, 4))
         n, m = int(boxes.shape[0]), int(prev_boxes.shape[0])
-        pts, prev_pts = (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
-                         for v in (pts, prev_pts))
+        pts, prev_pts = as_tensor(pts, np.float32), as_tensor(prev_pts, np.float32)
         widths = {int(v.shape[1]) for v in (pts, prev_pts) if v.dim() == 3 and v.shape[0]}
         if len(widths) > 1:
             raise ValueError("the two sets of skeletons have different joint counts")
         joints = widths.pop() if widths else 1
-        pts, prev_pts = on_device(pts, torch.float32, (-1, joints, 3)), on_device(prev_pts, torch.float32, (-1, joints, 3))
-        prev_ids = on_device(prev_ids, torch.int32, (-1,))
+        pts, prev_pts = device_tensor(pts, dev, torch.float32, (-1, joints, 3)), device_tensor(prev_pts, dev, torch.float32, (-1, joints, 3))
+        prev_ids = device_tensor(prev_ids, dev, torch.int32, (-1,))
         if int(pts.shape[0]) != n or int(prev_pts.shape[0]) != m or int(prev_ids.shape[0]) != m:
             raise ValueError("pts must be (n, J, 3) beside (n, 4) boxes with one J on both sides, and prev_ids one per previous "
                              "person: got %s, %s, %s, %s, %s" % tuple(tuple(v.shape) for v in (boxes, pts, prev_boxes, prev_pts, prev_ids)))
@@ -1197,13 +997,9 @@ class NativeHRNet:
         ids = torch.empty((n,), dtype=torch.int32, device=dev)
         match = torch.empty((n,), dtype=torch.int32, device=dev)
         status = torch.zeros((problems,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(self.device_index):
-            rc = self._lib.hrn_associate_people_dev(self._h, problems, cur.ctypes.data, prev.ctypes.data, joints, boxes.data_ptr(),
-                                                    pts.data_ptr(), prev_boxes.data_ptr(), prev_pts.data_ptr(), prev_ids.data_ptr(),
-                                                    nxt.data_ptr(), float(pose_alpha), float(similarity_threshold),
-                                                    float(smoothing_alpha), ids.data_ptr(), match.data_ptr(), status.data_ptr(),
-                                                    self._stream())
-        self._check(rc, "hrn_associate_people_dev")
+        self._launch("hrn_associate_people_dev", problems, cur.ctypes.data, prev.ctypes.data, joints, boxes.data_ptr(), pts.data_ptr(),
+                     prev_boxes.data_ptr(), prev_pts.data_ptr(), prev_ids.data_ptr(), nxt.data_ptr(), float(pose_alpha),
+                     float(similarity_threshold), float(smoothing_alpha), ids.data_ptr(), match.data_ptr(), status.data_ptr())
         return boxes, pts, ids, match, nxt, status
 
     # -- pose NMS: duplicate skeletons removed per image or stream, without leaving the device --------------------------------------
@@ -1226,13 +1022,10 @@ class NativeHRNet:
         scores_out = torch.empty((n,), dtype=torch.float64, device=dev)
         suppressor = torch.empty((n,), dtype=torch.int32, device=dev)
         status = torch.empty((problems,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(self.device_index):
-            rc = self._lib.hrn_pose_nms_dev(self._h, problems, seg.ctypes.data, joints, pose_nms_flags(engine, soft, suppress),
-                                            kpts.data_ptr(), areas.data_ptr(), None if scores is None else scores.data_ptr(),
-                                            float(thresh), _nan_if_none(in_vis_thre), _nan_if_none(rescore_thre),
-                                            None if sg is None else sg.data_ptr(), keep.data_ptr(), num.data_ptr(),
-                                            scores_out.data_ptr(), suppressor.data_ptr(), status.data_ptr(), self._stream())
-        self._check(rc, "hrn_pose_nms_dev")
+        self._launch("hrn_pose_nms_dev", problems, seg.ctypes.data, joints, pose_nms_flags(engine, soft, suppress), kpts.data_ptr(),
+                     areas.data_ptr(), None if scores is None else scores.data_ptr(), float(thresh), _nan_if_none(in_vis_thre),
+                     _nan_if_none(rescore_thre), None if sg is None else sg.data_ptr(), keep.data_ptr(), num.data_ptr(),
+                     scores_out.data_ptr(), suppressor.data_ptr(), status.data_ptr())
         return dict(keep=keep, num=num, scores=scores_out, suppressor=suppressor, status=status)
 
     def pose_nms(self, pts, boxes, det_scores=None, counts=None, thresh: float = 0.9, in_vis_thre=None, rescore_thre=None,
@@ -1257,17 +1050,11 @@ class NativeHRNet:
         from .postproc import _segments
 
         dev = self.torch_device
-
-        def on_device(v, dtype, np_dtype, shape):
-            if not isinstance(v, torch.Tensor):
-                v = torch.from_numpy(np.ascontiguousarray(v, dtype=np_dtype))
-            return v.to(dev, dtype=dtype, non_blocking=True).reshape(shape).contiguous()
-
-        boxes = on_device(boxes, torch.int32, np.int32, (-1, 4))
+        boxes = device_tensor(boxes, dev, torch.int32, (-1, 4))
         n = int(boxes.shape[0])
         joints = int(pts.shape[1]) if len(pts.shape) == 3 else (17 if sigmas is None else len(sigmas))
-        pts = on_device(pts, torch.float32, np.float32, (-1, joints, 3))
-        det = None if det_scores is None else on_device(det_scores, torch.float32, np.float32, (-1,))
+        pts = device_tensor(pts, dev, torch.float32, (-1, joints, 3))
+        det = None if det_scores is None else device_tensor(det_scores, dev, torch.float32, (-1,))
         if int(pts.shape[0]) != n or (det is not None and int(det.shape[0]) != n):
             raise ValueError("pts must be (n, J, 3) beside (n, 4) boxes and n det_scores, got %s, %s, %s"
                              % (tuple(pts.shape), tuple(boxes.shape), None if det is None else tuple(det.shape)))
@@ -1326,68 +1113,34 @@ class NativeHRNet:
         return scores, {image: by_image[image] for image in seen}
 
     # -- clip mode: the people of many frames in one pre-path launch and one pass (throughput, not latency) ------------------
-    def _device_frames(self, frames) -> List[Optional[torch.Tensor]]:
-        """``frames`` of ``preprocess_frames`` as a list of contiguous (Hf, Wf, 3) uint8 tensors on the engine's GPU; a 4-D stack
-        crosses PCIe in one copy and is then indexed, a sequence frame by frame (once each).  A sequence of ``YuvFrame``s comes
-        back as ``YuvFrame``s on the GPU; one that mixes the two kinds raises ValueError"""
-        dev = self.torch_device
-        if isinstance(frames, np.ndarray) and frames.ndim == 4:
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        if isinstance(frames, torch.Tensor):
-            if frames.dim() != 4:
-                raise ValueError("frames must be (F, Hf, Wf, 3) uint8 BGR or a sequence of (Hf, Wf, 3) frames")
-            stack = frames.to(dev, non_blocking=True).contiguous()
-            out = [stack[k] for k in range(int(stack.shape[0]))]
-        else:
-            frames = list(frames)
-            if _frame_kind(frames):
-                return [None if f is None else f.to(dev, non_blocking=True) for f in frames]
-            out = [None if f is None else (f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)))
-                   for f in frames]
-            out = [None if f is None else f.to(dev, non_blocking=True).contiguous() for f in out]
-        for k, f in enumerate(out):
-            if f is not None:
-                _check_frame(f, k)
-        return out
+    def _device_frames(self, frames, one: bool = False) -> Frames:
+        """``frames`` of ``preprocess_frames`` on the engine's GPU (``Frames.resident``); ``one``: a single frame is accepted too"""
+        return Frames.resident(frames, self.torch_device, one)
+
+    @staticmethod
+    def _frame_table(frames):
+        """the frame table of a list of device frames (``Frames.table``)"""
+        return Frames(frames).table()
 
     def _preprocess_table(self, table, nframes: int, dets: np.ndarray, frame_index: np.ndarray, variant: str):
         """``hrn_preprocess_frames`` over a ready frame table (``_lib.Frame`` array whose device memory the caller keeps alive), or
         ``hrn_preprocess_frames_yuv`` over a ``_lib.YuvFrameC`` array: ``dets`` (n, 4) float32, ``frame_index`` (n,) int32.
         Returns ``(images, boxes numpy, boxes on the device)``."""
+        crop = crop_code(variant)
+        # the table is all this signature carries of the frames (tests call it with tables of their own): its element type is their kind
         yuv = isinstance(table, ctypes.Array) and table._type_ is _lib.YuvFrameC
-        entry, name = (self._lib.hrn_preprocess_frames_yuv, "hrn_preprocess_frames_yuv") if yuv else \
-            (self._lib.hrn_preprocess_frames, "hrn_preprocess_frames")
         n = len(dets)
         h, w = self.resolution
         images = torch.empty((n, 3, h, w), dtype=torch.float32, device=self.torch_device)
         boxes = np.empty((n, 4), dtype=np.int32)
         boxes_dev = torch.empty((n, 4), dtype=torch.int32, device=self.torch_device)
         if n:
-            with torch.cuda.device(self.device_index):
-                rc = entry(self._h, table, nframes, dets.ctypes.data, 4, frame_index.ctypes.data, n, 0 if variant == "pad" else 1,
-                           images.data_ptr(), boxes.ctypes.data, boxes_dev.data_ptr(), self._stream())
-            self._check(rc, name)
+            self._launch("hrn_preprocess_frames" + ("_yuv" if yuv else ""), table, nframes, dets.ctypes.data, 4,
+                         frame_index.ctypes.data, n, crop, images.data_ptr(), boxes.ctypes.data, boxes_dev.data_ptr())
         return images, boxes, boxes_dev
 
-    @staticmethod
-    def _frame_table(frames):
-        """the ``hrn_frame`` table of a list of device frames (None: a null entry, for a frame nobody is cut from); the
-        ``hrn_yuv_frame`` table when they are ``YuvFrame``s"""
-        if _frame_kind(frames):
-            table = (_lib.YuvFrameC * len(frames))()
-            for k, f in enumerate(frames):
-                if f is not None:
-                    f._fill(table[k])
-            return table
-        table = (_lib.Frame * max(len(frames), 1))()
-        for k, f in enumerate(frames):
-            if f is not None:
-                table[k].data, table[k].height, table[k].width = f.data_ptr(), int(f.shape[0]), int(f.shape[1])
-        return table
-
     def _frame_arguments(self, frames, detections, variant):
-        if variant not in ("pad", "clamp"):
-            raise ValueError("variant must be 'pad' or 'clamp'")
+        crop_code(variant)
         frames = self._device_frames(frames)
         dets = [_detections(d) for d in detections]
         if len(dets) != len(frames):
@@ -1411,7 +1164,7 @@ class NativeHRNet:
         counts = [len(d) for d in dets]
         all_dets = np.ascontiguousarray(np.concatenate(dets, 0)) if dets else np.zeros((0, 4), np.float32)
         frame_index = np.repeat(np.arange(len(counts), dtype=np.int32), counts).astype(np.int32)
-        images, boxes, boxes_dev = self._preprocess_table(self._frame_table(frames), len(frames), all_dets, frame_index, variant)
+        images, boxes, boxes_dev = self._preprocess_table(frames.table(), len(frames), all_dets, frame_index, variant)
         return images, boxes, boxes_dev, counts
 
     def _run_group(self, table, nframes, dets, group, variant, return_heatmaps, refine):
@@ -1449,7 +1202,7 @@ class NativeHRNet:
         their pass's outputs; a frame without people gives (0,4), (0,J,3) and (0,J,H/4,W/4)."""
         refine_code(refine)
         frames, dets = self._frame_arguments(frames, detections, variant)
-        table = self._frame_table(frames)
+        table = frames.table()
         pieces = [[] for _ in frames]
         for group in group_frames([len(d) for d in dets], self.max_batch):
             if any(hi > lo for _, lo, hi in group):
@@ -1480,15 +1233,9 @@ class NativeHRNet:
         Yields per frame, in order, what ``predict_frames`` returns per frame; results are ready on the current stream (read them
         after a synchronize or through ``.cpu()``)."""
         refine_code(refine)
-        if variant not in ("pad", "clamp"):
-            raise ValueError("variant must be 'pad' or 'clamp'")
+        crop_code(variant)
         per_pass = self.max_batch if people_per_pass is None else people_per_pass
-        dev = self.torch_device
-        compute = torch.cuda.current_stream(dev)
-        copy = torch.cuda.Stream(dev)
-        arena = [None, None]
-        landed = [torch.cuda.Event(), torch.cuda.Event()]
-        consumed = [None, None]
+        pipe = UploadPipeline(self.torch_device)   # its slots: byte arenas, grown on demand
         held = {}            # frame number -> (host frame or None, detections) of the frames read ahead and not yet run
         kinds = set()        # {True}: a clip of YuvFrames, {False}: of BGR frames
 
@@ -1503,7 +1250,7 @@ class NativeHRNet:
                     if len(kinds) > 1:
                         raise ValueError("the frames of one clip are all YuvFrames or all BGR frames, not a mixture")
                     if not isinstance(frame, YuvFrame):
-                        frame = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame))
+                        frame = as_tensor(frame)
                         _check_frame(frame, k)
                         frame = frame.contiguous()
                 elif len(d):
@@ -1512,38 +1259,22 @@ class NativeHRNet:
                 yield len(d)
 
         def upload(slot, group):
-            """the frames of `group` that somebody is cut from -> arena[slot] on the copy stream; returns the group's table"""
+            """the frames of `group` that somebody is cut from -> the slot's arena on the copy stream; returns the group's table"""
             first = group[0][0]
-            nfr = group[-1][0] - first + 1
-            table = ((_lib.YuvFrameC if kinds == {True} else _lib.Frame) * nfr)()
-            offs, need = {}, 0
+            frames = Frames([None] * (group[-1][0] - first + 1), kinds == {True})
+            offs, need = {}, 0   # frame, counted from `first` -> where its bytes start in the arena
             for f, lo, hi in group:
-                if hi > lo and f not in offs:
-                    offs[f] = need
-                    need += (_host_bytes(held[f][0]).numel() + 255) // 256 * 256
-            if need and (arena[slot] is None or arena[slot].numel() < need):
-                # a new arena comes from the caching allocator on the COMPUTE stream and may be recycled memory that kernels already
-                # queued there still read: the upload into it must not overtake them
-                arena[slot] = torch.empty((need + need // 4,), dtype=torch.uint8, device=dev)
-                arena[slot].record_stream(copy)
-                copy.wait_stream(compute)
-            with torch.cuda.stream(copy):
-                if consumed[slot] is not None:
-                    copy.wait_event(consumed[slot])              # the pre-path that read this arena has finished
+                if hi > lo and f - first not in offs:
+                    frames[f - first] = held[f][0]
+                    offs[f - first] = need
+                    need += (host_bytes(held[f][0]).numel() + 255) // 256 * 256
+            arena = pipe.buffer(slot, torch.uint8, (need + need // 4,), at_least=need) if need else None
+            with pipe.filling(slot):                             # the pre-path that read this arena has finished
                 for f, off in offs.items():
-                    frame = held[f][0]
-                    flat = _host_bytes(frame)
-                    arena[slot][off:off + flat.numel()].copy_(flat, non_blocking=True)
-                    if isinstance(frame, YuvFrame):
-                        frame._fill(table[f - first], arena[slot].data_ptr() + off)
-                        continue
-                    table[f - first].data = arena[slot].data_ptr() + off
-                    table[f - first].height, table[f - first].width = int(frame.shape[0]), int(frame.shape[1])
-                landed[slot].record(copy)
-            return table, first, nfr, bool(offs)
+                    flat = host_bytes(frames[f])
+                    arena[off:off + flat.numel()].copy_(flat, non_blocking=True)
+            return frames.table({f: arena.data_ptr() + off for f, off in offs.items()}), first, len(frames), bool(offs)
 
-        # the arenas come from the caching allocator on the COMPUTE stream (see upload): the first upload must not overtake it
-        copy.wait_stream(compute)
         groups = group_frames(counts(), self.max_batch, per_pass)
         nxt = next(groups, None)
         pending = upload(0, nxt) if nxt is not None else None
@@ -1553,14 +1284,13 @@ class NativeHRNet:
             nxt = next(groups, None)
             pending = upload(slot ^ 1, nxt) if nxt is not None else None   # goes out while this group computes
             if busy:
-                compute.wait_event(landed[slot])
+                pipe.ready(slot)
                 local = [(f - first, lo, hi) for f, lo, hi in group]
                 dets = {f - first: held[f][1] for f, _, _ in group}
                 for f, lo, hi, bx, pts, hm in self._run_group(table, nfr, dets, local, variant, return_heatmaps, refine):
                     if hi > lo:
                         pieces.setdefault(f + first, []).append((bx, pts, hm))
-                consumed[slot] = torch.cuda.Event()
-                consumed[slot].record(compute)
+                pipe.release(slot)
             last = group[-1][0]
             for f in sorted({g[0] for g in group}):
                 # a frame above one pass spans several groups: it is complete with the group that holds its last people
@@ -1576,7 +1306,8 @@ class NativeHRNet:
         out = []
         for i in range(self._lib.hrn_tap_count(self._h)):
             ti = _lib.TapInfo()
-            self._check(self._lib.hrn_get_tap_info(self._h, i, ctypes.byref(ti)), "hrn_get_tap_info")
+            rc = self._lib.hrn_get_tap_info(self._h, i, ctypes.byref(ti))
+            self._check(rc, "hrn_get_tap_info")
             out.append(ti)
         return out
 
@@ -1595,17 +1326,16 @@ class NativeHRNet:
         dst = torch.empty((ncrops, info.c, info.h, info.w), dtype=torch.float32, device=x.device)
         h, w = self.resolution
         hm = torch.empty((n, self.nof_joints, h // 4, w // 4), dtype=torch.float32, device=x.device) if return_heatmaps else None
-        with torch.cuda.device(self.device_index):
-            self._check(self._lib.hrn_forward_tap(self._h, x.data_ptr(), n, name.encode(), int(crop0), int(ncrops), int(crop_step),
-                                                  dst.data_ptr(), hm.data_ptr() if hm is not None else None, self._stream()),
-                        "hrn_forward_tap")
+        self._launch("hrn_forward_tap", x.data_ptr(), n, name.encode(), int(crop0), int(ncrops), int(crop_step), dst.data_ptr(),
+                     hm.data_ptr() if hm is not None else None)
         return (dst, hm) if return_heatmaps else dst
 
     def conv_infos(self) -> List[_lib.ConvInfo]:
         out = []
         for i in range(self._lib.hrn_conv_count(self._h)):
             ci = _lib.ConvInfo()
-            self._check(self._lib.hrn_get_conv_info(self._h, i, ctypes.byref(ci)), "hrn_get_conv_info")
+            rc = self._lib.hrn_get_conv_info(self._h, i, ctypes.byref(ci))
+            self._check(rc, "hrn_get_conv_info")
             out.append(ci)
         return out
 
@@ -1646,9 +1376,7 @@ class NativeHRNet:
         nconv = self._lib.hrn_conv_count(self._h)
         conv_ms = (ctypes.c_float * nconv)()
         other = (ctypes.c_float * 4)()
-        with torch.cuda.device(self.device_index):
-            self._check(self._lib.hrn_profile_pass(self._h, x.data_ptr(), n, conv_ms, nconv, other, self._stream()),
-                        "hrn_profile_pass")
+        self._launch("hrn_profile_pass", x.data_ptr(), n, conv_ms, nconv, other)
         return list(conv_ms), dict(zip(("stem", "fuse", "head", "decode"), list(other)))
 
 
@@ -1738,9 +1466,9 @@ class MultiDeviceHRNet:
         return [shard_range(n, len(self.nets), k) for k in range(len(self.nets))]
 
     def _run(self, n: int, work):
-        """work(k, net, lo, hi) -> tuple of tensors on net's device (or None); runs every non-empty range on its own
-        thread and stream, orders it after the caller's stream on every device involved, returns the per-range results
-        moved to the first device (in range order)."""
+        """work(k, net, lo, hi) -> tuple of tensors on net's device (None and host arrays pass through); runs every non-empty
+        range on its own thread and stream, orders it after the caller's stream on every device involved, returns the per-range
+        results moved to the first device (in range order)."""
         first = self.torch_device
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream(first))   # inputs produced on the caller's stream of the first device
@@ -1775,7 +1503,7 @@ class MultiDeviceHRNet:
         refine_code(refine)
         kw = {} if refine is None else {"refine": refine}   # None: every engine is called as without the option
         n = int(images.shape[0])
-        b = boxes if isinstance(boxes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(boxes))
+        b = as_tensor(boxes)
         if n == 0:
             return self.nets[0].predict_crops(images, b, return_heatmaps=return_heatmaps, **kw)
 
@@ -1798,29 +1526,25 @@ class MultiDeviceHRNet:
 
     forward = __call__
 
+    def _frame_shards(self, frame, detections, call):
+        """``call(net, frame, dets)`` -> a tuple of numpy arrays and device tensors for the people of one frame: on the first
+        engine when there is nobody, else every engine on its range of the detections (the frame goes to each once); the pieces
+        joined in range order, the tensors on the first device"""
+        dets = _detections(detections)
+        if len(dets) == 0:
+            return call(self.nets[0], frame, dets)
+        frame = as_tensor(frame)
+        outs = self._run(len(dets), lambda k, net, lo, hi: call(net, frame, dets[lo:hi]))
+        return tuple(np.concatenate(p, 0) if isinstance(p[0], np.ndarray) else torch.cat(p, 0) for p in zip(*outs))
+
     def preprocess_frame(self, frame, detections, variant: str = "pad"):
         """crops of one frame, produced on the devices that will run them and gathered on the first one"""
-        dets = np.ascontiguousarray(np.asarray(detections.cpu() if isinstance(detections, torch.Tensor) else detections,
-                                               dtype=np.float32))
-        if len(dets) == 0:
-            return self.nets[0].preprocess_frame(frame, dets, variant)
-        if not isinstance(frame, torch.Tensor):
-            frame = torch.from_numpy(np.ascontiguousarray(frame))
-        boxes_np = [None] * len(self.nets)
-
-        def work(k, net, lo, hi):
-            images, bx, bx_dev = net.preprocess_frame(frame, dets[lo:hi], variant)
-            boxes_np[k] = bx
-            return images, bx_dev
-
-        outs = self._run(len(dets), work)
-        return (torch.cat([o[0] for o in outs], 0), np.concatenate([b for b in boxes_np if b is not None], 0),
-                torch.cat([o[1] for o in outs], 0))
+        return self._frame_shards(frame, detections, lambda net, frame, dets: net.preprocess_frame(frame, dets, variant))
 
     def warp_crops(self, frames, centers=None, scales=None, rotations=None, frame_index=None, pixel_std=200, matrices=None) -> torch.Tensor:
         """``NativeHRNet.warp_crops`` with the crops split into index ranges: every device gets the frames once, cuts its range, and
         the batch is gathered on the first one"""
-        frames = _frame_stack(frames)
+        frames = frame_stack(frames)
         h, w = self.resolution
         m, fi = _warp_arguments(int(frames.shape[0]), (w, h), centers, scales, rotations, frame_index, pixel_std, matrices)
         if len(m) == 0:
@@ -1833,7 +1557,7 @@ class MultiDeviceHRNet:
         """``NativeHRNet.predict_eval`` by the same split: each device warps, runs and decodes its range of people"""
         from . import postproc
 
-        frames = _frame_stack(frames)
+        frames = frame_stack(frames)
         h, w = self.resolution
         m, fi = _warp_arguments(int(frames.shape[0]), (w, h), centers, scales, None, frame_index, pixel_std, None)
         if len(m) == 0:
@@ -1850,22 +1574,5 @@ class MultiDeviceHRNet:
     def predict_frame(self, frame, detections, return_heatmaps: bool = False, variant: str = "pad", refine: Optional[str] = None):
         refine_code(refine)
         kw = {} if refine is None else {"refine": refine}
-        dets = np.ascontiguousarray(np.asarray(detections.cpu() if isinstance(detections, torch.Tensor) else detections,
-                                               dtype=np.float32))
-        if len(dets) == 0:
-            return self.nets[0].predict_frame(frame, dets, return_heatmaps=return_heatmaps, variant=variant, **kw)
-        if not isinstance(frame, torch.Tensor):
-            frame = torch.from_numpy(np.ascontiguousarray(frame))
-        boxes_np = [None] * len(self.nets)
-
-        def work(k, net, lo, hi):
-            out = net.predict_frame(frame, dets[lo:hi], return_heatmaps=return_heatmaps, variant=variant, **kw)
-            boxes_np[k] = out[0]
-            return tuple(out[1:])
-
-        outs = self._run(len(dets), work)
-        boxes = np.concatenate([b for b in boxes_np if b is not None], 0)
-        pts = torch.cat([o[0] for o in outs], 0)
-        if return_heatmaps:
-            return boxes, pts, torch.cat([o[1] for o in outs], 0)
-        return boxes, pts
+        return self._frame_shards(frame, detections, lambda net, frame, dets: net.predict_frame(
+            frame, dets, return_heatmaps=return_heatmaps, variant=variant, **kw))

@@ -40,16 +40,14 @@ class PersonTracker:
             return b, p.reshape(len(b), -1 if p.size else 1, 3) if p.ndim != 3 else p
         import torch
 
-        dev = self.net.torch_device
+        from .frames import device_tensor
 
-        def own(v, dtype, np_dtype):
-            if not isinstance(v, torch.Tensor):
-                return torch.from_numpy(np.ascontiguousarray(v, dtype=np_dtype)).to(dev, non_blocking=True)
-            moved = v.to(dev, dtype=dtype, non_blocking=True)
-            return moved.clone() if moved is v else moved
+        def own(v, dtype):
+            moved = device_tensor(v, self.net.torch_device, dtype)
+            return moved.clone() if moved is v else moved   # the caller's own tensor, used where it lies: never aliased
 
-        b = own(boxes, torch.int32, np.int32).reshape(-1, 4).contiguous()
-        p = own(pts, torch.float32, np.float32)
+        b = own(boxes, torch.int32).reshape(-1, 4).contiguous()
+        p = own(pts, torch.float32)
         return b, (p.reshape(int(b.shape[0]), -1 if p.numel() else 1, 3) if p.dim() != 3 else p).contiguous()
 
     def _upload(self, v: np.ndarray):
