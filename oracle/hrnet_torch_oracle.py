@@ -345,7 +345,12 @@ class EngineEmulation:
         return self._folded[conv]
 
     def _store(self, t):
+        self._pre = t   # the value before the storing rounding (eval_node(..., unrounded=True))
         return _bf16r(t) if self.ra else t
+
+    def _result(self, y, mag, magnitude, unrounded):
+        out = (y,) + ((mag,) if magnitude else ()) + ((self._pre,) if unrounded else ())
+        return out if len(out) > 1 else y
 
     def inputs_of(self, name) -> List[str]:
         nd = self.graph[name]
@@ -354,10 +359,11 @@ class EngineEmulation:
         return [nd["x"]] + ([nd["res"]] if nd.get("res") else [])
 
     @torch.no_grad()
-    def eval_node(self, name, vals: Dict[str, torch.Tensor], magnitude: bool = False):
+    def eval_node(self, name, vals: Dict[str, torch.Tensor], magnitude: bool = False, unrounded: bool = False):
         """the stored value of node ``name`` from the stored values of its inputs (``vals[input name]``).  With
         ``magnitude`` also the sum of the absolute values of everything that was added up per element (the scale fp32
-        summation noise is proportional to)."""
+        summation noise is proportional to).  With ``unrounded`` also, last, the fp32 value the storing rounding was
+        applied to (after bias, residual and ReLU): what decides whether a 16-bit store overflows."""
         nd = self.graph[name]
         mag = None
         if nd["op"] == "stem":
@@ -398,7 +404,8 @@ class EngineEmulation:
             y = F.conv2d(vals[nd["x"]], wh, bh)
             if magnitude:
                 mag = F.conv2d(vals[nd["x"]].abs(), wh.abs(), bh.abs())
-        return (y, mag) if magnitude else y
+            self._pre = y
+        return self._result(y, mag, magnitude, unrounded)
 
     @torch.no_grad()
     def forward(self, images, taps=None):
@@ -455,10 +462,10 @@ class PoseResNetEmulation(EngineEmulation):
         self._node(self.HEAD, op="head", x=x)
 
     @torch.no_grad()
-    def eval_node(self, name, vals, magnitude: bool = False):
+    def eval_node(self, name, vals, magnitude: bool = False, unrounded: bool = False):
         nd = self.graph[name]
         if nd["op"] not in ("stem7", "maxpool", "deconv"):
-            return super().eval_node(name, vals, magnitude)
+            return super().eval_node(name, vals, magnitude, unrounded)
         mag = None
         if nd["op"] == "stem7":
             x = vals[nd["x"]].to(torch.float32)
@@ -470,6 +477,7 @@ class PoseResNetEmulation(EngineEmulation):
                 mag = F.conv2d(x.abs(), w.abs(), b.abs(), stride=2, padding=3)
         elif nd["op"] == "maxpool":
             y = F.max_pool2d(vals[nd["x"]], 3, 2, 1)   # values are stored bf16 already: the maximum of stored values
+            self._pre = y
             if magnitude:
                 mag = y.abs()
         else:  # ConvTranspose2d(cin, cout, 4, 2, 1) weight [ci][co][ky][kx] + BatchNorm over co + ReLU
@@ -489,4 +497,4 @@ class PoseResNetEmulation(EngineEmulation):
             y = self._store(F.relu(F.conv_transpose2d(x, w, b, 2, 1, 0)))
             if magnitude:
                 mag = F.conv_transpose2d(x.abs(), w.abs(), b.abs(), 2, 1, 0)
-        return (y, mag) if magnitude else y
+        return self._result(y, mag, magnitude, unrounded)
