@@ -536,6 +536,64 @@ int hrn_detections_to_frame_dev(hrn_handle h, int rule, const float *dets_dev, i
                                 int conf_col, float conf_thres, int class_col, const int32_t *classes_host, int nclasses, int flags,
                                 float *dets_out_dev, int32_t *counts_dev, int32_t *status_dev, void *stream);
 
+/* ---- frame rotation on the GPU: cv2.rotate for BGR, NV12 and I420 frames, and people between the two orientations ----
+ * Replaces `frame = cv2.rotate(frame, rotation_code)` at the head of the reference's frame loops (scripts/live-demo.py:102-103,
+ * scripts/extract-keypoints.py:96-97; the code comes from the video's rotation tag, misc/visualization.py:271-293): a portrait
+ * video is stored sideways, a hardware decoder hands over the stored orientation.  The codes are cv2.ROTATE_*'s values.
+ *
+ * THE PIXEL RULE.  cv2.rotate is a pure permutation of elements, np.rot90 its exact restatement.  A source plane has (Hs, Ws)
+ * elements, dst(i, j) is the element of destination row i, column j:
+ *   HRN_ROTATE_90_CW  (0)   dst is (Ws, Hs):  dst(i, j) = src(Hs-1-j, i)
+ *   HRN_ROTATE_180    (1)   dst is (Hs, Ws):  dst(i, j) = src(Hs-1-i, Ws-1-j)
+ *   HRN_ROTATE_90_CCW (2)   dst is (Ws, Hs):  dst(i, j) = src(j, Ws-1-i)
+ * An element is: BGR -- the three bytes of a pixel, kept in order; the Y plane -- one byte; NV12's chroma plane -- the (U, V)
+ * byte pair, on (H/2, W/2); I420 -- the U and the V plane, one byte each, on (H/2, W/2).  2 x 2 luma blocks map onto 2 x 2 blocks,
+ * so converting a rotated YUV frame to BGR equals rotating the converted frame, bit for bit.
+ * Bytes of a destination row beyond its elements (pitch padding) are NOT written; every other byte of dst has exactly one writer;
+ * no atomics; source planes are only read.
+ *
+ * hrn_rotate_frames: src_host / dst_host are nframes hrn_canvas entries each, on the HOST, planes on the device; frames may differ
+ * in size, format and code (codes_host: nframes entries).  dst[k] has src[k]'s format and the rotated size, any pitch that
+ * holds its rows; matrix and range are documentation only.  ONE launch whatever nframes, no frame-sized scratch, stream-ordered;
+ * one block per 64 x 64-element tile of a plane (64 x 16 at 180 degrees), found through a per-call table (one frame: in the kernel arguments; more: uploaded
+ * through the handle's guarded table and pinned ring).  The 90-degree codes go through an LDS tile of padded pitch: source rows are
+ * read and destination rows written in whole dwords wherever a plane's base and pitch are multiples of 4, in bytes otherwise; 180
+ * degrees reverses the elements of four-element groups in registers.  Offsets inside a plane are 32-bit.  nframes == 0 succeeds
+ * and launches nothing.
+ * Fails with code 7, names the cause and launches nothing on: nframes < 0; null tables with nframes > 0; a code outside {0, 1, 2};
+ * formats that differ between src[k] and dst[k]; an unknown format; a null plane; a non-positive side; an odd side on a YUV frame;
+ * a destination whose size is not the rotated size; a pitch below the row's bytes; a plane with pitch * rows >= 2^31; a source
+ * and a destination, or two destinations, that name the same first plane (in-place rotation is not offered; overlapping views
+ * are the caller's to avoid); after all these, a plan-only handle.  Everything is judged before the device is touched.
+ *
+ * PEOPLE BETWEEN THE TWO ORIENTATIONS (csrc/rotate_math.h, one text for host and device).  (Hs, Ws) is the SOURCE frame.  A joint
+ * (y, x, c) is float32: each result is one float32 subtraction or a copy, c is copied; inf goes through the subtraction, a NaN
+ * coordinate is copied with its bits (host and device then agree on its sign).  A box (x1, y1, x2, y2) is int32, a half-open pixel range (the slice hrn_crop_geometry cuts): the rotated box is
+ * the range the rotated slice occupies; the all-zero box of a lost person stays all-zero.
+ *   code 0:  y' = x;  x' = (float)(Hs-1) - y                     box (Hs - y2, x1, Hs - y1, x2)
+ *   code 1:  y' = (float)(Hs-1) - y;  x' = (float)(Ws-1) - x     box (Ws - x2, Hs - y2, Ws - x1, Hs - y1)
+ *   code 2:  y' = (float)(Ws-1) - x;  x' = y                     box (y1, Ws - x2, y2, Ws - x1)
+ * There is no inverse flag: THE WAY BACK is code 2 - c with the ROTATED frame's (height, width); it returns every box and every
+ * integer-valued joint exactly.
+ * frame_hw: one (height, width) for everybody, or n of them (per_person_hw); codes: one, or n (per_person_code); pts (n, J, 3)
+ * and / or boxes (n, 4) -- a null input skips its output; an output may be its input.
+ * hrn_rotate_people: host, no handle; failure text: hrn_rotate_people_last_error().  hrn_rotate_people_dev: pts / boxes on the
+ * device, sizes and codes on the HOST (per-person ones travel through the pinned ring); one launch, one thread per joint and
+ * per box, stream-ordered; n == 0 launches nothing.
+ * Code 7 for both, naming the cause: n < 0; J outside [1, HRN_MAX_JOINTS]; pts and boxes both null; an input without its output;
+ * null sizes / codes with n > 0; a code outside {0, 1, 2}; a non-positive side; (device form, last) a plan-only handle. */
+enum { HRN_ROTATE_90_CW = 0, HRN_ROTATE_180 = 1, HRN_ROTATE_90_CCW = 2 };   /* the values of cv2.ROTATE_* */
+int hrn_rotate_frames(hrn_handle h, const hrn_canvas *src_host, const hrn_canvas *dst_host, int nframes,
+                      const int32_t *codes_host /* nframes entries */, void *stream);
+int hrn_rotate_people(int n, int J, const int32_t *frame_hw /* (n,2) or (1,2): the SOURCE frame */, int per_person_hw,
+                      const int32_t *codes /* n or 1 */, int per_person_code,
+                      const float *pts /* (n,J,3) or NULL */, const int32_t *boxes /* (n,4) or NULL */,
+                      float *pts_out, int32_t *boxes_out);
+const char *hrn_rotate_people_last_error(void);
+int hrn_rotate_people_dev(hrn_handle h, int n, int J, const int32_t *frame_hw_host, int per_person_hw,
+                          const int32_t *codes_host, int per_person_code, const float *pts_dev, const int32_t *boxes_dev,
+                          float *pts_out_dev, int32_t *boxes_out_dev, void *stream);
+
 /* Single-person pre-path on the GPU: replaces, for every frame of a call with multiperson=False,
  *   cv2.resize(image, (W, H), interpolation=self.interpolation); cv2.cvtColor(image, cv2.COLOR_BGR2RGB); self.transform(image)
  * (SimpleHRNet.py:213-222 for one frame, :355-366 for a stack; default interpolation cv2.INTER_CUBIC, :27) and writes the

@@ -25,6 +25,7 @@ SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "c
            "track.hip",    # the tracking link: boxes from joints, crop records from detections on the device (track_geometry.h)
            "pose_nms.hip",  # pose NMS: rescoring and hard / soft OKS NMS per image or stream in one launch (pose_nms_math.h)
            "letterbox.hip",  # the detector link: the letterboxed detector tensor, the detector's boxes back in frame coordinates (letterbox_math.h)
+           "rotate.hip",   # frame rotation: cv2.rotate for BGR / NV12 / I420 frames in one launch, people between the orientations (rotate_math.h)
            "assoc.hip",    # person ids between two frames: similarity, assignment, ids and smoothing in one launch (assoc_math.h)
            # fp16 instantiations of the three hand-scheduled kernel families (bodies shared through conv3x3_lds.inc / conv_s2.inc /
            # bottleneck_chain.inc): translation units of their own, so that each bf16 file still compiles to exactly its kernel set
@@ -259,6 +260,10 @@ SYMBOLS = {
                                                ctypes.c_float, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
     "hrn_detections_to_frame_dev": (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_int,
                                                    ctypes.c_int, ctypes.c_float, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
+    "hrn_rotate_frames": (ctypes.c_int, [_P, ctypes.POINTER(CanvasC), ctypes.POINTER(CanvasC), ctypes.c_int, _P, _P]),
+    "hrn_rotate_people": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P]),
+    "hrn_rotate_people_last_error": (ctypes.c_char_p, []),
+    "hrn_rotate_people_dev": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P, _P]),
     "hrn_yuv_from_bgr": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
     "hrn_crop_geometry": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
     "hrn_crop_geometry_last_error": (ctypes.c_char_p, []),

@@ -79,6 +79,8 @@
     CallScratch trk_table;     // the tracking link: the call's host table (frame sizes per person; frame table and frame index)
     CallScratch lb_table;      // hrn_letterbox_frames(_yuv): the frame records of a call with several frames
     CallScratch det_table;     // hrn_detections_to_frame_dev: the frame records of a call with several frames
+    CallScratch rot_table;     // hrn_rotate_frames: the plane records of a call with several frames
+    CallScratch rot_people;    // hrn_rotate_people_dev: the frame sizes / codes of a call that has them per person
 
     // the pre-path's device scratch for n people: `tmp_bytes` of intermediates (exact: they can be large), n records (and n YUV sources)
     bool pre_reserve(size_t tmp_bytes, int n, bool yuv) {
@@ -148,7 +150,7 @@
 
     void free_scratch() {
         for (CallScratch *c : {&rs_taps, &pre_tmp, &pre_params, &pre_yuv, &warp_params, &score_joints, &draw_table, &draw_records, &assoc_buf,
-                               &nms_table, &trk_table, &lb_table, &det_table})
+                               &nms_table, &trk_table, &lb_table, &det_table, &rot_table, &rot_people})
             c->release();
         pass.release();
         for (auto &kv : score_tables) (void)hipFree(kv.second);

@@ -20,6 +20,7 @@
 #include "letterbox_math.h"
 #include "pose_nms_math.h"
 #include "kernels.h"
+#include "rotate_math.h"
 #include "track_geometry.h"
 
 namespace {
@@ -1162,6 +1163,152 @@ int hrn_detections_to_frame_dev(hrn_handle h, int rule, const float *dets_dev, i
         one = frame(0);
     }
     if (!h->hip_ok(launch_detections_to_frame(a, one, q, s), "detections launch")) return 8;
+    return scope.leave() ? 0 : 6;
+}
+
+// ---- frame rotation: cv2.rotate for BGR, NV12 and I420 frames, and people between the two orientations (rotate.hip) -----------
+namespace {
+// the planes of a frame as (height, width) in elements, element size and the pitch / plane pointers of either side
+struct RotPlaneShape {
+    int h, w, es;
+    bool chroma, second;   // which pitch, and I420's V
+};
+int rotate_plane_shapes(const hrn_canvas &c, RotPlaneShape out[3]) {
+    if (c.format == HRN_PIX_BGR) {
+        out[0] = {c.height, c.width, 3, false, false};
+        return 1;
+    }
+    out[0] = {c.height, c.width, 1, false, false};
+    if (c.format == HRN_PIX_NV12) {
+        out[1] = {c.height / 2, c.width / 2, 2, true, false};
+        return 2;
+    }
+    out[1] = {c.height / 2, c.width / 2, 1, true, false};
+    out[2] = {c.height / 2, c.width / 2, 1, true, true};
+    return 3;
+}
+// what is wrong with one side of a frame of hrn_rotate_frames, or nullptr
+const char *rotate_frame_fault(const hrn_canvas &c) {
+    if (c.format != HRN_PIX_BGR && c.format != HRN_PIX_NV12 && c.format != HRN_PIX_I420)
+        return "has an unknown format (HRN_PIX_BGR, HRN_PIX_NV12 or HRN_PIX_I420)";
+    if (!c.y || (c.format != HRN_PIX_BGR && !c.u) || (c.format == HRN_PIX_I420 && !c.v)) return "has a null plane";
+    if (c.height <= 0 || c.width <= 0) return "has a non-positive width or height";
+    if (c.format != HRN_PIX_BGR && ((c.height & 1) || (c.width & 1))) return "has an odd width or height";
+    RotPlaneShape shapes[3];
+    const int np = rotate_plane_shapes(c, shapes);
+    for (int k = 0; k < np; ++k) {
+        const long pitch = shapes[k].chroma ? c.pitch_c : c.pitch_y;
+        if (pitch < (long)shapes[k].w * shapes[k].es) return shapes[k].chroma ? "has pitch_c below its chroma row's bytes" : "has pitch_y below its row's bytes";
+        if (pitch * shapes[k].h >= (1L << 31)) return "has a plane with pitch * rows >= 2^31";
+    }
+    return nullptr;
+}
+}  // namespace
+
+int hrn_rotate_frames(hrn_handle h, const hrn_canvas *src_host, const hrn_canvas *dst_host, int nframes, const int32_t *codes_host,
+                      void *stream) {
+    if (!h) return 1;
+    const auto fail = [&](const std::string &what) {
+        h->err = "hrn_rotate_frames: " + what;
+        return 7;
+    };
+    if (nframes < 0) return fail("nframes is negative");
+    if (nframes > 0 && (!src_host || !dst_host || !codes_host)) return fail("null frame tables / codes");
+    std::vector<RotPlane> planes;
+    long tiles = 0;
+    std::map<const uint8_t *, int> written;   // first plane of a destination -> its frame
+    for (int k = 0; k < nframes; ++k) {
+        const hrn_canvas &s = src_host[k], &d = dst_host[k];
+        const std::string frame = "frame " + std::to_string(k);
+        const int code = codes_host[k];
+        if (code != HRN_ROTATE_90_CW && code != HRN_ROTATE_180 && code != HRN_ROTATE_90_CCW)
+            return fail(frame + ": code " + std::to_string(code) + " is outside {0, 1, 2}");
+        if (s.format != d.format) return fail(frame + ": source and destination differ in format");
+        if (const char *fault = rotate_frame_fault(s)) return fail(frame + ": the source " + fault);
+        if (const char *fault = rotate_frame_fault(d)) return fail(frame + ": the destination " + fault);
+        const bool turn = code != HRN_ROTATE_180;
+        if (d.height != (turn ? s.width : s.height) || d.width != (turn ? s.height : s.width))
+            return fail(frame + ": the destination is " + std::to_string(d.height) + " x " + std::to_string(d.width) + ", the rotated size is " +
+                        std::to_string(turn ? s.width : s.height) + " x " + std::to_string(turn ? s.height : s.width));
+        if (!written.emplace(d.y, k).second)
+            return fail("frames " + std::to_string(written[d.y]) + " and " + std::to_string(k) + " name the same destination");
+        RotPlaneShape shapes[3];
+        const int np = rotate_plane_shapes(s, shapes);
+        for (int q = 0; q < np; ++q) {
+            RotPlane p{};
+            p.src = q == 0 ? s.y : shapes[q].second ? s.v : s.u, p.dst = q == 0 ? d.y : shapes[q].second ? d.v : d.u;
+            p.hs = shapes[q].h, p.ws = shapes[q].w, p.es = shapes[q].es, p.code = code;
+            p.spitch = shapes[q].chroma ? s.pitch_c : s.pitch_y, p.dpitch = shapes[q].chroma ? d.pitch_c : d.pitch_y;
+            const int dst_w = turn ? p.hs : p.ws, dst_h = turn ? p.ws : p.hs;
+            p.tile_start = (int)tiles, p.tiles_x = (dst_w + kRotTile - 1) / kRotTile;
+            const int tile_rows = turn ? kRotTile : kRotRows180;
+            tiles += (long)p.tiles_x * ((dst_h + tile_rows - 1) / tile_rows);
+            if (tiles > 0x7fffffffL) return fail("the call has more than 2^31 - 1 tiles");
+            planes.push_back(p);
+        }
+    }
+    for (int k = 0; k < nframes; ++k) {   // in-place rotation is not offered: no source is a destination of the call
+        const auto hit = written.find(src_host[k].y);
+        if (hit != written.end())
+            return fail("the source of frame " + std::to_string(k) + " is the destination of frame " + std::to_string(hit->second) +
+                        ": in-place rotation is not offered");
+    }
+    if (h->refuse_plan_only()) return 7;
+    if (nframes == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t table_bytes = planes.size() * sizeof(RotPlane);
+    if (nframes > 1 && !h->table_reserve(h->rot_table, table_bytes, 4096, "hipMalloc(rotation table)")) return 6;
+    CallScope scope(h, nframes > 1 ? &h->rot_table : nullptr, s);
+    if (!scope.entered) return 6;
+    RotArgs a{};
+    a.nplanes = (int)planes.size(), a.total_tiles = (int)tiles;
+    if (nframes > 1) {   // the table through the pinned ring
+        unsigned ring = 0;
+        char *pin = h->pre_stage(table_bytes, &ring);
+        if (!pin) return 6;
+        memcpy(pin, planes.data(), table_bytes);
+        if (!h->pre_upload(ring, s, {{h->rot_table.ptr, pin, table_bytes, "hipMemcpyAsync(rotation table)"}})) return 6;
+        a.table = h->rot_table.as<const RotPlane>();
+    } else {
+        for (size_t q = 0; q < planes.size(); ++q) a.one[q] = planes[q];
+    }
+    if (!h->hip_ok(launch_rotate(a, s), "rotate launch")) return 8;
+    return scope.leave() ? 0 : 6;
+}
+
+int hrn_rotate_people_dev(hrn_handle h, int n, int J, const int32_t *frame_hw_host, int per_person_hw, const int32_t *codes_host,
+                          int per_person_code, const float *pts_dev, const int32_t *boxes_dev, float *pts_out_dev, int32_t *boxes_out_dev,
+                          void *stream) {
+    if (!h) return 1;
+    if (const char *fault = rotate_people_fault(n, J, frame_hw_host, per_person_hw, codes_host, per_person_code, pts_dev, boxes_dev,
+                                                pts_out_dev, boxes_out_dev)) {
+        h->err = std::string("hrn_rotate_people_dev: ") + fault;
+        return 7;
+    }
+    if (h->refuse_plan_only()) return 7;
+    if (n == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t hw_bytes = per_person_hw ? (size_t)n * 2 * sizeof(int32_t) : 0, code_bytes = per_person_code ? (size_t)n * sizeof(int32_t) : 0;
+    const size_t need = hw_bytes + code_bytes;   // what the call has per person: a table through the pinned ring
+    if (need && !h->table_reserve(h->rot_people, need, 4096, "hipMalloc(rotated people table)")) return 6;
+    CallScope scope(h, need ? &h->rot_people : nullptr, s);
+    if (!scope.entered) return 6;
+    RotPeopleArgs a{};
+    a.n = n, a.J = J, a.hs = frame_hw_host[0], a.ws = frame_hw_host[1], a.code = codes_host[0];
+    a.pts = pts_dev, a.boxes = (const int *)boxes_dev, a.pts_out = pts_out_dev, a.boxes_out = (int *)boxes_out_dev;
+    if (need) {
+        unsigned ring = 0;
+        char *pin = h->pre_stage(need, &ring);
+        if (!pin) return 6;
+        if (hw_bytes) memcpy(pin, frame_hw_host, hw_bytes);
+        if (code_bytes) memcpy(pin + hw_bytes, codes_host, code_bytes);
+        if (!h->pre_upload(ring, s, {{h->rot_people.ptr, pin, need, "hipMemcpyAsync(rotated people table)"}})) return 6;
+        if (hw_bytes) a.frame_hw = h->rot_people.as<const int>();
+        if (code_bytes) a.codes = (const int *)(h->rot_people.ptr + hw_bytes);
+    }
+    if (!h->hip_ok(launch_rotate_people(a, s), "rotate people launch")) return 8;
     return scope.leave() ? 0 : 6;
 }
 

@@ -469,6 +469,34 @@ struct DetArgs {
 };
 hipError_t launch_detections_to_frame(const DetArgs &a, const DetFrame &one, const DetFilter &q, hipStream_t s);   // P blocks of 256
 
+// Frame rotation (rotate.hip; include/hrnet_mi355.h: hrn_rotate_frames, hrn_rotate_people_dev).
+constexpr int kRotTile = 64;       // elements per tile side, in destination coordinates
+constexpr int kRotRows180 = 16;    // ... but 64 x 16 at 180 degrees: one four-element group per thread
+struct RotPlane {                  // one plane of one frame of the call: BGR 1, NV12 2 (Y; the UV pairs), I420 3
+    const unsigned char *src;
+    unsigned char *dst;
+    int hs, ws;                    // the SOURCE plane, in elements
+    int es;                        // bytes per element: 1 (Y, U, V), 2 (NV12's UV pair), 3 (a BGR pixel)
+    int code;                      // HRN_ROTATE_*
+    int spitch, dpitch;            // bytes between rows
+    int tile_start, tiles_x;       // the plane's first tile of the launch; tiles per row of tiles of the DESTINATION
+};
+struct RotArgs {
+    int nplanes, total_tiles;
+    RotPlane one[3];               // table == nullptr: the planes of the call's only frame, in the kernel arguments
+    const RotPlane *table;         // else nplanes entries, device
+};
+hipError_t launch_rotate(const RotArgs &a, hipStream_t s);   // rotate_kernel: total_tiles blocks of 256 threads
+struct RotPeopleArgs {
+    int n, J, hs, ws, code;        // hs, ws, code: for everybody, where the per-person array is null
+    const int *frame_hw, *codes;   // (n, 2) / n on the device, or nullptr
+    const float *pts;              // (n, J, 3) or nullptr
+    const int *boxes;              // (n, 4) or nullptr
+    float *pts_out;
+    int *boxes_out;
+};
+hipError_t launch_rotate_people(const RotPeopleArgs &a, hipStream_t s);   // one thread per joint and per box
+
 struct TapArgs {           // debug tap: crops crop0, crop0 + crop_step, ... of a flat padded tensor -> (ncrops, c, h, w) fp32
     const void *in;
     float *dst;

@@ -22,6 +22,7 @@
 #include "assoc_math.h"
 #include "letterbox_math.h"
 #include "pose_nms_math.h"
+#include "rotate_math.h"
 
 #pragma clang fp contract(off)
 
@@ -463,6 +464,29 @@ int hrn_detections_to_frame(int rule, const float *dets, int det_stride, const i
     }
     return 0;
 }
+
+// ---- people between a frame and its rotation, on the host (rotate_math.h: the text rotate_people_kernel compiles) -----------------
+static thread_local std::string g_rotate_people_error;
+
+int hrn_rotate_people(int n, int J, const int32_t *frame_hw, int per_person_hw, const int32_t *codes, int per_person_code, const float *pts,
+                      const int32_t *boxes, float *pts_out, int32_t *boxes_out) {
+    using namespace hrn;
+    g_rotate_people_error.clear();
+    if (const char *fault = rotate_people_fault(n, J, frame_hw, per_person_hw, codes, per_person_code, pts, boxes, pts_out, boxes_out)) {
+        g_rotate_people_error = fault;
+        return 7;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int32_t *hw = frame_hw + (per_person_hw ? (size_t)i * 2 : 0);
+        const int code = codes[per_person_code ? i : 0];
+        if (pts)
+            for (int j = 0; j < J; ++j) rotate_joint(code, hw[0], hw[1], pts + ((size_t)i * J + j) * 3, pts_out + ((size_t)i * J + j) * 3);
+        if (boxes) rotate_box(code, hw[0], hw[1], boxes + (size_t)i * 4, boxes_out + (size_t)i * 4);
+    }
+    return 0;
+}
+
+const char *hrn_rotate_people_last_error(void) { return g_rotate_people_error.c_str(); }
 
 // the OKS of all n people of ONE problem against its person g, exactly as both entries compute it (a non-finite value as 0.0),
 // for measuring it against the reference's oks_iou; returns 0 or 7

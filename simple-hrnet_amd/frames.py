@@ -78,6 +78,16 @@ class YuvFrame:
                              % (height, width, format, pitch, self.nbytes, data.numel()))
         self.data = data[:self.nbytes]
 
+    @classmethod
+    def _trusted(cls, data: torch.Tensor, height: int, width: int, like: "YuvFrame") -> "YuvFrame":
+        """a packed frame (pitch == width) of ``like``'s format, matrix and range over the flat uint8 tensor ``data`` of exactly its
+        bytes, without the constructor's checks: ``rotate_frames``' fresh destination, whose arguments are its own"""
+        f = cls.__new__(cls)
+        f.height, f.width, f.pitch = height, width, width
+        f.format, f.matrix, f.range = like.format, like.matrix, like.range
+        f.data = data
+        return f
+
     @property
     def nbytes(self) -> int:
         return self.pitch * self.height * 3 // 2
@@ -100,6 +110,33 @@ class YuvFrame:
         entry.height, entry.width, entry.pitch_y = self.height, self.width, self.pitch
         entry.pitch_c = self.pitch if self.format == "nv12" else self.pitch // 2
         entry.format, entry.matrix, entry.range = PIX_FORMATS[self.format], YUV_MATRICES[self.matrix], YUV_RANGES[self.range]
+
+
+ROTATE_CODES = {"90cw": 0, "180": 1, "90ccw": 2}   # HRN_ROTATE_*: the values of cv2.ROTATE_90_CLOCKWISE / _180 / _90_COUNTERCLOCKWISE
+
+
+def rotation_code_from_degrees(deg) -> Optional[int]:
+    """The rotation tag of a video (degrees clockwise, what ffprobe reports) as the ``cv2.rotate`` code that turns its stored
+    frames upright -- the mapping of the reference's ``check_video_rotation`` (misc/visualization.py:271-293) without ffmpeg:
+    90 -> 0 (``ROTATE_90_CLOCKWISE``), 180 -> 1, 270 -> 2; None or 0 -> None (nothing to rotate); anything else: ValueError."""
+    if deg is None:
+        return None
+    if isinstance(deg, (bool, str)) or deg != int(deg) or int(deg) not in (0, 90, 180, 270):
+        raise ValueError("a rotation tag is 0, 90, 180 or 270 degrees, got %r" % (deg,))
+    return {0: None, 90: 0, 180: 1, 270: 2}[int(deg)]
+
+
+def rotation_codes(rotation_code, n: int) -> np.ndarray:
+    """``rotation_code`` of ``rotate_frames`` / ``rotate_people`` -- one code or n of them -- as n int32; ValueError otherwise"""
+    if type(rotation_code) is int and 0 <= rotation_code <= 2:   # (the usual call, without numpy's conversions)
+        return np.full((n,), rotation_code, np.int32)
+    codes = np.asarray(rotation_code)
+    if codes.dtype.kind not in "iu" or codes.ndim > 1 or (codes.ndim == 1 and len(codes) != n):
+        raise ValueError("rotation_code must be one integer code or one per item (%d), got %r" % (n, rotation_code))
+    codes = np.ascontiguousarray(np.broadcast_to(codes, (n,)), dtype=np.int32)
+    if ((codes < 0) | (codes > 2)).any():
+        raise ValueError("a rotation code is 0 (90 clockwise), 1 (180) or 2 (90 counter-clockwise), got %r" % (rotation_code,))
+    return codes
 
 
 def _frame_kind(frames) -> bool:
@@ -147,10 +184,12 @@ class Frames(list):
         self.yuv = _frame_kind(self) if yuv is None else yuv
 
     @classmethod
-    def resident(cls, frames, device, one: bool = False) -> "Frames":
+    def resident(cls, frames, device, one: bool = False, rows: bool = False) -> "Frames":
         """``frames`` of ``preprocess_frames`` as contiguous frames on ``device``; a 4-D stack crosses PCIe in one copy and is
         then indexed, a sequence frame by frame (once each).  A sequence of ``YuvFrame``s stays ``YuvFrame``s, now on the
-        device; one that mixes the two kinds raises ValueError.  ``one``: a single frame is taken as a sequence of one."""
+        device; one that mixes the two kinds raises ValueError.  ``one``: a single frame is taken as a sequence of one.
+        ``rows``: a BGR frame of packed pixels whose rows are strided (a view into a larger buffer) stays as it is -- for
+        ``rotate_frames``, whose ``hrn_canvas`` table carries a pitch."""
         if one and (isinstance(frames, YuvFrame) or (isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3)):
             frames = [frames]
         if isinstance(frames, np.ndarray) and frames.ndim == 4:
@@ -164,7 +203,8 @@ class Frames(list):
             frames = list(frames)
             if _frame_kind(frames):
                 return cls([None if f is None else f.to(device, non_blocking=True) for f in frames], True)
-            out = [None if f is None else as_tensor(f).to(device, non_blocking=True).contiguous() for f in frames]
+            out = [None if f is None else as_tensor(f).to(device, non_blocking=True) for f in frames]
+            out = [f if f is None or (rows and f.dim() == 3 and _bgr_rows(f)) else f.contiguous() for f in out]
         for k, f in enumerate(out):
             if f is not None:
                 _check_frame(f, k)
@@ -191,6 +231,22 @@ class Frames(list):
                 raise ValueError("frame %d cannot be drawn in place: its pixels must be packed (B, G, R) bytes in rows" % k)
             out.append(f)
         return cls(out, yuv)
+
+    def rotated(self, codes, device) -> "Frames":
+        """fresh destinations for ``rotate_frames``: per frame an (H', W', 3) tensor, or a ``YuvFrame`` of the rotated size with the
+        frame's format, matrix and range and pitch == width; None stays None"""
+        out = []
+        for f, code in zip(self, codes):
+            if f is None:
+                out.append(None)
+                continue
+            h, w = (f.height, f.width) if self.yuv else (int(f.shape[0]), int(f.shape[1]))
+            h, w = (h, w) if code == 1 else (w, h)
+            if self.yuv:
+                out.append(YuvFrame(torch.empty((h * w * 3 // 2,), dtype=torch.uint8, device=device), h, w, f.format, f.matrix, f.range))
+            else:
+                out.append(torch.empty((h, w, 3), dtype=torch.uint8, device=device))
+        return Frames(out, self.yuv)
 
     def sizes(self) -> np.ndarray:
         """(F, 2) int32 ``(height, width)`` per frame; zeros for None"""

@@ -19,8 +19,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .frames import (PIX_FORMATS, YUV_MATRICES, YUV_RANGES, Frames, YuvFrame, _check_frame, _frame_kind, as_tensor,  # noqa: F401
-                     device_tensor, frame_stack, host_array, host_bytes)
+from .frames import (PIX_FORMATS, YUV_MATRICES, YUV_RANGES, Frames, YuvFrame, _bgr_rows, _check_frame, _frame_kind, as_tensor,  # noqa: F401
+                     device_tensor, frame_stack, host_array, host_bytes, rotation_code_from_degrees, rotation_codes)
 from .palettes import bgr_to_yuv_colors, embedded_palette, find_palette  # noqa: F401
 
 DTYPES = {"fp32": 0, "f32": 0, "float32": 0, torch.float32: 0, "bf16": 1, "bfloat16": 1, torch.bfloat16: 1,
@@ -255,6 +255,10 @@ class NativeHRNet:
             self._h = ctypes.c_void_p()
             raise (ValueError if rc == 2 else RuntimeError)("hrn_create failed: " + msg)
         self._keep = None
+        # rotate_frames' lean path: the two hrn_canvas entries and the three codes of a one-frame call (read by the call before it returns)
+        self._rot_pair = (_lib.CanvasC * 2)()
+        self._rot_codes = np.arange(3, dtype=np.int32)
+        self._rot_code_ptr = [self._rot_codes.ctypes.data + 4 * k for k in range(3)]
 
     # -- lifetime -------------------------------------------------------------------------------
     def close(self):
@@ -952,6 +956,127 @@ class NativeHRNet:
                      ctypes.addressof(geometry.table), geometry.frame_hw.ctypes.data, geometry.size[0], geometry.size[1], int(conf_col),
                      ctypes.c_float(thres), col, ids.ctypes.data, len(ids), flags, out.data_ptr(), kept.data_ptr(), status.data_ptr())
         return out, kept, status
+
+    # -- frame rotation: a video stored sideways, upright without leaving the device -----------------------------------------------
+    def rotate_frames(self, frames, rotation_code, out=None):
+        """``cv2.rotate(frame, rotation_code)`` on the GPU (``hrn_rotate_frames``: ONE launch for all frames, no scratch) -- the
+        first step of the reference's frame loops for a video with a rotation tag (``scripts/live-demo.py:102-103``).  A pure
+        permutation of pixels: bit for bit ``np.rot90`` per plane (include/hrnet_mi355.h has the rule).
+
+        ``frames``: one (H, W, 3) uint8 BGR frame, an (F, H, W, 3) stack, a sequence of frames of any sizes, or ``YuvFrame``(s);
+        host frames are uploaded once, None entries pass through.  ``rotation_code``: 0 (90 degrees clockwise), 1 (180), 2 (90
+        counter-clockwise) -- ``cv2.ROTATE_*``'s values, see ``rotation_code_from_degrees`` -- for every frame, or one per frame;
+        None returns the resident frames unrotated.  Returns the rotated frames on the GPU in the shape they came in: a frame, a
+        stack (its frames then turn alike: all by 180 degrees or none), or a list; a ``YuvFrame`` comes back as a ``YuvFrame``
+        with swapped sides, its own format, matrix and range, and pitch == width.
+        ``out``: destinations on the engine's GPU to write into instead (the same shape of argument; pitched BGR views and pitched
+        ``YuvFrame``s are allowed; bytes of a row beyond its pixels keep their value); they are returned.  A destination may not
+        be a source: in-place rotation is not offered.  Nothing is synchronised."""
+        dev = self.torch_device
+        if out is None and type(rotation_code) is int and 0 <= rotation_code <= 2:
+            turned = self._rotate_one(frames, rotation_code, dev)
+            if turned is not None:
+                return turned
+        single = isinstance(frames, YuvFrame) or (isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3)
+        stack = not single and isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 4
+        if stack:   # uploaded here, in one copy: what comes back unrotated is this tensor
+            frames = as_tensor(frames).to(dev, non_blocking=True).contiguous()
+        src = Frames.resident(frames, dev, one=True, rows=True)
+        if rotation_code is None:
+            return src[0] if single else frames if stack else list(src)
+        codes = rotation_codes(rotation_code, len(src))
+        whole = None   # a stack's destination, as one tensor
+        if out is None:
+            if stack:
+                if len({int(c) == 1 for c in codes}) > 1:
+                    raise ValueError("the frames of a stack come back as a stack: they all turn by 180 degrees, or none does")
+                h, w = (int(d) for d in src[0].shape[:2]) if len(src) else (0, 0)
+                h, w = (h, w) if len(codes) and codes[0] == 1 else (w, h)
+                whole = torch.empty((len(src), h, w, 3), dtype=torch.uint8, device=dev)
+                dst = Frames([whole[k] for k in range(len(src))], False)
+            else:
+                dst = src.rotated(codes, dev)
+        else:
+            if stack and isinstance(out, torch.Tensor) and out.dim() == 4:
+                whole, out = out, [out[k] for k in range(int(out.shape[0]))]
+            items = [out] if single else list(out)
+            if len(items) != len(src):
+                raise ValueError("out has %d frames for %d" % (len(items), len(src)))
+            for k, f in enumerate(items):
+                if f is not None and (not isinstance(f, (torch.Tensor, YuvFrame)) or f.device != dev):
+                    raise ValueError("out[%d] must lie on the engine's device %s: it is written where it is" % (k, dev))
+            dst = Frames.canvases(items, dev)
+            if dst.yuv != src.yuv and any(f is not None for f in src):
+                raise ValueError("out must hold frames of the kind of `frames`: BGR tensors or YuvFrames")
+        live = [k for k, f in enumerate(src) if f is not None]
+        if any(dst[k] is None for k in live):
+            raise ValueError("out has no destination for a frame that is there")
+        if live:
+            s_table = Frames([src[k] for k in live], src.yuv).table(kind=_lib.CanvasC)
+            d_table = Frames([dst[k] for k in live], src.yuv).table(kind=_lib.CanvasC)
+            picked = np.ascontiguousarray(codes[live])
+            self._launch("hrn_rotate_frames", s_table, d_table, len(live), picked.ctypes.data)
+        if single:
+            return dst[0]
+        return whole if whole is not None else [dst[k] if src[k] is not None else None for k in range(len(src))]
+
+    def _rotate_one(self, frame, code: int, dev):
+        """the lean path of ``rotate_frames`` -- ONE frame that lies on the engine's GPU, one code, a fresh destination: the call a
+        video loop makes per frame, which is launch-bound, so the host side is what it costs.  None: not that case."""
+        src, dst = self._rot_pair[0], self._rot_pair[1]
+        if isinstance(frame, torch.Tensor):
+            if frame.dim() != 3 or frame.device != dev or frame.dtype != torch.uint8 or frame.shape[2] != 3 or not _bgr_rows(frame):
+                return None
+            h, w = int(frame.shape[0]), int(frame.shape[1])
+            if h < 1 or w < 1:
+                return None
+            rh, rw = (h, w) if code == 1 else (w, h)
+            out = torch.empty((rh, rw, 3), dtype=torch.uint8, device=dev)
+            src.y, src.height, src.width, src.pitch_y, src.format = frame.data_ptr(), h, w, max(int(frame.stride(0)), 3 * w), 0
+            dst.y, dst.height, dst.width, dst.pitch_y, dst.format = out.data_ptr(), rh, rw, 3 * rw, 0
+        elif isinstance(frame, YuvFrame) and frame.device == dev:
+            rh, rw = (frame.height, frame.width) if code == 1 else (frame.width, frame.height)
+            out = YuvFrame._trusted(torch.empty((rh * rw * 3 // 2,), dtype=torch.uint8, device=dev), rh, rw, frame)
+            frame._fill(src)
+            out._fill(dst)
+        else:
+            return None
+        if torch.cuda.current_device() != self.device_index:
+            self._launch("hrn_rotate_frames", ctypes.byref(src), ctypes.byref(dst), 1, self._rot_code_ptr[code])
+        else:   # already on the engine's device: no device context to enter and leave (the library selects its device itself)
+            self._check(self._lib.hrn_rotate_frames(self._h, ctypes.byref(src), ctypes.byref(dst), 1, self._rot_code_ptr[code], self._stream()),
+                        "hrn_rotate_frames")
+        return out
+
+    def rotate_people(self, pts=None, boxes=None, frame_hw=None, rotation_code=None):
+        """``postproc.rotate_people`` on the GPU (``hrn_rotate_people_dev``: one launch, one thread per joint and per box, no host
+        read): joints and boxes computed on one orientation of a frame, in the coordinates of the other.  ``pts`` (n, J, 3)
+        float32 ``(y, x, confidence)`` and / or ``boxes`` (n, 4) int32 ``(x1, y1, x2, y2)`` where the engine left them (a host
+        array is uploaded); ``frame_hw``: (height, width) of the SOURCE frame for everybody, or (n, 2); ``rotation_code``: one code
+        or n.  Returns the rotated tensor on the GPU -- ``(pts, boxes)`` when both were given -- bit for bit the host form's.  The
+        way back is code ``2 - c`` with the rotated frame's size."""
+        from .postproc import rotate_people_arguments
+
+        dev = self.torch_device
+        if pts is not None:
+            pts = as_tensor(pts, np.float32)
+            if pts.dim() != 3 or pts.shape[2] != 3:
+                raise ValueError("pts must be (n, J, 3), got %s" % (tuple(pts.shape),))
+            pts = device_tensor(pts, dev, torch.float32)
+        if boxes is not None:
+            boxes = as_tensor(boxes, np.int32)
+            if boxes.dim() != 2 or boxes.shape[1] != 4:
+                raise ValueError("boxes must be (n, 4), got %s" % (tuple(boxes.shape),))
+            boxes = device_tensor(boxes, dev, torch.int32)
+        n, J, hw, per_hw, codes, per_code = rotate_people_arguments(None if pts is None else tuple(pts.shape),
+                                                                     None if boxes is None else tuple(boxes.shape), frame_hw, rotation_code)
+        pts_out = None if pts is None else torch.empty_like(pts)
+        boxes_out = None if boxes is None else torch.empty_like(boxes)
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        if n > 0:   # (nobody: an empty tensor has no address to hand over, and nothing would be launched)
+            self._launch("hrn_rotate_people_dev", n, J, hw.ctypes.data, per_hw, codes.ctypes.data, per_code, ptr(pts), ptr(boxes), ptr(pts_out),
+                         ptr(boxes_out))
+        return pts_out if boxes is None else boxes_out if pts is None else (pts_out, boxes_out)
 
     # -- person ids between two frames: who of the previous frame is who of this one ------------------------------------------------
     def associate_people(self, boxes, pts, prev_boxes, prev_pts, prev_ids, next_id, pose_alpha: float = 0.5,

@@ -569,3 +569,46 @@ def detections_to_frame(dets, geometry: LetterboxGeometry, counts=None, conf_thr
     if rc != 0:
         raise ValueError("hrn_detections_to_frame: " + lib.hrn_letterbox_last_error().decode())
     return out, kept, status
+
+
+# -- people between a frame and its rotation, on the host ------------------------------------------------------------------------
+def rotate_people_arguments(pts_shape, boxes_shape, frame_hw, rotation_code):
+    """the host arguments ``rotate_people`` and ``NativeHRNet.rotate_people`` share: (n, J, frame sizes int32, their per-person flag,
+    codes int32, their per-person flag)"""
+    from .frames import rotation_codes
+
+    if pts_shape is None and boxes_shape is None:
+        raise ValueError("rotate_people needs pts, boxes or both")
+    if pts_shape is not None and boxes_shape is not None and pts_shape[0] != boxes_shape[0]:
+        raise ValueError("pts and boxes must describe the same people: %d and %d" % (pts_shape[0], boxes_shape[0]))
+    n = int((pts_shape or boxes_shape)[0])
+    J = int(pts_shape[1]) if pts_shape is not None else 1
+    if frame_hw is None or rotation_code is None:
+        raise ValueError("rotate_people needs frame_hw (the SOURCE frame's height and width) and rotation_code")
+    hw, per_hw = _frame_sizes(frame_hw, n)
+    one = np.ndim(rotation_code) == 0
+    return n, J, hw, per_hw, rotation_codes(rotation_code, 1 if one else n), int(not one and n > 1)
+
+
+def rotate_people(pts=None, boxes=None, frame_hw=None, rotation_code=None):
+    """Joints and boxes of people between a frame and its ``cv2.rotate``-d form, on the host (``hrn_rotate_people``, no GPU).
+    ``pts`` (n, J, 3) float32 ``(y, x, confidence)`` and / or ``boxes`` (n, 4) int32 half-open ``(x1, y1, x2, y2)``; ``frame_hw``:
+    (height, width) of the SOURCE frame for everybody, or (n, 2); ``rotation_code``: 0 (90 degrees clockwise), 1 (180), 2 (90
+    counter-clockwise), one or n.  A coordinate is one float32 subtraction or a copy; NaN and inf pass through; the all-zero box of
+    a lost person stays all-zero (include/hrnet_mi355.h has the table).  Returns the rotated array -- ``(pts, boxes)`` when both
+    were given.  There is no inverse flag: the way back is code ``2 - c`` with the ROTATED frame's (height, width)."""
+    p = None if pts is None else np.ascontiguousarray(np.asarray(pts, dtype=np.float32))
+    b = None if boxes is None else np.ascontiguousarray(np.asarray(boxes, dtype=np.int32))
+    if p is not None and (p.ndim != 3 or p.shape[2] != 3):
+        raise ValueError("pts must be (n, J, 3), got %s" % (p.shape,))
+    if b is not None and (b.ndim != 2 or b.shape[1] != 4):
+        raise ValueError("boxes must be (n, 4), got %s" % (b.shape,))
+    n, J, hw, per_hw, codes, per_code = rotate_people_arguments(None if p is None else p.shape, None if b is None else b.shape, frame_hw,
+                                                                 rotation_code)
+    p_out, b_out = None if p is None else np.empty_like(p), None if b is None else np.empty_like(b)
+    ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+    lib = _lib.load()
+    rc = lib.hrn_rotate_people(n, J, hw.ctypes.data, per_hw, codes.ctypes.data, per_code, ptr(p), ptr(b), ptr(p_out), ptr(b_out))
+    if rc != 0:
+        raise ValueError("hrn_rotate_people: " + lib.hrn_rotate_people_last_error().decode())
+    return p_out if b is None else b_out if p is None else (p_out, b_out)
