@@ -855,6 +855,9 @@ int hrn_plan_direct_map(hrn_handle h, int group, int n, int32_t *blocks, int cap
  * couts, at most one block per CU, every block an equal run of tiles. */
 int hrn_plan_s2_map(hrn_handle h, int group, int n, int32_t *blocks, int capacity, int32_t *parts, int part_capacity,
                     int32_t *active);
+/* The head / decode split of a call of n crops (works on plan-only handles): returns the number of slabs a heat-map is cut
+ * into, *slab_px = pixels per slab (1024, or 256 for a call of a few crops); -1 for a bad handle / n. */
+int hrn_plan_head_slabs(hrn_handle h, int n, int32_t *slab_px);
 /* per-kernel HIP-event timing of one pass (dominant-kernel roofline in bench.py):
  * runs one micro-batch of n crops and returns, for conv i, its device time in ms. */
 int hrn_profile_pass(hrn_handle h, const void *images_dev, int n, float *conv_ms, int conv_ms_len,

@@ -23,7 +23,10 @@
         if (plan_only) {
             fill_problems();
             index_s2groups();
-            blob = (char *)calloc(1, (size_t)blob_bytes);
+            // zero pages straight from the kernel, touched only where weights are written: calloc may hand back a recycled heap chunk and
+            // clear all of it (over 100 MB per handle), which made sweeps over thousands of plan-only handles allocator-dependent
+            blob = (char *)mmap(nullptr, (size_t)blob_bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+            if (blob == (char *)MAP_FAILED) blob = nullptr;
             return blob != nullptr;
         }
         if (!hip_ok(hipSetDevice(device), "hipSetDevice")) return false;
@@ -525,7 +528,7 @@
 
     void free_all() {
         if (plan_only) {
-            free(blob);
+            if (blob) (void)munmap(blob, (size_t)blob_bytes);
         } else {
             (void)hipSetDevice(device);
             for (auto &b : buffers)

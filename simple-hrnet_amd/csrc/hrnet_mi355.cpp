@@ -5,6 +5,7 @@
 #include "../../include/hrnet_mi355.h"
 
 #include <hip/hip_runtime.h>
+#include <sys/mman.h>
 
 #include <algorithm>
 #include <cmath>
@@ -1722,6 +1723,12 @@ int hrn_plan_s2_map(hrn_handle h, int group, int n, int32_t *blocks, int capacit
         }
     if (active) *active = h->s2_active(g, n) ? 1 : 0;
     return nblocks | (np << 20);
+}
+
+int hrn_plan_head_slabs(hrn_handle h, int n, int32_t *slab_px) {
+    if (!h || n <= 0 || n > h->max_batch) return -1;
+    if (slab_px) *slab_px = h->head_px_for(n);
+    return h->head_slabs_for(n);
 }
 
 int hrn_profile_pass(hrn_handle h, const void *images_dev, int n, float *conv_ms, int conv_ms_len, float *other_ms,
