@@ -858,6 +858,14 @@ int hrn_plan_s2_map(hrn_handle h, int group, int n, int32_t *blocks, int capacit
 /* The head / decode split of a call of n crops (works on plan-only handles): returns the number of slabs a heat-map is cut
  * into, *slab_px = pixels per slab (1024, or 256 for a call of a few crops); -1 for a bad handle / n. */
 int hrn_plan_head_slabs(hrn_handle h, int n, int32_t *slab_px);
+/* Where a grouped launch sits in a pass and how its blocks loop (works on plan-only handles).  kind 0: the `index`-th grouped
+ * BasicBlock launch (hrn_plan_block_map numbering); kind 1: the `index`-th launch of the layer1 chain kernel.  out[0] = position
+ * in the launch list, out[1] = 1 when a pass walks this launch's tensors backwards (every odd position; pass it to
+ * hrn_plan_block_map as `reverse`); kind 1 also: out[2] = waves of the launch of a call of n crops (persistent blocks x waves per
+ * block), out[3] = 16-pixel fragments they share by a grid-stride loop, out[4] = the kernel form (0: conv3 + the next conv1,
+ * 1: with the projection shortcut, 2: with the 3x3 in front, 3: that on a layer's last block).  `out` holds five int32.
+ * Returns 0, -1 for a bad kind / index / n. */
+int hrn_plan_launch_walk(hrn_handle h, int kind, int index, int n, int32_t *out);
 /* per-kernel HIP-event timing of one pass (dominant-kernel roofline in bench.py):
  * runs one micro-batch of n crops and returns, for conv i, its device time in ms. */
 int hrn_profile_pass(hrn_handle h, const void *images_dev, int n, float *conv_ms, int conv_ms_len,

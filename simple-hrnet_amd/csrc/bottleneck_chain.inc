@@ -244,12 +244,9 @@ static hipError_t launch_chain_t(const ChainArgs &a, hipStream_t s) {
         if (e != hipSuccess) return e;
     }
     // persistent: 8 waves per CU re-use their staged weights over many 16-pixel fragments
-    const int blocks_env = a.max_blocks > 0 ? a.max_blocks : 512;
     constexpr int WAVES = C3 ? C3_WAVES : DS ? 8 : 4;
-    const int mfrags = (a.m + 15) / 16;
-    int blocks = (mfrags + WAVES - 1) / WAVES;
-    const int cap = (DS || C3) ? (blocks_env / 2 > 1 ? blocks_env / 2 : 1) : blocks_env;   // (HRN_CHAIN_BLOCKS < 2 must not give a zero grid)
-    if (blocks > cap) blocks = cap;
+    static_assert(WAVES == chain_waves(DS, C3 != 0), "kernels.h: chain_waves");
+    const int blocks = chain_grid(a.m, DS, C3 != 0, a.max_blocks);
     hipLaunchKernelGGL((bottleneck_chain_kernel<DS, C3, DT>), dim3(blocks), dim3(64 * WAVES), lds_bytes(DS, C3), s, a);
     return hipGetLastError();
 }

@@ -1731,6 +1731,25 @@ int hrn_plan_head_slabs(hrn_handle h, int n, int32_t *slab_px) {
     return h->head_slabs_for(n);
 }
 
+int hrn_plan_launch_walk(hrn_handle h, int kind, int index, int n, int32_t *out) {
+    if (!h || !out || n <= 0 || n > h->max_batch || index < 0) return -1;
+    if (kind != 0 && kind != 1) return -1;
+    if (index >= (int)(kind == 0 ? h->groups.size() : h->chains.size())) return -1;
+    int pos = -1;
+    for (size_t oi = 0; oi < h->ops.size(); ++oi)
+        if (h->ops[oi].kind == (kind == 0 ? OP_CONV3_GROUP : OP_CHAIN) && h->ops[oi].idx == index) pos = (int)oi;
+    if (pos < 0) return -1;
+    out[0] = pos, out[1] = h->alternate && (pos & 1) ? 1 : 0, out[2] = out[3] = out[4] = 0;   // (run_pass: rev)
+    if (kind == 1) {
+        const auto &ch = h->chains[index];
+        out[4] = ch.conv2 >= 0 ? (ch.conv1 >= 0 ? 2 : 3) : ch.ds >= 0 ? 1 : 0;   // (launch_bottleneck_chain_t)
+        const int m = n * h->tensors[h->convs[ch.conv3].out_t].hpwp;
+        out[2] = chain_waves(ch.ds >= 0, ch.conv2 >= 0) * chain_grid(m, ch.ds >= 0, ch.conv2 >= 0, h->chain_blocks);
+        out[3] = (m + 15) / 16;
+    }
+    return 0;
+}
+
 int hrn_profile_pass(hrn_handle h, const void *images_dev, int n, float *conv_ms, int conv_ms_len, float *other_ms,
                      void *stream) {
     if (!h) return 1;

@@ -171,6 +171,16 @@ struct ChainArgs {
     int rev;
     int max_blocks;        // persistent blocks of the launch (512: two per CU)
 };
+// the grid of a chain-kernel launch (bottleneck_chain.inc: launch_chain_t; hrn_plan_launch_walk reports it): waves per block of the
+// kernel form (projection shortcut folded in: `ds`; the 3x3 in front of conv3: `c3`) and the persistent blocks of a call of m rows
+constexpr int chain_waves(bool ds, bool c3) { return c3 || ds ? 8 : 4; }
+inline int chain_grid(int m, bool ds, bool c3, int max_blocks) {
+    const int blocks_env = max_blocks > 0 ? max_blocks : 512;
+    const int waves = chain_waves(ds, c3), mfrags = (m + 15) / 16;
+    const int blocks = (mfrags + waves - 1) / waves;
+    const int cap = (ds || c3) ? (blocks_env / 2 > 1 ? blocks_env / 2 : 1) : blocks_env;   // (HRN_CHAIN_BLOCKS < 2 must not give a zero grid)
+    return blocks > cap ? cap : blocks;
+}
 hipError_t launch_bottleneck_chain(const ChainArgs &a, hipStream_t s);
 hipError_t launch_bottleneck_chain_f16(const ChainArgs &a, hipStream_t s);   // bottleneck_chain_f16.hip
 

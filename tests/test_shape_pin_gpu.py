@@ -149,7 +149,7 @@ SHAPES_16 = [s for s in C.PIN_SHAPES if s[4] != "fp32"]
 SHAPES_32 = [s for s in C.PIN_SHAPES if s[4] == "fp32"]
 
 
-@pytest.mark.parametrize("variant", list(C.VARIANTS))
+@pytest.mark.parametrize("variant", list(C.PIN_VARIANTS))
 @pytest.mark.parametrize("shape", SHAPES_16, ids=_id)
 def test_every_operation_at_a_covering_shape(pkg, monkeypatch, shape, variant):
     """bf16 / fp16: every operation against the emulation on the engine's own stored inputs (Pinner, unchanged bounds); then, end to
@@ -199,7 +199,7 @@ def test_every_operation_at_a_covering_shape(pkg, monkeypatch, shape, variant):
           % (_id(shape), variant, done, worst[0], worst[1], worst_loose[0], worst_loose[1], 100 * differ[2], differ[0], time.time() - t0))
 
 
-@pytest.mark.parametrize("variant", list(C.VARIANTS))
+@pytest.mark.parametrize("variant", list(C.PIN_VARIANTS))
 @pytest.mark.parametrize("shape", SHAPES_32, ids=_id)
 def test_fp32_taps_at_a_covering_shape(pkg, monkeypatch, shape, variant):
     """fp32: the comparator of test_bf16_pin.test_fp32_engine_taps_meet_the_unrounded_emulation as it stands -- every tap within 1e-4
