@@ -330,6 +330,60 @@ int hrn_assoc_exp(const double *x, int n, double *out);
 int hrn_associate_similarity(const int32_t *boxes, const float *pts, int n, const int32_t *prev_boxes, const float *prev_pts, int m, int J,
                              double pose_alpha, double *cost_out /* (n,m) */, float *sim_out /* (n,m) */);
 
+/* ---- joints over time: One-Euro smoothing and motion lookahead, on the host and on the device ----
+ * The One-Euro filter (Casiez, Roussel, Vogel, CHI 2012) of every joint, a first-order low-pass whose cut-off rises with the
+ * filtered speed, and the prediction its derivative estimate gives: next frame's joints ~ this frame's RAW joints + filtered
+ * velocity * lookahead (what hrn_boxes_from_poses / the tracking link should be fed instead of where the joints were).  The state
+ * follows people through `match` as hrn_associate_people(_dev) writes it, so on the device it never passes through the host.
+ * Both entries serve P independent streams with segment tables as in hrn_associate_people: stream p has the current people
+ * [cur_start[p], cur_start[p + 1]) and the previous people [prev_start[p], prev_start[p + 1]).  The arithmetic is
+ * csrc/temporal_math.h's, one text for both entries: plain C++, fp contraction off, doubles, the operation order below, no library
+ * call -- every operation one correctly rounded IEEE operation.
+ *   Per call   dt (seconds since the previous frame), min_cutoff, beta, d_cutoff, lookahead as doubles; threshold as a float.
+ *   State      state (n, J, 6) float32 = (y_raw, x_raw, y_hat, x_hat, dy_hat, dx_hat); age (n, J) int32: 0 no state, 1 initialised
+ *              by this update, otherwise the previous age + 1, saturating at 2^30.
+ *   alpha      TWO_PI = 6.283185307179586;  alpha(fc) = 1.0 / (1.0 + (1.0 / (TWO_PI * fc)) / dt), in exactly this order.
+ *   LIVE       joint (i, j) of this frame is live iff confidence > threshold and y, x are finite.  The compare is in float32, so
+ *              equality and NaN are not live: hrn_pose_boxes' predicate.
+ *   PRIOR      the joint has a prior iff person i's match lies in [0, m_p) of its stream AND that previous person's age[j] > 0.
+ *              A match outside [-1, m_p) counts as -1.  match == NULL: nobody has a prior.
+ *   Not live   pts_out and pred_out carry the input through, bit for bit; the six state values are +0.0f and age is 0.
+ *   Live without a prior   raw = hat = v (the input's bits), d_hat = +0.0f, age = 1; output and prediction equal the input.
+ *   Live with a prior      per axis, y then x, with x = (double)v and r, p, d the previous raw, hat, d_hat widened:
+ *                  raw_d = (x - r) / dt                       the derivative of RAW samples, as in the paper's reference code
+ *                  dh    = d + alpha(d_cutoff) * (raw_d - d)
+ *                  fc    = min_cutoff + beta * fabs(dh)
+ *                  xh    = p + alpha(fc) * (x - p)            the lerp form: a constant input is a fixed point, exactly
+ *                  store (float)xh, (float)dh, raw = v;  age = min(previous age + 1, 2^30)
+ *                  pred  = (float)(x + (double)(float)dh * lookahead)
+ *              pts_out holds (float)xh.  If (float)xh or (float)dh of either axis is not finite, the whole joint is re-initialised
+ *              as "live without a prior": a stored state is always finite.  A non-finite pred component becomes the input's.
+ *   The confidence is copied untouched into pts_out and pred_out.
+ * THE PREDICTION STARTS FROM THE RAW POSITION on purpose: on steady motion the filtered position lags (about 4 px at 1 px/frame and
+ * 21 px at 60 px/frame with min_cutoff 1, beta 0.007, d_cutoff 1 at 30 frames/s) while raw + velocity converges to zero error.
+ * The lag is the filter's known trade, tuned by beta.
+ *   pts        (n, J, 3) float32 (y, x, confidence)           match     n int32, counted from prev_start[p]; NULL: no priors
+ *   prev_state (m, J, 6), prev_age (m, J)                     the state the previous call wrote
+ *   pts_out    (n, J, 3); may be pts itself                   pred_out  (n, J, 3) or NULL: not wanted
+ *   state      (n, J, 6) out, age (n, J) out
+ * Code 7 for both, judged before anything is written, named by hrn_filter_poses_last_error() (per thread) / hrn_last_error(h): P < 0;
+ * J outside [1, HRN_MAX_JOINTS]; dt, min_cutoff or d_cutoff not finite or not positive; beta or lookahead not finite or negative;
+ * null segment tables with P > 0; a table that starts below zero or decreases; null pts / pts_out / state / age with n > 0; more than
+ * 2^31 - 1 (person, joint) pairs in one call; state / age overlapping prev_state / prev_age; m > 0 with null previous arrays while
+ * match is given; then, for the device entry, a plan-only handle.  There is no cap on people per stream.
+ * hrn_filter_poses is the host form: no handle, no GPU.  hrn_filter_poses_dev has every array in device memory and the two segment
+ * tables on the HOST: ONE launch, one thread per (person, joint), 256-thread blocks, the state gathered through match; no atomics,
+ * no scratch, one writer per byte, stream-ordered, no host read; its results equal the host form's bit for bit.  P == 1 uploads
+ * nothing; P > 1 sends one table (8 bytes per person) through one upload; P == 0 or n == 0 launches nothing. */
+int hrn_filter_poses(int P, const int32_t *cur_start, const int32_t *prev_start, int J, const float *pts, const int32_t *match,
+                     const float *prev_state, const int32_t *prev_age, double dt, double min_cutoff, double beta, double d_cutoff,
+                     float threshold, double lookahead, float *pts_out, float *pred_out, float *state, int32_t *age);
+const char *hrn_filter_poses_last_error(void);
+int hrn_filter_poses_dev(hrn_handle h, int P, const int32_t *cur_start_host, const int32_t *prev_start_host, int J,
+                         const float *pts_dev, const int32_t *match_dev, const float *prev_state_dev, const int32_t *prev_age_dev,
+                         double dt, double min_cutoff, double beta, double d_cutoff, float threshold, double lookahead,
+                         float *pts_out_dev, float *pred_out_dev, float *state_dev, int32_t *age_dev, void *stream);
+
 /* ---- pose NMS: rescoring and OKS non-maximum suppression per image or stream, on the host and on the device ----
  * What the evaluation does after the last batch (datasets/COCO.py:353-382: every person's score becomes box score times the mean
  * confidence of its joints above in_vis_thre, then oks_nms or soft_oks_nms per image, misc/nms/nms.py:75-177), and what a video

@@ -22,6 +22,7 @@
 #include "pose_nms_math.h"
 #include "kernels.h"
 #include "rotate_math.h"
+#include "temporal_math.h"
 #include "track_geometry.h"
 
 namespace {
@@ -1310,6 +1311,47 @@ int hrn_rotate_people_dev(hrn_handle h, int n, int J, const int32_t *frame_hw_ho
         if (code_bytes) a.codes = (const int *)(h->rot_people.ptr + hw_bytes);
     }
     if (!h->hip_ok(launch_rotate_people(a, s), "rotate people launch")) return 8;
+    return scope.leave() ? 0 : 6;
+}
+
+// the One-Euro filter and the motion lookahead of every joint of the call in one launch (temporal.hip); the arguments are judged
+// first (temporal_math.h's temporal_fault, as in the host form: they need no device), then the handle.  Only a call with several
+// problems touches the handle (the per-person segment table), so only that call enters a guard.
+int hrn_filter_poses_dev(hrn_handle h, int P, const int32_t *cur_start_host, const int32_t *prev_start_host, int J, const float *pts_dev,
+                         const int32_t *match_dev, const float *prev_state_dev, const int32_t *prev_age_dev, double dt, double min_cutoff,
+                         double beta, double d_cutoff, float threshold, double lookahead, float *pts_out_dev, float *pred_out_dev,
+                         float *state_dev, int32_t *age_dev, void *stream) {
+    if (!h) return 1;
+    if (const char *fault = temporal_fault(P, cur_start_host, prev_start_host, J, pts_dev, match_dev, prev_state_dev, prev_age_dev, dt,
+                                           min_cutoff, beta, d_cutoff, lookahead, pts_out_dev, state_dev, age_dev)) {
+        h->err = std::string("hrn_filter_poses_dev: ") + fault;
+        return 7;
+    }
+    if (h->refuse_plan_only()) return 7;
+    const int n = P > 0 ? cur_start_host[P] - cur_start_host[0] : 0;
+    if (n == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t table_bytes = P > 1 ? (size_t)n * sizeof(TemporalSegment) : 0;
+    if (table_bytes && !h->table_reserve(h->tmp_table, table_bytes, 4096, "hipMalloc(filter segment table)")) return 6;
+    CallScope scope(h, table_bytes ? &h->tmp_table : nullptr, s);
+    if (!scope.entered) return 6;
+    TemporalArgs a{};
+    a.J = J, a.first = cur_start_host[0], a.total = n * J;   // (n * J <= 2^31 - 1: temporal_fault)
+    a.one.prev0 = prev_start_host[0], a.one.m = prev_start_host[1] - prev_start_host[0];
+    if (table_bytes) {   // every person's segment through the pinned ring
+        unsigned ring = 0;
+        TemporalSegment *pin = (TemporalSegment *)h->pre_stage(table_bytes, &ring);
+        if (!pin) return 6;
+        for (int p = 0; p < P; ++p)
+            for (int i = cur_start_host[p]; i < cur_start_host[p + 1]; ++i)
+                pin[i - a.first] = TemporalSegment{prev_start_host[p], prev_start_host[p + 1] - prev_start_host[p]};
+        if (!h->pre_upload(ring, s, {{h->tmp_table.ptr, pin, table_bytes, "hipMemcpyAsync(filter segment table)"}})) return 6;
+        a.table = h->tmp_table.as<const TemporalSegment>();
+    }
+    a.pts = pts_dev, a.match = (const int *)match_dev, a.prev_state = prev_state_dev, a.prev_age = (const int *)prev_age_dev;
+    a.pts_out = pts_out_dev, a.pred_out = pred_out_dev, a.state = state_dev, a.age = (int *)age_dev;
+    if (!h->hip_ok(launch_temporal(a, temporal_params(dt, min_cutoff, beta, d_cutoff, threshold, lookahead), s), "filter launch")) return 8;
     return scope.leave() ? 0 : 6;
 }
 

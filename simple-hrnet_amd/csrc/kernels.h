@@ -507,6 +507,26 @@ struct RotPeopleArgs {
 };
 hipError_t launch_rotate_people(const RotPeopleArgs &a, hipStream_t s);   // one thread per joint and per box
 
+// Joints over time (temporal.hip; include/hrnet_mi355.h: hrn_filter_poses_dev): the One-Euro filter and the motion lookahead of
+// every joint of the call in one launch, one thread per (person, joint) (the arithmetic: temporal_math.h).
+struct TemporalParams;
+struct TemporalSegment {           // where one current person's previous people lie: m of them from prev0
+    int prev0, m;
+};
+struct TemporalArgs {
+    int J, first, total;           // people first .. of the arrays; total = people * J threads
+    TemporalSegment one;           // table == nullptr: everybody's segment, in the kernel arguments (nothing is uploaded)
+    const TemporalSegment *table;  // else one entry per person of the call, device
+    const float *pts;              // (n, J, 3)
+    const int *match;              // n, or nullptr: nobody has a prior
+    const float *prev_state;       // (m, J, 6)
+    const int *prev_age;           // (m, J)
+    float *pts_out, *pred_out;     // (n, J, 3); pts_out may be pts, pred_out may be nullptr
+    float *state;                  // out: (n, J, 6)
+    int *age;                      // out: (n, J)
+};
+hipError_t launch_temporal(const TemporalArgs &a, const TemporalParams &prm, hipStream_t s);   // temporal_kernel: 256-thread blocks
+
 struct TapArgs {           // debug tap: crops crop0, crop0 + crop_step, ... of a flat padded tensor -> (ncrops, c, h, w) fp32
     const void *in;
     float *dst;

@@ -4,6 +4,7 @@
 //     (live demo: scripts/live-demo.py:120-123)
 //   * person ids and pose NMS in the arithmetic their kernels compile (assoc_math.h, pose_nms_math.h): the host forms of
 //     hrn_associate_people_dev and hrn_pose_nms_dev, equal to them bit for bit
+//   * joints over time (temporal_math.h): the One-Euro filter and the motion lookahead, the host form of hrn_filter_poses_dev
 // These are O(people^2 * joints) on a handful of skeletons: they are host code in the reference (numpy + the munkres
 // package) and stay host code here -- a kernel launch costs more than the whole computation.  What matters is that the
 // numbers are the reference's: float64 arithmetic in numpy's operation order (its pairwise summation included), float32
@@ -23,6 +24,7 @@
 #include "letterbox_math.h"
 #include "pose_nms_math.h"
 #include "rotate_math.h"
+#include "temporal_math.h"
 
 #pragma clang fp contract(off)
 
@@ -487,6 +489,42 @@ int hrn_rotate_people(int n, int J, const int32_t *frame_hw, int per_person_hw, 
 }
 
 const char *hrn_rotate_people_last_error(void) { return g_rotate_people_error.c_str(); }
+
+// ---- joints over time on the host: the One-Euro filter and the motion lookahead (temporal_math.h: the text temporal_kernel compiles) --
+static thread_local std::string g_filter_poses_error;
+
+int hrn_filter_poses(int P, const int32_t *cur_start, const int32_t *prev_start, int J, const float *pts, const int32_t *match,
+                     const float *prev_state, const int32_t *prev_age, double dt, double min_cutoff, double beta, double d_cutoff,
+                     float threshold, double lookahead, float *pts_out, float *pred_out, float *state, int32_t *age) {
+    using namespace hrn;
+    g_filter_poses_error.clear();
+    if (const char *fault = temporal_fault(P, cur_start, prev_start, J, pts, match, prev_state, prev_age, dt, min_cutoff, beta, d_cutoff,
+                                           lookahead, pts_out, state, age)) {
+        g_filter_poses_error = fault;
+        return 7;
+    }
+    const TemporalParams prm = temporal_params(dt, min_cutoff, beta, d_cutoff, threshold, lookahead);
+    for (int p = 0; p < P; ++p) {
+        const int prev0 = prev_start[p], m = prev_start[p + 1] - prev0;
+        for (size_t i = (size_t)cur_start[p]; i < (size_t)cur_start[p + 1]; ++i) {
+            const long long before = match ? temporal_previous(match[i], prev0, m) : -1;
+            for (int j = 0; j < J; ++j) {
+                const size_t at = i * J + j;
+                const float v[3] = {pts[at * 3], pts[at * 3 + 1], pts[at * 3 + 2]};
+                const size_t q = before >= 0 ? (size_t)before * J + j : 0;
+                const int32_t before_age = before >= 0 ? prev_age[q] : 0;
+                const TemporalJoint r = temporal_joint(v, before_age > 0, before_age > 0 ? prev_state + q * 6 : nullptr, before_age, prm);
+                pts_out[at * 3] = r.out[0], pts_out[at * 3 + 1] = r.out[1], pts_out[at * 3 + 2] = v[2];
+                if (pred_out) pred_out[at * 3] = r.pred[0], pred_out[at * 3 + 1] = r.pred[1], pred_out[at * 3 + 2] = v[2];
+                for (int k = 0; k < 6; ++k) state[at * 6 + k] = r.state[k];
+                age[at] = r.age;
+            }
+        }
+    }
+    return 0;
+}
+
+const char *hrn_filter_poses_last_error(void) { return g_filter_poses_error.c_str(); }
 
 // the OKS of all n people of ONE problem against its person g, exactly as both entries compute it (a non-finite value as 0.0),
 // for measuring it against the reference's oks_iou; returns 0 or 7

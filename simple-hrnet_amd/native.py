@@ -1127,6 +1127,41 @@ class NativeHRNet:
                      float(similarity_threshold), float(smoothing_alpha), ids.data_ptr(), match.data_ptr(), status.data_ptr())
         return boxes, pts, ids, match, nxt, status
 
+    # -- joints over time: One-Euro smoothing and the prediction of the next frame's joints -----------------------------------------
+    def filter_poses(self, pts, state=None, match=None, counts=None, prev_counts=None, dt: float = 1 / 30, min_cutoff: float = 1.0,
+                     beta: float = 0.007, d_cutoff: float = 1.0, threshold: float = 0.5, lookahead: Optional[float] = None):
+        """``postproc.filter_poses`` on the GPU (``hrn_filter_poses_dev``: one launch, one thread per (person, joint), no host
+        read): the One-Euro filter of every joint and the predicted joints ``raw position + filtered velocity * lookahead``,
+        for one video or the streams of a camera wall (``counts`` / ``prev_counts``: people per stream, on the host).
+
+        ``pts`` (n, J, 3) float32 as ``predict_frame`` / ``track_frame`` / ``associate_people`` return them, ``state`` the pair the
+        previous call returned (None on the first frame), ``match`` (n,) int32 as ``associate_people`` wrote it (None: nobody is
+        known).  Tensors of the right type on the engine's GPU are used where they lie; host arrays are uploaded.  The arguments
+        are left as they are.  Returns ``(pts_out, pred, (values, age))`` on the GPU, bit for bit the host form's; ``pred`` is what
+        ``track_frame`` wants as ``prev_pts``.  The prediction starts from the RAW position on purpose: the filtered position lags on
+        steady motion -- the filter's known trade, tuned by ``beta`` -- while raw + velocity converges to zero error."""
+        from .postproc import filter_arguments
+
+        dev = self.torch_device
+        pts = as_tensor(pts, np.float32)
+        if pts.numel() == 0 and pts.dim() != 3:
+            pts = pts.reshape(0, int(state[0].shape[1]) if state is not None and len(state[0].shape) == 3 else 1, 3)
+        pts = device_tensor(pts, dev, torch.float32)
+        if state is not None:
+            state = device_tensor(state[0], dev, torch.float32), device_tensor(state[1], dev, torch.int32)
+        if match is not None:
+            match = device_tensor(match, dev, torch.int32, (-1,))
+        n, m, joints, cur, prev, numbers = filter_arguments(tuple(pts.shape), None if state is None else (tuple(state[0].shape), tuple(state[1].shape)),
+                                                            None if match is None else int(match.shape[0]), counts, prev_counts, dt, min_cutoff,
+                                                            beta, d_cutoff, threshold, lookahead)
+        pts_out, pred = torch.empty_like(pts), torch.empty_like(pts)
+        values = torch.empty((n, joints, 6), dtype=torch.float32, device=dev)
+        age = torch.empty((n, joints), dtype=torch.int32, device=dev)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()   # noqa: E731 -- (an empty tensor has no address)
+        self._launch("hrn_filter_poses_dev", len(cur) - 1, cur.ctypes.data, prev.ctypes.data, joints, ptr(pts), ptr(match),
+                     ptr(state and state[0]), ptr(state and state[1]), *numbers, ptr(pts_out), ptr(pred), ptr(values), ptr(age))
+        return pts_out, pred, (values, age)
+
     # -- pose NMS: duplicate skeletons removed per image or stream, without leaving the device --------------------------------------
     def _pose_nms_launch(self, engine: bool, kpts, areas, scores, seg: np.ndarray, thresh, in_vis_thre, rescore_thre, soft, sigmas,
                          suppress):

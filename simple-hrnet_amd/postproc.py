@@ -198,6 +198,71 @@ def associate_people(boxes, pts, prev_boxes, prev_pts, prev_ids, next_id, pose_a
     return boxes, pts, ids, match, nxt, status
 
 
+def filter_arguments(pts_shape, state_shapes, match_len, counts, prev_counts, dt, min_cutoff, beta, d_cutoff, threshold, lookahead):
+    """what ``filter_poses`` and ``NativeHRNet.filter_poses`` share, from shapes alone: ``(n, m, joints, cur, prev, numbers)`` --
+    people on either side, J, the two int32 segment tables and the six numbers in the entries' order (``lookahead=None``: ``dt``)"""
+    if len(pts_shape) != 3 or pts_shape[2] != 3:
+        raise ValueError("pts must be (n, J, 3), got %s" % (tuple(pts_shape),))
+    n, m = int(pts_shape[0]), 0
+    if n and pts_shape[1] < 1:
+        raise ValueError("pts holds people without joints: %s" % (tuple(pts_shape),))
+    if state_shapes is not None:
+        values, age = (tuple(s) for s in state_shapes)
+        if len(values) != 3 or values[2] != 6 or age != values[:2]:
+            raise ValueError("state must be ((m, J, 6) values, (m, J) ages), got %s and %s" % (values, age))
+        m = int(values[0])
+        if n and m and values[1] != pts_shape[1]:
+            raise ValueError("the state holds %d joints per person, pts %d" % (values[1], pts_shape[1]))
+    joints = int(pts_shape[1] if n or not m else state_shapes[0][1]) or 1
+    if match_len is not None and match_len != n:
+        raise ValueError("match must hold one value per person: %d for %d" % (match_len, n))
+    cur = _segments(counts, n, "counts")
+    prev = np.zeros(len(cur), np.int32) if prev_counts is None and m == 0 else _segments(prev_counts, m, "prev_counts")
+    if len(cur) != len(prev):
+        raise ValueError("counts and prev_counts name %d and %d streams" % (len(cur) - 1, len(prev) - 1))
+    dt = float(dt)
+    return n, m, joints, cur, prev, (dt, float(min_cutoff), float(beta), float(d_cutoff), float(threshold), dt if lookahead is None else float(lookahead))
+
+
+def filter_poses(pts, state=None, match=None, counts=None, prev_counts=None, dt=1 / 30, min_cutoff=1.0, beta=0.007, d_cutoff=1.0,
+                 threshold=0.5, lookahead=None):
+    """Joints over time in one native call (``hrn_filter_poses``, no GPU): the One-Euro filter (Casiez, Roussel, Vogel, CHI 2012)
+    of every joint and the prediction of the next frame's joints -- the host form of ``NativeHRNet.filter_poses``, equal to it bit
+    for bit (``include/hrnet_mi355.h`` states the arithmetic in full).
+
+    ``pts`` (n, J, 3) float32 ``(y, x, confidence)`` of this frame; ``state``: what the previous call returned, or None on the
+    first frame; ``match`` (n,) int32: who of the previous frame each person is, counted inside its stream, or -1
+    (``associate_people``'s ``match``; None: nobody is known); ``counts`` / ``prev_counts``: people per stream on either side
+    (None: one stream); ``dt``: seconds since the previous frame; ``min_cutoff`` (Hz: less jitter at rest when lower), ``beta``
+    (less lag in motion when higher), ``d_cutoff``: the filter's parameters; joints with ``confidence > threshold`` and finite
+    coordinates are filtered, the others pass through and lose their state; ``lookahead``: seconds ahead of this frame that the
+    prediction looks (None: ``dt``, the next frame).
+
+    Returns ``(pts_out, pred, state)``: the filtered joints, the predicted joints ``raw position + filtered velocity * lookahead``
+    (what ``track_frame`` wants as ``prev_pts``) and the ``(values (n, J, 6) float32, age (n, J) int32)`` pair to pass back in.
+    The prediction starts from the RAW position on purpose: the filtered position lags on steady motion -- the filter's known
+    trade, tuned by ``beta`` -- while raw + velocity converges to zero error.  ``pts`` is left as it is."""
+    pts = np.ascontiguousarray(pts, dtype=np.float32)
+    if pts.size == 0 and pts.ndim != 3:           # (an empty list of skeletons)
+        pts = pts.reshape(0, state[0].shape[1] if state is not None and np.ndim(state[0]) == 3 else 1, 3)
+    if state is not None:
+        state = np.ascontiguousarray(state[0], dtype=np.float32), np.ascontiguousarray(state[1], dtype=np.int32)
+    if match is not None:
+        match = np.ascontiguousarray(match, dtype=np.int32).reshape(-1)
+    n, m, joints, cur, prev, numbers = filter_arguments(pts.shape, None if state is None else (state[0].shape, state[1].shape),
+                                                        None if match is None else len(match), counts, prev_counts, dt, min_cutoff, beta,
+                                                        d_cutoff, threshold, lookahead)
+    pts_out, pred = np.empty_like(pts), np.empty_like(pts)
+    values, age = np.empty((n, joints, 6), np.float32), np.empty((n, joints), np.int32)
+    ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+    lib = _lib.load()
+    rc = lib.hrn_filter_poses(len(cur) - 1, cur.ctypes.data, prev.ctypes.data, joints, ptr(pts), ptr(match), ptr(state and state[0]),
+                              ptr(state and state[1]), *numbers, ptr(pts_out), ptr(pred), ptr(values), ptr(age))
+    if rc:
+        raise ValueError("hrn_filter_poses: " + lib.hrn_filter_poses_last_error().decode())
+    return pts_out, pred, (values, age)
+
+
 POSE_NMS_SOFT, POSE_NMS_SUPPRESS, POSE_NMS_ENGINE = 1, 2, 4      # HRN_POSE_NMS_* of include/hrnet_mi355.h
 
 

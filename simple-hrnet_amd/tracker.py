@@ -2,7 +2,9 @@
 
 ``PersonTracker`` holds the previous frame's boxes, joints and ids and ``next_id``; every ``update`` is one
 ``associate_people`` -- ``NativeHRNet.associate_people`` on the engine's GPU (one launch, no host read: the ids feed
-``draw_poses`` from the device), or ``postproc.associate_people`` on the host when there is no engine."""
+``draw_poses`` from the device), or ``postproc.associate_people`` on the host when there is no engine.  With ``one_euro`` it
+also holds the joints' filter state and follows every association with one ``filter_poses``: smoothed joints for the overlay,
+predicted joints for the next frame's crops."""
 from __future__ import annotations
 
 from typing import Optional
@@ -22,15 +24,33 @@ class PersonTracker:
     matched) are the tracker's state until the next update -- read them, do not write to them.  The FIRST update follows the
     demo: ids ``arange(n)`` and ``next_id = n + 1`` per stream that has somebody (no kernel; a first frame without people leaves
     ``next_id`` at 0, as the demo does).  An update with nobody keeps ``next_id`` and stores empty arrays.  ``status`` holds the
-    last association's status per stream (None before), ``next_id`` the counters; ``reset()`` forgets everything."""
+    last association's status per stream (None before), ``next_id`` the counters; ``reset()`` forgets everything.
 
-    def __init__(self, net=None, pose_alpha: float = 0.2, similarity_threshold: float = 0.4, smoothing_alpha: float = 0.1):
+    ``one_euro``: None, or ``dict(min_cutoff, beta, d_cutoff, threshold, rate=30.0)`` (any subset; the rest are
+    ``filter_poses``' defaults): every update is then followed by ONE ``filter_poses`` call whose state follows the people
+    through that update's ``match`` (no ``match`` on the first update; with nobody present the state is emptied).  ``update``
+    then returns the FILTERED joints, and ``predicted`` holds the joints expected ``lookahead`` seconds later -- for
+    ``track_frame(frame, tracker.predicted)``.  ``dt``: seconds since the previous update (None: ``1 / rate``); ``lookahead``
+    None: ``dt``.  What the tracker keeps for the next association stays the association's own output.  The prediction starts
+    from the raw position; the filtered joints lag on steady motion, the filter's known trade (``beta``).  With ``one_euro=None``
+    no filter call is made and every result is what it is without the option."""
+
+    def __init__(self, net=None, pose_alpha: float = 0.2, similarity_threshold: float = 0.4, smoothing_alpha: float = 0.1,
+                 one_euro: Optional[dict] = None):
         self.net = net
         self.pose_alpha, self.similarity_threshold, self.smoothing_alpha = float(pose_alpha), float(similarity_threshold), float(smoothing_alpha)
+        self.one_euro = None
+        if one_euro is not None:
+            self.one_euro = dict(one_euro)
+            self.rate = float(self.one_euro.pop("rate", 30.0))
+            unknown = set(self.one_euro) - {"min_cutoff", "beta", "d_cutoff", "threshold"}
+            if unknown or not self.rate > 0.0:
+                raise ValueError("one_euro takes min_cutoff, beta, d_cutoff, threshold and a positive rate, got %r" % (one_euro,))
         self.reset()
 
     def reset(self):
         self.prev_boxes = self.prev_pts = self.prev_ids = self.prev_counts = self.next_id = self.status = None
+        self.filter_state = self.predicted = None
 
     def _own(self, boxes, pts):
         """copies of this frame's boxes and joints where the tracker works: (n, 4) int32 and (n, J, 3) float32"""
@@ -57,8 +77,9 @@ class PersonTracker:
 
         return torch.from_numpy(v).to(self.net.torch_device, non_blocking=True)
 
-    def update(self, boxes, pts, counts: Optional[object] = None):
+    def update(self, boxes, pts, counts: Optional[object] = None, dt: Optional[float] = None, lookahead: Optional[float] = None):
         boxes, pts = self._own(boxes, pts)
+        match = None
         n = int(boxes.shape[0])
         if int(pts.shape[0]) != n:
             raise ValueError("%d boxes for %d skeletons" % (n, int(pts.shape[0])))
@@ -74,8 +95,14 @@ class PersonTracker:
             ids = self._upload(np.zeros(0, np.int32))
         else:
             entry = postproc.associate_people if self.net is None else self.net.associate_people
-            boxes, pts, ids, _, self.next_id, self.status = entry(boxes, pts, self.prev_boxes, self.prev_pts, self.prev_ids, self.next_id,
-                                                                  self.pose_alpha, self.similarity_threshold, self.smoothing_alpha,
-                                                                  counts=counts, prev_counts=self.prev_counts)
+            boxes, pts, ids, match, self.next_id, self.status = entry(boxes, pts, self.prev_boxes, self.prev_pts, self.prev_ids, self.next_id,
+                                                                      self.pose_alpha, self.similarity_threshold, self.smoothing_alpha,
+                                                                      counts=counts, prev_counts=self.prev_counts)
+        filtered = pts
+        if self.one_euro is not None:     # the state follows the people through this update's match; prev_pts stays the association's
+            entry = postproc.filter_poses if self.net is None else self.net.filter_poses
+            filtered, self.predicted, self.filter_state = entry(pts, self.filter_state, match, counts=counts,
+                                                                prev_counts=None if self.filter_state is None else self.prev_counts,
+                                                                dt=1.0 / self.rate if dt is None else dt, lookahead=lookahead, **self.one_euro)
         self.prev_boxes, self.prev_pts, self.prev_ids, self.prev_counts = boxes, pts, ids, counts
-        return boxes, pts, ids
+        return boxes, filtered, ids
