@@ -438,6 +438,64 @@ int hrn_pose_nms_dev(hrn_handle h, int P, const int32_t *start_host, int J, int 
 int hrn_pose_nms_oks_row(int n, int J, int flags, const void *kpts, const void *areas, int g, double in_vis_thre, const double *sigmas,
                          double *oks_out /* n */);
 
+/* ---- COCO keypoint AP / AR: OKS matching per image and precision / recall accumulation over the set, host and device ----
+ * The number evaluate_overall_accuracy returns (datasets/COCO.py:574-588): the ten statistics AP, AP .5, AP .75, AP (M), AP (L),
+ * AR, AR .5, AR .75, AR (M), AR (L) that the reference gets from pycocotools' COCOeval (iouType 'keypoints', one category,
+ * maxDets 20).  pycocotools is not available where this library is built and tested, so THE CONTRACT IS THE DEFINITION in
+ * csrc/keypoint_eval_math.h -- one text for both entries, every expression and its rounding -- and parity with pycocotools is NOT
+ * pinned (tests/golden/make_cocoeval_golden.py measures it wherever pycocotools is installed).  In short:
+ *   inputs     P images in ascending image-id order; dt_start / gt_start hold P + 1 non-decreasing int32 on the HOST in both
+ *              entries; dt_kpts (N, J, 3) fp64 (x, y, score), dt_scores (N) fp64; gt_kpts (M, J, 3) fp64 (x, y, v), gt_area (M) fp64,
+ *              gt_bbox (M, 4) fp64 (x, y, w, h), gt_iscrowd (M) int32; sigmas J fp64 or NULL for COCO's 17 (then J must be 17)
+ *   constants  iouThrs = np.linspace(0.5, 0.95, 10), recThrs = np.linspace(0, 1, 101), maxDet = 20, area ranges all [0, 1e10],
+ *              medium [32^2, 96^2], large [96^2, 1e10]
+ *   slots      per image the detections in descending score, STABLE, NaN last (status bit 0); the first 20 are the image's slots,
+ *              the rest take no part; a detection's area is (max x - min x) * (max y - min y) over all J joints
+ *   OKS(d, g)  k1 = g's joints with v > 0.  k1 > 0: dx = x_d - x_g, dy likewise, over g's joints with v > 0.  k1 = 0: the distance
+ *              to the doubled box, dx = max(0, (bx - bw) - x_d) + max(0, x_d - (bx + 2 bw)), dy likewise, over all J joints.
+ *              e_j = (dx dx + dy dy) / (2 sigma_j)^2 / (area_g + spacing(1)) / 2; the mean of exp(-e_j) in numpy's pairwise order
+ *              with assoc_math.h's exp.  A non-finite OKS counts as 0 (status bit 1).
+ *   flags      ignore_g = iscrowd_g or k1 == 0; in range a: ig_g = ignore_g or area_g outside [lo_a, hi_a]; people are visited
+ *              ig = 0 first, then ig = 1, each part in index order
+ *   matching   per (range a, threshold t), slots in order: best = min(t, 1 - 1e-10); walk the people: skip a taken non-crowd; stop
+ *              when a counted match is held and the ignored part begins; skip OKS < best; else take it (equal replaces).  A match
+ *              on an ignored person makes the slot ignored; an unmatched slot with its own area outside the range is ignored.
+ *   curve      per (a, t) all slots of the set in descending score, stably (ties: image order, then slot order; NaN last); tp / fp
+ *              running counts of matched / unmatched slots that are not ignored; npig_a = people with ig = 0; rc = tp / npig_a,
+ *              pr = tp / (fp + tp + spacing(1)), pr made non-increasing from the end; precision(a, t, r) = pr at the first index
+ *              with rc >= recThr_r, or 0; recall(a, t) = the last rc, or 0 without slots; npig_a == 0: both are -1 for the range
+ *   stats      each the mean over the entries > -1 of its slice (sequential fp64 sum in (t, r) order, one division), -1 if none
+ * Outputs, S = the sum over the images of min(detections, 20), slots in image order then slot order:
+ *   stats (10) fp64; precision (3, 10, 101) fp64; recall (3, 10) fp64
+ *   slot_person (S) int32: the detection's index in dt_kpts; slot_score (S) fp64
+ *   dt_match (3, 10, S) int32: the matched person's index in gt_kpts, or -1; dt_ignore (3, 10, S) uint8
+ *   npig (P, 3) int32; status (P) int32
+ * At most HRN_MAX_TRACKED detections and HRN_MAX_TRACKED ground-truth people per image, J in [1, HRN_MAX_JOINTS].  Argument errors
+ * are code 7, judged before anything is launched or written: a bad J, J != 17 without sigmas, null arrays, decreasing segment
+ * tables, more than that on either side; hrn_keypoint_eval_last_error() (per thread) / hrn_last_error(h) names the cause.
+ * hrn_keypoint_eval is the host form: no handle, no GPU.  hrn_keypoint_eval_dev has every array except the two segment tables in
+ * device memory (sigmas included); stream-ordered, no host read, no atomics, every byte has one writer; its results equal the
+ * host form's bit for bit.  Four launches: MATCH, one 256-thread block per image (the order, the <= 20 x <= 256 OKS matrix in
+ * LDS with one thread per pair and serial joints, the people's orders, the 30 matchings on 30 lanes); RANK, every slot's place in
+ * the set-wide order by counting the slots before it (O(S^2) compares through LDS tiles, no sort); CURVE, one block per (a, t):
+ * the totals, then one pass from the end with block scans of the exact integer counts, the envelope and the 101 look-ups;
+ * FINISH, one block: the ten statistics.  The image table goes through one upload; with P == 0 only CURVE and FINISH run.
+ * hrn_keypoint_eval_oks (no GPU): the OKS of all n_d x n_g pairs of one image exactly as both entries compute it (a non-finite
+ * value as 0.0); hrn_keypoint_eval_constants (no GPU): the tables above; both 0, or 7 on null tables or sizes out of range. */
+int hrn_keypoint_eval(int P, const int32_t *dt_start, const int32_t *gt_start, int J, const double *dt_kpts, const double *dt_scores,
+                      const double *gt_kpts, const double *gt_area, const double *gt_bbox, const int32_t *gt_iscrowd,
+                      const double *sigmas, double *stats, double *precision, double *recall, int32_t *slot_person,
+                      double *slot_score, int32_t *dt_match, uint8_t *dt_ignore, int32_t *npig, int32_t *status);
+const char *hrn_keypoint_eval_last_error(void);
+int hrn_keypoint_eval_dev(hrn_handle h, int P, const int32_t *dt_start_host, const int32_t *gt_start_host, int J,
+                          const double *dt_kpts_dev, const double *dt_scores_dev, const double *gt_kpts_dev, const double *gt_area_dev,
+                          const double *gt_bbox_dev, const int32_t *gt_iscrowd_dev, const double *sigmas_dev, double *stats_dev,
+                          double *precision_dev, double *recall_dev, int32_t *slot_person_dev, double *slot_score_dev,
+                          int32_t *dt_match_dev, uint8_t *dt_ignore_dev, int32_t *npig_dev, int32_t *status_dev, void *stream);
+int hrn_keypoint_eval_oks(int n_d, int n_g, int J, const double *dt_kpts, const double *gt_kpts, const double *gt_area,
+                          const double *gt_bbox, const double *sigmas, double *oks_out /* n_d x n_g */);
+int hrn_keypoint_eval_constants(double *iou_thrs /* 10 */, double *rec_thrs /* 101 */, double *area_ranges /* 3 x (lo, hi) */);
+
 /* ---- pose overlays on the GPU: the joints and bones of every person, drawn into frames that stay on the device ----
  * Replaces, for every frame of the two demo programs (scripts/live-demo.py:135-138, scripts/extract-keypoints.py's sibling loop),
  *   for i, pt in enumerate(pts): frame = draw_points_and_skeleton(frame, pt, skeleton, person_index=i, ...)

@@ -76,6 +76,7 @@
     CallScratch assoc_buf;     // hrn_associate_people_dev: the problem table of a call with several problems, then the costs and
                                // similarities the kernel keeps between its phases
     CallScratch nms_table;     // hrn_pose_nms_dev: the problem table of a call with several problems
+    CallScratch eval_buf;      // hrn_keypoint_eval_dev: the image table, then the set-wide order of the slots
     CallScratch trk_table;     // the tracking link: the call's host table (frame sizes per person; frame table and frame index)
     CallScratch lb_table;      // hrn_letterbox_frames(_yuv): the frame records of a call with several frames
     CallScratch det_table;     // hrn_detections_to_frame_dev: the frame records of a call with several frames
@@ -151,7 +152,7 @@
 
     void free_scratch() {
         for (CallScratch *c : {&rs_taps, &pre_tmp, &pre_params, &pre_yuv, &warp_params, &score_joints, &draw_table, &draw_records, &assoc_buf,
-                               &nms_table, &trk_table, &lb_table, &det_table, &rot_table, &rot_people, &tmp_table})
+                               &nms_table, &eval_buf, &trk_table, &lb_table, &det_table, &rot_table, &rot_people, &tmp_table})
             c->release();
         pass.release();
         for (auto &kv : score_tables) (void)hipFree(kv.second);

@@ -20,6 +20,7 @@
 #include "assoc_math.h"
 #include "letterbox_math.h"
 #include "pose_nms_math.h"
+#include "keypoint_eval_math.h"
 #include "kernels.h"
 #include "rotate_math.h"
 #include "temporal_math.h"
@@ -1032,6 +1033,49 @@ int hrn_pose_nms_dev(hrn_handle h, int P, const int32_t *start_host, int J, int 
     a.thresh = thresh, a.in_vis_thre = in_vis_thre, a.rescore_thre = rescore_thre;
     a.keep = keep_dev, a.num = num_dev, a.scores_out = scores_out_dev, a.suppressor = suppressor_dev, a.status = status_dev;
     if (!h->hip_ok(launch_pose_nms(a, s), "pose NMS launch")) return 8;
+    return scope.leave() ? 0 : 6;
+}
+
+// COCO keypoint AP / AR of an evaluation set (keypoint_eval.hip); the arguments are judged first (keypoint_eval_math.h's
+// keypoint_eval_fault, as in the host form: they need no device), then the handle.  The handle keeps the image table and the
+// set-wide order of the slots; the table goes through the pinned ring.
+int hrn_keypoint_eval_dev(hrn_handle h, int P, const int32_t *dt_start_host, const int32_t *gt_start_host, int J,
+                          const double *dt_kpts_dev, const double *dt_scores_dev, const double *gt_kpts_dev, const double *gt_area_dev,
+                          const double *gt_bbox_dev, const int32_t *gt_iscrowd_dev, const double *sigmas_dev, double *stats_dev,
+                          double *precision_dev, double *recall_dev, int32_t *slot_person_dev, double *slot_score_dev,
+                          int32_t *dt_match_dev, uint8_t *dt_ignore_dev, int32_t *npig_dev, int32_t *status_dev, void *stream) {
+    if (!h) return 1;
+    if (const char *fault = keypoint_eval_fault(P, dt_start_host, gt_start_host, J, dt_kpts_dev, dt_scores_dev, gt_kpts_dev, gt_area_dev,
+                                                gt_bbox_dev, gt_iscrowd_dev, sigmas_dev, stats_dev, precision_dev, recall_dev,
+                                                slot_person_dev, slot_score_dev, dt_match_dev, dt_ignore_dev, npig_dev, status_dev)) {
+        h->err = std::string("hrn_keypoint_eval_dev: ") + fault;
+        return 7;
+    }
+    if (h->refuse_plan_only()) return 7;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    int S = 0;
+    for (int p = 0; p < P; ++p) S += std::min(dt_start_host[p + 1] - dt_start_host[p], kEvalMaxDet);
+    const size_t table_bytes = ((size_t)P * sizeof(EvalImage) + 255) / 256 * 256, need = table_bytes + (size_t)S * sizeof(int);
+    if (need && !h->table_reserve(h->eval_buf, need, 4096, "hipMalloc(keypoint evaluation scratch)")) return 6;
+    CallScope scope(h, need ? &h->eval_buf : nullptr, s);
+    if (!scope.entered) return 6;
+    KeypointEvalArgs a{};
+    a.P = P, a.J = J, a.S = S;
+    if (P > 0) {   // the image table through the pinned ring
+        unsigned ring = 0;
+        EvalImage *pin = (EvalImage *)h->pre_stage((size_t)P * sizeof(EvalImage), &ring);
+        if (!pin) return 6;
+        keypoint_eval_images(P, dt_start_host, gt_start_host, pin);
+        if (!h->pre_upload(ring, s, {{h->eval_buf.ptr, pin, (size_t)P * sizeof(EvalImage), "hipMemcpyAsync(keypoint evaluation table)"}})) return 6;
+        a.images = h->eval_buf.as<const EvalImage>();
+        a.set_order = (int *)(h->eval_buf.ptr + table_bytes);
+    }
+    a.dt_kpts = dt_kpts_dev, a.dt_scores = dt_scores_dev, a.gt_kpts = gt_kpts_dev, a.gt_area = gt_area_dev, a.gt_bbox = gt_bbox_dev;
+    a.gt_iscrowd = gt_iscrowd_dev, a.sigmas = sigmas_dev;
+    a.stats = stats_dev, a.precision = precision_dev, a.recall = recall_dev, a.slot_person = slot_person_dev, a.slot_score = slot_score_dev;
+    a.dt_match = dt_match_dev, a.dt_ignore = dt_ignore_dev, a.npig = npig_dev, a.status = status_dev;
+    if (!h->hip_ok(launch_keypoint_eval(a, s), "keypoint evaluation launch")) return 8;
     return scope.leave() ? 0 : 6;
 }
 

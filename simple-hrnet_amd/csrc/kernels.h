@@ -452,6 +452,25 @@ struct PoseNmsArgs {
 };
 hipError_t launch_pose_nms(const PoseNmsArgs &a, hipStream_t s);   // pose_nms_kernel: P blocks of 256 threads
 
+// COCO keypoint AP / AR (keypoint_eval.hip; include/hrnet_mi355.h: hrn_keypoint_eval_dev): matching per image, the set-wide order,
+// the precision / recall curves and the statistics in four launches (the arithmetic: keypoint_eval_math.h).
+struct EvalImage;                  // keypoint_eval_math.h: one image's detections, people and slots
+struct KeypointEvalArgs {
+    int P, J, S;                   // images, joints, slots of the set
+    const EvalImage *images;       // P entries, device
+    const double *dt_kpts, *dt_scores, *gt_kpts, *gt_area, *gt_bbox;
+    const int *gt_iscrowd;
+    const double *sigmas;          // J, or nullptr: COCO's 17
+    int *set_order;                // scratch, S: the slots in set order
+    double *stats, *precision, *recall;   // out: 10, (3, 10, 101), (3, 10)
+    int *slot_person;              // out: S
+    double *slot_score;            // out: S
+    int *dt_match;                 // out: (3, 10, S)
+    unsigned char *dt_ignore;      // out: (3, 10, S)
+    int *npig, *status;            // out: (P, 3), P
+};
+hipError_t launch_keypoint_eval(const KeypointEvalArgs &a, hipStream_t s);   // match (P blocks), rank (S / 256), curve (30), finish (1)
+
 // The detector link (letterbox.hip; include/hrnet_mi355.h: hrn_letterbox_frames, hrn_detections_to_frame_dev).
 enum { LB_MODE_LINEAR = 0, LB_MODE_COPY = 1, LB_MODE_AREA = 2 };   // how an interior pixel is formed (cv2.resize's three paths)
 struct LetterboxFrame {            // one frame of the call, prepared on the host (letterbox_math.h's geometry)

@@ -23,6 +23,7 @@
 #include "assoc_math.h"
 #include "letterbox_math.h"
 #include "pose_nms_math.h"
+#include "keypoint_eval_math.h"
 #include "rotate_math.h"
 #include "temporal_math.h"
 
@@ -423,6 +424,139 @@ int hrn_pose_nms(int P, const int32_t *start, int J, int flags, void *kpts, void
 }
 
 const char *hrn_pose_nms_last_error(void) { return g_pose_nms_error.c_str(); }
+
+// ---- COCO keypoint AP / AR on the host (keypoint_eval_math.h: the text the kernels of keypoint_eval.hip compile) ------------------
+static thread_local std::string g_keypoint_eval_error;
+
+int hrn_keypoint_eval(int P, const int32_t *dt_start, const int32_t *gt_start, int J, const double *dt_kpts, const double *dt_scores,
+                      const double *gt_kpts, const double *gt_area, const double *gt_bbox, const int32_t *gt_iscrowd,
+                      const double *sigmas, double *stats, double *precision, double *recall, int32_t *slot_person,
+                      double *slot_score, int32_t *dt_match, uint8_t *dt_ignore, int32_t *npig, int32_t *status) {
+    using namespace hrn;
+    g_keypoint_eval_error.clear();
+    if (const char *fault = keypoint_eval_fault(P, dt_start, gt_start, J, dt_kpts, dt_scores, gt_kpts, gt_area, gt_bbox, gt_iscrowd, sigmas,
+                                                stats, precision, recall, slot_person, slot_score, dt_match, dt_ignore, npig, status)) {
+        g_keypoint_eval_error = fault;
+        return 7;
+    }
+    std::vector<EvalImage> images((size_t)P);
+    const size_t S = (size_t)keypoint_eval_images(P, dt_start, gt_start, images.data());
+    std::vector<double> vars(J), oks((size_t)kEvalMaxDet * kMaxTracked), dt_area(kEvalMaxDet);
+    std::vector<int> k1(kMaxTracked), slot(kEvalMaxDet);
+    std::vector<unsigned char> ig((size_t)kEvalAreas * kMaxTracked), order((size_t)kEvalAreas * kMaxTracked), crowd(kMaxTracked),
+        taken(kMaxTracked);
+    for (int j = 0; j < J; ++j) vars[j] = pose_nms_var(sigmas, j);
+
+    // ---- per image: the slots, the OKS matrix, the 30 matchings ----
+    for (int p = 0; p < P; ++p) {
+        const EvalImage &im = images[p];
+        int st = 0, bad = 0;
+        const double *sc = dt_scores + im.dt_first;
+        for (int d = 0; d < im.dt_n; ++d) {
+            if (sc[d] != sc[d]) st |= 1;
+            const int r = pose_nms_rank(sc, im.dt_n, d);
+            if (r < im.slots) slot[r] = d;
+        }
+        for (int g = 0; g < im.gt_n; ++g) {
+            const size_t at = (size_t)im.gt_first + g;
+            k1[g] = eval_k1(gt_kpts + at * J * 3, J);
+            crowd[g] = gt_iscrowd[at] != 0;
+            for (int a = 0; a < kEvalAreas; ++a) ig[(size_t)a * kMaxTracked + g] = eval_gt_ig(crowd[g] || k1[g] == 0, gt_area[at], a);
+        }
+        for (int a = 0; a < kEvalAreas; ++a)
+            npig[(size_t)p * kEvalAreas + a] = eval_gt_order(&ig[(size_t)a * kMaxTracked], im.gt_n, &order[(size_t)a * kMaxTracked]);
+        for (int s = 0; s < im.slots; ++s) {
+            const size_t d = (size_t)im.dt_first + slot[s];
+            slot_person[im.slot_first + s] = (int32_t)d, slot_score[im.slot_first + s] = dt_scores[d];
+            dt_area[s] = eval_dt_area(dt_kpts + d * J * 3, J);
+            for (int g = 0; g < im.gt_n; ++g) {
+                const size_t at = (size_t)im.gt_first + g;
+                oks[(size_t)s * im.gt_n + g] = eval_oks(dt_kpts + d * J * 3, gt_kpts + at * J * 3, J, k1[g], gt_bbox + at * 4, gt_area[at],
+                                                        vars.data(), &bad);
+            }
+        }
+        for (int a = 0; a < kEvalAreas; ++a)
+            for (int t = 0; t < kEvalThrs; ++t) {
+                const size_t out = (size_t)(a * kEvalThrs + t) * S + im.slot_first;
+                eval_match(oks.data(), im.slots, im.gt_n, &order[(size_t)a * kMaxTracked], &ig[(size_t)a * kMaxTracked], crowd.data(),
+                           dt_area.data(), a, kEvalIouThrs[t], im.gt_first, taken.data(), dt_match + out, dt_ignore + out);
+            }
+        status[p] = st | (bad ? 2 : 0);
+    }
+
+    // ---- over the set: the order, then per (a, t) the counts from the front and the envelope and look-ups from the end ----
+    std::vector<int32_t> set_order(S);
+    std::iota(set_order.begin(), set_order.end(), 0);
+    std::stable_sort(set_order.begin(), set_order.end(), [&](int32_t x, int32_t y) {
+        const double sx = slot_score[x], sy = slot_score[y];
+        return (sx == sx && sy != sy) || sx > sy;
+    });
+    std::vector<int> tps(S);
+    for (int a = 0; a < kEvalAreas; ++a) {
+        long long total = 0;
+        for (int p = 0; p < P; ++p) total += npig[(size_t)p * kEvalAreas + a];
+        const int npig_a = (int)total;
+        for (int t = 0; t < kEvalThrs; ++t) {
+            double *prec = precision + (size_t)(a * kEvalThrs + t) * kEvalRecs;
+            if (npig_a == 0) {
+                for (int r = 0; r < kEvalRecs; ++r) prec[r] = -1.0;
+                recall[a * kEvalThrs + t] = -1.0;
+                continue;
+            }
+            const int32_t *match = dt_match + (size_t)(a * kEvalThrs + t) * S;
+            const uint8_t *ignore = dt_ignore + (size_t)(a * kEvalThrs + t) * S;
+            int tp = 0, fp = 0;
+            for (size_t i = 0; i < S; ++i) {
+                const int32_t s = set_order[i];
+                if (!ignore[s]) (match[s] >= 0 ? tp : fp) += 1;
+                tps[i] = tp;
+            }
+            recall[a * kEvalThrs + t] = S ? eval_recall(tp, npig_a) : 0.0;
+            for (int r = 0; r < kEvalRecs; ++r) prec[r] = 0.0;
+            double env = -1.0;
+            for (size_t i = S; i-- > 0;) {
+                const double pr = eval_precision(tp, fp);
+                env = pr > env ? pr : env;
+                const int before = i ? tps[i - 1] : 0;
+                if (i == 0 || before != tp)
+                    for (int r = 0; r < kEvalRecs; ++r)
+                        if (eval_owns(tp, before, i == 0, npig_a, r)) prec[r] = env;
+                const int32_t s = set_order[i];
+                if (!ignore[s]) (match[s] >= 0 ? tp : fp) -= 1;
+            }
+        }
+    }
+    for (int k = 0; k < 10; ++k) stats[k] = eval_stat(precision, recall, k);
+    return 0;
+}
+
+const char *hrn_keypoint_eval_last_error(void) { return g_keypoint_eval_error.c_str(); }
+
+int hrn_keypoint_eval_oks(int n_d, int n_g, int J, const double *dt_kpts, const double *gt_kpts, const double *gt_area,
+                          const double *gt_bbox, const double *sigmas, double *oks_out) {
+    using namespace hrn;
+    if (n_d < 0 || n_g < 0 || n_d > kMaxTracked || n_g > kMaxTracked || J < 1 || J > kAssocMaxJoints || (!sigmas && J != 17)) return 7;
+    if (n_d && n_g && (!dt_kpts || !gt_kpts || !gt_area || !gt_bbox || !oks_out)) return 7;
+    std::vector<double> vars(J);
+    for (int j = 0; j < J; ++j) vars[j] = pose_nms_var(sigmas, j);
+    int bad = 0;
+    for (int g = 0; g < n_g; ++g) {
+        const int k1 = eval_k1(gt_kpts + (size_t)g * J * 3, J);
+        for (int d = 0; d < n_d; ++d)
+            oks_out[(size_t)d * n_g + g] =
+                eval_oks(dt_kpts + (size_t)d * J * 3, gt_kpts + (size_t)g * J * 3, J, k1, gt_bbox + (size_t)g * 4, gt_area[g], vars.data(), &bad);
+    }
+    return 0;
+}
+
+int hrn_keypoint_eval_constants(double *iou_thrs, double *rec_thrs, double *area_ranges) {
+    using namespace hrn;
+    if (!iou_thrs || !rec_thrs || !area_ranges) return 7;
+    for (int t = 0; t < kEvalThrs; ++t) iou_thrs[t] = kEvalIouThrs[t];
+    for (int r = 0; r < kEvalRecs; ++r) rec_thrs[r] = kEvalRecThrs[r];
+    for (int a = 0; a < kEvalAreas; ++a) area_ranges[2 * a] = kEvalAreaLo[a], area_ranges[2 * a + 1] = kEvalAreaHi[a];
+    return 0;
+}
 
 // ---- the detector link on the host: letterbox geometry and the detector's boxes back in frame coordinates (letterbox_math.h) ----
 static thread_local std::string g_letterbox_error;

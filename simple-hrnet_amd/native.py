@@ -1247,30 +1247,72 @@ class NativeHRNet:
         the indices into the caller's arrays that survive, best first, images in order of first appearance -- the structure the
         reference builds as ``oks_nmsed_kpts``.  Where nothing is kept everybody is returned (``COCO.py:379-380``).  At most 256
         people per image."""
-        preds = np.asarray(preds.detach().cpu().numpy() if hasattr(preds, "detach") else preds, dtype=np.float64)
-        maxvals = np.asarray(maxvals.detach().cpu().numpy() if hasattr(maxvals, "detach") else maxvals, dtype=np.float64)
-        total = len(preds)
-        if preds.ndim != 3 or preds.shape[2] != 2 or maxvals.size != total * preds.shape[1]:
-            raise ValueError("preds must be (N, J, 2) and maxvals (N, J) or (N, J, 1), got %s, %s" % (preds.shape, maxvals.shape))
-        image_index = np.asarray(image_index).reshape(-1)
-        areas = np.asarray(areas, dtype=np.float64).reshape(-1)
-        box_scores = np.asarray(box_scores, dtype=np.float64).reshape(-1)
-        if not (len(image_index) == len(areas) == len(box_scores) == total):
-            raise ValueError("areas, box_scores and image_index must hold one value per person")
-        order = np.argsort(image_index, kind="stable")
-        images, counts = np.unique(image_index, return_counts=True)
-        kpts = np.ascontiguousarray(np.concatenate([preds, maxvals.reshape(total, -1, 1)], axis=2)[order])
-        res = self._pose_nms_coco(kpts, np.ascontiguousarray(areas[order]), np.ascontiguousarray(box_scores[order]), counts, oks_thre,
-                                  None, in_vis_thre, soft, sigmas)
-        scores = np.empty(total, np.float64)
-        scores[order] = res["scores"]
-        by_image, first = {}, 0
-        for image, count, num in zip(images.tolist(), counts.tolist(), res["num"].tolist()):
-            members = order[first:first + count]
-            by_image[image] = members[res["keep"][first:first + num]] if num else members
-            first += count
-        seen = dict.fromkeys(image_index.tolist())
-        return scores, {image: by_image[image] for image in seen}
+        from .postproc import nms_eval
+
+        return nms_eval(preds, maxvals, areas, box_scores, image_index, oks_thre, in_vis_thre, soft, sigmas, solve=self._pose_nms_coco)
+
+    # -- COCO keypoint AP / AR: the number an evaluation reports, without leaving the device ------------------------------------------
+    def keypoint_eval(self, dt_kpts, dt_scores, dt_image, gt_kpts, gt_area, gt_bbox, gt_iscrowd, gt_image, sigmas=None):
+        """``postproc.keypoint_eval`` on the GPU (``hrn_keypoint_eval_dev``: four stream-ordered launches, no host read, no
+        atomics): OKS matching of the detections to the ground truth per image, precision / recall over the set and the ten AP /
+        AR statistics, as DEFINED in ``csrc/keypoint_eval_math.h`` (what ``COCOeval(gt, dt, 'keypoints')`` does with one category
+        and ``maxDets = 20``; parity with pycocotools is not pinned).
+
+        Arguments as ``postproc.keypoint_eval``; ``dt_image`` / ``gt_image`` are read on the host (both sides are grouped by image
+        id there: a stable sort, ids ascending, the union of both sides' ids), everything else is a float64 / int32 tensor on the
+        engine's GPU -- used where it lies when the side already is in image order, gathered on the device otherwise -- or a host
+        array, which is uploaded.  Returns the dict of ``postproc.keypoint_eval`` as device tensors, bit for bit the host form's,
+        plus ``images`` (P,) int64 on the host.  At most 256 detections and 256 people per image."""
+        from .postproc import EVAL_AREAS, EVAL_RECS, EVAL_THRS, keypoint_eval_groups, keypoint_eval_joints
+
+        dev = self.torch_device
+        images, dt_order, gt_order, dt_start, gt_start, slots = keypoint_eval_groups(dt_image, gt_image)
+        total, people, problems = int(dt_start[-1]), int(gt_start[-1]), len(images)
+        joints = keypoint_eval_joints(tuple(dt_kpts.shape) if hasattr(dt_kpts, "shape") else np.shape(dt_kpts),
+                                      tuple(gt_kpts.shape) if hasattr(gt_kpts, "shape") else np.shape(gt_kpts), sigmas)
+        sg = None
+        if sigmas is not None:
+            sg = torch.as_tensor(np.ascontiguousarray(sigmas, dtype=np.float64).reshape(-1))
+            if sg.numel() != joints:
+                raise ValueError("sigmas must have one value per joint")
+            sg = sg.to(dev, non_blocking=True)
+        orders = [None if o is None else torch.from_numpy(o).to(dev, non_blocking=True) for o in (dt_order, gt_order)]
+
+        def side(x, dtype, shape, order):
+            x = device_tensor(x, dev, dtype, shape)
+            return x if order is None else x[order.long()].contiguous()
+
+        dk, ds = side(dt_kpts, torch.float64, (total, joints, 3), orders[0]), side(dt_scores, torch.float64, (total,), orders[0])
+        gk, ga = side(gt_kpts, torch.float64, (people, joints, 3), orders[1]), side(gt_area, torch.float64, (people,), orders[1])
+        gb, gc = side(gt_bbox, torch.float64, (people, 4), orders[1]), side(gt_iscrowd, torch.int32, (people,), orders[1])
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)   # noqa: E731
+        out = dict(stats=new((10,), torch.float64), precision=new((EVAL_AREAS, EVAL_THRS, EVAL_RECS), torch.float64),
+                   recall=new((EVAL_AREAS, EVAL_THRS), torch.float64), slot_person=new((slots,), torch.int32),
+                   slot_score=new((slots,), torch.float64), dt_match=new((EVAL_AREAS, EVAL_THRS, slots), torch.int32),
+                   dt_ignore=new((EVAL_AREAS, EVAL_THRS, slots), torch.uint8), npig=new((problems, EVAL_AREAS), torch.int32),
+                   status=new((problems,), torch.int32))
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()   # noqa: E731 -- (an empty tensor has no address)
+        self._launch("hrn_keypoint_eval_dev", problems, dt_start.ctypes.data, gt_start.ctypes.data, joints, ptr(dk), ptr(ds), ptr(gk),
+                     ptr(ga), ptr(gb), ptr(gc), ptr(sg), *[ptr(v) for v in out.values()])
+        if orders[0] is not None:
+            out["slot_person"] = orders[0][out["slot_person"].long()]
+        if orders[1] is not None:
+            m = out["dt_match"]
+            out["dt_match"] = torch.where(m >= 0, orders[1][m.clamp(min=0).long()], torch.full_like(m, -1))
+        out["images"] = images
+        return out
+
+    def evaluate_overall_accuracy(self, preds, maxvals, areas, box_scores, image_index, gt_kpts, gt_area, gt_bbox, gt_iscrowd, gt_image,
+                                  oks_thre: float = 0.9, in_vis_thre: float = 0.2, soft: bool = False, sigmas=None):
+        """``evaluate_overall_accuracy`` of the reference's COCO dataset after the last batch (``datasets/COCO.py:353-388``) from
+        arrays: ``nms_eval`` (rescoring and OKS NMS per image), the float32 rounding of the result file
+        (``COCO.py:551-564``), then ``keypoint_eval`` against the ground truth -- both on the GPU.  ``preds`` .. ``image_index`` as
+        ``nms_eval`` takes them, ``gt_*`` as ``keypoint_eval``.  Returns the reference's value: ``(OrderedDict of 'AP', 'Ap .5',
+        'AP .75', 'AP (M)', 'AP (L)', 'AR', 'AR .5', 'AR .75', 'AR (M)', 'AR (L)', AP)``."""
+        from .postproc import evaluate_overall_accuracy
+
+        return evaluate_overall_accuracy(preds, maxvals, areas, box_scores, image_index, gt_kpts, gt_area, gt_bbox, gt_iscrowd, gt_image,
+                                         oks_thre, in_vis_thre, soft, sigmas, nms=self.nms_eval, evaluate=self.keypoint_eval)
 
     # -- clip mode: the people of many frames in one pre-path launch and one pass (throughput, not latency) ------------------
     def _device_frames(self, frames, one: bool = False) -> Frames:

@@ -350,6 +350,176 @@ def pose_nms_oks_row(kpts, areas, g: int, in_vis_thre=None, sigmas=None) -> np.n
     return out
 
 
+def _host(x, dtype) -> np.ndarray:
+    return np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=dtype)
+
+
+def nms_eval(preds, maxvals, areas, box_scores, image_index, oks_thre=0.9, in_vis_thre=0.2, soft=False, sigmas=None, solve=None):
+    """The rescoring and OKS NMS of ``evaluate_overall_accuracy`` (``datasets/COCO.py:353-382``) for a whole evaluation set, one
+    problem per image: the host form of ``NativeHRNet.nms_eval`` (same arguments and result; it passes its device call as
+    ``solve``, which takes ``pose_nms``'s COCO-layout arguments in order and returns its dict)."""
+    if solve is None:
+        def solve(kpts, areas, scores, counts, thresh, vis, rescore, soft, sigmas):
+            return pose_nms(kpts=kpts, areas=areas, scores=scores, counts=counts, thresh=thresh, in_vis_thre=vis, rescore_thre=rescore,
+                            soft=soft, sigmas=sigmas)
+    preds, maxvals = _host(preds, np.float64), _host(maxvals, np.float64)
+    total = len(preds)
+    if preds.ndim != 3 or preds.shape[2] != 2 or maxvals.size != total * preds.shape[1]:
+        raise ValueError("preds must be (N, J, 2) and maxvals (N, J) or (N, J, 1), got %s, %s" % (preds.shape, maxvals.shape))
+    image_index = np.asarray(image_index).reshape(-1)
+    areas = np.asarray(areas, dtype=np.float64).reshape(-1)
+    box_scores = np.asarray(box_scores, dtype=np.float64).reshape(-1)
+    if not (len(image_index) == len(areas) == len(box_scores) == total):
+        raise ValueError("areas, box_scores and image_index must hold one value per person")
+    order = np.argsort(image_index, kind="stable")
+    images, counts = np.unique(image_index, return_counts=True)
+    kpts = np.ascontiguousarray(np.concatenate([preds, maxvals.reshape(total, -1, 1)], axis=2)[order])
+    res = solve(kpts, np.ascontiguousarray(areas[order]), np.ascontiguousarray(box_scores[order]), counts, oks_thre, None, in_vis_thre,
+                soft, sigmas)
+    scores = np.empty(total, np.float64)
+    scores[order] = res["scores"]
+    by_image, first = {}, 0
+    for image, count, num in zip(images.tolist(), counts.tolist(), res["num"].tolist()):
+        members = order[first:first + count]
+        by_image[image] = members[res["keep"][first:first + num]] if num else members
+        first += count
+    seen = dict.fromkeys(image_index.tolist())
+    return scores, {image: by_image[image] for image in seen}
+
+
+# -- COCO keypoint AP / AR (csrc/keypoint_eval_math.h) ---------------------------------------------------------------------------------
+EVAL_MAX_DET, EVAL_AREAS, EVAL_THRS, EVAL_RECS = 20, 3, 10, 101
+# the ten statistics as datasets/COCO.py:582 spells them
+EVAL_STAT_NAMES = ("AP", "Ap .5", "AP .75", "AP (M)", "AP (L)", "AR", "AR .5", "AR .75", "AR (M)", "AR (L)")
+
+
+def keypoint_eval_constants():
+    """``(iouThrs (10,), recThrs (101,), area ranges (3, 2))`` as the library holds them (``hrn_keypoint_eval_constants``)"""
+    iou, rec, areas = np.zeros(EVAL_THRS), np.zeros(EVAL_RECS), np.zeros((EVAL_AREAS, 2))
+    if _lib.load().hrn_keypoint_eval_constants(iou.ctypes.data, rec.ctypes.data, areas.ctypes.data):
+        raise ValueError("hrn_keypoint_eval_constants: bad arguments")
+    return iou, rec, areas
+
+
+def keypoint_eval_groups(dt_image, gt_image):
+    """Both sides of an evaluation grouped by image id on the host: ``(images, dt_order, gt_order, dt_start, gt_start, slots)``.
+    ``images``: the union of the ids of both sides, ascending; ``*_order``: a stable sort of each side by id (None where the side
+    already is in that order); ``*_start`` (P + 1,) int32: where each image's members start in the sorted side; ``slots``: the sum
+    over the images of min(detections, 20)."""
+    dt_image, gt_image = np.asarray(dt_image, dtype=np.int64).reshape(-1), np.asarray(gt_image, dtype=np.int64).reshape(-1)
+    images = np.union1d(dt_image, gt_image)
+    sides = []
+    for ids in (dt_image, gt_image):
+        order = np.argsort(ids, kind="stable")
+        start = np.append(np.searchsorted(ids[order], images, side="left"), len(ids)).astype(np.int32)
+        sides.append((None if np.array_equal(order, np.arange(len(ids))) else order.astype(np.int32), start))
+    slots = int(np.minimum(np.diff(sides[0][1]), EVAL_MAX_DET).sum())
+    return images, sides[0][0], sides[1][0], sides[0][1], sides[1][1], slots
+
+
+def keypoint_eval_joints(dt_shape, gt_shape, sigmas) -> int:
+    """J of an evaluation call from the (n, J, 3) shapes of its keypoints (an empty side has no say), else from ``sigmas``, else 17"""
+    for shape in (tuple(dt_shape), tuple(gt_shape)):
+        if len(shape) == 3 and shape[0] > 0:
+            if shape[2] != 3:
+                raise ValueError("keypoints must be (n, J, 3), got %s" % (shape,))
+            return int(shape[1])
+    return 17 if sigmas is None else len(sigmas)
+
+
+def keypoint_eval(dt_kpts, dt_scores, dt_image, gt_kpts, gt_area, gt_bbox, gt_iscrowd, gt_image, sigmas=None):
+    """COCO keypoint AP / AR of an evaluation set in one native call (``hrn_keypoint_eval``, no GPU): the host form of
+    ``NativeHRNet.keypoint_eval``, equal to it bit for bit.  What pycocotools' ``COCOeval(gt, dt, 'keypoints')`` computes for one
+    category with ``maxDets = 20``, as DEFINED in ``csrc/keypoint_eval_math.h`` (parity with pycocotools is not pinned).
+
+    ``dt_kpts`` (N, J, 3) ``(x, y, score)``, ``dt_scores`` (N,), ``dt_image`` (N,) integer image ids; ``gt_kpts`` (M, J, 3)
+    ``(x, y, v)``, ``gt_area`` (M,), ``gt_bbox`` (M, 4) ``(x, y, w, h)``, ``gt_iscrowd`` (M,), ``gt_image`` (M,).  Any order: both
+    sides are grouped by image id (a stable sort; the images are the union of both sides' ids, ascending).  ``sigmas``: J values,
+    or None for COCO's 17.  At most 256 detections and 256 people per image.
+
+    Returns a dict: ``stats`` (10,) in ``EVAL_STAT_NAMES``' order; ``precision`` (3, 10, 101) and ``recall`` (3, 10) over (area
+    range all / medium / large, OKS threshold, recall threshold), -1 where a range has no counted ground truth; per slot (each
+    image's up to 20 best detections, images in order) ``slot_person`` (S,) int32 -- the index into the caller's detections --
+    ``slot_score`` (S,), ``dt_match`` (3, 10, S) int32 -- the index into the caller's ground truth or -1 -- and ``dt_ignore``
+    (3, 10, S) uint8; ``npig`` (P, 3) int32; ``status`` (P,) int32 -- bit 0: a NaN score was ordered last, bit 1: a non-finite OKS
+    counted as 0; ``images`` (P,) int64."""
+    images, dt_order, gt_order, dt_start, gt_start, slots = keypoint_eval_groups(dt_image, gt_image)
+    total, people, problems = int(dt_start[-1]), int(gt_start[-1]), len(images)
+    joints = keypoint_eval_joints(np.shape(dt_kpts), np.shape(gt_kpts), sigmas)
+    sg = None if sigmas is None else np.ascontiguousarray(sigmas, dtype=np.float64).reshape(-1)
+    if sg is not None and len(sg) != joints:
+        raise ValueError("sigmas must have one value per joint")
+
+    def side(x, dtype, shape, order):
+        x = np.asarray(x, dtype=dtype).reshape(shape)
+        return np.ascontiguousarray(x if order is None else x[order])
+
+    dk, ds = side(dt_kpts, np.float64, (total, joints, 3), dt_order), side(dt_scores, np.float64, (total,), dt_order)
+    gk, ga = side(gt_kpts, np.float64, (people, joints, 3), gt_order), side(gt_area, np.float64, (people,), gt_order)
+    gb, gc = side(gt_bbox, np.float64, (people, 4), gt_order), side(gt_iscrowd, np.int32, (people,), gt_order)
+    out = dict(stats=np.zeros(10), precision=np.zeros((EVAL_AREAS, EVAL_THRS, EVAL_RECS)), recall=np.zeros((EVAL_AREAS, EVAL_THRS)),
+               slot_person=np.zeros(slots, np.int32), slot_score=np.zeros(slots), dt_match=np.zeros((EVAL_AREAS, EVAL_THRS, slots), np.int32),
+               dt_ignore=np.zeros((EVAL_AREAS, EVAL_THRS, slots), np.uint8), npig=np.zeros((problems, EVAL_AREAS), np.int32),
+               status=np.zeros(problems, np.int32))
+    lib = _lib.load()
+    rc = lib.hrn_keypoint_eval(problems, dt_start.ctypes.data, gt_start.ctypes.data, joints, dk.ctypes.data, ds.ctypes.data, gk.ctypes.data,
+                               ga.ctypes.data, gb.ctypes.data, gc.ctypes.data, None if sg is None else sg.ctypes.data,
+                               *[out[k].ctypes.data for k in ("stats", "precision", "recall", "slot_person", "slot_score", "dt_match",
+                                                              "dt_ignore", "npig", "status")])
+    if rc:
+        raise ValueError("hrn_keypoint_eval: " + lib.hrn_keypoint_eval_last_error().decode())
+    if dt_order is not None:
+        out["slot_person"] = dt_order[out["slot_person"]]
+    if gt_order is not None:
+        out["dt_match"] = np.where(out["dt_match"] >= 0, gt_order[np.maximum(out["dt_match"], 0)], -1).astype(np.int32)
+    out["images"] = images
+    return out
+
+
+def keypoint_eval_oks(dt_kpts, gt_kpts, gt_area, gt_bbox, sigmas=None) -> np.ndarray:
+    """The OKS of every (detection, person) pair of one image, (n_d, n_g), as ``keypoint_eval`` computes it
+    (``hrn_keypoint_eval_oks``, no GPU): what COCOeval's ``computeOks`` returns, in keypoint_eval_math.h's arithmetic."""
+    dk, gk = np.ascontiguousarray(dt_kpts, dtype=np.float64), np.ascontiguousarray(gt_kpts, dtype=np.float64)
+    ga, gb = np.ascontiguousarray(gt_area, dtype=np.float64).reshape(-1), np.ascontiguousarray(gt_bbox, dtype=np.float64).reshape(-1, 4)
+    if dk.ndim != 3 or gk.ndim != 3 or dk.shape[1:] != gk.shape[1:] or dk.shape[2] != 3 or len(ga) != len(gk) or len(gb) != len(gk):
+        raise ValueError("keypoints must be (n_d, J, 3) and (n_g, J, 3) beside n_g areas and boxes")
+    sg = None if sigmas is None else np.ascontiguousarray(sigmas, dtype=np.float64).reshape(-1)
+    if sg is not None and len(sg) != dk.shape[1]:
+        raise ValueError("sigmas must have one value per joint")
+    out = np.zeros((len(dk), len(gk)), np.float64)
+    if _lib.load().hrn_keypoint_eval_oks(len(dk), len(gk), int(dk.shape[1]), dk.ctypes.data, gk.ctypes.data, ga.ctypes.data, gb.ctypes.data,
+                                         None if sg is None else sg.ctypes.data, out.ctypes.data):
+        raise ValueError("hrn_keypoint_eval_oks: bad arguments")
+    return out
+
+
+def eval_detections(preds, maxvals, scores, kept):
+    """What ``_coco_keypoint_results_one_category_kernel`` writes to the result file (``datasets/COCO.py:551-564``) for the people
+    ``nms_eval`` kept: ``(dt_kpts (n, J, 3), dt_scores (n,), dt_image (n,))``, keypoints and scores rounded through float32, the
+    people of each image best first."""
+    preds, maxvals = _host(preds, np.float64), _host(maxvals, np.float64)
+    index = np.concatenate([np.asarray(v, dtype=np.int64) for v in kept.values()]) if kept else np.zeros(0, np.int64)
+    image = np.concatenate([np.full(len(v), k, np.int64) for k, v in kept.items()]) if kept else np.zeros(0, np.int64)
+    kpts = np.concatenate([preds, maxvals.reshape(len(preds), -1, 1)], axis=2)[index]
+    return kpts.astype(np.float32).astype(np.float64), np.asarray(scores)[index].astype(np.float32).astype(np.float64), image
+
+
+def evaluate_overall_accuracy(preds, maxvals, areas, box_scores, image_index, gt_kpts, gt_area, gt_bbox, gt_iscrowd, gt_image,
+                              oks_thre=0.9, in_vis_thre=0.2, soft=False, sigmas=None, nms=None, evaluate=None):
+    """``evaluate_overall_accuracy`` of the reference's COCO dataset (``datasets/COCO.py:353-388``) from arrays: rescoring and OKS
+    NMS (``nms_eval``), the float32 rounding of the result file (``eval_detections``), then the keypoint evaluation
+    (``keypoint_eval``).  Returns ``(OrderedDict of the ten statistics by EVAL_STAT_NAMES, AP)``.  The host form of
+    ``NativeHRNet.evaluate_overall_accuracy``, which passes its device calls as ``nms`` / ``evaluate``."""
+    from collections import OrderedDict
+
+    scores, kept = (nms or nms_eval)(preds, maxvals, areas, box_scores, image_index, oks_thre, in_vis_thre, soft, sigmas)
+    dt_kpts, dt_scores, dt_image = eval_detections(preds, maxvals, scores, kept)
+    out = (evaluate or keypoint_eval)(dt_kpts, dt_scores, dt_image, gt_kpts, gt_area, gt_bbox, gt_iscrowd, gt_image, sigmas)
+    stats = _host(out["stats"], np.float64)
+    name_value = OrderedDict((name, float(v)) for name, v in zip(EVAL_STAT_NAMES, stats))
+    return name_value, name_value["AP"]
+
+
 def inverse_affine(center, scale, pixel_std, output_size) -> np.ndarray:
     """The 2x3 matrix ``get_affine_transform(center, scale, pixel_std, 0, output_size, inv=1)`` returns
     (``misc/utils.py:44-76``): heat-map coordinates back to image coordinates for an unrotated crop.  The reference builds
