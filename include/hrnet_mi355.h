@@ -567,7 +567,7 @@ int hrn_draw_poses_ids_dev(hrn_handle h, const hrn_canvas *canvases_host, int nf
 int hrn_yuv_from_bgr(int matrix, int range, const uint8_t *bgr /* (n,3) */, int n, uint8_t *yuv_out /* (n,3) */);
 
 /* ---- the detector link on the GPU: the letterboxed detector tensor, and the detector's boxes back in frame coordinates ----
- * Replaces the host code AROUND an injected person detector (the network and its NMS stay the caller's):
+ * Replaces the host code AROUND an injected person detector (the network stays the caller's; its NMS is hrn_detector_nms_dev below):
  * models_/detectors/YOLOv3.py:23-76 (letterbox + prepare_data before the network, filter_classes + scale_coords after it) and
  * models_/detectors/YOLOv5.py:9-39, 88-98 (letterbox before; confidence / class filter and (x - dw) / ratio after).
  *
@@ -647,6 +647,75 @@ int hrn_detections_to_frame_dev(hrn_handle h, int rule, const float *dets_dev, i
                                 const hrn_letterbox *geometry_host, const int32_t *frame_hw_host, int out_h, int out_w,
                                 int conf_col, float conf_thres, int class_col, const int32_t *classes_host, int nclasses, int flags,
                                 float *dets_out_dev, int32_t *counts_dev, int32_t *status_dev, void *stream);
+
+/* ---- detector NMS: the raw output of a YOLO head to kept rows, on the host or without leaving the device ----
+ * The step between the detector NETWORK and hrn_detections_to_frame: the reference takes it from non_max_suppression of its
+ * YOLOv3 submodule (models_/detectors/YOLOv3.py:13,135) and from ultralytics' AutoShape, i.e. torchvision.ops.nms
+ * (models_/detectors/YOLOv5.py:85-87).  hrn_detector_nms is the host form (no handle, no GPU; failure text:
+ * hrn_detector_nms_last_error(), per thread); hrn_detector_nms_dev has every array in device memory, is stream-ordered, makes
+ * no host read and equals the host form bit for bit on all four outputs.  csrc/detector_nms_math.h is the one text both compile:
+ * float32 throughout, every operation rounded on its own (no FMA), no library call.
+ *
+ * INPUT   pred (B, N, 5 + C) contiguous, dtype HRN_F32 or HRN_F16 (widened to float32 exactly on load).  A row is
+ *         cx, cy, w, h, obj, cls_0 .. cls_{C-1}.
+ * BOX     x1 = cx - w / 2, y1 = cy - h / 2, x2 = cx + w / 2, y2 = cy + h / 2.
+ * BEST    the FIRST maximum of the classes: best = 0, cls_conf = cls_0; for c = 1 .. C-1: if cls_c > cls_conf: best = c,
+ *         cls_conf = cls_c.  (A NaN cls_0 stays; a NaN elsewhere is passed over; of -0 and +0 the first one stays.)
+ * min / max below: max(a, b) = a > b ? a : b, min(a, b) = a < b ? a : b -- with a NaN operand the result is b.
+ *
+ * HRN_DNMS_YOLOV5  ultralytics' non_max_suppression with multi_label=False:
+ *   candidate iff obj > conf_thres and conf = obj * cls_conf > conf_thres; the sort key is conf;
+ *   the output row is x1, y1, x2, y2, conf, best: 6 floats;
+ *   iw = max(min(ax2, bx2) - max(ax1, bx1), 0), ih likewise; inter = iw * ih; area = (x2 - x1) * (y2 - y1);
+ *   iou = inter / (area_a + area_b - inter), a the kept box.
+ *   Classes are separated by LABEL EQUALITY, not by ultralytics' `+ class * max_wh` offset of the boxes: on boxes of one class
+ *   the offset only changes the rounding of an IoU that sits at the threshold, and boxes of two classes never overlap with it.
+ * HRN_DNMS_YOLOV3  the YOLOv3 wrapper's non_max_suppression, its weighted merge included:
+ *   candidate iff obj >= conf_thres; the sort key is obj * cls_conf;
+ *   the output row is x1, y1, x2, y2 (merged), obj, cls_conf, best: 7 floats;
+ *   the pixel convention: iw = max(min(ax2, bx2) - max(ax1, bx1) + 1, 0), ih likewise; area = (x2 - x1 + 1) * (y2 - y1 + 1);
+ *   iou = inter / (area_a + area_b - inter + 1e-16f).
+ *   The yolo submodule is not part of the reference tree: this rule is a definition of this library, written from the wrapper's
+ *   call site and the published algorithm; parity with the submodule is UNPINNED.
+ *
+ * COMMON TO BOTH RULES
+ *   A candidate whose key is NaN is dropped and sets status bit 2 of its image.
+ *   The order is descending key; equal keys (-0 equals +0) go by ascending row: the order is stable and total.
+ *   Only the first max_candidates of that order take part (ultralytics' max_nms); status bit 0: more rows qualified.
+ *   The sweep is greedy in that order: a candidate is kept unless an earlier KEPT candidate of the same class (flag
+ *   HRN_DNMS_AGNOSTIC: of any class) has iou > iou_thres with it.  A NaN IoU never suppresses.  The IoU is always taken on the
+ *   original boxes.  The sweep stops after max_det kept rows; status bit 1: a candidate that is not suppressed remains after
+ *   the last keeper.
+ * THE YOLOV3 MERGE  Each kept row's box becomes sum(w_j * box_j) / sum(w_j), w = obj, over its merge set: the keeper itself,
+ *   always, plus every candidate that was still alive when it was taken and that it suppressed -- in ascending order position,
+ *   starting from the keeper's own term (acc = w * v; then acc = acc + w_j * v_j), float32, product and sum rounded separately.
+ *   (The submodule loops forever on a keeper whose own IoU is NaN; here the keeper always leaves the list.)
+ * A NaN in an output row is written as the quiet NaN 0x7FC00000, whatever payload the arithmetic left.
+ *
+ * OUTPUTS, all written for every image
+ *   rows    (B, max_det, 6 | 7) float32, kept rows in sweep order; rows beyond the count are all zero
+ *   index   (B, max_det) int32: the row of pred each kept row came from; -1 beyond the count
+ *   counts  (B,) int32;  status (B,) int32: the bits above
+ *
+ * LIMITS: B >= 0; N in [0, 2^24]; C in [1, 4096]; max_candidates in [1, 4096]; max_det in [1, max_candidates]; conf_thres and
+ * iou_thres finite; a known rule, dtype and flag bits; non-null outputs when B > 0, non-null pred when B * N > 0.  Anything else
+ * is code 7 with its message, judged before anything is written or launched; then a plan-only handle is refused (code 7).
+ *
+ * THE DEVICE ENTRY: two launches, no atomics on global memory, one writer per output byte.  The scoring launch (256 rows per
+ * block) reads pred once: the obj column first, the classes and the box only of rows whose obj passes, one wave per such row
+ * with a lane per class; it leaves each block's candidates compacted in row order, with their count.  The per-image launch (one
+ * block per image) scans the counts, selects the first max_candidates exactly when more qualified (a radix select over the key
+ * bits, integer histogram counts in LDS; the equal keys at the cut by row), ranks the candidates by counting, then sweeps, merges
+ * and writes with the candidates in LDS.  The scratch (32 bytes per row of pred, 8 per block of 256 rows) lives in the handle
+ * and grows on demand; calls on different streams are serialised on it. */
+enum { HRN_DNMS_YOLOV3 = 0, HRN_DNMS_YOLOV5 = 1 };
+enum { HRN_DNMS_AGNOSTIC = 1 };
+int hrn_detector_nms(const void *pred, int dtype, int B, int N, int C, int rule, int flags, float conf_thres, float iou_thres,
+                     int max_candidates, int max_det, float *rows, int32_t *index, int32_t *counts, int32_t *status);
+const char *hrn_detector_nms_last_error(void);
+int hrn_detector_nms_dev(hrn_handle h, const void *pred_dev, int dtype, int B, int N, int C, int rule, int flags, float conf_thres,
+                         float iou_thres, int max_candidates, int max_det, float *rows_dev, int32_t *index_dev,
+                         int32_t *counts_dev, int32_t *status_dev, void *stream);
 
 /* ---- frame rotation on the GPU: cv2.rotate for BGR, NV12 and I420 frames, and people between the two orientations ----
  * Replaces `frame = cv2.rotate(frame, rotation_code)` at the head of the reference's frame loops (scripts/live-demo.py:102-103,

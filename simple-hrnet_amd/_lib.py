@@ -24,6 +24,7 @@ SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "c
            "draw.hip",     # pose overlays: joints and bones of every person drawn into BGR / NV12 / I420 frames on the device
            "track.hip",    # the tracking link: boxes from joints, crop records from detections on the device (track_geometry.h)
            "pose_nms.hip",  # pose NMS: rescoring and hard / soft OKS NMS per image or stream in one launch (pose_nms_math.h)
+           "detector_nms.hip",  # detector NMS: the raw output of a YOLO head to kept rows, scoring pass + one block per image (detector_nms_math.h)
            "keypoint_eval.hip",  # COCO keypoint AP / AR: OKS matching per image, precision / recall over the set (keypoint_eval_math.h)
            "letterbox.hip",  # the detector link: the letterboxed detector tensor, the detector's boxes back in frame coordinates (letterbox_math.h)
            "rotate.hip",   # frame rotation: cv2.rotate for BGR / NV12 / I420 frames in one launch, people between the orientations (rotate_math.h)
@@ -257,6 +258,11 @@ SYMBOLS = {
     "hrn_pose_nms_dev": (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, ctypes.c_double, ctypes.c_double,
                                         ctypes.c_double, _P, _P, _P, _P, _P, _P, _P]),
     "hrn_pose_nms_oks_row": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_double, _P, _P]),
+    "hrn_detector_nms": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                        ctypes.c_float, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
+    "hrn_detector_nms_last_error": (ctypes.c_char_p, []),
+    "hrn_detector_nms_dev": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P]),
     "hrn_keypoint_eval": (ctypes.c_int, [ctypes.c_int, _P, _P, ctypes.c_int] + [_P] * 16),
     "hrn_keypoint_eval_last_error": (ctypes.c_char_p, []),
     "hrn_keypoint_eval_dev": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_int] + [_P] * 17),

@@ -20,6 +20,7 @@
 #include "assoc_math.h"
 #include "letterbox_math.h"
 #include "pose_nms_math.h"
+#include "detector_nms_math.h"
 #include "keypoint_eval_math.h"
 #include "kernels.h"
 #include "rotate_math.h"
@@ -1033,6 +1034,38 @@ int hrn_pose_nms_dev(hrn_handle h, int P, const int32_t *start_host, int J, int 
     a.thresh = thresh, a.in_vis_thre = in_vis_thre, a.rescore_thre = rescore_thre;
     a.keep = keep_dev, a.num = num_dev, a.scores_out = scores_out_dev, a.suppressor = suppressor_dev, a.status = status_dev;
     if (!h->hip_ok(launch_pose_nms(a, s), "pose NMS launch")) return 8;
+    return scope.leave() ? 0 : 6;
+}
+
+// detector NMS for B images in two launches (detector_nms.hip); the arguments are judged first (detector_nms_math.h's dnms_fault,
+// as in the host form: they need no device), then the handle.  The handle keeps the scratch of the scoring launch: 32 bytes per
+// row of pred, then two ints per block of 256 rows.
+int hrn_detector_nms_dev(hrn_handle h, const void *pred_dev, int dtype, int B, int N, int C, int rule, int flags, float conf_thres,
+                         float iou_thres, int max_candidates, int max_det, float *rows_dev, int32_t *index_dev, int32_t *counts_dev,
+                         int32_t *status_dev, void *stream) {
+    if (!h) return 1;
+    if (const char *fault = dnms_fault(pred_dev, dtype, B, N, C, rule, flags, conf_thres, iou_thres, max_candidates, max_det, rows_dev,
+                                       index_dev, counts_dev, status_dev)) {
+        h->err = std::string("hrn_detector_nms_dev: ") + fault;
+        return 7;
+    }
+    if (h->refuse_plan_only()) return 7;
+    if (B == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    DetectorNmsArgs a{};
+    a.nchunks = (N + kDnmsChunk - 1) / kDnmsChunk;
+    const size_t cand_bytes = ((size_t)B * N * sizeof(DnmsCand) + 255) / 256 * 256;
+    const size_t info_bytes = ((size_t)B * a.nchunks * sizeof(int) + 255) / 256 * 256, need = cand_bytes + 2 * info_bytes;
+    if (need && !h->table_reserve(h->dnms_buf, need, 1 << 20, "hipMalloc(detector NMS scratch)")) return 6;
+    CallScope scope(h, need ? &h->dnms_buf : nullptr, s);
+    if (!scope.entered) return 6;
+    a.pred = pred_dev, a.dtype = dtype, a.B = B, a.N = N, a.C = C, a.rule = rule, a.flags = flags;
+    a.max_candidates = max_candidates, a.max_det = max_det, a.conf_thres = conf_thres, a.iou_thres = iou_thres;
+    a.cand = h->dnms_buf.as<DnmsCand>(), a.chunk_info = (int *)(h->dnms_buf.ptr + cand_bytes);
+    a.chunk_off = (int *)(h->dnms_buf.ptr + cand_bytes + info_bytes);
+    a.rows = rows_dev, a.index = index_dev, a.counts = counts_dev, a.status = status_dev;
+    if (!h->hip_ok(launch_detector_nms(a, s), "detector NMS launch")) return 8;
     return scope.leave() ? 0 : 6;
 }
 

@@ -452,6 +452,24 @@ struct PoseNmsArgs {
 };
 hipError_t launch_pose_nms(const PoseNmsArgs &a, hipStream_t s);   // pose_nms_kernel: P blocks of 256 threads
 
+// Detector NMS (detector_nms.hip; include/hrnet_mi355.h: hrn_detector_nms_dev): the raw (B, N, 5 + C) output of a YOLO head to kept
+// rows in two launches (the arithmetic: detector_nms_math.h).
+struct DnmsCand;                   // detector_nms_math.h: one candidate, 32 bytes
+constexpr int kDnmsChunk = 256;    // rows of pred per block of the scoring launch
+struct DetectorNmsArgs {
+    const void *pred;              // (B, N, 5 + C), float or half
+    int dtype, B, N, C, rule, flags, max_candidates, max_det;
+    int nchunks;                   // ceil(N / kDnmsChunk)
+    float conf_thres, iou_thres;
+    DnmsCand *cand;                // scratch: (B, N): chunk c of image b keeps its candidates from (b * N + c * kDnmsChunk), in row order
+    int *chunk_info;               // scratch: (B, nchunks): the chunk's candidate count; bit 30: it dropped a NaN key
+    int *chunk_off;                // scratch: (B, nchunks): the per-image launch's exclusive scan of the counts
+    float *rows;                   // out: (B, max_det, 6 | 7)
+    int *index, *counts, *status;  // out: (B, max_det), B, B
+};
+size_t detector_nms_lds_bytes(int max_candidates);
+hipError_t launch_detector_nms(const DetectorNmsArgs &a, hipStream_t s);   // the scoring launch, then one block per image
+
 // COCO keypoint AP / AR (keypoint_eval.hip; include/hrnet_mi355.h: hrn_keypoint_eval_dev): matching per image, the set-wide order,
 // the precision / recall curves and the statistics in four launches (the arithmetic: keypoint_eval_math.h).
 struct EvalImage;                  // keypoint_eval_math.h: one image's detections, people and slots

@@ -23,6 +23,7 @@
 #include "assoc_math.h"
 #include "letterbox_math.h"
 #include "pose_nms_math.h"
+#include "detector_nms_math.h"
 #include "keypoint_eval_math.h"
 #include "rotate_math.h"
 #include "temporal_math.h"
@@ -424,6 +425,88 @@ int hrn_pose_nms(int P, const int32_t *start, int J, int flags, void *kpts, void
 }
 
 const char *hrn_pose_nms_last_error(void) { return g_pose_nms_error.c_str(); }
+
+// ---- detector NMS on the host (detector_nms_math.h: the text the kernels of detector_nms.hip compile) -----------------------------
+// One image after the other, everything sequential: the candidates in row order, the order by sorting the 64-bit order keys (no two
+// are equal), the greedy sweep, the YOLOV3 merge in ascending position.  hrn_detector_nms_dev equals this bit for bit.
+static thread_local std::string g_detector_nms_error;
+
+int hrn_detector_nms(const void *pred, int dtype, int B, int N, int C, int rule, int flags, float conf_thres, float iou_thres,
+                     int max_candidates, int max_det, float *rows, int32_t *index, int32_t *counts, int32_t *status) {
+    using namespace hrn;
+    if (const char *fault = dnms_fault(pred, dtype, B, N, C, rule, flags, conf_thres, iou_thres, max_candidates, max_det, rows, index,
+                                       counts, status)) {
+        g_detector_nms_error = fault;
+        return 7;
+    }
+    const int F = dnms_row_floats(rule);
+    const size_t stride = (size_t)5 + C;
+    const bool agnostic = (flags & kDnmsAgnostic) != 0;
+    std::vector<DnmsCand> cand;
+    std::vector<std::pair<uint64_t, int>> order;   // (order key, index into cand)
+    std::vector<DnmsCand> s;
+    std::vector<float> area;
+    std::vector<int> state, sup;   // state: 1 alive, 0 suppressed, 2 kept; sup: the position of the keeper that suppressed it
+    for (int b = 0; b < B; ++b) {
+        int st = 0;
+        cand.clear();
+        for (int r = 0; r < N; ++r) {
+            const size_t at = ((size_t)b * N + r) * stride;
+            const float obj = dnms_load(pred, dtype, at + 4);
+            if (!dnms_obj_passes(rule, obj, conf_thres)) continue;
+            float v = dnms_load(pred, dtype, at + 5);
+            int best = 0;
+            for (int c = 1; c < C; ++c) dnms_best_step(v, best, dnms_load(pred, dtype, at + 5 + c), c);
+            DnmsCand q;
+            const int what = dnms_candidate(rule, conf_thres, dnms_load(pred, dtype, at), dnms_load(pred, dtype, at + 1),
+                                            dnms_load(pred, dtype, at + 2), dnms_load(pred, dtype, at + 3), obj, v, best, r, &q);
+            if (what == 1) cand.push_back(q);
+            else if (what == 2) st |= kDnmsNanKey;
+        }
+        order.resize(cand.size());
+        for (size_t i = 0; i < cand.size(); ++i) order[i] = {dnms_order_key(dnms_key_bits(dnms_key(cand[i])), cand[i].row), (int)i};
+        std::sort(order.begin(), order.end());
+        if ((int)order.size() > max_candidates) st |= kDnmsTruncated, order.resize((size_t)max_candidates);
+        const int K = (int)order.size();
+        s.resize(K), area.resize(K), state.assign(K, 1), sup.assign(K, -1);
+        for (int p = 0; p < K; ++p) s[p] = cand[order[p].second], area[p] = dnms_area(rule, s[p]);
+        float *out = rows + (size_t)b * max_det * F;
+        int32_t *idx = index + (size_t)b * max_det;
+        int kept = 0;
+        for (int p = 0; p < K; ++p) {
+            if (!state[p]) continue;
+            if (kept == max_det) {
+                st |= kDnmsMaxDetHit;
+                break;
+            }
+            state[p] = 2, sup[p] = kept++;
+            for (int q = p + 1; q < K; ++q) {
+                if (state[q] != 1 || !(agnostic || s[q].best == s[p].best)) continue;
+                const float o = dnms_iou(rule, s[p].x1, s[p].y1, s[p].x2, s[p].y2, area[p], s[q].x1, s[q].y1, s[q].x2, s[q].y2, area[q]);
+                if (o > iou_thres) state[q] = 0, sup[q] = p;
+            }
+        }
+        for (int p = 0; p < K; ++p) {
+            if (state[p] != 2) continue;
+            float acc[4] = {0, 0, 0, 0}, sum = 0;
+            if (rule == kDnmsYoloV3) {
+                dnms_merge_first(s[p].obj, s[p].x1, s[p].y1, s[p].x2, s[p].y2, acc, sum);
+                for (int q = p + 1; q < K; ++q)
+                    if (state[q] == 0 && sup[q] == p) dnms_merge_add(s[q].obj, s[q].x1, s[q].y1, s[q].x2, s[q].y2, acc, sum);
+            }
+            dnms_write_row(rule, s[p], acc, sum, out + (size_t)sup[p] * F);
+            idx[sup[p]] = s[p].row;
+        }
+        for (int k = kept; k < max_det; ++k) {
+            for (int f = 0; f < F; ++f) out[(size_t)k * F + f] = 0.0f;
+            idx[k] = -1;
+        }
+        counts[b] = kept, status[b] = st;
+    }
+    return 0;
+}
+
+const char *hrn_detector_nms_last_error(void) { return g_detector_nms_error.c_str(); }
 
 // ---- COCO keypoint AP / AR on the host (keypoint_eval_math.h: the text the kernels of keypoint_eval.hip compile) ------------------
 static thread_local std::string g_keypoint_eval_error;

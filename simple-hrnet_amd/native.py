@@ -957,6 +957,35 @@ class NativeHRNet:
                      ctypes.c_float(thres), col, ids.ctypes.data, len(ids), flags, out.data_ptr(), kept.data_ptr(), status.data_ptr())
         return out, kept, status
 
+    def detector_nms(self, pred, rule, conf_thres, iou_thres, max_det: int = 300, max_candidates: int = 4096, agnostic: bool = False):
+        """``postproc.detector_nms`` on the GPU (``hrn_detector_nms_dev``: a scoring launch over the head's output and one block per
+        image, no host read): the detector's own non-maximum suppression, the step between the detector network and
+        ``detections_to_frame``.  ``pred`` (B, N, 5 + C) float32 or float16, the raw output of a YOLO head (rows ``cx, cy, w, h,
+        obj, cls...``); a tensor on the engine's GPU is used where it lies, a host array is uploaded; the other arguments as in
+        ``postproc.detector_nms``.  Returns ``(rows (B, max_det, 6 | 7) float32, counts (B,) int32, index (B, max_det) int32,
+        status (B,) int32)`` on the GPU, bit for bit the host form's; ``rows.reshape(-1, F)`` with ``max_det`` rows per image can go
+        to ``detections_to_frame`` as it is, whose confidence filter drops the zero rows (a positive ``conf_thres``).  Nothing is
+        synchronised."""
+        from .postproc import detector_nms_arguments
+
+        pred = as_tensor(pred)
+        if pred.dtype not in (torch.float16, torch.float32):
+            pred = pred.to(torch.float32)
+        dev = self.torch_device
+        pred = device_tensor(pred, dev, pred.dtype)
+        name = {torch.float32: "float32", torch.float16: "float16"}.get(pred.dtype, str(pred.dtype))
+        B, N, C, dtype, code, flags, F = detector_nms_arguments(tuple(pred.shape), name, rule, max_det, max_candidates, agnostic)
+        max_det, max_candidates = int(max_det), int(max_candidates)
+        shape = (B, max(max_det, 0))
+        rows = torch.empty(shape + (F,), dtype=torch.float32, device=dev)
+        index = torch.empty(shape, dtype=torch.int32, device=dev)
+        counts = torch.empty((B,), dtype=torch.int32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        ptr = lambda t: None if t.numel() == 0 else t.data_ptr()   # noqa: E731 -- (an empty tensor has no address)
+        self._launch("hrn_detector_nms_dev", ptr(pred), dtype, B, N, C, code, flags, float(conf_thres), float(iou_thres), max_candidates,
+                     max_det, ptr(rows), ptr(index), ptr(counts), ptr(status))
+        return rows, counts, index, status
+
     # -- frame rotation: a video stored sideways, upright without leaving the device -----------------------------------------------
     def rotate_frames(self, frames, rotation_code, out=None):
         """``cv2.rotate(frame, rotation_code)`` on the GPU (``hrn_rotate_frames``: ONE launch for all frames, no scratch) -- the

@@ -806,6 +806,57 @@ def detections_to_frame(dets, geometry: LetterboxGeometry, counts=None, conf_thr
     return out, kept, status
 
 
+# -- detector NMS: the raw output of a YOLO head to kept rows, on the host ---------------------------------------------------------
+DETECTOR_NMS_RULES = {"yolov3": 0, "yolov5": 1}   # include/hrnet_mi355.h: HRN_DNMS_YOLOV3 / _YOLOV5
+DETECTOR_NMS_AGNOSTIC = 1                          # HRN_DNMS_AGNOSTIC
+DETECTOR_NMS_DTYPES = {"float32": 0, "float16": 2}   # HRN_F32 / HRN_F16
+DETECTOR_NMS_STATUS = {1: "more rows qualified than max_candidates", 2: "max_det reached with candidates left", 4: "a NaN key was dropped"}
+
+
+def detector_nms_arguments(pred_shape, dtype_name: str, rule, max_det, max_candidates, agnostic):
+    """the host arguments ``detector_nms`` and ``NativeHRNet.detector_nms`` share: (B, N, C, dtype code, rule code, flags, floats
+    per output row).  The library judges the numbers; this judges the shapes and names."""
+    if len(pred_shape) != 3 or pred_shape[2] < 6:
+        raise ValueError("pred must be (B, N, 5 + C) with C >= 1, got %s" % (tuple(pred_shape),))
+    if dtype_name not in DETECTOR_NMS_DTYPES:
+        raise ValueError("pred must be float32 or float16, got %s" % dtype_name)
+    if rule not in DETECTOR_NMS_RULES:
+        raise ValueError("rule must be 'yolov3' or 'yolov5', got %r" % (rule,))
+    code = DETECTOR_NMS_RULES[rule]
+    return (int(pred_shape[0]), int(pred_shape[1]), int(pred_shape[2]) - 5, DETECTOR_NMS_DTYPES[dtype_name], code,
+            DETECTOR_NMS_AGNOSTIC if agnostic else 0, 7 if code == 0 else 6)
+
+
+def detector_nms(pred, rule, conf_thres, iou_thres, max_det: int = 300, max_candidates: int = 4096, agnostic: bool = False):
+    """The detector's own non-maximum suppression on the host (``hrn_detector_nms``, no GPU): the raw ``(B, N, 5 + C)`` output of
+    a YOLO head (rows ``cx, cy, w, h, obj, cls...``, float32 or float16) to kept rows -- the host form of
+    ``NativeHRNet.detector_nms``, equal to it bit for bit.  ``rule``: ``"yolov5"`` (ultralytics' ``non_max_suppression`` with
+    ``multi_label=False``: rows ``x1, y1, x2, y2, conf, class``) or ``"yolov3"`` (the YOLOv3 wrapper's, with its weighted merge:
+    rows ``x1, y1, x2, y2, obj, class confidence, class``); include/hrnet_mi355.h states both in full.  ``agnostic``: boxes of
+    different classes suppress one another.  At most ``max_candidates`` (<= 4096) rows per image take part, at most ``max_det``
+    are kept.
+
+    Returns ``(rows (B, max_det, 6 | 7) float32, counts (B,) int32, index (B, max_det) int32, status (B,) int32)``: the rows beyond
+    an image's count are zeros, ``index`` is the row of ``pred`` a kept row came from (-1 beyond the count), ``status`` bit 0: more
+    rows qualified than ``max_candidates``, bit 1: ``max_det`` was reached with candidates left, bit 2: a candidate with a NaN key
+    was dropped."""
+    p = np.asarray(pred)
+    if p.dtype != np.float16:
+        p = p.astype(np.float32, copy=False)
+    p = np.ascontiguousarray(p)
+    B, N, C, dtype, code, flags, F = detector_nms_arguments(p.shape, p.dtype.name, rule, max_det, max_candidates, agnostic)
+    max_det, max_candidates = int(max_det), int(max_candidates)
+    shape = (B, max(max_det, 0))
+    rows, index = np.empty(shape + (F,), np.float32), np.empty(shape, np.int32)
+    counts, status = np.empty((B,), np.int32), np.empty((B,), np.int32)
+    lib = _lib.load()
+    rc = lib.hrn_detector_nms(p.ctypes.data, dtype, B, N, C, code, flags, float(conf_thres), float(iou_thres), max_candidates, max_det,
+                              rows.ctypes.data, index.ctypes.data, counts.ctypes.data, status.ctypes.data)
+    if rc != 0:
+        raise ValueError("hrn_detector_nms: " + lib.hrn_detector_nms_last_error().decode())
+    return rows, counts, index, status
+
+
 # -- people between a frame and its rotation, on the host ------------------------------------------------------------------------
 def rotate_people_arguments(pts_shape, boxes_shape, frame_hw, rotation_code):
     """the host arguments ``rotate_people`` and ``NativeHRNet.rotate_people`` share: (n, J, frame sizes int32, their per-person flag,

@@ -28,7 +28,13 @@ different, and why:
   attributes ``size``, ``style`` (``"yolov3"`` / ``"yolov5"``), ``conf_thres`` and ``classes`` (either may be None).  The letterbox,
   the filters and the way back to frame coordinates run on the GPU (``detector_input`` -> ``predict_tensor`` ->
   ``detections_to_frame`` -> ``preprocess_frames_dev``); only the number of people per image is read back.  A box the host path
-  would refuse with an error (degenerate, outside the frame) goes through as an all-padding crop instead;
+  would refuse with an error (degenerate, outside the frame) goes through as an all-padding crop instead.
+  A detector object that has ``predict_raw(x)`` and no ``predict_tensor`` returns the RAW (n, N, 5 + C) output of its YOLO head
+  (rows ``cx, cy, w, h, obj, cls...``, float32 or float16, on the device) and leaves the NMS to the GPU as well
+  (``detector_input`` -> ``predict_raw`` -> ``NativeHRNet.detector_nms`` -> ``detections_to_frame`` -> ...): the rule is its
+  ``style``, the IoU threshold its attribute ``nms_thres`` (required), and ``max_det`` (300), ``max_candidates`` (4096) and
+  ``agnostic`` (False) are read when present.  On this path ``conf_thres`` must be set and positive (ValueError otherwise): the
+  rows beyond an image's count are zeros, and a zero row must never become a person;
 * devices: ``'cuda:N'`` is that GPU.  ``'cuda'`` (all GPUs) and ``'cuda:1,2'`` (the listed ones) are, in a plain Python
   process, ONE engine per listed GPU driven from this process (``native.MultiDeviceHRNet``: the crop batch of a
   ``predict()`` call is split by index range, one host thread per GPU) -- what ``DataParallel`` gives the reference with
@@ -47,6 +53,21 @@ from .native import MultiDeviceHRNet, NativeHRNet, refine_code
 
 _MEAN = (0.485, 0.456, 0.406)   # SimpleHRNet.py:171
 _STD = (0.229, 0.224, 0.225)
+
+
+def _raw_detector_arguments(dd) -> dict:
+    """the NMS arguments of a ``device_detector`` that has ``predict_raw`` and no ``predict_tensor``, as keywords of
+    ``NativeHRNet.detector_nms``; ValueError when the object cannot be driven that way"""
+    if not hasattr(dd, "predict_raw"):
+        raise ValueError("device_detector needs predict_tensor(x) or predict_raw(x)")
+    conf = getattr(dd, "conf_thres", None)
+    if conf is None or not float(conf) > 0.0:
+        raise ValueError("a device_detector with predict_raw needs a positive conf_thres (a zero row must never become a person), "
+                         "got %r" % (conf,))
+    if getattr(dd, "nms_thres", None) is None:
+        raise ValueError("a device_detector with predict_raw needs nms_thres (the IoU threshold of its NMS)")
+    return dict(iou_thres=float(dd.nms_thres), max_det=int(getattr(dd, "max_det", 300)),
+                max_candidates=int(getattr(dd, "max_candidates", 4096)), agnostic=bool(getattr(dd, "agnostic", False)))
 
 
 # (local-rank variable, task-count variables of the same launcher): srun / mpirun export their local rank even for a one-task
@@ -175,6 +196,8 @@ class SimpleHRNet:
         if multiperson and detector is None and device_detector is None:
             raise ValueError("multiperson=True needs detector= (the reference's YOLO wrappers are un-vendored third-party code)")
         self.detector, self.device_detector = detector, device_detector
+        if device_detector is not None and not hasattr(device_detector, "predict_tensor"):
+            _raw_detector_arguments(device_detector)   # (raises ValueError before any engine is built)
         if len(self.devices) == 1:
             self.model = NativeHRNet(c, nof_joints, self.resolution, dtype, max_batch=max_batch_size, device=self.device,
                                      model_name=model_name)
@@ -244,19 +267,28 @@ class SimpleHRNet:
 
     def _device_detections(self, frames):
         """the detector link on the GPU for device frames (one (Hf, Wf, 3) tensor or a stack): ``detector_input`` ->
-        ``predict_tensor`` -> ``detections_to_frame``.  Returns ``(rows, found, kept)``: the compacted rows in frame coordinates
+        ``predict_tensor`` (or ``predict_raw`` -> ``detector_nms``) -> ``detections_to_frame``.  Returns ``(rows, found, kept)``: the compacted rows in frame coordinates
         on the device (None when the detector found nothing anywhere), per image whether the detector returned rows at all, and
         the number of rows kept per image -- the one thing read back."""
         dd = self.device_detector
+        nms = None if hasattr(dd, "predict_tensor") else _raw_detector_arguments(dd)
         x, geometry = self.model.detector_input(frames, dd.size, dd.style)
-        per_image = list(dd.predict_tensor(x))
-        if len(per_image) != len(geometry):
-            raise ValueError("predict_tensor returned %d results for %d images" % (len(per_image), len(geometry)))
-        found = [t is not None for t in per_image]
-        counts = [int(t.shape[0]) if t is not None else 0 for t in per_image]
-        if not any(counts):
-            return None, found, [0] * len(counts)
-        dets = torch.cat([t.to(self.device, torch.float32) for t in per_image if t is not None and len(t)], 0)
+        if nms is not None:   # the raw head output: its NMS on the GPU; max_det rows per image, the zero rows fall to the filter below
+            raw = dd.predict_raw(x)
+            if len(raw.shape) != 3 or int(raw.shape[0]) != len(geometry):
+                raise ValueError("predict_raw returned %s for %d images" % (tuple(raw.shape), len(geometry)))
+            kept_rows = self.model.detector_nms(raw, dd.style, dd.conf_thres, **nms)[0]
+            found, counts = [True] * len(geometry), [int(kept_rows.shape[1])] * len(geometry)
+            dets = kept_rows.reshape(-1, int(kept_rows.shape[2]))
+        else:
+            per_image = list(dd.predict_tensor(x))
+            if len(per_image) != len(geometry):
+                raise ValueError("predict_tensor returned %d results for %d images" % (len(per_image), len(geometry)))
+            found = [t is not None for t in per_image]
+            counts = [int(t.shape[0]) if t is not None else 0 for t in per_image]
+            if not any(counts):
+                return None, found, [0] * len(counts)
+            dets = torch.cat([t.to(self.device, torch.float32) for t in per_image if t is not None and len(t)], 0)
         rows, kept, _ = self.model.detections_to_frame(dets, geometry, counts=counts, conf_thres=getattr(dd, "conf_thres", None),
                                                        classes=getattr(dd, "classes", None), compact=True)
         kept = kept.cpu().numpy().tolist()
