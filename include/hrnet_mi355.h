@@ -330,6 +330,74 @@ int hrn_assoc_exp(const double *x, int n, double *out);
 int hrn_associate_similarity(const int32_t *boxes, const float *pts, int n, const int32_t *prev_boxes, const float *prev_pts, int m, int J,
                              double pose_alpha, double *cost_out /* (n,m) */, float *sim_out /* (n,m) */);
 
+/* ---- person ids through occlusions: a per-stream track table, on the host and on the device ----
+ * hrn_associate_people compares this frame with the previous frame and nothing else: a person missing for one frame returns as a
+ * stranger, and the library's "nobody" row (all zeros: track_frame's lost person, pose_nms' suppressed one, detections_to_frame's
+ * dropped one) is numbered anew on every frame.  A TRACK TABLE replaces the pair "previous frame's arrays + hrn_associate_people":
+ * one update per frame, lost tracks stay for up to max_lost updates, and with coast a track is compared where a constant-velocity
+ * model expects it.  The arithmetic is csrc/tracks_math.h's over csrc/assoc_math.h's (unchanged), one text for both entries.
+ *
+ * TABLE.  Stream p of P has capacity C, 1 <= C <= HRN_MAX_TRACKED.  All arrays are in / out, C-contiguous:
+ *   slot_id    (P, C) int32      -1: the slot is free            slot_lost  (P, C) int32   updates since the track was last accepted
+ *   slot_hits  (P, C) int32      accepted updates, saturating at 2^30 (a new track starts at 1)
+ *   slot_row   (P, C) int32      the track's row in the latest update, counted from cur_start[p]; -1 when it was not seen
+ *   slot_boxes (P, C, 4) int32   the last accepted observation, after smoothing       slot_pts  (P, C, J, 3) float32  likewise
+ *   slot_vel   (P, C, 2) float32 box-centre velocity (dy, dx) per update               next_id   (P) int32  the stream's id counter
+ * A fresh table has slot_id -1, slot_row -1 and every other value 0 (all bits); a freed slot is written back to exactly that.
+ *
+ * ONE UPDATE of stream p, with the rows [cur_start[p], cur_start[p + 1]) of boxes (n, 4) int32 and pts (n, J, 3) float32 (in / out):
+ *  1. A row is PRESENT iff x2 > x1 && y2 > y1.  An absent row takes part in nothing: ids = match_row = slot = -1, its box and joints
+ *     keep their bits.
+ *  2. The COLUMNS are the live slots (slot_id >= 0): first those with slot_lost == 0 in ascending (slot_row, slot index), then the
+ *     others in ascending slot index.  The rows are the present rows in row order.  (While nobody is lost this is the previous
+ *     frame's row order, so ties in the assignment fall as in hrn_associate_people.)
+ *  3. COMPARED STATE of a column: k = coast ? (double)slot_lost + 1 : 0.  k == 0: the stored bits.  Otherwise a box component is
+ *     t = (double)b + (double)v * k with v = dx for x1, x2 and dy for y1, y2 (product and sum each rounded once); NaN: b; else
+ *     clamped to [-2^31, 2^31 - 1] and truncated towards zero.  A joint's y and x are (float)((double)c + (double)v * k); the
+ *     confidence is copied.
+ *  4. ASSOCIATION: assoc_pair on (row, compared state) over (present rows x columns), hrn_assignment's matching, acceptance
+ *     sim > f32(similarity_threshold) -- hrn_associate_people's, expression for expression.
+ *  5. ACCEPTED pair (row i, slot s): ids[i] = slot_id[s]; match_row[i] = the slot's OLD slot_row if its old slot_lost was 0, else
+ *     -1; slot[i] = s.  Velocity first, from the RAW current box and the STORED box (not the compared one): centres
+ *     ((double)lo + (double)hi) / 2 per axis, d = (c_now - c_stored) / ((double)old_lost + 1); old slot_hits == 1: vel = (float)d,
+ *     otherwise vel = (float)((double)vel + va * (d - (double)vel)), va = velocity_alpha; a non-finite component becomes +0.0f.
+ *     Then, when smoothing_alpha != 0, assoc_smooth_box / assoc_smooth_joint of the row against the COMPARED state (all three
+ *     joint components, as today).  The result is written to boxes / pts and into the slot (without smoothing the slot takes the
+ *     row as it is).  slot_lost = 0, slot_hits = min(hits + 1, 2^30), slot_row = i.
+ *  6. UNACCEPTED live slot: freed when slot_lost + 1 > max_lost; otherwise slot_lost += 1, slot_row = -1 and its observation and
+ *     velocity keep their bits.
+ *  7. NEW PEOPLE, the present rows not accepted, take in row order the free slots in ascending slot index (those freed in step 6
+ *     included) and are numbered assoc_fresh_id(next_id, rank) in row order.  A new slot: observation = the row, vel = 0,
+ *     slot_lost = 0, slot_hits = 1, slot_row = i.  With no slot left the row is still numbered, gets slot = -1 and status bit 2.
+ *  8. next_id = assoc_next_id(next_id, max id among this update's present rows); a stream without a present row leaves it (steps
+ *     2 and 6 still run: lost tracks age).
+ *   cur_start  P + 1 int32, non-decreasing, on the HOST in both entries;  ids, match_row, slot  n int32 out;  status  P int32 out:
+ *   bits 0 and 1 as in hrn_associate_people, bit 2: the table was full.
+ *   pose_alpha, similarity_threshold finite; smoothing_alpha in [0, 1]; max_lost in [0, 2^20]; coast 0 or 1; velocity_alpha in (0, 1].
+ * A table the caller filled is taken as it is (it cannot be read before a stream-ordered launch): slot_lost and slot_hits are
+ * expected non-negative; no value leads to an access outside the arrays.
+ * Code 7, judged before anything is written and named by hrn_track_people_last_error() (per thread) / hrn_last_error(h): the set
+ * of hrn_associate_people (P < 0, J, the parameters, null or decreasing segment table, null arrays), C out of range, max_lost /
+ * coast / velocity_alpha out of range, null table arrays, more than HRN_MAX_TRACKED rows in a stream; then, for the device entry,
+ * a plan-only handle.
+ * hrn_track_people is the host form: no handle, no GPU.  hrn_track_people_dev has every array in device memory and cur_start on the
+ * host: ONE launch, one 256-thread block per stream that owns the stream's table and updates it in place (columns ranked by
+ * counting, rows compacted by ballot, pairs by all threads, the assignment by one wave -- the text hrn_associate_people_dev runs,
+ * csrc/assoc_assign.h -- steps 5-8 by the block), stream-ordered, no host read, no atomics; equal to the host form bit for bit.
+ * The live-column count is known only on the device, so the handle keeps scratch for n x C per stream: 12 * n * C bytes (at most
+ * 768 KiB) plus, with coast, 16 * C + 12 * C * J bytes of compared state (at most 772 KiB), grown on demand.  For P > 1 the stream
+ * table goes through one upload.  P == 0 launches nothing. */
+int hrn_track_people(int P, const int32_t *cur_start, int C, int J, int32_t *boxes, float *pts, int32_t *slot_id, int32_t *slot_lost,
+                     int32_t *slot_hits, int32_t *slot_row, int32_t *slot_boxes, float *slot_pts, float *slot_vel, int32_t *next_id,
+                     double pose_alpha, double similarity_threshold, double smoothing_alpha, int max_lost, int coast,
+                     double velocity_alpha, int32_t *ids, int32_t *match_row, int32_t *slot, int32_t *status);
+const char *hrn_track_people_last_error(void);
+int hrn_track_people_dev(hrn_handle h, int P, const int32_t *cur_start_host, int C, int J, int32_t *boxes_dev, float *pts_dev,
+                         int32_t *slot_id_dev, int32_t *slot_lost_dev, int32_t *slot_hits_dev, int32_t *slot_row_dev,
+                         int32_t *slot_boxes_dev, float *slot_pts_dev, float *slot_vel_dev, int32_t *next_id_dev, double pose_alpha,
+                         double similarity_threshold, double smoothing_alpha, int max_lost, int coast, double velocity_alpha,
+                         int32_t *ids_dev, int32_t *match_row_dev, int32_t *slot_dev, int32_t *status_dev, void *stream);
+
 /* ---- joints over time: One-Euro smoothing and motion lookahead, on the host and on the device ----
  * The One-Euro filter (Casiez, Roussel, Vogel, CHI 2012) of every joint, a first-order low-pass whose cut-off rises with the
  * filtered speed, and the prediction its derivative estimate gives: next frame's joints ~ this frame's RAW joints + filtered

@@ -29,6 +29,7 @@ SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "c
            "letterbox.hip",  # the detector link: the letterboxed detector tensor, the detector's boxes back in frame coordinates (letterbox_math.h)
            "rotate.hip",   # frame rotation: cv2.rotate for BGR / NV12 / I420 frames in one launch, people between the orientations (rotate_math.h)
            "assoc.hip",    # person ids between two frames: similarity, assignment, ids and smoothing in one launch (assoc_math.h)
+           "tracks.hip",   # the person track table: one update per frame keeps ids through occlusions, one launch (tracks_math.h, assoc_assign.h)
            "temporal.hip",  # joints over time: the One-Euro filter and the motion lookahead of every joint in one launch (temporal_math.h)
            # fp16 instantiations of the three hand-scheduled kernel families (bodies shared through conv3x3_lds.inc / conv_s2.inc /
            # bottleneck_chain.inc): translation units of their own, so that each bf16 file still compiles to exactly its kernel set
@@ -245,6 +246,11 @@ SYMBOLS = {
     "hrn_associate_people_last_error": (ctypes.c_char_p, []),
     "hrn_associate_people_dev": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P, ctypes.c_double,
                                                 ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
+    "hrn_track_people": (ctypes.c_int, [ctypes.c_int, _P, ctypes.c_int, ctypes.c_int] + [_P] * 10 + [ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, _P, _P, _P, _P]),
+    "hrn_track_people_last_error": (ctypes.c_char_p, []),
+    "hrn_track_people_dev": (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int] + [_P] * 10 + [ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, _P, _P, _P, _P, _P]),
     "hrn_assoc_exp": (ctypes.c_int, [_P, ctypes.c_int, _P]),
     "hrn_associate_similarity": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_double, _P, _P]),
     "hrn_filter_poses": (ctypes.c_int, [ctypes.c_int, _P, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double,

@@ -5,9 +5,10 @@
 //   phase 1   threads stride over the (current, previous) pairs; each runs assoc_math.h's similarity and blend serially over the
 //             joints (numpy's pairwise summation order forbids splitting a pair across lanes) and writes cost and similarity to
 //             the engine's scratch
-//   phase 2   ONE wave runs hrn_assignment's shortest augmenting paths.  u, v, minv, p, way and used live in LDS; lane l owns the
-//             columns l + 1, l + 65, ... in ascending order, and the wave's minimum keeps the lower column on equal values, so
-//             every step is elementwise or that argmin: the matching is hrn_assignment's by construction, not by tolerance
+//   phase 2   ONE wave runs hrn_assignment's shortest augmenting paths (assoc_assign.h, shared with tracks.hip).  u, v, minv, p,
+//             way and used live in LDS; lane l owns the columns l + 1, l + 65, ... in ascending order, and the wave's minimum
+//             keeps the lower column on equal values, so every step is elementwise or that argmin: the matching is
+//             hrn_assignment's by construction, not by tolerance
 //   phase 3   the block applies the threshold, carries ids over, numbers new people in index order (ballot + prefix count),
 //             smooths matched boxes and joints, updates next_id and writes the status
 //
@@ -15,28 +16,17 @@
 // the steps of each augmenting path, and one wave of one CU runs it.
 #include <hip/hip_runtime.h>
 
+#include "assoc_assign.h"
 #include "assoc_math.h"
 #include "kernels.h"
 
 namespace hrn {
 
-namespace {
-
-// orders the LDS traffic of the lanes of ONE wave (its DS instructions execute in order; this keeps the compiler from moving
-// them across and waits for the ones in flight)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(256) void assoc_kernel(AssocArgs a) {
 #pragma clang fp contract(off)
-    __shared__ double s_u[kMaxTracked + 1], s_v[kMaxTracked + 1], s_minv[kMaxTracked + 1], s_vars[17];
-    __shared__ int s_p[kMaxTracked + 1], s_way[kMaxTracked + 1], s_col[kMaxTracked], s_cnt[4], s_max[4];
-    __shared__ unsigned char s_used[kMaxTracked + 1];
+    __shared__ AssignLds s_assign;
+    __shared__ double s_vars[17];
+    __shared__ int s_col[kMaxTracked], s_cnt[4], s_max[4];
     __shared__ int s_fail;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const AssocProblem pr = a.P == 1 ? a.one : a.table[blockIdx.x];
@@ -64,79 +54,8 @@ __global__ __launch_bounds__(256) void assoc_kernel(AssocArgs a) {
     int status = __syncthreads_or(replaced) ? 1 : 0;   // (the barrier also publishes the scratch to the block)
 
     // ---- phase 2: the assignment, one wave (hrn_assignment, postproc.cpp, step for step) ----
-    if (wave == 0 && m > 0 && !a.no_assign) {
-        const bool tr = n > m;                          // rows > cols: work on the transposed matrix
-        const int nn = tr ? m : n, mm = tr ? n : m;     // nn <= mm
-        const double inf = __builtin_huge_val();
-        for (int j = lane; j <= mm; j += 64) s_v[j] = 0.0, s_p[j] = 0, s_way[j] = 0;
-        for (int i = lane; i <= nn; i += 64) s_u[i] = 0.0;
-        bool ok = true;
-        for (int i = 1; i <= nn; ++i) {
-            for (int j = lane; j <= mm; j += 64) s_minv[j] = inf, s_used[j] = 0;
-            if (lane == 0) s_p[0] = i;
-            wave_sync();
-            int j0 = 0;
-            for (;;) {
-                if (lane == 0) s_used[j0] = 1;
-                wave_sync();
-                const int i0 = __builtin_amdgcn_readfirstlane(s_p[j0]);
-                const double ui0 = s_u[i0];
-                double best = inf;
-                int bestj = 0;
-                for (int j = lane + 1; j <= mm; j += 64) {
-                    if (s_used[j]) continue;
-                    const double c = tr ? cost[(size_t)(j - 1) * m + (i0 - 1)] : cost[(size_t)(i0 - 1) * m + (j - 1)];
-                    const double cur = c - ui0 - s_v[j];
-                    double mv = s_minv[j];
-                    if (cur < mv) mv = cur, s_minv[j] = cur, s_way[j] = j0;
-                    if (mv < best) best = mv, bestj = j;
-                }
-                for (int o = 32; o > 0; o >>= 1) {      // the lower value; on equal values the lower column
-                    const double wv = __shfl_xor(best, o);
-                    const int wj = __shfl_xor(bestj, o);
-                    if (wv < best || (wv == best && wj < bestj)) best = wv, bestj = wj;
-                }
-                const int j1 = __builtin_amdgcn_readfirstlane(bestj);
-                const double delta = best;
-                if (j1 == 0) {                          // no augmenting path (cannot happen with finite costs): the loop still ends
-                    ok = false;
-                    break;
-                }
-                // (ui0 above is every lane's read of s_u[i0]; the writes below come later in the wave's program order, and no
-                // wave_sync is needed between them only because one wave64 runs in lockstep: keep the ui0 load ABOVE this update)
-                if (lane == 0) s_u[s_p[0]] += delta, s_v[0] -= delta;   // column 0 is always used
-                for (int j = lane + 1; j <= mm; j += 64) {
-                    if (s_used[j])
-                        s_u[s_p[j]] += delta, s_v[j] -= delta;          // (the rows of used columns are distinct)
-                    else
-                        s_minv[j] -= delta;
-                }
-                j0 = j1;
-                wave_sync();
-                if (__builtin_amdgcn_readfirstlane(s_p[j0]) == 0) break;
-            }
-            if (!ok) break;
-            if (lane == 0) {
-                do {
-                    const int j1 = s_way[j0];
-                    s_p[j0] = s_p[j1];
-                    j0 = j1;
-                } while (j0);
-            }
-            wave_sync();
-        }
-        if (ok) {
-            for (int j = lane + 1; j <= mm; j += 64)
-                if (s_p[j]) {
-                    const int small = s_p[j] - 1, big = j - 1;
-                    if (tr)
-                        s_col[big] = small;
-                    else
-                        s_col[small] = big;
-                }
-        } else if (lane == 0) {
-            s_fail = 1;
-        }
+    if (wave == 0 && m > 0 && !a.no_assign) {   // (assoc_assign.h: the text tracks.hip runs too)
+        if (!assoc_assign_wave(cost, n, m, lane, s_assign, s_col) && lane == 0) s_fail = 1;
     }
     __syncthreads();
     if (s_fail) status |= 2;

@@ -75,6 +75,8 @@
                                             // per-person records the build launch writes; draw_table's guard
     CallScratch assoc_buf;     // hrn_associate_people_dev: the problem table of a call with several problems, then the costs and
                                // similarities the kernel keeps between its phases
+    CallScratch tracks_buf;    // hrn_track_people_dev: the stream table of a call with several streams, then per stream the costs,
+                               // the similarities and (coast) the compared state the kernel keeps between its phases
     CallScratch nms_table;     // hrn_pose_nms_dev: the problem table of a call with several problems
     CallScratch eval_buf;      // hrn_keypoint_eval_dev: the image table, then the set-wide order of the slots
     CallScratch trk_table;     // the tracking link: the call's host table (frame sizes per person; frame table and frame index)
@@ -152,7 +154,7 @@
     }
 
     void free_scratch() {
-        for (CallScratch *c : {&rs_taps, &pre_tmp, &pre_params, &pre_yuv, &warp_params, &score_joints, &draw_table, &draw_records, &assoc_buf,
+        for (CallScratch *c : {&rs_taps, &pre_tmp, &pre_params, &pre_yuv, &warp_params, &score_joints, &draw_table, &draw_records, &assoc_buf, &tracks_buf,
                                &nms_table, &eval_buf, &trk_table, &lb_table, &det_table, &rot_table, &rot_people, &dnms_buf, &tmp_table})
             c->release();
         pass.release();

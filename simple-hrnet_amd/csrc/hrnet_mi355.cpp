@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "assoc_math.h"
+#include "tracks_math.h"
 #include "letterbox_math.h"
 #include "pose_nms_math.h"
 #include "detector_nms_math.h"
@@ -994,6 +995,60 @@ int hrn_associate_people_dev(hrn_handle h, int P, const int32_t *cur_start_host,
     a.next_id = next_id_dev, a.pose_alpha = pose_alpha, a.similarity_threshold = similarity_threshold, a.smoothing_alpha = smoothing_alpha;
     a.ids = ids_dev, a.match = match_dev, a.status = status_dev, a.scratch = h->assoc_buf.ptr;
     if (!h->hip_ok(launch_assoc(a, s), "association launch")) return 8;
+    return scope.leave() ? 0 : 6;
+}
+
+// one update of P per-stream track tables in one launch (tracks.hip); the arguments are judged first (tracks_math.h's track_fault,
+// as in the host form: they need no device), then the handle.  The scratch per stream: 12 * n * C bytes of costs and similarities
+// (at most 768 KiB) and, with coast, the compared state of the C slots (16 * C + 12 * C * J bytes, at most 772 KiB).
+int hrn_track_people_dev(hrn_handle h, int P, const int32_t *cur_start_host, int C, int J, int32_t *boxes_dev, float *pts_dev,
+                         int32_t *slot_id_dev, int32_t *slot_lost_dev, int32_t *slot_hits_dev, int32_t *slot_row_dev,
+                         int32_t *slot_boxes_dev, float *slot_pts_dev, float *slot_vel_dev, int32_t *next_id_dev, double pose_alpha,
+                         double similarity_threshold, double smoothing_alpha, int max_lost, int coast, double velocity_alpha,
+                         int32_t *ids_dev, int32_t *match_row_dev, int32_t *slot_dev, int32_t *status_dev, void *stream) {
+    if (!h) return 1;
+    if (const char *fault = track_fault(P, cur_start_host, C, J, boxes_dev, pts_dev, slot_id_dev, slot_lost_dev, slot_hits_dev, slot_row_dev,
+                                        slot_boxes_dev, slot_pts_dev, slot_vel_dev, next_id_dev, pose_alpha, similarity_threshold,
+                                        smoothing_alpha, max_lost, coast, velocity_alpha, ids_dev, match_row_dev, slot_dev, status_dev)) {
+        h->err = std::string("hrn_track_people_dev: ") + fault;
+        return 7;
+    }
+    if (h->refuse_plan_only()) return 7;
+    if (P == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    // the streams, each with its piece of the scratch behind the table
+    const size_t table_bytes = P > 1 ? ((size_t)P * sizeof(TrackProblem) + 255) / 256 * 256 : 0;
+    const size_t compared = coast ? (size_t)C * 16 + (size_t)C * J * 12 : 0;
+    std::vector<TrackProblem> probs((size_t)P);
+    size_t need = table_bytes;
+    for (int p = 0; p < P; ++p) {
+        TrackProblem &q = probs[p];
+        q.cur0 = cur_start_host[p], q.n = cur_start_host[p + 1] - q.cur0;
+        q.scratch = (long long)need;
+        need += ((size_t)q.n * C * 12 + compared + 15) / 16 * 16;
+    }
+    if (need && !h->table_reserve(h->tracks_buf, need, 65536, "hipMalloc(track table scratch)")) return 6;
+    CallScope scope(h, &h->tracks_buf, s);
+    if (!scope.entered) return 6;
+    TracksArgs a{};
+    a.P = P, a.C = C, a.J = J, a.max_lost = max_lost, a.coast = coast;
+    if (P > 1) {   // the table through the pinned ring
+        unsigned ring = 0;
+        char *pin = h->pre_stage(table_bytes, &ring);
+        if (!pin) return 6;
+        memcpy(pin, probs.data(), (size_t)P * sizeof(TrackProblem));
+        if (!h->pre_upload(ring, s, {{h->tracks_buf.ptr, pin, (size_t)P * sizeof(TrackProblem), "hipMemcpyAsync(track stream table)"}})) return 6;
+        a.table = h->tracks_buf.as<const TrackProblem>();
+    } else {
+        a.one = probs[0];
+    }
+    a.boxes = boxes_dev, a.pts = pts_dev, a.slot_id = slot_id_dev, a.slot_lost = slot_lost_dev, a.slot_hits = slot_hits_dev;
+    a.slot_row = slot_row_dev, a.slot_boxes = slot_boxes_dev, a.slot_pts = slot_pts_dev, a.slot_vel = slot_vel_dev, a.next_id = next_id_dev;
+    a.pose_alpha = pose_alpha, a.similarity_threshold = similarity_threshold, a.smoothing_alpha = smoothing_alpha;
+    a.velocity_alpha = velocity_alpha;
+    a.ids = ids_dev, a.match_row = match_row_dev, a.slot = slot_dev, a.status = status_dev, a.scratch = h->tracks_buf.ptr;
+    if (!h->hip_ok(launch_tracks(a, s), "track table launch")) return 8;
     return scope.leave() ? 0 : 6;
 }
 

@@ -432,6 +432,30 @@ hipError_t launch_assoc(const AssocArgs &a, hipStream_t s);   // assoc_kernel: P
 // bone[i] = palette[ids[i] mod Cb] (Python's modulo) for hrn_draw_poses_ids_dev: the ids never leave the device
 hipError_t launch_bone_ids(const int *ids, int n, const unsigned *palette, int Cb, unsigned *bone, hipStream_t s);
 
+// The person track table (tracks.hip; include/hrnet_mi355.h: hrn_track_people_dev): one update of P per-stream tables in one
+// launch, one block per stream (the arithmetic: tracks_math.h over assoc_math.h).
+struct TrackProblem {              // one stream: n rows from cur0
+    int cur0, n;
+    long long scratch;             // byte offset of its piece of TracksArgs::scratch: n * C costs (double), n * C similarities (float),
+                                   // then (coast) C compared boxes (4 int32) and C * J * 3 compared joint values (float)
+};
+struct TracksArgs {
+    int P, C, J, max_lost, coast;
+    TrackProblem one;              // P == 1: the stream, in the kernel arguments (nothing is uploaded)
+    const TrackProblem *table;     // else P entries, device
+    int *boxes;                    // (n, 4) int32, in / out
+    float *pts;                    // (n, J, 3) float32, in / out
+    int *slot_id, *slot_lost, *slot_hits, *slot_row;   // (P, C), in / out
+    int *slot_boxes;               // (P, C, 4), in / out
+    float *slot_pts;               // (P, C, J, 3), in / out
+    float *slot_vel;               // (P, C, 2), in / out
+    int *next_id;                  // P, in / out
+    double pose_alpha, similarity_threshold, smoothing_alpha, velocity_alpha;
+    int *ids, *match_row, *slot, *status;   // out: n, n, n, P
+    char *scratch;
+};
+hipError_t launch_tracks(const TracksArgs &a, hipStream_t s);   // tracks_kernel: P blocks of 256 threads
+
 // Pose NMS (pose_nms.hip; include/hrnet_mi355.h: hrn_pose_nms_dev): rescoring, ordering and hard or soft OKS NMS of P independent
 // problems in one launch, one block per problem (the arithmetic: pose_nms_math.h).
 struct PoseNmsProblem {            // one problem: n people from `first`

@@ -27,6 +27,7 @@
 #include "keypoint_eval_math.h"
 #include "rotate_math.h"
 #include "temporal_math.h"
+#include "tracks_math.h"
 
 #pragma clang fp contract(off)
 
@@ -302,6 +303,120 @@ int hrn_associate_people(int P, const int32_t *cur_start, const int32_t *prev_st
 }
 
 const char *hrn_associate_people_last_error(void) { return g_associate_error.c_str(); }
+
+// One update of P per-stream track tables on the host (include/hrnet_mi355.h states the eight steps), in tracks_math.h's and
+// assoc_math.h's arithmetic -- the text the kernel of tracks.hip compiles, so hrn_track_people_dev equals this bit for bit.
+namespace {
+thread_local std::string g_track_people_error;
+}
+
+int hrn_track_people(int P, const int32_t *cur_start, int C, int J, int32_t *boxes, float *pts, int32_t *slot_id, int32_t *slot_lost,
+                     int32_t *slot_hits, int32_t *slot_row, int32_t *slot_boxes, float *slot_pts, float *slot_vel, int32_t *next_id,
+                     double pose_alpha, double similarity_threshold, double smoothing_alpha, int max_lost, int coast,
+                     double velocity_alpha, int32_t *ids, int32_t *match_row, int32_t *slot, int32_t *status) {
+    using namespace hrn;
+    if (const char *fault = track_fault(P, cur_start, C, J, boxes, pts, slot_id, slot_lost, slot_hits, slot_row, slot_boxes, slot_pts,
+                                        slot_vel, next_id, pose_alpha, similarity_threshold, smoothing_alpha, max_lost, coast,
+                                        velocity_alpha, ids, match_row, slot, status)) {
+        g_track_people_error = fault;
+        return 7;
+    }
+    const AssocParams prm = assoc_params(pose_alpha, similarity_threshold, smoothing_alpha);
+    double vars[17];
+    for (int j = 0; j < 17; ++j) vars[j] = assoc_coco_var(j);
+    const size_t per = (size_t)J * 3;
+    std::vector<double> cost;
+    std::vector<float> sim, cmp_pts((size_t)C * per);
+    std::vector<int32_t> col, cmp_boxes((size_t)C * 4);
+    std::vector<int> rows, cols, row_of_slot(C);
+    std::vector<std::pair<long long, int>> order;
+    for (int p = 0; p < P; ++p) {
+        const int cur0 = cur_start[p], n = cur_start[p + 1] - cur0;
+        int32_t *sid = slot_id + (size_t)p * C, *slost = slot_lost + (size_t)p * C, *shits = slot_hits + (size_t)p * C;
+        int32_t *srow = slot_row + (size_t)p * C, *sbox = slot_boxes + (size_t)p * C * 4;
+        float *spts = slot_pts + (size_t)p * C * per, *svel = slot_vel + (size_t)p * C * 2;
+        status[p] = 0;
+        // steps 1-3: the present rows, the live columns in order, their compared state
+        rows.clear(), order.clear(), cols.clear();
+        for (int i = 0; i < n; ++i) {
+            ids[cur0 + i] = match_row[cur0 + i] = slot[cur0 + i] = -1;
+            if (track_present(boxes + (size_t)(cur0 + i) * 4)) rows.push_back(i);
+        }
+        for (int s = 0; s < C; ++s)
+            if (sid[s] >= 0) order.emplace_back(track_column_key(slost[s], srow[s], s), s);
+        std::sort(order.begin(), order.end());
+        for (const auto &o : order) cols.push_back(o.second);
+        for (int s : cols) {
+            const double k = track_k(coast, slost[s]);
+            for (int c = 0; c < 4; ++c) cmp_boxes[(size_t)s * 4 + c] = track_compared_box(sbox[(size_t)s * 4 + c], track_box_axis(svel + s * 2, c), k);
+            for (size_t e = 0; e < per; ++e) cmp_pts[s * per + e] = track_compared_joint(spts[s * per + e], svel + s * 2, (int)(e % 3), k);
+        }
+        // step 4: the association
+        const int np = (int)rows.size(), m = (int)cols.size();
+        cost.assign((size_t)np * m, 0.0), sim.assign((size_t)np * m, 0.0f), col.assign(np, -1);
+        for (int r = 0; r < np; ++r)
+            for (int k = 0; k < m; ++k)
+                status[p] |= assoc_pair(pts + (cur0 + rows[r]) * per, &cmp_pts[cols[k] * per], J, boxes + (size_t)(cur0 + rows[r]) * 4,
+                                        &cmp_boxes[(size_t)cols[k] * 4], vars, prm, &cost[(size_t)r * m + k], &sim[(size_t)r * m + k]);
+        if (np > 0 && m > 0 && hrn_assignment(cost.data(), np, m, col.data()) != 0) {   // (cannot happen: every cost is finite)
+            col.assign(np, -1);
+            status[p] |= 2;
+        }
+        // step 5: accepted pairs
+        std::fill(row_of_slot.begin(), row_of_slot.end(), -1);
+        int32_t max_id = std::numeric_limits<int32_t>::min();
+        for (int r = 0; r < np; ++r) {
+            const int c = col[r], i = rows[r];
+            if (c < 0 || !assoc_accepted(sim[(size_t)r * m + c], prm)) continue;
+            const int s = cols[c];
+            row_of_slot[s] = i;
+            ids[cur0 + i] = sid[s], match_row[cur0 + i] = slost[s] == 0 ? srow[s] : -1, slot[cur0 + i] = s;
+            max_id = std::max(max_id, sid[s]);
+            int32_t *box = boxes + (size_t)(cur0 + i) * 4;
+            track_accept_box(box, sbox + (size_t)s * 4, svel + s * 2, slost[s], shits[s], coast, velocity_alpha, prm);
+            for (size_t e = 0; e < per; ++e) {
+                float *q = pts + (cur0 + i) * per + e;
+                if (prm.smoothing != 0.0) *q = assoc_smooth_joint(*q, cmp_pts[s * per + e], prm);
+                spts[s * per + e] = *q;
+            }
+            slost[s] = 0, shits[s] = track_hits(shits[s]), srow[s] = i;
+        }
+        // step 6: unaccepted live slots age or are freed
+        for (int s : cols) {
+            if (row_of_slot[s] >= 0) continue;
+            if (track_retired(slost[s], max_lost)) {
+                sid[s] = -1, slost[s] = 0, shits[s] = 0, srow[s] = -1, svel[s * 2] = svel[s * 2 + 1] = 0.0f;
+                for (int c = 0; c < 4; ++c) sbox[(size_t)s * 4 + c] = 0;
+                for (size_t e = 0; e < per; ++e) spts[s * per + e] = 0.0f;
+            } else {
+                slost[s] += 1, srow[s] = -1;
+            }
+        }
+        // step 7: new people into the free slots, both in ascending order
+        int rank = 0, s = 0;
+        for (int r = 0; r < np; ++r) {
+            const int i = rows[r];
+            if (slot[cur0 + i] != -1) continue;   // accepted
+            const int32_t id = assoc_fresh_id(next_id[p], rank++);
+            ids[cur0 + i] = id;
+            max_id = std::max(max_id, id);
+            while (s < C && sid[s] >= 0) ++s;
+            if (s == C) {
+                status[p] |= kTrackStatusFull;
+                continue;
+            }
+            sid[s] = id, slost[s] = 0, shits[s] = 1, srow[s] = i, svel[s * 2] = svel[s * 2 + 1] = 0.0f;
+            for (int c = 0; c < 4; ++c) sbox[(size_t)s * 4 + c] = boxes[(size_t)(cur0 + i) * 4 + c];
+            for (size_t e = 0; e < per; ++e) spts[s * per + e] = pts[(cur0 + i) * per + e];
+            slot[cur0 + i] = s;
+        }
+        // step 8
+        if (np > 0) next_id[p] = assoc_next_id(next_id[p], max_id);
+    }
+    return 0;
+}
+
+const char *hrn_track_people_last_error(void) { return g_track_people_error.c_str(); }
 
 // the (n, m) costs and blended similarities of ONE problem as both entries compute them (assoc_math.h's assoc_pair: the
 // similarity is NaN where the blend was not finite), for measuring them against the reference's matrices; returns 0 or 7

@@ -1156,6 +1156,51 @@ class NativeHRNet:
                      float(similarity_threshold), float(smoothing_alpha), ids.data_ptr(), match.data_ptr(), status.data_ptr())
         return boxes, pts, ids, match, nxt, status
 
+    # -- person ids through occlusions: the track table ---------------------------------------------------------------------------
+    def new_track_table(self, streams: int = 1, capacity: int = 256, joints: Optional[int] = None) -> dict:
+        """``postproc.new_track_table`` on the engine's GPU: a fresh table for ``track_people`` (``joints`` None: the engine's)"""
+        from .postproc import new_track_table
+
+        host = new_track_table(streams, capacity, self.nof_joints if joints is None else joints)
+        return {name: torch.from_numpy(a).to(self.torch_device, non_blocking=True) for name, a in host.items()}
+
+    def track_people(self, boxes, pts, table, pose_alpha: float = 0.5, similarity_threshold: float = 0.5, smoothing_alpha: float = 0.0,
+                     max_lost: int = 0, coast: bool = False, velocity_alpha: float = 0.5, counts=None):
+        """``postproc.track_people`` on the GPU (``hrn_track_people_dev``: one launch, one block per stream, no host read): one
+        update of a track table that lives in device memory -- ids that survive gaps of up to ``max_lost`` updates, lost people
+        compared where their velocity expects them with ``coast``, the library's zero rows numbered -1.
+
+        ``boxes`` (n, 4) int32 and ``pts`` (n, J, 3) float32 as ``predict_frame`` / ``track_frame`` return them; tensors of the
+        right type on the engine's GPU are used where they lie and smoothed IN PLACE, host arrays are uploaded.  ``table``: what
+        ``new_track_table`` returned -- contiguous tensors on the engine's GPU, updated in place (``next_id`` included).
+        ``counts``: rows per stream, on the host.  Returns ``(boxes, pts, ids, match_row, slot, status)`` on the GPU, bit for bit
+        the host form's."""
+        from .postproc import TRACK_FIELDS, _segments, track_table_shape
+
+        dev = self.torch_device
+        streams, capacity, joints = track_table_shape(table, lambda t: t.shape)
+        for name, _, dtype, _ in TRACK_FIELDS + (("next_id", (), np.int32, 0),):
+            t = table[name]
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != (torch.int32 if dtype is np.int32 else torch.float32) \
+                    or not t.is_contiguous():
+                raise ValueError("%s of the track table must be a contiguous %s tensor on %s" % (name, np.dtype(dtype).name, dev))
+        boxes = device_tensor(boxes, dev, torch.int32, (-1, 4))
+        n = int(boxes.shape[0])
+        pts = device_tensor(as_tensor(pts, np.float32), dev, torch.float32, (-1, joints, 3))
+        if int(pts.shape[0]) != n:
+            raise ValueError("pts must be (n, %d, 3) beside (n, 4) boxes: got %s, %s" % (joints, tuple(boxes.shape), tuple(pts.shape)))
+        cur = _segments(counts, n, "counts")
+        if len(cur) - 1 != streams:
+            raise ValueError("counts names %d streams, the table holds %d" % (len(cur) - 1, streams))
+        ids, match_row, slot = (torch.empty((n,), dtype=torch.int32, device=dev) for _ in range(3))
+        status = torch.zeros((streams,), dtype=torch.int32, device=dev)
+        ptr = lambda t: t.data_ptr() if t.numel() else None   # noqa: E731 -- (an empty tensor has no address to hand over)
+        self._launch("hrn_track_people_dev", streams, cur.ctypes.data, capacity, joints, ptr(boxes), ptr(pts),
+                     *[table[name].data_ptr() for name, *_ in TRACK_FIELDS], table["next_id"].data_ptr(), float(pose_alpha),
+                     float(similarity_threshold), float(smoothing_alpha), int(max_lost), int(coast), float(velocity_alpha), ptr(ids),
+                     ptr(match_row), ptr(slot), status.data_ptr())
+        return boxes, pts, ids, match_row, slot, status
+
     # -- joints over time: One-Euro smoothing and the prediction of the next frame's joints -----------------------------------------
     def filter_poses(self, pts, state=None, match=None, counts=None, prev_counts=None, dt: float = 1 / 30, min_cutoff: float = 1.0,
                      beta: float = 0.007, d_cutoff: float = 1.0, threshold: float = 0.5, lookahead: Optional[float] = None):

@@ -198,7 +198,84 @@ def associate_people(boxes, pts, prev_boxes, prev_pts, prev_ids, next_id, pose_a
     return boxes, pts, ids, match, nxt, status
 
 
-def filter_arguments(pts_shape, state_shapes, match_len, counts, prev_counts, dt, min_cutoff, beta, d_cutoff, threshold, lookahead):
+HRN_MAX_TRACKED = 256
+# the arrays of a track table in the entries' order: name, shape behind (P, C), dtype, value of a fresh table
+TRACK_FIELDS = (("slot_id", (), np.int32, -1), ("slot_lost", (), np.int32, 0), ("slot_hits", (), np.int32, 0), ("slot_row", (), np.int32, -1),
+                ("slot_boxes", (4,), np.int32, 0), ("slot_pts", None, np.float32, 0), ("slot_vel", (2,), np.float32, 0))
+
+
+def new_track_table(streams: int = 1, capacity: int = HRN_MAX_TRACKED, joints: int = 17) -> dict:
+    """a fresh track table for ``track_people``: a dict of numpy arrays, ``slot_id`` / ``slot_lost`` / ``slot_hits`` / ``slot_row``
+    (P, C) int32, ``slot_boxes`` (P, C, 4) int32, ``slot_pts`` (P, C, J, 3) float32, ``slot_vel`` (P, C, 2) float32 and ``next_id``
+    (P,) int32 -- ids and rows -1, everything else 0"""
+    if streams < 0 or not 1 <= capacity <= HRN_MAX_TRACKED or joints < 1:
+        raise ValueError("a track table needs streams >= 0, 1 <= capacity <= %d and joints >= 1, got %d, %d, %d"
+                         % (HRN_MAX_TRACKED, streams, capacity, joints))
+    table = {name: np.full((streams, capacity) + ((joints, 3) if tail is None else tail), fill, dtype)
+             for name, tail, dtype, fill in TRACK_FIELDS}
+    table["next_id"] = np.zeros(streams, np.int32)
+    return table
+
+
+def track_table_shape(table, shape_of) -> tuple:
+    """(P, C, J) of a track table whose arrays answer ``shape_of(array)``; raises on a table that is not one"""
+    try:
+        shapes = {name: tuple(shape_of(table[name])) for name, *_ in TRACK_FIELDS}
+        shapes["next_id"] = tuple(shape_of(table["next_id"]))
+    except (KeyError, TypeError) as exc:
+        raise ValueError("a track table is the dict new_track_table returns: %s" % (exc,))
+    pts = shapes["slot_pts"]
+    if len(pts) != 4 or pts[3] != 3:
+        raise ValueError("slot_pts must be (P, C, J, 3), got %s" % (pts,))
+    P, C, J = pts[:3]
+    want = {name: (P, C) + ((J, 3) if tail is None else tail) for name, tail, _, _ in TRACK_FIELDS}
+    want["next_id"] = (P,)
+    if shapes != want:
+        raise ValueError("the arrays of the track table do not fit together: %s" % (shapes,))
+    return int(P), int(C), int(J)
+
+
+def track_people(boxes, pts, table, pose_alpha=0.5, similarity_threshold=0.5, smoothing_alpha=0., max_lost=0, coast=False,
+                 velocity_alpha=0.5, counts=None):
+    """one update of a track table (``hrn_track_people``, no GPU): the host form of ``NativeHRNet.track_people``, equal to it bit
+    for bit.  ``include/hrnet_mi355.h`` states the update; in short: rows with an empty box are nobody (ids -1); the others are
+    matched against the live tracks -- lost ones for up to ``max_lost`` updates, with ``coast`` where their velocity expects them
+    -- exactly as ``associate_people`` matches two frames; new people take free slots and fresh ids.
+
+    ``boxes`` (n, 4) int32, ``pts`` (n, J, 3) float32 ``(y, x, confidence)``; ``table``: what ``new_track_table`` returned,
+    C-contiguous arrays of its dtypes, updated IN PLACE (``next_id`` included); ``counts``: rows per stream (None: one stream).
+    C-contiguous int32 ``boxes`` / float32 ``pts`` are smoothed in place, anything else is converted first.  Returns
+    ``(boxes, pts, ids, match_row, slot, status)``: ``match_row`` the row the person had in the previous update (what
+    ``filter_poses`` takes as ``match``) or -1, ``slot`` the person's slot or -1, ``status`` per stream (bits 0, 1 as
+    ``associate_people``; bit 2: the table was full and somebody new got no slot)."""
+    streams, capacity, joints = track_table_shape(table, lambda a: a.shape)
+    for name, _, dtype, _ in TRACK_FIELDS + (("next_id", (), np.int32, 0),):
+        a = table[name]
+        if not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError("%s of the track table must be a writable C-contiguous %s array" % (name, np.dtype(dtype).name))
+    boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
+    pts = np.ascontiguousarray(pts, dtype=np.float32)
+    if pts.size == 0 and pts.ndim != 3:
+        pts = pts.reshape(0, joints, 3)
+    n = len(boxes)
+    if pts.ndim != 3 or pts.shape[2] != 3 or len(pts) != n or (n and pts.shape[1] != joints):
+        raise ValueError("pts must be (n, %d, 3) beside (n, 4) boxes: got %s, %s" % (joints, boxes.shape, pts.shape))
+    cur = _segments(counts, n, "counts")
+    if len(cur) - 1 != streams:
+        raise ValueError("counts names %d streams, the table holds %d" % (len(cur) - 1, streams))
+    ids, match_row, slot = (np.empty(n, np.int32) for _ in range(3))
+    status = np.zeros(streams, np.int32)
+    lib = _lib.load()
+    rc = lib.hrn_track_people(streams, cur.ctypes.data, capacity, joints, boxes.ctypes.data, pts.ctypes.data,
+                              *[table[name].ctypes.data for name, *_ in TRACK_FIELDS], table["next_id"].ctypes.data, float(pose_alpha),
+                              float(similarity_threshold), float(smoothing_alpha), int(max_lost), int(coast), float(velocity_alpha),
+                              ids.ctypes.data, match_row.ctypes.data, slot.ctypes.data, status.ctypes.data)
+    if rc:
+        raise ValueError("hrn_track_people: " + lib.hrn_track_people_last_error().decode())
+    return boxes, pts, ids, match_row, slot, status
+
+
+def filter_arguments(pts_shape,state_shapes, match_len, counts, prev_counts, dt, min_cutoff, beta, d_cutoff, threshold, lookahead):
     """what ``filter_poses`` and ``NativeHRNet.filter_poses`` share, from shapes alone: ``(n, m, joints, cur, prev, numbers)`` --
     people on either side, J, the two int32 segment tables and the six numbers in the entries' order (``lookahead=None``: ``dt``)"""
     if len(pts_shape) != 3 or pts_shape[2] != 3:

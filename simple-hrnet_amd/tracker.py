@@ -33,11 +33,23 @@ class PersonTracker:
     ``track_frame(frame, tracker.predicted)``.  ``dt``: seconds since the previous update (None: ``1 / rate``); ``lookahead``
     None: ``dt``.  What the tracker keeps for the next association stays the association's own output.  The prediction starts
     from the raw position; the filtered joints lag on steady motion, the filter's known trade (``beta``).  With ``one_euro=None``
-    no filter call is made and every result is what it is without the option."""
+    no filter call is made and every result is what it is without the option.
+
+    ``max_lost``: None -- everything above, nothing else -- or a number: the tracker then owns a TRACK TABLE (``capacity`` slots per
+    stream, at most 256) and every ``update``, the first included, is one ``track_people`` on it (``include/hrnet_mi355.h``
+    states the update).  A person missing for up to ``max_lost`` updates returns with their id; with ``coast`` a lost person is
+    compared where a constant-velocity model of the box centre (``velocity_alpha``: its exponential smoothing) expects them; a row
+    with an empty box -- ``track_frame``'s lost person, ``pose_nms``' suppressed one -- is nobody: id -1, no new id spent.  The
+    demo's ``next_id = n + 1`` after the first frame is kept (one in-place add on the streams that had somebody), so
+    ``max_lost=0`` on frames without empty boxes gives what ``max_lost=None`` gives.  ``slot`` then holds every row's slot (-1:
+    nobody, or the table was full -- ``status`` bit 2); with ``one_euro`` a person returning from a gap starts a fresh filter
+    state.  ``lost()`` names the tracks that are currently lost."""
 
     def __init__(self, net=None, pose_alpha: float = 0.2, similarity_threshold: float = 0.4, smoothing_alpha: float = 0.1,
-                 one_euro: Optional[dict] = None):
+                 one_euro: Optional[dict] = None, max_lost: Optional[int] = None, coast: bool = False, velocity_alpha: float = 0.5,
+                 capacity: int = postproc.HRN_MAX_TRACKED):
         self.net = net
+        self.max_lost, self.coast, self.velocity_alpha, self.capacity = max_lost, bool(coast), float(velocity_alpha), int(capacity)
         self.pose_alpha, self.similarity_threshold, self.smoothing_alpha = float(pose_alpha), float(similarity_threshold), float(smoothing_alpha)
         self.one_euro = None
         if one_euro is not None:
@@ -51,6 +63,7 @@ class PersonTracker:
     def reset(self):
         self.prev_boxes = self.prev_pts = self.prev_ids = self.prev_counts = self.next_id = self.status = None
         self.filter_state = self.predicted = None
+        self.table = self.slot = None
 
     def _own(self, boxes, pts):
         """copies of this frame's boxes and joints where the tracker works: (n, 4) int32 and (n, J, 3) float32"""
@@ -88,7 +101,22 @@ class PersonTracker:
             raise ValueError("counts must be non-negative and sum to %d people, got %s" % (n, counts.tolist()))
         if self.prev_counts is not None and len(counts) != len(self.prev_counts):
             raise ValueError("%d streams after %d: reset() the tracker first" % (len(counts), len(self.prev_counts)))
-        if self.prev_counts is None:      # live-demo.py:116-118, per stream
+        if self.max_lost is not None and self.table is None and n == 0:   # nobody yet: the table waits for somebody (and their J)
+            ids, self.next_id = self._upload(np.zeros(0, np.int32)), self._upload(np.zeros(len(counts), np.int32))
+        elif self.max_lost is not None:
+            if self.table is None:
+                fresh = postproc.new_track_table if self.net is None else self.net.new_track_table
+                self.table = fresh(len(counts), self.capacity, int(pts.shape[1]))
+            entry = postproc.track_people if self.net is None else self.net.track_people
+            boxes, pts, ids, match, self.slot, self.status = entry(boxes, pts, self.table, self.pose_alpha, self.similarity_threshold,
+                                                                   self.smoothing_alpha, self.max_lost, self.coast, self.velocity_alpha,
+                                                                   counts=counts)
+            self.next_id = self.table["next_id"]
+            if self.prev_counts is None:  # live-demo.py:118: next_id = n + 1 after the first frame, on the streams that had somebody
+                self.next_id += self.next_id > 0
+            if self.prev_counts is None or n == 0:   # (no filter state to follow yet / nobody to follow it)
+                match = None
+        elif self.prev_counts is None:    # live-demo.py:116-118, per stream
             ids = np.concatenate([np.arange(c, dtype=np.int32) for c in counts]) if n else np.zeros(0, np.int32)
             ids, self.next_id = self._upload(ids), self._upload(np.where(counts > 0, counts + 1, 0).astype(np.int32))
         elif n == 0:                      # live-demo.py:125-126: nobody, next_id stays
@@ -106,3 +134,31 @@ class PersonTracker:
                                                                 dt=1.0 / self.rate if dt is None else dt, lookahead=lookahead, **self.one_euro)
         self.prev_boxes, self.prev_pts, self.prev_ids, self.prev_counts = boxes, pts, ids, counts
         return boxes, filtered, ids
+
+    def lost(self):
+        """``(ids, boxes, pts, lost)`` of the tracks that are currently lost (``max_lost`` given): their ids (k,) int32, the boxes
+        (k, 4) int32 and joints (k, J, 3) float32 they are compared at in the next update (with ``coast``: where the velocity
+        expects them; otherwise as last seen) and the updates they have been missing (k,) int32 -- stream after stream, slots in
+        order; tensors on the engine's GPU or numpy arrays.  For drawing ghosts or seeding crops.  The masking reads a count back."""
+        if self.table is None:
+            raise ValueError("lost() needs a tracker with max_lost and at least one update")
+        t = self.table
+        mask = (t["slot_id"] >= 0) & (t["slot_lost"] > 0)
+        lost, vel = t["slot_lost"][mask], t["slot_vel"][mask]
+        boxes, pts = t["slot_boxes"][mask], t["slot_pts"][mask]
+        if self.coast and len(lost):
+            f64, f32, i32 = (np.float64, np.float32, np.int32) if self.net is None else (_torch().float64, _torch().float32, _torch().int32)
+            cast = (lambda a, d: a.astype(d)) if self.net is None else (lambda a, d: a.to(d))
+            k = cast(lost, f64) + 1.0
+            step = cast(vel, f64) * k[:, None]                                  # (k, 2): dy, dx
+            moved = cast(boxes, f64) + step[:, [1, 0, 1, 0]]
+            boxes = cast((np.clip if self.net is None else _torch().clamp)(moved, -2147483648.0, 2147483647.0), i32)
+            pts = pts.copy() if self.net is None else pts.clone()
+            pts[:, :, :2] = cast(cast(pts[:, :, :2], f64) + step[:, None, :], f32)
+        return t["slot_id"][mask], boxes, pts, lost
+
+
+def _torch():
+    import torch
+
+    return torch
