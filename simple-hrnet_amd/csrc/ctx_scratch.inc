@@ -1,6 +1,8 @@
 // hrn_ctx, part 5: what a call keeps on the handle outside the planned workspace -- the guard that serialises calls on different
-// streams, the device arrays a call rewrites, the pinned staging ring their uploads go through, the Gaussian tables of the scoring.
-// Included inside struct hrn_ctx (hrnet_mi355.cpp).
+// streams (CallGuard, CallScope), the device arrays a call rewrites (CallScratch), the pinned staging ring their uploads go through
+// (PinnedImage) and the one frame every entry that keeps such an array runs in (CallFrame: reserve, enter, upload, leave, in that
+// order); then the Gaussian tables of the scoring.  Outside this file an entry meets a CallScratch only through a CallFrame, and a
+// CallScope only on `pass`.  Included inside struct hrn_ctx (hrnet_mi355.cpp).
 
     // One handle, one copy of everything a call writes: calls on DIFFERENT streams must not overlap on it.  Whoever uses the guarded
     // thing records `done` behind its last kernel (leave); a call on another stream than the previous one waits for that event first
@@ -24,7 +26,7 @@
 
     // A device array of the handle that each call rewrites, with its guard.  reserve() before enter(): growing waits on the host
     // until the last user's kernels have read the old array.  A family with several arrays enters the guard of its first one and
-    // names it as `readers` when it reserves the others.
+    // names it as `readers` when it reserves the others (CallFrame, below, does both).
     struct CallScratch : CallGuard {
         char *ptr = nullptr;
         size_t bytes = 0;
@@ -87,17 +89,6 @@
     CallScratch dnms_buf;      // hrn_detector_nms_dev: the candidates of the scoring launch, then the chunk counts and their scan
     CallScratch tmp_table;     // hrn_filter_poses_dev: every person's segment of the previous people, of a call with several problems
 
-    // the pre-path's device scratch for n people: `tmp_bytes` of intermediates (exact: they can be large), n records (and n YUV sources)
-    bool pre_reserve(size_t tmp_bytes, int n, bool yuv) {
-        return pre_tmp.reserve(this, tmp_bytes, tmp_bytes, "hipMalloc(pre-path scratch)") &&
-               pre_params.reserve(this, (size_t)n * sizeof(CropParams), (size_t)n * sizeof(CropParams), "hipMalloc(crop params)", &pre_tmp) &&
-               (!yuv || pre_yuv.reserve(this, (size_t)n * sizeof(YuvSource), (size_t)n * sizeof(YuvSource), "hipMalloc(YUV sources)", &pre_tmp));
-    }
-    // a table of `need` bytes: twice the need, at least `floor`
-    bool table_reserve(CallScratch &t, size_t need, size_t floor, const char *what, CallGuard *readers = nullptr) {
-        return t.reserve(this, need, std::max(need * 2, floor), what, readers);
-    }
-
     // pinned host image of one call's tables (the async uploads read it after the call returned); kPreRing images in rotation,
     // each rewritten only after the upload that last read it has completed
     static constexpr int kPreRing = 4;
@@ -105,37 +96,108 @@
     size_t pre_pin_bytes[kPreRing] = {0, 0, 0, 0};
     hipEvent_t pre_landed[kPreRing] = {nullptr, nullptr, nullptr, nullptr};
     unsigned pre_ring_next = 0;
-    // the next image of the ring, at least `need` bytes, free to be rewritten (nullptr + err on failure); pre_upload(*ring, ...)
-    // sends it
-    char *pre_stage(size_t need, unsigned *ring_out) {
+    struct PinnedImage {
+        char *ptr = nullptr;
+        unsigned slot = 0;   // of the ring
+        size_t bytes = 0;
+        explicit operator bool() const { return ptr != nullptr; }
+        template <class T>
+        T *as(size_t at = 0) const { return (T *)(ptr + at); }
+    };
+    // the next image of the ring, `need` bytes, free to be rewritten (empty + err on failure).  It needs no guard: an entry that
+    // validates while it fills takes it first and may still refuse; CallFrame::upload sends it
+    PinnedImage image(size_t need) {
         const unsigned ring = pre_ring_next++ % kPreRing;
         if (pre_landed[ring]) {
-            if (!hip_ok(hipEventSynchronize(pre_landed[ring]), "hipEventSynchronize")) return nullptr;
+            if (!hip_ok(hipEventSynchronize(pre_landed[ring]), "hipEventSynchronize")) return {};
         } else if (!hip_ok(hipEventCreateWithFlags(&pre_landed[ring], hipEventDisableTiming), "hipEventCreate")) {
-            return nullptr;
+            return {};
         }
         if (need > pre_pin_bytes[ring]) {
             if (pre_pin[ring]) (void)hipHostFree(pre_pin[ring]);
             pre_pin[ring] = nullptr, pre_pin_bytes[ring] = 0;
             const size_t cap = std::max<size_t>(need * 2, 4096);
-            if (!hip_ok(hipHostMalloc((void **)&pre_pin[ring], cap, hipHostMallocDefault), "hipHostMalloc(crop params)")) return nullptr;
+            if (!hip_ok(hipHostMalloc((void **)&pre_pin[ring], cap, hipHostMallocDefault), "hipHostMalloc(crop params)")) return {};
             pre_pin_bytes[ring] = cap;
         }
-        *ring_out = ring;
-        return pre_pin[ring];
+        return {pre_pin[ring], ring, need};
     }
-    // pieces of image `ring` to the device on s, then the event that lets the image be rewritten (a null destination: skipped)
-    struct PreCopy {
-        void *dst;
-        const void *src;
-        size_t bytes;
+
+    // One call on the arrays of one family.  The constructor reserves every array (a grow waits on the host for the last reader,
+    // so it comes first), then enters the guard of the first one on s; the others are reserved against that guard.  Only an entered
+    // frame hands out device pointers or queues uploads, and it leaves as CallScope does: leave() on success, the destructor on
+    // every other exit.  A first need of 0 bytes -- the one problem that travels in the kernel arguments -- reserves, guards and
+    // uploads nothing and costs no HIP call.
+    struct Want {
+        CallScratch *array;
+        size_t need, cap;   // cap: what a grow allocates -- `need` (exact), twice(need, floor), or a rule of the entry's own
         const char *what;
     };
-    bool pre_upload(unsigned ring, hipStream_t s, std::initializer_list<PreCopy> copies) {
-        for (const PreCopy &c : copies)
-            if (c.dst && !hip_ok(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyHostToDevice, s), c.what)) return false;
-        return hip_ok(hipEventRecord(pre_landed[ring], s), "hipEventRecord");
-    }
+    static size_t twice(size_t need, size_t floor) { return std::max(need * 2, floor); }
+    struct CallFrame {
+        hrn_ctx *h;
+        hipStream_t s;
+        CallScratch *first;
+        bool reserved;
+        CallScope scope;
+        bool failed = false;   // an upload
+        CallFrame(hrn_ctx *h_, hipStream_t s_, std::initializer_list<Want> wants)
+            : h(h_), s(s_), first(wants.begin()->array), reserved(reserve(h_, wants)),
+              scope(h_, reserved && wants.begin()->need ? first : nullptr, s_) {}
+        static bool reserve(hrn_ctx *h, std::initializer_list<Want> wants) {
+            if (!wants.begin()->need) return true;
+            for (const Want &w : wants)
+                if (!w.array->reserve(h, w.need, w.cap, w.what, wants.begin()->array)) return false;
+            return true;
+        }
+        bool guarded() const { return scope.g != nullptr; }
+        bool ok() const { return reserved && scope.entered && !failed; }   // false: the entry returns 6
+        bool leave() { return ok() && scope.leave(); }
+        template <class T = char>
+        T *dev(const CallScratch &a, size_t at = 0) const { return ok() ? (T *)(a.ptr + at) : nullptr; }
+        template <class T = char>
+        T *dev(size_t at = 0) const { return dev<T>(*first, at); }
+        // pieces of `img` to the device on s, then the event that lets the image be rewritten (a null destination: skipped; a
+        // destination may be the caller's own)
+        struct Piece {
+            void *dst;
+            const void *src;
+            size_t bytes;
+            const char *what;
+        };
+        bool upload(const PinnedImage &img, std::initializer_list<Piece> pieces) {
+            if (!ok()) return false;
+            for (const Piece &p : pieces)
+                if (p.dst && !h->hip_ok(hipMemcpyAsync(p.dst, p.src, p.bytes, hipMemcpyHostToDevice, s), p.what)) return !(failed = true);
+            return !(failed = !h->hip_ok(hipEventRecord(h->pre_landed[img.slot], s), "hipEventRecord"));
+        }
+        // the first `bytes` of `img` into the first array at `at`; where they lie, or nullptr (not guarded, or failed: ok())
+        template <class T = char>
+        T *upload(const PinnedImage &img, size_t bytes, const char *what, size_t at = 0) {
+            return guarded() && upload(img, {{first->ptr + at, img.ptr, bytes, what}}) ? (T *)(first->ptr + at) : nullptr;
+        }
+        // `count` records through an image that fill(T *) writes: the table on the device, or nullptr -- not guarded (the one
+        // record goes into the kernel arguments), or failed (ok())
+        template <class T, class Fill>
+        const T *table(size_t count, const char *what, const Fill &fill) {
+            if (!guarded() || !ok()) return nullptr;
+            const PinnedImage img = h->image(count * sizeof(T));
+            if (!img) return failed = true, nullptr;
+            fill(img.as<T>());
+            return upload<T>(img, count * sizeof(T), what);
+        }
+        template <class T>
+        const T *table(const T *records, size_t count, const char *what) {
+            return table<T>(count, what, [&](T *out) { memcpy(out, records, count * sizeof(T)); });
+        }
+    };
+    // the pre-path's frame for n people: `tmp_bytes` of intermediates (exact: they can be large), n records (and n YUV sources)
+    struct PreFrame : CallFrame {
+        PreFrame(hrn_ctx *h, size_t tmp_bytes, size_t n, bool yuv, hipStream_t s)
+            : CallFrame(h, s, {{&h->pre_tmp, tmp_bytes, tmp_bytes, "hipMalloc(pre-path scratch)"},
+                               {&h->pre_params, n * sizeof(CropParams), n * sizeof(CropParams), "hipMalloc(crop params)"},
+                               {&h->pre_yuv, yuv ? n * sizeof(YuvSource) : 0, n * sizeof(YuvSource), "hipMalloc(YUV sources)"}}) {}
+    };
 
     // scoring: the Gaussian tables g[d2] = float32(exp(-d2 / (2 sigma^2))), d2 = 0 .. 2 t^2, by t = 3 sigma
     std::map<int, float *> score_tables;

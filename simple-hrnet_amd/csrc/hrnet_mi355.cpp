@@ -177,6 +177,17 @@ struct hrn_ctx {
 // ====================================================================================================
 namespace {
 using CallScope = hrn_ctx::CallScope;
+using CallFrame = hrn_ctx::CallFrame;
+using PreFrame = hrn_ctx::PreFrame;
+using PinnedImage = hrn_ctx::PinnedImage;
+
+// The refusals of an entry whose text is "<entry>: <fault>", in the newer entries' order: the arguments (`fault`, or nullptr: they
+// need no device, so a plan-only handle judges them too), then the handle; true + err: the entry returns 7.
+bool refused(hrn_ctx *h, const char *entry, const char *fault) {
+    if (!fault) return h->refuse_plan_only();
+    h->err = std::string(entry) + ": " + fault;
+    return true;
+}
 
 // The loop of every forward entry: the device, then (n > 0) the scratch heat-maps if asked for, one CallScope on the pass guard and
 // pass(off, nb) for each micro-batch of at most max_batch crops (false: the entry returns 8).
@@ -486,11 +497,11 @@ int preprocess_people(hrn_handle h, const hrn_frame *frames, const hrn_yuv_frame
     // each reused only once the upload that read it last has completed
     const size_t cp_bytes = ((size_t)n * sizeof(CropParams) + 63) / 64 * 64, box_bytes = (size_t)n * 16;
     const size_t need = cp_bytes + box_bytes + (yframes ? (size_t)n * sizeof(YuvSource) : 0);
-    unsigned ring = 0;
-    if (!h->pre_stage(need, &ring)) return 6;
-    CropParams *cps = (CropParams *)h->pre_pin[ring];
-    int32_t *boxes = (int32_t *)(h->pre_pin[ring] + cp_bytes);
-    YuvSource *srcs = (YuvSource *)(h->pre_pin[ring] + cp_bytes + box_bytes);
+    const PinnedImage img = h->image(need);
+    if (!img) return 6;
+    CropParams *cps = img.as<CropParams>();
+    int32_t *boxes = img.as<int32_t>(cp_bytes);
+    YuvSource *srcs = img.as<YuvSource>(cp_bytes + box_bytes);
     size_t tmp_bytes = 0;
     int max_h_pad = 0;
     for (int i = 0; i < n; ++i) {
@@ -505,20 +516,18 @@ int preprocess_people(hrn_handle h, const hrn_frame *frames, const hrn_yuv_frame
         tmp_bytes += ((size_t)cp.h_pad * W * 3 + 255) / 256 * 256;
         if (cp.h_pad > max_h_pad) max_h_pad = cp.h_pad;
     }
-    if (!h->pre_reserve(tmp_bytes, n, yframes != nullptr)) return 6;
-    CallScope scope(h, &h->pre_tmp, s);
-    if (!scope.entered) return 6;
-    CropParams *params = h->pre_params.as<CropParams>();
-    YuvSource *yuv = yframes ? h->pre_yuv.as<YuvSource>() : nullptr;
-    if (!h->pre_upload(ring, s, {{yuv, srcs, (size_t)n * sizeof(YuvSource), "hipMemcpyAsync(YUV sources)"},
-                                 {params, cps, (size_t)n * sizeof(CropParams), "hipMemcpyAsync(crop params)"},
-                                 {boxes_dev, boxes, (size_t)n * 16, "hipMemcpyAsync(boxes)"}}))
+    PreFrame frame(h, tmp_bytes, n, yframes != nullptr, s);
+    CropParams *params = frame.dev<CropParams>(h->pre_params);
+    YuvSource *yuv = yframes ? frame.dev<YuvSource>(h->pre_yuv) : nullptr;
+    if (!frame.upload(img, {{yuv, srcs, (size_t)n * sizeof(YuvSource), "hipMemcpyAsync(YUV sources)"},
+                            {params, cps, (size_t)n * sizeof(CropParams), "hipMemcpyAsync(crop params)"},
+                            {boxes_dev, boxes, (size_t)n * 16, "hipMemcpyAsync(boxes)"}}))
         return 6;
     if (boxes_host) memcpy(boxes_host, boxes, (size_t)n * 16);
-    const hipError_t e = yframes ? launch_prepath_yuv(params, yuv, n, max_h_pad, h->pre_tmp.as<unsigned char>(), images_dev, H, W, s)
-                                 : launch_prepath(params, n, max_h_pad, h->pre_tmp.as<unsigned char>(), images_dev, H, W, s);
+    const hipError_t e = yframes ? launch_prepath_yuv(params, yuv, n, max_h_pad, frame.dev<unsigned char>(), images_dev, H, W, s)
+                                 : launch_prepath(params, n, max_h_pad, frame.dev<unsigned char>(), images_dev, H, W, s);
     if (!h->hip_ok(e, "pre-path launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 }  // namespace
 
@@ -668,35 +677,30 @@ int preprocess_people_dev(hrn_handle h, const hrn_frame *frames, const hrn_yuv_f
     const size_t slot = ((size_t)rows * W * 3 + 255) / 256 * 256;
     // (fidx) the frame table and everybody's entry of it
     const size_t table_bytes = fidx ? (size_t)nframes * sizeof(TrackFrame) : 0, need = fidx ? table_bytes + (size_t)n * sizeof(int32_t) : 0;
-    if (!h->pre_reserve((size_t)n * slot, n, yframes != nullptr) || !h->table_reserve(h->trk_table, need, 4096, "hipMalloc(tracking table)"))
-        return 6;
-    CallScope scope(h, &h->pre_tmp, s), table(h, fidx ? &h->trk_table : nullptr, s);   // (the table's is left behind the launch that reads it)
-    if (!scope.entered || !table.entered) return 6;
-    CropParams *params = h->pre_params.as<CropParams>();
-    YuvSource *yuv = h->pre_yuv.as<YuvSource>();
+    PreFrame frame(h, (size_t)n * slot, n, yframes != nullptr, s);
+    // (the table's guard is left behind the launch that reads it)
+    CallFrame table(h, s, {{&h->trk_table, need, hrn_ctx::twice(need, 4096), "hipMalloc(tracking table)"}});
+    CropParams *params = frame.dev<CropParams>(h->pre_params);
+    YuvSource *yuv = frame.dev<YuvSource>(h->pre_yuv);
     CropRecordArgs a{};
     a.dets = dets_dev, a.det_stride = det_stride, a.n = n, a.H = H, a.W = W, a.variant = variant, a.yuv = yframes ? 1 : 0;
     a.slot_bytes = (long long)slot;
     a.crops = params, a.srcs = yuv, a.boxes = boxes_dev, a.status = status_dev;
-    if (fidx) {   // through the pinned ring
-        unsigned ring = 0;
-        char *pin = h->pre_stage(need, &ring);
-        if (!pin) return 6;
+    const char *dev = table.table<char>(need, "hipMemcpyAsync(tracking table)", [&](char *pin) {
         std::vector<char> used((size_t)nframes, 0);
         for (int i = 0; i < n; ++i) used[fidx[i]] = 1;
         for (int f = 0; f < nframes; ++f) ((TrackFrame *)pin)[f] = used[f] ? entry(f) : TrackFrame{};
         memcpy(pin + table_bytes, fidx, (size_t)n * sizeof(int32_t));
-        if (!h->pre_upload(ring, s, {{h->trk_table.ptr, pin, need, "hipMemcpyAsync(tracking table)"}})) return 6;
-        a.frames = h->trk_table.as<const TrackFrame>(), a.frame_index = (const int *)(h->trk_table.ptr + table_bytes);
-    } else {
-        a.frame0 = entry(0);
-    }
+    });
+    if (!frame.ok() || !table.ok()) return 6;
+    if (dev) a.frames = (const TrackFrame *)dev, a.frame_index = (const int *)(dev + table_bytes);
+    else a.frame0 = entry(0);
     if (!h->hip_ok(launch_crop_records(a, s), "crop records launch")) return 8;
     if (!table.leave()) return 6;
-    const hipError_t e = yframes ? launch_prepath_yuv(params, yuv, n, (int)rows, h->pre_tmp.as<unsigned char>(), images_dev, H, W, s)
-                                 : launch_prepath(params, n, (int)rows, h->pre_tmp.as<unsigned char>(), images_dev, H, W, s);
+    const hipError_t e = yframes ? launch_prepath_yuv(params, yuv, n, (int)rows, frame.dev<unsigned char>(), images_dev, H, W, s)
+                                 : launch_prepath(params, n, (int)rows, frame.dev<unsigned char>(), images_dev, H, W, s);
     if (!h->hip_ok(e, "pre-path launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 }  // namespace
 
@@ -716,11 +720,8 @@ int hrn_boxes_from_poses(hrn_handle h, const float *pts_dev, int n, int J, const
                          float threshold, int min_joints, double scale, double min_side, float *dets_dev, void *stream) {
     if (!h) return 1;
     std::string fault;
-    if (pose_box_fault(pts_dev, n, J, frame_hw_host, per_person_hw, min_joints, scale, min_side, dets_dev, fault)) {
-        h->err = "hrn_boxes_from_poses: " + fault;
-        return 7;
-    }
-    if (h->refuse_plan_only()) return 7;
+    const bool bad = pose_box_fault(pts_dev, n, J, frame_hw_host, per_person_hw, min_joints, scale, min_side, dets_dev, fault);
+    if (refused(h, "hrn_boxes_from_poses", bad ? fault.c_str() : nullptr)) return 7;
     if (n == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
@@ -728,21 +729,12 @@ int hrn_boxes_from_poses(hrn_handle h, const float *pts_dev, int n, int J, const
     a.pts = pts_dev, a.n = n, a.J = J, a.threshold = threshold, a.min_joints = min_joints, a.scale = scale, a.min_side = min_side;
     a.dets = dets_dev;
     const size_t need = per_person_hw ? (size_t)n * 2 * sizeof(int32_t) : 0;   // a frame size per person: a table through the pinned ring
-    if (!h->table_reserve(h->trk_table, need, 4096, "hipMalloc(tracking table)")) return 6;
-    CallScope scope(h, per_person_hw ? &h->trk_table : nullptr, s);
-    if (!scope.entered) return 6;
-    if (per_person_hw) {
-        unsigned ring = 0;
-        char *pin = h->pre_stage(need, &ring);
-        if (!pin) return 6;
-        memcpy(pin, frame_hw_host, need);
-        if (!h->pre_upload(ring, s, {{h->trk_table.ptr, pin, need, "hipMemcpyAsync(tracking table)"}})) return 6;
-        a.frame_hw = h->trk_table.as<const int>();
-    } else {
-        a.frame_h = frame_hw_host[0], a.frame_w = frame_hw_host[1];
-    }
+    CallFrame frame(h, s, {{&h->trk_table, need, hrn_ctx::twice(need, 4096), "hipMalloc(tracking table)"}});
+    a.frame_hw = frame.table<int>(frame_hw_host, (size_t)n * 2, "hipMemcpyAsync(tracking table)");
+    if (!frame.ok()) return 6;
+    if (!a.frame_hw) a.frame_h = frame_hw_host[0], a.frame_w = frame_hw_host[1];
     if (!h->hip_ok(launch_pose_boxes(a, s), "pose boxes launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 // hrn_preprocess_frames with the detections on the device: its argument checks and texts (minus the per-detection ones, which
@@ -876,9 +868,9 @@ int draw_poses(const char *entry, hrn_handle h, const hrn_canvas *canvases_host,
                  off_bone = off_pframe + align16((size_t)n * 4), off_point = off_bone + align16((size_t)n * 4),
                  off_skel = off_point + align16((size_t)Cp * 4), off_palette = off_skel + align16((size_t)std::max(K, 1) * 4),
                  table_bytes = off_palette + (ids_on_device ? align16((size_t)Cb * 4) : 0);   // (host ids: the table ends at off_palette)
-    unsigned ring = 0;
-    char *pin = h->pre_stage(table_bytes, &ring);
-    if (!pin) return 6;
+    const PinnedImage img = h->image(table_bytes);
+    if (!img) return 6;
+    char *pin = img.ptr;
     DrawFrame *frames = (DrawFrame *)pin;
     int *order = (int *)(pin + off_order), *pframe = (int *)(pin + off_pframe);
     unsigned *bone = (unsigned *)(pin + off_bone), *point = (unsigned *)(pin + off_point), *skel = (unsigned *)(pin + off_skel);
@@ -910,13 +902,10 @@ int draw_poses(const char *entry, hrn_handle h, const hrn_canvas *canvases_host,
 
     const size_t off_live = align16((size_t)n * J * sizeof(short2)), off_box = off_live + align16((size_t)n * (kMaxJoints / 32) * 4),
                  rec_bytes = off_box + (size_t)n * sizeof(int4);
-    if (!h->table_reserve(h->draw_table, table_bytes, 4096, "hipMalloc(draw table)") ||
-        !h->table_reserve(h->draw_records, rec_bytes, 4096, "hipMalloc(draw records)", &h->draw_table))
-        return 6;
-    CallScope scope(h, &h->draw_table, s);
-    if (!scope.entered) return 6;
-    char *table = h->draw_table.ptr, *records = h->draw_records.ptr;
-    if (!h->pre_upload(ring, s, {{table, pin, table_bytes, "hipMemcpyAsync(draw table)"}})) return 6;
+    CallFrame frame(h, s, {{&h->draw_table, table_bytes, hrn_ctx::twice(table_bytes, 4096), "hipMalloc(draw table)"},
+                           {&h->draw_records, rec_bytes, hrn_ctx::twice(rec_bytes, 4096), "hipMalloc(draw records)"}});
+    char *table = frame.upload(img, table_bytes, "hipMemcpyAsync(draw table)"), *records = frame.dev(h->draw_records);
+    if (!table) return 6;
     if (ids_on_device && !h->hip_ok(launch_bone_ids(person_index_dev, n, (const unsigned *)(table + off_palette), Cb,
                                                     (unsigned *)(table + off_bone), s), "bone colour launch"))
         return 8;
@@ -928,7 +917,7 @@ int draw_poses(const char *entry, hrn_handle h, const hrn_canvas *canvases_host,
     a.point_colour = (const unsigned *)(table + off_point), a.skeleton = (const unsigned *)(table + off_skel);
     a.xy = (short2 *)records, a.live = (unsigned *)(records + off_live), a.box = (int4 *)(records + off_box);
     if (!h->hip_ok(launch_draw(a, s), "draw launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 }  // namespace
 
@@ -955,13 +944,10 @@ int hrn_associate_people_dev(hrn_handle h, int P, const int32_t *cur_start_host,
                              const int32_t *prev_ids_dev, int32_t *next_id_dev, double pose_alpha, double similarity_threshold,
                              double smoothing_alpha, int32_t *ids_dev, int32_t *match_dev, int32_t *status_dev, void *stream) {
     if (!h) return 1;
-    if (const char *fault = assoc_fault(P, cur_start_host, prev_start_host, J, boxes_dev, pts_dev, prev_boxes_dev, prev_pts_dev,
-                                        prev_ids_dev, next_id_dev, pose_alpha, similarity_threshold, smoothing_alpha, ids_dev,
-                                        match_dev, status_dev)) {
-        h->err = std::string("hrn_associate_people_dev: ") + fault;
+    if (refused(h, "hrn_associate_people_dev",
+                assoc_fault(P, cur_start_host, prev_start_host, J, boxes_dev, pts_dev, prev_boxes_dev, prev_pts_dev, prev_ids_dev, next_id_dev,
+                            pose_alpha, similarity_threshold, smoothing_alpha, ids_dev, match_dev, status_dev)))
         return 7;
-    }
-    if (h->refuse_plan_only()) return 7;
     if (P == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
@@ -976,26 +962,17 @@ int hrn_associate_people_dev(hrn_handle h, int P, const int32_t *cur_start_host,
         q.scratch = (long long)need;
         need += ((size_t)q.n * q.m * 12 + 15) / 16 * 16;
     }
-    if (!h->table_reserve(h->assoc_buf, need, 65536, "hipMalloc(association scratch)")) return 6;
-    CallScope scope(h, &h->assoc_buf, s);
-    if (!scope.entered) return 6;
+    CallFrame frame(h, s, {{&h->assoc_buf, need, hrn_ctx::twice(need, 65536), "hipMalloc(association scratch)"}});
     AssocArgs a{};
     a.P = P, a.J = J, a.no_assign = h->assoc_no_assign ? 1 : 0;
-    if (P > 1) {   // the table through the pinned ring
-        unsigned ring = 0;
-        char *pin = h->pre_stage(table_bytes, &ring);
-        if (!pin) return 6;
-        memcpy(pin, probs.data(), (size_t)P * sizeof(AssocProblem));
-        if (!h->pre_upload(ring, s, {{h->assoc_buf.ptr, pin, (size_t)P * sizeof(AssocProblem), "hipMemcpyAsync(association table)"}})) return 6;
-        a.table = h->assoc_buf.as<const AssocProblem>();
-    } else {
-        a.one = probs[0];
-    }
+    if (P > 1) a.table = frame.table(probs.data(), (size_t)P, "hipMemcpyAsync(association table)");
+    else a.one = probs[0];
+    if (!frame.ok()) return 6;
     a.boxes = boxes_dev, a.pts = pts_dev, a.prev_boxes = prev_boxes_dev, a.prev_pts = prev_pts_dev, a.prev_ids = prev_ids_dev;
     a.next_id = next_id_dev, a.pose_alpha = pose_alpha, a.similarity_threshold = similarity_threshold, a.smoothing_alpha = smoothing_alpha;
-    a.ids = ids_dev, a.match = match_dev, a.status = status_dev, a.scratch = h->assoc_buf.ptr;
+    a.ids = ids_dev, a.match = match_dev, a.status = status_dev, a.scratch = frame.dev();
     if (!h->hip_ok(launch_assoc(a, s), "association launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 // one update of P per-stream track tables in one launch (tracks.hip); the arguments are judged first (tracks_math.h's track_fault,
@@ -1007,13 +984,11 @@ int hrn_track_people_dev(hrn_handle h, int P, const int32_t *cur_start_host, int
                          double similarity_threshold, double smoothing_alpha, int max_lost, int coast, double velocity_alpha,
                          int32_t *ids_dev, int32_t *match_row_dev, int32_t *slot_dev, int32_t *status_dev, void *stream) {
     if (!h) return 1;
-    if (const char *fault = track_fault(P, cur_start_host, C, J, boxes_dev, pts_dev, slot_id_dev, slot_lost_dev, slot_hits_dev, slot_row_dev,
-                                        slot_boxes_dev, slot_pts_dev, slot_vel_dev, next_id_dev, pose_alpha, similarity_threshold,
-                                        smoothing_alpha, max_lost, coast, velocity_alpha, ids_dev, match_row_dev, slot_dev, status_dev)) {
-        h->err = std::string("hrn_track_people_dev: ") + fault;
+    if (refused(h, "hrn_track_people_dev",
+                track_fault(P, cur_start_host, C, J, boxes_dev, pts_dev, slot_id_dev, slot_lost_dev, slot_hits_dev, slot_row_dev, slot_boxes_dev,
+                            slot_pts_dev, slot_vel_dev, next_id_dev, pose_alpha, similarity_threshold, smoothing_alpha, max_lost, coast,
+                            velocity_alpha, ids_dev, match_row_dev, slot_dev, status_dev)))
         return 7;
-    }
-    if (h->refuse_plan_only()) return 7;
     if (P == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
@@ -1028,28 +1003,19 @@ int hrn_track_people_dev(hrn_handle h, int P, const int32_t *cur_start_host, int
         q.scratch = (long long)need;
         need += ((size_t)q.n * C * 12 + compared + 15) / 16 * 16;
     }
-    if (need && !h->table_reserve(h->tracks_buf, need, 65536, "hipMalloc(track table scratch)")) return 6;
-    CallScope scope(h, &h->tracks_buf, s);
-    if (!scope.entered) return 6;
+    CallFrame frame(h, s, {{&h->tracks_buf, need, hrn_ctx::twice(need, 65536), "hipMalloc(track table scratch)"}});
     TracksArgs a{};
     a.P = P, a.C = C, a.J = J, a.max_lost = max_lost, a.coast = coast;
-    if (P > 1) {   // the table through the pinned ring
-        unsigned ring = 0;
-        char *pin = h->pre_stage(table_bytes, &ring);
-        if (!pin) return 6;
-        memcpy(pin, probs.data(), (size_t)P * sizeof(TrackProblem));
-        if (!h->pre_upload(ring, s, {{h->tracks_buf.ptr, pin, (size_t)P * sizeof(TrackProblem), "hipMemcpyAsync(track stream table)"}})) return 6;
-        a.table = h->tracks_buf.as<const TrackProblem>();
-    } else {
-        a.one = probs[0];
-    }
+    if (P > 1) a.table = frame.table(probs.data(), (size_t)P, "hipMemcpyAsync(track stream table)");
+    else a.one = probs[0];
+    if (!frame.ok()) return 6;
     a.boxes = boxes_dev, a.pts = pts_dev, a.slot_id = slot_id_dev, a.slot_lost = slot_lost_dev, a.slot_hits = slot_hits_dev;
     a.slot_row = slot_row_dev, a.slot_boxes = slot_boxes_dev, a.slot_pts = slot_pts_dev, a.slot_vel = slot_vel_dev, a.next_id = next_id_dev;
     a.pose_alpha = pose_alpha, a.similarity_threshold = similarity_threshold, a.smoothing_alpha = smoothing_alpha;
     a.velocity_alpha = velocity_alpha;
-    a.ids = ids_dev, a.match_row = match_row_dev, a.slot = slot_dev, a.status = status_dev, a.scratch = h->tracks_buf.ptr;
+    a.ids = ids_dev, a.match_row = match_row_dev, a.slot = slot_dev, a.status = status_dev, a.scratch = frame.dev();
     if (!h->hip_ok(launch_tracks(a, s), "track table launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 // rescoring and OKS NMS for P problems in one launch (pose_nms.hip); the arguments are judged first (pose_nms_math.h's
@@ -1060,36 +1026,26 @@ int hrn_pose_nms_dev(hrn_handle h, int P, const int32_t *start_host, int J, int 
                      int32_t *keep_dev, int32_t *num_dev, double *scores_out_dev, int32_t *suppressor_dev, int32_t *status_dev,
                      void *stream) {
     if (!h) return 1;
-    if (const char *fault = pose_nms_fault(P, start_host, J, flags, kpts_dev, areas_dev, scores_dev, thresh, sigmas_dev, keep_dev, num_dev,
-                                           scores_out_dev, suppressor_dev, status_dev)) {
-        h->err = std::string("hrn_pose_nms_dev: ") + fault;
+    if (refused(h, "hrn_pose_nms_dev", pose_nms_fault(P, start_host, J, flags, kpts_dev, areas_dev, scores_dev, thresh, sigmas_dev, keep_dev,
+                                                      num_dev, scores_out_dev, suppressor_dev, status_dev)))
         return 7;
-    }
-    if (h->refuse_plan_only()) return 7;
     if (P == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
-    const size_t table_bytes = (size_t)P * sizeof(PoseNmsProblem);
-    if (P > 1 && !h->table_reserve(h->nms_table, table_bytes, 4096, "hipMalloc(pose NMS table)")) return 6;
-    CallScope scope(h, P > 1 ? &h->nms_table : nullptr, s);
-    if (!scope.entered) return 6;
+    const size_t table_bytes = P > 1 ? (size_t)P * sizeof(PoseNmsProblem) : 0;
+    CallFrame frame(h, s, {{&h->nms_table, table_bytes, hrn_ctx::twice(table_bytes, 4096), "hipMalloc(pose NMS table)"}});
     PoseNmsArgs a{};
     a.P = P, a.J = J, a.flags = flags;
-    if (P > 1) {   // the table through the pinned ring
-        unsigned ring = 0;
-        PoseNmsProblem *pin = (PoseNmsProblem *)h->pre_stage(table_bytes, &ring);
-        if (!pin) return 6;
-        for (int p = 0; p < P; ++p) pin[p].first = start_host[p], pin[p].n = start_host[p + 1] - start_host[p];
-        if (!h->pre_upload(ring, s, {{h->nms_table.ptr, pin, table_bytes, "hipMemcpyAsync(pose NMS table)"}})) return 6;
-        a.table = h->nms_table.as<const PoseNmsProblem>();
-    } else {
-        a.one.first = start_host[0], a.one.n = start_host[1] - start_host[0];
-    }
+    a.table = frame.table<PoseNmsProblem>((size_t)P, "hipMemcpyAsync(pose NMS table)", [&](PoseNmsProblem *t) {
+        for (int p = 0; p < P; ++p) t[p].first = start_host[p], t[p].n = start_host[p + 1] - start_host[p];
+    });
+    if (!frame.ok()) return 6;
+    if (!a.table) a.one.first = start_host[0], a.one.n = start_host[1] - start_host[0];
     a.kpts = kpts_dev, a.areas = areas_dev, a.scores = scores_dev, a.sigmas = sigmas_dev;
     a.thresh = thresh, a.in_vis_thre = in_vis_thre, a.rescore_thre = rescore_thre;
     a.keep = keep_dev, a.num = num_dev, a.scores_out = scores_out_dev, a.suppressor = suppressor_dev, a.status = status_dev;
     if (!h->hip_ok(launch_pose_nms(a, s), "pose NMS launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 // detector NMS for B images in two launches (detector_nms.hip); the arguments are judged first (detector_nms_math.h's dnms_fault,
@@ -1099,12 +1055,9 @@ int hrn_detector_nms_dev(hrn_handle h, const void *pred_dev, int dtype, int B, i
                          float iou_thres, int max_candidates, int max_det, float *rows_dev, int32_t *index_dev, int32_t *counts_dev,
                          int32_t *status_dev, void *stream) {
     if (!h) return 1;
-    if (const char *fault = dnms_fault(pred_dev, dtype, B, N, C, rule, flags, conf_thres, iou_thres, max_candidates, max_det, rows_dev,
-                                       index_dev, counts_dev, status_dev)) {
-        h->err = std::string("hrn_detector_nms_dev: ") + fault;
+    if (refused(h, "hrn_detector_nms_dev", dnms_fault(pred_dev, dtype, B, N, C, rule, flags, conf_thres, iou_thres, max_candidates, max_det,
+                                                      rows_dev, index_dev, counts_dev, status_dev)))
         return 7;
-    }
-    if (h->refuse_plan_only()) return 7;
     if (B == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
@@ -1112,16 +1065,14 @@ int hrn_detector_nms_dev(hrn_handle h, const void *pred_dev, int dtype, int B, i
     a.nchunks = (N + kDnmsChunk - 1) / kDnmsChunk;
     const size_t cand_bytes = ((size_t)B * N * sizeof(DnmsCand) + 255) / 256 * 256;
     const size_t info_bytes = ((size_t)B * a.nchunks * sizeof(int) + 255) / 256 * 256, need = cand_bytes + 2 * info_bytes;
-    if (need && !h->table_reserve(h->dnms_buf, need, 1 << 20, "hipMalloc(detector NMS scratch)")) return 6;
-    CallScope scope(h, need ? &h->dnms_buf : nullptr, s);
-    if (!scope.entered) return 6;
+    CallFrame frame(h, s, {{&h->dnms_buf, need, hrn_ctx::twice(need, 1 << 20), "hipMalloc(detector NMS scratch)"}});
+    if (!frame.ok()) return 6;
     a.pred = pred_dev, a.dtype = dtype, a.B = B, a.N = N, a.C = C, a.rule = rule, a.flags = flags;
     a.max_candidates = max_candidates, a.max_det = max_det, a.conf_thres = conf_thres, a.iou_thres = iou_thres;
-    a.cand = h->dnms_buf.as<DnmsCand>(), a.chunk_info = (int *)(h->dnms_buf.ptr + cand_bytes);
-    a.chunk_off = (int *)(h->dnms_buf.ptr + cand_bytes + info_bytes);
+    a.cand = frame.dev<DnmsCand>(), a.chunk_info = frame.dev<int>(cand_bytes), a.chunk_off = frame.dev<int>(cand_bytes + info_bytes);
     a.rows = rows_dev, a.index = index_dev, a.counts = counts_dev, a.status = status_dev;
     if (!h->hip_ok(launch_detector_nms(a, s), "detector NMS launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 // COCO keypoint AP / AR of an evaluation set (keypoint_eval.hip); the arguments are judged first (keypoint_eval_math.h's
@@ -1133,38 +1084,29 @@ int hrn_keypoint_eval_dev(hrn_handle h, int P, const int32_t *dt_start_host, con
                           double *precision_dev, double *recall_dev, int32_t *slot_person_dev, double *slot_score_dev,
                           int32_t *dt_match_dev, uint8_t *dt_ignore_dev, int32_t *npig_dev, int32_t *status_dev, void *stream) {
     if (!h) return 1;
-    if (const char *fault = keypoint_eval_fault(P, dt_start_host, gt_start_host, J, dt_kpts_dev, dt_scores_dev, gt_kpts_dev, gt_area_dev,
-                                                gt_bbox_dev, gt_iscrowd_dev, sigmas_dev, stats_dev, precision_dev, recall_dev,
-                                                slot_person_dev, slot_score_dev, dt_match_dev, dt_ignore_dev, npig_dev, status_dev)) {
-        h->err = std::string("hrn_keypoint_eval_dev: ") + fault;
+    if (refused(h, "hrn_keypoint_eval_dev",
+                keypoint_eval_fault(P, dt_start_host, gt_start_host, J, dt_kpts_dev, dt_scores_dev, gt_kpts_dev, gt_area_dev, gt_bbox_dev,
+                                    gt_iscrowd_dev, sigmas_dev, stats_dev, precision_dev, recall_dev, slot_person_dev, slot_score_dev,
+                                    dt_match_dev, dt_ignore_dev, npig_dev, status_dev)))
         return 7;
-    }
-    if (h->refuse_plan_only()) return 7;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
     int S = 0;
     for (int p = 0; p < P; ++p) S += std::min(dt_start_host[p + 1] - dt_start_host[p], kEvalMaxDet);
     const size_t table_bytes = ((size_t)P * sizeof(EvalImage) + 255) / 256 * 256, need = table_bytes + (size_t)S * sizeof(int);
-    if (need && !h->table_reserve(h->eval_buf, need, 4096, "hipMalloc(keypoint evaluation scratch)")) return 6;
-    CallScope scope(h, need ? &h->eval_buf : nullptr, s);
-    if (!scope.entered) return 6;
+    CallFrame frame(h, s, {{&h->eval_buf, need, hrn_ctx::twice(need, 4096), "hipMalloc(keypoint evaluation scratch)"}});
     KeypointEvalArgs a{};
     a.P = P, a.J = J, a.S = S;
-    if (P > 0) {   // the image table through the pinned ring
-        unsigned ring = 0;
-        EvalImage *pin = (EvalImage *)h->pre_stage((size_t)P * sizeof(EvalImage), &ring);
-        if (!pin) return 6;
-        keypoint_eval_images(P, dt_start_host, gt_start_host, pin);
-        if (!h->pre_upload(ring, s, {{h->eval_buf.ptr, pin, (size_t)P * sizeof(EvalImage), "hipMemcpyAsync(keypoint evaluation table)"}})) return 6;
-        a.images = h->eval_buf.as<const EvalImage>();
-        a.set_order = (int *)(h->eval_buf.ptr + table_bytes);
-    }
+    a.images = frame.table<EvalImage>((size_t)P, "hipMemcpyAsync(keypoint evaluation table)",
+                                      [&](EvalImage *t) { keypoint_eval_images(P, dt_start_host, gt_start_host, t); });
+    if (!frame.ok()) return 6;
+    if (a.images) a.set_order = frame.dev<int>(table_bytes);
     a.dt_kpts = dt_kpts_dev, a.dt_scores = dt_scores_dev, a.gt_kpts = gt_kpts_dev, a.gt_area = gt_area_dev, a.gt_bbox = gt_bbox_dev;
     a.gt_iscrowd = gt_iscrowd_dev, a.sigmas = sigmas_dev;
     a.stats = stats_dev, a.precision = precision_dev, a.recall = recall_dev, a.slot_person = slot_person_dev, a.slot_score = slot_score_dev;
     a.dt_match = dt_match_dev, a.dt_ignore = dt_ignore_dev, a.npig = npig_dev, a.status = status_dev;
     if (!h->hip_ok(launch_keypoint_eval(a, s), "keypoint evaluation launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 // ---- the detector link: the letterboxed detector tensor, and the detector's boxes back in frame coordinates --------------------
@@ -1216,26 +1158,17 @@ int letterbox_frames(const char *entry, hrn_handle h, const hrn_frame *frames, c
     if (h->refuse_plan_only()) return 7;
     if (n == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
-    const size_t table_bytes = (size_t)n * sizeof(LetterboxFrame);
-    if (n > 1 && !h->table_reserve(h->lb_table, table_bytes, 4096, "hipMalloc(letterbox table)")) return 6;
-    CallScope scope(h, n > 1 ? &h->lb_table : nullptr, s);
-    if (!scope.entered) return 6;
+    const size_t table_bytes = n > 1 ? (size_t)n * sizeof(LetterboxFrame) : 0;
+    CallFrame frame(h, s, {{&h->lb_table, table_bytes, hrn_ctx::twice(table_bytes, 4096), "hipMalloc(letterbox table)"}});
     LetterboxArgs a{};
     a.n = n, a.out_h = out_h, a.out_w = out_w, a.form = form, a.order = order, a.yuv = yframes ? 1 : 0;
     a.pad[0] = pad[0], a.pad[1] = pad[1], a.pad[2] = pad[2];
     a.out = out_dev;
-    if (n > 1) {   // the table through the pinned ring
-        unsigned ring = 0;
-        char *pin = h->pre_stage(table_bytes, &ring);
-        if (!pin) return 6;
-        memcpy(pin, recs.data(), table_bytes);
-        if (!h->pre_upload(ring, s, {{h->lb_table.ptr, pin, table_bytes, "hipMemcpyAsync(letterbox table)"}})) return 6;
-        a.table = h->lb_table.as<const LetterboxFrame>();
-    } else {
-        a.one = recs[0];
-    }
+    a.table = frame.table(recs.data(), (size_t)n, "hipMemcpyAsync(letterbox table)");
+    if (!frame.ok()) return 6;
+    if (!a.table) a.one = recs[0];
     if (!h->hip_ok(launch_letterbox(a, s), "letterbox launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 }  // namespace
 
@@ -1261,43 +1194,27 @@ int hrn_detections_to_frame_dev(hrn_handle h, int rule, const float *dets_dev, i
                                 float *dets_out_dev, int32_t *counts_dev, int32_t *status_dev, void *stream) {
     if (!h) return 1;
     DetFilter q{};
-    if (const char *fault = det_fault(rule, dets_dev, det_stride, start_host, P, geometry_host, frame_hw_host, out_h, out_w, conf_col,
-                                      conf_thres, class_col, classes_host, nclasses, flags, dets_out_dev, counts_dev, status_dev, q)) {
-        h->err = std::string("hrn_detections_to_frame_dev: ") + fault;
-        return 7;
-    }
-    if (P > 65535) {
-        h->err = "hrn_detections_to_frame_dev: at most 65535 frames";
-        return 7;
-    }
-    if (h->refuse_plan_only()) return 7;
+    const char *fault = det_fault(rule, dets_dev, det_stride, start_host, P, geometry_host, frame_hw_host, out_h, out_w, conf_col, conf_thres,
+                                  class_col, classes_host, nclasses, flags, dets_out_dev, counts_dev, status_dev, q);
+    if (refused(h, "hrn_detections_to_frame_dev", fault ? fault : P > 65535 ? "at most 65535 frames" : nullptr)) return 7;
     if (P == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
-    const size_t table_bytes = (size_t)P * sizeof(DetFrame);
-    if (P > 1 && !h->table_reserve(h->det_table, table_bytes, 4096, "hipMalloc(detection table)")) return 6;
-    CallScope scope(h, P > 1 ? &h->det_table : nullptr, s);
-    if (!scope.entered) return 6;
-    const auto frame = [&](int p) {
+    const size_t table_bytes = P > 1 ? (size_t)P * sizeof(DetFrame) : 0;
+    CallFrame frame(h, s, {{&h->det_table, table_bytes, hrn_ctx::twice(table_bytes, 4096), "hipMalloc(detection table)"}});
+    const auto record = [&](int p) {
         return det_frame(rule, geometry_host[p], frame_hw_host[2 * (size_t)p], frame_hw_host[2 * (size_t)p + 1], out_h, out_w, start_host[p],
                          start_host[p + 1] - start_host[p]);
     };
     DetArgs a{};
     a.P = P, a.compact = (flags & kDetCompact) ? 1 : 0;
     a.dets = dets_dev, a.out = dets_out_dev, a.counts = counts_dev, a.status = status_dev;
-    DetFrame one{};
-    if (P > 1) {   // the table through the pinned ring
-        unsigned ring = 0;
-        DetFrame *pin = (DetFrame *)h->pre_stage(table_bytes, &ring);
-        if (!pin) return 6;
-        for (int p = 0; p < P; ++p) pin[p] = frame(p);
-        if (!h->pre_upload(ring, s, {{h->det_table.ptr, pin, table_bytes, "hipMemcpyAsync(detection table)"}})) return 6;
-        a.table = h->det_table.as<const DetFrame>();
-    } else {
-        one = frame(0);
-    }
-    if (!h->hip_ok(launch_detections_to_frame(a, one, q, s), "detections launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    a.table = frame.table<DetFrame>((size_t)P, "hipMemcpyAsync(detection table)", [&](DetFrame *t) {
+        for (int p = 0; p < P; ++p) t[p] = record(p);
+    });
+    if (!frame.ok()) return 6;
+    if (!h->hip_ok(launch_detections_to_frame(a, a.table ? DetFrame{} : record(0), q, s), "detections launch")) return 8;
+    return frame.leave() ? 0 : 6;
 }
 
 // ---- frame rotation: cv2.rotate for BGR, NV12 and I420 frames, and people between the two orientations (rotate.hip) -----------
@@ -1391,59 +1308,42 @@ int hrn_rotate_frames(hrn_handle h, const hrn_canvas *src_host, const hrn_canvas
     if (nframes == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
-    const size_t table_bytes = planes.size() * sizeof(RotPlane);
-    if (nframes > 1 && !h->table_reserve(h->rot_table, table_bytes, 4096, "hipMalloc(rotation table)")) return 6;
-    CallScope scope(h, nframes > 1 ? &h->rot_table : nullptr, s);
-    if (!scope.entered) return 6;
+    const size_t table_bytes = nframes > 1 ? planes.size() * sizeof(RotPlane) : 0;
+    CallFrame frame(h, s, {{&h->rot_table, table_bytes, hrn_ctx::twice(table_bytes, 4096), "hipMalloc(rotation table)"}});
     RotArgs a{};
     a.nplanes = (int)planes.size(), a.total_tiles = (int)tiles;
-    if (nframes > 1) {   // the table through the pinned ring
-        unsigned ring = 0;
-        char *pin = h->pre_stage(table_bytes, &ring);
-        if (!pin) return 6;
-        memcpy(pin, planes.data(), table_bytes);
-        if (!h->pre_upload(ring, s, {{h->rot_table.ptr, pin, table_bytes, "hipMemcpyAsync(rotation table)"}})) return 6;
-        a.table = h->rot_table.as<const RotPlane>();
-    } else {
-        for (size_t q = 0; q < planes.size(); ++q) a.one[q] = planes[q];
-    }
+    a.table = frame.table(planes.data(), planes.size(), "hipMemcpyAsync(rotation table)");
+    if (!frame.ok()) return 6;
+    if (!a.table) std::copy(planes.begin(), planes.end(), a.one);
     if (!h->hip_ok(launch_rotate(a, s), "rotate launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 int hrn_rotate_people_dev(hrn_handle h, int n, int J, const int32_t *frame_hw_host, int per_person_hw, const int32_t *codes_host,
                           int per_person_code, const float *pts_dev, const int32_t *boxes_dev, float *pts_out_dev, int32_t *boxes_out_dev,
                           void *stream) {
     if (!h) return 1;
-    if (const char *fault = rotate_people_fault(n, J, frame_hw_host, per_person_hw, codes_host, per_person_code, pts_dev, boxes_dev,
-                                                pts_out_dev, boxes_out_dev)) {
-        h->err = std::string("hrn_rotate_people_dev: ") + fault;
+    if (refused(h, "hrn_rotate_people_dev", rotate_people_fault(n, J, frame_hw_host, per_person_hw, codes_host, per_person_code, pts_dev,
+                                                                boxes_dev, pts_out_dev, boxes_out_dev)))
         return 7;
-    }
-    if (h->refuse_plan_only()) return 7;
     if (n == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
     const size_t hw_bytes = per_person_hw ? (size_t)n * 2 * sizeof(int32_t) : 0, code_bytes = per_person_code ? (size_t)n * sizeof(int32_t) : 0;
     const size_t need = hw_bytes + code_bytes;   // what the call has per person: a table through the pinned ring
-    if (need && !h->table_reserve(h->rot_people, need, 4096, "hipMalloc(rotated people table)")) return 6;
-    CallScope scope(h, need ? &h->rot_people : nullptr, s);
-    if (!scope.entered) return 6;
+    CallFrame frame(h, s, {{&h->rot_people, need, hrn_ctx::twice(need, 4096), "hipMalloc(rotated people table)"}});
     RotPeopleArgs a{};
     a.n = n, a.J = J, a.hs = frame_hw_host[0], a.ws = frame_hw_host[1], a.code = codes_host[0];
     a.pts = pts_dev, a.boxes = (const int *)boxes_dev, a.pts_out = pts_out_dev, a.boxes_out = (int *)boxes_out_dev;
-    if (need) {
-        unsigned ring = 0;
-        char *pin = h->pre_stage(need, &ring);
-        if (!pin) return 6;
+    const char *dev = frame.table<char>(need, "hipMemcpyAsync(rotated people table)", [&](char *pin) {
         if (hw_bytes) memcpy(pin, frame_hw_host, hw_bytes);
         if (code_bytes) memcpy(pin + hw_bytes, codes_host, code_bytes);
-        if (!h->pre_upload(ring, s, {{h->rot_people.ptr, pin, need, "hipMemcpyAsync(rotated people table)"}})) return 6;
-        if (hw_bytes) a.frame_hw = h->rot_people.as<const int>();
-        if (code_bytes) a.codes = (const int *)(h->rot_people.ptr + hw_bytes);
-    }
+    });
+    if (!frame.ok()) return 6;
+    if (hw_bytes) a.frame_hw = (const int *)dev;
+    if (code_bytes) a.codes = (const int *)(dev + hw_bytes);
     if (!h->hip_ok(launch_rotate_people(a, s), "rotate people launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 // the One-Euro filter and the motion lookahead of every joint of the call in one launch (temporal.hip); the arguments are judged
@@ -1454,37 +1354,28 @@ int hrn_filter_poses_dev(hrn_handle h, int P, const int32_t *cur_start_host, con
                          double beta, double d_cutoff, float threshold, double lookahead, float *pts_out_dev, float *pred_out_dev,
                          float *state_dev, int32_t *age_dev, void *stream) {
     if (!h) return 1;
-    if (const char *fault = temporal_fault(P, cur_start_host, prev_start_host, J, pts_dev, match_dev, prev_state_dev, prev_age_dev, dt,
-                                           min_cutoff, beta, d_cutoff, lookahead, pts_out_dev, state_dev, age_dev)) {
-        h->err = std::string("hrn_filter_poses_dev: ") + fault;
+    if (refused(h, "hrn_filter_poses_dev", temporal_fault(P, cur_start_host, prev_start_host, J, pts_dev, match_dev, prev_state_dev, prev_age_dev,
+                                                          dt, min_cutoff, beta, d_cutoff, lookahead, pts_out_dev, state_dev, age_dev)))
         return 7;
-    }
-    if (h->refuse_plan_only()) return 7;
     const int n = P > 0 ? cur_start_host[P] - cur_start_host[0] : 0;
     if (n == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
     const size_t table_bytes = P > 1 ? (size_t)n * sizeof(TemporalSegment) : 0;
-    if (table_bytes && !h->table_reserve(h->tmp_table, table_bytes, 4096, "hipMalloc(filter segment table)")) return 6;
-    CallScope scope(h, table_bytes ? &h->tmp_table : nullptr, s);
-    if (!scope.entered) return 6;
+    CallFrame frame(h, s, {{&h->tmp_table, table_bytes, hrn_ctx::twice(table_bytes, 4096), "hipMalloc(filter segment table)"}});
     TemporalArgs a{};
     a.J = J, a.first = cur_start_host[0], a.total = n * J;   // (n * J <= 2^31 - 1: temporal_fault)
     a.one.prev0 = prev_start_host[0], a.one.m = prev_start_host[1] - prev_start_host[0];
-    if (table_bytes) {   // every person's segment through the pinned ring
-        unsigned ring = 0;
-        TemporalSegment *pin = (TemporalSegment *)h->pre_stage(table_bytes, &ring);
-        if (!pin) return 6;
+    a.table = frame.table<TemporalSegment>((size_t)n, "hipMemcpyAsync(filter segment table)", [&](TemporalSegment *t) {   // everybody's
         for (int p = 0; p < P; ++p)
             for (int i = cur_start_host[p]; i < cur_start_host[p + 1]; ++i)
-                pin[i - a.first] = TemporalSegment{prev_start_host[p], prev_start_host[p + 1] - prev_start_host[p]};
-        if (!h->pre_upload(ring, s, {{h->tmp_table.ptr, pin, table_bytes, "hipMemcpyAsync(filter segment table)"}})) return 6;
-        a.table = h->tmp_table.as<const TemporalSegment>();
-    }
+                t[i - a.first] = TemporalSegment{prev_start_host[p], prev_start_host[p + 1] - prev_start_host[p]};
+    });
+    if (!frame.ok()) return 6;
     a.pts = pts_dev, a.match = (const int *)match_dev, a.prev_state = prev_state_dev, a.prev_age = (const int *)prev_age_dev;
     a.pts_out = pts_out_dev, a.pred_out = pred_out_dev, a.state = state_dev, a.age = (int *)age_dev;
     if (!h->hip_ok(launch_temporal(a, temporal_params(dt, min_cutoff, beta, d_cutoff, threshold, lookahead), s), "filter launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 int hrn_resize_frames(hrn_handle h, const uint8_t *frames_dev, int n, int frame_h, int frame_w, int interpolation,
@@ -1504,13 +1395,12 @@ int hrn_resize_frames(hrn_handle h, const uint8_t *frames_dev, int n, int frame_
     hipStream_t s = (hipStream_t)stream;
     const int H = h->H, W = h->W;
     const size_t taps_bytes = (size_t)(W + H) * sizeof(ResizeTaps);   // the one tap table of the handle, rewritten by every call
-    if (!h->rs_taps.reserve(h, taps_bytes, taps_bytes, "hipMalloc(resize taps)")) return 6;
-    CallScope scope(h, &h->rs_taps, s);
-    if (!scope.entered) return 6;
-    if (!h->hip_ok(launch_resize_frames(frames_dev, n, frame_h, frame_w, interpolation, h->rs_taps.as<ResizeTaps>(), images_dev, H, W, s),
+    CallFrame frame(h, s, {{&h->rs_taps, taps_bytes, taps_bytes, "hipMalloc(resize taps)"}});
+    if (!frame.ok()) return 6;
+    if (!h->hip_ok(launch_resize_frames(frames_dev, n, frame_h, frame_w, interpolation, frame.dev<ResizeTaps>(), images_dev, H, W, s),
                    "resize launch"))
         return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 namespace {
@@ -1557,9 +1447,10 @@ int hrn_warp_crops(hrn_handle h, const uint8_t *frames_dev, int nframes, int fra
     }
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     const int H = h->H, W = h->W;
-    unsigned ring = 0;
-    WarpParams *wp = (WarpParams *)h->pre_stage((size_t)n * sizeof(WarpParams), &ring);
-    if (!wp) return 6;
+    const size_t bytes = (size_t)n * sizeof(WarpParams);
+    const PinnedImage img = h->image(bytes);
+    if (!img) return 6;
+    WarpParams *wp = img.as<WarpParams>();
     for (int i = 0; i < n; ++i) {
         const long f = frame_index_host ? (long)frame_index_host[i] : nframes == 1 ? 0 : i;
         if (f < 0 || f >= nframes) {
@@ -1586,14 +1477,11 @@ int hrn_warp_crops(hrn_handle h, const uint8_t *frames_dev, int nframes, int fra
         }
     }
     hipStream_t s = (hipStream_t)stream;
-    const size_t bytes = (size_t)n * sizeof(WarpParams);
-    if (!h->warp_params.reserve(h, bytes, std::max(n, 256) * sizeof(WarpParams), "hipMalloc(warp params)")) return 6;
-    CallScope scope(h, &h->warp_params, s);
-    if (!scope.entered) return 6;
-    if (!h->pre_upload(ring, s, {{h->warp_params.ptr, wp, bytes, "hipMemcpyAsync(warp params)"}})) return 6;
-    if (!h->hip_ok(launch_warp_crops(frames_dev, frame_h, frame_w, h->warp_params.as<WarpParams>(), n, images_dev, H, W, s), "warp launch"))
-        return 8;
-    return scope.leave() ? 0 : 6;
+    CallFrame frame(h, s, {{&h->warp_params, bytes, std::max(n, 256) * sizeof(WarpParams), "hipMalloc(warp params)"}});
+    const WarpParams *params = frame.upload<WarpParams>(img, bytes, "hipMemcpyAsync(warp params)");
+    if (!params) return 6;
+    if (!h->hip_ok(launch_warp_crops(frames_dev, frame_h, frame_w, params, n, images_dev, H, W, s), "warp launch")) return 8;
+    return frame.leave() ? 0 : 6;
 }
 
 extern "C++" {
@@ -1630,6 +1518,17 @@ std::string target_centers(const double *joints, const float *vis, const float *
     }
     return "";
 }
+
+// what hrn_generate_targets and hrn_score_heatmaps share: the image their n * J records are written into, and the frame on
+// score_joints that carries them to the device
+PinnedImage score_image(hrn_ctx *h, int64_t count) { return h->image((size_t)std::max<int64_t>(count, 1) * sizeof(ScoreJoint)); }
+struct ScoreFrame : CallFrame {
+    const ScoreJoint *joints;   // on the device (nullptr and not ok(): the entry returns 6)
+    ScoreFrame(hrn_ctx *h, const PinnedImage &img, int64_t count, hipStream_t s)
+        : CallFrame(h, s, {{&h->score_joints, (size_t)count * sizeof(ScoreJoint), (size_t)std::max<int64_t>(count, 256 * 17) * sizeof(ScoreJoint),
+                            "hipMalloc(score records)"}}),
+          joints(upload<ScoreJoint>(img, (size_t)count * sizeof(ScoreJoint), "hipMemcpyAsync(score records)")) {}
+};
 }  // namespace
 }  // extern "C++"
 
@@ -1651,11 +1550,10 @@ int hrn_generate_targets(hrn_handle h, const double *joints_host, const float *v
     }
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     const int64_t count = (int64_t)n * h->joints;
-    unsigned ring = 0;
-    ScoreJoint *recs = (ScoreJoint *)h->pre_stage((size_t)std::max<int64_t>(count, 1) * sizeof(ScoreJoint), &ring);
-    if (!recs) return 6;
+    const PinnedImage img = score_image(h, count);
+    if (!img) return 6;
     const std::string bad = target_centers(joints_host, vis_host, joints_weight_host, n, h->joints, h->H, h->W, sigma, nullptr, nullptr,
-                                           target_weight_host, recs);
+                                           target_weight_host, img.as<ScoreJoint>());
     if (!bad.empty()) {
         h->err = "hrn_generate_targets: " + bad;
         return 7;
@@ -1666,13 +1564,11 @@ int hrn_generate_targets(hrn_handle h, const double *joints_host, const float *v
     a.table = h->score_table(a.t, sigma);
     if (!a.table) return 6;
     hipStream_t s = (hipStream_t)stream;
-    const size_t bytes = (size_t)count * sizeof(ScoreJoint);
-    if (!h->score_joints.reserve(h, bytes, (size_t)std::max<int64_t>(count, 256 * 17) * sizeof(ScoreJoint), "hipMalloc(score records)")) return 6;
-    CallScope scope(h, &h->score_joints, s);
-    if (!scope.entered || !h->pre_upload(ring, s, {{h->score_joints.ptr, recs, bytes, "hipMemcpyAsync(score records)"}})) return 6;
-    a.joints = h->score_joints.as<ScoreJoint>(), a.n = n, a.J = h->joints, a.h = h->H / 4, a.w = h->W / 4;
+    ScoreFrame frame(h, img, count, s);
+    if (!frame.ok()) return 6;
+    a.joints = frame.joints, a.n = n, a.J = h->joints, a.h = h->H / 4, a.w = h->W / 4;
     if (!h->hip_ok(launch_targets(a, targets_dev, s), "targets launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 // testing/Test.py:141-157: loss_fn(output, target, target_weight) and evaluate_pck_accuracy(output, target) of one batch.
@@ -1714,9 +1610,9 @@ int hrn_score_heatmaps(hrn_handle h, const float *heatmaps_dev, int n, const flo
     }
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     const int64_t count = (int64_t)n * h->joints;
-    unsigned ring = 0;
-    ScoreJoint *recs = (ScoreJoint *)h->pre_stage((size_t)std::max<int64_t>(count, 1) * sizeof(ScoreJoint), &ring);
-    if (!recs) return 6;
+    const PinnedImage img = score_image(h, count);
+    if (!img) return 6;
+    ScoreJoint *recs = img.as<ScoreJoint>();
     ScoreArgs a{};
     if (analytic) {
         const std::string bad = target_centers(joints_host, vis_host, joints_weight_host, n, h->joints, h->H, h->W, sigma, nullptr, nullptr,
@@ -1732,17 +1628,15 @@ int hrn_score_heatmaps(hrn_handle h, const float *heatmaps_dev, int n, const flo
         for (int64_t k = 0; k < count; ++k) recs[k] = ScoreJoint{0, 0, target_weight_host[k], 0};
     }
     hipStream_t s = (hipStream_t)stream;
-    const size_t bytes = (size_t)count * sizeof(ScoreJoint);
-    if (!h->score_joints.reserve(h, bytes, (size_t)std::max<int64_t>(count, 256 * 17) * sizeof(ScoreJoint), "hipMalloc(score records)")) return 6;
-    CallScope scope(h, &h->score_joints, s);
-    if (!scope.entered || (count > 0 && !h->pre_upload(ring, s, {{h->score_joints.ptr, recs, bytes, "hipMemcpyAsync(score records)"}}))) return 6;
-    a.heatmaps = heatmaps_dev, a.targets = targets_dev, a.joints = h->score_joints.as<ScoreJoint>();
+    ScoreFrame frame(h, img, count, s);
+    if (!frame.ok()) return 6;
+    a.heatmaps = heatmaps_dev, a.targets = targets_dev, a.joints = frame.joints;
     a.n = n, a.J = h->joints, a.h = h->H / 4, a.w = h->W / 4;
     a.map_loss = out_dev->map_loss, a.preds = out_dev->preds, a.target_preds = out_dev->target_preds, a.maxvals = out_dev->maxvals;
     a.loss_mse = out_dev->loss_mse, a.loss_ohkm = out_dev->loss_ohkm, a.avg_acc = out_dev->avg_acc, a.acc = out_dev->acc;
     a.dists = out_dev->dists, a.cnt = out_dev->cnt, a.pck_thr = pck_thr, a.ohkm_topk = ohkm_topk;
     if (!h->hip_ok(launch_score(a, s), "score launch")) return 8;
-    return scope.leave() ? 0 : 6;
+    return frame.leave() ? 0 : 6;
 }
 
 // Debug tap: one micro-batch with the named tensor copied out right after the launch that completes it.

@@ -1,6 +1,7 @@
 """One handle under callers that alternate streams, for every family of calls that keeps a device array on the handle (crop
-pre-path, tracking table, warp, scoring, overlays, person ids): the handle's one guard type (csrc/ctx_scratch.inc) must serialise
-them, and an array must be able to grow while another stream was its last user."""
+pre-path, tracking table, warp, scoring, overlays, person ids, the detector link, frame rotation, the temporal filter, pose NMS,
+the track table): the handle's one call frame (csrc/ctx_scratch.inc) must serialise them, and an array must be able to grow while
+another stream was its last user."""
 import numpy as np
 import pytest
 import torch
@@ -8,6 +9,7 @@ import torch
 from conftest import load_pkg
 
 H, W, FH, FW, J = 128, 96, 96, 80, 17
+SH, SW, LB = 24, 20, 32   # the small frames of the detector link and the rotation, and the detector's input side
 SKELETON = [(0, 1), (1, 2), (2, 3), (5, 6), (5, 7), (7, 9), (11, 13), (13, 15)]
 
 
@@ -23,7 +25,8 @@ def _poses(rng, n):
                           2).astype(np.float32)
 
 
-def _arguments(pkg, seed, people=3, table=2, tracked=3, drawn=3, warped=3, scored=3, matched=(2, 1)):
+def _arguments(pkg, seed, people=3, table=2, tracked=3, drawn=3, warped=3, scored=3, matched=(2, 1), small=3, turned=3, filtered=(2, 1),
+               nms=(2, 1), streams=(2, 1), capacity=8):
     """one argument set: `people` in every call unless a count says otherwise (the large set: past the first call's capacity)"""
     rng = np.random.default_rng(seed)
     dev = torch.device("cuda", 0)
@@ -51,6 +54,20 @@ def _arguments(pkg, seed, people=3, table=2, tracked=3, drawn=3, warped=3, score
                       prev_boxes=_boxes(rng, m).astype(np.int32), prev_pts=_poses(rng, m),
                       prev_ids=np.arange(m, dtype=np.int32), next_id=np.asarray([100, 200], np.int32), counts=list(matched),
                       prev_counts=list(matched[::-1]), smoothing_alpha=0.25)
+    # the families whose table travels only with several frames / people / problems: `small` frames of SH x SW with a rotation code
+    # and two detector rows each, `turned` people with a frame size and a code each, and people by problem
+    a["small"] = list(torch.from_numpy(rng.integers(0, 256, (small, SH, SW, 3), dtype=np.uint8)).to(dev).unbind(0))
+    a["codes"] = rng.integers(0, 3, small).astype(np.int32)
+    x1, y1 = rng.uniform(0, LB / 2, 2 * small), rng.uniform(0, LB / 2, 2 * small)
+    a["rows"] = np.stack([x1, y1, x1 + rng.uniform(2, LB / 2, 2 * small), y1 + rng.uniform(2, LB / 2, 2 * small),
+                          rng.uniform(0, 1, 2 * small), rng.integers(0, 3, 2 * small)], 1).astype(np.float32)
+    a["turned"] = dict(pts=_poses(rng, turned), boxes=_boxes(rng, turned).astype(np.int32),
+                       frame_hw=np.stack([rng.integers(FH, 2 * FH, turned), rng.integers(FW, 2 * FW, turned)], 1).astype(np.int32),
+                       rotation_code=rng.integers(0, 3, turned).astype(np.int32))
+    a["filtered"] = dict(pts=_poses(rng, sum(filtered)), counts=list(filtered))
+    a["nms"] = dict(pts=_poses(rng, sum(nms)), boxes=_boxes(rng, sum(nms)).astype(np.int32), counts=list(nms), thresh=0.5)
+    a["tracked"] = dict(boxes=_boxes(rng, sum(streams)).astype(np.int32), pts=_poses(rng, sum(streams)), counts=list(streams))
+    a["capacity"] = capacity
     return a
 
 
@@ -74,6 +91,20 @@ def _calls(net, a):
         out["draw_%d" % k] = canvas
     for k, value in enumerate(net.associate_people(**a["assoc"])):
         out["assoc_%d" % k] = value
+    out["letterbox"], geometry = net.detector_input(a["small"], LB)
+    for k, value in enumerate(net.detections_to_frame(a["rows"], geometry, counts=[2] * len(a["small"]), conf_thres=0.3)):
+        out["dets_%d" % k] = value
+    out["rotated"] = torch.cat([f.reshape(-1) for f in net.rotate_frames(a["small"], a["codes"])])
+    out["turned_pts"], out["turned_boxes"] = net.rotate_people(**a["turned"])
+    pts, pred, (values, age) = net.filter_poses(**a["filtered"])
+    out["filter_pts"], out["filter_pred"], out["filter_values"], out["filter_age"] = pts, pred, values, age
+    for key, value in net.pose_nms(**a["nms"]).items():
+        out["nms_%s" % key] = value
+    table = net.new_track_table(len(a["tracked"]["counts"]), a["capacity"])     # every round starts from the same table
+    for k, value in enumerate(net.track_people(table=table, **a["tracked"])):
+        out["track_%d" % k] = value
+    for key, value in table.items():
+        out["track_table_%s" % key] = value
     return out
 
 
@@ -84,13 +115,18 @@ def test_every_call_family_under_alternating_streams():
     table, and one whose sizes exceed the capacity the first call allocated, issued when another stream was the last user -- and
     every output must equal, bit for bit, what the same arguments gave on the default stream of a fresh handle.  It is NOT a
     race detector: at these sizes a missing wait may well go unnoticed, so the review of the guard's code (CallGuard /
-    CallScope in csrc/ctx_scratch.inc) carries that weight."""
+    CallScope / CallFrame in csrc/ctx_scratch.inc) carries that weight."""
     pkg = load_pkg()
     sets = [_arguments(pkg, 1), _arguments(pkg, 2),
             # past the floors of the growth rules: 4096 B of tables (130 frames x 80 B; 600 x 8 B of frame sizes; 400 people drawn), 256
             # warp records, 256 x 17 score records, 65536 B of association scratch (two problems of 60 x 60 x 12 B), and more people
-            # than the exactly-sized pre-path arrays held
-            _arguments(pkg, 3, people=7, table=130, tracked=600, drawn=400, warped=260, scored=257, matched=(60, 60))]
+            # than the exactly-sized pre-path arrays held; and of the tables that travel only with several problems: 130 BGR frames
+            # x 120 B of letterbox records (kernels.h's LetterboxFrame: a pointer, a 64 B YuvSource, 8 ints, 2 doubles), x 32 B of detection
+            # records (letterbox_math.h's DetFrame) and x 48 B of rotation planes (RotPlane, one per BGR frame), 350 people x 12 B of frame sizes and codes,
+            # 520 people x 8 B of filter segments, 520 problems x 8 B of pose NMS; and 65536 B of track scratch (a 256 B stream table,
+            # then two streams of 45 rows x 64 slots x 12 B)
+            _arguments(pkg, 3, people=7, table=130, tracked=600, drawn=400, warped=260, scored=257, matched=(60, 60), small=130, turned=350,
+                       filtered=(300, 220), nms=(1,) * 520, streams=(45, 45), capacity=64)]
     net = pkg.NativeHRNet(32, J, (H, W), "fp32", max_batch=4, device=0)
     want = [{k: v.cpu().numpy() for k, v in _calls(net, a).items()} for a in sets]
     torch.cuda.synchronize()
