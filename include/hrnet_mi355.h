@@ -632,6 +632,79 @@ int hrn_draw_poses_ids_dev(hrn_handle h, const hrn_canvas *canvases_host, int nf
                            const int32_t *frame_index_host, const int32_t *skeleton_host, int K, const uint8_t *point_colors_host,
                            int Cp, const uint8_t *bone_colors_host, int Cb, const int32_t *person_index_dev, int radius,
                            int thickness, float threshold, void *stream);
+
+/* ---- person labels on the GPU: the box, the id and the score of every person, drawn beside it ----
+ * The overlay above shows skeletons; the state of the tracking chain -- the id that hrn_associate_people_dev / hrn_track_people_dev
+ * gives a person, the box the next crop is cut from, the person's score -- is printed by this entry, from the device memory where
+ * it lies, with no host read: the decimal digits are formed, laid out and rasterised on the device.  (The reference's demo has
+ * its cv2.rectangle commented out, scripts/live-demo.py:140-141.)  As with hrn_draw_poses, pixel equality with cv2.rectangle /
+ * cv2.putText is NOT claimed (Hershey fonts cannot be restated blind): THE CONTRACT IS THIS INTEGER DEFINITION.
+ * tests/label_ref.py restates it in numpy; the kernels equal it byte for byte.  One text, csrc/draw_labels_math.h, is compiled
+ * into the kernels and into hrn_label_layout / hrn_label_covers.
+ *
+ * Inputs per person i.  box[i] = (x1, y1, x2, y2) int32 -- the boxes hrn_preprocess_frames*, hrn_associate_people_dev and
+ * hrn_track_people_dev write; optional id[i] int32; optional score[i] float32, read at scores_dev[i * score_stride] (column 4
+ * of an (n, 5) detection tensor is passed where it lies, score_stride = 5).
+ * Drawn iff all four coordinates lie in [-8192, 16383] and x2 > x1 and y2 > y1; the library's empty box (0, 0, 0, 0), "nobody", is
+ * therefore never drawn.  Frame sides are at most 8192.  Every expression fits 32 bits: |coordinate| < 2^14, a plate is at most
+ * 16 * 85 = 1360 wide.
+ * Colour index.  c = id[i] when ids are given, else i.  The person's colour is colors[c mod Cb], the person's text colour
+ * text_colors[c mod Cb] (Python's modulo: id -1 takes Cb - 1); both palettes have Cb entries of three bytes in the canvas's
+ * channel order (B, G, R or Y, U, V).
+ * Text.  A row of D <= 14 cells, each a digit or a blank.  With id[i] >= 0: its decimal digits, most significant first (1 to 10
+ * cells; a negative id prints nothing).  With a score v = score[i]: NaN gives no score field; v < 0 is taken as 0 and v > 1 as 1;
+ * p = (int)(v * 100.0f + 0.5f) -- two float32 operations, each rounded once, never contracted into an FMA -- lies in 0 .. 100; the
+ * cells are one blank when id digits precede, then the decimal digits of p.  No cells at all: no plate and no ink.
+ * Glyphs.  5 columns x 7 rows, rows top to bottom, bit 4 = the leftmost column (the HD44780 digit set):
+ *     0: 0E 11 13 15 19 11 0E    5: 1F 10 1E 01 01 11 0E
+ *     1: 04 0C 04 04 04 04 0E    6: 06 08 10 1E 11 11 0E
+ *     2: 0E 11 01 02 04 08 1F    7: 1F 01 02 04 08 08 08
+ *     3: 1F 02 04 02 01 11 0E    8: 0E 11 11 0E 11 11 0E
+ *     4: 02 06 0A 12 1F 02 02    9: 0E 11 11 0F 01 02 0C
+ * Scale s in [1, 16]: a glyph dot is s x s pixels.  scale = 0: min(16, max(1, min(height, width) / 360)) per canvas (the rule
+ * of radius = 0 above, bounded by the range of s).  Thickness T in [0, 16].
+ * Primitives of person i, in this order:
+ *   0. Outline: the pixels with x1 <= px <= x2 and y1 <= py <= y2 (both corners inclusive) that do NOT satisfy
+ *      x1 + T <= px <= x2 - T and y1 + T <= py <= y2 - T.  T = 0 gives none; a box narrower than 2 T is filled.  The person's colour.
+ *   1. Plate: with D cells, width = s (6 D + 1) and height = 9 s; left = x1; top = y1 - 9 s when y1 - 9 s >= 0 (above the box),
+ *      else top = y1 (inside it).  It covers left <= px < left + width and top <= py < top + height.  The person's colour.
+ *   2. Ink: the digit d in cell k covers (px, py) iff, with u = px - left - s (1 + 6 k) and v = py - top - s, 0 <= u < 5 s and
+ *      0 <= v < 7 s and bit 4 - u / s of row v / s of glyph d is set.  The person's text colour.  A blank cell has no ink.
+ * Order.  Primitives are numbered person-major in call order; a pixel takes the HIGHEST-numbered primitive that covers it.
+ * As in hrn_draw_poses: everything is clipped by the canvas; untouched pixels are NOT WRITTEN, pitch padding never is; on NV12 /
+ * I420 a covered pixel's Y byte takes the winner's Y, and the chroma sample of a 2x2 block is written iff at least one of its four
+ * pixels is covered, and takes U and V of the highest-numbered primitive that covers any of the four.
+ *
+ * hrn_label_layout (no handle, no GPU): the record of one person from (box, id, score, scale in [1, 16], thickness in [0, 16]).
+ * hrn_label_record is 16 int32: drawn (0: nothing of this person is drawn, every other field 0); x1, y1, x2, y2 and thickness of
+ * the outline; the plate's left, top, width, height (no cells: 0); scale; ncells = D; cells_lo, cells_hi: cell k in the four bits
+ * at 4 k of (cells_hi : cells_lo), 0 .. 9 a digit, 15 a blank; colour, text_colour: filled on the device from the palettes, 0 here.
+ * hrn_label_covers: what the record puts on pixel (px, py) -- 0 nothing, 1 the person's colour (plate or outline), 2 the person's
+ * text colour (ink).  Both return 7 on bad arguments, with hrn_label_last_error() (per thread) = "null box / record",
+ * "scale must be in [1, 16]", "thickness must be in [0, 16]", "null record" or "the record is not one hrn_label_layout wrote".
+ *
+ * hrn_draw_labels_dev.  canvases_host, frame_index_host and their rules are hrn_draw_poses'; boxes_dev (n, 4) int32, ids_dev n
+ * int32 or NULL, scores_dev or NULL, all on the device; colors_host / text_colors_host Cb colours each, on the host.  Two launches
+ * whatever n and nframes, stream-ordered, no host read of device data: a build launch (one thread per person writes the record)
+ * and a rasteriser of hrn_draw_poses' geometry (one 256-thread block per 32 x 32 tile of the canvases referred to, a thread per
+ * 2x2 block; a tile culls its frame's people 256 at a time from the end of the call order and resolves the survivors last person
+ * first -- any number of people on one tile loses none; no atomics, one writer per byte).  n == 0 succeeds and launches nothing.
+ * Fails with code 7 and nothing launched, each failure naming its cause, on: n < 0; Cb < 1; scale outside [0, 16]; thickness
+ * outside [0, 16]; score_stride < 1 with scores; null tables; several frames without frame_index; a frame index outside
+ * [0, nframes); every canvas refusal of hrn_draw_poses (null, unknown format, bad side or pitch, mixed formats, the same buffer
+ * twice); after those, a plan-only handle.  Everything is judged before the device is touched. */
+typedef struct { int32_t drawn, x1, y1, x2, y2, thickness, left, top, width, height, scale, ncells;
+                 uint32_t cells_lo, cells_hi, colour, text_colour; } hrn_label_record;
+int hrn_label_layout(const int32_t *box /* 4 */, int has_id, int32_t id, int has_score, float score, int scale, int thickness,
+                     hrn_label_record *record_out);
+int hrn_label_covers(const hrn_label_record *record, int px, int py);
+const char *hrn_label_last_error(void);
+int hrn_draw_labels_dev(hrn_handle h, const hrn_canvas *canvases_host, int nframes,
+                        const int32_t *boxes_dev /* (n,4) */, const int32_t *ids_dev /* n or NULL */,
+                        const float *scores_dev /* or NULL */, int score_stride, int n,
+                        const int32_t *frame_index_host /* n entries; NULL: nframes == 1 */,
+                        const uint8_t *colors_host, const uint8_t *text_colors_host, int Cb,
+                        int scale /* 0: the rule */, int thickness, void *stream);
 int hrn_yuv_from_bgr(int matrix, int range, const uint8_t *bgr /* (n,3) */, int n, uint8_t *yuv_out /* (n,3) */);
 
 /* ---- the detector link on the GPU: the letterboxed detector tensor, and the detector's boxes back in frame coordinates ----

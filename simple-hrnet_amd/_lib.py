@@ -21,7 +21,7 @@ if os.environ.get("HRN_LIB_TAG"):   # A/B runs of compile-time variants (tools/m
 SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "conv3x3_f32.hip", "bottleneck_chain.hip", "prepath.hip", "warp.hip", "nms.hip", "postproc.cpp", "hrnet_mi355.cpp",
            "decode.hip",   # heat-maps to joint coordinates: the plain and sub-pixel decodes, flip-TTA's decode
            "score.hip",    # heat-maps against the ground truth: Gaussian targets, loss and PCK of an evaluation batch
-           "draw.hip",     # pose overlays: joints and bones of every person drawn into BGR / NV12 / I420 frames on the device
+           "draw.hip",     # pose overlays and person labels: joints, bones, boxes, ids and scores drawn into BGR / NV12 / I420 frames on the device (draw_labels_math.h)
            "track.hip",    # the tracking link: boxes from joints, crop records from detections on the device (track_geometry.h)
            "pose_nms.hip",  # pose NMS: rescoring and hard / soft OKS NMS per image or stream in one launch (pose_nms_math.h)
            "detector_nms.hip",  # detector NMS: the raw output of a YOLO head to kept rows, scoring pass + one block per image (detector_nms_math.h)
@@ -210,6 +210,13 @@ class CanvasC(ctypes.Structure):
     _fields_ = list(YuvFrameC._fields_)
 
 
+class LabelRecordC(ctypes.Structure):
+    """hrn_label_record: one person's label as hrn_label_layout builds it (csrc/draw_labels_math.h: LabelRecord)"""
+    _fields_ = [(name, ctypes.c_int32) for name in ("drawn", "x1", "y1", "x2", "y2", "thickness", "left", "top", "width", "height",
+                                                    "scale", "ncells")] + \
+               [(name, ctypes.c_uint32) for name in ("cells_lo", "cells_hi", "colour", "text_colour")]
+
+
 # every symbol include/hrnet_mi355.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 SYMBOLS = {
@@ -241,6 +248,12 @@ SYMBOLS = {
                                       _P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P]),
     "hrn_draw_poses_ids_dev": (ctypes.c_int, [_P, ctypes.POINTER(CanvasC), ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_int,
                                               _P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P]),
+    "hrn_label_layout": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int32, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int,
+                                        ctypes.POINTER(LabelRecordC)]),
+    "hrn_label_covers": (ctypes.c_int, [ctypes.POINTER(LabelRecordC), ctypes.c_int, ctypes.c_int]),
+    "hrn_label_last_error": (ctypes.c_char_p, []),
+    "hrn_draw_labels_dev": (ctypes.c_int, [_P, ctypes.POINTER(CanvasC), ctypes.c_int, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     "hrn_associate_people": (ctypes.c_int, [ctypes.c_int, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, _P, _P, _P]),
     "hrn_associate_people_last_error": (ctypes.c_char_p, []),

@@ -19,8 +19,12 @@
 // chunk might not fit, and at the end: each thread walks it from the front -- the highest-numbered primitive -- and stops once
 // its four pixels have a colour; the block stops once every thread has.  Nothing is dropped, no atomics, no scratch of frame
 // size; each byte of a canvas is written by at most one thread, and only when a primitive covers its pixel.
+//
+// Person labels (hrn_draw_labels_dev) follow at the end of the file: label_build_kernel and label_raster_kernel, on the same tile
+// geometry, frame table and writer.
 #include <hip/hip_runtime.h>
 
+#include "draw_labels_math.h"
 #include "kernels.h"
 
 namespace hrn {
@@ -85,6 +89,40 @@ __device__ __forceinline__ bool covers(int px, int py, int x0, int y0, int x1, i
     return 4 * cross * cross <= (long long)q2 * l2;
 }
 
+// the frame of a tile: the last one whose first tile is not behind it (every frame of the table has tiles)
+__device__ __forceinline__ int frame_of_tile(const DrawFrame *frames, int nframes, int tile) {
+    int lo = 0, hi = nframes - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (frames[mid].tile_start <= tile) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// what a thread writes of its 2 x 2 block at (px, py): the pixels of `drawn` in their colours; on a 4:2:0 canvas the block's
+// chroma sample from `first`, the colour of the highest primitive on any of the four
+__device__ __forceinline__ void write_block(const DrawFrame &f, int px, int py, unsigned drawn, const unsigned (&colour)[4], unsigned first) {
+    if (drawn == 0) return;
+    if (f.format == 0) {   // HRN_PIX_BGR
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            if ((drawn >> p) & 1u) {
+                unsigned char *dst = f.p0 + (size_t)(py + (p >> 1)) * f.pitch0 + (size_t)(px + (p & 1)) * 3;
+                dst[0] = (unsigned char)colour[p], dst[1] = (unsigned char)(colour[p] >> 8), dst[2] = (unsigned char)(colour[p] >> 16);
+            }
+        return;
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+        if ((drawn >> p) & 1u) f.p0[(size_t)(py + (p >> 1)) * f.pitch0 + px + (p & 1)] = (unsigned char)colour[p];
+    const size_t crow = (size_t)(py >> 1) * f.pitch1;
+    if (f.format == 1) {   // HRN_PIX_NV12: interleaved U, V
+        f.p1[crow + px] = (unsigned char)(first >> 8), f.p1[crow + px + 1] = (unsigned char)(first >> 16);
+    } else {               // HRN_PIX_I420
+        f.p1[crow + (px >> 1)] = (unsigned char)(first >> 8), f.p2[crow + (px >> 1)] = (unsigned char)(first >> 16);
+    }
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(64) void draw_build_kernel(DrawArgs a) {
@@ -120,14 +158,8 @@ __global__ __launch_bounds__(kThreads) void draw_raster_kernel(DrawArgs a) {
     __shared__ int wave_count[kWaves];
     const int tid = threadIdx.x;
 
-    // the frame of this tile: the last one whose first tile is not behind it (every frame of the table has tiles)
-    int lo = 0, hi = a.nframes - 1;
     const int tile = blockIdx.x;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.frames[mid].tile_start <= tile) lo = mid; else hi = mid - 1;
-    }
-    const DrawFrame f = a.frames[lo];
+    const DrawFrame f = a.frames[frame_of_tile(a.frames, a.nframes, tile)];
     const int local = tile - f.tile_start, trow = local / f.tiles_x, tcol = local - trow * f.tiles_x;
     const int tx0 = tcol * kDrawTile, ty0 = trow * kDrawTile, tx1 = tx0 + kDrawTile - 1, ty1 = ty0 + kDrawTile - 1;
     const int px = tx0 + 2 * (tid & 15), py = ty0 + 2 * (tid >> 4);   // this thread's 2 x 2 block: pixel k = (px + (k & 1), py + (k >> 1))
@@ -213,26 +245,7 @@ __global__ __launch_bounds__(kThreads) void draw_raster_kernel(DrawArgs a) {
     }
     if (!finished && held > 0) resolve(held);
 
-    const unsigned drawn = done & ~outside;
-    if (drawn == 0) return;
-    if (f.format == 0) {   // HRN_PIX_BGR
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-            if ((drawn >> p) & 1u) {
-                unsigned char *dst = f.p0 + (size_t)(py + (p >> 1)) * f.pitch0 + (size_t)(px + (p & 1)) * 3;
-                dst[0] = (unsigned char)colour[p], dst[1] = (unsigned char)(colour[p] >> 8), dst[2] = (unsigned char)(colour[p] >> 16);
-            }
-        return;
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-        if ((drawn >> p) & 1u) f.p0[(size_t)(py + (p >> 1)) * f.pitch0 + px + (p & 1)] = (unsigned char)colour[p];
-    const size_t crow = (size_t)(py >> 1) * f.pitch1;
-    if (f.format == 1) {   // HRN_PIX_NV12: interleaved U, V
-        f.p1[crow + px] = (unsigned char)(first >> 8), f.p1[crow + px + 1] = (unsigned char)(first >> 16);
-    } else {               // HRN_PIX_I420
-        f.p1[crow + (px >> 1)] = (unsigned char)(first >> 8), f.p2[crow + (px >> 1)] = (unsigned char)(first >> 16);
-    }
+    write_block(f, px, py, done & ~outside, colour, first);
 }
 
 hipError_t launch_draw(const DrawArgs &a, hipStream_t s) {
@@ -241,6 +254,96 @@ hipError_t launch_draw(const DrawArgs &a, hipStream_t s) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(draw_raster_kernel, dim3((unsigned)a.total_tiles), dim3(kThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- person labels (include/hrnet_mi355.h: hrn_draw_labels_dev; every rule: draw_labels_math.h) -----------------------------------
+//   label_build_kernel    one thread per person: the record (outline, plate, cells, colours) and its reach, from box / id / score
+//                         where they lie on the device
+//   label_raster_kernel   draw_raster_kernel's geometry.  A tile culls its frame's people 256 at a time from the end of the call
+//                         order -- first by reach, then by what of the record really meets the tile (a tile inside a box's interior
+//                         holds no outline) -- and keeps the survivors' records in LDS, last person first; every thread walks them
+//                         from the front and stops once its four pixels have a colour, the block once every thread has.  A chunk is
+//                         resolved before the next is read, so no number of people on a tile loses anybody.
+__global__ __launch_bounds__(kThreads) void label_build_kernel(LabelArgs a) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= a.n) return;
+    const int32_t box[4] = {a.boxes[4 * (size_t)i], a.boxes[4 * (size_t)i + 1], a.boxes[4 * (size_t)i + 2], a.boxes[4 * (size_t)i + 3]};
+    const int id = a.ids ? a.ids[i] : 0;
+    const float score = a.scores ? a.scores[(size_t)i * a.score_stride] : 0.0f;
+    LabelRecord r = label_layout(box, a.ids != nullptr, id, a.scores != nullptr, score, a.frames[a.person_frame[i]].radius, a.thickness);
+    if (r.drawn) {
+        const int c = label_colour_index(a.ids ? id : i, a.Cb);
+        r.colour = a.colour[c], r.text_colour = a.text_colour[c];
+    }
+    a.records[i] = r;
+    int32_t reach[4];
+    label_reach(r, reach);
+    a.reach[i] = make_int4(reach[0], reach[1], reach[2], reach[3]);
+}
+
+__global__ __launch_bounds__(kThreads) void label_raster_kernel(LabelArgs a) {
+    __shared__ LabelRecord recs[kThreads];   // the people of the current chunk that meet the tile, last first
+    __shared__ int wave_count[kWaves];
+    const int tid = threadIdx.x;
+    const int tile = blockIdx.x;
+    const DrawFrame f = a.frames[frame_of_tile(a.frames, a.nframes, tile)];
+    const int local = tile - f.tile_start, trow = local / f.tiles_x, tcol = local - trow * f.tiles_x;
+    const int tx0 = tcol * kDrawTile, ty0 = trow * kDrawTile, tx1 = tx0 + kDrawTile - 1, ty1 = ty0 + kDrawTile - 1;
+    const int px = tx0 + 2 * (tid & 15), py = ty0 + 2 * (tid >> 4);   // this thread's 2 x 2 block: pixel k = (px + (k & 1), py + (k >> 1))
+
+    unsigned outside = 0;   // pixels beyond an odd BGR frame's edge count as finished and are never written
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (px + (k & 1) >= f.width || py + (k >> 1) >= f.height) outside |= 1u << k;
+    unsigned done = outside, c0 = 0, c1 = 0, c2 = 0, c3 = 0, first = 0;   // first: the colour of the highest primitive on any of the four
+
+    for (int pend = f.person_count; pend > 0; pend -= kThreads) {
+        const int pi = pend - 1 - tid;   // people of the frame from the last backwards
+        bool meets = false;
+        int person = 0;
+        if (pi >= 0) {
+            person = a.order[f.person_start + pi];
+            const int4 b = a.reach[person];
+            if (b.x <= tx1 && b.z >= tx0 && b.y <= ty1 && b.w >= ty0) {
+                const LabelRecord rec = a.records[person];
+                const int T = rec.thickness;
+                const bool plate = rec.ncells > 0 && rec.left <= tx1 && rec.left + rec.width - 1 >= tx0 && rec.top <= ty1 &&
+                                   rec.top + rec.height - 1 >= ty0;
+                const bool outer = T > 0 && rec.x1 <= tx1 && rec.x2 >= tx0 && rec.y1 <= ty1 && rec.y2 >= ty0;
+                const bool interior = tx0 >= rec.x1 + T && tx1 <= rec.x2 - T && ty0 >= rec.y1 + T && ty1 <= rec.y2 - T;
+                meets = plate || (outer && !interior);
+            }
+        }
+        const int np = block_compact(meets, wave_count, [&](int at) { recs[at] = a.records[person]; });   // (read again: it is in cache)
+        for (int k = 0; k < np && done != 15u; ++k) {
+            const LabelRecord &r = recs[k];
+            unsigned now = 0;
+            int best = LABEL_NONE;   // ink outnumbers plate and outline of the same person
+            const auto pixel = [&](int p, unsigned &c) {
+                if ((done >> p) & 1u) return;
+                const int cls = label_covers(r, px + (p & 1), py + (p >> 1));
+                if (cls == LABEL_NONE) return;
+                c = cls == LABEL_TEXT ? r.text_colour : r.colour;
+                now |= 1u << p;
+                best = max(best, cls);
+            };
+            pixel(0, c0), pixel(1, c1), pixel(2, c2), pixel(3, c3);
+            if (now != 0 && done == outside) first = best == LABEL_TEXT ? r.text_colour : r.colour;
+            done |= now;
+        }
+        if (__syncthreads_count(done != 15u) == 0) break;
+    }
+    const unsigned colour[4] = {c0, c1, c2, c3};
+    write_block(f, px, py, done & ~outside, colour, first);
+}
+
+hipError_t launch_draw_labels(const LabelArgs &a, hipStream_t s) {
+    if (a.n <= 0 || a.total_tiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(label_build_kernel, dim3((unsigned)((a.n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(label_raster_kernel, dim3((unsigned)a.total_tiles), dim3(kThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -22,6 +22,7 @@
 #include "letterbox_math.h"
 #include "pose_nms_math.h"
 #include "detector_nms_math.h"
+#include "draw_labels_math.h"
 #include "keypoint_eval_math.h"
 #include "kernels.h"
 #include "rotate_math.h"
@@ -801,6 +802,78 @@ const char *canvas_fault(const hrn_canvas &c) {
 }
 inline unsigned pack_colour(const uint8_t *c) { return (unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16); }
 inline size_t align16(size_t v) { return (v + 15) / 16 * 16; }
+
+extern "C++" {   // (a std::string result and a member template, inside this file's extern "C")
+// What is wrong with the canvases the n people of a call refer to, or "": a frame index out of range, a referenced canvas that
+// canvas_fault refuses, BGR and YUV canvases in one call, two referenced canvases that start at the same address.  (One writer
+// per byte needs canvases that do not overlap; overlapping views of one buffer cannot be told from here: the header forbids them.)
+std::string canvas_table_fault(const hrn_canvas *canvases, int nframes, int n, const int32_t *frame_index) {
+    int kind = -1;   // 0: BGR canvases, 1: YUV
+    for (int i = 0; i < n; ++i) {
+        const long f = frame_index ? (long)frame_index[i] : 0;
+        if (f < 0 || f >= nframes)
+            return "frame_index " + std::to_string(f) + " of person " + std::to_string(i) + " is outside [0, " + std::to_string(nframes) + ")";
+        if (const char *fault = canvas_fault(canvases[f]))
+            return "canvas " + std::to_string(f) + ", which person " + std::to_string(i) + " is drawn on, " + fault;
+        const int k = canvases[f].format == HRN_PIX_BGR ? 0 : 1;
+        if (kind >= 0 && k != kind)
+            return "canvas " + std::to_string(f) + ", which person " + std::to_string(i) +
+                   " is drawn on, mixes formats: the canvases of a call are all BGR or all YUV";
+        kind = k;
+    }
+    std::map<const uint8_t *, int> first_at;
+    for (int i = 0; i < n; ++i) {
+        const int f = frame_index ? frame_index[i] : 0;
+        const auto seen = first_at.emplace(canvases[f].y, f);
+        if (!seen.second && seen.first->second != f)
+            return "canvases " + std::to_string(seen.first->second) + " and " + std::to_string(f) +
+                   " name the same buffer: the canvases of a call must not overlap";
+    }
+    return "";
+}
+
+// The head of a drawing call's table, the same for hrn_draw_poses and hrn_draw_labels_dev: the canvases somebody refers to, in
+// table order, each with its tiles and its people; the people grouped by canvas in call order; everybody's canvas.  The entry's
+// own pieces follow from `end`.
+struct CanvasTable {
+    std::vector<int> slot, count;   // per canvas of the call: its DrawFrame or -1, its people
+    int used = 0;                   // DrawFrames
+    size_t off_order = 0, off_pframe = 0, end = 0;
+    CanvasTable(int nframes, int n, const int32_t *frame_index) : slot(nframes, -1), count(nframes, 0) {
+        for (int i = 0; i < n; ++i) ++count[frame_index ? frame_index[i] : 0];
+        for (int f = 0; f < nframes; ++f)
+            if (count[f]) slot[f] = used++;
+        off_order = align16((size_t)used * sizeof(DrawFrame)), off_pframe = off_order + align16((size_t)n * 4);
+        end = off_pframe + align16((size_t)n * 4);
+    }
+    // fills the three pieces at `pin`; size_of(canvas) goes into DrawFrame::radius; returns the tiles of the launch
+    template <class Size>
+    int fill(char *pin, const hrn_canvas *canvases, int n, const int32_t *frame_index, const Size &size_of) const {
+        DrawFrame *frames = (DrawFrame *)pin;
+        int *order = (int *)(pin + off_order), *pframe = (int *)(pin + off_pframe);
+        int tiles = 0, people = 0;
+        for (int f = 0; f < (int)slot.size(); ++f) {
+            if (slot[f] < 0) continue;
+            const hrn_canvas &c = canvases[f];
+            DrawFrame &d = frames[slot[f]];
+            d.p0 = c.y, d.p1 = c.format == HRN_PIX_BGR ? nullptr : c.u, d.p2 = c.format == HRN_PIX_I420 ? c.v : nullptr;
+            d.height = c.height, d.width = c.width, d.pitch0 = c.pitch_y, d.pitch1 = c.format == HRN_PIX_BGR ? 0 : c.pitch_c;
+            d.format = c.format;
+            d.radius = size_of(c);
+            d.tile_start = tiles, d.tiles_x = (c.width + kDrawTile - 1) / kDrawTile;
+            tiles += d.tiles_x * ((c.height + kDrawTile - 1) / kDrawTile);                      // (at most 256 x 256 per canvas)
+            d.person_start = people, d.person_count = 0;
+            people += count[f];
+        }
+        for (int i = 0; i < n; ++i) {
+            DrawFrame &d = frames[slot[frame_index ? frame_index[i] : 0]];
+            order[d.person_start + d.person_count++] = i;
+            pframe[i] = (int)(&d - frames);
+        }
+        return tiles;
+    }
+};
+}  // extern "C++"
 }  // namespace
 
 namespace {
@@ -830,68 +903,27 @@ int draw_poses(const char *entry, hrn_handle h, const hrn_canvas *canvases_host,
         if (skeleton_host[k] < 0 || skeleton_host[k] >= J)
             return fail("skeleton index " + std::to_string(skeleton_host[k]) + " of bone " + std::to_string(k / 2) + " is outside [0, " +
                         std::to_string(J) + ")");
-    int kind = -1;   // 0: BGR canvases, 1: YUV
-    for (int i = 0; i < n; ++i) {
-        const long f = frame_index_host ? (long)frame_index_host[i] : 0;
-        if (f < 0 || f >= nframes)
-            return fail("frame_index " + std::to_string(f) + " of person " + std::to_string(i) + " is outside [0, " + std::to_string(nframes) + ")");
-        if (const char *fault = canvas_fault(canvases_host[f]))
-            return fail("canvas " + std::to_string(f) + ", which person " + std::to_string(i) + " is drawn on, " + fault);
-        const int k = canvases_host[f].format == HRN_PIX_BGR ? 0 : 1;
-        if (kind >= 0 && k != kind)
-            return fail("canvas " + std::to_string(f) + ", which person " + std::to_string(i) +
-                        " is drawn on, mixes formats: the canvases of a call are all BGR or all YUV");
-        kind = k;
-    }
-    // one writer per byte needs canvases that do not overlap: two table entries people are drawn on that start at the same address
-    // are refused (overlapping views of one buffer cannot be told from here: the header forbids them)
-    std::map<const uint8_t *, int> first_at;
-    for (int i = 0; i < n; ++i) {
-        const int f = frame_index_host ? frame_index_host[i] : 0;
-        const auto seen = first_at.emplace(canvases_host[f].y, f);
-        if (!seen.second && seen.first->second != f)
-            return fail("canvases " + std::to_string(seen.first->second) + " and " + std::to_string(f) +
-                        " name the same buffer: the canvases of a call must not overlap");
-    }
+    const std::string fault = canvas_table_fault(canvases_host, nframes, n, frame_index_host);
+    if (!fault.empty()) return fail(fault);
     if (h->refuse_plan_only()) return 7;
     if (n == 0) return 0;
     if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
     hipStream_t s = (hipStream_t)stream;
 
-    // the canvases somebody refers to, in table order, and their people in call order
-    std::vector<int> slot(nframes, -1), count(nframes, 0);
-    for (int i = 0; i < n; ++i) ++count[frame_index_host ? frame_index_host[i] : 0];
-    int used = 0;
-    for (int f = 0; f < nframes; ++f)
-        if (count[f]) slot[f] = used++;
-    const size_t off_order = align16((size_t)used * sizeof(DrawFrame)), off_pframe = off_order + align16((size_t)n * 4),
-                 off_bone = off_pframe + align16((size_t)n * 4), off_point = off_bone + align16((size_t)n * 4),
+    // the canvases somebody refers to, in table order, and their people in call order (CanvasTable); then the entry's own pieces
+    const CanvasTable ct(nframes, n, frame_index_host);
+    const int used = ct.used;
+    const size_t off_order = ct.off_order, off_pframe = ct.off_pframe, off_bone = ct.end, off_point = off_bone + align16((size_t)n * 4),
                  off_skel = off_point + align16((size_t)Cp * 4), off_palette = off_skel + align16((size_t)std::max(K, 1) * 4),
                  table_bytes = off_palette + (ids_on_device ? align16((size_t)Cb * 4) : 0);   // (host ids: the table ends at off_palette)
     const PinnedImage img = h->image(table_bytes);
     if (!img) return 6;
     char *pin = img.ptr;
-    DrawFrame *frames = (DrawFrame *)pin;
-    int *order = (int *)(pin + off_order), *pframe = (int *)(pin + off_pframe);
     unsigned *bone = (unsigned *)(pin + off_bone), *point = (unsigned *)(pin + off_point), *skel = (unsigned *)(pin + off_skel);
-    int tiles = 0, people = 0;
-    for (int f = 0; f < nframes; ++f) {
-        if (slot[f] < 0) continue;
-        const hrn_canvas &c = canvases_host[f];
-        DrawFrame &d = frames[slot[f]];
-        d.p0 = c.y, d.p1 = c.format == HRN_PIX_BGR ? nullptr : c.u, d.p2 = c.format == HRN_PIX_I420 ? c.v : nullptr;
-        d.height = c.height, d.width = c.width, d.pitch0 = c.pitch_y, d.pitch1 = c.format == HRN_PIX_BGR ? 0 : c.pitch_c;
-        d.format = c.format;
-        d.radius = radius > 0 ? radius : std::max(1, std::min(c.height, c.width) / 160);   // (at most 8192 / 160 = 51)
-        d.tile_start = tiles, d.tiles_x = (c.width + kDrawTile - 1) / kDrawTile;
-        tiles += d.tiles_x * ((c.height + kDrawTile - 1) / kDrawTile);                      // (at most 256 x 256 per canvas)
-        d.person_start = people, d.person_count = 0;
-        people += count[f];
-    }
+    const int tiles = ct.fill(pin, canvases_host, n, frame_index_host, [&](const hrn_canvas &c) {
+        return radius > 0 ? radius : std::max(1, std::min(c.height, c.width) / 160);   // (at most 8192 / 160 = 51)
+    });
     for (int i = 0; i < n; ++i) {
-        DrawFrame &d = frames[slot[frame_index_host ? frame_index_host[i] : 0]];
-        order[d.person_start + d.person_count++] = i;
-        pframe[i] = (int)(&d - frames);
         const long id = person_index_host ? (long)person_index_host[i] : (long)i;
         bone[i] = ids_on_device ? 0u : pack_colour(bone_colors_host + 3 * (size_t)(((id % Cb) + Cb) % Cb));   // Python's modulo
     }
@@ -935,6 +967,87 @@ int hrn_draw_poses_ids_dev(hrn_handle h, const hrn_canvas *canvases_host, int nf
                            int thickness, float threshold, void *stream) {
     return draw_poses("hrn_draw_poses_ids_dev", h, canvases_host, nframes, pts_dev, n, J, frame_index_host, skeleton_host, K,
                       point_colors_host, Cp, bone_colors_host, Cb, nullptr, person_index_dev, true, radius, thickness, threshold, stream);
+}
+
+// ---- person labels: the box, the id and the score of every person drawn beside it (draw_labels_math.h, draw.hip) ----------------
+static thread_local std::string g_label_error;
+
+int hrn_label_layout(const int32_t *box, int has_id, int32_t id, int has_score, float score, int scale, int thickness,
+                     hrn_label_record *record_out) {
+    static_assert(sizeof(hrn_label_record) == sizeof(LabelRecord), "hrn_label_record is LabelRecord");
+    g_label_error.clear();
+    if (!box || !record_out) g_label_error = "null box / record";
+    else if (scale < 1 || scale > kLabelMaxScale) g_label_error = "scale must be in [1, " + std::to_string(kLabelMaxScale) + "]";
+    else if (thickness < 0 || thickness > kLabelMaxThickness)
+        g_label_error = "thickness must be in [0, " + std::to_string(kLabelMaxThickness) + "]";
+    if (!g_label_error.empty()) return 7;
+    const LabelRecord r = label_layout(box, has_id != 0, id, has_score != 0, score, scale, thickness);
+    memcpy(record_out, &r, sizeof(r));
+    return 0;
+}
+
+// 0: not covered, 1: the person's colour (plate or outline), 2: the person's text colour (ink); 7 on a bad record
+int hrn_label_covers(const hrn_label_record *record, int px, int py) {
+    g_label_error.clear();
+    if (!record) g_label_error = "null record";
+    else if (record->drawn && (record->scale < 1 || record->scale > kLabelMaxScale || record->thickness < 0 ||
+                               record->thickness > kLabelMaxThickness || record->ncells < 0 || record->ncells > kLabelMaxCells))
+        g_label_error = "the record is not one hrn_label_layout wrote";
+    if (!g_label_error.empty()) return 7;
+    LabelRecord r;
+    memcpy(&r, record, sizeof(r));
+    return label_covers(r, px, py);
+}
+
+const char *hrn_label_last_error(void) { return g_label_error.c_str(); }
+
+// the arguments are judged first (they need no device), then the handle; one table upload and two launches follow
+int hrn_draw_labels_dev(hrn_handle h, const hrn_canvas *canvases_host, int nframes, const int32_t *boxes_dev, const int32_t *ids_dev,
+                        const float *scores_dev, int score_stride, int n, const int32_t *frame_index_host, const uint8_t *colors_host,
+                        const uint8_t *text_colors_host, int Cb, int scale, int thickness, void *stream) {
+    if (!h) return 1;
+    const auto fail = [&](const std::string &what) {
+        h->err = "hrn_draw_labels_dev: " + what;
+        return 7;
+    };
+    if (n < 0) return fail("n is negative");
+    if (Cb < 1) return fail("Cb must be at least 1");
+    if (scale < 0 || scale > kLabelMaxScale) return fail("scale must be in [0, " + std::to_string(kLabelMaxScale) + "]");
+    if (thickness < 0 || thickness > kLabelMaxThickness) return fail("thickness must be in [0, " + std::to_string(kLabelMaxThickness) + "]");
+    if (scores_dev && score_stride < 1) return fail("score_stride must be at least 1");
+    if (!canvases_host || nframes < 1 || !colors_host || !text_colors_host || (n > 0 && !boxes_dev)) return fail("null canvases / boxes / colours");
+    if (!frame_index_host && nframes != 1) return fail("without frame_index there must be one frame");
+    const std::string fault = canvas_table_fault(canvases_host, nframes, n, frame_index_host);
+    if (!fault.empty()) return fail(fault);
+    if (h->refuse_plan_only()) return 7;
+    if (n == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+
+    const CanvasTable ct(nframes, n, frame_index_host);
+    const size_t off_colour = ct.end, off_text = off_colour + align16((size_t)Cb * 4), table_bytes = off_text + align16((size_t)Cb * 4);
+    const PinnedImage img = h->image(table_bytes);
+    if (!img) return 6;
+    const int tiles = ct.fill(img.ptr, canvases_host, n, frame_index_host, [&](const hrn_canvas &c) {
+        return scale > 0 ? scale : std::min(kLabelMaxScale, std::max(1, std::min(c.height, c.width) / 360));   // (the glyph scale)
+    });
+    for (int k = 0; k < Cb; ++k) {
+        img.as<unsigned>(off_colour)[k] = pack_colour(colors_host + 3 * (size_t)k);
+        img.as<unsigned>(off_text)[k] = pack_colour(text_colors_host + 3 * (size_t)k);
+    }
+    const size_t off_reach = (size_t)n * sizeof(LabelRecord), rec_bytes = off_reach + (size_t)n * sizeof(int4);
+    CallFrame frame(h, s, {{&h->draw_table, table_bytes, hrn_ctx::twice(table_bytes, 4096), "hipMalloc(draw table)"},
+                           {&h->draw_records, rec_bytes, hrn_ctx::twice(rec_bytes, 4096), "hipMalloc(draw records)"}});
+    char *table = frame.upload(img, table_bytes, "hipMemcpyAsync(draw table)"), *records = frame.dev(h->draw_records);
+    if (!table) return 6;
+    LabelArgs a{};
+    a.boxes = boxes_dev, a.ids = ids_dev, a.scores = scores_dev, a.score_stride = score_stride, a.n = n, a.Cb = Cb;
+    a.nframes = ct.used, a.total_tiles = tiles, a.thickness = thickness;
+    a.frames = (const DrawFrame *)table, a.order = (const int *)(table + ct.off_order), a.person_frame = (const int *)(table + ct.off_pframe);
+    a.colour = (const unsigned *)(table + off_colour), a.text_colour = (const unsigned *)(table + off_text);
+    a.records = (LabelRecord *)records, a.reach = (int4 *)(records + off_reach);
+    if (!h->hip_ok(launch_draw_labels(a, s), "label launch")) return 8;
+    return frame.leave() ? 0 : 6;
 }
 
 // find_person_id_associations and the demo's next_id update for P problems in one launch (assoc.hip); the arguments are judged

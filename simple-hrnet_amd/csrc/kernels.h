@@ -354,7 +354,7 @@ struct DrawFrame {                 // one canvas that at least one person refers
     unsigned char *p0, *p1, *p2;   // BGR: the pixels; NV12: Y, interleaved UV; I420: Y, U, V
     int height, width, pitch0, pitch1;
     int format;                    // HRN_PIX_BGR (0), HRN_PIX_NV12 (1) or HRN_PIX_I420 (2)
-    int radius;                    // of a joint's disc on this canvas
+    int radius;                    // of a joint's disc on this canvas (hrn_draw_labels_dev: the canvas's glyph scale)
     int tile_start, tiles_x;       // first tile of the launch that belongs to this canvas, tiles per tile row
     int person_start, person_count;   // its people: order[person_start .. + person_count), in call order
 };
@@ -374,6 +374,24 @@ struct DrawArgs {
     int4 *box;                     // n: bounding box of the live joints grown by max(radius, ceil(T / 2)); (1, 1, 0, 0) when nobody is
 };
 hipError_t launch_draw(const DrawArgs &a, hipStream_t s);   // draw_build_kernel, then draw_raster_kernel
+
+// Person labels (draw.hip; include/hrnet_mi355.h: hrn_draw_labels_dev; the arithmetic: draw_labels_math.h).  The table is
+// hrn_draw_poses' -- canvases, people by canvas -- with DrawFrame::radius holding the canvas's glyph scale, and the two palettes.
+struct LabelRecord;                // draw_labels_math.h
+struct LabelArgs {
+    const int *boxes;              // (n, 4) int32 (x1, y1, x2, y2), device: where the tracker / pre-path left them
+    const int *ids;                // n int32, device, or nullptr: the colour index is i and no id is printed
+    const float *scores;           // person i's score at scores[i * score_stride], device, or nullptr
+    int score_stride, n, Cb, nframes, total_tiles, thickness;
+    const DrawFrame *frames;       // nframes entries
+    const int *order;              // n person indices grouped by canvas, call order kept inside a canvas
+    const int *person_frame;       // n: index into frames
+    const unsigned *colour, *text_colour;   // Cb each: three bytes, byte 0 first
+    // written by the build launch, read by the rasteriser
+    LabelRecord *records;          // n
+    int4 *reach;                   // n: outline and plate together, corners inclusive; (1, 1, 0, 0): nothing to draw
+};
+hipError_t launch_draw_labels(const LabelArgs &a, hipStream_t s);   // label_build_kernel, then label_raster_kernel
 
 // The tracking link (track.hip; include/hrnet_mi355.h: hrn_boxes_from_poses, hrn_preprocess_frames_dev): boxes from the joints
 // where the decode left them, and the crop records of the pre-path from detections on the device -- one launch each.

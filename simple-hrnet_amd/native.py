@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .frames import (PIX_FORMATS, YUV_MATRICES, YUV_RANGES, Frames, YuvFrame, _bgr_rows, _check_frame, _frame_kind, as_tensor,  # noqa: F401
+from .frames import (NUMPY_DTYPES, PIX_FORMATS, YUV_MATRICES, YUV_RANGES, Frames, YuvFrame, _bgr_rows, _check_frame, _frame_kind, as_tensor,  # noqa: F401
                      device_tensor, frame_stack, host_array, host_bytes, rotation_code_from_degrees, rotation_codes)
 from .palettes import bgr_to_yuv_colors, embedded_palette, find_palette  # noqa: F401
 
@@ -611,6 +611,85 @@ class NativeHRNet:
         self._launch("hrn_draw_poses" if ids_dev is None else "hrn_draw_poses_ids_dev", table, len(items), pts.data_ptr(), n, joints,
                      None if fi is None else fi.ctypes.data, skel.ctypes.data if len(skel) else None, len(skel), pc.ctypes.data, len(pc),
                      bc.ctypes.data, len(bc), index, 0 if radius is None else int(radius), int(thickness), float(confidence_threshold))
+        return canvases[0] if single else list(canvases)
+
+    def draw_labels(self, frames, boxes, person_ids=None, scores=None, frame_index=None, palette="Set2", samples: int = 8,  # noqa: A002
+                    text_colors=None, scale: Optional[int] = None, thickness: int = 2):
+        """Every person's box, id and score drawn beside it, on the GPU (``hrn_draw_labels_dev``): the outline of ``boxes[i]``, and
+        above its top-left corner (inside it where there is no room above) a plate in the person's colour with the decimal digits
+        of ``person_ids[i]`` and of the score as a percentage -- formed, laid out and rasterised on the device in two launches,
+        with no host read: ids, boxes and scores are used where ``PersonTracker.update`` / ``predict_frame`` left them.  The
+        shapes are the integer definition of include/hrnet_mi355.h (5 x 7 dot-matrix digits); equality with cv2.putText is not
+        claimed.  Call it after ``draw_poses``: later drawing lies on top.
+
+        ``frames``: as in ``draw_poses`` -- a BGR tensor or array (rows may be strided), a ``YuvFrame``, or a list of either kind
+        with None for frames nobody is on; frames on the engine's GPU are drawn IN PLACE and returned, host frames are uploaded.
+        ``boxes``: (n, 4) or (4,) int32 (x1, y1, x2, y2); a person whose box is (0, 0, 0, 0) or degenerate is not drawn.
+        ``person_ids``: n int32 or None (no id is printed, colour index i; a negative id prints nothing); ``scores``: n float32 or
+        None, possibly a strided view such as ``dets[:, 4]``; tensors on the engine's GPU stay there, anything else is uploaded.
+        ``frame_index``: n frame numbers when there are several frames.  ``palette``: the people's colours, a matplotlib name or
+        (C, 3) uint8 BGR (``person_ids[i] % C``, as the bones of ``draw_poses``); ``text_colors``: (C, 3) uint8 BGR, default black
+        or white per colour by its luma ``(114 B + 587 G + 299 R) / 1000 >= 128``; both are converted with ``bgr_to_yuv_colors``
+        for ``YuvFrame``s.  ``scale``: pixels per glyph dot, 1..16 (default ``max(1, min(H, W) // 360)`` per frame, at most 16);
+        ``thickness``: of the outline, 0..16 (0: none)."""
+        single = not isinstance(frames, (list, tuple))
+        items = [frames] if single else list(frames)
+        if not items:
+            raise ValueError("draw_labels needs at least one frame")
+        dev = self.torch_device
+        canvases = Frames.canvases(items, dev)
+        table = canvases.table(kind=_lib.CanvasC)
+        if not isinstance(boxes, torch.Tensor):
+            boxes = np.asarray(boxes)
+        if (boxes.is_floating_point() or boxes.dtype == torch.bool) if isinstance(boxes, torch.Tensor) else boxes.dtype.kind not in "iu":
+            raise ValueError("boxes must be integers (the int32 boxes predict_frame / PersonTracker.update return)")
+        boxes = as_tensor(boxes, np.int32)
+        if boxes.dim() == 1:
+            boxes = boxes.unsqueeze(0)
+        if boxes.dim() != 2 or boxes.shape[1] != 4:
+            raise ValueError("boxes must be (4,) or (n, 4) (x1, y1, x2, y2)")
+        boxes = device_tensor(boxes, dev, torch.int32)
+        n = int(boxes.shape[0])
+
+        def per_person(x, dtype, what):
+            x = as_tensor(x, NUMPY_DTYPES[dtype]).reshape(-1)
+            if len(x) != n:
+                raise ValueError("%s must have one entry per person: %d for %d people" % (what, len(x), n))
+            return x.to(dev, dtype=dtype, non_blocking=True)
+
+        ids = None if person_ids is None else per_person(person_ids, torch.int32, "person_ids").contiguous()
+        stride = 1
+        if scores is not None:
+            scores = per_person(scores, torch.float32, "scores")     # a view such as dets[:, 4] is read where it lies
+            if n > 1 and scores.stride(0) < 1:
+                scores = scores.contiguous()
+            stride = int(scores.stride(0)) if n > 1 else 1
+        fi = None
+        if frame_index is not None:
+            fi = np.ascontiguousarray(np.asarray(frame_index, dtype=np.int32).reshape(-1))
+            if len(fi) != n:
+                raise ValueError("frame_index must have one entry per person: %d for %d people" % (len(fi), n))
+        elif len(items) != 1:
+            raise ValueError("several frames need frame_index: which frame each person is drawn on")
+        colours = _colors(palette, samples)
+        if text_colors is None:   # black on a light colour, white on a dark one: by the BGR luma, before any YUV conversion
+            wide = colours.astype(np.int64)
+            luma = (114 * wide[:, 0] + 587 * wide[:, 1] + 299 * wide[:, 2]) // 1000
+            text = np.where((luma >= 128)[:, None], np.uint8(0), np.uint8(255)).repeat(3, 1).astype(np.uint8)
+        else:
+            text = _colors(text_colors, 0)
+            if len(text) != len(colours):
+                raise ValueError("text_colors must have one colour per palette entry: %d for %d" % (len(text), len(colours)))
+        text = np.ascontiguousarray(text)
+        if canvases.yuv:
+            spaces = {(f.matrix, f.range) for f in canvases if f is not None}
+            if len(spaces) != 1:
+                raise ValueError("the YuvFrames of one draw_labels call share one matrix and range (the colours are converted once)")
+            (matrix, range_), = spaces
+            colours, text = bgr_to_yuv_colors(colours, matrix, range_), bgr_to_yuv_colors(text, matrix, range_)
+        self._launch("hrn_draw_labels_dev", table, len(items), boxes.data_ptr() if n else None, None if ids is None else ids.data_ptr(),
+                     None if scores is None else scores.data_ptr(), stride, n, None if fi is None else fi.ctypes.data,
+                     colours.ctypes.data, text.ctypes.data, len(colours), 0 if scale is None else int(scale), int(thickness))
         return canvases[0] if single else list(canvases)
 
     def resize_frames(self, frames, interpolation: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:

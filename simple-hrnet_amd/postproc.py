@@ -787,6 +787,43 @@ def pose_boxes(pts, frame_hw, threshold: float = 0.5, min_joints: int = 3, scale
     return out
 
 
+# -- person labels on the host: the record of one person and what it puts on a pixel ------------------------------------------------
+def label_layout(box, person_id=None, score=None, scale: int = 1, thickness: int = 2):
+    """The label of one person as ``NativeHRNet.draw_labels`` builds it on the device (``hrn_label_layout``, no GPU): a
+    ``_lib.LabelRecordC`` with the outline rectangle, the plate rectangle and the cells (``ncells``; cell k = four bits at 4 k of
+    ``cells_hi : cells_lo``, 0..9 a digit, 15 a blank).  ``box`` = (x1, y1, x2, y2) integers; ``person_id`` / ``score``: None = not
+    given; ``scale`` in [1, 16], ``thickness`` in [0, 16].  include/hrnet_mi355.h has the definition."""
+    import ctypes
+
+    from . import _lib
+
+    b = np.ascontiguousarray(np.asarray(box, dtype=np.int32).reshape(-1))
+    if b.shape != (4,):
+        raise ValueError("box must be (x1, y1, x2, y2)")
+    lib = _lib.load()
+    rec = _lib.LabelRecordC()
+    rc = lib.hrn_label_layout(b.ctypes.data, int(person_id is not None), 0 if person_id is None else int(person_id),
+                              int(score is not None), ctypes.c_float(0.0 if score is None else score), int(scale), int(thickness),
+                              ctypes.byref(rec))
+    if rc != 0:
+        raise ValueError("hrn_label_layout: " + lib.hrn_label_last_error().decode())
+    return rec
+
+
+def label_covers(record, px: int, py: int) -> int:
+    """What the label ``record`` (of ``label_layout``) puts on pixel (px, py): 0 nothing, 1 the person's colour (plate or outline),
+    2 the person's text colour (ink) -- ``hrn_label_covers``, the function the rasteriser compiles."""
+    import ctypes
+
+    from . import _lib
+
+    lib = _lib.load()
+    rc = lib.hrn_label_covers(ctypes.byref(record), int(px), int(py))
+    if rc not in (0, 1, 2):
+        raise ValueError("hrn_label_covers: " + lib.hrn_label_last_error().decode())
+    return rc
+
+
 # -- the detector link on the host: letterbox geometry and the detector's boxes back in frame coordinates -------------------------
 LETTERBOX_RULES = {"yolov3": 0, "yolov5": 1}     # include/hrnet_mi355.h: HRN_LETTERBOX_MAX_SIDE / _MIN_RATIO
 LETTERBOX_PAD = {"yolov3": 128, "yolov5": 114}   # the wrappers' border: 127.5 is 128 under cv2's round-half-even saturation

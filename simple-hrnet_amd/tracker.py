@@ -25,6 +25,7 @@ class PersonTracker:
     demo: ids ``arange(n)`` and ``next_id = n + 1`` per stream that has somebody (no kernel; a first frame without people leaves
     ``next_id`` at 0, as the demo does).  An update with nobody keeps ``next_id`` and stores empty arrays.  ``status`` holds the
     last association's status per stream (None before), ``next_id`` the counters; ``reset()`` forgets everything.
+    Behind an update, on the frame: ``net.draw_poses(frame, pts, skeleton, person_ids=ids)``; ``net.draw_labels(frame, boxes, ids)``.
 
     ``one_euro``: None, or ``dict(min_cutoff, beta, d_cutoff, threshold, rate=30.0)`` (any subset; the rest are
     ``filter_poses``' defaults): every update is then followed by ONE ``filter_poses`` call whose state follows the people
