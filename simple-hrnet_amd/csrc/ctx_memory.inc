@@ -261,15 +261,20 @@
         return (int)span + 2 * wp + 2;
     }
 
+    // 16-pixel fragments per wave of a grouped generic launch: shorter M tiles for small launches (fill the chip, shorten the
+    // serial K loop per block)
+    int direct_mr(const DirectGroup &g, int nb) const {
+        int mr = 4;
+        while (mr > 1 && direct_group_blocks(g, nb, nullptr, mr) < 512) mr >>= 1;
+        return mr;
+    }
+
     bool setup_dgroups() {
-        for (auto &g : dgroups) {
+        for (auto &g : dgroups)
             // M tiles shrink (mr 4 -> 2 -> 1) only while a launch has fewer than 512 blocks: 4x that bounds every case
-            g.map_capacity = std::max<int64_t>(direct_group_blocks(g, max_batch, nullptr), 4 * 512 + 64 * (int64_t)g.conv_idx.size() * 8);
-            for (MapSlot &sl : g.slot) {
-                if (!alloc_slot(sl, g.map_capacity, g.conv_idx.size())) return false;
-                workspace_bytes += g.map_capacity * (int64_t)sizeof(int2) + (int64_t)(g.conv_idx.size() * sizeof(ConvArgs));
-            }
-        }
+            if (!alloc_maps(g.maps, std::max<int64_t>(direct_group_blocks(g, max_batch, nullptr), 4 * 512 + 64 * (int64_t)g.conv_idx.size() * 8),
+                            g.conv_idx.size()))
+                return false;
         return true;
     }
 
@@ -389,35 +394,62 @@
                     pt.cout = cv.cout, pt.ch0 = pr.parts[i].second * 16 * nf, pt.relu = cv.relu;
                 }
             }
-            g.map_capacity = 64;
-            for (auto &pr : g.probs) g.map_capacity += (int64_t)max_batch * pr.tiles_per_image;  // one tile per block bounds every split
-            for (MapSlot &sl : g.slot) {
-                if (!alloc_slot(sl, g.map_capacity, 0)) return false;
-                workspace_bytes += g.map_capacity * (int64_t)sizeof(int2);
-            }
+            int64_t capacity = 64;
+            for (auto &pr : g.probs) capacity += (int64_t)max_batch * pr.tiles_per_image;  // one tile per block bounds every split
+            if (!alloc_maps(g.maps, capacity)) return false;
         }
         if (!hip_ok(hipMalloc((void **)&s2probs_dev, nprob * sizeof(S2Problem)), "hipMalloc(s2 problems)")) return false;
         return hip_ok(hipMemcpy(s2probs_dev, hp.data(), nprob * sizeof(S2Problem), hipMemcpyHostToDevice), "hipMemcpy(s2 problems)");
     }
 
-    bool alloc_slot(MapSlot &sl, int64_t capacity, size_t nargs) {
-        if (!hip_ok(hipMalloc((void **)&sl.dev, (size_t)capacity * sizeof(int2)), "hipMalloc(blockmap)")) return false;
-        if (!hip_ok(hipHostMalloc((void **)&sl.pin, (size_t)capacity * sizeof(int2), hipHostMallocDefault), "hipHostMalloc(blockmap)"))
-            return false;
-        if (nargs) {
-            if (!hip_ok(hipMalloc((void **)&sl.args_dev, nargs * sizeof(ConvArgs)), "hipMalloc(conv args)")) return false;
-            if (!hip_ok(hipHostMalloc((void **)&sl.args_pin, nargs * sizeof(ConvArgs), hipHostMallocDefault), "hipHostMalloc(conv args)"))
+    // ---- the block-map cache of a grouped launch (BlockMaps, ctx_types.h): every slot holds `capacity` blocks and, for the
+    // generic kernel, `nargs` descriptors; all of it counts as workspace
+    bool alloc_maps(BlockMaps &m, int64_t capacity, size_t nargs = 0) {
+        m.capacity = capacity, m.nargs = nargs;
+        for (MapSlot &sl : m.slot) {
+            if (!hip_ok(hipMalloc((void **)&sl.dev, (size_t)capacity * sizeof(int2)), "hipMalloc(blockmap)")) return false;
+            if (!hip_ok(hipHostMalloc((void **)&sl.pin, (size_t)capacity * sizeof(int2), hipHostMallocDefault), "hipHostMalloc(blockmap)"))
                 return false;
+            if (nargs) {
+                if (!hip_ok(hipMalloc((void **)&sl.args_dev, nargs * sizeof(ConvArgs)), "hipMalloc(conv args)")) return false;
+                if (!hip_ok(hipHostMalloc((void **)&sl.args_pin, nargs * sizeof(ConvArgs), hipHostMallocDefault), "hipHostMalloc(conv args)"))
+                    return false;
+            }
+            if (!hip_ok(hipEventCreateWithFlags(&sl.landed, hipEventDisableTiming), "hipEventCreate")) return false;
+            workspace_bytes += capacity * (int64_t)sizeof(int2) + (int64_t)(nargs * sizeof(ConvArgs));
         }
-        return hip_ok(hipEventCreateWithFlags(&sl.landed, hipEventDisableTiming), "hipEventCreate");
+        return true;
     }
-    void free_slot(MapSlot &sl) {
-        if (sl.dev) (void)hipFree(sl.dev);
-        if (sl.pin) (void)hipHostFree(sl.pin);
-        if (sl.args_dev) (void)hipFree(sl.args_dev);
-        if (sl.args_pin) (void)hipHostFree(sl.args_pin);
-        if (sl.landed) (void)hipEventDestroy(sl.landed);
-        sl = MapSlot();
+    void free_maps(BlockMaps &m) {
+        for (MapSlot &sl : m.slot) {
+            if (sl.dev) (void)hipFree(sl.dev);
+            if (sl.pin) (void)hipHostFree(sl.pin);
+            if (sl.args_dev) (void)hipFree(sl.args_dev);
+            if (sl.args_pin) (void)hipHostFree(sl.args_pin);
+            if (sl.landed) (void)hipEventDestroy(sl.landed);
+            sl = MapSlot();
+        }
+    }
+    // The slot holding the map of micro-batch size nb, ready for a launch on stream s (*out), or the error.  A miss runs
+    // `build(slot, &scratch)` -- it fills the scratch (the generic kernel: also the slot's mr and args_pin) and returns the
+    // block count -- and uploads on s: descriptors, then the map, then `landed`.  The slot takes its nb only after all of
+    // that was queued: whatever fails on the way leaves it at nb == -1, and the next call builds again.
+    template <class Build>
+    hipError_t acquire_maps(BlockMaps &m, int nb, hipStream_t s, MapSlot **out, const Build &build) {
+        bool hit;
+        MapSlot *sl = *out = find_slot(m.slot, nb, &hit);
+        hipError_t e = slot_ready(sl, hit, s);
+        if (hit || e != hipSuccess) return e;
+        sl->nblocks = build(sl, &m.host);
+        if (sl->nblocks > m.capacity) return hipErrorInvalidValue;   // (ADVICE r3: never write past the slot)
+        memcpy(sl->pin, m.host.data(), (size_t)sl->nblocks * sizeof(int2));
+        if (m.nargs) e = hipMemcpyAsync(sl->args_dev, sl->args_pin, m.nargs * sizeof(ConvArgs), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(sl->dev, sl->pin, (size_t)sl->nblocks * sizeof(int2), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipEventRecord(sl->landed, s);
+        if (e != hipSuccess) return e;
+        sl->nb = nb;
+        ++map_builds;
+        return hipSuccess;
     }
     // the slot holding the maps of micro-batch size nb, or the least recently used one to rebuild (*hit = false); a
     // slot about to be rebuilt has had its previous upload waited for, so its pinned image may be rewritten
@@ -508,18 +540,15 @@
         if (!nprob) return true;
         std::vector<Conv3Problem> &hp = probs_host;
         for (auto &g : groups) {
-            g.map_capacity = 64 + 4 * (int64_t)std::max(small_below, 256) + 1024;  // one M tile per block = most blocks any split can produce (+ the small-tile mode)
+            int64_t capacity = 64 + 4 * (int64_t)std::max(small_below, 256) + 1024;  // one M tile per block = most blocks any split can produce (+ the small-tile mode)
             for (int ci : g.conv_idx) {
                 const ConvOp &cv = convs[ci];
                 const Tensor &to = tensors[cv.out_t];
                 // (128-pixel tiles whenever a knob may ask for them: HRN_F32_SMALL_SLICES -- ADVICE r3)
                 const int bm = f32_small_slices > 0 ? 128 : conv3x3_lds_bm(cv.ks, cv.nr, to.wp);
-                g.map_capacity += (int64_t)((max_batch * to.hpwp + bm - 1) / bm) * cv.ntiles;   // (compact convolutions have fewer)
+                capacity += (int64_t)((max_batch * to.hpwp + bm - 1) / bm) * cv.ntiles;   // (compact convolutions have fewer)
             }
-            for (MapSlot &sl : g.slot) {
-                if (!alloc_slot(sl, g.map_capacity, 0)) return false;
-                workspace_bytes += g.map_capacity * (int64_t)sizeof(int2);
-            }
+            if (!alloc_maps(g.maps, capacity)) return false;
         }
         if (!hip_ok(hipMalloc((void **)&probs_dev, nprob * sizeof(Conv3Problem)), "hipMalloc(problems)")) return false;
         return hip_ok(hipMemcpy(probs_dev, hp.data(), nprob * sizeof(Conv3Problem), hipMemcpyHostToDevice),
@@ -540,13 +569,10 @@
             if (part_idx) (void)hipFree(part_idx);
             if (probs_dev) (void)hipFree(probs_dev);
             if (s2probs_dev) (void)hipFree(s2probs_dev);
-            for (auto &g : s2groups)
-                for (MapSlot &sl : g.slot) free_slot(sl);
-            for (MapSlot &sl : stemf.slot) free_slot(sl);
-            for (auto &g : groups)
-                for (MapSlot &sl : g.slot) free_slot(sl);
-            for (auto &g : dgroups)
-                for (MapSlot &sl : g.slot) free_slot(sl);
+            for (auto &g : s2groups) free_maps(g.maps);
+            free_maps(stemf.maps);
+            for (auto &g : groups) free_maps(g.maps);
+            for (auto &g : dgroups) free_maps(g.maps);
         }
         blob = nullptr;
     }

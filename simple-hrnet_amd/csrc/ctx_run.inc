@@ -6,15 +6,17 @@
         std::vector<hipEvent_t> ev;  // ops.size()+1 events
     };
 
+    // every other launch walks its tensors backwards: it starts on what its producer wrote last, i.e. on the
+    // part most likely still in the Infinity Cache (256 MB; a 256-crop tensor is up to 0.9 GB)
+    bool walks_back(size_t oi) const { return alternate && (oi & 1); }
+
     bool run_pass(const float *images, int nb, const void *boxes, int box_dtype, float *pts, float *heatmaps,
                   hipStream_t s, Timing *tm, int flip = 0, const TapReq *tap = nullptr, int refine = RF_NONE) {
         if (tm && !hip_ok(hipEventRecord(tm->ev[0], s), "hipEventRecord")) return false;
         // the fused stem writes conv2's output only: a call that taps "stem" (ops[0]'s tensor) takes the two launches
         const bool fused_stem = stem_fuse && !(tap && tap->op == 0);
         for (size_t oi = 0; oi < ops.size(); ++oi) {
-            // every other launch walks its tensors backwards: it starts on what its producer wrote last, i.e. on the
-            // part most likely still in the Infinity Cache (256 MB; a 256-crop tensor is up to 0.9 GB)
-            const bool rev = alternate && (oi & 1);
+            const bool rev = walks_back(oi);
             hipError_t e = hipSuccess;
             if (fused_stem && oi == 0)
                 e = exec_stem_fused(images, nb, s, flip);
@@ -34,60 +36,60 @@
         return true;
     }
 
-    hipError_t exec_stem_fused(const float *images, int nb, hipStream_t s, int flip) {
-        S2Group &g = stemf;
-        bool hit;
-        MapSlot *sl = find_slot(g.slot, nb, &hit);
-        hipError_t e = slot_ready(sl, hit, s);
-        if (e != hipSuccess) return e;
-        if (!hit) {
-            sl->nblocks = s2_blocks(g, nb, &g.map_host);
-            if (sl->nblocks > g.map_capacity) return hipErrorInvalidValue;
-            memcpy(sl->pin, g.map_host.data(), (size_t)sl->nblocks * sizeof(int2));
-            e = hipMemcpyAsync(sl->dev, sl->pin, (size_t)sl->nblocks * sizeof(int2), hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipEventRecord(sl->landed, s);
-            if (e != hipSuccess) return e;
-            sl->nb = nb;
-            ++map_builds;
-        }
+    // the three hand-scheduled kernel families have one launcher per element format (fp16: the same kernels instantiated with
+    // fp16 elements, *_f16.hip): picked by dtype here, as the other launchers of kernels.h do themselves
+    static hipError_t launch_conv3x3_lds(int dtype, const Conv3Problem *probs, const void *map, int nblocks, int nb, int ks, int nrb,
+                                         hipStream_t s) {
+        return (dtype == HRN_F16 ? hrn::launch_conv3x3_lds_f16 : hrn::launch_conv3x3_lds)(probs, map, nblocks, nb, ks, nrb, s);
+    }
+    static hipError_t launch_conv_s2(int dtype, const S2Problem *probs, const void *map, int nblocks, hipStream_t s) {
+        return (dtype == HRN_F16 ? hrn::launch_conv_s2_f16 : hrn::launch_conv_s2)(probs, map, nblocks, s);
+    }
+    static hipError_t launch_bottleneck_chain(int dtype, const ChainArgs &a, hipStream_t s) {
+        return (dtype == HRN_F16 ? hrn::launch_bottleneck_chain_f16 : hrn::launch_bottleneck_chain)(a, s);
+    }
+
+    // conv1's arguments (StemArgs and Stem7Args carry the same fields): `out` = its tensor, `w` = the fp32 weights, `wp` = their
+    // MFMA image (nullptr: the kernel takes `w`)
+    template <class Args>
+    Args stem_args(const float *images, int nb, int flip, void *out, const float *w, const void *wp) const {
         const Tensor &t = tensors[stem_out_t];
-        StemArgs a;
-        a.images = images, a.out = nullptr;
-        a.w = nullptr, a.bias = (const float *)(blob + stem_b_off), a.wp = (const void *)(blob + stem_wp_off);
+        Args a;
+        a.images = images, a.out = out;
+        a.w = w, a.bias = (const float *)(blob + stem_b_off), a.wp = wp;
         a.n = nb, a.H = H, a.W = W;
         a.out_h = t.h, a.out_w = t.w, a.out_wp = t.wp, a.out_hpwp = t.hpwp;
         a.flip = flip;
+        return a;
+    }
+    // ... of conv1's own launch
+    template <class Args>
+    Args stem_args(const float *images, int nb, int flip) const {
+        return stem_args<Args>(images, nb, flip, row0(stem_out_t), (const float *)(blob + stem_w_off),
+                               (is16() && !disable_stem_mfma) ? (const void *)(blob + stem_wp_off) : nullptr);
+    }
+
+    hipError_t exec_stem_fused(const float *images, int nb, hipStream_t s, int flip) {
+        S2Group &g = stemf;
+        MapSlot *sl = nullptr;
+        hipError_t e = acquire_maps(g.maps, nb, s, &sl, [&](MapSlot *, std::vector<int2> *map) { return s2_blocks(g, nb, map); });
+        if (e != hipSuccess) return e;
+        // (conv1 writes no tensor and reads no fp32 weights here: always the MFMA image)
+        const StemArgs a = stem_args<StemArgs>(images, nb, flip, nullptr, nullptr, (const void *)(blob + stem_wp_off));
         return launch_stem_fused(dtype, s2probs_dev + g.prob_first, sl->dev, sl->nblocks, a, s);
     }
 
     hipError_t exec_op(const Op &op, bool rev, const float *images, int nb, const void *boxes, int box_dtype, float *pts,
                        float *heatmaps, hipStream_t s, int flip, int refine) {
         hipError_t e = hipSuccess;
+        MapSlot *sl = nullptr;
         switch (op.kind) {
-        case OP_STEM: {
-            const Tensor &t = tensors[stem_out_t];
-            StemArgs a;
-            a.images = images, a.out = row0(stem_out_t);
-            a.w = (const float *)(blob + stem_w_off), a.bias = (const float *)(blob + stem_b_off);
-            a.wp = (is16() && !disable_stem_mfma) ? (const void *)(blob + stem_wp_off) : nullptr;
-            a.n = nb, a.H = H, a.W = W;
-            a.out_h = t.h, a.out_w = t.w, a.out_wp = t.wp, a.out_hpwp = t.hpwp;
-            a.flip = flip;
-            e = launch_stem(dtype, a, s);
+        case OP_STEM:
+            e = launch_stem(dtype, stem_args<StemArgs>(images, nb, flip), s);
             break;
-        }
-        case OP_STEM7: {
-            const Tensor &t = tensors[stem_out_t];
-            Stem7Args a;
-            a.images = images, a.out = row0(stem_out_t);
-            a.w = (const float *)(blob + stem_w_off), a.bias = (const float *)(blob + stem_b_off);
-            a.wp = (is16() && !disable_stem_mfma) ? (const void *)(blob + stem_wp_off) : nullptr;
-            a.n = nb, a.H = H, a.W = W;
-            a.out_h = t.h, a.out_w = t.w, a.out_wp = t.wp, a.out_hpwp = t.hpwp;
-            a.flip = flip;
-            e = launch_stem7(dtype, a, s);
+        case OP_STEM7:
+            e = launch_stem7(dtype, stem_args<Stem7Args>(images, nb, flip), s);
             break;
-        }
         case OP_MAXPOOL: {
             const Tensor &ti = tensors[pool_in_t], &to = tensors[pool_out_t];
             PoolArgs a;
@@ -103,59 +105,26 @@
             e = launch_conv(dtype, a, cv.nr, s);
             break;
         }
-        case OP_CONV3_GROUP: {
+        case OP_CONV3_GROUP: {   // block map depends on the micro-batch size: built once per size (kMapSlots sizes kept)
             Conv3Group &g = groups[op.idx];
-            bool hit;
-            MapSlot *sl = find_slot(g.slot, nb, &hit);
-            if ((e = slot_ready(sl, hit, s)) != hipSuccess) break;
-            if (!hit) {  // block map depends on the micro-batch size: build it once per size (kMapSlots sizes kept)
-                sl->nblocks = group_blocks(g, nb, &g.map_host, rev);
-                if (sl->nblocks > g.map_capacity) {   // (ADVICE r3: never write past the slot)
-                    e = hipErrorInvalidValue;
-                    break;
-                }
-                memcpy(sl->pin, g.map_host.data(), (size_t)sl->nblocks * sizeof(int2));
-                e = hipMemcpyAsync(sl->dev, sl->pin, (size_t)sl->nblocks * sizeof(int2), hipMemcpyHostToDevice, s);
-                if (e == hipSuccess) e = hipEventRecord(sl->landed, s);
-                if (e != hipSuccess) break;
-                sl->nb = nb;
-                ++map_builds;
-            }
-            // (fp16: the same kernels instantiated with fp16 elements, conv3x3_lds_f16.hip)
-            e = (dtype == HRN_F16 ? launch_conv3x3_lds_f16 : launch_conv3x3_lds)(probs_dev + g.prob_first, sl->dev, sl->nblocks, nb,
-                                                                             convs[g.conv_idx[0]].ks, convs[g.conv_idx[0]].nr, s);
+            e = acquire_maps(g.maps, nb, s, &sl, [&](MapSlot *, std::vector<int2> *map) { return group_blocks(g, nb, map, rev); });
+            if (e != hipSuccess) break;
+            e = launch_conv3x3_lds(dtype, probs_dev + g.prob_first, sl->dev, sl->nblocks, nb, convs[g.conv_idx[0]].ks, convs[g.conv_idx[0]].nr, s);
             break;
         }
-        case OP_CONV_GROUP: {
+        case OP_CONV_GROUP: {   // descriptors (row counts), M tile and block map depend on the micro-batch size
             DirectGroup &g = dgroups[op.idx];
-            bool hit;
-            MapSlot *sl = find_slot(g.slot, nb, &hit);
-            if ((e = slot_ready(sl, hit, s)) != hipSuccess) break;
-            if (!hit) {  // descriptors (row counts) and block map depend on the micro-batch size
-                for (size_t k = 0; k < g.conv_idx.size(); ++k) sl->args_pin[k] = conv_args(convs[g.conv_idx[k]], nb, rev);
-                sl->mr = 4;  // shorter M tiles for small launches: fill the chip, shorten the serial K loop per block
-                while (sl->mr > 1 && direct_group_blocks(g, nb, nullptr, sl->mr) < 512) sl->mr >>= 1;
-                sl->nblocks = direct_group_blocks(g, nb, &g.map_host, sl->mr);
-                if (sl->nblocks > g.map_capacity) {   // (ADVICE r3: never write past the slot)
-                    e = hipErrorInvalidValue;
-                    break;
-                }
-                memcpy(sl->pin, g.map_host.data(), (size_t)sl->nblocks * sizeof(int2));
-                e = hipMemcpyAsync(sl->args_dev, sl->args_pin, g.conv_idx.size() * sizeof(ConvArgs), hipMemcpyHostToDevice, s);
-                if (e == hipSuccess)
-                    e = hipMemcpyAsync(sl->dev, sl->pin, (size_t)sl->nblocks * sizeof(int2), hipMemcpyHostToDevice, s);
-                if (e == hipSuccess) e = hipEventRecord(sl->landed, s);
-                if (e != hipSuccess) break;
-                sl->nb = nb;
-                ++map_builds;
-            }
-            {
-                int wl = direct_wlds && is16() ? 1 : 0;   // 2: a member takes the XL form (its LDS layout is the larger one)
-                if (wl)
-                    for (int ci : g.conv_idx)
-                        if (conv_xl(convs[ci])) wl = 2;
-                e = launch_conv_group(dtype, sl->args_dev, sl->dev, sl->nblocks, g.nr, sl->mr, wl, s);
-            }
+            e = acquire_maps(g.maps, nb, s, &sl, [&](MapSlot *slot, std::vector<int2> *map) {
+                for (size_t k = 0; k < g.conv_idx.size(); ++k) slot->args_pin[k] = conv_args(convs[g.conv_idx[k]], nb, rev);
+                slot->mr = direct_mr(g, nb);
+                return direct_group_blocks(g, nb, map, slot->mr);
+            });
+            if (e != hipSuccess) break;
+            int wl = direct_wlds && is16() ? 1 : 0;   // 2: a member takes the XL form (its LDS layout is the larger one)
+            if (wl)
+                for (int ci : g.conv_idx)
+                    if (conv_xl(convs[ci])) wl = 2;
+            e = launch_conv_group(dtype, sl->args_dev, sl->dev, sl->nblocks, g.nr, sl->mr, wl, s);
             break;
         }
         case OP_S2_GROUP: {
@@ -167,23 +136,9 @@
                 }
                 break;
             }
-            bool hit;
-            MapSlot *sl = find_slot(g.slot, nb, &hit);
-            if ((e = slot_ready(sl, hit, s)) != hipSuccess) break;
-            if (!hit) {
-                sl->nblocks = s2_blocks(g, nb, &g.map_host);
-                if (sl->nblocks > g.map_capacity) {
-                    e = hipErrorInvalidValue;
-                    break;
-                }
-                memcpy(sl->pin, g.map_host.data(), (size_t)sl->nblocks * sizeof(int2));
-                e = hipMemcpyAsync(sl->dev, sl->pin, (size_t)sl->nblocks * sizeof(int2), hipMemcpyHostToDevice, s);
-                if (e == hipSuccess) e = hipEventRecord(sl->landed, s);
-                if (e != hipSuccess) break;
-                sl->nb = nb;
-                ++map_builds;
-            }
-            e = (dtype == HRN_F16 ? launch_conv_s2_f16 : launch_conv_s2)(s2probs_dev + g.prob_first, sl->dev, sl->nblocks, s);
+            e = acquire_maps(g.maps, nb, s, &sl, [&](MapSlot *, std::vector<int2> *map) { return s2_blocks(g, nb, map); });
+            if (e != hipSuccess) break;
+            e = launch_conv_s2(dtype, s2probs_dev + g.prob_first, sl->dev, sl->nblocks, s);
             break;
         }
         case OP_CHAIN: {
@@ -211,7 +166,7 @@
                 a.res = nullptr;
             }
             a.m = nb * to.hpwp, a.h = to.h, a.w = to.w, a.wp = to.wp, a.hpwp = to.hpwp, a.rev = rev, a.max_blocks = chain_blocks;
-            e = dtype == HRN_F16 ? launch_bottleneck_chain_f16(a, s) : launch_bottleneck_chain(a, s);
+            e = launch_bottleneck_chain(dtype, a, s);
             break;
         }
         case OP_FUSE: {

@@ -59,6 +59,13 @@ struct MapSlot {
     hipStream_t up_stream = nullptr;   // the stream the upload went out on: a hit from ANOTHER stream waits for `landed` first
     uint64_t stamp = 0;
 };
+// the cache of one grouped launch (hrn_ctx::acquire_maps owns the order of its calls)
+struct BlockMaps {
+    int64_t capacity = 0;        // blocks a slot holds: the group's bound at max_batch
+    size_t nargs = 0;            // descriptors per slot (generic kernel only)
+    MapSlot slot[kMapSlots];
+    std::vector<int2> host;      // scratch of the group's map builder
+};
 
 // a set of independent LDS-staged 3x3 convolutions issued as ONE launch (conv3x3_lds.hip)
 struct Conv3Group {
@@ -66,18 +73,14 @@ struct Conv3Group {
     std::vector<int> fused_prob;  // per member: index (within the group) of its fused-BasicBlock descriptor, or -1
     int prob_first = 0;          // index of the group's first descriptor in the device array
     int max_wp = 0;
-    int64_t map_capacity = 0;    // blocks at max_batch
-    MapSlot slot[kMapSlots];
-    std::vector<int2> map_host;  // scratch of group_blocks()
+    BlockMaps maps;              // built by group_blocks()
 };
 
 // a set of independent convolutions on the generic kernel issued as ONE launch (kernels.hip: conv_direct_group_kernel)
 struct DirectGroup {
     std::vector<int> conv_idx;
     int nr = 0;
-    int64_t map_capacity = 0;
-    MapSlot slot[kMapSlots];
-    std::vector<int2> map_host;  // scratch of direct_group_blocks()
+    BlockMaps maps;              // built by direct_group_blocks(), with the descriptors (conv_args) and mr of that size
 };
 
 struct Op {
@@ -98,9 +101,7 @@ struct S2Group {
     std::vector<Prob> probs;
     std::vector<Op> fallback;
     int prob_first = 0;
-    int64_t map_capacity = 0;
-    MapSlot slot[kMapSlots];
-    std::vector<int2> map_host;
+    BlockMaps maps;              // built by s2_blocks()
 };
 
 struct FuseOp {

@@ -44,6 +44,20 @@ const char *env_sw(const char *name) {
     }
     return v;
 }
+// the three ways a switch is read (ctx_switches.inc), each looking its variable up once
+bool sw_set(const char *name) { return env_sw(name) != nullptr; }
+int sw_int(const char *name, int dflt) {
+    const char *v = env_sw(name);
+    return v ? atoi(v) : dflt;
+}
+double sw_real(const char *name, double dflt) {
+    const char *v = env_sw(name);
+    return v ? atof(v) : dflt;
+}
+bool sw_zero(const char *name) {   // set, and reads as 0: what turns off a switch that is on by default
+    const char *v = env_sw(name);
+    return v && atoi(v) == 0;
+}
 }  // namespace
 
 struct hrn_ctx {
@@ -81,74 +95,15 @@ struct hrn_ctx {
     char *blob = nullptr;  // device (or host when plan_only)
     bool weights_loaded = false;
 
-    bool disable_lds = env_sw("HRN_DISABLE_LDS") != nullptr;
-    bool assoc_no_assign = env_sw("HRN_ASSOC_NO_ASSIGN") != nullptr;   // timing only: hrn_associate_people_dev skips its assignment phase
-    bool disable_group = env_sw("HRN_DISABLE_GROUP") != nullptr;
-    bool disable_dgroup = env_sw("HRN_DISABLE_DGROUP") != nullptr;
-    bool disable_chain = env_sw("HRN_DISABLE_CHAIN") != nullptr;
-    bool small_tiles = env_sw("HRN_SMALL_TILES") ? atoi(env_sw("HRN_SMALL_TILES")) != 0 : true;
-    int small_below = env_sw("HRN_SMALL_BELOW") ? atoi(env_sw("HRN_SMALL_BELOW")) : 384;
-    int small_keep_above = env_sw("HRN_SMALL_KEEP") ? atoi(env_sw("HRN_SMALL_KEEP")) : 300;   // (0: every convolution of a small launch takes 128-pixel tiles, round 5's rule)
-    bool disable_chain_ds = env_sw("HRN_DISABLE_CHAIN_DS") != nullptr;
-    // generic conv kernel, bf16: the block's weights through LDS instead of one copy per wave from L2 (+1.6 % on the pass)
-    // residual-prefetch variant of the K = 64 1x1 convs; persistent blocks of a chain-kernel launch (read here, at create,
-    // like every other switch -- not in a function-local static at the first launch)
-    int pre_mode = env_sw("HRN_PRE_MODE") ? atoi(env_sw("HRN_PRE_MODE")) : 1;
-    int chain_blocks = env_sw("HRN_CHAIN_BLOCKS") ? atoi(env_sw("HRN_CHAIN_BLOCKS")) : 512;
-    // round 5: the 3x3 conv of a Bottleneck without projection shortcut in front of its conv3 inside the chain kernel (off: its own launch)
-    bool disable_chain3 = env_sw("HRN_DISABLE_CHAIN3") != nullptr;
-    bool direct_wlds = !(env_sw("HRN_DIRECT_WLDS") && atoi(env_sw("HRN_DIRECT_WLDS")) == 0);
-    // round 6: stride-2 3x3 convolutions with cin % 32 == 0 on the generic kernel request their pixel fragments two K chunks ahead by
-    // LDS-DMA into a per-wave LDS ring (kernels.hip: XL); same arithmetic in the same order: bit-identical to HRN_DIRECT_XLDS=0
-    bool direct_xlds = !(env_sw("HRN_DIRECT_XLDS") && atoi(env_sw("HRN_DIRECT_XLDS")) == 0);
+#include "ctx_switches.inc"
     bool conv_xl(const ConvOp &cv) const {
         return direct_xlds && direct_wlds && is16() && cv.k == 3 && cv.stride == 2 && cv.cin % 32 == 0 && !cv.up && cv.res_t < 0 && cv.nr == 6 &&
                cv.kchunks >= 4;
     }
-    // fused BasicBlocks on the 48-channel branch (conv3x3_lds.hip: bbf_run): bit-identical, 2.5x less HBM traffic on that
-    // branch, +2.6 % on the whole pass at 256 crops; HRN_BBF=0 goes back to two launches per block
-    bool disable_bbf = env_sw("HRN_BBF") && atoi(env_sw("HRN_BBF")) == 0;
-    // a fused block walks conv3_tiles_per_block / bbf_tpb_div tiles (short blocks of 1; long ones, 85 % of the tiles, long_factor = 4
-    // times that): 64 % of the fused tiles slide (conv1's halo rows carried over, not recomputed).  Longer blocks (2 / 1: 81 / 87 %
-    // sliding) measured +0.5 % on two boxes and -4.4 % on a third (profiles/carry_block_length_sweep.txt): not adopted
-    int bbf_tpb_div = env_sw("HRN_BBF_TPB_DIV") ? std::max(1, atoi(env_sw("HRN_BBF_TPB_DIV"))) : 3;
-    // estimated cost of a sliding tile for the longest-first order, against 28000 for a block's first tile (as the plain blocks'
-    // estimates count): the phase stamps measured 21.2 k ticks against 24.1 k
-    double bbf_slide_cost = env_sw("HRN_BBF_SLIDE_COST") ? atof(env_sw("HRN_BBF_SLIDE_COST")) : 24600.0;
-    // fused only when the call has at least this many 512-pixel tiles (four per CU): measured at 384x288 +2 % at 256
-    // crops (3541 tiles), +1 % at 128-192, +6 % at 96 (1328 tiles), -1 % at 64 (885 tiles), -2 % at 20, -5 % at one crop,
-    // where the two plain launches with their smaller tiles spread the work over more CUs
-    int bbf_min_tiles = env_sw("HRN_BBF_MIN_TILES") ? atoi(env_sw("HRN_BBF_MIN_TILES")) : 1100;
-    // 1: convolutions that read the same tensor share one cout-tile width so that they can share a launch (and L2)
-    int dgroup_nr_mode = env_sw("HRN_DGROUP_NR") ? atoi(env_sw("HRN_DGROUP_NR")) : 1;
-    bool disable_lds32 = env_sw("HRN_DISABLE_LDS32") != nullptr;
-    bool disable_n96 = env_sw("HRN_DISABLE_N96") != nullptr;
-    bool disable_fgroup = env_sw("HRN_DISABLE_FGROUP") != nullptr;   // one launch per fuse output instead of one per StageModule
-    bool disable_f32lds = env_sw("HRN_DISABLE_F32LDS") != nullptr;   // fp32 3x3 stride-1 convs back on the generic kernel
-    int f32_small_slices = env_sw("HRN_F32_SMALL_SLICES") ? atoi(env_sw("HRN_F32_SMALL_SLICES")) : 0;   // fp32: 128-pixel tiles from this many slices on (0: never; 4 and 8 measured: no gain)
-    // stride-2 slab kernel (conv_s2.hip) off: those convolutions stay on the generic kernel (bit-identical results)
     std::vector<Conv3Problem> probs_host;
-    // round 4: the 96-cout form enumerates real pixels only (no MFMAs on the pad column / pad row of the flat layout) on grids whose
-    // padding is at least this share of the flat pixels; bit-identical to the flat enumeration
-    bool disable_compact = env_sw("HRN_DISABLE_COMPACT") != nullptr;
-    double compact_min_pad = env_sw("HRN_COMPACT_MIN_PAD") ? atof(env_sw("HRN_COMPACT_MIN_PAD")) : 0.08;
-    bool disable_s2 = env_sw("HRN_DISABLE_S2") != nullptr;
-    // the slab kernel is taken when a launch has at least this many tiles (one per CU); smaller calls use the generic kernel
-    int s2_min_tiles = env_sw("HRN_S2_MIN_TILES") ? atoi(env_sw("HRN_S2_MIN_TILES")) : 256;
-    int s2_target_blocks = env_sw("HRN_S2_BLOCKS") ? std::max(1, atoi(env_sw("HRN_S2_BLOCKS"))) : 256;
-    bool disable_stem_mfma = env_sw("HRN_DISABLE_STEM_MFMA") != nullptr;
-    // round 4: conv1 + conv2 of the stem as one kernel (stem_fused.hip), bit-identical to the two launches it replaces
-    bool disable_stem_fuse = env_sw("HRN_DISABLE_STEM_FUSE") != nullptr;
     bool stem_fuse = false;       // planned (bf16 HRNet whose geometry fits: stem_fused_fits)
     int stem_conv2_op = -1;       // ops[] index of conv2's own launch (skipped by a pass that ran the fused kernel)
     S2Group stemf;                // the fused kernel's problem (conv2 with one output row per tile) and block maps
-    bool disable_head_mfma = env_sw("HRN_DISABLE_HEAD_MFMA") != nullptr;
-    bool direct_nr6 = env_sw("HRN_DIRECT_NR6") ? atoi(env_sw("HRN_DIRECT_NR6")) != 0 : true;
-    int half_stages_per_block = env_sw("HRN_HALF_STAGES") ? atoi(env_sw("HRN_HALF_STAGES")) : 8;
-    bool alternate = env_sw("HRN_ALTERNATE") ? atoi(env_sw("HRN_ALTERNATE")) != 0 : true;
-    int block_order = env_sw("HRN_BLOCK_ORDER") ? atoi(env_sw("HRN_BLOCK_ORDER")) : 1;
-    int long_factor = env_sw("HRN_LONG_FACTOR") ? atoi(env_sw("HRN_LONG_FACTOR")) : 4;
-    double long_share = env_sw("HRN_LONG_SHARE") ? atof(env_sw("HRN_LONG_SHARE")) : 0.85;
     int head_slabs = 1, head_slab_px = 1024;
     static constexpr int kHeadSlabPxSmall = 256;
     int head_slabs_small = 1;
@@ -1872,8 +1827,7 @@ int hrn_plan_direct_map(hrn_handle h, int group, int n, int32_t *blocks, int cap
     if (!h || n <= 0 || n > h->max_batch) return -1;
     if (group < 0 || group >= (int)h->dgroups.size()) return -1;
     const DirectGroup &g = h->dgroups[group];
-    int mr = 4;  // as run_pass chooses it
-    while (mr > 1 && h->direct_group_blocks(g, n, nullptr, mr) < 512) mr >>= 1;
+    const int mr = h->direct_mr(g, n);
     std::vector<int2> map;
     const int nblocks = h->direct_group_blocks(g, n, &map, mr);
     for (int i = 0; i < nblocks && i < capacity; ++i)
@@ -1920,7 +1874,7 @@ int hrn_plan_launch_walk(hrn_handle h, int kind, int index, int n, int32_t *out)
     for (size_t oi = 0; oi < h->ops.size(); ++oi)
         if (h->ops[oi].kind == (kind == 0 ? OP_CONV3_GROUP : OP_CHAIN) && h->ops[oi].idx == index) pos = (int)oi;
     if (pos < 0) return -1;
-    out[0] = pos, out[1] = h->alternate && (pos & 1) ? 1 : 0, out[2] = out[3] = out[4] = 0;   // (run_pass: rev)
+    out[0] = pos, out[1] = h->walks_back(pos) ? 1 : 0, out[2] = out[3] = out[4] = 0;
     if (kind == 1) {
         const auto &ch = h->chains[index];
         out[4] = ch.conv2 >= 0 ? (ch.conv1 >= 0 ? 2 : 3) : ch.ds >= 0 ? 1 : 0;   // (launch_bottleneck_chain_t)

@@ -2,7 +2,7 @@
 
 * BASELINE configs[2]'s ACTUAL code path (W48 384x288, 256 crops in one micro-batch: 512/384-pixel tiles, the fused
   BasicBlock pass, weights through LDS, LPT block order) against the CPU oracle, directly;
-* the block-map cache keyed by micro-batch size (ragged calls stop rebuilding);
+* the block-map cache keyed by micro-batch size (ragged calls stop rebuilding; five sizes from two streams evict and hit);
 * one process / several engines (``'cuda:0,0'``) == one engine;
 * the configs[4] clip runner == ``predict_frame`` per frame;
 * the real engine's weight blob through ``ShardedHRNet.load_and_broadcast`` in a 2-rank job sharing GPU 0, and through
@@ -99,6 +99,65 @@ def test_ragged_calls_stop_rebuilding_block_maps(pkg):
     net.predict_crops(crops[:13], boxes[:13])
     assert net.map_rebuilds() > four
     assert torch.equal(net.predict_crops(crops, boxes), first)
+    net.close()
+
+
+@pytest.mark.parametrize("model, c, dtype, res, env", [
+    ("HRNet", 32, "bf16", (64, 64), {"HRN_S2_MIN_TILES": "1"}),     # the slab kernel's cache at every size
+    ("HRNet", 32, "bf16", (64, 64), {}),                            # the stride-2 groups on their generic fallback at every size
+    ("HRNet", 32, "fp32", (64, 64), {}),                            # the fp32 plan: staged and generic groups only
+    ("PoseResNet", 50, "bf16", (32, 32), {}),                       # its smallest shape of plan_census.PIN_SHAPES
+], ids=["W32-bf16-slab", "W32-bf16-fallback", "W32-fp32", "R50-bf16"])
+def test_five_sizes_on_two_streams_evict_and_hit_bit_identically(pkg, model, c, dtype, res, env):
+    """Five micro-batch sizes on the four slots of every block-map cache, from two alternating non-default streams: each call of
+    the three turns through n = 5, 4, 3, 2, 1 evicts the least recently used size (its pinned image is rewritten, its upload goes
+    out on the other stream than the last one).  A fourth turn through 5, 4, 3, 2 leaves exactly those four cached: a fifth,
+    each size now from the stream that did NOT upload its map, rebuilds nothing (hrn_map_rebuilds), and n = 1, evicted, does.
+    Every output equals that of a fresh handle (cold caches, default stream) bit for bit, and no pad is written.
+
+    (With five sizes in turn on four least-recently-used slots no size survives until its next call, so the turn that rebuilds
+    nothing is the one AFTER the fourth; the check around it is the one the caches can meet, on this and on the previous host code.)"""
+    from plan_census import switches
+
+    sizes = (5, 4, 3, 2, 1)
+    sd = state_dict_np(c) if model == "HRNet" else pkg.synth_state_dict(c, 17, 0, model=model)
+
+    def engine():
+        with switches(env):
+            return pkg.NativeHRNet(c, 17, res, dtype, max_batch=5, device=0, model_name=model).load_state_dict(sd)
+
+    x = torch.from_numpy(pkg.synth_crops(5, res[0], res[1], seed=3)).cuda()
+    want = {}
+    for n in sizes:
+        net = engine()
+        want[n] = net(x[:n]).cpu()
+        net.close()
+    net = engine()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    outs, uploaded_on = [], {}
+
+    def call(n, k):
+        streams[k].wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(streams[k]):
+            outs.append((n, net(x[:n])))
+
+    k = 0
+    for n in sizes * 3 + sizes[:4]:          # three turns of misses, then 5, 4, 3, 2 once more: those four are cached now
+        before = net.map_rebuilds()
+        call(n, k % 2)
+        assert net.map_rebuilds() > before
+        uploaded_on[n] = k % 2
+        k += 1
+    cached = net.map_rebuilds()
+    for n in sizes[:4]:                      # hits, each from the other stream than the one its map went out on
+        call(n, 1 - uploaded_on[n])
+    assert net.map_rebuilds() == cached
+    call(1, 0)                               # the fifth size was evicted
+    assert net.map_rebuilds() > cached
+    torch.cuda.synchronize()
+    for n, o in outs:
+        assert torch.equal(o.cpu(), want[n]), n
+    assert net.pad_violations() == 0
     net.close()
 
 
