@@ -193,11 +193,33 @@ int hrn_preprocess_frames(hrn_handle h, const hrn_frame *frames_host, int nframe
  * Both fail with code 7 and nothing launched, beyond hrn_preprocess_frames' failures, on a frame (that a person refers to)
  * with: an unknown format, matrix or range; an odd or non-positive width or height; pitch_y < width; pitch_c < width (NV12)
  * or < width / 2 (I420); a null plane (y, u; v for I420).  Everything is judged before the device is touched, so a plan-only
- * handle reports argument errors as such and a good call as "plan-only". */
-enum { HRN_PIX_NV12 = 1, HRN_PIX_I420 = 2 };
+ * handle reports argument errors as such and a good call as "plan-only".
+ *
+ * THREE MORE LAYOUTS, through the same entries (these two, hrn_preprocess_frames_yuv_dev, hrn_letterbox_frames_yuv and
+ * hrn_rotate_frames; frames of all five layouts may share a call).  Value 3 is unassigned and stays "unknown".
+ *   HRN_PIX_NV21 (4)  8-bit; a Y plane and one plane of interleaved (V, U) pairs (ffmpeg nv21, Android cameras).  NV12's
+ *                     arithmetic with V = pair[0], U = pair[1]; validated as NV12.
+ *   HRN_PIX_P010 (5)  10-bit; 16-bit little-endian words, the sample in the TOP 10 bits (s = word >> 6; the low six bits are
+ *                     ignored, whatever they hold); a Y plane and one plane of interleaved (U, V) words (p010le: what a
+ *                     hardware decoder delivers for 10-bit HEVC / AV1).
+ *   HRN_PIX_I010 (6)  10-bit; 16-bit little-endian words, the sample in the LOW 10 bits (s = word & 1023; the high six bits are
+ *                     ignored); Y, U and V planes (yuv420p10le: what a software decoder delivers).
+ * Pitches stay in BYTES.  10-bit planes are read as aligned 16-bit words: pitch_y >= 2 * width; pitch_c >= 2 * width (P010)
+ * or >= width (I010); every plane address and both pitches even -- otherwise code 7, nothing launched, the text naming "odd
+ * plane address or pitch on a 10-bit frame".
+ * A 10-bit triple becomes 8-bit B, G, R through the SAME table, in exact integers, with one rounding from the 10-bit samples:
+ *   yy = max(0, Y - 4*y0) * CY;  u = U - 512;  v = V - 512;  h = 1 << 21
+ *   B = clip8((yy + h + CUB*u) >> 22);  G = clip8((yy + h + CVG*v + CUG*u) >> 22);  R = clip8((yy + h + CVR*v) >> 22)
+ * (arithmetic shift; one chroma sample per 2x2 block).  These sums do NOT fit int32 -- BT.709 limited: yy + h + CUB*u reaches
+ * 2 304 855 561 -- and are evaluated in 64 bits.  PINNED (tests/yuv10_ref.py, tests/test_yuv10_*.py): for samples that are
+ * multiples of 4 the result equals the 8-bit conversion of s / 4 bit for bit (every term scales by 4), so a P010 frame made from
+ * an NV12 frame by << 8 converts and crops to the same bits; the form is within one grey level of clip(rint(float64 formula));
+ * the kernels equal the numpy restatement bit for bit.  HDR transfer functions (PQ / HLG) and BT.2020 are not offered: such content
+ * goes through the chosen matrix as it is.  The output of every entry stays 8-bit. */
+enum { HRN_PIX_NV12 = 1, HRN_PIX_I420 = 2, HRN_PIX_NV21 = 4, HRN_PIX_P010 = 5, HRN_PIX_I010 = 6 };
 enum { HRN_YUV_BT601 = 0, HRN_YUV_BT709 = 1 };
 enum { HRN_YUV_LIMITED = 0, HRN_YUV_FULL = 1 };
-typedef struct { const uint8_t *y, *u, *v;     /* device; NV12: u = the UV plane, v ignored */
+typedef struct { const uint8_t *y, *u, *v;     /* device; NV12 / NV21 / P010: u = the interleaved chroma plane, v ignored */
                  int32_t height, width, pitch_y, pitch_c, format, matrix, range; } hrn_yuv_frame;
 int hrn_yuv_coefficients(int matrix, int range, int32_t out[6]);
 int hrn_yuv_to_bgr(hrn_handle h, const hrn_yuv_frame *frame_host, uint8_t *bgr_dev, void *stream);
@@ -591,7 +613,9 @@ int hrn_keypoint_eval_constants(double *iou_thrs /* 10 */, double *rec_thrs /* 1
  * Untouched pixels are NOT WRITTEN: the call is in place, every other byte of a buffer (pitch padding included) keeps its value.
  * YUV canvases (NV12 / I420, even sides, any pitch): colours are (Y, U, V) bytes (hrn_yuv_from_bgr); a covered pixel's Y byte takes
  * the winner's Y; the chroma sample of a 2x2 block is written iff at least one of its four pixels is covered, and takes U and V of
- * the highest-numbered primitive that covers any of the four.
+ * the highest-numbered primitive that covers any of the four.  HRN_PIX_NV21, _P010 and _I010 canvases are refused as an unknown
+ * format, here and in hrn_draw_labels_dev (colours are 8-bit triples: a 10-bit overlay wants a definition of its own); a pipeline
+ * of such frames draws on the BGR frame hrn_yuv_to_bgr gives it.
  *
  *   canvases_host     nframes entries on the HOST; hrn_canvas has hrn_yuv_frame's fields with writable planes.  HRN_PIX_BGR: y = the
  *                     (height, width, 3) uint8 pixels, pitch_y = bytes between rows >= 3 * width (a view into a larger buffer
@@ -858,7 +882,7 @@ int hrn_detector_nms_dev(hrn_handle h, const void *pred_dev, int dtype, int B, i
                          float iou_thres, int max_candidates, int max_det, float *rows_dev, int32_t *index_dev,
                          int32_t *counts_dev, int32_t *status_dev, void *stream);
 
-/* ---- frame rotation on the GPU: cv2.rotate for BGR, NV12 and I420 frames, and people between the two orientations ----
+/* ---- frame rotation on the GPU: cv2.rotate for BGR, NV12 / NV21, I420, P010 and I010 frames, and people between the two orientations ----
  * Replaces `frame = cv2.rotate(frame, rotation_code)` at the head of the reference's frame loops (scripts/live-demo.py:102-103,
  * scripts/extract-keypoints.py:96-97; the code comes from the video's rotation tag, misc/visualization.py:271-293): a portrait
  * video is stored sideways, a hardware decoder hands over the stored orientation.  The codes are cv2.ROTATE_*'s values.
@@ -871,6 +895,9 @@ int hrn_detector_nms_dev(hrn_handle h, const void *pred_dev, int dtype, int B, i
  * An element is: BGR -- the three bytes of a pixel, kept in order; the Y plane -- one byte; NV12's chroma plane -- the (U, V)
  * byte pair, on (H/2, W/2); I420 -- the U and the V plane, one byte each, on (H/2, W/2).  2 x 2 luma blocks map onto 2 x 2 blocks,
  * so converting a rotated YUV frame to BGR equals rotating the converted frame, bit for bit.
+ * HRN_PIX_NV21 rotates as NV12 (its pair is (V, U)).  The 10-bit layouts: an element of a Y, U or V plane is the 16-bit word (2
+ * bytes), of P010's chroma plane the (U, V) word pair (4 bytes); a word travels with all 16 bits, the ignored ones included.
+ * Both sides of a 10-bit frame need even plane addresses and pitches (code 7: "odd plane address or pitch on a 10-bit frame").
  * Bytes of a destination row beyond its elements (pitch padding) are NOT written; every other byte of dst has exactly one writer;
  * no atomics; source planes are only read.
  *

@@ -419,21 +419,41 @@ bool yuv_coefficients(int matrix, int range, int32_t out[6]) {
 }
 
 // what is wrong with a YUV frame somebody reads, or nullptr
+// the 4:2:0 layouts by name: every place that treats one differently from another asks one of these
+inline bool pix_is_yuv(int format) {
+    return format == HRN_PIX_NV12 || format == HRN_PIX_I420 || format == HRN_PIX_NV21 || format == HRN_PIX_P010 || format == HRN_PIX_I010;
+}
+inline bool pix_is_planar(int format) { return format == HRN_PIX_I420 || format == HRN_PIX_I010; }   // U and V planes of their own
+inline bool pix_is_10bit(int format) { return format == HRN_PIX_P010 || format == HRN_PIX_I010; }    // 16-bit words
+
+// the pitch and plane checks of a YUV frame, behind its format and size checks: planes of 8-bit samples or of 16-bit words
+const char *yuv_plane_fault(const hrn_yuv_frame &f) {
+    const bool planar = pix_is_planar(f.format), wide = pix_is_10bit(f.format);
+    if (f.pitch_y < (wide ? 2L : 1L) * f.width) return wide ? "has pitch_y below twice its width" : "has pitch_y below its width";
+    // a chroma row: width bytes (NV12 / NV21: width / 2 pairs; I010: width / 2 words), width / 2 (I420) or 2 * width (P010)
+    const long need_c = f.format == HRN_PIX_P010 ? 2L * f.width : f.format == HRN_PIX_I420 ? f.width / 2 : f.width;
+    if (f.pitch_c < need_c)
+        return f.format == HRN_PIX_P010   ? "has pitch_c below twice its width"
+               : f.format == HRN_PIX_I420 ? "has pitch_c below half its width"
+                                          : "has pitch_c below its width";
+    if (!f.y || !f.u || (planar && !f.v)) return "has a null plane";
+    if (wide && (((size_t)f.y | (size_t)f.u | (planar ? (size_t)f.v : 0) | (size_t)f.pitch_y | (size_t)f.pitch_c) & 1))
+        return "has an odd plane address or pitch on a 10-bit frame";
+    return nullptr;
+}
+
 const char *yuv_frame_fault(const hrn_yuv_frame &f) {
-    if (f.format != HRN_PIX_NV12 && f.format != HRN_PIX_I420) return "has an unknown format (HRN_PIX_NV12 or HRN_PIX_I420)";
+    if (!pix_is_yuv(f.format))
+        return "has an unknown format (HRN_PIX_NV12, HRN_PIX_I420, HRN_PIX_NV21, HRN_PIX_P010 or HRN_PIX_I010)";
     if (f.matrix != HRN_YUV_BT601 && f.matrix != HRN_YUV_BT709) return "has an unknown matrix (HRN_YUV_BT601 or HRN_YUV_BT709)";
     if (f.range != HRN_YUV_LIMITED && f.range != HRN_YUV_FULL) return "has an unknown range (HRN_YUV_LIMITED or HRN_YUV_FULL)";
     if (f.height <= 0 || f.width <= 0 || (f.height & 1) || (f.width & 1)) return "has an odd or non-positive width or height";
-    if (f.pitch_y < f.width) return "has pitch_y below its width";
-    if (f.pitch_c < (f.format == HRN_PIX_NV12 ? f.width : f.width / 2))
-        return f.format == HRN_PIX_NV12 ? "has pitch_c below its width" : "has pitch_c below half its width";
-    if (!f.y || !f.u || (f.format == HRN_PIX_I420 && !f.v)) return "has a null plane";
-    return nullptr;
+    return yuv_plane_fault(f);
 }
 
 YuvSource yuv_source(const hrn_yuv_frame &f) {   // of a frame yuv_frame_fault has passed
     YuvSource ys{};
-    ys.y = f.y, ys.u = f.u, ys.v = f.format == HRN_PIX_I420 ? f.v : nullptr;
+    ys.y = f.y, ys.u = f.u, ys.v = pix_is_planar(f.format) ? f.v : nullptr;
     ys.pitch_y = f.pitch_y, ys.pitch_c = f.pitch_c, ys.format = f.format;
     int32_t c[6];
     (void)yuv_coefficients(f.matrix, f.range, c);
@@ -1230,6 +1250,8 @@ int letterbox_frames(const char *entry, hrn_handle h, const hrn_frame *frames, c
     CallFrame frame(h, s, {{&h->lb_table, table_bytes, hrn_ctx::twice(table_bytes, 4096), "hipMalloc(letterbox table)"}});
     LetterboxArgs a{};
     a.n = n, a.out_h = out_h, a.out_w = out_w, a.form = form, a.order = order, a.yuv = yframes ? 1 : 0;
+    for (int i = 0; yframes && i < n; ++i)   // a call of NV12 / I420 frames alone keeps the two-way kernel
+        if (yframes[i].format != HRN_PIX_NV12 && yframes[i].format != HRN_PIX_I420) a.yuv = 2;
     a.pad[0] = pad[0], a.pad[1] = pad[1], a.pad[2] = pad[2];
     a.out = out_dev;
     a.table = frame.table(recs.data(), (size_t)n, "hipMemcpyAsync(letterbox table)");
@@ -1297,20 +1319,21 @@ int rotate_plane_shapes(const hrn_canvas &c, RotPlaneShape out[3]) {
         out[0] = {c.height, c.width, 3, false, false};
         return 1;
     }
-    out[0] = {c.height, c.width, 1, false, false};
-    if (c.format == HRN_PIX_NV12) {
-        out[1] = {c.height / 2, c.width / 2, 2, true, false};
+    const int sample = pix_is_10bit(c.format) ? 2 : 1;   // bytes of a Y, U or V sample
+    out[0] = {c.height, c.width, sample, false, false};
+    if (!pix_is_planar(c.format)) {   // NV12 / NV21 / P010 (the caller has named the format): one plane of chroma pairs
+        out[1] = {c.height / 2, c.width / 2, 2 * sample, true, false};
         return 2;
     }
-    out[1] = {c.height / 2, c.width / 2, 1, true, false};
-    out[2] = {c.height / 2, c.width / 2, 1, true, true};
+    out[1] = {c.height / 2, c.width / 2, sample, true, false};
+    out[2] = {c.height / 2, c.width / 2, sample, true, true};
     return 3;
 }
 // what is wrong with one side of a frame of hrn_rotate_frames, or nullptr
 const char *rotate_frame_fault(const hrn_canvas &c) {
-    if (c.format != HRN_PIX_BGR && c.format != HRN_PIX_NV12 && c.format != HRN_PIX_I420)
-        return "has an unknown format (HRN_PIX_BGR, HRN_PIX_NV12 or HRN_PIX_I420)";
-    if (!c.y || (c.format != HRN_PIX_BGR && !c.u) || (c.format == HRN_PIX_I420 && !c.v)) return "has a null plane";
+    if (c.format != HRN_PIX_BGR && !pix_is_yuv(c.format))
+        return "has an unknown format (HRN_PIX_BGR, HRN_PIX_NV12, HRN_PIX_I420, HRN_PIX_NV21, HRN_PIX_P010 or HRN_PIX_I010)";
+    if (!c.y || (c.format != HRN_PIX_BGR && !c.u) || (pix_is_planar(c.format) && !c.v)) return "has a null plane";
     if (c.height <= 0 || c.width <= 0) return "has a non-positive width or height";
     if (c.format != HRN_PIX_BGR && ((c.height & 1) || (c.width & 1))) return "has an odd width or height";
     RotPlaneShape shapes[3];
@@ -1320,6 +1343,9 @@ const char *rotate_frame_fault(const hrn_canvas &c) {
         if (pitch < (long)shapes[k].w * shapes[k].es) return shapes[k].chroma ? "has pitch_c below its chroma row's bytes" : "has pitch_y below its row's bytes";
         if (pitch * shapes[k].h >= (1L << 31)) return "has a plane with pitch * rows >= 2^31";
     }
+    if (pix_is_10bit(c.format) &&
+        (((size_t)c.y | (size_t)c.u | (pix_is_planar(c.format) ? (size_t)c.v : 0) | (size_t)c.pitch_y | (size_t)c.pitch_c) & 1))
+        return "has an odd plane address or pitch on a 10-bit frame";
     return nullptr;
 }
 }  // namespace

@@ -209,12 +209,12 @@ struct CropParams {
 // crops [0, n) of crops_dev, each from its own frame, into images_dev[0, n); any n (sliced by the grid's y limit)
 hipError_t launch_prepath(const CropParams *crops_dev, int n, int max_h_pad, unsigned char *tmp_dev, float *images_dev, int H, int W,
                           hipStream_t s);
-// The same pre-path cut from 4:2:0 YCbCr frames (NV12 / I420): person i's CropParams (frame = nullptr, frame_w / frame_h the
+// The same pre-path cut from 4:2:0 YCbCr frames (NV12 / NV21 / I420, 10-bit P010 / I010): person i's CropParams (frame = nullptr, frame_w / frame_h the
 // frame's size) plus this record of its own -- CropParams, the BGR kernels and their launch stay exactly as they are.
 struct YuvSource {
-    const unsigned char *y, *u, *v;   // planes of the person's frame, device; NV12: u = the interleaved UV plane, v unused
-    int pitch_y, pitch_c;             // bytes between rows of the Y plane / of a chroma plane
-    int format;                       // HRN_PIX_NV12 (1) or HRN_PIX_I420 (2)
+    const unsigned char *y, *u, *v;   // planes of the person's frame, device; NV12 / NV21 / P010: u = the interleaved plane, v unused
+    int pitch_y, pitch_c;             // bytes between rows of the Y plane / of a chroma plane (10-bit layouts: rows of 16-bit words)
+    int format;                       // HRN_PIX_NV12 (1), _I420 (2), _NV21 (4), _P010 (5) or _I010 (6): yuv_px.h's kPix*
     int coef[6];                      // y0, CY, CUB, CUG, CVG, CVR of hrn_yuv_coefficients: 20-bit fixed point
     int pad_;
 };
@@ -540,7 +540,8 @@ struct LetterboxFrame {            // one frame of the call, prepared on the hos
     double scale_x, scale_y;       // resize_scale(new, src): LB_MODE_LINEAR reads them
 };
 struct LetterboxArgs {
-    int n, out_h, out_w, form, order, yuv;   // form = HRN_LB_*, order = HRN_LB_RGB / _BGR
+    int n, out_h, out_w, form, order, yuv;   // form = HRN_LB_*, order = HRN_LB_RGB / _BGR; yuv: 0 BGR frames, 1 YUV frames that are
+                                             // all NV12 / I420 (the two-way kernel), 2 YUV frames of any of the five layouts
     unsigned char pad[4];          // pad[c] in output channel order
     LetterboxFrame one;            // n == 1: the frame, in the kernel arguments (nothing is uploaded)
     const LetterboxFrame *table;   // else n entries, device

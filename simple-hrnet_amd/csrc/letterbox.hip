@@ -1,7 +1,7 @@
 // The detector link on the GPU (include/hrnet_mi355.h: hrn_letterbox_frames, hrn_letterbox_frames_yuv,
 // hrn_detections_to_frame_dev): what the reference runs on the host around its person detector.
 //
-//   letterbox_kernel        frames (BGR or NV12 / I420, of differing sizes) -> the detector tensor, ONE launch for all frames of a
+//   letterbox_kernel        frames (BGR or YUV 4:2:0, 8- or 10-bit, of differing sizes) -> the detector tensor, ONE launch for all frames of a
 //                           call (blockIdx.y = frame).  An interior pixel is cv2.resize(INTER_LINEAR)'s: resize_taps.h's window
 //                           per axis, computed by the thread (two short double expressions: no tap table, no scratch, no second
 //                           launch), the 2 x 2 taps, VResizeLinear -- bit for bit resize_frames_kernel with interp == 1 -- or a
@@ -28,7 +28,7 @@ namespace hrn {
 
 namespace {
 
-constexpr int kSrcBgr = 0;   // the frame's layout: HRN_PIX_BGR; kPixNV12 and kPixI420 are the other two
+constexpr int kSrcBgr = 0;   // the frame's layout: HRN_PIX_BGR; yuv_px.h's kPix* are the others
 
 struct Bgr {
     int b, g, r;
@@ -36,12 +36,13 @@ struct Bgr {
 
 template <int SRC>
 __device__ __forceinline__ Bgr lb_src_px(const LetterboxFrame &f, int y, int x) {
-    if (SRC == kSrcBgr) {
+    if constexpr (SRC == kSrcBgr) {
         const unsigned char *px = f.bgr + ((size_t)y * f.src_w + x) * 3;
         return Bgr{px[0], px[1], px[2]};
+    } else {
+        const Rgb p = yuv_frame_px<SRC>(f.yuv, y, x);
+        return Bgr{p.b, p.g, p.r};
     }
-    const Rgb p = yuv_frame_px<SRC>(f.yuv, y, x);
-    return Bgr{p.b, p.g, p.r};
 }
 
 // interior pixel (dy, dx) of the resized frame, 0 <= dy < new_h, 0 <= dx < new_w
@@ -139,46 +140,77 @@ __device__ __forceinline__ void letterbox_u8(const LetterboxArgs &a, const Lette
 
 }  // namespace
 
-// One kernel per (form, kind of frames).  YUV frames of both layouts may share a call: the branch on the frame's layout is
-// uniform over a block (blockIdx.y is the frame).
-template <int FORM, bool YUV>
+// One kernel per (form, kind of frames).  YUV frames of all five layouts (NV12, I420, NV21, P010, I010) may share a call: the
+// branch on the frame's layout is uniform over a block (blockIdx.y is the frame).  KIND: kLbBgr; kLbYuv8 -- every frame of the
+// call is NV12 or I420: the two-way kernel, with the registers and the occupancy it has always had; kLbYuvAny -- some frame has one
+// of the other layouts: the five-way kernel (the 10-bit bodies cost the u8 form 13 VGPRs and two waves of occupancy).  The host has
+// refused every other value of `format`: such a frame writes nothing.
+constexpr int kLbBgr = 0, kLbYuv8 = 1, kLbYuvAny = 2;
+
+template <int FORM, int KIND>
 __global__ __launch_bounds__(256) void letterbox_kernel(LetterboxArgs a) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     const LetterboxFrame &f = a.n == 1 ? a.one : a.table[blockIdx.y];
     if (FORM == 3) {   // HRN_LB_U8_HWC
         const int runs = (a.out_w + kLbRun - 1) / kLbRun;
         if (idx >= (long)a.out_h * runs) return;
-        if (!YUV) letterbox_u8<kSrcBgr>(a, f, idx, runs);
-        else if (f.yuv.format == kPixNV12) letterbox_u8<kPixNV12>(a, f, idx, runs);
-        else letterbox_u8<kPixI420>(a, f, idx, runs);
+        if (KIND == kLbBgr) {
+            letterbox_u8<kSrcBgr>(a, f, idx, runs);
+        } else if (KIND == kLbYuv8) {
+            if (f.yuv.format == kPixNV12) letterbox_u8<kPixNV12>(a, f, idx, runs);
+            else if (f.yuv.format == kPixI420) letterbox_u8<kPixI420>(a, f, idx, runs);
+        } else {
+            switch (f.yuv.format) {
+                case kPixNV12: letterbox_u8<kPixNV12>(a, f, idx, runs); break;
+                case kPixI420: letterbox_u8<kPixI420>(a, f, idx, runs); break;
+                case kPixNV21: letterbox_u8<kPixNV21>(a, f, idx, runs); break;
+                case kPixP010: letterbox_u8<kPixP010>(a, f, idx, runs); break;
+                case kPixI010: letterbox_u8<kPixI010>(a, f, idx, runs); break;
+                default: break;
+            }
+        }
     } else {
         const long plane = (long)a.out_h * a.out_w;
         if (idx >= plane) return;
         constexpr int F = FORM == 3 ? 0 : FORM;
-        if (!YUV) letterbox_planar<F, kSrcBgr>(a, f, idx, plane);
-        else if (f.yuv.format == kPixNV12) letterbox_planar<F, kPixNV12>(a, f, idx, plane);
-        else letterbox_planar<F, kPixI420>(a, f, idx, plane);
+        if (KIND == kLbBgr) {
+            letterbox_planar<F, kSrcBgr>(a, f, idx, plane);
+        } else if (KIND == kLbYuv8) {
+            if (f.yuv.format == kPixNV12) letterbox_planar<F, kPixNV12>(a, f, idx, plane);
+            else if (f.yuv.format == kPixI420) letterbox_planar<F, kPixI420>(a, f, idx, plane);
+        } else {
+            switch (f.yuv.format) {
+                case kPixNV12: letterbox_planar<F, kPixNV12>(a, f, idx, plane); break;
+                case kPixI420: letterbox_planar<F, kPixI420>(a, f, idx, plane); break;
+                case kPixNV21: letterbox_planar<F, kPixNV21>(a, f, idx, plane); break;
+                case kPixP010: letterbox_planar<F, kPixP010>(a, f, idx, plane); break;
+                case kPixI010: letterbox_planar<F, kPixI010>(a, f, idx, plane); break;
+                default: break;
+            }
+        }
     }
 }
 
 namespace {
-template <bool YUV>
+template <int KIND>
 void launch_letterbox_kind(const LetterboxArgs &a, hipStream_t s) {
     const long threads = a.form == 3 ? (long)a.out_h * ((a.out_w + kLbRun - 1) / kLbRun) : (long)a.out_h * a.out_w;
     const dim3 g((unsigned)((threads + 255) / 256), (unsigned)a.n);
     switch (a.form) {
-        case 0: hipLaunchKernelGGL((letterbox_kernel<0, YUV>), g, dim3(256), 0, s, a); break;
-        case 1: hipLaunchKernelGGL((letterbox_kernel<1, YUV>), g, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((letterbox_kernel<2, YUV>), g, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((letterbox_kernel<3, YUV>), g, dim3(256), 0, s, a);
+        case 0: hipLaunchKernelGGL((letterbox_kernel<0, KIND>), g, dim3(256), 0, s, a); break;
+        case 1: hipLaunchKernelGGL((letterbox_kernel<1, KIND>), g, dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((letterbox_kernel<2, KIND>), g, dim3(256), 0, s, a); break;
+        default: hipLaunchKernelGGL((letterbox_kernel<3, KIND>), g, dim3(256), 0, s, a);
     }
 }
 }  // namespace
 
+// a.yuv: 0 -- BGR frames; 1 -- YUV frames, all NV12 or I420; 2 -- YUV frames of any of the five layouts
 hipError_t launch_letterbox(const LetterboxArgs &a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
-    if (a.yuv) launch_letterbox_kind<true>(a, s);
-    else launch_letterbox_kind<false>(a, s);
+    if (a.yuv == 2) launch_letterbox_kind<kLbYuvAny>(a, s);
+    else if (a.yuv) launch_letterbox_kind<kLbYuv8>(a, s);
+    else launch_letterbox_kind<kLbBgr>(a, s);
     return hipGetLastError();
 }
 

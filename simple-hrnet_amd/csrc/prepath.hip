@@ -157,6 +157,8 @@ hipError_t launch_prepath(const CropParams *crops_dev, int n, int max_h_pad, uns
 //   B = clip8((yy + h + CUB*u) >> 20);  G = clip8((yy + h + CVG*v + CUG*u) >> 20);  R = clip8((yy + h + CVR*v) >> 20)
 // Everything behind the tap is the BGR path's arithmetic, so a crop equals, bit for bit, the BGR path's crop of the converted
 // frame (tests/yuv_ref.py restates the conversion; tests/test_yuv_gpu.py holds both equalities).
+// NV21 (the pair is V, U) and the 10-bit layouts P010 / I010 (16-bit words, one rounding from the 10-bit samples: yuv_px.h) are
+// further instantiations of the same body (tests/yuv10_ref.py, tests/test_yuv10_gpu.py).
 namespace {
 
 // (the conversion of one pixel: yuv_px.h, shared with letterbox.hip)
@@ -205,10 +207,14 @@ __global__ __launch_bounds__(256) void prepath_horizontal_yuv_kernel(const CropP
     const YuvSource ys = srcs[blockIdx.y];
     const int y = (int)(idx / W), xx = (int)(idx - (long)y * W);
     unsigned char *o = tmp + cp.tmp_off + ((size_t)y * W + xx) * 3;
-    if (ys.format == kPixNV12)
-        horizontal_yuv<kPixNV12>(cp, ys, o, y, xx, W);
-    else
-        horizontal_yuv<kPixI420>(cp, ys, o, y, xx, W);
+    switch (ys.format) {
+        case kPixNV12: horizontal_yuv<kPixNV12>(cp, ys, o, y, xx, W); break;
+        case kPixI420: horizontal_yuv<kPixI420>(cp, ys, o, y, xx, W); break;
+        case kPixNV21: horizontal_yuv<kPixNV21>(cp, ys, o, y, xx, W); break;
+        case kPixP010: horizontal_yuv<kPixP010>(cp, ys, o, y, xx, W); break;
+        case kPixI010: horizontal_yuv<kPixI010>(cp, ys, o, y, xx, W); break;
+        default: o[0] = o[1] = o[2] = 0;   // (the host refuses every other value: nothing of such a frame is read)
+    }
 }
 
 hipError_t launch_prepath_yuv(const CropParams *crops_dev, const YuvSource *src_dev, int n, int max_h_pad, unsigned char *tmp_dev,
@@ -226,25 +232,76 @@ hipError_t launch_prepath_yuv(const CropParams *crops_dev, const YuvSource *src_
 }
 
 // A whole frame to contiguous (height, width, 3) BGR, for the consumer that needs BGR (the detector).  One thread converts a
-// run of 4 pixels of a row PAIR: 2 x 4 Y bytes and the 2 chroma pairs they share, out as 2 x 12 bytes = three dword stores per
+// run of 4 pixels of a row PAIR: 2 x 4 Y samples and the 2 chroma pairs they share, out as 2 x 12 bytes = three dword stores per
 // row where the row's address allows it (always when width % 4 == 0), bytes otherwise and in a last run of 2 pixels.
+// 8-bit layouts: 4 Y bytes per row and 4 (NV12 / NV21) or 2 x 2 (I420) chroma bytes.  10-bit layouts: 8 bytes of Y per row and
+// 8 (P010) or 2 x 4 (I010) bytes of chroma, in dwords where the address is a multiple of 4, in 16-bit words otherwise (the host
+// guarantees even addresses).  The output is 8-bit BGR whatever the layout.
 constexpr int kYuvRun = 4;
+
+namespace {
+// four / two 16-bit words at p (an even address, the words readable)
+__device__ __forceinline__ void load4w(const unsigned char *p, unsigned (&w)[4]) {
+    if (((size_t)p & 3) == 0) {
+        const unsigned a = ((const unsigned *)p)[0], b = ((const unsigned *)p)[1];
+        w[0] = a & 0xffffu, w[1] = a >> 16, w[2] = b & 0xffffu, w[3] = b >> 16;
+    } else {
+        const unsigned short *q = (const unsigned short *)p;
+        w[0] = q[0], w[1] = q[1], w[2] = q[2], w[3] = q[3];
+    }
+}
+__device__ __forceinline__ void load2w(const unsigned char *p, unsigned (&w)[2]) {
+    if (((size_t)p & 3) == 0) {
+        const unsigned a = *(const unsigned *)p;
+        w[0] = a & 0xffffu, w[1] = a >> 16;
+    } else {
+        const unsigned short *q = (const unsigned short *)p;
+        w[0] = q[0], w[1] = q[1];
+    }
+}
+}  // namespace
 
 template <int FMT>
 __global__ __launch_bounds__(256) void yuv_to_bgr_kernel(YuvSource ys, int height, int width, unsigned char *bgr) {
+    constexpr bool T10 = yuv_is10<FMT>();
     const int runs = (width + kYuvRun - 1) / kYuvRun;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)(height / 2) * runs) return;
     const int yp = (int)(idx / runs), x0 = (int)(idx - (long)yp * runs) * kYuvRun;
     const int npx = width - x0 < kYuvRun ? width - x0 : kYuvRun;   // 4, or 2 at the end of a row (width is even)
     int U[2], V[2];
-    if (FMT == kPixNV12) {
+    if (FMT == kPixNV12 || FMT == kPixNV21) {
         const unsigned char *c = ys.u + (size_t)yp * ys.pitch_c + x0;
         if (npx == kYuvRun) {
             const unsigned q = load4(c);
             U[0] = q & 255, V[0] = (q >> 8) & 255, U[1] = (q >> 16) & 255, V[1] = q >> 24;
         } else {
             U[0] = U[1] = c[0], V[0] = V[1] = c[1];
+        }
+        if (FMT == kPixNV21) {   // the pair is (V, U)
+            const int t0 = U[0], t1 = U[1];
+            U[0] = V[0], U[1] = V[1], V[0] = t0, V[1] = t1;
+        }
+    } else if (FMT == kPixP010) {
+        const unsigned char *c = ys.u + (size_t)yp * ys.pitch_c + 2 * x0;
+        if (npx == kYuvRun) {
+            unsigned w[4];
+            load4w(c, w);
+            U[0] = yuv_sample10<FMT>(w[0]), V[0] = yuv_sample10<FMT>(w[1]), U[1] = yuv_sample10<FMT>(w[2]), V[1] = yuv_sample10<FMT>(w[3]);
+        } else {
+            unsigned w[2];
+            load2w(c, w);
+            U[0] = U[1] = yuv_sample10<FMT>(w[0]), V[0] = V[1] = yuv_sample10<FMT>(w[1]);
+        }
+    } else if (FMT == kPixI010) {
+        const size_t off = (size_t)yp * ys.pitch_c + x0;   // chroma column x0 / 2, two bytes each
+        if (npx == kYuvRun) {
+            unsigned wu[2], wv[2];
+            load2w(ys.u + off, wu), load2w(ys.v + off, wv);
+            U[0] = yuv_sample10<FMT>(wu[0]), U[1] = yuv_sample10<FMT>(wu[1]), V[0] = yuv_sample10<FMT>(wv[0]), V[1] = yuv_sample10<FMT>(wv[1]);
+        } else {
+            U[0] = U[1] = yuv_sample10<FMT>(*(const unsigned short *)(ys.u + off));
+            V[0] = V[1] = yuv_sample10<FMT>(*(const unsigned short *)(ys.v + off));
         }
     } else {
         const size_t off = (size_t)yp * ys.pitch_c + (x0 >> 1);
@@ -254,14 +311,24 @@ __global__ __launch_bounds__(256) void yuv_to_bgr_kernel(YuvSource ys, int heigh
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int fy = 2 * yp + r;
-        const unsigned char *yrow = ys.y + (size_t)fy * ys.pitch_y + x0;
+        const unsigned char *yrow = ys.y + (size_t)fy * ys.pitch_y + (T10 ? 2 : 1) * x0;
         unsigned char *o = bgr + ((size_t)fy * width + x0) * 3;
         if (npx == kYuvRun) {
-            const unsigned q = load4(yrow);
+            int Ys[4];
+            if (T10) {
+                unsigned w[4];
+                load4w(yrow, w);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) Ys[k] = yuv_sample10<FMT>(w[k]);
+            } else {
+                const unsigned q = load4(yrow);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) Ys[k] = (q >> (8 * k)) & 255;
+            }
             unsigned char px[12];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const Rgb p = yuv_rgb(ys.coef, (q >> (8 * k)) & 255, U[k >> 1], V[k >> 1]);
+                const Rgb p = yuv_rgb_of<FMT>(ys.coef, Ys[k], U[k >> 1], V[k >> 1]);
                 px[3 * k] = (unsigned char)p.b, px[3 * k + 1] = (unsigned char)p.g, px[3 * k + 2] = (unsigned char)p.r;
             }
             if (((size_t)o & 3) == 0) {
@@ -275,20 +342,26 @@ __global__ __launch_bounds__(256) void yuv_to_bgr_kernel(YuvSource ys, int heigh
             }
         } else {
             for (int k = 0; k < npx; ++k) {
-                const Rgb p = yuv_rgb(ys.coef, yrow[k], U[0], V[0]);
+                const int Yk = T10 ? yuv_sample10<FMT>(((const unsigned short *)yrow)[k]) : (int)yrow[k];
+                const Rgb p = yuv_rgb_of<FMT>(ys.coef, Yk, U[0], V[0]);
                 o[3 * k] = (unsigned char)p.b, o[3 * k + 1] = (unsigned char)p.g, o[3 * k + 2] = (unsigned char)p.r;
             }
         }
     }
 }
 
+// (the host has refused every other layout: an unknown value launches nothing and is an error)
 hipError_t launch_yuv_to_bgr(const YuvSource &src, int height, int width, unsigned char *bgr_dev, hipStream_t s) {
     const long threads = (long)(height / 2) * ((width + kYuvRun - 1) / kYuvRun);
     dim3 g((unsigned)((threads + 255) / 256));
-    if (src.format == kPixNV12)
-        hipLaunchKernelGGL(yuv_to_bgr_kernel<kPixNV12>, g, dim3(256), 0, s, src, height, width, bgr_dev);
-    else
-        hipLaunchKernelGGL(yuv_to_bgr_kernel<kPixI420>, g, dim3(256), 0, s, src, height, width, bgr_dev);
+    switch (src.format) {
+        case kPixNV12: hipLaunchKernelGGL(yuv_to_bgr_kernel<kPixNV12>, g, dim3(256), 0, s, src, height, width, bgr_dev); break;
+        case kPixI420: hipLaunchKernelGGL(yuv_to_bgr_kernel<kPixI420>, g, dim3(256), 0, s, src, height, width, bgr_dev); break;
+        case kPixNV21: hipLaunchKernelGGL(yuv_to_bgr_kernel<kPixNV21>, g, dim3(256), 0, s, src, height, width, bgr_dev); break;
+        case kPixP010: hipLaunchKernelGGL(yuv_to_bgr_kernel<kPixP010>, g, dim3(256), 0, s, src, height, width, bgr_dev); break;
+        case kPixI010: hipLaunchKernelGGL(yuv_to_bgr_kernel<kPixI010>, g, dim3(256), 0, s, src, height, width, bgr_dev); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

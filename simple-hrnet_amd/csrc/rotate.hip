@@ -1,9 +1,10 @@
 // Frame rotation on the GPU (include/hrnet_mi355.h: hrn_rotate_frames, hrn_rotate_people_dev): cv2.rotate -- a pure permutation of
-// elements -- for BGR, NV12 and I420 frames, and people between the two orientations.
+// elements -- for BGR, NV12 / NV21, I420 and 10-bit P010 / I010 frames, and people between the two orientations.
 //
 //   rotate_kernel          ONE launch for all planes of all frames of a call: one 256-thread block per 64 x 64-element tile of a
 //                          plane (64 x 16 at 180 degrees), found by binary search in the call's plane table (one frame: its planes sit in the kernel
-//                          arguments).  An element is 1 byte (Y, U, V), 2 (NV12's UV pair) or 3 (a BGR pixel), kept in order.
+//                          arguments).  An element is 1 byte (Y, U, V), 2 (NV12's UV / NV21's VU pair; a 10-bit Y, U or V word), 3 (a BGR
+//                          pixel) or 4 (P010's UV word pair), its bytes kept in order -- so a 10-bit word travels with all 16 bits.
 //                          90 degrees: the tile's source rows go into LDS as they lie -- coalesced, in dwords when the plane's
 //                          base and pitch are multiples of 4 (a tile's first column is a multiple of 64 elements, so its rows then
 //                          start on a dword), in bytes otherwise and for a row's last bytes.  A thread then gathers four elements
@@ -129,7 +130,7 @@ __device__ __forceinline__ void rotate180_tile(const RotPlane &p, int tx, int ty
 }  // namespace
 
 __global__ __launch_bounds__(kRotThreads) void rotate_kernel(RotArgs a) {
-    __shared__ unsigned lds32[kRotTile * (kRotTile * 3 + 4) / 4];
+    __shared__ unsigned lds32[kRotTile * (kRotTile * 4 + 4) / 4];   // the widest element: 4 bytes
     const int tile = blockIdx.x;
     RotPlane p;
     if (a.table) {   // the last plane whose first tile is not beyond this one
@@ -148,11 +149,13 @@ __global__ __launch_bounds__(kRotThreads) void rotate_kernel(RotArgs a) {
     if (p.code == 1) {
         if (p.es == 1) rotate180_tile<1>(p, tx, ty);
         else if (p.es == 2) rotate180_tile<2>(p, tx, ty);
-        else rotate180_tile<3>(p, tx, ty);
+        else if (p.es == 3) rotate180_tile<3>(p, tx, ty);
+        else if (p.es == 4) rotate180_tile<4>(p, tx, ty);
     } else {
         if (p.es == 1) rotate90_tile<1>(p, tx, ty, lds32);
         else if (p.es == 2) rotate90_tile<2>(p, tx, ty, lds32);
-        else rotate90_tile<3>(p, tx, ty, lds32);
+        else if (p.es == 3) rotate90_tile<3>(p, tx, ty, lds32);
+        else if (p.es == 4) rotate90_tile<4>(p, tx, ty, lds32);
     }
 }
 

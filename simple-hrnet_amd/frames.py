@@ -1,6 +1,6 @@
 """What a caller's "frames" are, and how they become device memory plus a frame table of the C ABI (include/hrnet_mi355.h).
 
-A frame is an (Hf, Wf, 3) uint8 BGR tensor or array, or a ``YuvFrame`` (NV12 / I420); the frames of a call are one frame, an
+A frame is an (Hf, Wf, 3) uint8 BGR tensor or array, or a ``YuvFrame`` (NV12 / NV21 / I420, 10-bit P010 / I010); the frames of a call are one frame, an
 (F, Hf, Wf, 3) stack, or a sequence of frames of any sizes with None for a frame nobody is cut from -- all of one kind.
 ``Frames`` is that list together with its kind, its sizes and its ``hrn_frame`` / ``hrn_yuv_frame`` / ``hrn_canvas`` table.
 The coercions every caller's tensor-or-array-like goes through (``as_tensor``, ``host_array``, ``device_tensor``) live here too.
@@ -14,7 +14,11 @@ import torch
 
 from . import _lib
 
-PIX_FORMATS = {"nv12": 1, "i420": 2}          # include/hrnet_mi355.h: HRN_PIX_*
+PIX_FORMATS = {"nv12": 1, "i420": 2}          # include/hrnet_mi355.h: HRN_PIX_*: the 8-bit formats, which every entry takes
+PIX_FORMATS_10BIT = {"p010": 5, "i010": 6}     # HRN_PIX_P010 / _I010: planes of 16-bit little-endian words; input side only
+PIX_NV21 = 4                                   # HRN_PIX_NV21: an "nv12" frame with chroma_order="vu"; input side only (3 is unassigned)
+PIX_10BIT = tuple(PIX_FORMATS_10BIT)
+PIX_PLANAR = ("i420", "i010")                  # U and V planes of their own, rows of pitch / 2 bytes
 YUV_MATRICES = {"bt601": 0, "bt709": 1}        # HRN_YUV_BT601 / _BT709
 YUV_RANGES = {"limited": 0, "full": 1}         # HRN_YUV_LIMITED / _FULL
 
@@ -41,20 +45,30 @@ def device_tensor(x, device, dtype, shape=None) -> torch.Tensor:
 
 
 class YuvFrame:
-    """One 8-bit 4:2:0 video frame as a decoder or ``ffmpeg -pix_fmt nv12|yuv420p`` delivers it, accepted wherever a BGR frame is
-    (``preprocess_frame(s)``, ``predict_frame(s)``, ``predict_clip``) and by ``NativeHRNet.yuv_to_bgr``.
+    """One 4:2:0 video frame as a decoder or ``ffmpeg -pix_fmt nv12|nv21|yuv420p|p010le|yuv420p10le`` delivers it, accepted
+    wherever a BGR frame is (``preprocess_frame(s)``, ``predict_frame(s)``, ``predict_clip``, ``track_frame``, ``detector_input``,
+    ``rotate_frames``) and by ``NativeHRNet.yuv_to_bgr``; ``draw_poses`` / ``draw_labels`` take ``"nv12"`` and ``"i420"`` only.
 
     ``data``: uint8 tensor or array of any shape, host or device, in the rawvideo layout: ``height`` rows of ``pitch`` bytes of Y,
-    then the chroma -- ``"nv12"``: ``height / 2`` rows of ``pitch`` bytes of interleaved U, V; ``"i420"``: ``height / 2`` rows of
-    ``pitch / 2`` bytes of U, then the same of V.  ``pitch`` defaults to ``width``; bytes of a row beyond the width are never
-    read into a result.  ``matrix``: ``"bt601"`` or ``"bt709"``; ``range``: ``"limited"`` (16..235) or ``"full"``.
-    ValueError on an odd or non-positive size, a pitch below the width (odd, for i420), a buffer shorter than ``nbytes``, or
-    an unknown format, matrix or range."""
+    then the chroma -- ``"nv12"``: ``height / 2`` rows of ``pitch`` bytes of interleaved U, V; ``"i420"``:
+    ``height / 2`` rows of ``pitch / 2`` bytes of U, then the same of V.  NV21 (ffmpeg ``nv21``, Android cameras) is ``"nv12"``
+    with ``chroma_order="vu"``: the pairs are V, U.  (The format string ``"nv21"`` itself stays refused, as it always was.)  The 10-bit formats have the same layouts in 16-bit
+    little-endian words, ``pitch`` still in BYTES: ``"p010"`` is nv12's, the sample in the top 10 bits of a word; ``"i010"``
+    (yuv420p10le) is i420's, the sample in the low 10 bits; the other six bits are ignored.  For these ``data`` may also be a numpy
+    ``uint16`` array or a torch ``int16`` / ``uint16`` tensor, which is taken as its bytes.  ``pitch`` defaults to ``width``
+    (``2 * width`` for the 10-bit formats); bytes of a row beyond its samples are never read into a result.  ``matrix``:
+    ``"bt601"`` or ``"bt709"``; ``range``: ``"limited"`` (16..235, x 4 for 10 bits) or ``"full"``.
+    ``draw_poses`` / ``draw_labels`` refuse a ``"vu"`` frame as they refuse the 10-bit formats.
+    ValueError on an odd or non-positive size, a ``chroma_order`` other than ``"uv"`` / ``"vu"`` (``"vu"``: nv12 only), a pitch below the row's bytes, an odd pitch for i420, p010 and i010 (i010: not a
+    multiple of 4 -- its chroma rows are ``pitch / 2`` bytes of words), a buffer shorter than ``nbytes``, or an unknown format,
+    matrix or range."""
 
     def __init__(self, data, height: int, width: int, format: str = "nv12", matrix: str = "bt601", range: str = "limited",  # noqa: A002
-                 pitch: Optional[int] = None):
-        if format not in PIX_FORMATS:
-            raise ValueError("format must be 'nv12' or 'i420', got %r" % (format,))
+                 pitch: Optional[int] = None, chroma_order: str = "uv"):
+        if format not in PIX_FORMATS and format not in PIX_FORMATS_10BIT:
+            raise ValueError("format must be one of %s, got %r" % (", ".join(repr(k) for k in list(PIX_FORMATS) + list(PIX_FORMATS_10BIT)), format))
+        if chroma_order not in ("uv", "vu") or (chroma_order == "vu" and format != "nv12"):
+            raise ValueError("chroma_order must be 'uv', or 'vu' on an 'nv12' frame (NV21), got %r on %r" % (chroma_order, format))
         if matrix not in YUV_MATRICES:
             raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
         if range not in YUV_RANGES:
@@ -62,16 +76,25 @@ class YuvFrame:
         height, width = int(height), int(width)
         if height <= 0 or width <= 0 or height % 2 or width % 2:
             raise ValueError("a 4:2:0 frame has an even, positive height and width, got %d x %d" % (height, width))
-        pitch = width if pitch is None else int(pitch)
-        if pitch < width:
-            raise ValueError("pitch %d is below the width %d" % (pitch, width))
+        wide = format in PIX_10BIT
+        row = 2 * width if wide else width
+        pitch = row if pitch is None else int(pitch)
+        if pitch < row:
+            raise ValueError("pitch %d is below %s %d" % (pitch, "twice the width" if wide else "the width", width))
         if format == "i420" and pitch % 2:
             raise ValueError("an i420 frame has an even pitch (its chroma rows are pitch / 2 bytes), got %d" % pitch)
+        if wide and pitch % (4 if format == "i010" else 2):
+            raise ValueError("a %s frame has a pitch that is a multiple of %d (its rows are 16-bit words%s), got %d"
+                             % (format, 4 if format == "i010" else 2, ", its chroma rows pitch / 2 bytes" if format == "i010" else "", pitch))
+        if wide and isinstance(data, np.ndarray) and data.dtype == np.uint16:
+            data = np.ascontiguousarray(data).reshape(-1).view(np.uint8)
         data = as_tensor(data)
+        if wide and data.dtype in (torch.int16, torch.uint16):
+            data = data.contiguous().view(-1).view(torch.uint8)
         if data.dtype != torch.uint8:
-            raise ValueError("data must be uint8")
+            raise ValueError("data must be uint8" + (" (or 16-bit words, for a 10-bit format)" if wide else ""))
         self.height, self.width, self.pitch = height, width, pitch
-        self.format, self.matrix, self.range = format, matrix, range
+        self.format, self.matrix, self.range, self.chroma_order = format, matrix, range, chroma_order
         data = data.contiguous().view(-1)
         if data.numel() < self.nbytes:
             raise ValueError("a %d x %d %s frame of pitch %d has %d bytes, the buffer has %d"
@@ -80,13 +103,18 @@ class YuvFrame:
 
     @classmethod
     def _trusted(cls, data: torch.Tensor, height: int, width: int, like: "YuvFrame") -> "YuvFrame":
-        """a packed frame (pitch == width) of ``like``'s format, matrix and range over the flat uint8 tensor ``data`` of exactly its
-        bytes, without the constructor's checks: ``rotate_frames``' fresh destination, whose arguments are its own"""
+        """a packed frame (pitch == a row's bytes) of ``like``'s format, matrix and range over the flat uint8 tensor ``data`` of
+        exactly its bytes, without the constructor's checks: ``rotate_frames``' fresh destination, whose arguments are its own"""
         f = cls.__new__(cls)
-        f.height, f.width, f.pitch = height, width, width
-        f.format, f.matrix, f.range = like.format, like.matrix, like.range
+        f.height, f.width, f.pitch = height, width, width * like.sample_bytes
+        f.format, f.matrix, f.range, f.chroma_order = like.format, like.matrix, like.range, like.chroma_order
         f.data = data
         return f
+
+    @property
+    def sample_bytes(self) -> int:
+        """bytes of one Y, U or V sample: 2 for the 10-bit formats"""
+        return 2 if self.format in PIX_10BIT else 1
 
     @property
     def nbytes(self) -> int:
@@ -99,17 +127,20 @@ class YuvFrame:
     def to(self, device, non_blocking: bool = False) -> "YuvFrame":
         """the same frame with its bytes on ``device`` (itself when they already are)"""
         data = self.data.to(device, non_blocking=non_blocking)
-        return self if data is self.data else YuvFrame(data, self.height, self.width, self.format, self.matrix, self.range, self.pitch)
+        return self if data is self.data else YuvFrame(data, self.height, self.width, self.format, self.matrix, self.range, self.pitch,
+                                                       self.chroma_order)
 
     def _fill(self, entry: "_lib.YuvFrameC", base: Optional[int] = None):
         """``entry`` = the ``hrn_yuv_frame`` of this frame, its bytes at device address ``base`` (default: where ``data`` is)"""
         base = self.data.data_ptr() if base is None else base
         luma = self.pitch * self.height
         entry.y, entry.u = base, base + luma
-        entry.v = base + luma + (self.pitch // 2) * (self.height // 2) if self.format == "i420" else None
+        planar = self.format in PIX_PLANAR
+        entry.v = base + luma + (self.pitch // 2) * (self.height // 2) if planar else None
         entry.height, entry.width, entry.pitch_y = self.height, self.width, self.pitch
-        entry.pitch_c = self.pitch if self.format == "nv12" else self.pitch // 2
-        entry.format, entry.matrix, entry.range = PIX_FORMATS[self.format], YUV_MATRICES[self.matrix], YUV_RANGES[self.range]
+        entry.pitch_c = self.pitch // 2 if planar else self.pitch
+        code = PIX_NV21 if self.chroma_order == "vu" else PIX_FORMATS.get(self.format) or PIX_FORMATS_10BIT[self.format]
+        entry.format, entry.matrix, entry.range = code, YUV_MATRICES[self.matrix], YUV_RANGES[self.range]
 
 
 ROTATE_CODES = {"90cw": 0, "180": 1, "90ccw": 2}   # HRN_ROTATE_*: the values of cv2.ROTATE_90_CLOCKWISE / _180 / _90_COUNTERCLOCKWISE
@@ -234,7 +265,7 @@ class Frames(list):
 
     def rotated(self, codes, device) -> "Frames":
         """fresh destinations for ``rotate_frames``: per frame an (H', W', 3) tensor, or a ``YuvFrame`` of the rotated size with the
-        frame's format, matrix and range and pitch == width; None stays None"""
+        frame's format, matrix and range and no pitch padding (2 bytes per sample for the 10-bit formats); None stays None"""
         out = []
         for f, code in zip(self, codes):
             if f is None:
@@ -243,7 +274,8 @@ class Frames(list):
             h, w = (f.height, f.width) if self.yuv else (int(f.shape[0]), int(f.shape[1]))
             h, w = (h, w) if code == 1 else (w, h)
             if self.yuv:
-                out.append(YuvFrame(torch.empty((h * w * 3 // 2,), dtype=torch.uint8, device=device), h, w, f.format, f.matrix, f.range))
+                out.append(YuvFrame(torch.empty((h * w * 3 // 2 * f.sample_bytes,), dtype=torch.uint8, device=device), h, w, f.format,
+                                    f.matrix, f.range, chroma_order=f.chroma_order))
             else:
                 out.append(torch.empty((h, w, 3), dtype=torch.uint8, device=device))
         return Frames(out, self.yuv)

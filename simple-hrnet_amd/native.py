@@ -505,8 +505,8 @@ class NativeHRNet:
     def preprocess_frame(self, frame: torch.Tensor, detections, variant: str = "pad") -> Tuple[torch.Tensor, np.ndarray, torch.Tensor]:
         """The crop pre-path of ``SimpleHRNet.predict`` for one frame (``SimpleHRNet.py:236-278``) on the GPU.
 
-        ``frame``: (Hf, Wf, 3) uint8 BGR (the cv2 frame; host tensors / arrays are uploaded once), or a ``YuvFrame`` (NV12 / I420:
-        the crops equal, bit for bit, those of the frame ``yuv_to_bgr`` makes of it);
+        ``frame``: (Hf, Wf, 3) uint8 BGR (the cv2 frame; host tensors / arrays are uploaded once), or a ``YuvFrame`` (any of its
+        formats, 8- or 10-bit: the crops equal, bit for bit, those of the frame ``yuv_to_bgr`` makes of it);
         ``detections``: (P, >=4) float array-like, columns 0..3 = x1, y1, x2, y2 as the detector returns them.
         ``variant``: ``"pad"`` = the single-image path (aspect ratio corrected by zero padding), ``"clamp"`` = the batch
         path's enlarge-and-clamp (``SimpleHRNet.py:383-412``; call once per image of the stack).
@@ -534,8 +534,9 @@ class NativeHRNet:
 
     def yuv_to_bgr(self, frame: YuvFrame) -> torch.Tensor:
         """A whole ``YuvFrame`` as an (H, W, 3) uint8 BGR tensor on the engine's GPU (``hrn_yuv_to_bgr``): the bridge to a consumer
-        that needs BGR, such as the detector -- a host frame still crosses PCIe once, at 1.5 bytes per pixel.  The arithmetic is
-        the crop pre-path's (include/hrnet_mi355.h), cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420)'s form."""
+        that needs BGR, such as the detector -- a host frame still crosses PCIe once, at 1.5 bytes per pixel (3 for the 10-bit
+        formats, whose result is 8-bit BGR too).  The arithmetic is the crop pre-path's (include/hrnet_mi355.h),
+        cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420)'s form."""
         if not isinstance(frame, YuvFrame):
             raise TypeError("yuv_to_bgr takes a YuvFrame")
         frame = frame.to(self.torch_device, non_blocking=True)
@@ -1076,7 +1077,7 @@ class NativeHRNet:
         counter-clockwise) -- ``cv2.ROTATE_*``'s values, see ``rotation_code_from_degrees`` -- for every frame, or one per frame;
         None returns the resident frames unrotated.  Returns the rotated frames on the GPU in the shape they came in: a frame, a
         stack (its frames then turn alike: all by 180 degrees or none), or a list; a ``YuvFrame`` comes back as a ``YuvFrame``
-        with swapped sides, its own format, matrix and range, and pitch == width.
+        with swapped sides, its own format (8- or 10-bit), matrix and range, and no pitch padding.
         ``out``: destinations on the engine's GPU to write into instead (the same shape of argument; pitched BGR views and pitched
         ``YuvFrame``s are allowed; bytes of a row beyond its pixels keep their value); they are returned.  A destination may not
         be a source: in-place rotation is not offered.  Nothing is synchronised."""
@@ -1144,7 +1145,7 @@ class NativeHRNet:
             dst.y, dst.height, dst.width, dst.pitch_y, dst.format = out.data_ptr(), rh, rw, 3 * rw, 0
         elif isinstance(frame, YuvFrame) and frame.device == dev:
             rh, rw = (frame.height, frame.width) if code == 1 else (frame.width, frame.height)
-            out = YuvFrame._trusted(torch.empty((rh * rw * 3 // 2,), dtype=torch.uint8, device=dev), rh, rw, frame)
+            out = YuvFrame._trusted(torch.empty((rh * rw * 3 // 2 * frame.sample_bytes,), dtype=torch.uint8, device=dev), rh, rw, frame)
             frame._fill(src)
             out._fill(dst)
         else:
@@ -1622,7 +1623,7 @@ class NativeHRNet:
                 if hi > lo and f - first not in offs:
                     frames[f - first] = held[f][0]
                     offs[f - first] = need
-                    need += (host_bytes(held[f][0]).numel() + 255) // 256 * 256
+                    need += (host_bytes(held[f][0]).numel() + 255) // 256 * 256   # (a 10-bit frame needs an even address, whatever lies before it)
             arena = pipe.buffer(slot, torch.uint8, (need + need // 4,), at_least=need) if need else None
             with pipe.filling(slot):                             # the pre-path that read this arena has finished
                 for f, off in offs.items():
