@@ -8,105 +8,29 @@ costs beside the host round trip it replaces, and what its single-wave assignmen
       assignment phase is skipped): the difference is the single wave's share.
   (b) draw_poses with ids from the host against ids on the device (8 people, 1080p BGR, resident).
   (c) --ab-root DIR: draw_poses with host ids (8 people, 1080p) and predict_frame (8 people, HRNet-W32 256x192 bf16) in THIS tree
-      against the checkout at DIR (the parent commit, built), each in fresh child processes run alternately on the same box; a
-      difference inside the spread of the children's medians is "unchanged".  Without --ab-root: NOT MEASURED.
+      against the checkout at DIR (the parent commit, built): costlib.ab, the protocol of tools/README.md.  Without --ab-root:
+      NOT MEASURED.
 
-usage: python tools/assoc_cost.py --out DIR [--rounds R] [--reps K] [--ab-root DIR]
-       python tools/assoc_cost.py --child-only [--root DIR]     (the child of (c): one JSON line)"""
-import argparse
+usage: python tools/assoc_cost.py --out DIR [--rounds R] [--reps K] [--ab-root DIR]"""
 import importlib
-import json
 import os
 import statistics
-import subprocess
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-ap = argparse.ArgumentParser()
-ap.add_argument("--out", help="directory assoc_ids.txt is written to")
-ap.add_argument("--rounds", type=int, default=9)
-ap.add_argument("--reps", type=int, default=20, help="calls per timed sample")
-ap.add_argument("--ab-root", help="checkout of the parent commit, built: draw_poses and predict_frame there against here")
-ap.add_argument("--ab-pairs", type=int, default=3, help="child processes per side of the A/B")
-ap.add_argument("--child-only", action="store_true", help="time draw_poses and predict_frame of (c) alone and print one JSON line")
-ap.add_argument("--root", default=ROOT, help="with --child-only: the checkout whose package is timed")
-args = ap.parse_args()
-if not args.child_only and not args.out:
-    ap.error("--out is needed")
-sys.path.insert(0, os.path.abspath(args.root) if args.child_only else ROOT)
+import costlib
+from costlib import people_of, timed
+
+args = costlib.parser(__doc__, "assoc_ids.txt", rounds=9, reps=20, ab="draw_poses and predict_frame").parse_args()
+sys.path.insert(0, costlib.ROOT)
 os.environ["HRN_DEBUG_ENV"] = "1"   # (the library reads switches only in a process that opts in; none is set but for (a)'s second engine)
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
 
 hf, wf = 1080, 1920
-COCO = json.load(open(os.path.join(ROOT, "tests", "golden", "coco_skeleton.json")))["coco_skeleton"]
-
-
-def timed(cands, rounds, reps):
-    """HIP-event ms per call of every candidate: `rounds` samples of `reps` calls each, interleaved in a rotated order"""
-    for fn in cands.values():
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    names = list(cands)
-    samples = {k: [] for k in names}
-    for r in range(rounds):
-        for k in names[r % len(names):] + names[:r % len(names)]:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                cands[k]()
-            b.record()
-            b.synchronize()
-            samples[k].append(a.elapsed_time(b) / reps)
-    return samples
-
-
-def people_of(count, seed, jitter=0.0, base=None):
-    """`count` people spread over the frame: ((count, 17, 3) (y, x, confidence), (count, 4) int32 boxes)"""
-    rng = np.random.default_rng(seed)
-    if base is None:
-        pts = np.empty((count, 17, 3), np.float32)
-        for i in range(count):
-            bh = rng.uniform(300, 900)
-            bw = bh * rng.uniform(0.3, 0.6)
-            x1, y1 = rng.uniform(0, wf - bw), rng.uniform(0, hf - bh)
-            pts[i, :, 0] = rng.uniform(y1, y1 + bh, 17)
-            pts[i, :, 1] = rng.uniform(x1, x1 + bw, 17)
-        pts[..., 2] = 0.9
-    else:
-        pts = base.copy()
-        pts[..., :2] += rng.normal(0, jitter, pts[..., :2].shape).astype(np.float32)
-    boxes = np.stack([pts[..., 1].min(1), pts[..., 0].min(1), pts[..., 1].max(1), pts[..., 0].max(1)], 1)
-    return pts, np.round(boxes).astype(np.int32)
-
-
+COCO = costlib.coco_skeleton()
 pkg = importlib.import_module("simple-hrnet_amd")
-
-if args.child_only:
-    net = pkg.NativeHRNet(32, 17, (256, 192), "bf16", max_batch=8, device=0).load_state_dict(pkg.synth_state_dict(32, 17, 0))
-    fdev = torch.from_numpy(np.random.default_rng(6).integers(0, 256, (hf, wf, 3), dtype=np.uint8)).cuda()
-    p, boxes = people_of(8, 1)
-    pdev, ids = torch.from_numpy(p).cuda(), np.arange(8, dtype=np.int32)
-    s = timed({"predict": lambda: net.predict_frame(fdev, boxes.astype(np.float32)),
-               "draw": lambda: net.draw_poses(fdev, pdev, COCO, person_ids=ids)}, args.rounds, args.reps)
-    net.close()
-    print(json.dumps({k: statistics.median(v) for k, v in s.items()}))
-    sys.exit(0)
-
-os.makedirs(args.out, exist_ok=True)
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
-
-
-def fmt(s):
-    return "%8.4f ms  (min %.4f .. max %.4f)" % (statistics.median(s), min(s), max(s))
-
+report = costlib.Report(args.out, "assoc_ids.txt")
+say, fmt = report.say, report.fmt
 
 say("person ids -- tools/assoc_cost.py; %d samples of %d calls per candidate, interleaved, HIP events, host side included, medians"
     % (args.rounds, args.reps))
@@ -123,9 +47,9 @@ say("(a) associate_people, J = 17, demo parameters (pose_alpha %.1f, threshold %
     % (alpha, thr, smooth))
 say("    previous person in shuffled order; host path = download pts + boxes, find_person_id_associations, upload ids + pts + boxes")
 for count in (8, 64, 256):
-    prev_pts, prev_boxes = people_of(count, count)
+    prev_pts, prev_boxes = people_of(count, seed=count)
     order = np.random.default_rng(count).permutation(count)
-    cur_pts, cur_boxes = people_of(count, count + 1, jitter=3.0, base=prev_pts[order])
+    cur_pts, cur_boxes = people_of(count, seed=count + 1, jitter=3.0, base=prev_pts[order])
     prev_ids = np.arange(count, dtype=np.int32)
     dev = [torch.from_numpy(v).cuda() for v in (cur_boxes, cur_pts, prev_boxes, prev_pts, prev_ids)]
     work_boxes, work_pts = dev[0].clone(), dev[1].clone()
@@ -167,7 +91,7 @@ bare.close()
 
 say()
 bgr = torch.from_numpy(np.random.default_rng(6).integers(0, 256, (hf, wf, 3), dtype=np.uint8)).cuda()
-pts8 = torch.from_numpy(people_of(8, 8)[0]).cuda()
+pts8 = torch.from_numpy(people_of(8, seed=8)[0]).cuda()
 ids_host = np.arange(3, 11, dtype=np.int32)
 ids_dev = torch.from_numpy(ids_host).cuda()
 s = timed({"host": lambda: net.draw_poses(bgr, pts8, COCO, person_ids=ids_host), "device": lambda: net.draw_poses(bgr, pts8, COCO, person_ids=ids_dev)},
@@ -178,28 +102,7 @@ say("    ids on the device    %s   (three launches, no host read)" % fmt(s["devi
 net.close()
 
 say()
-if not args.ab_root:
-    say("(c) draw_poses with host ids and predict_frame, this tree against the parent commit: NOT MEASURED (no --ab-root)")
-else:
-    sides = {"parent": os.path.abspath(args.ab_root), "this tree": ROOT}
-    meds = {k: {"draw": [], "predict": []} for k in sides}
-    for _ in range(args.ab_pairs):
-        for k, root in sides.items():    # fresh children, alternately
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-only", "--root", root, "--rounds", str(args.rounds),
-                                  "--reps", str(args.reps)], capture_output=True, text=True, timeout=300, check=True).stdout
-            res = json.loads(out.strip().splitlines()[-1])
-            for what in ("draw", "predict"):
-                meds[k][what].append(res[what])
-    say("(c) this tree against the parent commit, %d fresh processes per side, alternately, same box" % args.ab_pairs)
-    for what, title in (("draw", "draw_poses, host ids, 8 people, 1080p BGR"), ("predict", "predict_frame, 8 people of a 1080p frame, HRNet-W32 256x192 bf16")):
-        say("    %s" % title)
-        for k in sides:
-            say("        %-10s medians %s ms -> %.4f ms" % (k, ", ".join("%.4f" % v for v in meds[k][what]), statistics.median(meds[k][what])))
-        spread = max(max(meds[k][what]) - min(meds[k][what]) for k in sides)
-        diff = statistics.median(meds["this tree"][what]) - statistics.median(meds["parent"][what])
-        say("        difference %+.4f ms; spread of the processes' medians (the wider side) %.4f ms -> %s"
-            % (diff, spread, "unchanged" if abs(diff) <= spread else ("SLOWER" if diff > 0 else "faster") + " beyond the spread"))
+runs = costlib.ab(report, "(c)", ["draw8_ids", "predict"], args.ab_root, args.ab_pairs, args.rounds, args.reps)
 say()
 say("Not claimed: how well these ids follow people on a trained network -- no trained weights and no video exist where this was measured.")
-with open(os.path.join(args.out, "assoc_ids.txt"), "w") as f:
-    f.write("\n".join(lines) + "\n")
+sys.exit(runs is None)

@@ -30,6 +30,7 @@ import numpy as np   # noqa: E402
 import torch         # noqa: E402
 
 import bench         # noqa: E402  (make_clip, run_clip: arm A and D are bench.py's own code)
+import costlib       # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", required=True, help="directory clip_mode.txt is written to")
@@ -38,17 +39,11 @@ ap.add_argument("--frames", type=int, nargs="+", default=[30, 240])
 args = ap.parse_args()
 if args.reps < 9:
     ap.error("--reps must be at least 9")
-os.makedirs(args.out, exist_ok=True)
 
 pkg = importlib.import_module("simple-hrnet_amd")
 dev = torch.device("cuda", 0)
 net = pkg.NativeHRNet(48, 17, (384, 288), "bf16", max_batch=256, device=0).load_state_dict(pkg.synth_state_dict(48, 17, 0))
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
+say = costlib.Report(args.out, "clip_mode.txt").say
 
 
 def run_frames(clip_host, dets):
@@ -102,7 +97,7 @@ for nf in args.frames:
     secs = {k: [] for k in names}
     peak = {}
     for r in range(args.reps):
-        for k in names[r % len(names):] + names[:r % len(names)]:
+        for k in costlib.rotated(names, r):
             torch.cuda.synchronize(dev)
             torch.cuda.reset_peak_memory_stats(dev)
             _, dt = arms[k]()
@@ -131,5 +126,3 @@ say("condition (B on the 30-frame clip, the best C on the 240-frame clip, each n
 for v in verdicts:
     say("  " + v)
 net.close()
-with open(os.path.join(args.out, "clip_mode.txt"), "w") as f:
-    f.write("\n".join(lines) + "\n")

@@ -11,40 +11,26 @@ record -- the call may be launch-bound, and a size may lose to the round trip.
       rotated order), medians.
   (b) the two launches alone under `rocprofv3 --kernel-trace --stats`, one traced child process per size.
   (c) --ab-root DIR: predict_frame (8 people, HRNet-W32 256x192 bf16) in THIS tree against the checkout at DIR (the parent commit,
-      built), each in fresh child processes run alternately on the same box; a difference inside the spread of the children's
-      medians is "unchanged".  Without --ab-root: NOT MEASURED.
+      built): costlib.ab, the protocol of tools/README.md.  Without --ab-root: NOT MEASURED.
 
 usage: python tools/detector_nms_cost.py --out DIR [--rounds R] [--reps K] [--no-trace] [--ab-root DIR]
-       python tools/detector_nms_cost.py --trace-child K         (the child of (b): a few calls of size K, under rocprofv3)
-       python tools/detector_nms_cost.py --child-only [--root DIR]     (the child of (c): one JSON line)"""
-import argparse
-import csv
-import glob
+       python tools/detector_nms_cost.py --trace-child K         (the child of (b): a few calls of size K, under rocprofv3)"""
 import importlib
-import json
 import os
 import shutil
 import statistics
-import subprocess
 import sys
 import tempfile
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-ap = argparse.ArgumentParser()
-ap.add_argument("--out", help="directory detector_nms.txt is written to")
-ap.add_argument("--rounds", type=int, default=9)
-ap.add_argument("--reps", type=int, default=20, help="calls per timed sample")
+import costlib
+
+ap = costlib.parser(__doc__, "detector_nms.txt", rounds=9, reps=20, ab="predict_frame", out_required=False)
 ap.add_argument("--no-trace", action="store_true", help="skip (b)")
 ap.add_argument("--trace-child", type=int, help="run a few device calls of size K (under rocprofv3)")
-ap.add_argument("--ab-root", help="checkout of the parent commit, built: predict_frame there against here")
-ap.add_argument("--ab-pairs", type=int, default=3, help="child processes per side of the A/B")
-ap.add_argument("--child-only", action="store_true", help="time predict_frame of (c) alone and print one JSON line")
-ap.add_argument("--root", default=ROOT, help="with --child-only: the checkout whose package is timed")
 args = ap.parse_args()
-if not args.child_only and args.trace_child is None and not args.out:
+if args.trace_child is None and not args.out:
     ap.error("--out is needed")
-sys.path.insert(0, os.path.abspath(args.root) if args.child_only else ROOT)
+sys.path.insert(0, costlib.ROOT)
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
 
@@ -52,26 +38,6 @@ SIZES = ((1, 25200, 80, "yolov5"), (16, 25200, 80, "yolov5"), (1, 10647, 80, "yo
 CANDIDATES, CONF, IOU = 200, 0.25, 0.45
 KERNELS = ("dnms_score_kernel", "dnms_image_kernel")
 PEAK = 6.15e12   # bytes / s, HBM
-
-
-def timed(cands, rounds, reps):
-    """HIP-event ms per call of every candidate: `rounds` samples of `reps` calls each, interleaved in a rotated order"""
-    for fn in cands.values():
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    names = list(cands)
-    samples = {k: [] for k in names}
-    for r in range(rounds):
-        for k in names[r % len(names):] + names[:r % len(names)]:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                cands[k]()
-            b.record()
-            b.synchronize()
-            samples[k].append(a.elapsed_time(b) / reps)
-    return samples
 
 
 def head_output(B, N, C, passing, seed):
@@ -95,25 +61,7 @@ def head_output(B, N, C, passing, seed):
     return pred
 
 
-def frame_people(count, seed, hf=1080, wf=1920):
-    rng = np.random.default_rng(seed)
-    bh = rng.uniform(200, 600, count)
-    bw = bh * rng.uniform(0.3, 0.6, count)
-    x1, y1 = rng.uniform(0, wf - bw), rng.uniform(0, hf - bh)
-    return np.stack([x1, y1, x1 + bw, y1 + bh], 1).astype(np.float32)
-
-
 pkg = importlib.import_module("simple-hrnet_amd")
-
-if args.child_only:
-    net = pkg.NativeHRNet(32, 17, (256, 192), "bf16", max_batch=8, device=0).load_state_dict(pkg.synth_state_dict(32, 17, 0))
-    fdev = torch.from_numpy(np.random.default_rng(6).integers(0, 256, (1080, 1920, 3), dtype=np.uint8)).cuda()
-    boxes = frame_people(8, 1)
-    s = timed({"predict": lambda: net.predict_frame(fdev, boxes)}, args.rounds, args.reps)
-    net.close()
-    print(json.dumps({k: statistics.median(v) for k, v in s.items()}))
-    sys.exit(0)
-
 net = pkg.NativeHRNet(32, 17, (64, 64), "bf16", max_batch=1, device=0)   # detector NMS needs no weights
 
 if args.trace_child is not None:
@@ -125,29 +73,8 @@ if args.trace_child is not None:
     net.close()
     sys.exit(0)
 
-os.makedirs(args.out, exist_ok=True)
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
-
-
-def fmt(s):
-    return "%9.4f ms  (min %.4f .. max %.4f)" % (statistics.median(s), min(s), max(s))
-
-
-def kernel_stats(stats_dir):
-    """name -> (calls, average ns) of the two kernels in a rocprofv3 --stats directory"""
-    found = {}
-    for path in glob.glob(os.path.join(stats_dir, "**", "*kernel_stats.csv"), recursive=True):
-        for row in csv.DictReader(open(path)):
-            for name in KERNELS:
-                if name in row["Name"]:
-                    found[name] = (int(row["Calls"]), float(row["AverageNs"]))
-    return found
-
+report = costlib.Report(args.out, "detector_nms.txt", "%9.4f ms  (min %.4f .. max %.4f)")
+say, fmt = report.say, report.fmt
 
 say("detector NMS -- tools/detector_nms_cost.py; %d samples of %d calls per candidate, interleaved, HIP events, host side included, medians"
     % (args.rounds, args.reps))
@@ -175,7 +102,7 @@ for k, (B, N, C, rule) in enumerate(SIZES):
     same = np.array_equal(got[0].cpu().numpy().view(np.uint32), want[0].cpu().numpy().view(np.uint32)) and \
         np.array_equal(got[1].cpu().numpy(), want[1])
     reps = args.reps if B == 1 else max(2, args.reps // 4)
-    s = timed({"device": device_call, "empty": empty_call, "host": host_call}, args.rounds, reps)
+    s = costlib.timed({"device": device_call, "empty": empty_call, "host": host_call}, args.rounds, reps)
     med = {key: statistics.median(v) for key, v in s.items()}
     stride = 4 * (5 + C)
     useful = B * (4 * N + CANDIDATES * (stride - 4))
@@ -191,18 +118,15 @@ for k, (B, N, C, rule) in enumerate(SIZES):
         % (useful / 1e6, useful / PEAK * 1e3, lines_touched / 1e6, lines_touched / PEAK * 1e3))
     say("      device call / line floor = %.1f; (device call - empty call) / line floor = %.1f"
         % (med["device"] / (lines_touched / PEAK * 1e3), max(med["device"] - med["empty"], 0.0) / (lines_touched / PEAK * 1e3)))
-    rocprof = shutil.which("rocprofv3")
-    if args.no_trace or not rocprof:
+    if args.no_trace or not shutil.which("rocprofv3"):
         say("(b) the two launches under rocprofv3 --kernel-trace --stats: NOT MEASURED (%s)" % ("--no-trace" if args.no_trace else "no rocprofv3"))
         continue
     d = tempfile.mkdtemp(prefix="dnms_trace_")
-    rc = subprocess.run([rocprof, "--kernel-trace", "--stats", "-d", d, "-o", "t", "--output-format", "csv", "--", sys.executable,
-                         os.path.abspath(__file__), "--trace-child", str(k)], timeout=600, stdin=subprocess.DEVNULL,
-                        stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL).returncode
-    found = kernel_stats(d)
+    costlib.traced([sys.executable, os.path.abspath(__file__), "--trace-child", str(k)], d)
+    found = costlib.kernel_stats(d, KERNELS)
     shutil.rmtree(d, ignore_errors=True)
-    if rc != 0 or not found:
-        say("(b) the two launches under rocprofv3 --kernel-trace --stats: NOT MEASURED (exit code %d, %d kernels found)" % (rc, len(found)))
+    if not found:
+        say("(b) the two launches under rocprofv3 --kernel-trace --stats: NOT MEASURED (no kernel of the call in the statistics)")
         continue
     say("(b) the two launches (rocprofv3 --kernel-trace --stats, a traced run of its own; average over %d calls):" % max(v[0] for v in found.values()))
     for name in KERNELS:
@@ -217,27 +141,7 @@ for k, (B, N, C, rule) in enumerate(SIZES):
 net.close()
 
 say()
-if not args.ab_root:
-    say("(c) predict_frame, this tree against the parent commit: NOT MEASURED (no --ab-root)")
-else:
-    sides = {"parent": os.path.abspath(args.ab_root), "this tree": ROOT}
-    meds = {key: [] for key in sides}
-    for _ in range(args.ab_pairs):
-        for key, root in sides.items():    # fresh children, alternately
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-only", "--root", root, "--rounds", str(args.rounds),
-                                  "--reps", str(args.reps)], capture_output=True, text=True, timeout=300, check=True,
-                                 stdin=subprocess.DEVNULL).stdout
-            meds[key].append(json.loads(out.strip().splitlines()[-1])["predict"])
-    say("(c) predict_frame, 8 people of a 1080p frame, HRNet-W32 256x192 bf16: this tree against the parent commit, %d fresh processes per"
-        % args.ab_pairs)
-    say("    side, alternately, same box")
-    for key in sides:
-        say("        %-10s medians %s ms -> %.4f ms" % (key, ", ".join("%.4f" % v for v in meds[key]), statistics.median(meds[key])))
-    spread = max(max(meds[key]) - min(meds[key]) for key in sides)
-    diff = statistics.median(meds["this tree"]) - statistics.median(meds["parent"])
-    say("        difference %+.4f ms; spread of the processes' medians (the wider side) %.4f ms -> %s"
-        % (diff, spread, "unchanged" if abs(diff) <= spread else ("SLOWER" if diff > 0 else "faster") + " beyond the spread"))
+runs = costlib.ab(report, "(c)", ["predict"], args.ab_root, args.ab_pairs, args.rounds, args.reps)
 say()
 say("Not claimed: the candidate count of a trained detector on real video -- no trained weights and no video exist where this was measured.")
-with open(os.path.join(args.out, "detector_nms.txt"), "w") as f:
-    f.write("\n".join(lines) + "\n")
+sys.exit(runs is None)

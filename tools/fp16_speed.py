@@ -6,6 +6,8 @@ import argparse, importlib, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
+import costlib
+
 pkg = importlib.import_module("simple-hrnet_amd")
 ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=8)
@@ -16,20 +18,8 @@ sd = pkg.synth_state_dict(c, 17, 0)
 crops = torch.randn((n, 3, h, w), generator=torch.Generator(device="cuda").manual_seed(1234), device="cuda")
 boxes = torch.from_numpy(pkg.synth_boxes(n)).cuda()
 nets = {dt: pkg.NativeHRNet(c, 17, (h, w), dt, max_batch=n, device=0).load_state_dict(sd) for dt in ("bf16", "fp16")}
-for net in nets.values():            # warm-up: block maps, LDS attributes, clocks
-    for _ in range(3):
-        net.predict_crops(crops, boxes)
-torch.cuda.synchronize()
-samples = {dt: [] for dt in nets}
-for r in range(args.rounds):
-    for dt in (("bf16", "fp16") if r % 2 == 0 else ("fp16", "bf16")):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(args.reps):
-            nets[dt].predict_crops(crops, boxes)
-        b.record()
-        b.synchronize()
-        samples[dt].append(n * args.reps / (a.elapsed_time(b) / 1e3))
+ms = costlib.timed({dt: (lambda net=net: net.predict_crops(crops, boxes)) for dt, net in nets.items()}, args.rounds, args.reps)
+samples = {dt: [n / (v / 1e3) for v in ms[dt]] for dt in nets}   # (the warm-up: block maps, LDS attributes, clocks)
 for net in nets.values():
     net.close()
 med = {dt: statistics.median(v) for dt, v in samples.items()}

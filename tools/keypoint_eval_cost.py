@@ -8,29 +8,21 @@ call costs beside the host forms is a result to record, and the call may lose (t
         - the numpy restatement tests/keypoint_eval_ref.py, wall clock, one run: a STAND-IN for pycocotools' COCOeval, which is
           not installed where this is measured.
   (b) each kernel's share of the device call: `rocprofv3 --kernel-trace --stats`, a traced child of its own per size.
-  (c) --ab-root DIR: predict_frame in THIS tree against the checkout at DIR (the parent commit, built), through the child mode of
-      tools/pose_nms_cost.py: fresh processes, alternately, same box.  Without --ab-root: NOT MEASURED.
+  (c) --ab-root DIR: predict_frame (8 people, HRNet-W32 256x192 bf16) in THIS tree against the checkout at DIR (the parent commit,
+      built): costlib.ab, the protocol of tools/README.md.  Without --ab-root: NOT MEASURED.
 
 usage: python tools/keypoint_eval_cost.py --out DIR [--rounds R] [--ab-root DIR] [--no-trace]
        python tools/keypoint_eval_cost.py --trace-child K       (the child of (b): size K, a few device calls)"""
-import argparse
-import csv
-import glob
 import importlib
-import json
 import os
 import statistics
-import subprocess
 import sys
 import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-ap = argparse.ArgumentParser()
-ap.add_argument("--out", help="directory keypoint_eval.txt is written to")
-ap.add_argument("--rounds", type=int, default=5)
-ap.add_argument("--ab-root", help="checkout of the parent commit, built: predict_frame there against here")
-ap.add_argument("--ab-pairs", type=int, default=3)
+import costlib
+from costlib import ROOT
+
+ap = costlib.parser(__doc__, "keypoint_eval.txt", rounds=5, ab="predict_frame", out_required=False)
 ap.add_argument("--no-trace", action="store_true", help="skip (b)")
 ap.add_argument("--trace-child", type=int, help="run a few device calls of size K (under rocprofv3)")
 args = ap.parse_args()
@@ -68,46 +60,8 @@ if args.trace_child is not None:
     net.close()
     sys.exit(0)
 
-os.makedirs(args.out, exist_ok=True)
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
-    with open(os.path.join(args.out, "keypoint_eval.txt"), "w") as f:   # every finished line is kept at once
-        f.write("\n".join(lines) + "\n")
-
-
-def fmt(s):
-    return "%10.3f ms  (min %.3f .. max %.3f)" % (statistics.median(s), min(s), max(s))
-
-
-def timed(cands, rounds):
-    """HIP-event ms per call of every candidate, host side included: `rounds` samples, interleaved in a rotated order"""
-    names = list(cands)
-    samples = {k: [] for k in names}
-    for r in range(rounds):
-        for k in names[r % len(names):] + names[:r % len(names)]:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            cands[k]()
-            b.record()
-            b.synchronize()
-            samples[k].append(a.elapsed_time(b))
-    return samples
-
-
-def kernel_stats(stats_dir):
-    """name -> (calls, average ns) of the four kernels in a rocprofv3 --stats directory"""
-    found = {}
-    for path in glob.glob(os.path.join(stats_dir, "**", "*kernel_stats.csv"), recursive=True):
-        for row in csv.DictReader(open(path)):
-            for name in KERNELS:
-                if name in row["Name"]:
-                    found[name] = (int(row["Calls"]), float(row["AverageNs"]))
-    return found
-
+report = costlib.Report(args.out, "keypoint_eval.txt", "%10.3f ms  (min %.3f .. max %.3f)")
+say, fmt = report.say, report.fmt
 
 say("COCO keypoint AP / AR -- tools/keypoint_eval_cost.py; %d samples per candidate, one call each, interleaved, HIP events, host side"
     % args.rounds)
@@ -128,7 +82,7 @@ for k, (images, dets, joints) in enumerate(SIZES):
 
     got, want = device_call(), host_call()[0]
     same = all(np.array_equal(got[key].cpu().numpy(), want[key], equal_nan=True) for key in ("stats", "precision", "recall", "dt_match", "dt_ignore"))
-    s = timed({"device": device_call, "host": host_call}, args.rounds)
+    s = costlib.timed({"device": device_call, "host": host_call}, args.rounds, warmup=0)
     t0 = time.perf_counter()
     ref = R.keypoint_eval(**case)
     ref_ms = (time.perf_counter() - t0) * 1e3
@@ -146,10 +100,8 @@ for k, (images, dets, joints) in enumerate(SIZES):
         say("(b) kernel shares: NOT MEASURED (--no-trace)")
         continue
     d = os.path.join(args.out, "keypoint_eval_trace_%d" % k)
-    subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "t", "--output-format", "csv", "--", sys.executable,
-                    os.path.abspath(__file__), "--trace-child", str(k)], check=True, timeout=600, stdin=subprocess.DEVNULL,
-                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    found = kernel_stats(d)
+    costlib.traced([sys.executable, os.path.abspath(__file__), "--trace-child", str(k)], d)
+    found = costlib.kernel_stats(d, KERNELS)
     total = sum(v[1] for v in found.values()) or 1.0
     say("(b) kernels of one call (rocprofv3 --kernel-trace --stats, a traced run of its own; average over %d calls):"
         % (max(v[0] for v in found.values()) if found else 0))
@@ -161,25 +113,8 @@ for k, (images, dets, joints) in enumerate(SIZES):
 net.close()
 
 say()
-if not args.ab_root:
-    say("(c) predict_frame, this tree against the parent commit: NOT MEASURED (no --ab-root)")
-else:
-    sides = {"parent": os.path.abspath(args.ab_root), "this tree": ROOT}
-    meds = {key: [] for key in sides}
-    for _ in range(args.ab_pairs):
-        for key, root in sides.items():    # fresh children, alternately
-            out = subprocess.run([sys.executable, os.path.join(HERE, "pose_nms_cost.py"), "--child-only", "--root", root], capture_output=True,
-                                 text=True, timeout=300, check=True, stdin=subprocess.DEVNULL).stdout
-            meds[key].append(json.loads(out.strip().splitlines()[-1])["predict"])
-    say("(c) predict_frame, 8 people of a 1080p frame, HRNet-W32 256x192 bf16: this tree against the parent commit, %d fresh processes per"
-        % args.ab_pairs)
-    say("    side, alternately, same box")
-    for key in sides:
-        say("        %-10s medians %s ms -> %.4f ms" % (key, ", ".join("%.4f" % v for v in meds[key]), statistics.median(meds[key])))
-    spread = max(max(meds[key]) - min(meds[key]) for key in sides)
-    diff = statistics.median(meds["this tree"]) - statistics.median(meds["parent"])
-    say("        difference %+.4f ms; spread of the processes' medians (the wider side) %.4f ms -> %s"
-        % (diff, spread, "unchanged" if abs(diff) <= spread else ("SLOWER" if diff > 0 else "faster") + " beyond the spread"))
+runs = costlib.ab(report, "(c)", ["predict"], args.ab_root, args.ab_pairs, rounds=9, reps=20)   # (the child's own sample counts)
 say()
 say("Not claimed: parity with pycocotools' COCOeval (not installed here; tests/golden/make_cocoeval_golden.py measures it where it is),")
 say("and any AP of trained weights -- no trained weights and no images exist where this was measured.")
+sys.exit(runs is None)

@@ -10,107 +10,37 @@ beside an empty launch pair, and beside what a label drawn on the host must pay 
           before they draw.
       And, by the host's clock (a synchronisation is not on any stream): the download of ids, boxes and scores followed by the
       synchronisation a host needs before it can turn an id into text, with the stream idle and behind one draw_poses call.
-  (b) --ab-root DIR: draw_poses (8 and 64 people, BGR) in THIS tree against the checkout at DIR (the parent commit, built), each
-      in fresh child processes run alternately on the same box, the parent first and last.  The spread between the parent's own
-      runs is stated; a difference inside it is "unchanged".  Without --ab-root: NOT MEASURED.
+  (b) --ab-root DIR: draw_poses (8 and 64 people, BGR) in THIS tree against the checkout at DIR (the parent commit, built):
+      costlib.ab, the protocol of tools/README.md.  Without --ab-root: NOT MEASURED.
 
-usage: python tools/labels_cost.py --out DIR [--rounds R] [--reps K] [--ab-root DIR]
-       python tools/labels_cost.py --draw-only [--root DIR]     (the child of (b): one JSON line)"""
-import argparse
+usage: python tools/labels_cost.py --out DIR [--rounds R] [--reps K] [--ab-root DIR]"""
 import importlib
-import json
-import os
 import statistics
-import subprocess
 import sys
 import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-ap = argparse.ArgumentParser()
-ap.add_argument("--out", help="directory draw_labels.txt is written to")
-ap.add_argument("--rounds", type=int, default=9)
-ap.add_argument("--reps", type=int, default=20, help="calls per timed sample")
-ap.add_argument("--ab-root", help="checkout of the parent commit, built: draw_poses there against here")
-ap.add_argument("--ab-pairs", type=int, default=3, help="child processes of this tree in the A/B (the parent runs once more)")
-ap.add_argument("--draw-only", action="store_true", help="time draw_poses of (b) alone and print one JSON line")
-ap.add_argument("--root", default=ROOT, help="with --draw-only: the checkout whose package is timed")
-args = ap.parse_args()
-if not args.draw_only and not args.out:
-    ap.error("--out is needed")
-sys.path.insert(0, os.path.abspath(args.root) if args.draw_only else ROOT)
+import costlib
+
+args = costlib.parser(__doc__, "draw_labels.txt", rounds=9, reps=20, ab="draw_poses").parse_args()
+sys.path.insert(0, costlib.ROOT)
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
 
 hf, wf = 1080, 1920
-COCO = json.load(open(os.path.join(ROOT, "tests", "golden", "coco_skeleton.json")))["coco_skeleton"]
-
-
-def timed(cands, rounds, reps):
-    """HIP-event ms per call of every candidate: `rounds` samples of `reps` calls each, interleaved in a rotated order"""
-    for fn in cands.values():
-        for _ in range(5):
-            fn()
-    torch.cuda.synchronize()
-    names = list(cands)
-    samples = {k: [] for k in names}
-    for r in range(rounds):
-        for k in names[r % len(names):] + names[:r % len(names)]:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                cands[k]()
-            b.record()
-            b.synchronize()
-            samples[k].append(a.elapsed_time(b) / reps)
-    return samples
-
-
-def people_of(count, seed):
-    """`count` people of plausible size spread over the frame: boxes (count, 4) int32 and joints (count, 17, 3) inside them"""
-    rng = np.random.default_rng(seed)
-    boxes, pts = np.empty((count, 4), np.int32), np.empty((count, 17, 3), np.float32)
-    for i in range(count):
-        bh = rng.uniform(300, 900)
-        bw = bh * rng.uniform(0.3, 0.6)
-        x1, y1 = rng.uniform(0, wf - bw), rng.uniform(0, hf - bh)
-        boxes[i] = x1, y1, x1 + bw, y1 + bh
-        pts[i, :, 0] = rng.uniform(y1, y1 + bh, 17)
-        pts[i, :, 1] = rng.uniform(x1, x1 + bw, 17)
-    pts[..., 2] = 0.9
-    return boxes, pts
-
-
+COCO = costlib.coco_skeleton()
 pkg = importlib.import_module("simple-hrnet_amd")
 net = pkg.NativeHRNet(32, 17, (64, 64), "bf16", max_batch=1, device=0)   # drawing needs no weights
 rng = np.random.default_rng(6)
 bgr = torch.from_numpy(rng.integers(0, 256, (hf, wf, 3), dtype=np.uint8)).cuda()
-people = {c: people_of(c, c) for c in (8, 64)}
-pts = {c: torch.from_numpy(people[c][1]).cuda() for c in (8, 64)}
-
-if args.draw_only:
-    s = timed({"bgr%d" % c: (lambda c=c: net.draw_poses(bgr, pts[c], COCO)) for c in (8, 64)}, args.rounds, args.reps)
-    net.close()
-    print(json.dumps({k: statistics.median(v) for k, v in s.items()}))
-    sys.exit(0)
-
-os.makedirs(args.out, exist_ok=True)
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
-
-
-def fmt(s):
-    return "%8.4f ms  (min %.4f .. max %.4f)" % (statistics.median(s), min(s), max(s))
-
+people = {c: costlib.people_of(c, seed=c) for c in (8, 64)}
+pts = {c: torch.from_numpy(people[c][0]).cuda() for c in (8, 64)}
+report = costlib.Report(args.out, "draw_labels.txt")
+say, fmt = report.say, report.fmt
 
 say("person labels -- tools/labels_cost.py; %d samples of %d calls per candidate, interleaved, HIP events, medians" % (args.rounds, args.reps))
 say("device: %s" % torch.cuda.get_device_name(0))
 nv12 = pkg.YuvFrame(rng.integers(0, 256, hf * wf * 3 // 2, dtype=np.uint8), hf, wf, "nv12").to("cuda:0")
-boxes = {c: torch.from_numpy(people[c][0]).cuda() for c in (8, 64)}
+boxes = {c: torch.from_numpy(people[c][1]).cuda() for c in (8, 64)}
 ids = {c: torch.arange(100, 100 + c, dtype=torch.int32, device="cuda") for c in (8, 64)}
 scores = {c: torch.from_numpy(rng.uniform(0, 1, c).astype(np.float32)).cuda() for c in (8, 64)}
 host = torch.empty((hf, wf, 3), dtype=torch.uint8).pin_memory()
@@ -126,7 +56,7 @@ cands = {"empty": lambda: net.draw_labels(bgr[:32, :32], nobody), "copies": roun
 for c in (8, 64):
     cands["bgr%d" % c] = lambda c=c: net.draw_labels(bgr, boxes[c], ids[c], scores[c])
     cands["nv12%d" % c] = lambda c=c: net.draw_labels(nv12, boxes[c], ids[c], scores[c])
-s = timed(cands, args.rounds, args.reps)
+s = costlib.timed(cands, args.rounds, args.reps, warmup=5)
 say()
 say("(a) draw_labels on a %dx%d frame resident in HBM: outline (thickness 2), three id digits, a blank and the score, scale %d"
     % (wf, hf, max(1, hf // 360)))
@@ -164,24 +94,4 @@ for c in (8, 64):
 net.close()
 
 say()
-if not args.ab_root:
-    say("(b) draw_poses, this tree against the parent commit: NOT MEASURED (no --ab-root)")
-else:
-    sides = {"parent": os.path.abspath(args.ab_root), "this tree": ROOT}
-    order = ["parent"] + ["this tree", "parent"] * args.ab_pairs         # fresh children, alternately, the parent first and last
-    meds = {k: {"bgr8": [], "bgr64": []} for k in sides}
-    for k in order:
-        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--draw-only", "--root", sides[k], "--rounds", str(args.rounds),
-                              "--reps", str(args.reps)], capture_output=True, text=True, timeout=300, check=True).stdout
-        for name, v in json.loads(out.strip().splitlines()[-1]).items():
-            meds[k][name].append(v)
-    say("(b) draw_poses on the %dx%d BGR frame: this tree against the parent commit, fresh processes run alternately on the same box" % (wf, hf))
-    for name, c in (("bgr8", 8), ("bgr64", 64)):
-        for k in sides:
-            say("    %2d people, %-10s medians %s ms -> %.4f ms" % (c, k, ", ".join("%.4f" % v for v in meds[k][name]), statistics.median(meds[k][name])))
-        spread = max(meds["parent"][name]) - min(meds["parent"][name])
-        diff = statistics.median(meds["this tree"][name]) - statistics.median(meds["parent"][name])
-        say("    %2d people: difference %+.4f ms; spread between the parent's own runs %.4f ms -> %s"
-            % (c, diff, spread, "unchanged" if abs(diff) <= spread else ("SLOWER" if diff > 0 else "faster") + " beyond the spread"))
-with open(os.path.join(args.out, "draw_labels.txt"), "w") as f:
-    f.write("\n".join(lines) + "\n")
+sys.exit(costlib.ab(report, "(b)", ["draw8", "draw64"], args.ab_root, args.ab_pairs, args.rounds, args.reps) is None)

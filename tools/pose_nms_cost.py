@@ -9,59 +9,24 @@ person, serial over the joints: profiles/pose_nms.txt has it losing at 133 joint
   (b) NativeHRNet.nms_eval at 5 000 images x 20 people (uploads, one launch, downloads and the grouping included) against the host
       loop of datasets/COCO.py:358-382 over postproc.oks_nms; wall clock, `--eval-rounds` runs each, alternately.
   (c) --ab-root DIR: predict_frame (8 people, HRNet-W32 256x192 bf16) in THIS tree against the checkout at DIR (the parent commit,
-      built), each in fresh child processes run alternately on the same box; a difference inside the spread of the children's
-      medians is "unchanged".  Without --ab-root: NOT MEASURED.
+      built): costlib.ab, the protocol of tools/README.md.  Without --ab-root: NOT MEASURED.
 
-usage: python tools/pose_nms_cost.py --out DIR [--rounds R] [--reps K] [--eval-rounds E] [--ab-root DIR]
-       python tools/pose_nms_cost.py --child-only [--root DIR]     (the child of (c): one JSON line)"""
-import argparse
+usage: python tools/pose_nms_cost.py --out DIR [--rounds R] [--reps K] [--eval-rounds E] [--ab-root DIR]"""
 import importlib
-import json
-import os
 import statistics
-import subprocess
 import sys
 import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-ap = argparse.ArgumentParser()
-ap.add_argument("--out", help="directory pose_nms.txt is written to")
-ap.add_argument("--rounds", type=int, default=9)
-ap.add_argument("--reps", type=int, default=20, help="calls per timed sample")
+import costlib
+
+ap = costlib.parser(__doc__, "pose_nms.txt", rounds=9, reps=20, ab="predict_frame")
 ap.add_argument("--eval-rounds", type=int, default=3)
-ap.add_argument("--ab-root", help="checkout of the parent commit, built: predict_frame there against here")
-ap.add_argument("--ab-pairs", type=int, default=3, help="child processes per side of the A/B")
-ap.add_argument("--child-only", action="store_true", help="time predict_frame of (c) alone and print one JSON line")
-ap.add_argument("--root", default=ROOT, help="with --child-only: the checkout whose package is timed")
 args = ap.parse_args()
-if not args.child_only and not args.out:
-    ap.error("--out is needed")
-sys.path.insert(0, os.path.abspath(args.root) if args.child_only else ROOT)
+sys.path.insert(0, costlib.ROOT)
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
 
 hf, wf = 1080, 1920
-
-
-def timed(cands, rounds, reps):
-    """HIP-event ms per call of every candidate: `rounds` samples of `reps` calls each, interleaved in a rotated order"""
-    for fn in cands.values():
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    names = list(cands)
-    samples = {k: [] for k in names}
-    for r in range(rounds):
-        for k in names[r % len(names):] + names[:r % len(names)]:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                cands[k]()
-            b.record()
-            b.synchronize()
-            samples[k].append(a.elapsed_time(b) / reps)
-    return samples
 
 
 def crowd(count, joints, seed, bodies=None, per_image=None):
@@ -85,28 +50,8 @@ def crowd(count, joints, seed, bodies=None, per_image=None):
 
 
 pkg = importlib.import_module("simple-hrnet_amd")
-
-if args.child_only:
-    net = pkg.NativeHRNet(32, 17, (256, 192), "bf16", max_batch=8, device=0).load_state_dict(pkg.synth_state_dict(32, 17, 0))
-    fdev = torch.from_numpy(np.random.default_rng(6).integers(0, 256, (hf, wf, 3), dtype=np.uint8)).cuda()
-    boxes = crowd(8, 17, 1, bodies=8)[1].astype(np.float32)
-    s = timed({"predict": lambda: net.predict_frame(fdev, boxes)}, args.rounds, args.reps)
-    net.close()
-    print(json.dumps({k: statistics.median(v) for k, v in s.items()}))
-    sys.exit(0)
-
-os.makedirs(args.out, exist_ok=True)
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
-
-
-def fmt(s):
-    return "%9.4f ms  (min %.4f .. max %.4f)" % (statistics.median(s), min(s), max(s))
-
+report = costlib.Report(args.out, "pose_nms.txt", "%9.4f ms  (min %.4f .. max %.4f)")
+say, fmt = report.say, report.fmt
 
 say("pose NMS -- tools/pose_nms_cost.py; %d samples of %d calls per candidate, interleaved, HIP events, host side included, medians"
     % (args.rounds, args.reps))
@@ -147,7 +92,7 @@ for count, joints in ((8, 17), (64, 17), (256, 17), (64, 133)):
     kept = int(got["num"][0])
     same = sorted(got["keep"][:kept].tolist()) == np.flatnonzero(mask.cpu().numpy()).tolist()
     reps = args.reps if count < 256 else max(2, args.reps // 4)
-    s = timed({"device": device_call, "refresh": refresh_only, "host": host_call}, args.rounds, reps)
+    s = costlib.timed({"device": device_call, "refresh": refresh_only, "host": host_call}, args.rounds, reps)
     med = {k: statistics.median(v) for k, v in s.items()}
     say("    %3d people, J = %3d (%d kept; the host path keeps %s)" % (count, joints, kept, "the same people" if same else "OTHER people"))
     say("        device call              %s" % fmt(s["device"]))
@@ -215,26 +160,7 @@ say("    device / host = %.4f; images on which both keep the same people: %d of 
 net.close()
 
 say()
-if not args.ab_root:
-    say("(c) predict_frame, this tree against the parent commit: NOT MEASURED (no --ab-root)")
-else:
-    sides = {"parent": os.path.abspath(args.ab_root), "this tree": ROOT}
-    meds = {k: [] for k in sides}
-    for _ in range(args.ab_pairs):
-        for k, root in sides.items():    # fresh children, alternately
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-only", "--root", root, "--rounds", str(args.rounds),
-                                  "--reps", str(args.reps)], capture_output=True, text=True, timeout=300, check=True).stdout
-            meds[k].append(json.loads(out.strip().splitlines()[-1])["predict"])
-    say("(c) predict_frame, 8 people of a 1080p frame, HRNet-W32 256x192 bf16: this tree against the parent commit, %d fresh processes per"
-        % args.ab_pairs)
-    say("    side, alternately, same box")
-    for k in sides:
-        say("        %-10s medians %s ms -> %.4f ms" % (k, ", ".join("%.4f" % v for v in meds[k]), statistics.median(meds[k])))
-    spread = max(max(meds[k]) - min(meds[k]) for k in sides)
-    diff = statistics.median(meds["this tree"]) - statistics.median(meds["parent"])
-    say("        difference %+.4f ms; spread of the processes' medians (the wider side) %.4f ms -> %s"
-        % (diff, spread, "unchanged" if abs(diff) <= spread else ("SLOWER" if diff > 0 else "faster") + " beyond the spread"))
+runs = costlib.ab(report, "(c)", ["predict"], args.ab_root, args.ab_pairs, args.rounds, args.reps)
 say()
 say("Not claimed: how many duplicate tracks a trained network produces -- no trained weights and no video exist where this was measured.")
-with open(os.path.join(args.out, "pose_nms.txt"), "w") as f:
-    f.write("\n".join(lines) + "\n")
+sys.exit(runs is None)

@@ -7,6 +7,8 @@ import argparse, importlib, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
+import costlib
+
 pkg = importlib.import_module("simple-hrnet_amd")
 ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=9)
@@ -16,21 +18,8 @@ c, h, w, n = 48, 384, 288, 256
 crops = torch.randn((n, 3, h, w), generator=torch.Generator(device="cuda").manual_seed(1234), device="cuda")
 boxes = torch.from_numpy(pkg.synth_boxes(n)).cuda()
 net = pkg.NativeHRNet(c, 17, (h, w), "bf16", max_batch=n, device=0).load_state_dict(pkg.synth_state_dict(c, 17, 0))
-modes = [None, "quarter", "dark"]
-for mode in modes:                   # warm-up: block maps, the scratch heat-map buffer, clocks
-    for _ in range(3):
-        net.predict_crops(crops, boxes, refine=mode)
-torch.cuda.synchronize()
-samples = {str(m): [] for m in modes}
-for r in range(args.rounds):
-    for mode in modes[r % 3:] + modes[:r % 3]:
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(args.reps):
-            net.predict_crops(crops, boxes, refine=mode)
-        b.record()
-        b.synchronize()
-        samples[str(mode)].append(a.elapsed_time(b) / args.reps)
+samples = costlib.timed({str(mode): (lambda mode=mode: net.predict_crops(crops, boxes, refine=mode)) for mode in (None, "quarter", "dark")},
+                        args.rounds, args.reps)   # (the warm-up: block maps, the scratch heat-map buffer, clocks)
 net.close()
 med = {m: statistics.median(v) for m, v in samples.items()}
 print(json.dumps({"shape": "W48 384x288 batch 256 bf16", "ms_per_pass": {m: round(v, 4) for m, v in med.items()},

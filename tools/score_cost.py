@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 pkg = importlib.import_module("simple-hrnet_amd")
+import costlib
 import score_ref as R   # the numpy restatement: the host-side target builder of yardstick 2
 
 ap = argparse.ArgumentParser()
@@ -77,21 +78,8 @@ for k, tag in ((many, "256"), (few, "16")):
     cands["score_analytic_" + tag] = (k, 1, lambda k=k: net.score_heatmaps(nxt()[:k], joints=joints[:k], visibility=vis[:k], sigma=sigma, topk=8))
     cands["score_maps_" + tag] = (k, 2, lambda k=k: net.score_heatmaps(nxt()[:k], targets=targets[:k], target_weight=tw[:k], topk=8))
     cands["torch_ops_resident_targets_" + tag] = (k, 2, lambda k=k: torch_score(nxt()[:k], targets[:k], tw_dev[:k]))
-for _, _, fn in cands.values():        # warm-up: staging ring, the table, the allocator's blocks, clocks
-    for _ in range(3):
-        fn()
-torch.cuda.synchronize()
 names = list(cands)
-samples = {k: [] for k in names}
-for r in range(args.rounds):
-    for k in names[r % len(names):] + names[:r % len(names)]:
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(args.reps):
-            cands[k][2]()
-        b.record()
-        b.synchronize()
-        samples[k].append(a.elapsed_time(b) / args.reps)
+samples = costlib.timed({k: fn for k, (_, _, fn) in cands.items()}, args.rounds, args.reps)   # (warm-up: staging ring, the table, blocks, clocks)
 med = {k: statistics.median(v) for k, v in samples.items()}
 floor_ms = {k: cands[k][0] * cands[k][1] * J * h * w * 4 / 6.15e12 * 1e3 for k in names if k.startswith("score")}
 host = {}

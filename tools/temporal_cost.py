@@ -7,87 +7,27 @@ is reported as seen.
       moving its bytes once at 6.15 TB/s (12 read + 24 + 4 gathered + 12 + 12 + 24 + 4 written per joint, 4 per person), and a bare
       kernel-sized launch for scale (torch's copy of the same joints).
   (b) --ab-root DIR: predict_frame (8 people, HRNet-W32 256x192 bf16) in THIS tree against the checkout at DIR (the parent commit,
-      built), each in fresh child processes run alternately on the same box; a difference inside the spread of the children's
-      medians is "unchanged".  Without --ab-root: NOT MEASURED.
+      built): costlib.ab, the protocol of tools/README.md.  Without --ab-root: NOT MEASURED.
   HIP events around back-to-back calls, host side included, interleaved (round r runs the candidates in a rotated order), medians
-  with the spread of the samples beside them; every child process under a time limit.
+  with the spread of the samples beside them.
 
-usage: python tools/temporal_cost.py --out DIR [--rounds R] [--reps K] [--ab-root DIR]
-       python tools/temporal_cost.py --child-only [--root DIR]     (the child of (b): one JSON line)"""
-import argparse
+usage: python tools/temporal_cost.py --out DIR [--rounds R] [--reps K] [--ab-root DIR]"""
 import importlib
-import json
-import os
 import statistics
-import subprocess
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-ap = argparse.ArgumentParser()
-ap.add_argument("--out", help="directory temporal_filter.txt is written to")
-ap.add_argument("--rounds", type=int, default=9)
-ap.add_argument("--reps", type=int, default=50, help="calls per timed sample")
-ap.add_argument("--ab-root", help="checkout of the parent commit, built: predict_frame there against here")
-ap.add_argument("--ab-pairs", type=int, default=3, help="child processes per side of the A/B")
-ap.add_argument("--child-only", action="store_true", help="time predict_frame of (b) alone and print one JSON line")
-ap.add_argument("--root", default=ROOT, help="with --child-only: the checkout whose package is timed")
-args = ap.parse_args()
-if not args.child_only and not args.out:
-    ap.error("--out is needed")
-sys.path.insert(0, os.path.abspath(args.root) if args.child_only else ROOT)
+import costlib
+from costlib import timed
+
+args = costlib.parser(__doc__, "temporal_filter.txt", rounds=9, reps=50, ab="predict_frame").parse_args()
+sys.path.insert(0, costlib.ROOT)
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
 
 HBM = 6.15e12   # bytes per second: the floor printed beside the timings
-
-
-def timed(cands, rounds, reps):
-    """HIP-event ms per call of every candidate: `rounds` samples of `reps` calls each, interleaved in a rotated order"""
-    for fn in cands.values():
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    names = list(cands)
-    samples = {k: [] for k in names}
-    for r in range(rounds):
-        for k in names[r % len(names):] + names[:r % len(names)]:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                cands[k]()
-            b.record()
-            b.synchronize()
-            samples[k].append(a.elapsed_time(b) / reps)
-    return samples
-
-
 pkg = importlib.import_module("simple-hrnet_amd")
-
-if args.child_only:
-    hf, wf = 1080, 1920
-    net = pkg.NativeHRNet(32, 17, (256, 192), "bf16", max_batch=8, device=0).load_state_dict(pkg.synth_state_dict(32, 17, 0))
-    fdev = torch.from_numpy(np.random.default_rng(6).integers(0, 256, (hf, wf, 3), dtype=np.uint8)).cuda()
-    rng = np.random.default_rng(1)
-    x1, y1 = rng.uniform(0, wf - 400, 8), rng.uniform(0, hf - 700, 8)
-    boxes = np.stack([x1, y1, x1 + rng.uniform(150, 400, 8), y1 + rng.uniform(300, 700, 8)], 1).astype(np.float32)
-    s = timed({"predict": lambda: net.predict_frame(fdev, boxes)}, args.rounds, max(args.reps // 2, 2))
-    net.close()
-    print(json.dumps({k: statistics.median(v) for k, v in s.items()}))
-    sys.exit(0)
-
-os.makedirs(args.out, exist_ok=True)
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
-
-
-def fmt(s):
-    return "%9.4f ms  (min %.4f .. max %.4f)" % (statistics.median(s), min(s), max(s))
-
+report = costlib.Report(args.out, "temporal_filter.txt", "%9.4f ms  (min %.4f .. max %.4f)")
+say, fmt = report.say, report.fmt
 
 say("joints over time -- tools/temporal_cost.py; %d samples of %d calls per candidate, interleaved, HIP events, host side included, medians"
     % (args.rounds, args.reps))
@@ -142,26 +82,7 @@ say("    the device call %s" % ("won at every size" if not lost else "LOST at " 
 net.close()
 
 say()
-if not args.ab_root:
-    say("(b) predict_frame, this tree against the parent commit: NOT MEASURED (no --ab-root)")
-else:
-    sides = {"parent": os.path.abspath(args.ab_root), "this tree": ROOT}
-    meds = {k: [] for k in sides}
-    for _ in range(args.ab_pairs):
-        for k, root in sides.items():    # fresh children, alternately
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-only", "--root", root, "--rounds", str(args.rounds),
-                                  "--reps", str(args.reps)], capture_output=True, text=True, timeout=300, check=True).stdout
-            meds[k].append(json.loads(out.strip().splitlines()[-1])["predict"])
-    say("(b) predict_frame, 8 people of a 1080p frame, HRNet-W32 256x192 bf16: this tree against the parent commit, %d fresh processes per"
-        % args.ab_pairs)
-    say("    side, alternately, same box")
-    for k in sides:
-        say("        %-10s medians %s ms -> %.4f ms" % (k, ", ".join("%.4f" % v for v in meds[k]), statistics.median(meds[k])))
-    spread = max(max(meds[k]) - min(meds[k]) for k in sides)
-    diff = statistics.median(meds["this tree"]) - statistics.median(meds["parent"])
-    say("        difference %+.4f ms; spread of the processes' medians (the wider side) %.4f ms -> %s"
-        % (diff, spread, "unchanged" if abs(diff) <= spread else ("SLOWER" if diff > 0 else "faster") + " beyond the spread"))
+runs = costlib.ab(report, "(b)", ["predict"], args.ab_root, args.ab_pairs, args.rounds, max(args.reps // 2, 2))   # (a pass is no small call)
 say()
 say("Not claimed: that filtered joints or predicted boxes improve accuracy or tracking on a trained network (no weights, no video here).")
-with open(os.path.join(args.out, "temporal_filter.txt"), "w") as f:
-    f.write("\n".join(lines) + "\n")
+sys.exit(runs is None)

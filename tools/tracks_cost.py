@@ -10,101 +10,24 @@ table lost (the matrix is then twice as wide) are results to record.
       HIP events around back-to-back calls, host side included, interleaved (round r runs the candidates in a rotated order),
       medians.  Every call starts from the same table and the frame's own boxes and joints (refresh copies, timed on their own).
   (b) --ab-root DIR: predict_frame (8 people, HRNet-W32 256x192 bf16) and bench.py in THIS tree against the checkout at DIR (the
-      parent commit, built), each in fresh child processes run alternately on the same box, three per side; a difference inside
-      the spread of the children's results is "unchanged".  Without --ab-root: NOT MEASURED.
+      parent commit, built): costlib.ab, the protocol of tools/README.md.  Without --ab-root: NOT MEASURED.
 
-usage: python tools/tracks_cost.py --out DIR [--rounds R] [--reps K] [--ab-root DIR]
-       python tools/tracks_cost.py --child-only [--root DIR]     (the child of (b): one JSON line)"""
-import argparse
+usage: python tools/tracks_cost.py --out DIR [--rounds R] [--reps K] [--ab-root DIR]"""
 import importlib
-import json
-import os
 import statistics
-import subprocess
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-ap = argparse.ArgumentParser()
-ap.add_argument("--out", help="directory track_table.txt is written to")
-ap.add_argument("--rounds", type=int, default=9)
-ap.add_argument("--reps", type=int, default=20, help="calls per timed sample")
-ap.add_argument("--ab-root", help="checkout of the parent commit, built: predict_frame and bench.py there against here")
-ap.add_argument("--ab-pairs", type=int, default=3, help="child processes per side of the A/B")
-ap.add_argument("--child-only", action="store_true", help="time predict_frame of (b) alone and print one JSON line")
-ap.add_argument("--root", default=ROOT, help="with --child-only: the checkout whose package is timed")
-args = ap.parse_args()
-if not args.child_only and not args.out:
-    ap.error("--out is needed")
-sys.path.insert(0, os.path.abspath(args.root) if args.child_only else ROOT)
+import costlib
+from costlib import people_of, timed
+
+args = costlib.parser(__doc__, "track_table.txt", rounds=9, reps=20, ab="predict_frame and bench.py").parse_args()
+sys.path.insert(0, costlib.ROOT)
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
 
-hf, wf = 1080, 1920
-
-
-def timed(cands, rounds, reps):
-    """HIP-event ms per call of every candidate: `rounds` samples of `reps` calls each, interleaved in a rotated order"""
-    for fn in cands.values():
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    names = list(cands)
-    samples = {k: [] for k in names}
-    for r in range(rounds):
-        for k in names[r % len(names):] + names[:r % len(names)]:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                cands[k]()
-            b.record()
-            b.synchronize()
-            samples[k].append(a.elapsed_time(b) / reps)
-    return samples
-
-
-def people_of(count, joints, seed, jitter=0.0, base=None):
-    """`count` people spread over the frame: ((count, joints, 3) (y, x, confidence), (count, 4) int32 boxes)"""
-    rng = np.random.default_rng(seed)
-    if base is None:
-        pts = np.empty((count, joints, 3), np.float32)
-        for i in range(count):
-            bh = rng.uniform(300, 900)
-            bw = bh * rng.uniform(0.3, 0.6)
-            x1, y1 = rng.uniform(0, wf - bw), rng.uniform(0, hf - bh)
-            pts[i, :, 0] = rng.uniform(y1, y1 + bh, joints)
-            pts[i, :, 1] = rng.uniform(x1, x1 + bw, joints)
-        pts[..., 2] = 0.9
-    else:
-        pts = base.copy()
-        pts[..., :2] += rng.normal(0, jitter, pts[..., :2].shape).astype(np.float32)
-    boxes = np.stack([pts[..., 1].min(1), pts[..., 0].min(1), pts[..., 1].max(1), pts[..., 0].max(1)], 1)
-    return pts, np.round(boxes).astype(np.int32)
-
-
 pkg = importlib.import_module("simple-hrnet_amd")
-
-if args.child_only:
-    net = pkg.NativeHRNet(32, 17, (256, 192), "bf16", max_batch=8, device=0).load_state_dict(pkg.synth_state_dict(32, 17, 0))
-    fdev = torch.from_numpy(np.random.default_rng(6).integers(0, 256, (hf, wf, 3), dtype=np.uint8)).cuda()
-    boxes = people_of(8, 17, 1)[1]
-    s = timed({"predict": lambda: net.predict_frame(fdev, boxes.astype(np.float32))}, args.rounds, args.reps)
-    net.close()
-    print(json.dumps({k: statistics.median(v) for k, v in s.items()}))
-    sys.exit(0)
-
-os.makedirs(args.out, exist_ok=True)
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
-
-
-def fmt(s):
-    return "%8.4f ms  (min %.4f .. max %.4f)" % (statistics.median(s), min(s), max(s))
-
+report = costlib.Report(args.out, "track_table.txt")
+say, fmt = report.say, report.fmt
 
 say("person track table -- tools/tracks_cost.py; %d samples of %d calls per candidate, interleaved, HIP events, host side included, medians"
     % (args.rounds, args.reps))
@@ -187,33 +110,7 @@ for count, joints in ((8, 17), (64, 17), (256, 17), (64, 133)):
 net.close()
 
 say()
-if not args.ab_root:
-    say("(b) predict_frame and bench.py, this tree against the parent commit: NOT MEASURED (no --ab-root)")
-else:
-    sides = {"parent": os.path.abspath(args.ab_root), "this tree": ROOT}
-    meds = {k: {"predict": [], "bench": []} for k in sides}
-    bench_key = None
-    for _ in range(args.ab_pairs):
-        for k, root in sides.items():    # fresh children, alternately
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-only", "--root", root, "--rounds", str(args.rounds),
-                                  "--reps", str(args.reps)], capture_output=True, text=True, timeout=300, check=True).stdout
-            meds[k]["predict"].append(json.loads(out.strip().splitlines()[-1])["predict"])
-            out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5"], cwd=root,
-                                 capture_output=True, text=True, timeout=600, check=True).stdout
-            res = json.loads([ln for ln in out.strip().splitlines() if ln.startswith("{")][-1])
-            bench_key = bench_key or next(key for key in ("value", "images_per_sec", "throughput", "crops_per_sec") if key in res)
-            meds[k]["bench"].append(float(res[bench_key]))
-    say("(b) this tree against the parent commit, %d fresh processes per side, alternately, same box" % args.ab_pairs)
-    for what, title, unit in (("predict", "predict_frame, 8 people of a 1080p frame, HRNet-W32 256x192 bf16", "ms"),
-                              ("bench", "bench.py --gpus 1 --steps 30 --warmup 5, its '%s'" % bench_key, "")):
-        say("    %s" % title)
-        for k in sides:
-            say("        %-10s %s %s -> median %.4f" % (k, ", ".join("%.4f" % v for v in meds[k][what]), unit, statistics.median(meds[k][what])))
-        spread = max(max(meds[k][what]) - min(meds[k][what]) for k in sides)
-        diff = statistics.median(meds["this tree"][what]) - statistics.median(meds["parent"][what])
-        say("        difference %+.4f; spread of the processes' results (the wider side) %.4f -> %s"
-            % (diff, spread, "unchanged" if abs(diff) <= spread else "DIFFERENT beyond the spread"))
+runs = costlib.ab(report, "(b)", ["predict"], args.ab_root, args.ab_pairs, args.rounds, args.reps, bench=True)
 say()
 say("Not claimed: how well these ids hold on a trained network -- no trained weights and no video exist where this was measured.")
-with open(os.path.join(args.out, "track_table.txt"), "w") as f:
-    f.write("\n".join(lines) + "\n")
+sys.exit(runs is None)

@@ -12,20 +12,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
+import costlib
+
 pkg = importlib.import_module("simple-hrnet_amd")
 ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=9)
 ap.add_argument("--reps", type=int, default=20, help="calls per timed sample")
 args = ap.parse_args()
 h, w, hf, wf, people, many = 384, 288, 1080, 1920, 16, 256
-rng = np.random.default_rng(5)                      # bench.py: prepath_measure
-frame = rng.integers(0, 256, (hf, wf, 3), dtype=np.uint8)
-dets = np.zeros((many, 4), np.float32)
-for i in range(many):
-    bh = rng.integers(300, 900)
-    bw = int(bh * rng.uniform(0.3, 0.6))
-    x1, y1 = rng.uniform(0, wf - bw), rng.uniform(0, hf - bh)
-    dets[i] = (x1, y1, x1 + bw, y1 + bh)
+frame = np.random.default_rng(5).integers(0, 256, (hf, wf, 3), dtype=np.uint8)   # bench.py: prepath_measure
+dets = costlib.prepath_boxes(many)
 cs = [pkg.postproc.box_to_center_scale((d[0], d[1], d[2] - d[0], d[3] - d[1]), w / h) for d in dets]
 centers, scales = np.stack([c for c, _ in cs]), np.stack([s for _, s in cs])
 mats = np.stack([pkg.postproc.affine_matrix(centers[i], scales[i], 200, 0, (w, h)) for i in range(many)])
@@ -37,21 +33,8 @@ cands = {
     "warp_crops_16_from_centers_scales": (people, lambda: net.warp_crops(fdev, centers[:people], scales[:people])),
     "warp_crops_256": (many, lambda: net.warp_crops(fdev, matrices=mats)),
 }
-for _, fn in cands.values():         # warm-up: staging ring, scratch, the allocator's blocks, clocks
-    for _ in range(5):
-        fn()
-torch.cuda.synchronize()
 names = list(cands)
-samples = {k: [] for k in names}
-for r in range(args.rounds):
-    for k in names[r % len(names):] + names[:r % len(names)]:
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(args.reps):
-            cands[k][1]()
-        b.record()
-        b.synchronize()
-        samples[k].append(a.elapsed_time(b) / args.reps)
+samples = costlib.timed({k: fn for k, (_, fn) in cands.items()}, args.rounds, args.reps, warmup=5)   # (staging ring, scratch, blocks, clocks)
 net.close()
 med = {k: statistics.median(v) for k, v in samples.items()}
 floor_ms = {k: cands[k][0] * 3 * h * w * 4 / 6.15e12 * 1e3 for k in names}   # middle of the measured 6.0-6.3 TB/s store rate

@@ -14,19 +14,17 @@ Device events around windows of at least a second each (the calls per window are
 the candidates of a block take turns, round by round, in a rotated order; medians of the windows.
 
 usage: python tools/yuv10_cost.py --out DIR [--parent-lib PATH] [--rounds R] [--window SECONDS]"""
-import argparse
 import ctypes
 import importlib
 import os
 import statistics
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-ap = argparse.ArgumentParser()
-ap.add_argument("--out", required=True, help="directory yuv10.txt is written to")
+import costlib
+from costlib import ROOT, window
+
+ap = costlib.parser(__doc__, "yuv10.txt", rounds=5)
 ap.add_argument("--parent-lib", help="libhrnet_mi355.so built from the parent commit: (c) is NOT MEASURED without it")
-ap.add_argument("--rounds", type=int, default=5, help="windows per candidate")
 ap.add_argument("--window", type=float, default=1.0, help="seconds per window, at least")
 args = ap.parse_args()
 sys.path.insert(0, ROOT)
@@ -41,13 +39,6 @@ L = importlib.import_module("simple-hrnet_amd._lib")
 H, W, HF, WF, PEOPLE = 256, 192, 1080, 1920, 8
 HBM_PEAK, HBM_COPY = 8.0e12, 6.3e12      # MI355X: spec, and what a float4 copy reaches
 FORMATS = ("nv12", "nv21", "p010", "i010")
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
-
 
 def engine(lib_path=None):
     """an engine on this tree's library, or on the library at `lib_path` (bound through the package's own symbol table)"""
@@ -98,36 +89,22 @@ def to_bgr_call(net, frame, out):
     return call
 
 
-def window(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps            # ms per call
-
-
-def timed(cands):
+def calibrated(cands):
     """ms per call of every candidate: args.rounds windows of at least args.window seconds each, interleaved in a rotated order"""
     reps = {}
     for k, fn in cands.items():                # warm-up (staging ring, scratch, clocks), then the calls a window needs
         window(fn, 200)
         per_call = window(fn, 2000)
         reps[k] = max(2000, int(args.window * 1e3 / per_call) + 1)
-    names = list(cands)
-    samples = {k: [] for k in names}
+    samples = {k: [] for k in cands}
     for r in range(args.rounds):
-        for k in names[r % len(names):] + names[:r % len(names)]:
+        for k in costlib.rotated(cands, r):
             samples[k].append(window(cands[k], reps[k]))
     return samples, reps
 
 
-def fmt_ms(s):
-    return "%9.3f us  (min %.3f .. max %.3f)" % (1e3 * statistics.median(s), 1e3 * min(s), 1e3 * max(s))
-
-
-os.makedirs(args.out, exist_ok=True)
+report = costlib.Report(args.out, "yuv10.txt", "%9.3f us  (min %.3f .. max %.3f)", scale=1e3)
+say, fmt_ms = report.say, report.fmt
 say("NV21 / P010 / I010 input -- tools/yuv10_cost.py; %d windows of >= %.1f s per candidate, interleaved, device events, medians"
     % (args.rounds, args.window))
 say("device: %s" % torch.cuda.get_device_name(0))
@@ -141,7 +118,7 @@ want = {f: net.yuv_to_bgr(frames[f]) for f in FORMATS}
 tiny, tiny_out = frame_of("nv12", 2, 2), torch.empty((2, 2, 3), dtype=torch.uint8, device="cuda:0")
 cands = {f: to_bgr_call(net, frames[f], out) for f in FORMATS}
 cands["floor"] = to_bgr_call(net, tiny, tiny_out)
-s, reps = timed(cands)
+s, reps = calibrated(cands)
 say()
 say("(a) hrn_yuv_to_bgr of a resident %dx%d frame, BT.709 limited, one preallocated output" % (WF, HF))
 say("    a 2x2 frame (the call's own floor: ctypes + launch)      %s" % fmt_ms(s["floor"]))
@@ -159,7 +136,7 @@ say("    against nv12: " + ", ".join("%s x %.2f" % (f, statistics.median(s[f]) /
 say()
 crops = {f: net.preprocess_frame(frames[f], dets)[0] for f in FORMATS}
 same = all(torch.equal(crops[f], net.preprocess_frame(want[f], dets)[0]) for f in FORMATS)
-s, reps = timed({f: (lambda f=f: net.preprocess_frame(frames[f], dets)) for f in FORMATS})
+s, reps = calibrated({f: (lambda f=f: net.preprocess_frame(frames[f], dets)) for f in FORMATS})
 say("(b) preprocess_frame, %d people of that frame, %dx%d crops, through the Python entry (crops equal the BGR path's bit for bit: %s)"
     % (PEOPLE, H, W, "yes" if same else "NO"))
 for f in FORMATS:
@@ -182,7 +159,7 @@ else:
     verdicts = []
     for what, cands in (("hrn_yuv_to_bgr, 1080p NV12", {k: to_bgr_call(e, frames["nv12"], outs[k]) for k, e in arms.items()}),
                         ("preprocess_frame, %d people, NV12" % PEOPLE, {k: (lambda e=e: e.preprocess_frame(frames["nv12"], dets)) for k, e in arms.items()})):
-        s, reps = timed(cands)
+        s, reps = calibrated(cands)
         say("    %s" % what)
         for k in arms:
             say("      %-10s %s   [%d calls per window]" % (k, fmt_ms(s[k]), reps[k]))
@@ -193,5 +170,3 @@ else:
         say("      this - parent = %+.3f us; spread (this against this again) = %.3f us -> %s" % (diff, spread, verdict))
     parent.close(), again.close()
 net.close()
-with open(os.path.join(args.out, "yuv10.txt"), "w") as f:
-    f.write("\n".join(lines) + "\n")

@@ -11,102 +11,35 @@ input is faster or slower than BGR input per call is a result to record.
   (d) the host alternative: the numpy restatement (tests/yuv_ref.py) of one 1080p NV12 -> BGR conversion, single thread of
       numpy -- NOT cv2, which is not installed where this runs.
   (e) --ab-root DIR: BGR preprocess_frame of (a) in THIS tree against the same call in the checkout at DIR (the parent commit,
-      built), each in fresh child processes run alternately on the same box; a difference inside the spread of the children's
-      medians is "unchanged".  Without --ab-root the pair is reported as NOT MEASURED.
+      built): costlib.ab, the protocol of tools/README.md.  Without --ab-root the pair is reported as NOT MEASURED.
 
-usage: python tools/yuv_cost.py --out DIR [--rounds R] [--reps K] [--ab-root DIR] [--skip-clip]
-       python tools/yuv_cost.py --bgr-only [--root DIR]     (the child of (e): one JSON line)"""
-import argparse
+usage: python tools/yuv_cost.py --out DIR [--rounds R] [--reps K] [--ab-root DIR] [--skip-clip]"""
 import importlib
-import json
 import os
 import statistics
-import subprocess
 import sys
 import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-ap = argparse.ArgumentParser()
-ap.add_argument("--out", help="directory yuv_input.txt is written to")
-ap.add_argument("--rounds", type=int, default=9)
-ap.add_argument("--reps", type=int, default=20, help="calls per timed sample")
-ap.add_argument("--ab-root", help="checkout of the parent commit, built: BGR preprocess_frame there against here")
-ap.add_argument("--ab-pairs", type=int, default=3, help="child processes per side of the A/B")
+import costlib
+from costlib import ROOT
+
+ap = costlib.parser(__doc__, "yuv_input.txt", rounds=9, reps=20, ab="BGR preprocess_frame")
 ap.add_argument("--skip-clip", action="store_true", help="leave (c) out (reported as NOT MEASURED)")
-ap.add_argument("--bgr-only", action="store_true", help="time BGR preprocess_frame of (a) alone and print one JSON line")
-ap.add_argument("--root", default=ROOT, help="with --bgr-only: the checkout whose package is timed")
 args = ap.parse_args()
-if not args.bgr_only and not args.out:
-    ap.error("--out is needed")
-sys.path.insert(0, os.path.abspath(args.root) if args.bgr_only else ROOT)
+sys.path[:0] = [os.path.join(ROOT, "tests"), ROOT]
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
 
-h, w, hf, wf, people = 384, 288, 1080, 1920, 16
-FLOOR_RATE = 6.15e12
-
-
-def prepath_boxes():
-    rng = np.random.default_rng(5)                      # bench.py: prepath_measure
-    rng.integers(0, 256, (hf, wf, 3), dtype=np.uint8)   # (its frame: drawn first there, so the boxes are the same)
-    dets = np.zeros((people, 4), np.float32)
-    for i in range(people):
-        bh = rng.integers(300, 900)
-        bw = int(bh * rng.uniform(0.3, 0.6))
-        x1, y1 = rng.uniform(0, wf - bw), rng.uniform(0, hf - bh)
-        dets[i] = (x1, y1, x1 + bw, y1 + bh)
-    return dets
-
-
-def timed(cands, rounds, reps):
-    """HIP-event ms per call of every candidate: `rounds` samples of `reps` calls each, interleaved in a rotated order"""
-    for fn in cands.values():            # warm-up: staging ring, scratch, the allocator's blocks, clocks
-        for _ in range(5):
-            fn()
-    torch.cuda.synchronize()
-    names = list(cands)
-    samples = {k: [] for k in names}
-    for r in range(rounds):
-        for k in names[r % len(names):] + names[:r % len(names)]:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                cands[k]()
-            b.record()
-            b.synchronize()
-            samples[k].append(a.elapsed_time(b) / reps)
-    return samples
-
-
-pkg = importlib.import_module("simple-hrnet_amd")
-dets16 = prepath_boxes()
-
-if args.bgr_only:
-    net = pkg.NativeHRNet(32, 17, (h, w), "bf16", max_batch=32, device=0)   # the pre-path needs no weights
-    fdev = torch.from_numpy(np.random.default_rng(6).integers(0, 256, (hf, wf, 3), dtype=np.uint8)).cuda()
-    s = timed({"bgr": lambda: net.preprocess_frame(fdev, dets16)}, args.rounds, args.reps)["bgr"]
-    net.close()
-    print(json.dumps({"median_ms": statistics.median(s), "min_ms": min(s), "max_ms": max(s)}))
-    sys.exit(0)
-
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import yuv_ref       # noqa: E402
 
 import bench         # noqa: E402  (make_clip)
 
-os.makedirs(args.out, exist_ok=True)
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
-
-
-def fmt(s):
-    return "%8.4f ms  (min %.4f .. max %.4f)" % (statistics.median(s), min(s), max(s))
-
+h, w, hf, wf, people = 384, 288, 1080, 1920, 16
+FLOOR_RATE = 6.15e12
+pkg = importlib.import_module("simple-hrnet_amd")
+dets16 = costlib.prepath_boxes(people)
+report = costlib.Report(args.out, "yuv_input.txt")
+say, fmt = report.say, report.fmt
 
 say("YUV (NV12 / I420) input -- tools/yuv_cost.py; %d samples of %d calls per candidate, interleaved, HIP events, medians" % (args.rounds, args.reps))
 say("device: %s" % torch.cuda.get_device_name(0))
@@ -116,8 +49,8 @@ yuv_dev = pkg.YuvFrame(nv12_host, hf, wf, "nv12").to("cuda:0")
 net = pkg.NativeHRNet(32, 17, (h, w), "bf16", max_batch=32, device=0)
 bgr_dev = net.yuv_to_bgr(yuv_dev)                      # the same picture on both sides
 same = torch.equal(net.preprocess_frame(yuv_dev, dets16)[0], net.preprocess_frame(bgr_dev, dets16)[0])
-s = timed({"nv12": lambda: net.preprocess_frame(yuv_dev, dets16), "bgr": lambda: net.preprocess_frame(bgr_dev, dets16),
-           "to_bgr": lambda: net.yuv_to_bgr(yuv_dev)}, args.rounds, args.reps)
+s = costlib.timed({"nv12": lambda: net.preprocess_frame(yuv_dev, dets16), "bgr": lambda: net.preprocess_frame(bgr_dev, dets16),
+                   "to_bgr": lambda: net.yuv_to_bgr(yuv_dev)}, args.rounds, args.reps, warmup=5)
 net.close()
 say()
 say("(a) preprocess_frame, %d people of a %dx%d frame resident in HBM, %dx%d crops (crops equal bit for bit: %s)"
@@ -184,23 +117,4 @@ say("(d) the host alternative, NUMPY (tests/yuv_ref.py, not cv2): one %dx%d NV12
 say("    %8.2f ms  (min %.2f .. max %.2f of 5)" % (statistics.median(t), min(t), max(t)))
 
 say()
-if not args.ab_root:
-    say("(e) BGR preprocess_frame of (a), this tree against the parent commit: NOT MEASURED (no --ab-root)")
-else:
-    sides = {"parent": os.path.abspath(args.ab_root), "this tree": ROOT}
-    meds = {k: [] for k in sides}
-    for _ in range(args.ab_pairs):
-        for k, root in sides.items():    # fresh children, alternately
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--bgr-only", "--root", root, "--rounds", str(args.rounds),
-                                  "--reps", str(args.reps)],
-                                 capture_output=True, text=True, timeout=300, check=True).stdout
-            meds[k].append(json.loads(out.strip().splitlines()[-1])["median_ms"])
-    say("(e) BGR preprocess_frame of (a): this tree against the parent commit, %d fresh processes per side, alternately, same box" % args.ab_pairs)
-    for k in sides:
-        say("    %-10s medians %s ms -> %.4f ms" % (k, ", ".join("%.4f" % v for v in meds[k]), statistics.median(meds[k])))
-    spread = max(max(v) - min(v) for v in meds.values())
-    diff = statistics.median(meds["this tree"]) - statistics.median(meds["parent"])
-    say("    difference %+.4f ms; spread of the processes' medians (the wider side) %.4f ms -> %s"
-        % (diff, spread, "unchanged" if abs(diff) <= spread else ("SLOWER" if diff > 0 else "faster") + " beyond the spread"))
-with open(os.path.join(args.out, "yuv_input.txt"), "w") as f:
-    f.write("\n".join(lines) + "\n")
+sys.exit(costlib.ab(report, "(e)", ["prepath_bgr"], args.ab_root, args.ab_pairs, args.rounds, args.reps) is None)
