@@ -615,7 +615,7 @@ int hrn_keypoint_eval_constants(double *iou_thrs /* 10 */, double *rec_thrs /* 1
  * the winner's Y; the chroma sample of a 2x2 block is written iff at least one of its four pixels is covered, and takes U and V of
  * the highest-numbered primitive that covers any of the four.  HRN_PIX_NV21, _P010 and _I010 canvases are refused as an unknown
  * format, here and in hrn_draw_labels_dev (colours are 8-bit triples: a 10-bit overlay wants a definition of its own); a pipeline
- * of such frames draws on the BGR frame hrn_yuv_to_bgr gives it.
+ * of such frames draws on the BGR frame hrn_yuv_to_bgr gives it, and hrn_bgr_to_yuv_frames carries the drawn frame back to its layout.
  *
  *   canvases_host     nframes entries on the HOST; hrn_canvas has hrn_yuv_frame's fields with writable planes.  HRN_PIX_BGR: y = the
  *                     (height, width, 3) uint8 pixels, pitch_y = bytes between rows >= 3 * width (a view into a larger buffer
@@ -942,6 +942,65 @@ const char *hrn_rotate_people_last_error(void);
 int hrn_rotate_people_dev(hrn_handle h, int n, int J, const int32_t *frame_hw_host, int per_person_hw,
                           const int32_t *codes_host, int per_person_code, const float *pts_dev, const int32_t *boxes_dev,
                           float *pts_out_dev, int32_t *boxes_out_dev, void *stream);
+
+/* ---- BGR frames back to 4:2:0 YCbCr on the GPU: NV12 / NV21, I420 and 10-bit P010 / I010 -- the annotated frame in the encoder's layout ----
+ * The inverse direction of hrn_yuv_to_bgr, for a pipeline that draws on BGR (every pipeline whose frames start as BGR, and the
+ * NV21 / P010 / I010 pipelines the overlays refuse): decode -> pose -> draw on BGR -> back to the stream's own layout -> an encoder,
+ * a recorder or `ffmpeg -f rawvideo -pix_fmt nv12|nv21|yuv420p|p010le|yuv420p10le`.  On 8-bit output half the bytes cross PCIe.
+ *
+ * THE TABLE (csrc/yuv_fwd.h, one text for the host entries and the kernel).  hrn_yuv_forward_coefficients writes ten int32:
+ * y0, CYR CYG CYB, CUR CUG CUB, CVR CVG CVB -- the rows (R, G, B) of Y, U and V at scale 2^20, q(x) = floor(x * 2^20 + 0.5) (the
+ * rounding of hrn_yuv_coefficients) of the exact forward coefficients: Kr / Kb = 0.299 / 0.114 (BT.601) or 0.2126 / 0.0722
+ * (BT.709), Kg = 1 - Kr - Kb; limited range sy = 219/255, sc = 224/255, y0 = 16; full range sy = sc = 1, y0 = 0:
+ *   CYR = q(sy Kr)                  CYG = q(sy Kg)                  CYB = q(sy Kb)
+ *   CUR = q(-sc Kr / (2 (1 - Kb)))  CUG = q(-sc Kg / (2 (1 - Kb)))  CUB = -(CUR + CUG)
+ *   CVG = q(-sc Kg / (2 (1 - Kr)))  CVB = q(-sc Kb / (2 (1 - Kr)))  CVR = -(CVG + CVB)
+ * Each chroma row sums to zero: a grey pixel gives exactly 128 / 512.  BT.601 limited follows the same rule; it is NOT OpenCV's
+ * forward table (which is coarser and cannot be consulted where this library is tested): equality with
+ * cv2.cvtColor(COLOR_BGR2YUV_I420) is NOT pinned, as with the other cv2 pins.
+ *
+ * THE PIXEL RULE.  All integers, arithmetic shift, one rounding each; every sum fits int32 (the largest is exactly 2^30).
+ *   8-bit luma, per pixel:        Y = clip8 ((CYR R  + CYG G  + CYB B  + (y0  << 20) + (1 << 19)) >> 20)
+ *   8-bit chroma, per 2x2 block:  U = clip8 ((CUR Rs + CUG Gs + CUB Bs + (128 << 22) + (1 << 21)) >> 22),  V likewise
+ *   10-bit luma:                  Y = clip10((CYR R  + CYG G  + CYB B  + (y0  << 20) + (1 << 17)) >> 18)
+ *   10-bit chroma:                U = clip10((CUR Rs + CUG Gs + CUB Bs + (128 << 22) + (1 << 19)) >> 20),  V likewise
+ * Rs, Gs, Bs are the SUMS over the four pixels of the block (0 .. 1020): the chroma sample is the conversion of the block's mean
+ * (MPEG-1 centre siting) -- a definition of this library, like the table.  The 10-bit samples come from the same 8-bit BGR with
+ * one rounding, not from the 8-bit samples.  P010 stores s << 6 (the low six bits zero), I010 stores s (the high six bits zero),
+ * NV21 is NV12 with the pair written (V, U).  In limited range no clip engages (Y in 16 .. 235, U, V in 16 .. 240; x 4 for 10 bits);
+ * in full range exactly two values meet one: pure blue's U and pure red's V are 256 before the 8-bit clip (128 + 127.5).
+ * PINNED (tests/bgr2yuv_ref.py, tests/test_bgr2yuv_*.py), over all 2^24 colours and the four tables: a block of four equal pixels
+ * converts as one pixel; Y, U, V are within 1 of hrn_yuv_from_bgr's float64 formula; through hrn_yuv_to_bgr's 8-bit form a
+ * uniform block comes back within 2 levels in B and 1 in G and R (limited) or 1 in all three (full); through its 10-bit form
+ * exactly, except B within 1 for BT.601 limited (OpenCV's inverse table is not an exact inverse); |s10 - 4 s8| <= 2.
+ *
+ * hrn_bgr_to_yuv_blocks (no handle, no GPU): the host form -- n 2x2 blocks, (n, 4, 3) uint8 (B, G, R) of the four pixels
+ * row-major, to (n, 6) uint16 sample values Y00 Y01 Y10 Y11 U V (not shifted: 0 .. 255 or 0 .. 1023); depth is 8 or 10.
+ * Both return 7 on an unknown matrix or range (the blocks: also depth, n < 0, null arrays with n > 0).
+ *
+ * hrn_bgr_to_yuv_frames follows hrn_rotate_frames' contract: src_host / dst_host are nframes hrn_canvas entries each, on the
+ * HOST, planes on the device.  src[k] is an HRN_PIX_BGR canvas (pitched views are allowed); dst[k] is any of the five YUV
+ * layouts, of the same size, any pitch that holds its rows; its matrix and range fields are READ here: they choose the table.
+ * Frames of one call may differ in size, format, matrix and range.  ONE launch whatever nframes, no frame-sized scratch,
+ * stream-ordered, no atomics; one block per 256 x 8-pixel tile of a frame, found through a per-call table (one frame: in the
+ * kernel arguments; more: uploaded through the handle's guarded table and pinned ring).  A thread owns 2 rows x 4 pixels: three
+ * dword loads per row, one dword of Y per row (two for 10 bits) and its two chroma samples in one dword (NV12 / NV21; I010: one per
+ * plane; P010: two; I420: one 16-bit store per plane) wherever a plane's base and pitch are multiples of 4, bytes (16-bit words for
+ * 10 bits) otherwise and for the 2-pixel group that ends a row whose width is not a multiple of 4.  Every destination byte that
+ * belongs to a sample has exactly one writer; pitch padding is never written; sources are only read.  Offsets inside a plane are
+ * 32-bit.  nframes == 0 succeeds and launches nothing.
+ * Fails with code 7, names the cause and launches nothing on: nframes < 0; null tables with nframes > 0; a source that is not
+ * BGR; a destination with an unknown format (0, 3, 7, ...), matrix or range; a null plane; a non-positive, odd or over-8192
+ * side; sizes that differ between src[k] and dst[k]; a pitch below the row's bytes; a plane with pitch * rows >= 2^31; an odd
+ * plane address or pitch on a 10-bit destination; a source and a destination, or two destinations, that name the same first
+ * plane (overlapping views are the caller's to avoid); after all these, a plan-only handle.  Everything is judged before the
+ * device is touched.
+ * NOT BUILT: 4:2:2 / 4:4:4 output, dithering, HDR transfer functions, a fused draw + convert; the overlays still refuse NV21,
+ * P010 and I010 canvases. */
+int hrn_yuv_forward_coefficients(int matrix, int range, int32_t out[10]);
+int hrn_bgr_to_yuv_blocks(int matrix, int range, int depth /* 8 | 10 */, const uint8_t *bgr /* (n,4,3): a 2x2 block, row-major */,
+                          int n, uint16_t *out /* (n,6): Y00 Y01 Y10 Y11 U V, sample values */);
+int hrn_bgr_to_yuv_frames(hrn_handle h, const hrn_canvas *src_host, const hrn_canvas *dst_host, int nframes, void *stream);
 
 /* Single-person pre-path on the GPU: replaces, for every frame of a call with multiperson=False,
  *   cv2.resize(image, (W, H), interpolation=self.interpolation); cv2.cvtColor(image, cv2.COLOR_BGR2RGB); self.transform(image)

@@ -28,6 +28,7 @@ SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "c
            "keypoint_eval.hip",  # COCO keypoint AP / AR: OKS matching per image, precision / recall over the set (keypoint_eval_math.h)
            "letterbox.hip",  # the detector link: the letterboxed detector tensor, the detector's boxes back in frame coordinates (letterbox_math.h)
            "rotate.hip",   # frame rotation: cv2.rotate for BGR / NV12 / I420 frames in one launch, people between the orientations (rotate_math.h)
+           "yuv_out.hip",  # BGR frames back to NV12 / NV21 / I420 / P010 / I010 frames in one launch: the encoder's layout (yuv_fwd.h)
            "assoc.hip",    # person ids between two frames: similarity, assignment, ids and smoothing in one launch (assoc_math.h)
            "tracks.hip",   # the person track table: one update per frame keeps ids through occlusions, one launch (tracks_math.h, assoc_assign.h)
            "temporal.hip",  # joints over time: the One-Euro filter and the motion lookahead of every joint in one launch (temporal_math.h)
@@ -301,6 +302,9 @@ SYMBOLS = {
     "hrn_rotate_people": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P]),
     "hrn_rotate_people_last_error": (ctypes.c_char_p, []),
     "hrn_rotate_people_dev": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P, _P]),
+    "hrn_yuv_forward_coefficients": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P]),
+    "hrn_bgr_to_yuv_blocks": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
+    "hrn_bgr_to_yuv_frames": (ctypes.c_int, [_P, ctypes.POINTER(CanvasC), ctypes.POINTER(CanvasC), ctypes.c_int, _P]),
     "hrn_yuv_from_bgr": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
     "hrn_crop_geometry": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
     "hrn_crop_geometry_last_error": (ctypes.c_char_p, []),

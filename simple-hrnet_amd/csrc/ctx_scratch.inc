@@ -86,6 +86,7 @@
     CallScratch det_table;     // hrn_detections_to_frame_dev: the frame records of a call with several frames
     CallScratch rot_table;     // hrn_rotate_frames: the plane records of a call with several frames
     CallScratch rot_people;    // hrn_rotate_people_dev: the frame sizes / codes of a call that has them per person
+    CallScratch yuvout_table;  // hrn_bgr_to_yuv_frames: the frame records of a call with several frames
     CallScratch dnms_buf;      // hrn_detector_nms_dev: the candidates of the scoring launch, then the chunk counts and their scan
     CallScratch tmp_table;     // hrn_filter_poses_dev: every person's segment of the previous people, of a call with several problems
 
@@ -217,7 +218,7 @@
 
     void free_scratch() {
         for (CallScratch *c : {&rs_taps, &pre_tmp, &pre_params, &pre_yuv, &warp_params, &score_joints, &draw_table, &draw_records, &assoc_buf, &tracks_buf,
-                               &nms_table, &eval_buf, &trk_table, &lb_table, &det_table, &rot_table, &rot_people, &dnms_buf, &tmp_table})
+                               &nms_table, &eval_buf, &trk_table, &lb_table, &det_table, &rot_table, &rot_people, &yuvout_table, &dnms_buf, &tmp_table})
             c->release();
         pass.release();
         for (auto &kv : score_tables) (void)hipFree(kv.second);

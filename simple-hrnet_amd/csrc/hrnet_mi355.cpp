@@ -28,6 +28,7 @@
 #include "rotate_math.h"
 #include "temporal_math.h"
 #include "track_geometry.h"
+#include "yuv_fwd.h"
 
 namespace {
 #include "ctx_types.h"
@@ -1437,6 +1438,82 @@ int hrn_rotate_people_dev(hrn_handle h, int n, int J, const int32_t *frame_hw_ho
     if (hw_bytes) a.frame_hw = (const int *)dev;
     if (code_bytes) a.codes = (const int *)(dev + hw_bytes);
     if (!h->hip_ok(launch_rotate_people(a, s), "rotate people launch")) return 8;
+    return frame.leave() ? 0 : 6;
+}
+
+// ---- BGR frames back to 4:2:0 YCbCr frames (yuv_out.hip; the arithmetic: yuv_fwd.h, one text for these entries and the kernel) ----
+int hrn_yuv_forward_coefficients(int matrix, int range, int32_t out[10]) {
+    if (!out) return 7;
+    return yuv_forward_table(matrix, range, out) ? 0 : 7;
+}
+
+int hrn_bgr_to_yuv_blocks(int matrix, int range, int depth, const uint8_t *bgr, int n, uint16_t *out) {
+    int32_t c[kYuvFwdCoefs];
+    if (!yuv_forward_table(matrix, range, c) || (depth != 8 && depth != 10)) return 7;
+    if (n < 0 || (n > 0 && (!bgr || !out))) return 7;
+    for (int i = 0; i < n; ++i) yuv_fwd_block(c, depth == 10, bgr + (size_t)i * 12, out + (size_t)i * 6);
+    return 0;
+}
+
+// One launch for all frames, as hrn_rotate_frames: both sides of every frame are judged by its plane checks (rotate_frame_fault),
+// the destination's matrix and range choose its table, the records go into the kernel arguments (one frame) or through the
+// handle's guarded table and the pinned ring (more).
+int hrn_bgr_to_yuv_frames(hrn_handle h, const hrn_canvas *src_host, const hrn_canvas *dst_host, int nframes, void *stream) {
+    if (!h) return 1;
+    const auto fail = [&](const std::string &what) {
+        h->err = "hrn_bgr_to_yuv_frames: " + what;
+        return 7;
+    };
+    if (nframes < 0) return fail("nframes is negative");
+    if (nframes > 0 && (!src_host || !dst_host)) return fail("null frame tables");
+    std::vector<YuvOutFrame> frames;
+    long tiles = 0;
+    std::map<const uint8_t *, int> written;   // first plane of a destination -> its frame
+    for (int k = 0; k < nframes; ++k) {
+        const hrn_canvas &s = src_host[k], &d = dst_host[k];
+        const std::string frame = "frame " + std::to_string(k);
+        if (s.format != HRN_PIX_BGR) return fail(frame + ": the source is not an HRN_PIX_BGR frame");
+        if (!pix_is_yuv(d.format))
+            return fail(frame + ": the destination has an unknown format (HRN_PIX_NV12, HRN_PIX_I420, HRN_PIX_NV21, HRN_PIX_P010 or HRN_PIX_I010)");
+        YuvOutFrame f{};
+        if (d.matrix != HRN_YUV_BT601 && d.matrix != HRN_YUV_BT709)
+            return fail(frame + ": the destination has an unknown matrix (HRN_YUV_BT601 or HRN_YUV_BT709)");
+        if (!yuv_forward_table(d.matrix, d.range, f.coef))
+            return fail(frame + ": the destination has an unknown range (HRN_YUV_LIMITED or HRN_YUV_FULL)");
+        if (const char *fault = rotate_frame_fault(s)) return fail(frame + ": the source " + fault);
+        if ((s.height & 1) || (s.width & 1)) return fail(frame + ": the source has an odd width or height");
+        if (s.height > 8192 || s.width > 8192) return fail(frame + ": the source has a side above 8192");
+        if (const char *fault = rotate_frame_fault(d)) return fail(frame + ": the destination " + fault);
+        if (d.height != s.height || d.width != s.width)
+            return fail(frame + ": the destination is " + std::to_string(d.height) + " x " + std::to_string(d.width) + ", the source is " +
+                        std::to_string(s.height) + " x " + std::to_string(s.width));
+        if (!written.emplace(d.y, k).second)
+            return fail("frames " + std::to_string(written[d.y]) + " and " + std::to_string(k) + " name the same destination");
+        f.src = s.y, f.y = d.y, f.u = d.u, f.v = pix_is_planar(d.format) ? d.v : nullptr;
+        f.height = s.height, f.width = s.width, f.spitch = s.pitch_y, f.pitch_y = d.pitch_y, f.pitch_c = d.pitch_c, f.format = d.format;
+        f.tile_start = (int)tiles, f.tiles_x = (f.width + kYuvOutTileW - 1) / kYuvOutTileW;
+        tiles += (long)f.tiles_x * ((f.height + kYuvOutTileH - 1) / kYuvOutTileH);   // (at most 32 x 1024 per frame)
+        if (tiles > 0x7fffffffL) return fail("the call has more than 2^31 - 1 tiles");
+        frames.push_back(f);
+    }
+    for (int k = 0; k < nframes; ++k) {   // a BGR buffer cannot hold its own YUV form: no source is a destination of the call
+        const auto hit = written.find(src_host[k].y);
+        if (hit != written.end())
+            return fail("the source of frame " + std::to_string(k) + " is the destination of frame " + std::to_string(hit->second) +
+                        ": in-place conversion is not offered");
+    }
+    if (h->refuse_plan_only()) return 7;
+    if (nframes == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t table_bytes = nframes > 1 ? frames.size() * sizeof(YuvOutFrame) : 0;
+    CallFrame frame(h, s, {{&h->yuvout_table, table_bytes, hrn_ctx::twice(table_bytes, 4096), "hipMalloc(BGR to YUV table)"}});
+    YuvOutArgs a{};
+    a.nframes = nframes, a.total_tiles = (int)tiles;
+    a.table = frame.table(frames.data(), frames.size(), "hipMemcpyAsync(BGR to YUV table)");
+    if (!frame.ok()) return 6;
+    if (!a.table) a.one = frames[0];
+    if (!h->hip_ok(launch_bgr_to_yuv(a, s), "bgr_to_yuv launch")) return 8;
     return frame.leave() ? 0 : 6;
 }
 

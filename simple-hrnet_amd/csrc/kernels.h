@@ -587,6 +587,25 @@ struct RotPeopleArgs {
 };
 hipError_t launch_rotate_people(const RotPeopleArgs &a, hipStream_t s);   // one thread per joint and per box
 
+// BGR frames to 4:2:0 YCbCr frames (yuv_out.hip; include/hrnet_mi355.h: hrn_bgr_to_yuv_frames; the arithmetic: yuv_fwd.h).
+constexpr int kYuvOutTileW = 256;  // pixels per tile row: 64 groups of 4 pixels, one wavefront wide
+constexpr int kYuvOutTileH = 8;    // rows per tile: 4 groups of 2 rows
+struct YuvOutFrame {               // one frame of the call
+    const unsigned char *src;      // (height, width, 3) BGR, rows spitch bytes apart
+    unsigned char *y, *u, *v;      // the destination's planes (v: I420 / I010 only)
+    int height, width;             // even
+    int spitch, pitch_y, pitch_c;  // bytes between rows
+    int format;                    // HRN_PIX_NV12 / _I420 / _NV21 / _P010 / _I010
+    int tile_start, tiles_x;       // the frame's first tile of the launch; tiles per row of tiles
+    int coef[10];                  // yuv_fwd.h's table of the destination's matrix and range
+};
+struct YuvOutArgs {
+    int nframes, total_tiles;
+    YuvOutFrame one;               // table == nullptr: the call's only frame, in the kernel arguments
+    const YuvOutFrame *table;      // else nframes entries, device
+};
+hipError_t launch_bgr_to_yuv(const YuvOutArgs &a, hipStream_t s);   // bgr_to_yuv_kernel: total_tiles blocks of 256 threads
+
 // Joints over time (temporal.hip; include/hrnet_mi355.h: hrn_filter_poses_dev): the One-Euro filter and the motion lookahead of
 // every joint of the call in one launch, one thread per (person, joint) (the arithmetic: temporal_math.h).
 struct TemporalParams;

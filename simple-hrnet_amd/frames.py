@@ -15,8 +15,8 @@ import torch
 from . import _lib
 
 PIX_FORMATS = {"nv12": 1, "i420": 2}          # include/hrnet_mi355.h: HRN_PIX_*: the 8-bit formats, which every entry takes
-PIX_FORMATS_10BIT = {"p010": 5, "i010": 6}     # HRN_PIX_P010 / _I010: planes of 16-bit little-endian words; input side only
-PIX_NV21 = 4                                   # HRN_PIX_NV21: an "nv12" frame with chroma_order="vu"; input side only (3 is unassigned)
+PIX_FORMATS_10BIT = {"p010": 5, "i010": 6}     # HRN_PIX_P010 / _I010: planes of 16-bit little-endian words; input side and bgr_to_yuv
+PIX_NV21 = 4                                   # HRN_PIX_NV21: an "nv12" frame with chroma_order="vu"; input side and bgr_to_yuv (3 is unassigned)
 PIX_10BIT = tuple(PIX_FORMATS_10BIT)
 PIX_PLANAR = ("i420", "i010")                  # U and V planes of their own, rows of pitch / 2 bytes
 YUV_MATRICES = {"bt601": 0, "bt709": 1}        # HRN_YUV_BT601 / _BT709
@@ -48,6 +48,8 @@ class YuvFrame:
     """One 4:2:0 video frame as a decoder or ``ffmpeg -pix_fmt nv12|nv21|yuv420p|p010le|yuv420p10le`` delivers it, accepted
     wherever a BGR frame is (``preprocess_frame(s)``, ``predict_frame(s)``, ``predict_clip``, ``track_frame``, ``detector_input``,
     ``rotate_frames``) and by ``NativeHRNet.yuv_to_bgr``; ``draw_poses`` / ``draw_labels`` take ``"nv12"`` and ``"i420"`` only.
+    ``NativeHRNet.bgr_to_yuv`` goes the other way: it returns BGR frames as ``YuvFrame``s of any of the five layouts (and writes
+    into a caller's, through ``out=``) -- the annotated frame in the layout an encoder consumes.
 
     ``data``: uint8 tensor or array of any shape, host or device, in the rawvideo layout: ``height`` rows of ``pitch`` bytes of Y,
     then the chroma -- ``"nv12"``: ``height / 2`` rows of ``pitch`` bytes of interleaved U, V; ``"i420"``:
@@ -110,6 +112,13 @@ class YuvFrame:
         f.format, f.matrix, f.range, f.chroma_order = like.format, like.matrix, like.range, like.chroma_order
         f.data = data
         return f
+
+    @classmethod
+    def empty(cls, height: int, width: int, format: str = "nv12", matrix: str = "bt601", range: str = "limited",  # noqa: A002
+              chroma_order: str = "uv", device=None) -> "YuvFrame":
+        """a packed frame over fresh, uninitialised bytes on ``device``: ``bgr_to_yuv``'s destination; the constructor's checks"""
+        nbytes = max(int(height), 0) * max(int(width), 0) * 3 // 2 * (2 if format in PIX_10BIT else 1)
+        return cls(torch.empty((nbytes,), dtype=torch.uint8, device=device), height, width, format, matrix, range, chroma_order=chroma_order)
 
     @property
     def sample_bytes(self) -> int:

@@ -1187,6 +1187,55 @@ class NativeHRNet:
                          ptr(boxes_out))
         return pts_out if boxes is None else boxes_out if pts is None else (pts_out, boxes_out)
 
+    # -- the annotated frame back to the encoder's layout ----------------------------------------------------------------------------
+    def bgr_to_yuv(self, frames, format: str = "nv12", matrix: str = "bt601", range: str = "limited",  # noqa: A002
+                   chroma_order: str = "uv", out=None):
+        """BGR frames as 4:2:0 ``YuvFrame``s on the GPU (``hrn_bgr_to_yuv_frames``: ONE launch for all frames, no scratch) -- the
+        way back from the frame the overlays draw on to what an encoder, a recorder or ``ffmpeg -f rawvideo -pix_fmt
+        nv12|nv21|yuv420p|p010le|yuv420p10le`` consumes.  The arithmetic is the integer definition of include/hrnet_mi355.h: the
+        exact forward coefficients at 20 bits, one chroma sample per 2x2 block from the block's mean; the 10-bit formats from the
+        same 8-bit pixels with one rounding.  Equality with ``cv2.cvtColor(COLOR_BGR2YUV_I420)`` is not pinned.
+
+        ``frames``: one (H, W, 3) uint8 BGR frame, an (F, H, W, 3) stack or a sequence of frames of any (even) sizes; host frames
+        are uploaded once.  ``format``: ``"nv12"``, ``"i420"``, ``"p010"`` or ``"i010"``; ``chroma_order="vu"`` on nv12 gives NV21;
+        ``matrix`` / ``range`` as in ``YuvFrame``.  Returns packed ``YuvFrame``(s) on the engine's GPU with those arguments: one for
+        a frame, a list for a stack or a sequence.
+        ``out``: ``YuvFrame`` destinations on the engine's GPU to write into instead (one, or one per frame; pitched ones are
+        allowed, their padding keeps its bytes); format, matrix, range and chroma order are then THEIRS, and they are returned.
+        Nothing is synchronised."""
+        # what the arguments alone tell is told before anything is uploaded
+        if not isinstance(frames, (torch.Tensor, np.ndarray, YuvFrame)):
+            frames = list(frames)
+        single = isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3
+        if isinstance(frames, YuvFrame) or (not single and any(f is None or isinstance(f, YuvFrame) for f in frames)):
+            raise ValueError("bgr_to_yuv takes BGR frames, none of them None, not YuvFrames")
+        shapes = [tuple(f.shape) if hasattr(f, "shape") else np.shape(f) for f in ([frames] if single else frames)]
+        for k, shape in enumerate(shapes):
+            if len(shape) != 3 or shape[2] != 3:
+                raise ValueError("frame %d must be (H, W, 3) uint8 BGR" % k)
+            if shape[0] <= 0 or shape[1] <= 0 or shape[0] % 2 or shape[1] % 2:
+                raise ValueError("frame %d: a 4:2:0 frame has an even, positive height and width, got %d x %d" % (k, shape[0], shape[1]))
+        if out is None:
+            YuvFrame.empty(2, 2, format, matrix, range, chroma_order)   # (its ValueError; judged even when there is no frame)
+        else:
+            dst = [out] if isinstance(out, YuvFrame) else list(out)
+            if len(dst) != len(shapes):
+                raise ValueError("out has %d frames for %d" % (len(dst), len(shapes)))
+            for k, (d, shape) in enumerate(zip(dst, shapes)):
+                if not isinstance(d, YuvFrame):
+                    raise ValueError("out[%d] must be a YuvFrame" % k)
+                if (d.height, d.width) != shape[:2]:
+                    raise ValueError("out[%d] is %d x %d, frame %d is %d x %d" % (k, d.height, d.width, k, shape[0], shape[1]))
+        dev = self.torch_device
+        src = Frames.resident(frames, dev, one=True, rows=True)
+        if out is None:
+            dst = [YuvFrame.empty(h, w, format, matrix, range, chroma_order, dev) for h, w, _ in shapes]
+        elif any(d.device != dev for d in dst):
+            raise ValueError("out must lie on the engine's device %s: it is written where it is" % (dev,))
+        if len(src):
+            self._launch("hrn_bgr_to_yuv_frames", src.table(kind=_lib.CanvasC), Frames(dst, True).table(kind=_lib.CanvasC), len(src))
+        return dst[0] if single else dst
+
     # -- person ids between two frames: who of the previous frame is who of this one ------------------------------------------------
     def associate_people(self, boxes, pts, prev_boxes, prev_pts, prev_ids, next_id, pose_alpha: float = 0.5,
                          similarity_threshold: float = 0.5, smoothing_alpha: float = 0.0, counts=None, prev_counts=None):
