@@ -729,6 +729,64 @@ int hrn_draw_labels_dev(hrn_handle h, const hrn_canvas *canvases_host, int nfram
                         const int32_t *frame_index_host /* n entries; NULL: nframes == 1 */,
                         const uint8_t *colors_host, const uint8_t *text_colors_host, int Cb,
                         int scale /* 0: the rule */, int thickness, void *stream);
+
+/* ---- heat-map overlays on the GPU: what the network sees, blended into the frame ----
+ * hrn_forward's heat-maps (n, J, hq, wq) never had a picture: the reference leaves it as a "# Heatmaps  # ToDo"
+ * (misc/visualization.py:261-266).  This entry reduces a person's maps over the chosen joints, stretches them over the person's
+ * box, colours them through a 256-entry table and blends them into the frame, from the device memory where maps, boxes and frame
+ * lie.  cv2 cannot be the reference where it is not installed: as with hrn_draw_poses, THE CONTRACT IS THIS INTEGER DEFINITION.
+ * tests/heat_ref.py restates it in numpy; the kernels and hrn_draw_heatmaps_host equal it byte for byte.  One text,
+ * csrc/heat_math.h, is compiled into the kernels and into the two host entries.
+ *
+ * Inputs.  Canvases, frame_index and their refusals are hrn_draw_poses' (HRN_PIX_BGR, _NV12, _I420; the other layouts stay "unknown
+ * format").  heatmaps (n, J, hq, wq) float32, hq and wq in [1, 1024]; boxes (n, 4) int32 (x1, y1, x2, y2), where hrn_boxes_from_poses /
+ * hrn_preprocess_frames_dev leave them; joint_mask J bytes, non-zero = the joint takes part (NULL: all; all zero: refused);
+ * lo < hi finite float32; lut (256, 3) uint8 in the canvas's own colour space (B, G, R, or Y, U, V: the caller converts, as for
+ * the palettes); alpha in [0, 255]; alpha_mode HRN_HEAT_ALPHA_CONST or HRN_HEAT_ALPHA_VALUE; cutoff in [1, 255].
+ * The span of a person's maps on the frame is the decode's (SimpleHRNet.py:306-307): cell (r, c) sits at x = x1 + c bw / wq,
+ * y = y1 + r bh / hq with bw = x2 - x1, bh = y2 - y1, so a peak lies under the disc hrn_draw_poses draws for it.  A person with
+ * bw <= 0, bh <= 0 or a coordinate outside [-8192, 16383] is skipped (the labels' rule).
+ * 1. Reduce and quantise, per person and cell.  v = the maximum over the masked joints, where a NaN never wins a comparison and
+ *    all-NaN gives NaN.  t = (v - lo) * k in float32, the subtraction and the product each rounded on their own (no fused
+ *    multiply-add), k = 255.0f / (hi - lo) formed once on the host in float32.  Q = 0 unless t > 0; Q = 255 if t >= 255; otherwise
+ *    Q = (int)(t + 0.5f) (one more float32 sum).  So NaN and -inf give 0, +inf gives 255.  Q is (n, hq, wq) uint8.
+ * 2. Sample, for frame pixel (px, py) with x1 <= px < x2 and y1 <= py < y2, all in integers:
+ *    ux = min(((px - x1) wq 256) / bw, (wq - 1) 256) (the product in 64 bits -- or 32 unsigned: on a canvas it stays below 2^32 --
+ *    the division floors); c0 = ux >> 8, fx = ux & 255, c1 = min(c0 + 1, wq - 1); uy, r0, r1, fy likewise from py, y1, hq, bh;
+ *    top = Q[r0][c0] (256 - fx) + Q[r0][c1] fx, bot the same on r1; S = (top (256 - fy) + bot fy + 32768) >> 16.
+ * 3. Combine.  V(px, py) = the maximum of S over the people of that canvas whose box holds the pixel, 0 where nobody's does.  A
+ *    maximum has no order: the result depends neither on the call order nor on scheduling.
+ * 4. Blend.  a = alpha (CONST) or (alpha V + 127) / 255 (VALUE).  A pixel is written iff V >= cutoff and a > 0; every written
+ *    byte is (src (255 - a) + lut[V][ch] a + 127) / 255.  Untouched pixels are NOT WRITTEN, pitch padding never is.  On NV12 / I420
+ *    the Y byte is blended per pixel with lut[V][0]; a 2x2 block with at least one written pixel blends its chroma sample once,
+ *    with Vc = (V0 + V1 + V2 + V3 + 2) >> 2 over all four pixels, written or not, a_c from Vc by the same mode rule without the
+ *    cutoff, U with lut[Vc][1] and V with lut[Vc][2]; the sample is not written when a_c = 0.
+ *
+ * hrn_draw_heatmaps_dev: two launches whatever n and nframes, stream-ordered, no host read of device data and no atomics -- a
+ * reduce launch (the one pass over the fp32 maps, writes Q into the handle's call scratch) and a rasteriser of hrn_draw_poses'
+ * geometry (one 256-thread block per 32 x 32 tile of the canvases referred to, a thread per 2x2 block; a tile culls its canvas's
+ * people by box 256 at a time and folds each chunk into the running maximum: any number of boxes on a tile loses nobody).  n == 0
+ * succeeds and launches nothing.  Fails with code 7 and nothing launched, each failure naming its cause, on: n < 0; J outside
+ * [1, HRN_MAX_JOINTS]; hq or wq outside [1, 1024]; lo or hi not finite; hi <= lo; a mask that selects no joint; alpha, alpha_mode
+ * or cutoff out of range; null tables; several frames without frame_index; every canvas refusal of hrn_draw_poses; after those, a
+ * plan-only handle.
+ * hrn_heatmap_quantise (no handle, no GPU): step 1 on host memory, out (n, hq, wq) uint8.  hrn_draw_heatmaps_host (no handle, no
+ * GPU): the whole definition on the CPU -- canvases (planes on the HOST), maps and boxes in host memory, the same arguments and
+ * refusals.  Both return 7 with hrn_heatmap_last_error() (per thread) naming the cause.
+ * Not built: heat-maps on NV21 / P010 / I010 canvases, per-joint colours, contour lines. */
+enum { HRN_HEAT_ALPHA_CONST = 0, HRN_HEAT_ALPHA_VALUE = 1 };
+int hrn_draw_heatmaps_dev(hrn_handle h, const hrn_canvas *canvases_host, int nframes,
+                          const float *heatmaps_dev /* (n,J,hq,wq) */, const int32_t *boxes_dev /* (n,4) */, int n, int J, int hq, int wq,
+                          const int32_t *frame_index_host /* n entries; NULL: nframes == 1 */,
+                          const uint8_t *joint_mask_host /* J bytes or NULL */, float lo, float hi,
+                          const uint8_t *lut_host /* (256,3) */, int alpha, int alpha_mode, int cutoff, void *stream);
+int hrn_heatmap_quantise(const float *maps /* (n,J,hq,wq), host */, int n, int J, int hq, int wq,
+                         const uint8_t *joint_mask /* J bytes or NULL */, float lo, float hi, uint8_t *out /* (n,hq,wq) */);
+int hrn_draw_heatmaps_host(const hrn_canvas *canvases_host /* planes on the host */, int nframes, const float *heatmaps_host,
+                           const int32_t *boxes_host, int n, int J, int hq, int wq, const int32_t *frame_index_host,
+                           const uint8_t *joint_mask_host, float lo, float hi, const uint8_t *lut_host, int alpha, int alpha_mode,
+                           int cutoff);
+const char *hrn_heatmap_last_error(void);
 int hrn_yuv_from_bgr(int matrix, int range, const uint8_t *bgr /* (n,3) */, int n, uint8_t *yuv_out /* (n,3) */);
 
 /* ---- the detector link on the GPU: the letterboxed detector tensor, and the detector's boxes back in frame coordinates ----

@@ -25,16 +25,16 @@
 #include <hip/hip_runtime.h>
 
 #include "draw_labels_math.h"
+#include "draw_tile.h"   // block_compact, frame_of_tile: shared with heat.hip
 #include "kernels.h"
 
 namespace hrn {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+constexpr int kThreads = kDrawThreads;
+constexpr int kWaves = kDrawWaves;
 constexpr int kList = 512;   // entries of the tile's primitive list: two chunks, so that a chunk always fits after a resolve
-static_assert(kDrawTile == 32 && kThreads == (kDrawTile / 2) * (kDrawTile / 2), "one thread per 2 x 2 block of the tile");
 
 __device__ __forceinline__ int wave_min(int v) {
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
@@ -53,29 +53,6 @@ __device__ __forceinline__ bool live_coordinate(float v, int *out) {
     return true;
 }
 
-// Order-keeping compaction over the block: the threads whose `pred` holds call write(position) with consecutive positions in
-// thread order; returns their number.  Three barriers: the first also ends every earlier read of what `write` overwrites, the
-// last publishes what it wrote.
-template <class Write>
-__device__ __forceinline__ int block_compact(bool pred, int *wave_count, const Write &write) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(pred);
-    const int rank = __popcll(b & ((1ull << lane) - 1ull));
-    __syncthreads();
-    if (lane == 0) wave_count[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) {
-        const int c = wave_count[k];
-        if (k < wave) before += c;
-        total += c;
-    }
-    if (pred) write(before + rank);
-    __syncthreads();
-    return total;
-}
-
 // the capsule test of include/hrnet_mi355.h, literally
 __device__ __forceinline__ bool covers(int px, int py, int x0, int y0, int x1, int y1, int q2) {
     const int dx = x1 - x0, dy = y1 - y0, wx = px - x0, wy = py - y0;
@@ -87,16 +64,6 @@ __device__ __forceinline__ bool covers(int px, int py, int x0, int y0, int x1, i
     }
     const long long cross = (long long)wx * dy - (long long)wy * dx;
     return 4 * cross * cross <= (long long)q2 * l2;
-}
-
-// the frame of a tile: the last one whose first tile is not behind it (every frame of the table has tiles)
-__device__ __forceinline__ int frame_of_tile(const DrawFrame *frames, int nframes, int tile) {
-    int lo = 0, hi = nframes - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (frames[mid].tile_start <= tile) lo = mid; else hi = mid - 1;
-    }
-    return lo;
 }
 
 // what a thread writes of its 2 x 2 block at (px, py): the pixels of `drawn` in their colours; on a 4:2:0 canvas the block's

@@ -23,6 +23,7 @@
 #include "pose_nms_math.h"
 #include "detector_nms_math.h"
 #include "draw_labels_math.h"
+#include "heat_math.h"
 #include "keypoint_eval_math.h"
 #include "kernels.h"
 #include "rotate_math.h"
@@ -1023,6 +1024,169 @@ int hrn_draw_labels_dev(hrn_handle h, const hrn_canvas *canvases_host, int nfram
     a.colour = (const unsigned *)(table + off_colour), a.text_colour = (const unsigned *)(table + off_text);
     a.records = (LabelRecord *)records, a.reach = (int4 *)(records + off_reach);
     if (!h->hip_ok(launch_draw_labels(a, s), "label launch")) return 8;
+    return frame.leave() ? 0 : 6;
+}
+
+// ---- heat-map overlays: the maximum over the chosen joints, coloured and blended into the frame (heat_math.h, heat.hip) -----------
+static thread_local std::string g_heat_error;
+
+namespace {
+extern "C++" {
+// what is wrong with the arguments the three heat-map entries share, or "" (canvases: hrn_draw_poses' checks, when there are any)
+std::string heat_fault(const hrn_canvas *canvases, int nframes, bool with_canvases, const void *maps, const void *boxes, int n, int J,
+                       int hq, int wq, const int32_t *frame_index, const uint8_t *joint_mask, float lo, float hi, const uint8_t *lut,
+                       int alpha, int alpha_mode, int cutoff) {
+    if (n < 0) return "n is negative";
+    if (J < 1 || J > HRN_MAX_JOINTS) return "J must be in [1, " + std::to_string(HRN_MAX_JOINTS) + "]";
+    if (hq < 1 || hq > kHeatMaxSide || wq < 1 || wq > kHeatMaxSide) return "hq and wq must be in [1, " + std::to_string(kHeatMaxSide) + "]";
+    if (!std::isfinite(lo) || !std::isfinite(hi)) return "lo and hi must be finite";
+    if (!(hi > lo)) return "hi must be above lo";
+    if (joint_mask) {
+        bool any = false;
+        for (int j = 0; j < J; ++j) any = any || joint_mask[j] != 0;
+        if (!any) return "the joint mask selects no joint";
+    }
+    if (!with_canvases) return n > 0 && !maps ? "null heat-maps" : "";
+    if (alpha < 0 || alpha > 255) return "alpha must be in [0, 255]";
+    if (alpha_mode != HRN_HEAT_ALPHA_CONST && alpha_mode != HRN_HEAT_ALPHA_VALUE)
+        return "alpha_mode must be HRN_HEAT_ALPHA_CONST or HRN_HEAT_ALPHA_VALUE";
+    if (cutoff < 1 || cutoff > 255) return "cutoff must be in [1, 255]";
+    if (!canvases || nframes < 1 || !lut || (n > 0 && (!maps || !boxes))) return "null canvases / heat-maps / boxes / colour table";
+    if (!frame_index && nframes != 1) return "without frame_index there must be one frame";
+    return canvas_table_fault(canvases, nframes, n, frame_index);
+}
+}  // extern "C++"
+// one person's Q (hq, wq) from its (J, hq, wq) maps: the host's form of heat_reduce_kernel
+void heat_quantise_person(const float *maps, int J, int cells, const uint8_t *joint_mask, float lo, float k, uint8_t *out) {
+    for (int c = 0; c < cells; ++c) {
+        float v = __builtin_nanf("");
+        for (int j = 0; j < J; ++j)
+            if (!joint_mask || joint_mask[j]) v = heat_max(v, maps[(size_t)j * cells + c]);
+        out[c] = (uint8_t)heat_quantise(v, lo, k);
+    }
+}
+}  // namespace
+
+const char *hrn_heatmap_last_error(void) { return g_heat_error.c_str(); }
+
+int hrn_heatmap_quantise(const float *maps, int n, int J, int hq, int wq, const uint8_t *joint_mask, float lo, float hi, uint8_t *out) {
+    g_heat_error = heat_fault(nullptr, 0, false, maps, nullptr, n, J, hq, wq, nullptr, joint_mask, lo, hi, nullptr, 0, 0, 1);
+    if (g_heat_error.empty() && n > 0 && !out) g_heat_error = "null output";
+    if (!g_heat_error.empty()) return 7;
+    const float k = 255.0f / (hi - lo);
+    const int cells = hq * wq;
+    for (int i = 0; i < n; ++i) heat_quantise_person(maps + (size_t)i * J * cells, J, cells, joint_mask, lo, k, out + (size_t)i * cells);
+    return 0;
+}
+
+// the whole definition on the CPU: Q of everybody, then per canvas one full-frame V and the blend
+int hrn_draw_heatmaps_host(const hrn_canvas *canvases_host, int nframes, const float *heatmaps_host, const int32_t *boxes_host, int n, int J,
+                           int hq, int wq, const int32_t *frame_index_host, const uint8_t *joint_mask_host, float lo, float hi,
+                           const uint8_t *lut_host, int alpha, int alpha_mode, int cutoff) {
+    g_heat_error = heat_fault(canvases_host, nframes, true, heatmaps_host, boxes_host, n, J, hq, wq, frame_index_host, joint_mask_host, lo,
+                              hi, lut_host, alpha, alpha_mode, cutoff);
+    if (!g_heat_error.empty()) return 7;
+    if (n == 0) return 0;
+    const float k = 255.0f / (hi - lo);
+    const int cells = hq * wq;
+    std::vector<uint8_t> q((size_t)n * cells);
+    for (int i = 0; i < n; ++i)
+        heat_quantise_person(heatmaps_host + (size_t)i * J * cells, J, cells, joint_mask_host, lo, k, q.data() + (size_t)i * cells);
+    std::vector<uint8_t> V;
+    for (int f = 0; f < nframes; ++f) {
+        std::vector<int> people;
+        for (int i = 0; i < n; ++i)
+            if ((frame_index_host ? frame_index_host[i] : 0) == f) people.push_back(i);
+        if (people.empty()) continue;
+        const hrn_canvas &c = canvases_host[f];
+        const int H = c.height, W = c.width;
+        V.assign((size_t)H * W, 0);
+        for (int i : people) {
+            const int32_t *b = boxes_host + 4 * (size_t)i;
+            if (!heat_box_drawn(b[0], b[1], b[2], b[3])) continue;
+            const int bw = b[2] - b[0], bh = b[3] - b[1];
+            for (int py = std::max(b[1], 0); py < std::min(b[3], H); ++py) {
+                const int uy = heat_coord(py - b[1], hq, bh);
+                for (int px = std::max(b[0], 0); px < std::min(b[2], W); ++px) {
+                    const int S = heat_sample(q.data() + (size_t)i * cells, hq, wq, heat_coord(px - b[0], wq, bw), uy);
+                    uint8_t &v = V[(size_t)py * W + px];
+                    if (S > v) v = (uint8_t)S;
+                }
+            }
+        }
+        const auto colour = [&](int v, int ch) { return (int)lut_host[3 * v + ch]; };
+        if (c.format == HRN_PIX_BGR) {
+            for (int py = 0; py < H; ++py)
+                for (int px = 0; px < W; ++px) {
+                    const int v = V[(size_t)py * W + px];
+                    int a;
+                    if (!heat_written(v, alpha, alpha_mode, cutoff, &a)) continue;
+                    uint8_t *dst = c.y + (size_t)py * c.pitch_y + 3 * (size_t)px;
+                    for (int ch = 0; ch < 3; ++ch) dst[ch] = (uint8_t)heat_blend(dst[ch], colour(v, ch), a);
+                }
+            continue;
+        }
+        for (int by = 0; by < H / 2; ++by)
+            for (int bx = 0; bx < W / 2; ++bx) {
+                int v4[4];
+                bool any = false;
+                for (int p = 0; p < 4; ++p) {
+                    const int py = 2 * by + (p >> 1), px = 2 * bx + (p & 1);
+                    v4[p] = V[(size_t)py * W + px];
+                    int a;
+                    if (!heat_written(v4[p], alpha, alpha_mode, cutoff, &a)) continue;
+                    uint8_t *dst = c.y + (size_t)py * c.pitch_y + px;
+                    *dst = (uint8_t)heat_blend(*dst, colour(v4[p], 0), a);
+                    any = true;
+                }
+                if (!any) continue;
+                const int vc = heat_block_value(v4[0], v4[1], v4[2], v4[3]), ac = heat_alpha(vc, alpha, alpha_mode);
+                if (ac <= 0) continue;
+                uint8_t *u = c.format == HRN_PIX_NV12 ? c.u + (size_t)by * c.pitch_c + 2 * bx : c.u + (size_t)by * c.pitch_c + bx;
+                uint8_t *v = c.format == HRN_PIX_NV12 ? u + 1 : c.v + (size_t)by * c.pitch_c + bx;
+                *u = (uint8_t)heat_blend(*u, colour(vc, 1), ac);
+                *v = (uint8_t)heat_blend(*v, colour(vc, 2), ac);
+            }
+    }
+    return 0;
+}
+
+// the arguments are judged first (they need no device), then the handle; one table upload and two launches follow
+int hrn_draw_heatmaps_dev(hrn_handle h, const hrn_canvas *canvases_host, int nframes, const float *heatmaps_dev, const int32_t *boxes_dev,
+                          int n, int J, int hq, int wq, const int32_t *frame_index_host, const uint8_t *joint_mask_host, float lo, float hi,
+                          const uint8_t *lut_host, int alpha, int alpha_mode, int cutoff, void *stream) {
+    if (!h) return 1;
+    const std::string fault = heat_fault(canvases_host, nframes, true, heatmaps_dev, boxes_dev, n, J, hq, wq, frame_index_host,
+                                         joint_mask_host, lo, hi, lut_host, alpha, alpha_mode, cutoff);
+    if (!fault.empty()) {
+        h->err = "hrn_draw_heatmaps_dev: " + fault;
+        return 7;
+    }
+    if (h->refuse_plan_only()) return 7;
+    if (n == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+
+    const CanvasTable ct(nframes, n, frame_index_host);
+    const size_t off_lut = ct.end, table_bytes = off_lut + 256 * 4;
+    const PinnedImage img = h->image(table_bytes);
+    if (!img) return 6;
+    const int tiles = ct.fill(img.ptr, canvases_host, n, frame_index_host, [](const hrn_canvas &) { return 0; });
+    for (int v = 0; v < 256; ++v) img.as<unsigned>(off_lut)[v] = pack_colour(lut_host + 3 * (size_t)v);
+    const size_t q_bytes = (size_t)n * hq * wq;
+    CallFrame frame(h, s, {{&h->draw_table, table_bytes, hrn_ctx::twice(table_bytes, 4096), "hipMalloc(draw table)"},
+                           {&h->draw_records, q_bytes, hrn_ctx::twice(q_bytes, 4096), "hipMalloc(quantised heat-maps)"}});
+    char *table = frame.upload(img, table_bytes, "hipMemcpyAsync(draw table)"), *records = frame.dev(h->draw_records);
+    if (!table) return 6;
+    HeatArgs a{};
+    a.maps = heatmaps_dev, a.boxes = boxes_dev, a.n = n, a.J = J, a.hq = hq, a.wq = wq, a.nframes = ct.used, a.total_tiles = tiles;
+    a.lo = lo, a.k = 255.0f / (hi - lo), a.alpha = alpha, a.mode = alpha_mode, a.cutoff = cutoff;
+    static_assert(kMaxJoints <= 256, "a joint index fits a byte");
+    for (int j = 0; j < J; ++j)
+        if (!joint_mask_host || joint_mask_host[j]) a.joints[a.njoints++] = (unsigned char)j;
+    a.frames = (const DrawFrame *)table, a.order = (const int *)(table + ct.off_order), a.lut = (const unsigned *)(table + off_lut);
+    a.q = (unsigned char *)records;
+    if (!h->hip_ok(launch_draw_heatmaps(a, s), "heat-map launch")) return 8;
     return frame.leave() ? 0 : 6;
 }
 

@@ -393,6 +393,23 @@ struct LabelArgs {
 };
 hipError_t launch_draw_labels(const LabelArgs &a, hipStream_t s);   // label_build_kernel, then label_raster_kernel
 
+// Heat-map overlays (heat.hip; include/hrnet_mi355.h: hrn_draw_heatmaps_dev; the arithmetic: heat_math.h).  The table is
+// hrn_draw_poses' -- canvases, people by canvas -- and the colour table; the joint mask and the scalars travel in the arguments.
+struct HeatArgs {
+    const float *maps;             // (n, J, hq, wq) float32, device: where the pass left them
+    const int *boxes;              // (n, 4) int32 (x1, y1, x2, y2), device
+    int n, J, hq, wq, nframes, total_tiles;
+    float lo, k;                   // k = 255 / (hi - lo), formed once on the host in float32
+    int alpha, mode, cutoff;
+    int njoints;                   // >= 1
+    unsigned char joints[kMaxJoints];   // the joints that take part in the maximum, ascending (an index fits a byte)
+    const DrawFrame *frames;       // nframes entries (DrawFrame::radius is unused)
+    const int *order;              // n person indices grouped by canvas
+    const unsigned *lut;           // 256: three bytes, byte 0 first
+    unsigned char *q;              // (n, hq, wq): written by the reduce launch, read by the rasteriser
+};
+hipError_t launch_draw_heatmaps(const HeatArgs &a, hipStream_t s);   // heat_reduce_kernel, then heat_raster_kernel
+
 // The tracking link (track.hip; include/hrnet_mi355.h: hrn_boxes_from_poses, hrn_preprocess_frames_dev): boxes from the joints
 // where the decode left them, and the crop records of the pre-path from detections on the device -- one launch each.
 struct PoseBoxArgs {

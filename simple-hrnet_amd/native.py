@@ -21,7 +21,7 @@ import torch
 from . import _lib
 from .frames import (NUMPY_DTYPES, PIX_FORMATS, YUV_MATRICES, YUV_RANGES, Frames, YuvFrame, _bgr_rows, _check_frame, _frame_kind, as_tensor,  # noqa: F401
                      device_tensor, frame_stack, host_array, host_bytes, rotation_code_from_degrees, rotation_codes)
-from .palettes import bgr_to_yuv_colors, embedded_palette, find_palette  # noqa: F401
+from .palettes import bgr_to_yuv_colors, embedded_palette, find_palette, heat_colormap  # noqa: F401
 
 DTYPES = {"fp32": 0, "f32": 0, "float32": 0, torch.float32: 0, "bf16": 1, "bfloat16": 1, torch.bfloat16: 1,
           "fp16": 2, "f16": 2, "float16": 2, "half": 2, torch.float16: 2}
@@ -59,6 +59,40 @@ def palette(name: str, samples: int = 16) -> np.ndarray:
     if key not in _PALETTE_CACHE:
         _PALETTE_CACHE[key] = find_palette(*key)
     return _PALETTE_CACHE[key].copy()
+
+
+HEAT_ALPHA_MODES = {"const": 0, "value": 1}   # include/hrnet_mi355.h: HRN_HEAT_ALPHA_CONST / _VALUE
+
+
+def heat_arguments(J: int, joints, colormap, alpha, alpha_mode, vmin, vmax, cutoff):
+    """the scalar arguments of ``draw_heatmaps`` (here and in ``postproc``) as the C ABI takes them: (joint mask (J,) uint8 or None,
+    BGR table (256, 3) uint8, alpha 0..255, mode code, lo, hi, cutoff 1..255); ValueError on what the library would not be asked"""
+    mask = None
+    if joints is not None:
+        if isinstance(joints, str) or any(isinstance(j, str) for j in joints):
+            raise ValueError("joints must be joint indices: this package knows no joint names (take them from the reference's joints_dict())")
+        idx = np.asarray(joints, dtype=np.int64).reshape(-1)
+        if len(idx) < 1 or idx.min() < 0 or idx.max() >= J:
+            raise ValueError("joints must be a non-empty list of indices in [0, %d)" % J)
+        mask = np.zeros((J,), np.uint8)
+        mask[idx] = 1
+    if isinstance(colormap, str):
+        lut = heat_colormap(colormap)
+    else:
+        lut = np.asarray(colormap)
+        if lut.shape != (256, 3) or lut.dtype != np.uint8:
+            raise ValueError("colormap must be a name (heat_colormap) or a (256, 3) uint8 array of (B, G, R) rows")
+        lut = np.ascontiguousarray(lut)
+    if alpha_mode not in HEAT_ALPHA_MODES:
+        raise ValueError("alpha_mode must be 'const' or 'value', got %r" % (alpha_mode,))
+
+    def byte(x, what, low):
+        v = int(round(255 * float(x))) if isinstance(x, (float, np.floating)) else int(x)
+        if not low <= v <= 255:
+            raise ValueError("%s must be in [%s, 1.0] as a float or [%d, 255] as an integer, got %r" % (what, "1/255" if low else "0.0", low, x))
+        return v
+
+    return mask, lut, byte(alpha, "alpha", 0), HEAT_ALPHA_MODES[alpha_mode], float(vmin), float(vmax), byte(cutoff, "cutoff", 1)
 
 
 def _colors(spec, samples) -> np.ndarray:
@@ -691,6 +725,68 @@ class NativeHRNet:
         self._launch("hrn_draw_labels_dev", table, len(items), boxes.data_ptr() if n else None, None if ids is None else ids.data_ptr(),
                      None if scores is None else scores.data_ptr(), stride, n, None if fi is None else fi.ctypes.data,
                      colours.ctypes.data, text.ctypes.data, len(colours), 0 if scale is None else int(scale), int(thickness))
+        return canvases[0] if single else list(canvases)
+
+    def draw_heatmaps(self, frames, heatmaps, boxes, frame_index=None, joints=None, colormap="jet", alpha=0.6, alpha_mode: str = "value",
+                      vmin: float = 0.0, vmax: float = 1.0, cutoff=0.1, matrix: Optional[str] = None, range: Optional[str] = None):  # noqa: A002
+        """What the network sees, on the frame, on the GPU (``hrn_draw_heatmaps_dev``): for every person the maximum of its
+        heat-maps over ``joints``, stretched over the person's box as the decode places it (a peak lies under the disc
+        ``draw_poses`` draws for it), coloured through ``colormap`` and blended into the frame; where boxes overlap the larger
+        value shows.  Two launches whatever the number of frames and people; maps, boxes and frames are used where
+        ``predict_frame(..., return_heatmaps=True)`` / ``track_frame`` left them.  The arithmetic is the integer definition of
+        include/hrnet_mi355.h; equality with cv2.resize / applyColorMap / addWeighted is not claimed.  Call it before
+        ``draw_poses``: later drawing lies on top.
+
+        ``frames``: as in ``draw_poses`` -- a BGR tensor or array (rows may be strided), a ``YuvFrame`` (``"nv12"`` / ``"i420"``), or
+        a list of either kind with None for frames nobody is on; frames on the engine's GPU are drawn IN PLACE and returned, host
+        frames are uploaded.  ``heatmaps``: (n, J, h, w) or (J, h, w) float32; ``boxes``: (n, 4) or (4,) integer (x1, y1, x2, y2), a
+        tensor on the device or the numpy boxes ``predict_frame`` returns; a degenerate box is skipped.  ``frame_index``: n frame
+        numbers when there are several frames.  ``joints``: the indices that take part (default all; this package knows no joint
+        names).  ``colormap``: a ``heat_colormap`` name or a (256, 3) uint8 BGR table -- converted with ``bgr_to_yuv_colors`` for
+        ``YuvFrame``s, by the frames' own matrix and range unless ``matrix`` / ``range`` name another.  ``vmin`` / ``vmax``: the
+        map values shown as 0 and 255.  ``alpha``, ``cutoff``: floats are mapped to 0..255 by ``round(255 x)``, integers are taken
+        as they are; ``alpha_mode``: ``"const"`` blends every shown pixel with ``alpha``, ``"value"`` with ``alpha`` times its value;
+        a pixel below ``cutoff`` is left alone.  For flip-TTA, pass ``predict_flip_tta``'s averaged maps."""
+        single = not isinstance(frames, (list, tuple))
+        items = [frames] if single else list(frames)
+        if not items:
+            raise ValueError("draw_heatmaps needs at least one frame")
+        dev = self.torch_device
+        canvases = Frames.canvases(items, dev)
+        table = canvases.table(kind=_lib.CanvasC)
+        maps = as_tensor(heatmaps, np.float32)
+        if maps.dim() == 3:
+            maps = maps.unsqueeze(0)
+        if maps.dim() != 4 or min(maps.shape[1:]) < 1:
+            raise ValueError("heatmaps must be (J, h, w) or (n, J, h, w)")
+        maps = device_tensor(maps, dev, torch.float32)
+        n, J, hq, wq = (int(v) for v in maps.shape)
+        if not isinstance(boxes, torch.Tensor):
+            boxes = np.asarray(boxes)
+        if (boxes.is_floating_point() or boxes.dtype == torch.bool) if isinstance(boxes, torch.Tensor) else boxes.dtype.kind not in "iu":
+            raise ValueError("boxes must be integers (the int32 boxes predict_frame / PersonTracker.update return)")
+        boxes = as_tensor(boxes, np.int32)
+        if boxes.dim() == 1:
+            boxes = boxes.unsqueeze(0)
+        if boxes.dim() != 2 or boxes.shape[1] != 4 or int(boxes.shape[0]) != n:
+            raise ValueError("boxes must be (n, 4) (x1, y1, x2, y2), one row per person: %s for %d people" % (tuple(boxes.shape), n))
+        boxes = device_tensor(boxes, dev, torch.int32)
+        fi = None
+        if frame_index is not None:
+            fi = np.ascontiguousarray(np.asarray(frame_index, dtype=np.int32).reshape(-1))
+            if len(fi) != n:
+                raise ValueError("frame_index must have one entry per person: %d for %d people" % (len(fi), n))
+        elif len(items) != 1:
+            raise ValueError("several frames need frame_index: which frame each person is drawn on")
+        mask, lut, a, mode, lo, hi, cut = heat_arguments(J, joints, colormap, alpha, alpha_mode, vmin, vmax, cutoff)
+        if canvases.yuv:
+            spaces = {(matrix or f.matrix, range or f.range) for f in canvases if f is not None}
+            if len(spaces) != 1:
+                raise ValueError("the YuvFrames of one draw_heatmaps call share one matrix and range (the table is converted once)")
+            (matrix_, range_), = spaces
+            lut = bgr_to_yuv_colors(lut, matrix_, range_)
+        self._launch("hrn_draw_heatmaps_dev", table, len(items), maps.data_ptr() if n else None, boxes.data_ptr() if n else None, n, J, hq, wq,
+                     None if fi is None else fi.ctypes.data, None if mask is None else mask.ctypes.data, lo, hi, lut.ctypes.data, a, mode, cut)
         return canvases[0] if single else list(canvases)
 
     def resize_frames(self, frames, interpolation: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -57,6 +57,28 @@ def find_palette(name: str, samples: int) -> np.ndarray:
     return np.ascontiguousarray(out)
 
 
+HEAT_COLORMAPS = ("jet", "hot", "gray")
+
+
+def heat_colormap(name: str = "jet") -> np.ndarray:
+    """The (256, 3) uint8 table of (B, G, R) rows ``draw_heatmaps`` colours a value 0..255 with, defined in integers (no matplotlib):
+
+    ``"jet"``: for ``i`` in 0..255 and ``k`` = 3, 2, 1 for R, G, B: ``(clamp(765 - |8 i - 510 k|, 0, 510) + 1) >> 1`` -- dark blue,
+    blue, cyan, yellow, red, dark red; ``"hot"``: for ``k`` = 0, 1, 2 for R, G, B: ``clamp(3 i - 255 k, 0, 255)`` -- black, red,
+    yellow, white, each channel ramping over a third of the range after the one before is full; ``"gray"``: ``i`` in all three.
+    For a ``YuvFrame`` the table goes through ``bgr_to_yuv_colors``.  Any other name raises ValueError."""
+    i = np.arange(256, dtype=np.int64)
+    if name == "jet":
+        rgb = [(np.clip(765 - np.abs(8 * i - 510 * k), 0, 510) + 1) >> 1 for k in (3, 2, 1)]
+    elif name == "hot":
+        rgb = [np.clip(3 * i - 255 * k, 0, 255) for k in (0, 1, 2)]
+    elif name == "gray":
+        rgb = [i, i, i]
+    else:
+        raise ValueError("colormap must be one of %s or a (256, 3) uint8 array, got %r" % (", ".join(repr(n) for n in HEAT_COLORMAPS), name))
+    return np.ascontiguousarray(np.stack(rgb[::-1], 1).astype(np.uint8))   # R, G, B -> B, G, R
+
+
 def bgr_to_yuv_colors(colors, matrix: str = "bt601", range: str = "limited") -> np.ndarray:  # noqa: A002
     """(C, 3) uint8 (B, G, R) colours as (Y, U, V) of a matrix and range (``hrn_yuv_from_bgr``: the float64 forward formula of the
     conversion ``YuvFrame``s are read with, rounded once): what ``draw_poses`` draws with on a ``YuvFrame``."""

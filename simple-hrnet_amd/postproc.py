@@ -824,6 +824,87 @@ def label_covers(record, px: int, py: int) -> int:
     return rc
 
 
+# -- heat-map overlays on the host: the quantised maps, and the whole definition on the CPU ---------------------------------------
+def heatmap_quantise(heatmaps, joints=None, vmin: float = 0.0, vmax: float = 1.0) -> np.ndarray:
+    """Step 1 of ``NativeHRNet.draw_heatmaps`` on the host (``hrn_heatmap_quantise``, no GPU): the maximum of every person's
+    (n, J, h, w) float32 maps over ``joints`` (indices; default all), quantised to (n, h, w) uint8 -- ``vmin`` -> 0, ``vmax`` ->
+    255, NaN -> 0.  include/hrnet_mi355.h has the definition."""
+    import ctypes
+
+    from . import _lib
+    from .native import heat_arguments
+
+    maps = np.ascontiguousarray(np.asarray(heatmaps, dtype=np.float32))
+    if maps.ndim == 3:
+        maps = maps[None]
+    if maps.ndim != 4:
+        raise ValueError("heatmaps must be (J, h, w) or (n, J, h, w)")
+    n, J, hq, wq = maps.shape
+    mask = heat_arguments(J, joints, "gray", 0, "const", vmin, vmax, 1)[0] if joints is not None else None
+    out = np.empty((n, hq, wq), np.uint8)
+    lib = _lib.load()
+    rc = lib.hrn_heatmap_quantise(maps.ctypes.data, n, J, hq, wq, None if mask is None else mask.ctypes.data, ctypes.c_float(vmin),
+                                  ctypes.c_float(vmax), out.ctypes.data)
+    if rc != 0:
+        raise ValueError("hrn_heatmap_quantise: " + lib.hrn_heatmap_last_error().decode())
+    return out
+
+
+def draw_heatmaps(frames, heatmaps, boxes, frame_index=None, joints=None, colormap="jet", alpha=0.6, alpha_mode: str = "value",
+                  vmin: float = 0.0, vmax: float = 1.0, cutoff=0.1, matrix=None, range=None):  # noqa: A002
+    """``NativeHRNet.draw_heatmaps`` on the host (``hrn_draw_heatmaps_host``, no GPU): the same arguments, the same bytes.
+    ``frames``: (H, W, 3) uint8 BGR arrays (rows may be strided) or host ``YuvFrame``s, one or a list (None: nobody is on it);
+    they are drawn IN PLACE and returned.  ``heatmaps`` (n, J, h, w) float32 and ``boxes`` (n, 4) integers are host arrays."""
+    import ctypes
+
+    import torch
+
+    from . import _lib
+    from .frames import Frames
+    from .native import heat_arguments
+    from .palettes import bgr_to_yuv_colors
+
+    single = not isinstance(frames, (list, tuple))
+    items = [frames] if single else list(frames)
+    if not items:
+        raise ValueError("draw_heatmaps needs at least one frame")
+    canvases = Frames.canvases(items, torch.device("cpu"))
+    table = canvases.table(kind=_lib.CanvasC)
+    maps = np.ascontiguousarray(np.asarray(heatmaps, dtype=np.float32))
+    if maps.ndim == 3:
+        maps = maps[None]
+    if maps.ndim != 4 or min(maps.shape[1:]) < 1:
+        raise ValueError("heatmaps must be (J, h, w) or (n, J, h, w)")
+    n, J, hq, wq = maps.shape
+    b = np.asarray(boxes)
+    if b.dtype.kind not in "iu":
+        raise ValueError("boxes must be integers (the int32 boxes predict_frame / PersonTracker.update return)")
+    b = np.ascontiguousarray(b.reshape(-1, 4), dtype=np.int32)
+    if len(b) != n:
+        raise ValueError("boxes must be (n, 4) (x1, y1, x2, y2), one row per person: %d for %d people" % (len(b), n))
+    fi = None
+    if frame_index is not None:
+        fi = np.ascontiguousarray(np.asarray(frame_index, dtype=np.int32).reshape(-1))
+        if len(fi) != n:
+            raise ValueError("frame_index must have one entry per person: %d for %d people" % (len(fi), n))
+    elif len(items) != 1:
+        raise ValueError("several frames need frame_index: which frame each person is drawn on")
+    mask, lut, a, mode, lo, hi, cut = heat_arguments(J, joints, colormap, alpha, alpha_mode, vmin, vmax, cutoff)
+    if canvases.yuv:
+        spaces = {(matrix or f.matrix, range or f.range) for f in canvases if f is not None}
+        if len(spaces) != 1:
+            raise ValueError("the YuvFrames of one draw_heatmaps call share one matrix and range (the table is converted once)")
+        (matrix_, range_), = spaces
+        lut = bgr_to_yuv_colors(lut, matrix_, range_)
+    lib = _lib.load()
+    rc = lib.hrn_draw_heatmaps_host(table, len(items), maps.ctypes.data if n else None, b.ctypes.data if n else None, n, J, hq, wq,
+                                    None if fi is None else fi.ctypes.data, None if mask is None else mask.ctypes.data,
+                                    ctypes.c_float(lo), ctypes.c_float(hi), lut.ctypes.data, a, mode, cut)
+    if rc != 0:
+        raise ValueError("hrn_draw_heatmaps_host: " + lib.hrn_heatmap_last_error().decode())
+    return items[0] if single else items
+
+
 # -- the detector link on the host: letterbox geometry and the detector's boxes back in frame coordinates -------------------------
 LETTERBOX_RULES = {"yolov3": 0, "yolov5": 1}     # include/hrnet_mi355.h: HRN_LETTERBOX_MAX_SIDE / _MIN_RATIO
 LETTERBOX_PAD = {"yolov3": 128, "yolov5": 114}   # the wrappers' border: 127.5 is 128 under cv2's round-half-even saturation
