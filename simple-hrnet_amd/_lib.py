@@ -36,7 +36,7 @@ SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "c
            # fp16 instantiations of the three hand-scheduled kernel families (bodies shared through conv3x3_lds.inc / conv_s2.inc /
            # bottleneck_chain.inc): translation units of their own, so that each bf16 file still compiles to exactly its kernel set
            "conv3x3_lds_f16.hip", "conv_s2_f16.hip", "bottleneck_chain_f16.hip"]
-HEADERS = [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "dt16.h"), os.path.join(CSRC, "argmax.h"), os.path.join(CSRC, "conv3x3_n96.inc"), os.path.join(CSRC, "conv3x3_lds.inc"),
+HEADERS = [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "elem.h"), os.path.join(CSRC, "argmax.h"), os.path.join(CSRC, "conv3x3_n96.inc"), os.path.join(CSRC, "conv3x3_lds.inc"),
            os.path.join(CSRC, "conv_s2.inc"), os.path.join(CSRC, "bottleneck_chain.inc"), os.path.join(INCLUDE, "hrnet_mi355.h")]
 MAX_BUILD_WORKERS = 16   # compiler processes at once (a shared build box gives a job 16 CPUs, whatever os.cpu_count() says)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-result", "-Wno-inline-asm"]
@@ -55,7 +55,7 @@ def _obj_dir() -> str:
 
 
 def _deps(src: str) -> List[str]:
-    """files whose change invalidates the object of `src` (every source includes kernels.h; the kernel sources dt16.h and the
+    """files whose change invalidates the object of `src` (every source includes kernels.h; the kernel sources elem.h and the
     .inc files that hold their bodies -- conv3x3_lds(_f16).hip, conv_s2(_f16).hip, bottleneck_chain(_f16).hip)"""
     d = [os.path.join(CSRC, src)] + HEADERS
     return d + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".inc") or f.endswith(".h")]

@@ -28,13 +28,18 @@
 #include <stdlib.h>
 
 #include "kernels.h"
-#include "dt16.h"
+#include "elem.h"
 
 namespace hrn {
 
 // (the kernel bodies: bottleneck_chain.inc, shared with the fp16 instantiations in bottleneck_chain_f16.hip)
 #include "bottleneck_chain.inc"
 
-hipError_t launch_bottleneck_chain(const ChainArgs &a, hipStream_t s) { return launch_bottleneck_chain_t<DT_BF16>(a, s); }
+hipError_t launch_bottleneck_chain_f16(const ChainArgs &a, hipStream_t s);   // bottleneck_chain_f16.hip
+
+hipError_t launch_bottleneck_chain(int dtype, const ChainArgs &a, hipStream_t s) {
+    if (dtype == DT_F16) return launch_bottleneck_chain_f16(a, s);
+    return dtype == DT_BF16 ? launch_bottleneck_chain_t<DT_BF16>(a, s) : hipErrorInvalidValue;
+}
 
 }  // namespace hrn

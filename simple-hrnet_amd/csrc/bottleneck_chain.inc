@@ -1,11 +1,6 @@
-// Body of the layer1 chain kernels (bottleneck_chain.hip: design notes), templated on the 16-bit element format DT (dt16.h).
+// Body of the layer1 chain kernels (bottleneck_chain.hip: design notes), templated on the 16-bit element format DT (elem.h).
 // bottleneck_chain.hip instantiates the four variants for bf16, bottleneck_chain_f16.hip for fp16.  Included inside namespace hrn,
-// after kernels.h / dt16.h.
-#define GLOBAL_AS __attribute__((address_space(1)))
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+// after elem.h.
 
 namespace {
 
@@ -113,7 +108,7 @@ __global__ __launch_bounds__(C3 ? 64 * C3_WAVES : DS ? 512 : 256, C3 ? C3_WAVES 
                     const int kc = dh * 6 + e;
 #pragma unroll
                     for (int f = 0; f < 4; ++f)
-                        acc2[f] = H16<DT>::mma(w2f[(f * W2_CHUNKS + kc) * 64], xt[dh & 1][e], acc2[f]);
+                        acc2[f] = Tr<DT>::mma(w2f[(f * W2_CHUNKS + kc) * 64], xt[dh & 1][e], acc2[f]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -126,7 +121,7 @@ __global__ __launch_bounds__(C3 ? 64 * C3_WAVES : DS ? 512 : 256, C3 ? C3_WAVES 
                     float v = acc2[2 * c + (e >> 2)][e & 3] + b2s[c * 32 + g * 8 + e];
                     v = fmaxf(v, 0.f);
                     if (!ok) v = 0.f;
-                    a[c][e] = (short)H16<DT>::st(v);
+                    a[c][e] = (short)Tr<DT>::st(v);
                 }
         }
         if constexpr (DS) {
@@ -148,7 +143,7 @@ __global__ __launch_bounds__(C3 ? 64 * C3_WAVES : DS ? 512 : 256, C3 ? C3_WAVES 
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const int f = 4 * (b & 3) + t;
-                    accd[f] = H16<DT>::mma(wb[b & 1][t], xa[b >> 2], accd[f]);
+                    accd[f] = Tr<DT>::mma(wb[b & 1][t], xa[b >> 2], accd[f]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -159,7 +154,7 @@ __global__ __launch_bounds__(C3 ? 64 * C3_WAVES : DS ? 512 : 256, C3 ? C3_WAVES 
                 for (int e = 0; e < 8; ++e) {
                     float v = accd[2 * j + (e >> 2)][e & 3] + (e < 4 ? ba[e & 3] : bb[e & 3]);
                     if (!ok) v = 0.f;
-                    r[j][e] = (short)H16<DT>::st(v);
+                    r[j][e] = (short)Tr<DT>::st(v);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -184,7 +179,7 @@ __global__ __launch_bounds__(C3 ? 64 * C3_WAVES : DS ? 512 : 256, C3 ? C3_WAVES 
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int f = 4 * (b & 3) + t;
-                acc[f] = H16<DT>::mma(wb[b & 1][t], a[b >> 2], acc[f]);
+                acc[f] = Tr<DT>::mma(wb[b & 1][t], a[b >> 2], acc[f]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -196,10 +191,10 @@ __global__ __launch_bounds__(C3 ? 64 * C3_WAVES : DS ? 512 : 256, C3 ? C3_WAVES 
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float v = acc[2 * j + (e >> 2)][e & 3] + (e < 4 ? ba[e & 3] : bb[e & 3]);
-                v += H16<DT>::ld((unsigned short)r[j][e]);
+                v += Tr<DT>::ld((unsigned short)r[j][e]);
                 v = fmaxf(v, 0.f);
                 if (!ok) v = 0.f;
-                y[j][e] = (short)H16<DT>::st(v);
+                y[j][e] = (short)Tr<DT>::st(v);
             }
             if (live) *(GLOBAL_AS s16x8 *)(out_y + (size_t)q * CMID + j * 32 + g * 8) = y[j];
         }
@@ -218,7 +213,7 @@ __global__ __launch_bounds__(C3 ? 64 * C3_WAVES : DS ? 512 : 256, C3 ? C3_WAVES 
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t)
-                acc2[t] = H16<DT>::mma(wb[kc & 1][t], y[kc], acc2[t]);
+                acc2[t] = Tr<DT>::mma(wb[kc & 1][t], y[kc], acc2[t]);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
@@ -229,7 +224,7 @@ __global__ __launch_bounds__(C3 ? 64 * C3_WAVES : DS ? 512 : 256, C3 ? C3_WAVES 
                 float v = acc2[2 * h + (e >> 2)][e & 3] + b3s[CMID + g * 16 + h * 8 + e];
                 v = fmaxf(v, 0.f);
                 if (!ok) v = 0.f;
-                o8[e] = (short)H16<DT>::st(v);
+                o8[e] = (short)Tr<DT>::st(v);
             }
             if (live) *(GLOBAL_AS s16x8 *)(out_t + (size_t)q * COUT + g * 16 + h * 8) = o8;
         }
@@ -238,17 +233,11 @@ __global__ __launch_bounds__(C3 ? 64 * C3_WAVES : DS ? 512 : 256, C3 ? C3_WAVES 
 
 template <int DT, bool DS, int C3 = 0>
 static hipError_t launch_chain_t(const ChainArgs &a, hipStream_t s) {
-    static std::atomic<unsigned long long> lds_set{0};   // per device: kernels.h set_dynamic_lds
-    {
-        const hipError_t e = set_dynamic_lds((const void *)bottleneck_chain_kernel<DS, C3, DT>, lds_bytes(DS, C3), lds_set);
-        if (e != hipSuccess) return e;
-    }
     // persistent: 8 waves per CU re-use their staged weights over many 16-pixel fragments
     constexpr int WAVES = C3 ? C3_WAVES : DS ? 8 : 4;
     static_assert(WAVES == chain_waves(DS, C3 != 0), "kernels.h: chain_waves");
     const int blocks = chain_grid(a.m, DS, C3 != 0, a.max_blocks);
-    hipLaunchKernelGGL((bottleneck_chain_kernel<DS, C3, DT>), dim3(blocks), dim3(64 * WAVES), lds_bytes(DS, C3), s, a);
-    return hipGetLastError();
+    return launch_large_lds<bottleneck_chain_kernel<DS, C3, DT>>(lds_bytes(DS, C3), dim3(blocks), dim3(64 * WAVES), lds_bytes(DS, C3), s, a);
 }
 
 template <int DT>

@@ -3,12 +3,13 @@
 #include <stdlib.h>
 
 #include "kernels.h"
-#include "dt16.h"
+#include "elem.h"
 
 namespace hrn {
 
 #include "bottleneck_chain.inc"
 
+// (called by launch_bottleneck_chain, bottleneck_chain.hip)
 hipError_t launch_bottleneck_chain_f16(const ChainArgs &a, hipStream_t s) { return launch_bottleneck_chain_t<DT_F16>(a, s); }
 
 }  // namespace hrn

@@ -14,11 +14,9 @@
 // K order: slice-major, tap, channel (the generic kernel: tap-major) -- so a convolution takes this form at EVERY batch
 // size (128-pixel tiles when a launch could not fill the chip) and a crop's result does not depend on its batch.
 #include "kernels.h"
+#include "elem.h"
 
 namespace hrn {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-#define GLOBAL_AS __attribute__((address_space(1)))
 
 namespace {
 
@@ -207,13 +205,7 @@ template <int NRB>
 hipError_t launch_c3f(const Conv3Problem *probs_dev, const int2 *blockmap_dev, int nblocks, int nb, hipStream_t s) {
     constexpr int LDS = 2 * F_NCH * NRB * 1024 + 2 * F_SLAB;
     static_assert(LDS <= 160 * 1024, "LDS budget");
-    static std::atomic<unsigned long long> lds_set{0};   // per device: kernels.h set_dynamic_lds
-    {
-        const hipError_t e = set_dynamic_lds((const void *)conv3x3_f32_kernel<NRB>, LDS, lds_set);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((conv3x3_f32_kernel<NRB>), dim3(nblocks), dim3(512), LDS, s, probs_dev, blockmap_dev, nb);
-    return hipGetLastError();
+    return launch_large_lds<conv3x3_f32_kernel<NRB>>(LDS, dim3(nblocks), dim3(512), LDS, s, probs_dev, blockmap_dev, nb);
 }
 
 }  // namespace

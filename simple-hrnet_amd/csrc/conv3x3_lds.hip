@@ -29,7 +29,7 @@
 // The kernel bodies live in conv3x3_lds.inc, templated on the element format; this file instantiates the bf16 ones
 // (conv3x3_lds_f16.hip: the fp16 ones).
 #include "kernels.h"
-#include "dt16.h"
+#include "elem.h"
 
 namespace hrn {
 
@@ -91,8 +91,12 @@ int conv3x3_lds_bm(int ks, int nrb, int wp) {
     return 0;
 }
 
-hipError_t launch_conv3x3_lds(const Conv3Problem *probs_dev, const void *blockmap_dev, int nblocks, int nb, int ks,
+hipError_t launch_conv3x3_lds_f16(const Conv3Problem *probs_dev, const void *blockmap_dev, int nblocks, int nb, int ks, int nrb,
+                                  hipStream_t s);   // conv3x3_lds_f16.hip
+
+hipError_t launch_conv3x3_lds(int dtype, const Conv3Problem *probs_dev, const void *blockmap_dev, int nblocks, int nb, int ks,
                               int nrb, hipStream_t s) {
+    if (dtype == DT_F16) return launch_conv3x3_lds_f16(probs_dev, blockmap_dev, nblocks, nb, ks, nrb, s);
     if (nblocks > 0 && ks == 16) return launch_conv3x3_f32(probs_dev, blockmap_dev, nblocks, nb, nrb, s);
     return launch_conv3x3_lds_t<DT_BF16>(probs_dev, blockmap_dev, nblocks, nb, ks, nrb, s);
 }

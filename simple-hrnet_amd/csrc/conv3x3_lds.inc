@@ -1,14 +1,7 @@
 // Body of the LDS-staged 3x3 convolution kernels (conv3x3_lds.hip: design notes), templated on the 16-bit element format DT
-// (dt16.h).  conv3x3_lds.hip instantiates it for bf16, conv3x3_lds_f16.hip for fp16: the same tiles, LDS images, pipelines and
-// counted waits -- only the MFMA opcode and the conversions differ.  Included inside namespace hrn, after kernels.h / dt16.h.
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-// The problem descriptors are read from memory, so their pointers are generic; tell the compiler they are
-// global, otherwise every access becomes a FLAT op, which counts on lgkmcnt as well and forces lgkmcnt(0)
-// drains in front of the MFMAs (measured: every wait in the chunk loop was a full drain).
-#define GLOBAL_AS __attribute__((address_space(1)))
+// (elem.h).  conv3x3_lds.hip instantiates it for bf16, conv3x3_lds_f16.hip for fp16: the same tiles, LDS images, pipelines and
+// counted waits -- only the MFMA opcode and the conversions differ.  Included inside namespace hrn, after elem.h.
+// (the problem descriptors are read from memory: their pointers are named global, elem.h's GLOBAL_AS)
 typedef const GLOBAL_AS unsigned short *gcu16;
 typedef GLOBAL_AS unsigned short *gu16;
 
@@ -32,7 +25,7 @@ __device__ __forceinline__ void glds16(const GLOBAL_AS void *gsrc, char *lds_wav
 template <int KS_, int NRB_, int DT_ = DT_BF16>
 struct C3Cfg {
     static constexpr int KS = KS_, NRB = NRB_;
-    static constexpr int DT = DT_;                            // element format: DT_BF16 or DT_F16 (dt16.h)
+    static constexpr int DT = DT_;                            // element format: DT_BF16 or DT_F16 (elem.h)
     static constexpr int PARTS = KS == 48 ? 2 : 1;            // parts per slice
     static constexpr int CPP = KS == 48 ? 7 : 9;              // chunks per part
     static constexpr int NCH = PARTS * CPP;                   // chunks per slice
@@ -352,7 +345,7 @@ __device__ __forceinline__ void conv3_run(const Conv3Problem &p, const int nt, c
                     for (int i = 0; i < MR; ++i)
 #pragma unroll
                         for (int j = 0; j < NRB; ++j)
-                            acc[i][j] = H16<DT>::mma(wf[cur][j], xf[cur][i], acc[i][j]);
+                            acc[i][j] = Tr<DT>::mma(wf[cur][j], xf[cur][i], acc[i][j]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #undef C3_READ_CHUNK
@@ -399,12 +392,12 @@ __device__ __forceinline__ void conv3_run(const Conv3Problem &p, const int nt, c
                 // residual: two bf16 per dword -> fp32 with one shift / one mask each
                 const unsigned r01 = (j >> 1) < N16 ? rpre4[i][(j >> 1) < N16 ? (j >> 1) : 0][2 * (j & 1)] : rpre2[i][0];
                 const unsigned r23 = (j >> 1) < N16 ? rpre4[i][(j >> 1) < N16 ? (j >> 1) : 0][2 * (j & 1) + 1] : rpre2[i][1];
-                float v0 = acc[i][j][0] + H16<DT>::lo(r01);
-                float v1 = acc[i][j][1] + H16<DT>::hi(r01);
-                float v2 = acc[i][j][2] + H16<DT>::lo(r23);
-                float v3 = acc[i][j][3] + H16<DT>::hi(r23);
+                float v0 = acc[i][j][0] + Tr<DT>::lo(r01);
+                float v1 = acc[i][j][1] + Tr<DT>::hi(r01);
+                float v2 = acc[i][j][2] + Tr<DT>::lo(r23);
+                float v3 = acc[i][j][3] + Tr<DT>::hi(r23);
                 if (p.relu) v0 = relu1(v0), v1 = relu1(v1), v2 = relu1(v2), v3 = relu1(v3);
-                const unsigned lo = H16<DT>::pk(v0, v1), hi = H16<DT>::pk(v2, v3);  // RNE, v_cvt_pk_{bf16,f16}_f32
+                const unsigned lo = Tr<DT>::pk(v0, v1), hi = Tr<DT>::pk(v2, v3);  // RNE, v_cvt_pk_{bf16,f16}_f32
                 pk[2 * j] = ok ? lo : 0u;
                 pk[2 * j + 1] = ok ? hi : 0u;
             }
@@ -517,7 +510,7 @@ __device__ __forceinline__ void bbf_conv1(const Conv3Problem &p, const int (&xof
         for (int i = 0; i < NF; ++i)
 #pragma unroll
             for (int j = 0; j < NRB; ++j)
-                acc[i][j] = H16<DT>::mma(wf[cur][j], xf[cur][i], acc[i][j]);
+                acc[i][j] = Tr<DT>::mma(wf[cur][j], xf[cur][i], acc[i][j]);
         __builtin_amdgcn_sched_barrier(0);
     }
 #undef BBF_READ1
@@ -537,8 +530,8 @@ __device__ __forceinline__ void bbf_conv1(const Conv3Problem &p, const int (&xof
         const bool ok = (okbits >> i) & 1u;
 #pragma unroll
         for (int j = 0; j < NRB; ++j) {
-            const unsigned lo = H16<DT>::pk(relu1(acc[i][j][0]), relu1(acc[i][j][1]));
-            const unsigned hi = H16<DT>::pk(relu1(acc[i][j][2]), relu1(acc[i][j][3]));
+            const unsigned lo = Tr<DT>::pk(relu1(acc[i][j][0]), relu1(acc[i][j][1]));
+            const unsigned hi = Tr<DT>::pk(relu1(acc[i][j][2]), relu1(acc[i][j][3]));
             pk[i][2 * j] = ok ? lo : 0u;
             pk[i][2 * j + 1] = ok ? hi : 0u;
         }
@@ -759,7 +752,7 @@ __device__ __forceinline__ void bbf_run(const Conv3Problem &p, const int mt0, co
                 for (int i = 0; i < MR; ++i)
 #pragma unroll
                     for (int j = 0; j < NRB; ++j)
-                        acc[i][j] = H16<DT>::mma(wf[cur][j], xf[cur][i], acc[i][j]);
+                        acc[i][j] = Tr<DT>::mma(wf[cur][j], xf[cur][i], acc[i][j]);
                 __builtin_amdgcn_sched_barrier(0);
             }
 #undef BBF_READ2
@@ -783,12 +776,12 @@ __device__ __forceinline__ void bbf_run(const Conv3Problem &p, const int mt0, co
 #pragma unroll
             for (int j = 0; j < NRB; ++j) {
                 const unsigned r01 = rpre[i][j][0], r23 = rpre[i][j][1];
-                float v0 = acc[i][j][0] + H16<DT>::lo(r01);
-                float v1 = acc[i][j][1] + H16<DT>::hi(r01);
-                float v2 = acc[i][j][2] + H16<DT>::lo(r23);
-                float v3 = acc[i][j][3] + H16<DT>::hi(r23);
+                float v0 = acc[i][j][0] + Tr<DT>::lo(r01);
+                float v1 = acc[i][j][1] + Tr<DT>::hi(r01);
+                float v2 = acc[i][j][2] + Tr<DT>::lo(r23);
+                float v3 = acc[i][j][3] + Tr<DT>::hi(r23);
                 if (p.relu) v0 = relu1(v0), v1 = relu1(v1), v2 = relu1(v2), v3 = relu1(v3);
-                const unsigned lo = H16<DT>::pk(v0, v1), hi = H16<DT>::pk(v2, v3);
+                const unsigned lo = Tr<DT>::pk(v0, v1), hi = Tr<DT>::pk(v2, v3);
                 pk[2 * j] = ok ? lo : 0u;
                 pk[2 * j + 1] = ok ? hi : 0u;
             }
@@ -880,16 +873,10 @@ static hipError_t launch_c3(const Conv3Problem *probs_dev, const int2 *blockmap_
     // the <48, 3> launches may carry fused BasicBlocks (bbf_run), which lay LDS out differently and use all of it
     constexpr int LDS = (KS == 48 && NRB == 3) ? (BBF_LDS > N96_LDS ? BBF_LDS : N96_LDS) : CFG::LDS;
     static_assert(LDS >= CFG::LDS, "LDS budget");
-    static std::atomic<unsigned long long> lds_set{0};   // per device: kernels.h set_dynamic_lds
-    {
-        const hipError_t e = set_dynamic_lds((const void *)conv3x3_lds_kernel<KS, NRB, DT>, LDS, lds_set);
-        if (e != hipSuccess) return e;
-    }
 #ifdef HRN_Q_TIMING
     hipLaunchKernelGGL(q_seq_bump, dim3(1), dim3(1), 0, s);
 #endif
-    hipLaunchKernelGGL((conv3x3_lds_kernel<KS, NRB, DT>), dim3(nblocks), dim3(512), LDS, s, probs_dev, blockmap_dev, nb);
-    return hipGetLastError();
+    return launch_large_lds<conv3x3_lds_kernel<KS, NRB, DT>>(LDS, dim3(nblocks), dim3(512), LDS, s, probs_dev, blockmap_dev, nb);
 }
 
 // the <KS, NRB> launch families of one element format (ks = 16, the fp32 kernel, is conv3x3_f32.hip's)

@@ -564,21 +564,21 @@ __device__ __forceinline__ void c3n_run(const Conv3Problem &p_, const int nt, co
 #pragma unroll
                         for (int j = 0; j < NRB; ++j) {
                             const unsigned r01 = rpre[i][j >> 1][2 * (j & 1)], r23 = rpre[i][j >> 1][2 * (j & 1) + 1];
-                            float v0 = acc[i][j][0] + H16<DT>::lo(r01);
-                            float v1 = acc[i][j][1] + H16<DT>::hi(r01);
-                            float v2 = acc[i][j][2] + H16<DT>::lo(r23);
-                            float v3 = acc[i][j][3] + H16<DT>::hi(r23);
+                            float v0 = acc[i][j][0] + Tr<DT>::lo(r01);
+                            float v1 = acc[i][j][1] + Tr<DT>::hi(r01);
+                            float v2 = acc[i][j][2] + Tr<DT>::lo(r23);
+                            float v3 = acc[i][j][3] + Tr<DT>::hi(r23);
                             if (p.relu) {
                                 // ReLU and the pad mask in ONE op per value: med3(x, 0, lim), lim = +inf on real pixels, 0 on pad pixels
                                 asm("v_med3_f32 %0, %1, 0, %2" : "=v"(v0) : "v"(v0), "v"(lim));
                                 asm("v_med3_f32 %0, %1, 0, %2" : "=v"(v1) : "v"(v1), "v"(lim));
                                 asm("v_med3_f32 %0, %1, 0, %2" : "=v"(v2) : "v"(v2), "v"(lim));
                                 asm("v_med3_f32 %0, %1, 0, %2" : "=v"(v3) : "v"(v3), "v"(lim));
-                                const unsigned lo = H16<DT>::pk(v0, v1), hi = H16<DT>::pk(v2, v3);   // RNE, v_cvt_pk_{bf16,f16}_f32
+                                const unsigned lo = Tr<DT>::pk(v0, v1), hi = Tr<DT>::pk(v2, v3);   // RNE, v_cvt_pk_{bf16,f16}_f32
                                 pk[2 * j] = lo;
                                 pk[2 * j + 1] = hi;
                             } else {
-                                const unsigned lo = H16<DT>::pk(v0, v1), hi = H16<DT>::pk(v2, v3);
+                                const unsigned lo = Tr<DT>::pk(v0, v1), hi = Tr<DT>::pk(v2, v3);
                                 pk[2 * j] = ok ? lo : 0u;
                                 pk[2 * j + 1] = ok ? hi : 0u;
                             }

@@ -26,15 +26,18 @@
 // how the small-call fallback (too few tiles to fill the chip -> generic kernel) keeps a crop's result independent of the
 // batch it arrives in, and how tests check this kernel element by element.
 #include "kernels.h"
-#include "dt16.h"
+#include "elem.h"
 
 namespace hrn {
 
 // (the kernel body: conv_s2.inc, shared with the fp16 instantiation in conv_s2_f16.hip)
 #include "conv_s2.inc"
 
-hipError_t launch_conv_s2(const S2Problem *probs_dev, const void *map_dev, int nblocks, hipStream_t s) {
-    return launch_conv_s2_t<DT_BF16>(probs_dev, map_dev, nblocks, s);
+hipError_t launch_conv_s2_f16(const S2Problem *probs_dev, const void *map_dev, int nblocks, hipStream_t s);   // conv_s2_f16.hip
+
+hipError_t launch_conv_s2(int dtype, const S2Problem *probs_dev, const void *map_dev, int nblocks, hipStream_t s) {
+    if (dtype == DT_F16) return launch_conv_s2_f16(probs_dev, map_dev, nblocks, s);
+    return dtype == DT_BF16 ? launch_conv_s2_t<DT_BF16>(probs_dev, map_dev, nblocks, s) : hipErrorInvalidValue;
 }
 
 }  // namespace hrn

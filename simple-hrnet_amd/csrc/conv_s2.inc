@@ -1,13 +1,6 @@
-// Body of the stride-2 slab kernel (conv_s2.hip: design notes), templated on the 16-bit element format DT (dt16.h).  conv_s2.hip
+// Body of the stride-2 slab kernel (conv_s2.hip: design notes), templated on the 16-bit element format DT (elem.h).  conv_s2.hip
 // instantiates it for bf16, conv_s2_f16.hip for fp16: the same slab, register image and counted waits.  Included inside namespace
-// hrn, after kernels.h / dt16.h.
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-#define GLOBAL_AS __attribute__((address_space(1)))
-
+// hrn, after elem.h.
 
 namespace {
 
@@ -254,7 +247,7 @@ __device__ __forceinline__ void s2_run(const GLOBAL_AS S2Problem *pp, const int 
                     for (int j = 0; j < NF; ++j)
 #pragma unroll
                         for (int i = 0; i < MW; ++i)
-                            acc[i][j] = H16<DT>::mma(wf[c][j], xf[cur][i], acc[i][j]);
+                            acc[i][j] = Tr<DT>::mma(wf[c][j], xf[cur][i], acc[i][j]);
                     __builtin_amdgcn_sched_barrier(0);
                     if ((c & 1) && pk < NSP) {   // one LDS-DMA piece every other chunk
                         piece(nx, pk);
@@ -286,7 +279,7 @@ __device__ __forceinline__ void s2_run(const GLOBAL_AS S2Problem *pp, const int 
                                 float a0 = acc[i][j][2 * h] + bs[j][2 * h], a1 = acc[i][j][2 * h + 1] + bs[j][2 * h + 1];
                                 asm("v_med3_f32 %0, %1, %2, %3" : "=v"(a0) : "v"(a0), "v"(lo_i), "v"(hi));
                                 asm("v_med3_f32 %0, %1, %2, %3" : "=v"(a1) : "v"(a1), "v"(lo_i), "v"(hi));
-                                pk2[2 * j + h] = H16<DT>::pk_asm(a0, a1);
+                                pk2[2 * j + h] = Tr<DT>::pk_asm(a0, a1);
                             }
                         GLOBAL_AS unsigned short *o = out + (size_t)(q0 + tp[i]) * cout + ch0 + g * 4 * NF;
                         *(GLOBAL_AS u32x4 *)o = u32x4{pk2[0], pk2[1], pk2[2], pk2[3]};
@@ -325,11 +318,5 @@ template <int DT>
 static hipError_t launch_conv_s2_t(const S2Problem *probs_dev, const void *map_dev, int nblocks, hipStream_t s) {
     if (nblocks <= 0) return hipSuccess;
     const int lds = 2 * kS2SlabBytes + 8 * 48 * 4;
-    static std::atomic<unsigned long long> lds_set{0};   // per device: kernels.h set_dynamic_lds
-    {
-        const hipError_t e = set_dynamic_lds((const void *)conv_s2_slab_kernel<DT>, lds, lds_set);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(conv_s2_slab_kernel<DT>, dim3(nblocks), dim3(512), lds, s, probs_dev, (const int2 *)map_dev);
-    return hipGetLastError();
+    return launch_large_lds<conv_s2_slab_kernel<DT>>(lds, dim3(nblocks), dim3(512), lds, s, probs_dev, (const int2 *)map_dev);
 }

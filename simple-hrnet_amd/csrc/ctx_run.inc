@@ -36,19 +36,6 @@
         return true;
     }
 
-    // the three hand-scheduled kernel families have one launcher per element format (fp16: the same kernels instantiated with
-    // fp16 elements, *_f16.hip): picked by dtype here, as the other launchers of kernels.h do themselves
-    static hipError_t launch_conv3x3_lds(int dtype, const Conv3Problem *probs, const void *map, int nblocks, int nb, int ks, int nrb,
-                                         hipStream_t s) {
-        return (dtype == HRN_F16 ? hrn::launch_conv3x3_lds_f16 : hrn::launch_conv3x3_lds)(probs, map, nblocks, nb, ks, nrb, s);
-    }
-    static hipError_t launch_conv_s2(int dtype, const S2Problem *probs, const void *map, int nblocks, hipStream_t s) {
-        return (dtype == HRN_F16 ? hrn::launch_conv_s2_f16 : hrn::launch_conv_s2)(probs, map, nblocks, s);
-    }
-    static hipError_t launch_bottleneck_chain(int dtype, const ChainArgs &a, hipStream_t s) {
-        return (dtype == HRN_F16 ? hrn::launch_bottleneck_chain_f16 : hrn::launch_bottleneck_chain)(a, s);
-    }
-
     // conv1's arguments (StemArgs and Stem7Args carry the same fields): `out` = its tensor, `w` = the fp32 weights, `wp` = their
     // MFMA image (nullptr: the kernel takes `w`)
     template <class Args>

@@ -12,7 +12,7 @@
     int small_keep_above = sw_int("HRN_SMALL_KEEP", 300);   // (0: every convolution of a small launch takes 128-pixel tiles, round 5's rule)
     bool disable_chain_ds = sw_set("HRN_DISABLE_CHAIN_DS");
     // generic conv kernel, bf16: the block's weights through LDS instead of one copy per wave from L2 (+1.6 % on the pass)
-    // residual-prefetch variant of the K = 64 1x1 convs; persistent blocks of a chain-kernel launch (ADVICE r4: read here, at create,
+    // the K = 64 1x1 convs with a residual fetch it before the K loop (1) or after it (0); persistent blocks of a chain-kernel launch (ADVICE r4: read here, at create,
     // like every other switch -- not in a function-local static at the first launch)
     int pre_mode = sw_int("HRN_PRE_MODE", 1);
     int chain_blocks = sw_int("HRN_CHAIN_BLOCKS", 512);

@@ -345,11 +345,8 @@ hipError_t launch_detector_nms(const DetectorNmsArgs &a, hipStream_t s) {
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    static std::atomic<unsigned long long> lds_set{0};
-    const hipError_t e = set_dynamic_lds((const void *)dnms_image_kernel, (int)detector_nms_lds_bytes(kDnmsMaxCandidates), lds_set);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dnms_image_kernel, dim3((unsigned)a.B), dim3(kImageThreads), detector_nms_lds_bytes(a.max_candidates), s, a);
-    return hipGetLastError();
+    return launch_large_lds<dnms_image_kernel>((int)detector_nms_lds_bytes(kDnmsMaxCandidates), dim3((unsigned)a.B), dim3(kImageThreads),
+                                               (int)detector_nms_lds_bytes(a.max_candidates), s, a);
 }
 
 }  // namespace hrn

@@ -12,7 +12,7 @@ namespace hrn {
 
 // Kernels that use more than 64 KiB of dynamic LDS: hipFuncAttributeMaxDynamicSharedMemorySize is a property of the function ON
 // ONE DEVICE, so it is set once per (kernel, device) -- a process-wide "done" flag left every device but the first handle's without
-// it (one process driving several GPUs: native.MultiDeviceHRNet).  `done` = one bit per device ordinal, a static of the caller.
+// it (one process driving several GPUs: native.MultiDeviceHRNet).  `done` = one bit per device ordinal.
 inline hipError_t set_dynamic_lds(const void *func, int bytes, std::atomic<unsigned long long> &done) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -22,6 +22,16 @@ inline hipError_t set_dynamic_lds(const void *func, int bytes, std::atomic<unsig
     e = hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
     return e;
+}
+// ... and the launch of such a kernel: the attribute set to attr_bytes (>= lds_bytes: a kernel whose launches differ in size asks for
+// its largest layout once), then the launch.  `done` is a static of this template: one mask per kernel instantiation.
+template <auto Kernel, class... Args>
+inline hipError_t launch_large_lds(int attr_bytes, dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const Args &...args) {
+    static std::atomic<unsigned long long> done{0};
+    const hipError_t e = set_dynamic_lds((const void *)Kernel, attr_bytes, done);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s, args...);
+    return hipGetLastError();
 }
 
 // The HRN_* switches exist for same-box A/B runs and the bit-identity tests.  In production NONE of them is
@@ -56,7 +66,7 @@ struct ConvArgs {
     int ksize, stride, relu;
     int kchunks;                            // padded K / (32 bf16 | 16 f32)
     int rev;                                // walk the M tiles backwards (see hrn_ctx::alternate)
-    int pre_mode;                           // K = 64 1x1 convs with a residual: prefetch variant (1: residual before the K loop, 4-fragment tiles)
+    int pre_mode;                           // K = 64 1x1 convs with a residual: 0, or 1: the residual is fetched before the K loop (kernels.hip: PRE)
     int wlds;                               // bf16, full-size tiles: weights staged through LDS once per block (kernels.hip: WL)
     int xlds;                               // ... and, for the stride-2 3x3 convolutions with cin % 32 == 0, the pixel fragments through a per-wave LDS ring (kernels.hip: XL)
     // one phase (a, b) of a ConvTranspose2d(4, stride 2, padding 1) run as a 3x3 conv on the input grid: the result of
@@ -141,8 +151,7 @@ struct S2Problem {
     int shift_wop;
     S2Part part[kS2MaxParts];
 };
-hipError_t launch_conv_s2(const S2Problem *probs_dev, const void *map_dev, int nblocks, hipStream_t s);
-hipError_t launch_conv_s2_f16(const S2Problem *probs_dev, const void *map_dev, int nblocks, hipStream_t s);   // conv_s2_f16.hip
+hipError_t launch_conv_s2(int dtype, const S2Problem *probs_dev, const void *map_dev, int nblocks, hipStream_t s);
 
 // The stem as one kernel (stem_fused.hip, round 4, bf16): conv1 computed into the stride-2 slab's LDS layout, conv2 from there;
 // one output row of conv2 per tile.  `probs_dev[.]` = conv2 as a slab-kernel problem with rows = 1 (its `in` is not read),
@@ -181,8 +190,7 @@ inline int chain_grid(int m, bool ds, bool c3, int max_blocks) {
     const int cap = (ds || c3) ? (blocks_env / 2 > 1 ? blocks_env / 2 : 1) : blocks_env;   // (HRN_CHAIN_BLOCKS < 2 must not give a zero grid)
     return blocks > cap ? cap : blocks;
 }
-hipError_t launch_bottleneck_chain(const ChainArgs &a, hipStream_t s);
-hipError_t launch_bottleneck_chain_f16(const ChainArgs &a, hipStream_t s);   // bottleneck_chain_f16.hip
+hipError_t launch_bottleneck_chain(int dtype, const ChainArgs &a, hipStream_t s);
 
 struct StemArgs {          // conv1 3->64 3x3 s2 + BN + ReLU, NCHW fp32 in, flat padded out
     const float *images;   // (n,3,H,W)
@@ -662,10 +670,8 @@ hipError_t launch_conv(int dtype, const ConvArgs &a, int nr, hipStream_t s);
 // grouped launch of the generic kernel: device-resident ConvArgs[], block map entries (prob | cout tile << 8, M tile)
 hipError_t launch_conv_group(int dtype, const ConvArgs *probs_dev, const void *map_dev, int nblocks, int nr, int mr, int wlds,
                              hipStream_t s);
-hipError_t launch_conv3x3_lds(const Conv3Problem *probs_dev, const void *blockmap_dev, int nblocks, int nb, int ks,
+hipError_t launch_conv3x3_lds(int dtype, const Conv3Problem *probs_dev, const void *blockmap_dev, int nblocks, int nb, int ks,
                               int nrb, hipStream_t s);
-hipError_t launch_conv3x3_lds_f16(const Conv3Problem *probs_dev, const void *blockmap_dev, int nblocks, int nb, int ks,
-                                  int nrb, hipStream_t s);   // conv3x3_lds_f16.hip: the same kernels with fp16 elements
 hipError_t launch_stem(int dtype, const StemArgs &a, hipStream_t s);
 hipError_t launch_fuse(int dtype, const FuseArgs &a, hipStream_t s);
 hipError_t launch_head(int dtype, const HeadArgs &a, hipStream_t s);

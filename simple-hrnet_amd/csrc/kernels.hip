@@ -10,73 +10,10 @@
 //   head_kernel         final 1x1 conv + bias, optional heat-map write-out, per-slab arg-max (decoded in decode.hip).
 #include "kernels.h"
 #include "argmax.h"
-#include "dt16.h"
+#include "elem.h"
 #include <stdlib.h>
 
 namespace hrn {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ unsigned short f32_to_bf16(float f) {  // round to nearest even
-    unsigned u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-
-// the 16-bit MFMA path (bf16 or fp16 elements: same layouts, tiles and kernels) versus the fp32 one
-constexpr bool is16(int dt) { return dt != DT_F32; }
-
-template <int DT>
-struct Tr;
-template <>
-struct Tr<DT_BF16> {
-    using elem = unsigned short;
-    using vec = s16x8;   // 8 bf16 = 16 B = one MFMA operand
-    using out4 = s16x4;  // 4 output channels
-    static constexpr int KC = 32, VEC = 8;
-    static __device__ __forceinline__ float ld(elem e) { return bf16_to_f32(e); }
-    static __device__ __forceinline__ elem st(float f) { return f32_to_bf16(f); }
-};
-template <>
-struct Tr<DT_F16> {   // the bf16 layouts and tiles with fp16 elements (dt16.h)
-    using elem = unsigned short;
-    using vec = s16x8;
-    using out4 = s16x4;
-    static constexpr int KC = 32, VEC = 8;
-    static __device__ __forceinline__ float ld(elem e) { return H16<DT_F16>::ld(e); }
-    static __device__ __forceinline__ elem st(float f) { return H16<DT_F16>::st(f); }
-};
-template <>
-struct Tr<DT_F32> {
-    using elem = float;
-    using vec = f32x4;  // 4 fp32 = 16 B = four 16x16x4 MFMA steps
-    using out4 = f32x4;
-    static constexpr int KC = 16, VEC = 4;
-    static __device__ __forceinline__ float ld(elem e) { return e; }
-    static __device__ __forceinline__ elem st(float f) { return f; }
-};
-
-template <int DT>
-__device__ __forceinline__ f32x4 mma(typename Tr<DT>::vec w, typename Tr<DT>::vec x, f32x4 acc);
-template <>
-__device__ __forceinline__ f32x4 mma<DT_BF16>(s16x8 w, s16x8 x, f32x4 acc) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0,
-                                                   0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mma<DT_F16>(s16x8 w, s16x8 x, f32x4 acc) {
-    return H16<DT_F16>::mma(w, x, acc);
-}
-template <>
-__device__ __forceinline__ f32x4 mma<DT_F32>(f32x4 w, f32x4 x, f32x4 acc) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t], x[t], acc, 0, 0, 0);
-    return acc;
-}
 
 // ---------------------------------------------------------------------------------------------------
 // Generic convolution.  GEMM view: D[cout][pixel] = sum_k W[cout][k] * X[k][pixel], k = tap*cin + ci.
@@ -84,7 +21,6 @@ __device__ __forceinline__ f32x4 mma<DT_F32>(f32x4 w, f32x4 x, f32x4 acc) {
 //   lane (li = lane&15, g = lane>>4):  X operand = pixel li, k-group g (VEC consecutive ci of one tap);
 //   W operand = packed row li, k-group g (pre-packed so the load is lane-linear: lane*16 B).
 //   result: lane holds pixel li, channels ch0 + [0, 4*NR), ch0 = ng*16*NR + g*4*NR  (see pack_conv_weights).
-#define GLOBAL_AS __attribute__((address_space(1)))
 
 // PRE: the residual is fetched before the K loop instead of after it.  The 1x1 convs of layer1 have K = 64: the
 // loop is two chunks long and the kernel is a chain of memory round trips (operands, residual, store); this folds
@@ -483,16 +419,9 @@ static hipError_t launch_conv_group_t(const ConvArgs *probs, const int2 *map, in
         hipLaunchKernelGGL((conv_direct_group_kernel<DT, NR, 1>), dim3(nblocks), dim3(256), 0, s, probs, map);
     else if (mr == 2)
         hipLaunchKernelGGL((conv_direct_group_kernel<DT, NR, 2>), dim3(nblocks), dim3(256), 0, s, probs, map);
-    else if (is16(DT) && wlds)
-    {
-        const int lds = direct_lds_bytes<DT, NR>(wlds);
-        static std::atomic<unsigned long long> lds_set{0};   // (more than 64 KiB of dynamic LDS: per device, kernels.h set_dynamic_lds)
-        if (lds > 65536) {
-            const hipError_t e = set_dynamic_lds((const void *)conv_direct_group_kernel<DT, NR, 4, is16(DT)>, direct_lds_bytes<DT, NR>(2), lds_set);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((conv_direct_group_kernel<DT, NR, 4, is16(DT)>), dim3(nblocks), dim3(256), lds, s, probs, map);
-    }
+    else if (is16(DT) && wlds)   // (the attribute: room for the XL layout, whichever this launch takes)
+        return launch_large_lds<conv_direct_group_kernel<DT, NR, 4, is16(DT)>>(direct_lds_bytes<DT, NR>(2), dim3(nblocks), dim3(256),
+                                                                               direct_lds_bytes<DT, NR>(wlds), s, probs, map);
     else
         hipLaunchKernelGGL((conv_direct_group_kernel<DT, NR, 4>), dim3(nblocks), dim3(256), 0, s, probs, map);
     return hipGetLastError();
@@ -502,23 +431,9 @@ static hipError_t launch_conv_group_t(const ConvArgs *probs, const int2 *map, in
 hipError_t launch_conv_group(int dtype, const ConvArgs *probs_dev, const void *map_dev, int nblocks, int nr, int mr, int wlds,
                              hipStream_t s) {
     if (nblocks <= 0) return hipSuccess;
-    const int2 *map = (const int2 *)map_dev;
-    if (dtype == DT_BF16) {
-        if (nr == 6) return launch_conv_group_t<DT_BF16, 6>(probs_dev, map, nblocks, mr, wlds, s);
-        if (nr == 4) return launch_conv_group_t<DT_BF16, 4>(probs_dev, map, nblocks, mr, wlds, s);
-        if (nr == 3) return launch_conv_group_t<DT_BF16, 3>(probs_dev, map, nblocks, mr, wlds, s);
-        if (nr == 2) return launch_conv_group_t<DT_BF16, 2>(probs_dev, map, nblocks, mr, wlds, s);
-    } else if (dtype == DT_F16) {
-        if (nr == 6) return launch_conv_group_t<DT_F16, 6>(probs_dev, map, nblocks, mr, wlds, s);
-        if (nr == 4) return launch_conv_group_t<DT_F16, 4>(probs_dev, map, nblocks, mr, wlds, s);
-        if (nr == 3) return launch_conv_group_t<DT_F16, 3>(probs_dev, map, nblocks, mr, wlds, s);
-        if (nr == 2) return launch_conv_group_t<DT_F16, 2>(probs_dev, map, nblocks, mr, wlds, s);
-    } else {
-        if (nr == 4) return launch_conv_group_t<DT_F32, 4>(probs_dev, map, nblocks, mr, wlds, s);
-        if (nr == 3) return launch_conv_group_t<DT_F32, 3>(probs_dev, map, nblocks, mr, wlds, s);
-        if (nr == 2) return launch_conv_group_t<DT_F32, 2>(probs_dev, map, nblocks, mr, wlds, s);
-    }
-    return hipErrorInvalidValue;
+    return with_elem_nr(dtype, nr, [&](auto dt, auto nrc) {
+        return launch_conv_group_t<dt(), nrc()>(probs_dev, (const int2 *)map_dev, nblocks, mr, wlds, s);
+    });
 }
 
 template <int DT, int NR, int MR, bool PRE>
@@ -531,12 +446,8 @@ static hipError_t launch_conv_tt(const ConvArgs &a, hipStream_t s) {
 
 template <int DT, int NR>
 static hipError_t launch_conv_t(const ConvArgs &a, hipStream_t s) {
-    if constexpr (is16(DT) && NR % 2 == 0) {
-        const int pre_mode = a.pre_mode;
-        if (a.res && a.ksize == 1 && pre_mode == 1) return launch_conv_tt<DT, NR, 4, true>(a, s);
-        if (a.res && a.ksize == 1 && pre_mode == 2) return launch_conv_tt<DT, NR, 2, true>(a, s);
-        if (a.res && a.ksize == 1 && pre_mode == 3) return launch_conv_tt<DT, NR, 2, false>(a, s);
-    }
+    if constexpr (is16(DT) && NR % 2 == 0)
+        if (a.res && a.ksize == 1 && a.pre_mode == 1) return launch_conv_tt<DT, NR, 4, true>(a, s);
     // small launches (few crops): shorter M tiles, so that the chip fills and a block's serial K loop shrinks with it
     const int ngroups = a.cout / (16 * NR);
     const long blocks4 = (long)((a.m + 255) / 256) * ngroups;
@@ -546,36 +457,15 @@ static hipError_t launch_conv_t(const ConvArgs &a, hipStream_t s) {
         if (a.wlds && a.kchunks >= 2 * WL_G) {
             const int mtiles = (a.m + 255) / 256;
             dim3 grid(((mtiles + 7) / 8) * 8 * (a.cout / (16 * NR)));
-            const int lds = direct_lds_bytes<DT, NR>(a.xlds ? 2 : 1);
-            static std::atomic<unsigned long long> lds_set{0};
-            if (lds > 65536) {
-                const hipError_t e = set_dynamic_lds((const void *)conv_direct_kernel<DT, NR, 4, false, true>, direct_lds_bytes<DT, NR>(2), lds_set);
-                if (e != hipSuccess) return e;
-            }
-            hipLaunchKernelGGL((conv_direct_kernel<DT, NR, 4, false, true>), grid, dim3(256), lds, s, a);
-            return hipGetLastError();
+            return launch_large_lds<conv_direct_kernel<DT, NR, 4, false, true>>(direct_lds_bytes<DT, NR>(2), grid, dim3(256),
+                                                                                direct_lds_bytes<DT, NR>(a.xlds ? 2 : 1), s, a);
         }
     return launch_conv_tt<DT, NR, 4, false>(a, s);
 }
 
 hipError_t launch_conv(int dtype, const ConvArgs &a, int nr, hipStream_t s) {
     if (a.m <= 0) return hipSuccess;
-    if (dtype == DT_BF16) {
-        if (nr == 6) return launch_conv_t<DT_BF16, 6>(a, s);
-        if (nr == 4) return launch_conv_t<DT_BF16, 4>(a, s);
-        if (nr == 3) return launch_conv_t<DT_BF16, 3>(a, s);
-        if (nr == 2) return launch_conv_t<DT_BF16, 2>(a, s);
-    } else if (dtype == DT_F16) {
-        if (nr == 6) return launch_conv_t<DT_F16, 6>(a, s);
-        if (nr == 4) return launch_conv_t<DT_F16, 4>(a, s);
-        if (nr == 3) return launch_conv_t<DT_F16, 3>(a, s);
-        if (nr == 2) return launch_conv_t<DT_F16, 2>(a, s);
-    } else {
-        if (nr == 4) return launch_conv_t<DT_F32, 4>(a, s);
-        if (nr == 3) return launch_conv_t<DT_F32, 3>(a, s);
-        if (nr == 2) return launch_conv_t<DT_F32, 2>(a, s);
-    }
-    return hipErrorInvalidValue;
+    return with_elem_nr(dtype, nr, [&](auto dt, auto nrc) { return launch_conv_t<dt(), nrc()>(a, s); });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -755,17 +645,15 @@ hipError_t launch_stem7(int dtype, const Stem7Args &a, hipStream_t s) {
     const int m = a.n * a.out_hpwp;
     if (m <= 0) return hipSuccess;
     dim3 grid((m + 255) / 256);
-    if (dtype == DT_BF16 && a.wp)
-        hipLaunchKernelGGL(stem7_mfma_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
-    else if (dtype == DT_F16 && a.wp)
-        hipLaunchKernelGGL(stem7_mfma_kernel<DT_F16>, grid, dim3(256), 0, s, a);
-    else if (dtype == DT_BF16)
-        hipLaunchKernelGGL(stem7_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(stem7_kernel<DT_F16>, grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(stem7_kernel<DT_F32>, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    if (is16(dtype) && a.wp)
+        return with_elem16(dtype, [&](auto dt) {
+            hipLaunchKernelGGL(stem7_mfma_kernel<dt()>, grid, dim3(256), 0, s, a);
+            return hipGetLastError();
+        });
+    return with_elem(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(stem7_kernel<dt()>, grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 // MaxPool2d(kernel 3, stride 2, padding 1) on the flat padded layout.  Its input is post-ReLU (>= 0) and the layout's
@@ -804,16 +692,13 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const PoolArgs p) {
 }
 
 hipError_t launch_maxpool(int dtype, const PoolArgs &a, hipStream_t s) {
-    const long total = (long)a.n * a.out_hpwp * (a.c / (dtype != DT_F32 ? 8 : 4));
+    const long total = (long)a.n * a.out_hpwp * (a.c / (is16(dtype) ? 8 : 4));
     if (total <= 0) return hipSuccess;
     dim3 grid((unsigned)((total + 255) / 256));
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(maxpool_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(maxpool_kernel<DT_F16>, grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(maxpool_kernel<DT_F32>, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return with_elem(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(maxpool_kernel<dt()>, grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 // 16-bit modes: the same 3->64 stride-2 convolution on MFMA.  K = 27 (ci, kh, kw) padded to one 32-wide chunk; a
@@ -888,17 +773,15 @@ hipError_t launch_stem(int dtype, const StemArgs &a, hipStream_t s) {
     const int m = a.n * a.out_hpwp;
     if (m <= 0) return hipSuccess;
     dim3 grid((m + 255) / 256);
-    if (dtype == DT_BF16 && a.wp)
-        hipLaunchKernelGGL(stem_mfma_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
-    else if (dtype == DT_F16 && a.wp)
-        hipLaunchKernelGGL(stem_mfma_kernel<DT_F16>, grid, dim3(256), 0, s, a);
-    else if (dtype == DT_BF16)
-        hipLaunchKernelGGL(stem_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(stem_kernel<DT_F16>, grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(stem_kernel<DT_F32>, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    if (is16(dtype) && a.wp)
+        return with_elem16(dtype, [&](auto dt) {
+            hipLaunchKernelGGL(stem_mfma_kernel<dt()>, grid, dim3(256), 0, s, a);
+            return hipGetLastError();
+        });
+    return with_elem(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(stem_kernel<dt()>, grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -962,33 +845,27 @@ __global__ __launch_bounds__(256) void fuse_group_kernel(const FuseGroupArgs g) 
 }
 
 hipError_t launch_fuse(int dtype, const FuseArgs &a, hipStream_t s) {
-    const long total = (long)a.m * (a.c / (dtype != DT_F32 ? 8 : 4));
+    const long total = (long)a.m * (a.c / (is16(dtype) ? 8 : 4));
     if (total <= 0) return hipSuccess;
     dim3 grid((unsigned)((total + 255) / 256));
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(fuse_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(fuse_kernel<DT_F16>, grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(fuse_kernel<DT_F32>, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return with_elem(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(fuse_kernel<dt()>, grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_fuse_group(int dtype, FuseGroupArgs &g, hipStream_t s) {
     long end = 0;
     for (int i = 0; i < g.nf; ++i) {
-        const long total = (long)g.f[i].m * (g.f[i].c / (dtype != DT_F32 ? 8 : 4));
+        const long total = (long)g.f[i].m * (g.f[i].c / (is16(dtype) ? 8 : 4));
         end += (total + 255) / 256;
         g.block_end[i] = (int)end;
     }
     if (end <= 0) return hipSuccess;
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(fuse_group_kernel<DT_BF16>, dim3((unsigned)end), dim3(256), 0, s, g);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(fuse_group_kernel<DT_F16>, dim3((unsigned)end), dim3(256), 0, s, g);
-    else
-        hipLaunchKernelGGL(fuse_group_kernel<DT_F32>, dim3((unsigned)end), dim3(256), 0, s, g);
-    return hipGetLastError();
+    return with_elem(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(fuse_group_kernel<dt()>, dim3((unsigned)end), dim3(256), 0, s, g);
+        return hipGetLastError();
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1215,23 +1092,18 @@ hipError_t launch_head(int dtype, const HeadArgs &a, hipStream_t s) {
     if (a.joints <= 0 || a.joints > kMaxJoints) return hipErrorInvalidValue;
     const bool groups = a.joints > kJointGroup;
     dim3 grid(a.slabs, a.n);
-    if (dtype != DT_F32 && a.wimg && a.slab_px % 64 == 0) {
-        if (dtype == DT_F16)
-            hipLaunchKernelGGL(groups ? head_mfma_groups_kernel<DT_F16> : head_mfma_kernel<DT_F16>, grid, dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL(groups ? head_mfma_groups_kernel<DT_BF16> : head_mfma_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
-        return hipGetLastError();
-    }
+    if (is16(dtype) && a.wimg && a.slab_px % 64 == 0)
+        return with_elem16(dtype, [&](auto dt) {
+            hipLaunchKernelGGL(groups ? head_mfma_groups_kernel<dt()> : head_mfma_kernel<dt()>, grid, dim3(256), 0, s, a);
+            return hipGetLastError();
+        });
     // the weight stage holds ONE group's rows: at most 32 x c floats (32 KiB at PoseResNet's c = 256), whatever the joint count
     const int staged = groups ? kJointGroup : a.joints;
     const size_t shm = sizeof(float) * ((size_t)staged * a.c + 4 * kJointGroup) + sizeof(int) * 4 * kJointGroup;
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(groups ? head_groups_kernel<DT_BF16> : head_kernel<DT_BF16>, grid, dim3(256), shm, s, a);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(groups ? head_groups_kernel<DT_F16> : head_kernel<DT_F16>, grid, dim3(256), shm, s, a);
-    else
-        hipLaunchKernelGGL(groups ? head_groups_kernel<DT_F32> : head_kernel<DT_F32>, grid, dim3(256), shm, s, a);
-    return hipGetLastError();
+    return with_elem(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(groups ? head_groups_kernel<dt()> : head_kernel<dt()>, grid, dim3(256), shm, s, a);
+        return hipGetLastError();
+    });
 }
 
 // Debug tap (hrn_forward_tap): the stored values of a flat padded NHWC tensor, widened exactly, as NCHW fp32.
@@ -1253,13 +1125,10 @@ hipError_t launch_tap(int dtype, const TapArgs &a, hipStream_t s) {
     const long total = (long)a.ncrops * a.c * a.h * a.w;
     if (total <= 0) return hipSuccess;
     dim3 grid((unsigned)((total + 255) / 256));
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(tap_kernel<DT_BF16>, grid, dim3(256), 0, s, a);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(tap_kernel<DT_F16>, grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(tap_kernel<DT_F32>, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return with_elem(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(tap_kernel<dt()>, grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 // Debug (hrn_debug_pad_violations): count the elements of a flat padded NHWC buffer that sit at a pad or guard position and are not
@@ -1285,13 +1154,10 @@ __global__ __launch_bounds__(256) void pad_check_kernel(const PadCheckArgs p) {
 hipError_t launch_pad_check(int dtype, const PadCheckArgs &a, hipStream_t s) {
     if (a.rows <= 0) return hipSuccess;
     const unsigned blocks = (unsigned)((a.rows + 255) / 256 < 4096 ? (a.rows + 255) / 256 : 4096);
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(pad_check_kernel<DT_BF16>, dim3(blocks), dim3(256), 0, s, a);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(pad_check_kernel<DT_F16>, dim3(blocks), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(pad_check_kernel<DT_F32>, dim3(blocks), dim3(256), 0, s, a);
-    return hipGetLastError();
+    return with_elem(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(pad_check_kernel<dt()>, dim3(blocks), dim3(256), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace hrn

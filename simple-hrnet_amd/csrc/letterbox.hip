@@ -18,7 +18,7 @@
 // No atomics; every byte has one writer.
 #include <hip/hip_runtime.h>
 
-#include "dt16.h"
+#include "elem.h"
 #include "kernels.h"
 #include "letterbox_math.h"
 #include "resize_taps.h"
@@ -98,9 +98,9 @@ __device__ __forceinline__ void lb_store(void *base, size_t idx, float x);
 template <>
 __device__ __forceinline__ void lb_store<0>(void *base, size_t idx, float x) { ((float *)base)[idx] = x; }
 template <>
-__device__ __forceinline__ void lb_store<1>(void *base, size_t idx, float x) { ((unsigned short *)base)[idx] = H16<DT_F16>::st(x); }
+__device__ __forceinline__ void lb_store<1>(void *base, size_t idx, float x) { ((unsigned short *)base)[idx] = Tr<DT_F16>::st(x); }
 template <>
-__device__ __forceinline__ void lb_store<2>(void *base, size_t idx, float x) { ((unsigned short *)base)[idx] = H16<DT_BF16>::st(x); }
+__device__ __forceinline__ void lb_store<2>(void *base, size_t idx, float x) { ((unsigned short *)base)[idx] = Tr<DT_BF16>::st(x); }
 
 
 // FORM = HRN_LB_F32 / _F16 / _BF16: (n, 3, out_h, out_w) planar, one pixel per thread

@@ -27,17 +27,9 @@
 // every phase is a dependent chain (gather -> MFMA -> pack -> LDS write; LDS read -> MFMA) that two waves cannot cover.
 // profiles/EXPERIMENTS.md (round 4) has the steps that got it from 643 us to here and what each was worth.
 #include "kernels.h"
-#include "dt16.h"
+#include "elem.h"
 
 namespace hrn {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-#define GLOBAL_AS __attribute__((address_space(1)))
-
 
 namespace {
 
@@ -211,8 +203,8 @@ __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const S
                 const float x0 = flip ? pre[q][3] : pre[q][0], x1 = flip ? pre[q][2] : pre[q][1];
                 const float x2 = flip ? pre[q][1] : pre[q][2], x3 = flip ? pre[q][0] : pre[q][3];
                 unsigned lo2, hi2;
-                lo2 = H16<DT>::pk_asm(x0, x1);
-                hi2 = H16<DT>::pk_asm(x2, x3);
+                lo2 = Tr<DT>::pk_asm(x0, x1);
+                hi2 = Tr<DT>::pk_asm(x2, x3);
                 *(u32x2 *)(pb + (fd & 0xfffffu)) = u32x2{in ? lo2 : 0u, in ? hi2 : 0u};
             }
         }
@@ -272,7 +264,7 @@ __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const S
                 f32x4 acc[4];
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj)
-                    acc[jj] = H16<DT>::mma(w1r[jj], xf, b1r[jj]);
+                    acc[jj] = Tr<DT>::mma(w1r[jj], xf, b1r[jj]);
                 // ReLU (clamp to [0, inf]) or, where conv2's padding is, exact zeros (clamp to [0, 0]); bf16 (nearest even, as
                 // stem_mfma_kernel); the lane owns channels 16 g .. 16 g + 15 of its pixel = its 32-byte sub-slot in region g
                 const float hi = ok ? INFINITY : 0.f;
@@ -283,7 +275,7 @@ __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const S
                     for (int h = 0; h < 2; ++h) {
                         // (the builtin, not asm: the compiler has to see this first read of the MFMA results to space it)
                         const float a0 = __builtin_amdgcn_fmed3f(acc[jj][2 * h], 0.f, hi), a1 = __builtin_amdgcn_fmed3f(acc[jj][2 * h + 1], 0.f, hi);
-                        pk[2 * jj + h] = H16<DT>::pk_asm(a0, a1);
+                        pk[2 * jj + h] = Tr<DT>::pk_asm(a0, a1);
                     }
                 if (fd & (1u << 19)) {
                     char *d = sl + g * SF_REGION + ((awave + 8 * i) * 16 + li) * ROWB;
@@ -339,7 +331,7 @@ __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const S
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int j = 0; j < NF; ++j)
-                        acc[j] = H16<DT>::mma(wf[c][j], xf[c & 3], acc[j]);
+                        acc[j] = Tr<DT>::mma(wf[c][j], xf[c & 3], acc[j]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #undef SF_READ
@@ -359,7 +351,7 @@ __device__ __forceinline__ void stemf_run(const GLOBAL_AS S2Problem *pp, const S
                             float a0 = acc[j][2 * h] + bs[j][2 * h], a1 = acc[j][2 * h + 1] + bs[j][2 * h + 1];
                             asm("v_med3_f32 %0, %1, %2, %3" : "=v"(a0) : "v"(a0), "v"(lo_i), "v"(hi));
                             asm("v_med3_f32 %0, %1, %2, %3" : "=v"(a1) : "v"(a1), "v"(lo_i), "v"(hi));
-                            pk2[2 * j + h] = H16<DT>::pk_asm(a0, a1);
+                            pk2[2 * j + h] = Tr<DT>::pk_asm(a0, a1);
                         }
                     GLOBAL_AS unsigned short *o = out + (size_t)(q0 + tp) * cout + ch0 + g * 4 * NF;
                     *(GLOBAL_AS u32x4 *)o = u32x4{pk2[0], pk2[1], pk2[2], pk2[3]};
@@ -385,22 +377,11 @@ int stem_fused_fits(int wop, int w_in) {
     return w_in % 4 == 0 && s2_pair_pitch(wop) + 2 * wop <= kStemFuseRegionBytes / 32 && 21 * (w_in + 8) * 2 <= kStemFusePatchBytes;
 }
 
-template <int DT>
-static hipError_t launch_stem_fused_t(const S2Problem *probs_dev, const void *map_dev, int nblocks, const StemArgs &stem, hipStream_t s) {
-    if (nblocks <= 0) return hipSuccess;
-    static std::atomic<unsigned long long> lds_set{0};   // per device: kernels.h set_dynamic_lds
-    {
-        const hipError_t e = set_dynamic_lds((const void *)stem_fused_kernel<DT>, SF_LDS, lds_set);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(stem_fused_kernel<DT>, dim3(nblocks), dim3(512), SF_LDS, s, probs_dev, (const int2 *)map_dev, stem);
-    return hipGetLastError();
-}
-
-// bf16 or fp16 elements (dt16.h): the same kernel, two instantiations
 hipError_t launch_stem_fused(int dtype, const S2Problem *probs_dev, const void *map_dev, int nblocks, const StemArgs &stem, hipStream_t s) {
-    return dtype == DT_F16 ? launch_stem_fused_t<DT_F16>(probs_dev, map_dev, nblocks, stem, s)
-                           : launch_stem_fused_t<DT_BF16>(probs_dev, map_dev, nblocks, stem, s);
+    if (nblocks <= 0) return hipSuccess;
+    return with_elem16(dtype, [&](auto dt) {
+        return launch_large_lds<stem_fused_kernel<dt()>>(SF_LDS, dim3(nblocks), dim3(512), SF_LDS, s, probs_dev, (const int2 *)map_dev, stem);
+    });
 }
 
 }  // namespace hrn

@@ -3,10 +3,12 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I simple-hrnet_amd/csrc -o /tmp/c3n_test tools/c3n_test.hip
 //   /tmp/c3n_test [crops]            (checks every output element of each shape, then times 20 launches)
 #include "../simple-hrnet_amd/csrc/conv3x3_lds.hip"
-// the library routes ks = 16 to the fp32 kernel (conv3x3_f32.hip), which this stand-alone harness does not link
+// the library routes ks = 16 to the fp32 kernel (conv3x3_f32.hip) and fp16 handles to conv3x3_lds_f16.hip, which this stand-alone
+// harness does not link
 namespace hrn {
 int conv3x3_f32_bm(int) { return 0; }
 hipError_t launch_conv3x3_f32(const Conv3Problem *, const void *, int, int, int, hipStream_t) { return hipErrorInvalidValue; }
+hipError_t launch_conv3x3_lds_f16(const Conv3Problem *, const void *, int, int, int, int, hipStream_t) { return hipErrorInvalidValue; }
 }  // namespace hrn
 #include <cstdio>
 #include <cstdlib>
@@ -146,7 +148,7 @@ static int run_shape(const Shape &sh, int nb, bool with_res, int tpb, bool small
     hipMalloc(&dp, sizeof p), hipMalloc(&dmap, map.size() * sizeof(int2));
     hipMemcpy(dp, &p, sizeof p, hipMemcpyHostToDevice);
     hipMemcpy(dmap, map.data(), map.size() * sizeof(int2), hipMemcpyHostToDevice);
-    hipError_t e = launch_conv3x3_lds(dp, dmap, (int)map.size(), nb, 32, 6, 0);
+    hipError_t e = launch_conv3x3_lds(DT_BF16, dp, dmap, (int)map.size(), nb, 32, 6, 0);
     hipError_t e2 = hipDeviceSynchronize();
     if (e != hipSuccess || e2 != hipSuccess) {
         printf("launch failed: %s / %s\n", hipGetErrorString(e), hipGetErrorString(e2));
@@ -183,9 +185,9 @@ static int run_shape(const Shape &sh, int nb, bool with_res, int tpb, bool small
     hipEventCreate(&e0), hipEventCreate(&e1);
     float ms = 0;
     if (reps > 0) {
-        for (int i = 0; i < 3; ++i) launch_conv3x3_lds(dp, dmap, (int)map.size(), nb, 32, 6, 0);
+        for (int i = 0; i < 3; ++i) launch_conv3x3_lds(DT_BF16, dp, dmap, (int)map.size(), nb, 32, 6, 0);
         hipEventRecord(e0);
-        for (int i = 0; i < reps; ++i) launch_conv3x3_lds(dp, dmap, (int)map.size(), nb, 32, 6, 0);
+        for (int i = 0; i < reps; ++i) launch_conv3x3_lds(DT_BF16, dp, dmap, (int)map.size(), nb, 32, 6, 0);
         hipEventRecord(e1);
         hipEventSynchronize(e1);
         hipEventElapsedTime(&ms, e0, e1);
