@@ -787,6 +787,74 @@ int hrn_draw_heatmaps_host(const hrn_canvas *canvases_host /* planes on the host
                            const uint8_t *joint_mask_host, float lo, float hi, const uint8_t *lut_host, int alpha, int alpha_mode,
                            int cutoff);
 const char *hrn_heatmap_last_error(void);
+
+/* ---- anonymise people on the GPU: a mosaic over the face, from the head joints ----
+ * What a deployment on public footage must do before it may store or show a frame is hide the faces.  After hrn_forward / the
+ * tracking link, nose, eyes and ears lie in pts on the device; this entry pixelates, IN PLACE, a square around chosen joints of
+ * every person -- or given boxes -- on BGR / NV12 / I420 canvases that stay on the device.  There is no cv2 here, and equality
+ * with cv2.blur or a resize down and up is NOT claimed: THE CONTRACT IS THIS INTEGER DEFINITION.  tests/mosaic_ref.py restates
+ * it in numpy; the kernels and hrn_mosaic_host equal it byte for byte.  One text, csrc/mosaic_math.h, is compiled into the
+ * kernels and into the host entries.
+ * WHAT THIS IS NOT: a mosaic with small cells is not irreversible anonymisation (a face can be guessed from 2 x 2 means); the
+ * caller chooses `cell`.  It hides what the joints find: a face the network misses is not covered.  ORDER: the mosaic goes
+ * BEFORE hrn_draw_heatmaps_dev / hrn_draw_poses / hrn_draw_labels_dev, which then draw on top of it.
+ *
+ * Inputs.  Canvases, frame_index and their refusals are hrn_draw_poses' (HRN_PIX_BGR, _NV12, _I420; all BGR or all YUV; even sides
+ * for YUV; sides <= 8192; no two entries on one buffer; an entry nobody refers to may be null; the other layouts stay "unknown
+ * format").  People come from exactly one of
+ *   pts (n, J, 3) float32 (y, x, confidence) with a joint list of K indices in [0, J), K in [1, 256] (a repeated index counts once);
+ *   boxes (n, 4) int32 (x1, y1, x2, y2), half-open as everywhere in this library.
+ * Region of a person from joints.  A joint is LIVE by hrn_draw_poses' predicate, literally: confidence > threshold in float32
+ * (equality and NaN are not live), y and x finite, X = trunc(x) and Y = trunc(y) in [-8192, 16383].  Over the live joints of the
+ * list: X0 = min X, X1 = max X, Y0, Y1 likewise, E = max(X1 - X0, Y1 - Y0).  Over ALL live joints of the person (all J): the same
+ * extent, P.  No listed joint live: the person has no region, status 1.  The half side is
+ *     R = max(rmin, (E scale_num + scale_den - 1) / scale_den),    scale_num, scale_den in [1, 64]
+ * (1 / 1: a square of side 2 E + 1 -- for a frontal face twice the ear-to-ear width), with rmin = min_half when min_half is in
+ * [1, 4096], and for min_half == 0 the rule rmin = (P + 15) / 16: the head of a standing person is about an eighth of their
+ * height, which keeps a face in profile, whose joints nearly coincide, from getting a dot.  With cx2 = X0 + X1, cy2 = Y0 + Y1
+ * the rectangle is x_lo = (cx2 >> 1) - R, x_hi = ((cx2 + 1) >> 1) + R + 1 (half-open), likewise in y; >> is an arithmetic shift
+ * (floor).  Every intermediate fits int32: E <= 16383 + 8192 = 24575, E * 64 < 2^21, |cx2| <= 32766.
+ * Region from a box.  The box itself (any int32); x2 <= x1 or y2 <= y1 -- an all-zero box is one -- has no region, status 1.
+ * Clipping.  The region is clipped to the person's canvas: [max(x_lo, 0), min(x_hi, width)) x [max(y_lo, 0), min(y_hi, height)).
+ * Nothing left: status 2; otherwise status 0.  A person without status 0 has the region (0, 0, 0, 0).
+ * Cells.  One cell size s per call from cell in {0, 2, 4, 8, 16, 32}; 0 means, per canvas, the largest power of two not above
+ * clamp(min(height, width) / 64, 8, 32): 16 at 1080p, 8 at 720p, 32 at 2160p.  The cells are the canvas-aligned s x s grid (a
+ * power of two up to 32 keeps every cell inside one 32 x 32 tile of the drawing family).  A cell is MARKED iff it intersects the
+ * clipped region of at least one person of that canvas: covering more than the region, never less, is the point.
+ * Pixels.  A marked cell with c pixels inside the canvas (edge cells are partial: c = min(s, width - x0) min(s, height - y0))
+ * gets every pixel set, per channel byte, to (sum + (c >> 1)) / c over those pixels.  On NV12 / I420: Y over the cell, U and V
+ * each over the cell's (s/2) x (s/2) chroma samples (sides are even: c / 4 of them).  Sums fit int32 (32 * 32 * 255).  Every
+ * byte of a marked cell is written; no byte of an unmarked cell, and no pitch padding, is written.
+ * What follows.  The result is a function of the SET of marked cells alone: it depends neither on the order of the people, nor on
+ * overlaps, nor on scheduling -- no blend, no "later over earlier".  Each mean is taken from the bytes the call found (a cell has
+ * one owner, which reads it whole before it writes it: in place is safe), and a second identical call changes no byte.
+ *
+ * hrn_mosaic_dev: two launches whatever n and nframes, stream-ordered, no host read of device data, no atomics and no scratch of
+ * frame size -- a build launch (one wave per person for joints, one thread per person for boxes: the clipped region and the
+ * status, from pts or boxes where they lie) and a rasteriser of hrn_draw_poses' geometry (one 256-thread block per 32 x 32 tile of
+ * the canvases referred to, a thread per 2x2 block; a tile culls its canvas's people by region 256 at a time into a cell mask, so
+ * no number of people on a tile loses anybody; a tile with an empty mask reads no frame byte).  status_dev: n int32 on the device,
+ * or NULL.  n == 0 succeeds and launches nothing.  Fails with code 7 and nothing launched, each failure naming its cause, on:
+ * n < 0; both or neither of pts_dev / boxes_dev; with pts: J outside [1, HRN_MAX_JOINTS], K outside [1, 256], a null list, a joint
+ * index outside [0, J); scale_num or scale_den outside [1, 64]; min_half outside [0, 4096]; cell not one of the six values; null
+ * canvases; several frames without frame_index; every canvas refusal of hrn_draw_poses; after those, a plan-only handle.
+ * hrn_mosaic_regions (no handle, no GPU; hrn_pose_boxes' sibling): pts or boxes on the host and each person's canvas size
+ * canvas_hw (n, 2) (height, width), sides in [1, 8192], to regions_out (n, 4) clipped rectangles and status_out n.
+ * hrn_mosaic_host (no handle, no GPU): the whole definition on the CPU -- canvases (planes on the HOST), pts or boxes in host
+ * memory, the same arguments and refusals; status_out n int32 or NULL.  Both return 7 with hrn_mosaic_last_error() (per thread)
+ * naming the cause.
+ * Not built: NV21 / P010 / I010 canvases, Gaussian blur, ellipses, a cell size per person. */
+int hrn_mosaic_dev(hrn_handle h, const hrn_canvas *canvases_host, int nframes, const float *pts_dev /* (n,J,3) or NULL */, int n, int J,
+                   const int32_t *joints_host /* K indices */, int K, const int32_t *boxes_dev /* (n,4) or NULL */,
+                   const int32_t *frame_index_host /* n entries; NULL: nframes == 1 */, float threshold, int scale_num, int scale_den,
+                   int min_half /* 0: the rule */, int cell /* 0: the rule */, int32_t *status_dev /* n or NULL */, void *stream);
+int hrn_mosaic_regions(const float *pts /* (n,J,3) or NULL, host */, int n, int J, const int32_t *joints /* K indices */, int K,
+                       const int32_t *boxes /* (n,4) or NULL, host */, const int32_t *canvas_hw /* (n,2) */, float threshold,
+                       int scale_num, int scale_den, int min_half, int32_t *regions_out /* (n,4) */, int32_t *status_out /* n */);
+int hrn_mosaic_host(const hrn_canvas *canvases_host /* planes on the host */, int nframes, const float *pts_host, int n, int J,
+                    const int32_t *joints_host, int K, const int32_t *boxes_host, const int32_t *frame_index_host, float threshold,
+                    int scale_num, int scale_den, int min_half, int cell, int32_t *status_out /* n or NULL */);
+const char *hrn_mosaic_last_error(void);
 int hrn_yuv_from_bgr(int matrix, int range, const uint8_t *bgr /* (n,3) */, int n, uint8_t *yuv_out /* (n,3) */);
 
 /* ---- the detector link on the GPU: the letterboxed detector tensor, and the detector's boxes back in frame coordinates ----

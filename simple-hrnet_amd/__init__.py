@@ -11,7 +11,7 @@ at the repository root.
 """
 from . import _lib  # noqa: F401
 from . import synth  # noqa: F401
-from .native import NativeHRNet, YuvFrame, bgr_to_yuv_colors, heat_colormap, palette, rotation_code_from_degrees  # noqa: F401
+from .native import COCO_HEAD_JOINTS, NativeHRNet, YuvFrame, bgr_to_yuv_colors, heat_colormap, palette, rotation_code_from_degrees  # noqa: F401
 from .nms import gpu_nms  # noqa: F401
 from . import postproc  # noqa: F401
 from .postproc import filter_poses, find_person_id_associations, oks_nms, rotate_people, soft_oks_nms  # noqa: F401
@@ -19,4 +19,4 @@ from .simple_hrnet import SimpleHRNet  # noqa: F401
 from .tracker import PersonTracker  # noqa: F401
 from .synth import synth_boxes, synth_crops, synth_state_dict  # noqa: F401
 
-__all__ = ["NativeHRNet", "YuvFrame", "palette", "heat_colormap", "bgr_to_yuv_colors", "SimpleHRNet", "PersonTracker", "gpu_nms", "oks_nms", "soft_oks_nms", "find_person_id_associations", "filter_poses", "rotate_people", "rotation_code_from_degrees", "postproc", "synth", "synth_state_dict", "synth_crops", "synth_boxes"]
+__all__ = ["NativeHRNet", "YuvFrame", "palette", "heat_colormap", "COCO_HEAD_JOINTS", "bgr_to_yuv_colors", "SimpleHRNet", "PersonTracker", "gpu_nms", "oks_nms", "soft_oks_nms", "find_person_id_associations", "filter_poses", "rotate_people", "rotation_code_from_degrees", "postproc", "synth", "synth_state_dict", "synth_crops", "synth_boxes"]

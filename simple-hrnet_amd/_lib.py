@@ -23,6 +23,7 @@ SOURCES = ["kernels.hip", "conv3x3_lds.hip", "conv_s2.hip", "stem_fused.hip", "c
            "score.hip",    # heat-maps against the ground truth: Gaussian targets, loss and PCK of an evaluation batch
            "draw.hip",     # pose overlays and person labels: joints, bones, boxes, ids and scores drawn into BGR / NV12 / I420 frames on the device (draw_labels_math.h)
            "heat.hip",     # heat-map overlays: the maximum over the chosen joints, coloured and blended into BGR / NV12 / I420 frames on the device (heat_math.h, draw_tile.h)
+           "mosaic.hip",   # the face mosaic: a square around chosen joints, or a box, pixelated in place in BGR / NV12 / I420 frames on the device (mosaic_math.h, draw_tile.h)
            "track.hip",    # the tracking link: boxes from joints, crop records from detections on the device (track_geometry.h)
            "pose_nms.hip",  # pose NMS: rescoring and hard / soft OKS NMS per image or stream in one launch (pose_nms_math.h)
            "detector_nms.hip",  # detector NMS: the raw output of a YOLO head to kept rows, scoring pass + one block per image (detector_nms_math.h)
@@ -262,6 +263,13 @@ SYMBOLS = {
     "hrn_draw_heatmaps_host": (ctypes.c_int, [ctypes.POINTER(CanvasC), ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               _P, _P, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "hrn_heatmap_last_error": (ctypes.c_char_p, []),
+    "hrn_mosaic_dev": (ctypes.c_int, [_P, ctypes.POINTER(CanvasC), ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P, _P,
+                                      ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "hrn_mosaic_regions": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P, _P, ctypes.c_float, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, _P, _P]),
+    "hrn_mosaic_host": (ctypes.c_int, [ctypes.POINTER(CanvasC), ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P, _P,
+                                       ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    "hrn_mosaic_last_error": (ctypes.c_char_p, []),
     "hrn_associate_people": (ctypes.c_int, [ctypes.c_int, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, _P, _P, _P]),
     "hrn_associate_people_last_error": (ctypes.c_char_p, []),

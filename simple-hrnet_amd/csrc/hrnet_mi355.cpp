@@ -24,6 +24,7 @@
 #include "detector_nms_math.h"
 #include "draw_labels_math.h"
 #include "heat_math.h"
+#include "mosaic_math.h"
 #include "keypoint_eval_math.h"
 #include "kernels.h"
 #include "rotate_math.h"
@@ -1187,6 +1188,170 @@ int hrn_draw_heatmaps_dev(hrn_handle h, const hrn_canvas *canvases_host, int nfr
     a.frames = (const DrawFrame *)table, a.order = (const int *)(table + ct.off_order), a.lut = (const unsigned *)(table + off_lut);
     a.q = (unsigned char *)records;
     if (!h->hip_ok(launch_draw_heatmaps(a, s), "heat-map launch")) return 8;
+    return frame.leave() ? 0 : 6;
+}
+
+// ---- the face mosaic: a square around chosen joints, or a box, pixelated in place (mosaic_math.h, mosaic.hip) -------------------
+static thread_local std::string g_mosaic_error;
+
+namespace {
+extern "C++" {
+// what is wrong with the arguments the mosaic entries share, or "" (canvases: hrn_draw_poses' checks, when there are any)
+std::string mosaic_fault(const hrn_canvas *canvases, int nframes, bool with_canvases, const void *pts, int n, int J, const int32_t *joints,
+                         int K, const void *boxes, const int32_t *frame_index, int scale_num, int scale_den, int min_half, int cell) {
+    if (n < 0) return "n is negative";
+    if (pts && boxes) return "people come from pts or from boxes, not from both";
+    if (n > 0 && !pts && !boxes) return "null pts and boxes: people come from one of them";
+    if (!boxes && (n > 0 || pts || joints)) {
+        if (J < 1 || J > HRN_MAX_JOINTS) return "J must be in [1, " + std::to_string(HRN_MAX_JOINTS) + "]";
+        if (K < 1 || K > kMosaicMaxList) return "K must be in [1, " + std::to_string(kMosaicMaxList) + "]";
+        if (!joints) return "null joint list";
+        for (int k = 0; k < K; ++k)
+            if (joints[k] < 0 || joints[k] >= J)
+                return "joint index " + std::to_string(joints[k]) + " at position " + std::to_string(k) + " of the list is outside [0, " +
+                       std::to_string(J) + ")";
+    }
+    if (scale_num < 1 || scale_num > kMosaicMaxScale || scale_den < 1 || scale_den > kMosaicMaxScale)
+        return "scale_num and scale_den must be in [1, " + std::to_string(kMosaicMaxScale) + "]";
+    if (min_half < 0 || min_half > kMosaicMaxHalf) return "min_half must be in [0, " + std::to_string(kMosaicMaxHalf) + "]";
+    if (!with_canvases) return "";
+    if (!mosaic_cell_valid(cell)) return "cell must be 0, 2, 4, 8, 16 or 32";
+    if (!canvases || nframes < 1) return "null canvases";
+    if (!frame_index && nframes != 1) return "without frame_index there must be one frame";
+    return canvas_table_fault(canvases, nframes, n, frame_index);
+}
+}  // extern "C++"
+// the joints of the list as a bit set (a repeated index marks its bit once more)
+void mosaic_listed_bits(const int32_t *joints, int K, uint32_t *bits /* kMaxJoints / 32 */) {
+    for (int w = 0; w < kMaxJoints / 32; ++w) bits[w] = 0;
+    for (int k = 0; k < K; ++k) bits[joints[k] >> 5] |= 1u << (joints[k] & 31);
+}
+// person i's region on a canvas of H x W from whichever source the call has: the host's form of mosaic_build_kernel
+int mosaic_person_region(const float *pts, int J, const uint32_t *bits, const int32_t *boxes, int i, float threshold, int scale_num,
+                         int scale_den, int min_half, int H, int W, int *out) {
+    if (boxes) return mosaic_region_of_box(boxes + 4 * (size_t)i, H, W, out);
+    return mosaic_region_of_person(pts + (size_t)i * J * 3, J, bits, threshold, scale_num, scale_den, min_half, H, W, out);
+}
+}  // namespace
+
+const char *hrn_mosaic_last_error(void) { return g_mosaic_error.c_str(); }
+
+int hrn_mosaic_regions(const float *pts, int n, int J, const int32_t *joints, int K, const int32_t *boxes, const int32_t *canvas_hw,
+                       float threshold, int scale_num, int scale_den, int min_half, int32_t *regions_out, int32_t *status_out) {
+    g_mosaic_error = mosaic_fault(nullptr, 0, false, pts, n, J, joints, K, boxes, nullptr, scale_num, scale_den, min_half, 0);
+    if (g_mosaic_error.empty() && n > 0 && (!canvas_hw || !regions_out || !status_out)) g_mosaic_error = "null canvas sizes / outputs";
+    for (int i = 0; g_mosaic_error.empty() && i < n; ++i)
+        if (canvas_hw[2 * i] < 1 || canvas_hw[2 * i] > 8192 || canvas_hw[2 * i + 1] < 1 || canvas_hw[2 * i + 1] > 8192)
+            g_mosaic_error = "the canvas size of person " + std::to_string(i) + " is outside [1, 8192]";
+    if (!g_mosaic_error.empty()) return 7;
+    uint32_t bits[kMaxJoints / 32] = {};
+    if (!boxes && n > 0) mosaic_listed_bits(joints, K, bits);
+    for (int i = 0; i < n; ++i)
+        status_out[i] = mosaic_person_region(pts, J, bits, boxes, i, threshold, scale_num, scale_den, min_half, canvas_hw[2 * i],
+                                             canvas_hw[2 * i + 1], regions_out + 4 * (size_t)i);
+    return 0;
+}
+
+// the whole definition on the CPU: everybody's region, then per canvas the marks of its cell grid and the means of the marked cells
+int hrn_mosaic_host(const hrn_canvas *canvases_host, int nframes, const float *pts_host, int n, int J, const int32_t *joints_host, int K,
+                    const int32_t *boxes_host, const int32_t *frame_index_host, float threshold, int scale_num, int scale_den,
+                    int min_half, int cell, int32_t *status_out) {
+    g_mosaic_error = mosaic_fault(canvases_host, nframes, true, pts_host, n, J, joints_host, K, boxes_host, frame_index_host, scale_num,
+                                  scale_den, min_half, cell);
+    if (!g_mosaic_error.empty()) return 7;
+    if (n == 0) return 0;
+    uint32_t bits[kMaxJoints / 32] = {};
+    if (!boxes_host) mosaic_listed_bits(joints_host, K, bits);
+    std::vector<int> region((size_t)4 * n);
+    for (int i = 0; i < n; ++i) {
+        const hrn_canvas &c = canvases_host[frame_index_host ? frame_index_host[i] : 0];
+        const int st = mosaic_person_region(pts_host, J, bits, boxes_host, i, threshold, scale_num, scale_den, min_half, c.height, c.width,
+                                            &region[4 * (size_t)i]);
+        if (status_out) status_out[i] = st;
+    }
+    std::vector<uint8_t> marks;
+    for (int f = 0; f < nframes; ++f) {
+        const hrn_canvas &c = canvases_host[f];
+        int s = 0, gw = 0, gh = 0;
+        for (int i = 0; i < n; ++i) {
+            if ((frame_index_host ? frame_index_host[i] : 0) != f) continue;
+            if (!s) {   // (a canvas somebody refers to has been judged: its sides are positive)
+                s = mosaic_cell_size(cell, c.height, c.width), gw = (c.width + s - 1) / s, gh = (c.height + s - 1) / s;
+                marks.assign((size_t)gw * gh, 0);
+            }
+            const int *r = &region[4 * (size_t)i];
+            if (r[2] <= r[0]) continue;
+            for (int cy = r[1] / s; cy <= (r[3] - 1) / s; ++cy)
+                for (int cx = r[0] / s; cx <= (r[2] - 1) / s; ++cx) marks[(size_t)cy * gw + cx] = 1;
+        }
+        if (!s) continue;
+        const bool bgr = c.format == HRN_PIX_BGR;
+        for (int cy = 0; cy < gh; ++cy)
+            for (int cx = 0; cx < gw; ++cx) {
+                if (!marks[(size_t)cy * gw + cx]) continue;
+                const int x0 = cx * s, y0 = cy * s, w = std::min(s, c.width - x0), h = std::min(s, c.height - y0);
+                const int count = mosaic_cell_count(x0, y0, s, c.height, c.width);
+                // one channel of the cell: its first byte, the bytes between rows and between samples, its rows and columns
+                const auto flatten = [](uint8_t *first, int pitch, int step, int rows, int cols, int cnt) {
+                    int sum = 0;
+                    for (int y = 0; y < rows; ++y)
+                        for (int x = 0; x < cols; ++x) sum += first[(size_t)y * pitch + (size_t)x * step];
+                    const uint8_t m = (uint8_t)mosaic_mean(sum, cnt);
+                    for (int y = 0; y < rows; ++y)
+                        for (int x = 0; x < cols; ++x) first[(size_t)y * pitch + (size_t)x * step] = m;
+                };
+                if (bgr) {
+                    for (int ch = 0; ch < 3; ++ch) flatten(c.y + (size_t)y0 * c.pitch_y + 3 * (size_t)x0 + ch, c.pitch_y, 3, h, w, count);
+                    continue;
+                }
+                flatten(c.y + (size_t)y0 * c.pitch_y + x0, c.pitch_y, 1, h, w, count);
+                if (c.format == HRN_PIX_NV12) {
+                    flatten(c.u + (size_t)(y0 / 2) * c.pitch_c + x0, c.pitch_c, 2, h / 2, w / 2, count / 4);
+                    flatten(c.u + (size_t)(y0 / 2) * c.pitch_c + x0 + 1, c.pitch_c, 2, h / 2, w / 2, count / 4);
+                } else {
+                    flatten(c.u + (size_t)(y0 / 2) * c.pitch_c + x0 / 2, c.pitch_c, 1, h / 2, w / 2, count / 4);
+                    flatten(c.v + (size_t)(y0 / 2) * c.pitch_c + x0 / 2, c.pitch_c, 1, h / 2, w / 2, count / 4);
+                }
+            }
+    }
+    return 0;
+}
+
+// the arguments are judged first (they need no device), then the handle; one table upload and two launches follow
+int hrn_mosaic_dev(hrn_handle h, const hrn_canvas *canvases_host, int nframes, const float *pts_dev, int n, int J,
+                   const int32_t *joints_host, int K, const int32_t *boxes_dev, const int32_t *frame_index_host, float threshold,
+                   int scale_num, int scale_den, int min_half, int cell, int32_t *status_dev, void *stream) {
+    if (!h) return 1;
+    const std::string fault = mosaic_fault(canvases_host, nframes, true, pts_dev, n, J, joints_host, K, boxes_dev, frame_index_host,
+                                           scale_num, scale_den, min_half, cell);
+    if (!fault.empty()) {
+        h->err = "hrn_mosaic_dev: " + fault;
+        return 7;
+    }
+    if (h->refuse_plan_only()) return 7;
+    if (n == 0) return 0;
+    if (!h->hip_ok(hipSetDevice(h->device), "hipSetDevice")) return 6;
+    hipStream_t s = (hipStream_t)stream;
+
+    const CanvasTable ct(nframes, n, frame_index_host);
+    const size_t off_listed = ct.end, table_bytes = off_listed + (kMaxJoints / 32) * 4;
+    const PinnedImage img = h->image(table_bytes);
+    if (!img) return 6;
+    const int tiles = ct.fill(img.ptr, canvases_host, n, frame_index_host,
+                              [&](const hrn_canvas &c) { return mosaic_cell_size(cell, c.height, c.width); });
+    if (boxes_dev) memset(img.as<unsigned>(off_listed), 0, (kMaxJoints / 32) * 4);
+    else mosaic_listed_bits(joints_host, K, img.as<unsigned>(off_listed));
+    const size_t rec_bytes = (size_t)n * sizeof(int4);
+    CallFrame frame(h, s, {{&h->draw_table, table_bytes, hrn_ctx::twice(table_bytes, 4096), "hipMalloc(draw table)"},
+                           {&h->draw_records, rec_bytes, hrn_ctx::twice(rec_bytes, 4096), "hipMalloc(mosaic regions)"}});
+    char *table = frame.upload(img, table_bytes, "hipMemcpyAsync(draw table)"), *records = frame.dev(h->draw_records);
+    if (!table) return 6;
+    MosaicArgs a{};
+    a.pts = pts_dev, a.boxes = boxes_dev, a.n = n, a.J = J, a.nframes = ct.used, a.total_tiles = tiles, a.threshold = threshold;
+    a.scale_num = scale_num, a.scale_den = scale_den, a.min_half = min_half;
+    a.frames = (const DrawFrame *)table, a.order = (const int *)(table + ct.off_order), a.person_frame = (const int *)(table + ct.off_pframe);
+    a.listed = (const unsigned *)(table + off_listed), a.status = status_dev, a.region = (int4 *)records;
+    if (!h->hip_ok(launch_mosaic(a, s), "mosaic launch")) return 8;
     return frame.leave() ? 0 : 6;
 }
 

@@ -418,6 +418,24 @@ struct HeatArgs {
 };
 hipError_t launch_draw_heatmaps(const HeatArgs &a, hipStream_t s);   // heat_reduce_kernel, then heat_raster_kernel
 
+// The face mosaic (mosaic.hip; include/hrnet_mi355.h: hrn_mosaic_dev; the arithmetic: mosaic_math.h).  The table is
+// hrn_draw_poses' -- canvases, people by canvas -- with DrawFrame::radius holding the canvas's cell size, and the listed joints
+// as a bit set.
+struct MosaicArgs {
+    const float *pts;              // (n, J, 3) (y, x, confidence), device, or nullptr: the people come from boxes
+    const int *boxes;              // (n, 4) int32 (x1, y1, x2, y2), device, or nullptr
+    int n, J, nframes, total_tiles;
+    float threshold;
+    int scale_num, scale_den, min_half;
+    const DrawFrame *frames;       // nframes entries
+    const int *order;              // n person indices grouped by canvas
+    const int *person_frame;       // n: index into frames
+    const unsigned *listed;        // kMaxJoints / 32 words: bit j = joint j is in the list
+    int *status;                   // n, device, or nullptr
+    int4 *region;                  // n: written by the build launch, read by the rasteriser; (0, 0, 0, 0): no region
+};
+hipError_t launch_mosaic(const MosaicArgs &a, hipStream_t s);   // mosaic_build_kernel, then mosaic_raster_kernel
+
 // The tracking link (track.hip; include/hrnet_mi355.h: hrn_boxes_from_poses, hrn_preprocess_frames_dev): boxes from the joints
 // where the decode left them, and the crop records of the pre-path from detections on the device -- one launch each.
 struct PoseBoxArgs {

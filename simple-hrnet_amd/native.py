@@ -95,6 +95,35 @@ def heat_arguments(J: int, joints, colormap, alpha, alpha_mode, vmin, vmax, cuto
     return mask, lut, byte(alpha, "alpha", 0), HEAT_ALPHA_MODES[alpha_mode], float(vmin), float(vmax), byte(cutoff, "cutoff", 1)
 
 
+COCO_HEAD_JOINTS = (0, 1, 2, 3, 4)   # nose, eyes and ears in the reference's joints_dict()["coco"] (misc/visualization.py): ``mosaic(joints=...)``
+
+
+def mosaic_arguments(J: Optional[int], joints, scale, min_half, cell):
+    """the scalar arguments of ``mosaic`` (here and in ``postproc``) as the C ABI takes them: (joint list (K,) int32 or None for
+    boxes, scale_num, scale_den, min_half, cell); ValueError on what the library would not be asked.  ``J`` None: the people come
+    from boxes and ``joints`` must not be given"""
+    idx = None
+    if J is None:
+        if joints is not None:
+            raise ValueError("joints choose among the joints of pts: with boxes there are none")
+    elif joints is None:
+        idx = np.arange(J, dtype=np.int32)
+    else:
+        if isinstance(joints, str) or any(isinstance(j, str) for j in joints):
+            raise ValueError("joints must be joint indices: this package knows no joint names (take them from the reference's joints_dict())")
+        idx = np.ascontiguousarray(np.asarray(joints, dtype=np.int64).reshape(-1))
+        if len(idx) < 1 or len(idx) > 256 or idx.min() < 0 or idx.max() >= J:
+            raise ValueError("joints must be a list of 1 to 256 indices in [0, %d)" % J)
+        idx = idx.astype(np.int32)
+    try:
+        num, den = (int(v) for v in scale)
+    except (TypeError, ValueError):
+        raise ValueError("scale must be a pair of integers (numerator, denominator), each in [1, 64], got %r" % (scale,)) from None
+    if (num, den) != tuple(scale):
+        raise ValueError("scale must be a pair of integers (numerator, denominator), each in [1, 64], got %r" % (scale,))
+    return idx, num, den, 0 if min_half is None else int(min_half), 0 if cell is None else int(cell)
+
+
 def _colors(spec, samples) -> np.ndarray:
     """a palette name, or ready (C, 3) uint8 BGR colours"""
     if isinstance(spec, str):
@@ -788,6 +817,75 @@ class NativeHRNet:
         self._launch("hrn_draw_heatmaps_dev", table, len(items), maps.data_ptr() if n else None, boxes.data_ptr() if n else None, n, J, hq, wq,
                      None if fi is None else fi.ctypes.data, None if mask is None else mask.ctypes.data, lo, hi, lut.ctypes.data, a, mode, cut)
         return canvases[0] if single else list(canvases)
+
+    def mosaic(self, frames, pts=None, boxes=None, joints=None, frame_index=None, confidence_threshold: float = 0.5, scale=(1, 1),
+               min_half: Optional[int] = None, cell: Optional[int] = None, return_status: bool = False):
+        """Hide people on the frame, on the GPU (``hrn_mosaic_dev``): a square around the chosen joints of every person -- for faces
+        ``joints=COCO_HEAD_JOINTS`` -- or the given ``boxes`` is pixelated IN PLACE: every cell of the frame's ``cell`` x ``cell``
+        grid that the square touches takes the mean of its own pixels, per channel.  Two launches whatever the number of frames
+        and people; joints, boxes and frames are used where ``predict_frame`` / ``track_frame`` left them.  The arithmetic is the
+        integer definition of include/hrnet_mi355.h; equality with cv2.blur or a resize down and up is not claimed.  The result
+        depends on the set of touched cells alone -- not on the order of the people or on overlaps -- and a second identical call
+        changes nothing.  A mosaic with small cells is NOT irreversible anonymisation: choose ``cell`` for the footage, and mind
+        that a face the network does not find is not hidden.  Call it BEFORE ``draw_heatmaps`` / ``draw_poses`` / ``draw_labels``:
+        later drawing lies on top.
+
+        ``frames``: as in ``draw_poses`` -- a BGR tensor or array (rows may be strided), a ``YuvFrame`` (``"nv12"`` / ``"i420"``), or
+        a list of either kind with None for frames nobody is on; frames on the engine's GPU are changed IN PLACE and returned, host
+        frames are uploaded and the device copy is returned.  Exactly one of ``pts``: (n, J, 3) or (J, 3) (y, x, confidence), and
+        ``boxes``: (n, 4) or (4,) integer (x1, y1, x2, y2); a degenerate box hides nothing.  ``joints``: the indices the square
+        is put around (default all: the whole person); a joint counts when its confidence is above ``confidence_threshold``.
+        ``frame_index``: n frame numbers when there are several frames.  ``scale``: (numerator, denominator), each 1..64: the
+        square's half side is the extent of the chosen joints times ``scale``, rounded up (1 / 1: twice the ear-to-ear width of a
+        frontal face).  ``min_half``: the least half side, 1..4096 (default: a sixteenth of the extent of all the person's joints,
+        rounded up, so that a face in profile is not a dot).  ``cell``: 2, 4, 8, 16 or 32 (default per frame: 8 at 720p, 16 at
+        1080p, 32 at 2160p).  ``return_status``: also return an (n,) int32 tensor on the device -- 0 hidden, 1 no region (no
+        chosen joint counts, or a degenerate box), 2 the region lies outside the frame."""
+        single = not isinstance(frames, (list, tuple))
+        items = [frames] if single else list(frames)
+        if not items:
+            raise ValueError("mosaic needs at least one frame")
+        if (pts is None) == (boxes is None):
+            raise ValueError("mosaic takes pts or boxes: exactly one of them")
+        dev = self.torch_device
+        canvases = Frames.canvases(items, dev)
+        table = canvases.table(kind=_lib.CanvasC)
+        J = None
+        if pts is not None:
+            pts = as_tensor(pts, np.float32)
+            if pts.dim() == 2:
+                pts = pts.unsqueeze(0)
+            if pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[1] < 1:
+                raise ValueError("pts must be (J, 3) or (n, J, 3) (y, x, confidence)")
+            pts = device_tensor(pts, dev, torch.float32)
+            n, J = int(pts.shape[0]), int(pts.shape[1])
+        else:
+            if not isinstance(boxes, torch.Tensor):
+                boxes = np.asarray(boxes)
+            if (boxes.is_floating_point() or boxes.dtype == torch.bool) if isinstance(boxes, torch.Tensor) else boxes.dtype.kind not in "iu":
+                raise ValueError("boxes must be integers (the int32 boxes predict_frame / PersonTracker.update return)")
+            boxes = as_tensor(boxes, np.int32)
+            if boxes.dim() == 1:
+                boxes = boxes.unsqueeze(0)
+            if boxes.dim() != 2 or boxes.shape[1] != 4:
+                raise ValueError("boxes must be (4,) or (n, 4) (x1, y1, x2, y2)")
+            boxes = device_tensor(boxes, dev, torch.int32)
+            n = int(boxes.shape[0])
+        fi = None
+        if frame_index is not None:
+            fi = np.ascontiguousarray(np.asarray(frame_index, dtype=np.int32).reshape(-1))
+            if len(fi) != n:
+                raise ValueError("frame_index must have one entry per person: %d for %d people" % (len(fi), n))
+        elif len(items) != 1:
+            raise ValueError("several frames need frame_index: which frame each person is on")
+        idx, num, den, half, size = mosaic_arguments(J, joints, scale, min_half, cell)
+        status = torch.empty((n,), dtype=torch.int32, device=dev) if return_status else None
+        self._launch("hrn_mosaic_dev", table, len(items), pts.data_ptr() if J is not None and n else None, n, J or 0,
+                     None if idx is None else idx.ctypes.data, 0 if idx is None else len(idx), boxes.data_ptr() if J is None and n else None,
+                     None if fi is None else fi.ctypes.data, float(confidence_threshold), num, den, half, size,
+                     status.data_ptr() if return_status and n else None)
+        out = canvases[0] if single else list(canvases)
+        return (out, status) if return_status else out
 
     def resize_frames(self, frames, interpolation: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The single-person pre-path (``multiperson=False``, ``SimpleHRNet.py:213-222`` / ``:355-366``) on the GPU:

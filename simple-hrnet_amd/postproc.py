@@ -905,6 +905,92 @@ def draw_heatmaps(frames, heatmaps, boxes, frame_index=None, joints=None, colorm
     return items[0] if single else items
 
 
+# -- the face mosaic on the host: everybody's region, and the whole definition on the CPU -------------------------------------------
+def _mosaic_people(pts, boxes):
+    """(pts (n, J, 3) float32 or None, boxes (n, 4) int32 or None, n, J or None) of exactly one source, host arrays"""
+    if (pts is None) == (boxes is None):
+        raise ValueError("mosaic takes pts or boxes: exactly one of them")
+    if pts is not None:
+        p = np.ascontiguousarray(np.asarray(pts, dtype=np.float32))
+        if p.ndim == 2:
+            p = p[None]
+        if p.ndim != 3 or p.shape[2] != 3 or p.shape[1] < 1:
+            raise ValueError("pts must be (J, 3) or (n, J, 3) (y, x, confidence)")
+        return p, None, p.shape[0], p.shape[1]
+    b = np.asarray(boxes)
+    if b.dtype.kind not in "iu":
+        raise ValueError("boxes must be integers (the int32 boxes predict_frame / PersonTracker.update return)")
+    b = np.ascontiguousarray(b.reshape(-1, 4), dtype=np.int32)
+    return None, b, len(b), None
+
+
+def mosaic_regions(canvas_hw, pts=None, boxes=None, joints=None, confidence_threshold: float = 0.5, scale=(1, 1), min_half=None):
+    """The rectangle ``NativeHRNet.mosaic`` hides of every person, on the host (``hrn_mosaic_regions``, no GPU): ``canvas_hw`` =
+    (height, width) for everybody or (n, 2); the other arguments are ``mosaic``'s.  Returns ((n, 4) int32 ``(x1, y1, x2, y2)``
+    clipped to the canvas, (n,) int32 status: 0 a region, 1 none -- no chosen joint counts, or a degenerate box --, 2 it lies
+    outside the canvas); without status 0 the rectangle is four zeros.  include/hrnet_mi355.h has the definition."""
+    import ctypes
+
+    from . import _lib
+    from .native import mosaic_arguments
+
+    p, b, n, J = _mosaic_people(pts, boxes)
+    hw = np.asarray(canvas_hw, dtype=np.int32).reshape(-1, 2)
+    if len(hw) not in (1, n):
+        raise ValueError("canvas_hw must be (height, width) or (n, 2), got %s for %d people" % (hw.shape, n))
+    hw = np.ascontiguousarray(np.broadcast_to(hw, (n, 2)))
+    idx, num, den, half, _ = mosaic_arguments(J, joints, scale, min_half, None)
+    regions, status = np.zeros((n, 4), np.int32), np.zeros((n,), np.int32)
+    lib = _lib.load()
+    rc = lib.hrn_mosaic_regions(p.ctypes.data if p is not None and n else None, n, J or 0, None if idx is None else idx.ctypes.data,
+                                0 if idx is None else len(idx), b.ctypes.data if b is not None and n else None, hw.ctypes.data,
+                                ctypes.c_float(confidence_threshold), num, den, half, regions.ctypes.data, status.ctypes.data)
+    if rc != 0:
+        raise ValueError("hrn_mosaic_regions: " + lib.hrn_mosaic_last_error().decode())
+    return regions, status
+
+
+def mosaic(frames, pts=None, boxes=None, joints=None, frame_index=None, confidence_threshold: float = 0.5, scale=(1, 1), min_half=None,
+           cell=None, return_status: bool = False):
+    """``NativeHRNet.mosaic`` on the host (``hrn_mosaic_host``, no GPU): the same arguments, the same bytes.  ``frames``:
+    (H, W, 3) uint8 BGR arrays (rows may be strided) or host ``YuvFrame``s, one or a list (None: nobody is on it); they are
+    changed IN PLACE and returned.  ``pts`` (n, J, 3) float32 or ``boxes`` (n, 4) integers are host arrays.  ``return_status``: also
+    the (n,) int32 status as a numpy array."""
+    import ctypes
+
+    import torch
+
+    from . import _lib
+    from .frames import Frames
+    from .native import mosaic_arguments
+
+    single = not isinstance(frames, (list, tuple))
+    items = [frames] if single else list(frames)
+    if not items:
+        raise ValueError("mosaic needs at least one frame")
+    p, b, n, J = _mosaic_people(pts, boxes)
+    canvases = Frames.canvases(items, torch.device("cpu"))
+    table = canvases.table(kind=_lib.CanvasC)
+    fi = None
+    if frame_index is not None:
+        fi = np.ascontiguousarray(np.asarray(frame_index, dtype=np.int32).reshape(-1))
+        if len(fi) != n:
+            raise ValueError("frame_index must have one entry per person: %d for %d people" % (len(fi), n))
+    elif len(items) != 1:
+        raise ValueError("several frames need frame_index: which frame each person is on")
+    idx, num, den, half, size = mosaic_arguments(J, joints, scale, min_half, cell)
+    status = np.zeros((n,), np.int32)
+    lib = _lib.load()
+    rc = lib.hrn_mosaic_host(table, len(items), p.ctypes.data if p is not None and n else None, n, J or 0,
+                             None if idx is None else idx.ctypes.data, 0 if idx is None else len(idx),
+                             b.ctypes.data if b is not None and n else None, None if fi is None else fi.ctypes.data,
+                             ctypes.c_float(confidence_threshold), num, den, half, size, status.ctypes.data if n else None)
+    if rc != 0:
+        raise ValueError("hrn_mosaic_host: " + lib.hrn_mosaic_last_error().decode())
+    out = items[0] if single else items
+    return (out, status) if return_status else out
+
+
 # -- the detector link on the host: letterbox geometry and the detector's boxes back in frame coordinates -------------------------
 LETTERBOX_RULES = {"yolov3": 0, "yolov5": 1}     # include/hrnet_mi355.h: HRN_LETTERBOX_MAX_SIDE / _MIN_RATIO
 LETTERBOX_PAD = {"yolov3": 128, "yolov5": 114}   # the wrappers' border: 127.5 is 128 under cv2's round-half-even saturation
